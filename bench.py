@@ -10,6 +10,8 @@ HashJoinExec(.. |x| lineitem) -> AggregateExec -> ProjectionExec -> SortExec (re
 benchmarks/src/bin/tpch.rs:286-351) over synthetic TPC-H-shaped tables resident in HBM (lineitem 600,037,902 rows, orders
 150,009,476, customer 15,000,000; SURVEY.md section 8d generator).  A "step" = one full q3 through the native plan executor.
 value = lineitem rows through the query per second.
+A plain run sets up, warms up, times --steps steps and prints the headline (metric, value, ms_per_step, config); --dump-outputs DIR
+writes the result of the last timed step (dump_q3_outputs).  Everything below the headline is measured only with --full:
 roofline: the hash-join probe of lineitem (the operator with the most kernel time); algorithmic bytes = SURVEY.md section 8d's
 24 B per probe row + 12 B per emitted pair x the counts measured on this input; duration = HIP events around the probe
 operator's kernels on the stream they run on.  "host": how the steps ran (deferred: one host round trip per step).
@@ -52,10 +54,15 @@ def main_q3():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--sf", type=float, default=100.0, help="scale factor of the WHOLE job (default 100 = BASELINE configs[2]); N ranks hold 1/N of every table each")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: per-operator times and the probe roofline "
+                    "(HIP events around every operator in the timed steps), the result against plain torch ops, the CPU baseline and the secondary legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample-sf", type=float, default=10.0)
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary legs (N=1: probe micro-grid, SF100 q1 / q5; N>1: q3 with the build side broadcast, distributed q5, q1)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary legs (N=1: probe micro-grid, SF100 q1 / q5; N>1: q3 with the build side broadcast, distributed q5, q1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the result of the last timed step to DIR/<column>.npy (float64; see dump_q3_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -129,23 +136,24 @@ def main_q3():
     for _ in range(max(args.warmup, 2)):
         res = plan.execute(0)
     tc.ctx.jit_wait()                                    # ... and the variants the warm-up asked for (layouts learned on the way)
+    # the two runs around the probe's pair count (--full) run in a plain run too: the timed steps start from the same state either way
     res = plan.execute(0)
-    m0 = plan.metrics()
+    m0 = plan.metrics() if args.full else None
     res = plan.execute(0)
     tc.sync()
-    m1 = plan.metrics()
-    # pairs emitted by the lineitem probe in one run = the larger of the two joins' output rows
-    matches = max([int(b["output_rows"]) - int(a["output_rows"]) for a, b in zip(m0, m1) if b["node"] == "HashJoinExec"] or [0])
-    plan.profile(True)
+    if args.full:
+        m1 = plan.metrics()
+        # pairs emitted by the lineitem probe in one run = the larger of the two joins' output rows
+        matches = max([int(b["output_rows"]) - int(a["output_rows"]) for a, b in zip(m0, m1) if b["node"] == "HashJoinExec"] or [0])
+        plan.profile(True)
     dt, res = timed_steps(lambda: plan.execute(0), args.steps)
-    ops = plan.profile_all()
-    plan.profile(False)
-    host = plan.exec_stats()
+    if args.full:
+        ops = plan.profile_all()
+        plan.profile(False)
+        host = plan.exec_stats()
     groups = res.num_rows
-
-    # measured counts of the lineitem probe on this input (outside the timed region): rows that pass the fused filter = probes
-    shipdate = li.columns[[c.name for c in li.columns].index("l_shipdate")].data[: 4 * n_li].view(torch.int32)
-    probes = int((shipdate > T.Q3_DATE).sum().item())
+    if args.dump_outputs and rank == 0:
+        dump_q3_outputs(res, args.dump_outputs)
 
     rows_job = n_li * world
     line = {
@@ -160,51 +168,55 @@ def main_q3():
                    "input": "Arrow-physical columns resident in HBM", "first_run_ms": first_ms, "first_run_note": "jit auto: interpreter kernels while the pipelines are specialised in the background (round 2: 1.3-1.7 s waiting for hiprtc)", "aggregate_strategy": "auto",
                    "parallelism": "single partition" if world == 1 else "partition-per-gpu x%d, exchange inside the native plan (%s)" % (world, comm.transport)},
     }
-    # host side of a step: deferred = no operator read anything back (counts travel as device words, operators keep what their first run
-    # learned); settles = host round trips per step (one: the plan's end), host_syncs = read-backs of operators that ran synchronously
-    line["host"] = {"deferred": host["deferred"], "round_trips_per_step": host["settles"] + host["host_syncs"], "settles": host["settles"],
-                    "operator_read_backs": host["host_syncs"], "deferred_runs_redone": host["retries"]}
-    probe_ops = sorted((o for o in ops if o["op"] == "join_probe"), key=lambda o: -o["kernel_ms"])
-    if probe_ops and probe_ops[0]["launches"] > 0:
-        po = probe_ops[0]
-        avg_ms = po["kernel_ms"] / po["launches"]
-        alg = (Q3_PROBE_KEY_BYTES + Q3_SLOT_BYTES) * probes + Q3_PAIR_BYTES * matches
-        achieved = alg / (avg_ms * 1e-3) / 1e9
-        # traffic: HBM bytes per launch from the PMC passes (FETCH_SIZE x 2 + WRITE_SIZE, MI355X_MICROARCH.md) of an EARLIER run of this
-        # command, read from profiles/ -- counters cannot be collected inside this process; traffic_source says which file
-        traffic, traffic_source = None, None
-        for name in ("r03_traffic.json", "r02_traffic.json"):
-            tp = os.path.join(ROOT, "profiles", name)
-            if sf == 100 and world == 1 and os.path.exists(tp):
-                traffic, traffic_source = json.load(open(tp)).get("traffic_bytes_per_launch"), "profiles/" + name + " (PMC passes of an earlier run of this command, not this run)"
-                break
-        import re
-        lab = re.search(r'"label":"(\w+)"', po.get("desc", ""))
-        line["roofline"] = {"bound": "hbm", "kernel": "HashJoinExec probe of lineitem (fused filter l_shipdate > date + key lookup + pair emit; rank 0's launch)",
-                            "kernel_name": "gpuq_jit_join_probe_unique" + ("_" + lab.group(1) if lab else ""),
-                            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                            "avg_launch_ms": avg_ms, "launches": po["launches"], "algorithmic_bytes_per_launch": alg,
-                            "probe_rows": probes, "matches": matches, "rows_scanned": n_li,
-                            "probe_rows_per_s": probes / (avg_ms * 1e-3), "rows_scanned_per_s": n_li / (avg_ms * 1e-3)}
-    # the dominant kernel of every operator the plan compiled (HIP events around it); the smaller launches around them (scans of segment
-    # counts, table initialisation, the aggregate's extract / emit) are inside ms_per_step, not in this list
-    import re as _re
-    def _lab(o):
-        m = _re.search(r'"label":"(\w+)"', o.get("desc", ""))
-        return m.group(1) if m else None
-    line["operators"] = [{"op": o["op"], "label": _lab(o), "kernel_ms_per_step": o["kernel_ms"] / max(1, args.steps),
-                          "op_ms_per_step": o.get("op_ms", 0.0) / max(1, args.steps), "launches": o["launches"]}
-                         for o in sorted(ops, key=lambda o: -o.get("op_ms", o["kernel_ms"])) if o["launches"] > 0 or o.get("op_ms", 0) > 0]
-    # op_ms: HIP events around everything the operator's calls queue (dominant kernel + table initialisation, scans, compaction, the
-    # aggregate's extract / result projection); their sum against ms_per_step is what the step spends outside operators
-    line["operators_ms_per_step"] = sum(o["op_ms_per_step"] for o in line["operators"])
-    line["operators_share_of_step"] = line["operators_ms_per_step"] / line["ms_per_step"]
-    if world == 1:
-        line["check"] = check_q3_result(torch, T, tc, res, li, od, cu)
+    if args.full:
+        # measured counts of the lineitem probe on this input (outside the timed region): rows that pass the fused filter = probes
+        shipdate = li.columns[[c.name for c in li.columns].index("l_shipdate")].data[: 4 * n_li].view(torch.int32)
+        probes = int((shipdate > T.Q3_DATE).sum().item())
+        # host side of a step: deferred = no operator read anything back (counts travel as device words, operators keep what their first run
+        # learned); settles = host round trips per step (one: the plan's end), host_syncs = read-backs of operators that ran synchronously
+        line["host"] = {"deferred": host["deferred"], "round_trips_per_step": host["settles"] + host["host_syncs"], "settles": host["settles"],
+                        "operator_read_backs": host["host_syncs"], "deferred_runs_redone": host["retries"]}
+        probe_ops = sorted((o for o in ops if o["op"] == "join_probe"), key=lambda o: -o["kernel_ms"])
+        if probe_ops and probe_ops[0]["launches"] > 0:
+            po = probe_ops[0]
+            avg_ms = po["kernel_ms"] / po["launches"]
+            alg = (Q3_PROBE_KEY_BYTES + Q3_SLOT_BYTES) * probes + Q3_PAIR_BYTES * matches
+            achieved = alg / (avg_ms * 1e-3) / 1e9
+            # traffic: HBM bytes per launch from the PMC passes (FETCH_SIZE x 2 + WRITE_SIZE, MI355X_MICROARCH.md) of an EARLIER run of this
+            # command, read from profiles/ -- counters cannot be collected inside this process; traffic_source says which file
+            traffic, traffic_source = None, None
+            for name in ("r03_traffic.json", "r02_traffic.json"):
+                tp = os.path.join(ROOT, "profiles", name)
+                if sf == 100 and world == 1 and os.path.exists(tp):
+                    traffic, traffic_source = json.load(open(tp)).get("traffic_bytes_per_launch"), "profiles/" + name + " (PMC passes of an earlier run of this command, not this run)"
+                    break
+            import re
+            lab = re.search(r'"label":"(\w+)"', po.get("desc", ""))
+            line["roofline"] = {"bound": "hbm", "kernel": "HashJoinExec probe of lineitem (fused filter l_shipdate > date + key lookup + pair emit; rank 0's launch)",
+                                "kernel_name": "gpuq_jit_join_probe_unique" + ("_" + lab.group(1) if lab else ""),
+                                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                                "avg_launch_ms": avg_ms, "launches": po["launches"], "algorithmic_bytes_per_launch": alg,
+                                "probe_rows": probes, "matches": matches, "rows_scanned": n_li,
+                                "probe_rows_per_s": probes / (avg_ms * 1e-3), "rows_scanned_per_s": n_li / (avg_ms * 1e-3)}
+        # the dominant kernel of every operator the plan compiled (HIP events around it); the smaller launches around them (scans of segment
+        # counts, table initialisation, the aggregate's extract / emit) are inside ms_per_step, not in this list
+        import re as _re
+        def _lab(o):
+            m = _re.search(r'"label":"(\w+)"', o.get("desc", ""))
+            return m.group(1) if m else None
+        line["operators"] = [{"op": o["op"], "label": _lab(o), "kernel_ms_per_step": o["kernel_ms"] / max(1, args.steps),
+                              "op_ms_per_step": o.get("op_ms", 0.0) / max(1, args.steps), "launches": o["launches"]}
+                             for o in sorted(ops, key=lambda o: -o.get("op_ms", o["kernel_ms"])) if o["launches"] > 0 or o.get("op_ms", 0) > 0]
+        # op_ms: HIP events around everything the operator's calls queue (dominant kernel + table initialisation, scans, compaction, the
+        # aggregate's extract / result projection); their sum against ms_per_step is what the step spends outside operators
+        line["operators_ms_per_step"] = sum(o["op_ms_per_step"] for o in line["operators"])
+        line["operators_share_of_step"] = line["operators_ms_per_step"] / line["ms_per_step"]
+        if world == 1:
+            line["check"] = check_q3_result(torch, T, tc, res, li, od, cu)
     del plan, res
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args.cpu_sample_sf)
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         import bench_extras
         tc.ctx.set_jit("wait")      # the secondary legs time steady state from their second run on: a large input waits for its specialised kernels
         if world == 1:
@@ -274,17 +286,39 @@ def main_q3():
         dist.barrier()
         comm.close()
         dist.destroy_process_group()
-    # The line is out and every rank has left the collectives.  What remains is the teardown of three runtimes in one process (torch,
-    # Arrow C++'s thread pools after the host-side comparison legs, hiprtc's worker): one run of a tool of this repo that ended with a
-    # multi-threaded pyarrow read aborted in that teardown ("terminate called without an active exception") after printing its result.
-    # The library's own exit path is the subject of tests/test_gpu_exit.py; here the background compiles are waited for and the process
-    # leaves without running the other runtimes' static destructors, so that a teardown race cannot turn a finished measurement into rc 134.
-    # (not under a profiler: rocprofv3 writes its traces from the very exit handlers this skips)
-    profiled = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
-    g.lib().gpuq_jit_quiesce()
-    sys.stdout.flush(); sys.stderr.flush()
-    if not profiled:
-        os._exit(0)
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_q3_outputs(res, out_dir):
+    """The q3 result of the last timed step as out_dir/<column>.npy, float64, one file per result column: l_orderkey, revenue (the
+    Decimal128 value, as pyarrow casts it), o_orderdate (days since 1970-01-01), o_shippriority.  Rows stay in the order the plan
+    returned them (ORDER BY revenue DESC, o_orderdate); only inside a run of rows with equal revenue and date, whose order the query
+    leaves open, are they put in l_orderkey order, so that two builds write the same files when they compute the same answer.  At
+    SF100 that is 1.2 M rows x 4 columns x 8 B = 38 MB; a result above DUMP_BYTES_MAX is cut to a fixed sample of rows (seed 0, in
+    result order) and row_index.npy holds their positions."""
+    import numpy as np
+    import pyarrow as pa
+    t = res.to_arrow()
+    cols = {}
+    for name in t.column_names:
+        a = t.column(name).combine_chunks()
+        if pa.types.is_date32(a.type):
+            a = a.cast(pa.int32())
+        cols[name] = a.cast(pa.float64()).to_numpy(zero_copy_only=False)
+    n = t.num_rows
+    tie = np.ones(n, dtype=bool)
+    tie[1:] = (cols["revenue"][1:] != cols["revenue"][:-1]) | (cols["o_orderdate"][1:] != cols["o_orderdate"][:-1])
+    order = np.lexsort((cols["l_orderkey"], np.cumsum(tie)))
+    keep = DUMP_BYTES_MAX // (8 * (len(cols) + 1))
+    rows = np.arange(n) if n <= keep else np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+    out = {k: v[order[rows]] for k, v in cols.items()}
+    if n > keep:
+        out["row_index"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 def check_q3_result(torch, T, tc, res, li, od, cu):

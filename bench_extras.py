@@ -659,7 +659,7 @@ def scan_decode(tc, T, g, sf=1):
     dt = best_of(lambda: pq.read_table(pa.BufferReader(zfile)))
     out["parquet_zstd_pyarrow_host"] = {"ms": dt * 1e3, "rows_per_s": n / dt, "threads": os.cpu_count()}
     co = pacsv.ConvertOptions(column_types=li.schema)
-    dt = best_of(lambda: pacsv.read_csv(io.BytesIO(text), read_options=pacsv.ReadOptions(column_names=li.schema.names),
+    dt = best_of(lambda: pacsv.read_csv(pa.BufferReader(text), read_options=pacsv.ReadOptions(column_names=li.schema.names),
                                         parse_options=pacsv.ParseOptions(delimiter="|", quote_char=False), convert_options=co))
     out["csv_pyarrow_host"] = {"ms": dt * 1e3, "file_GBps": len(text) / dt / 1e9, "rows_per_s": n / dt, "threads": os.cpu_count()}
     dt = best_of(lambda: pq.read_table(pa.BufferReader(pfile)))

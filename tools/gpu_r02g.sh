@@ -3,10 +3,10 @@ set -e
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 O=gpurun_out/r02g; mkdir -p $O
 # N=2 rehearsal on the one GPU (host-staged transport), small scale; then the N=1 headline
-GPUQ_BENCH_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus 2 --steps 3 --warmup 1 --sf 2 > $O/bench_n2.json 2> $O/bench_n2.err || { tail -30 $O/bench_n2.err; exit 1; }
+GPUQ_BENCH_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29655 bench.py --full --gpus 2 --steps 3 --warmup 1 --sf 2 > $O/bench_n2.json 2> $O/bench_n2.err || { tail -30 $O/bench_n2.err; exit 1; }
 python -c "
 import json; d=json.loads([l for l in open('gpurun_out/r02g/bench_n2.json') if l.startswith('{')][-1]); print('N2', d['ms_per_step'], d['value'], d['config']['parallelism'], d['extra'])"
-python bench.py --steps 10 --warmup 2 > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
+python bench.py --full --steps 10 --warmup 2 > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r02g/bench.json'))

@@ -3,7 +3,7 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 O=gpurun_out/r03d; mkdir -p $O
-( time timeout -k 10 900 python bench.py > $O/bench.json 2> $O/bench.err ) 2> $O/bench.time || { tail -30 $O/bench.err; exit 1; }
+( time timeout -k 10 900 python bench.py --full > $O/bench.json 2> $O/bench.err ) 2> $O/bench.time || { tail -30 $O/bench.err; exit 1; }
 tail -3 $O/bench.time
 python3 - <<'PY'
 import json

@@ -7,7 +7,7 @@ timeout -k 10 300 tools/gather_ceiling > $O/gather_ceiling.txt 2>&1 || { tail $O
 cat $O/gather_ceiling.txt
 for v in base nt; do
   if [ $v = nt ]; then export GPUQ_JIT_DEFINES="GPUQ_NT_STREAM=1"; else unset GPUQ_JIT_DEFINES; fi
-  GPUQ_JIT_CACHE_DIR=off timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $O/bench_$v.json 2> $O/bench_$v.err || { tail -20 $O/bench_$v.err; exit 1; }
+  GPUQ_JIT_CACHE_DIR=off timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $O/bench_$v.json 2> $O/bench_$v.err || { tail -20 $O/bench_$v.err; exit 1; }
 done
 python3 - <<'PY'
 import json

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 O=gpurun_out/r03h; mkdir -p $O
 for i in 1 2 3; do for v in base nt; do
   if [ $v = nt ]; then export GPUQ_JIT_DEFINES="GPUQ_NT_STREAM=1"; else unset GPUQ_JIT_DEFINES; fi
-  timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $O/bench_${v}_$i.json 2> $O/bench_${v}_$i.err || { tail -20 $O/bench_${v}_$i.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $O/bench_${v}_$i.json 2> $O/bench_${v}_$i.err || { tail -20 $O/bench_${v}_$i.err; exit 1; }
 done; done
 python3 - <<'PY'
 import json

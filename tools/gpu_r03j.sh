@@ -7,7 +7,7 @@ timeout -k 10 900 python -m pytest tests/test_gpu_join_chain.py tests/test_gpu_d
 tail -3 $O/pytest.log
 timeout -k 10 300 python tools/q5_step.py 100 > $O/q5.txt 2>&1 || { tail -20 $O/q5.txt; exit 1; }
 cat $O/q5.txt
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python3 - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r03j/bench.json").read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ O=gpurun_out/r03m; mkdir -p $O
 timeout -k 10 900 python -m pytest tests/test_gpu_join_tables.py tests/test_gpu_join_chain.py tests/test_gpu_vs_acero.py tests/test_gpu_tpch.py tests/test_gpu_deferred.py tests/test_gpu_fullsize.py -x -q -m gpu > $O/pytest.log 2>&1 || { tail -60 $O/pytest.log; exit 1; }
 tail -3 $O/pytest.log
 for i in 1 2 3; do
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $O/bench_$i.json 2> $O/bench_$i.err || { tail -20 $O/bench_$i.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $O/bench_$i.json 2> $O/bench_$i.err || { tail -20 $O/bench_$i.err; exit 1; }
 done
 python3 - <<'PY'
 import json
