@@ -54,25 +54,30 @@ struct gpuq_op {
   struct PostChunk { CompiledProgram prog; DevBuf code; int first_out = 0; };
   std::deque<PostChunk> posts; Schema post_schema;
   i64 expected_groups = 0;
-  i64 last_groups = -1;             // groups of this operator's previous run
-  int last_path = 0;                // ... and the way it took: 1 LDS dictionary, 2 global hash table, 3 radix-partitioned
   // join
   int join_type = JT_INNER; int null_eq = 0; bool build_side_rows = true;
   bool has_semi = false; KeySpec semi_keys{};      // chain fusion: the keys this build's rows are looked up with in another join's table
   // sort
-  SortSpec sort{}; i64 fetch = -1; bool sort_guess_failed = false, join_guess_failed = false;
+  SortSpec sort{}; i64 fetch = -1;
   // partition
   uint32_t nparts = 0;
-  // deferred execution (include/gpuq.h): what the last completed synchronous run learned, and what a deferred run may leave behind
   struct { void* data = nullptr; u64* valid = nullptr; bool done = false; } sort_dec;      // gpuq_sort_run_keys: where the sorted key column goes
   DType sort_key0;                  // sort: type of the first key expression
   std::string refuse;               // the operator compiles (its output types are known) but cannot run: why
   std::string label;                // descriptor "label": appended to the run-time compiled kernels' names (a plan node id: profiles tell call sites apart)
+  // deferred execution (include/gpuq.h): what the last completed synchronous run learned, and what a deferred run may leave behind.
+  // One value: a deferred run launches from it (`valid`: it may), gpuq_ops_settle takes that permission back when the run did not hold.
   bool deferred = false, defer_client = false;
-  uint32_t expect_flags = 0;        // status bits a deferred run is allowed to raise (a build side known to hold duplicate keys)
-  struct { bool valid = false, dense = false, sparse_bits = false, has_dups = false; i64 kmin = 0; u64 krange = 0; u64 n_slots = 0; } jb;
-  struct { bool valid = false; int path = 0, gmax = 0; u64 est = 0; bool use_lds = false; i64 groups = 0; } ag;      // path: 1 LDS dictionary, 2 global hash table
-  struct { bool valid = false; SortPack K{}; int total = 0; } so;
+  struct Learned {
+    struct { bool valid = false, dense = false, sparse_bits = false, has_dups = false; i64 kmin = 0; u64 krange = 0; } jb;
+    // groups / path: what this operator's previous run produced and the way it took (1 LDS dictionary, 2 global hash table, 3 radix-
+    // partitioned); they outlive `valid` (only paths 1 and 2 can be replayed) and steer the next synchronous run
+    struct { bool valid = false; int path = 0, gmax = 0; u64 est = 0; bool use_lds = false; i64 groups = -1; } ag;
+    struct { bool valid = false; SortPack K{}; int total = 0; } so;
+    bool join_guess_failed = false, sort_guess_failed = false;      // a guessed key range / key layout did not hold once: measure from now on
+    uint32_t expect_flags = 0;      // status bits a deferred run is allowed to raise (a build side known to hold duplicate keys)
+    void forget() { jb.valid = ag.valid = so.valid = false; }
+  } learned;
   // scratch
   DevBuf ws[10];
   // pinned host words for the small device->host reads (flags, counts): a pageable destination makes every such copy a
@@ -850,9 +855,9 @@ int gpuq_op_can_defer(gpuq_op* op) {
   if (!op) return 0;
   switch (op->kind) {
     case K_FILTER: case K_PROJECT: case K_JOIN_PROBE: return 1;      // nothing is read back inside these calls
-    case K_JOIN_BUILD: return op->jb.valid ? 1 : 0;
-    case K_AGG: return op->ag.valid ? 1 : 0;
-    case K_SORT: return op->so.valid ? 1 : 0;
+    case K_JOIN_BUILD: return op->learned.jb.valid ? 1 : 0;
+    case K_AGG: return op->learned.ag.valid ? 1 : 0;
+    case K_SORT: return op->learned.so.valid ? 1 : 0;
     default: return 0;
   }
 }
@@ -885,8 +890,9 @@ int gpuq_ops_settle(gpuq_ctx* ctx, void* stream, gpuq_op* const* ops, int n_ops,
       const uint32_t f = (uint32_t)B.host[i];
       if (f) reset_flags(ops[i], s);
       static const bool trace = getenv("GPUQ_TRACE_DEFER") != nullptr;
-      if (trace && (f & ~ops[i]->expect_flags)) fprintf(stderr, "[gpuq] settle: operator %d of %d (kind %d) raised status 0x%x (expected 0x%x)\n", i, n_ops, (int)ops[i]->kind, f, ops[i]->expect_flags);
-      if (f & ~ops[i]->expect_flags) { retry = true; ops[i]->jb.valid = false; ops[i]->ag.valid = false; ops[i]->so.valid = false; }
+      const uint32_t expected = ops[i]->learned.expect_flags;
+      if (trace && (f & ~expected)) fprintf(stderr, "[gpuq] settle: operator %d of %d (kind %d) raised status 0x%x (expected 0x%x)\n", i, n_ops, (int)ops[i]->kind, f, expected);
+      if (f & ~expected) { retry = true; ops[i]->learned.forget(); }
     }
     if (retry) throw Retry("an assumption of a deferred run did not hold");
   });
@@ -1014,134 +1020,42 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         { JitScope js(op, pc.prog, 2, rows); launch_project(s, PP, rows, O); }
       }
     };
-    // ---- deferred form: the strategy, table size and output capacity of the last completed synchronous run, nothing read back; a
-    // table or an output that turns out too small raises the status word gpuq_ops_settle reads
-    if (ndev_out && op->deferred && op->ag.valid) {
-      if (op->ag.path == 1) {
-        const int gmax = op->ag.gmax;
-        int nb = 0; const size_t wsb = agg_tiny_workspace_bytes(gmax, nk, na, &nb);
-        void* wsp = op->ws[4].ensure(wsb);
-        alloc_raw(64);
-        if ((i64)raw.cap <= cap) {
-          const std::string spec = agg_tiny_spec(op, gmax);
-          { JitScope js(op, op->prog, 3, n, spec); ProfScope ps(op, s); launch_agg_tiny(s, P, n, op->agg, gmax, wsp); }
-          launch_agg_tiny_merge(s, P, n, op->agg, gmax, wsp, raw);
-          run_post((uint32_t)raw.cap, raw.n_groups);
-          HIPCHECK(hipGetLastError());
-          for (int i = 0; i < n_outs; ++i) outs[i].length = raw.cap;
-          if (n_groups_out) *n_groups_out = raw.cap;
-          *ndev_out = (const uint64_t*)raw.n_groups;
-          return;
-        }
-      } else if (op->ag.path == 2) {
-        HashTable T{};
-        T.key_words = op->keys.key_words; T.slot_words = 1 + T.key_words + 2 * na;
-        // the table follows the group count of the last run (+ 1/4), not the size that run happened to use (its first run sizes from a sample)
-        const u64 est = std::min<u64>(std::max<u64>(op->ag.est, 64), (u64)(op->ag.groups + op->ag.groups / 4 + 64));
-        i64 rcap = op->ag.groups + op->ag.groups / 4 + 1024; if (rcap > cap) rcap = cap;
-        if (rcap >= 1 && rcap <= 0x7FFFFFFFll) {
-          T.n_slots = next_pow2(est * agg_slot_pct(true) / 100);
-          T.slots = (u64*)op->ws[5].ensure((size_t)T.n_slots * T.slot_words * 8);
-          launch_ht_init(s, T, &op->agg);
-          if (op->ag.use_lds) {
-            int n_fsum = 0; for (int a = 0; a < na; ++a) n_fsum += op->agg.acc_kind[a] == ACC_FSUM;
-            u64* fstage = nullptr;
-            const size_t fbytes = (size_t)T.n_slots * (size_t)n_fsum * (size_t)agg_lds_grid(n) * 8;
-            if (n_fsum > 0 && fbytes <= ((size_t)256 << 20)) { fstage = (u64*)op->ws[8].ensure(fbytes); HIPCHECK(hipMemsetAsync(fstage, 0, fbytes, s)); }
-            JitScope js(op, op->prog, 13, n); ProfScope ps(op, s); launch_agg_lds(s, P, n, op->keys, op->agg, T, fstage, n_fsum);
-          }
-          else { JitScope js(op, op->prog, 4, n); ProfScope ps(op, s); launch_agg_hash(s, P, n, op->keys, op->agg, T); }
-          alloc_raw(rcap);
-          launch_agg_hash_extract(s, op->keys, op->agg, T, raw, op->flags_dev.as<uint32_t>());
-          run_post((uint32_t)raw.cap, raw.n_groups);
-          HIPCHECK(hipGetLastError());
-          for (int i = 0; i < n_outs; ++i) outs[i].length = raw.cap;
-          if (n_groups_out) *n_groups_out = raw.cap;
-          *ndev_out = (const uint64_t*)raw.n_groups;
-          return;
-        }
+    // ---- the launch sequences, one per strategy: the synchronous form (reset: the status word is cleared first and read afterwards) and
+    // the deferred form (nothing reset, nothing read) queue the same ones
+    // LDS dictionary of `gmax` groups (path 1)
+    auto launch_tiny = [&](const int gmax, const bool reset) {
+      int nb = 0; const size_t wsb = agg_tiny_workspace_bytes(gmax, nk, na, &nb);
+      void* wsp = op->ws[4].ensure(wsb);
+      alloc_raw(64);
+      if (reset) reset_flags(op, s);
+      // the LDS aggregate is specialised on its whole shape (keys, accumulators, group capacity)
+      const std::string spec = agg_tiny_spec(op, gmax);
+      { JitScope js(op, op->prog, 3, n, spec); ProfScope ps(op, s); launch_agg_tiny(s, P, n, op->agg, gmax, wsp); }
+      launch_agg_tiny_merge(s, P, n, op->agg, gmax, wsp, raw);
+    };
+    // global hash table (path 2) of est * slot_pct / 100 slots (rounded up to a power of two), filled by the block-local kernel (use_lds:
+    // rows are folded inside the block first) or the plain one
+    HashTable T{};
+    T.key_words = op->keys.key_words; T.slot_words = 1 + T.key_words + 2 * na;
+    auto launch_table = [&](const u64 est, const u64 slot_pct, const bool use_lds, const bool reset) {
+      T.n_slots = next_pow2(est * slot_pct / 100);
+      T.slots = (u64*)op->ws[5].ensure((size_t)T.n_slots * T.slot_words * 8);
+      launch_ht_init(s, T, &op->agg);
+      if (reset) reset_flags(op, s);
+      if (use_lds) {
+        // float partial sums are parked per (table slot, sum, block) and added up in block order afterwards
+        int n_fsum = 0; for (int a = 0; a < na; ++a) n_fsum += op->agg.acc_kind[a] == ACC_FSUM;
+        u64* fstage = nullptr;
+        const size_t fbytes = (size_t)T.n_slots * (size_t)n_fsum * (size_t)agg_lds_grid(n) * 8;
+        if (n_fsum > 0 && fbytes <= ((size_t)256 << 20)) { fstage = (u64*)op->ws[8].ensure(fbytes); HIPCHECK(hipMemsetAsync(fstage, 0, fbytes, s)); }
+        JitScope js(op, op->prog, 13, n); ProfScope ps(op, s); launch_agg_lds(s, P, n, op->keys, op->agg, T, fstage, n_fsum);
       }
-    }
-    if (in->n_rows_dev) throw std::runtime_error("aggregate: a device-side row count needs a deferred operator with a completed synchronous run (gpuq_op_can_defer)");
-    op->ag.valid = false;
-    int path_done = 0, gmax_done = 0; u64 est_done = 0; bool lds_done = false;
-    bool done = false;
-    std::string strat = op->strategy;
-    if (nk == 0) strat = "tiny";
-    const int exact_gmax = 0;
-    // tiny input: a 2n-slot table beats the LDS kernel's fixed per-block cost (measured: 60 us for the five small hash-path
-    // launches against 83 us for one cold block of the 16-slot LDS kernel on a 4-row input)
-    if (strat == "auto" && n <= 16384) strat = "hash";
-    // groups this operator is expected to produce: the caller's hint, else what its previous run produced (another partition
-    // of the same stage, the same query again)
-    i64 known_groups = op->expected_groups > 0 ? op->expected_groups : op->last_groups;
-    bool many_groups = false;          // the sample says: far more groups than an LDS dictionary, count unknown
-    if (strat == "auto" && nk > 0 && known_groups < 0 && n >= (1ll << 20)) {
-      // a first run over a large input: estimate the cardinality from a strided sample of 2^20 rows (linear counting into 2^24
-      // bits), 20-40 us against the milliseconds a wrong strategy costs
-      const i64 nsample = 1ll << 20, stride = std::max<i64>(1, n / nsample);
-      const u64 nbits = 1ull << 24;
-      uint32_t* bm = (uint32_t*)op->ws[7].ensure(nbits / 8 + 64);
-      unsigned long long* cnt = (unsigned long long*)((char*)bm + nbits / 8);
-      HIPCHECK(hipMemsetAsync(bm, 0, nbits / 8 + 64, s));
-      launch_key_sample(s, P, n, op->keys, stride, nsample, bm, nbits, cnt + 1);
-      launch_popcount_bits(s, (const uint8_t*)bm, (i64)nbits, cnt);
-      unsigned long long* pd = (unsigned long long*)op->pinned();
-      unsigned long long host2[2] = {0, 0};
-      unsigned long long* dst = pd ? pd : host2;
-      HIPCHECK(hipMemcpyAsync(dst, cnt, 16, hipMemcpyDeviceToHost, s));
-      HIPCHECK(hipStreamSynchronize(s));
-      const i64 distinct = (i64)dst[0], passed = (i64)dst[1];
-      if (passed >= 4096) {
-        if (distinct * 4 <= passed) known_groups = std::max<i64>(1, distinct);      // every group seen several times: the sample covers the key domain (users of the number add their own margin)
-        else many_groups = true;
-      }
-    }
-    if (strat == "auto" && nk > 0 && (many_groups || known_groups > (i64)agg_tiny_max_groups(na))) {
-      // more groups than the LDS dictionary holds: do not even try it
-    } else if (strat == "auto" || strat == "tiny") {
-      const int fit_big = agg_tiny_max_groups(na);
-      if (fit_big < 1) { if (strat == "tiny") throw Unsupported("too many accumulators for the LDS aggregate"); }
-      else {
-        int fit_small = 0; for (int g = 1; g <= fit_big; ++g) { int nb; (void)nb; if ((size_t)g * na * 2048 + 4096 <= 64 * 1024) fit_small = g; }
-        std::vector<int> tries;
-        if (nk == 0) tries = {1};
-        else if (exact_gmax > 0) tries = {exact_gmax};
-        else { if (fit_small > 4) { tries.push_back(4); } if (fit_small >= 2) tries.push_back(fit_small); if (fit_big > fit_small) tries.push_back(fit_big); }
-        // a known group count goes straight to the smallest capacity that holds it
-        if (nk > 0 && known_groups > 0) while (tries.size() > 1 && (i64)tries.front() < known_groups) tries.erase(tries.begin());
-        for (int gmax : tries) {
-          int nb = 0; const size_t wsb = agg_tiny_workspace_bytes(gmax, nk, na, &nb);
-          void* wsp = op->ws[4].ensure(wsb);
-          alloc_raw(64);
-          reset_flags(op, s);
-          // the LDS aggregate is specialised on its whole shape (keys, accumulators, group capacity)
-          const std::string spec = agg_tiny_spec(op, gmax);
-          { JitScope js(op, op->prog, 3, n, spec); ProfScope ps(op, s); launch_agg_tiny(s, P, n, op->agg, gmax, wsp); }
-          launch_agg_tiny_merge(s, P, n, op->agg, gmax, wsp, raw);
-          HIPCHECK(hipGetLastError());
-          // The result projection is queued before the host knows whether this try held all groups (it reads the group
-          // count on the device): one host round trip per aggregate instead of two.  An overflowing try is simply redone.
-          const bool ahead = (i64)raw.cap <= cap;
-          if (ahead) run_post((uint32_t)raw.cap, raw.n_groups);
-          uint32_t fw[4] = {0, 0, 0, 0};
-          read_status(op, s, fw, 4);
-          const uint32_t f = fw[0];
-          if (f & ~FLAG_GROUP_OVERFLOW) { reset_flags(op, s); raise_flags(f & ~FLAG_GROUP_OVERFLOW); }
-          if (!(f & FLAG_GROUP_OVERFLOW)) { ng = fw[2]; done = true; posted = ahead; path_done = 1; gmax_done = gmax; break; }
-        }
-        if (!done && strat == "tiny") throw Capacity("more groups than the LDS aggregate holds; use strategy hash/auto");
-      }
-    }
-    // (a count that is merely REMEMBERED says nothing about how the keys lie: the run that produced it went through the global table --
-    // e.g. because its keys are clustered, which the table's wave-level run combining turns into one touch per run -- so the same
-    // path is taken again; the partitioned form is for a caller's hint or a sample that saw every group several times)
-    const bool remembered_hash = op->expected_groups <= 0 && op->last_path == 2;
-    if (!done && (strat == "radix" || (strat == "auto" && !remembered_hash && ((n >= (1ll << 22) && op->expected_groups >= (1ll << 20)) ||
-                                                            (n >= (1ll << 20) && known_groups >= 4096))))) {
-      // High cardinality: partition the rows by key hash into buckets whose groups fit an LDS table, aggregate every bucket
-      // inside one block (kernels_hash.hip).  Falls through to the global table when a bucket overflows (skew, or more
-      // groups than the hint promised).
+      else { JitScope js(op, op->prog, 4, n); ProfScope ps(op, s); launch_agg_hash(s, P, n, op->keys, op->agg, T); }
+    };
+    // radix-partitioned (path 3).  High cardinality: partition the rows by key hash into buckets whose groups fit an LDS table, aggregate
+    // every bucket inside one block (kernels_hash.hip).  false: on to the global table -- a bucket overflowed (skew, or more groups than
+    // the hint promised)
+    auto run_radix = [&](const std::string& strat, const i64 known_groups) -> bool {
       const int slot_words = 1 + op->keys.key_words + 2 * na;
       uint32_t capslots = 64; while ((size_t)capslots * 2 * slot_words * 8 <= 60 * 1024) capslots *= 2;
       if ((size_t)capslots * slot_words * 8 <= 60 * 1024 && n < (1ll << 31)) {
@@ -1174,11 +1088,108 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         uint32_t fw[4] = {0, 0, 0, 0};
         read_status(op, s, fw, 4);
         if (fw[0] & ~(FLAG_TABLE_FULL | FLAG_GROUP_OVERFLOW)) { reset_flags(op, s); raise_flags(fw[0] & ~(FLAG_TABLE_FULL | FLAG_GROUP_OVERFLOW)); }
-        if (!(fw[0] & (FLAG_TABLE_FULL | FLAG_GROUP_OVERFLOW))) { ng = fw[2]; done = true; path_done = 3; }
-        else if (strat == "radix" && op->expected_groups > 0 && est < (u64)n) throw Capacity("radix aggregate: a bucket overflowed; raise expected_groups or use strategy hash/auto");
-        else reset_flags(op, s);
+        if (!(fw[0] & (FLAG_TABLE_FULL | FLAG_GROUP_OVERFLOW))) { ng = fw[2]; return true; }
+        if (strat == "radix" && op->expected_groups > 0 && est < (u64)n) throw Capacity("radix aggregate: a bucket overflowed; raise expected_groups or use strategy hash/auto");
+        reset_flags(op, s);
       } else if (strat == "radix") throw Unsupported("radix aggregate: the group state does not fit an LDS table");
+      return false;
+    };
+    // the end of a run whose group count stays on the device: the projection reads it there, the caller gets the capacity as a bound
+    auto finish_on_device = [&]() {
+      run_post((uint32_t)raw.cap, raw.n_groups);
+      HIPCHECK(hipGetLastError());
+      for (int i = 0; i < n_outs; ++i) outs[i].length = raw.cap;
+      if (n_groups_out) *n_groups_out = raw.cap;
+      *ndev_out = (const uint64_t*)raw.n_groups;
+    };
+    auto& L = op->learned;
+    // ---- deferred form: the strategy, table size and output capacity of the last completed synchronous run, nothing read back; a
+    // table or an output that turns out too small raises the status word gpuq_ops_settle reads.  Caller's columns too small for the
+    // bound: on to the synchronous form
+    if (ndev_out && op->deferred && L.ag.valid) {
+      if (L.ag.path == 1) {
+        if (cap >= 64) { launch_tiny(L.ag.gmax, false); finish_on_device(); return; }
+      } else if (L.ag.path == 2) {
+        // the table follows the group count of the last run (+ 1/4), not the size that run happened to use (its first run sizes from a sample)
+        const u64 est = std::min<u64>(std::max<u64>(L.ag.est, 64), (u64)(L.ag.groups + L.ag.groups / 4 + 64));
+        const i64 rcap = std::min<i64>(L.ag.groups + L.ag.groups / 4 + 1024, cap);
+        if (rcap >= 1 && rcap <= 0x7FFFFFFFll) {
+          launch_table(est, agg_slot_pct(true), L.ag.use_lds, false);
+          alloc_raw(rcap);
+          launch_agg_hash_extract(s, op->keys, op->agg, T, raw, op->flags_dev.as<uint32_t>());
+          finish_on_device();
+          return;
+        }
+      }
     }
+    if (in->n_rows_dev) throw std::runtime_error("aggregate: a device-side row count needs a deferred operator with a completed synchronous run (gpuq_op_can_defer)");
+    L.ag.valid = false;
+    int path_done = 0, gmax_done = 0; u64 est_done = 0; bool lds_done = false;
+    bool done = false;
+    std::string strat = op->strategy;
+    if (nk == 0) strat = "tiny";
+    // tiny input: a 2n-slot table beats the LDS kernel's fixed per-block cost (measured: 60 us for the five small hash-path
+    // launches against 83 us for one cold block of the 16-slot LDS kernel on a 4-row input)
+    if (strat == "auto" && n <= 16384) strat = "hash";
+    // groups this operator is expected to produce: the caller's hint, else what its previous run produced (another partition
+    // of the same stage, the same query again)
+    i64 known_groups = op->expected_groups > 0 ? op->expected_groups : L.ag.groups;
+    bool many_groups = false;          // the sample says: far more groups than an LDS dictionary, count unknown
+    if (strat == "auto" && nk > 0 && known_groups < 0 && n >= (1ll << 20)) {
+      // a first run over a large input: estimate the cardinality from a strided sample of 2^20 rows (linear counting into 2^24
+      // bits), 20-40 us against the milliseconds a wrong strategy costs
+      const i64 nsample = 1ll << 20, stride = std::max<i64>(1, n / nsample);
+      const u64 nbits = 1ull << 24;
+      uint32_t* bm = (uint32_t*)op->ws[7].ensure(nbits / 8 + 64);
+      unsigned long long* cnt = (unsigned long long*)((char*)bm + nbits / 8);
+      HIPCHECK(hipMemsetAsync(bm, 0, nbits / 8 + 64, s));
+      launch_key_sample(s, P, n, op->keys, stride, nsample, bm, nbits, cnt + 1);
+      launch_popcount_bits(s, (const uint8_t*)bm, (i64)nbits, cnt);
+      unsigned long long* pd = (unsigned long long*)op->pinned();
+      unsigned long long host2[2] = {0, 0};
+      unsigned long long* dst = pd ? pd : host2;
+      HIPCHECK(hipMemcpyAsync(dst, cnt, 16, hipMemcpyDeviceToHost, s));
+      HIPCHECK(hipStreamSynchronize(s));
+      const i64 distinct = (i64)dst[0], passed = (i64)dst[1];
+      if (passed >= 4096) {
+        if (distinct * 4 <= passed) known_groups = std::max<i64>(1, distinct);      // every group seen several times: the sample covers the key domain (users of the number add their own margin)
+        else many_groups = true;
+      }
+    }
+    if (strat == "auto" && nk > 0 && (many_groups || known_groups > (i64)agg_tiny_max_groups(na))) {
+      // more groups than the LDS dictionary holds: do not even try it
+    } else if (strat == "auto" || strat == "tiny") {
+      const int fit_big = agg_tiny_max_groups(na);
+      if (fit_big < 1) { if (strat == "tiny") throw Unsupported("too many accumulators for the LDS aggregate"); }
+      else {
+        int fit_small = 0; for (int g = 1; g <= fit_big; ++g) { int nb; (void)nb; if ((size_t)g * na * 2048 + 4096 <= 64 * 1024) fit_small = g; }
+        std::vector<int> tries;
+        if (nk == 0) tries = {1};
+        else { if (fit_small > 4) { tries.push_back(4); } if (fit_small >= 2) tries.push_back(fit_small); if (fit_big > fit_small) tries.push_back(fit_big); }
+        // a known group count goes straight to the smallest capacity that holds it
+        if (nk > 0 && known_groups > 0) while (tries.size() > 1 && (i64)tries.front() < known_groups) tries.erase(tries.begin());
+        for (int gmax : tries) {
+          launch_tiny(gmax, true);
+          HIPCHECK(hipGetLastError());
+          // The result projection is queued before the host knows whether this try held all groups (it reads the group
+          // count on the device): one host round trip per aggregate instead of two.  An overflowing try is simply redone.
+          const bool ahead = (i64)raw.cap <= cap;
+          if (ahead) run_post((uint32_t)raw.cap, raw.n_groups);
+          uint32_t fw[4] = {0, 0, 0, 0};
+          read_status(op, s, fw, 4);
+          const uint32_t f = fw[0];
+          if (f & ~FLAG_GROUP_OVERFLOW) { reset_flags(op, s); raise_flags(f & ~FLAG_GROUP_OVERFLOW); }
+          if (!(f & FLAG_GROUP_OVERFLOW)) { ng = fw[2]; done = true; posted = ahead; path_done = 1; gmax_done = gmax; break; }
+        }
+        if (!done && strat == "tiny") throw Capacity("more groups than the LDS aggregate holds; use strategy hash/auto");
+      }
+    }
+    // (a count that is merely REMEMBERED says nothing about how the keys lie: the run that produced it went through the global table --
+    // e.g. because its keys are clustered, which the table's wave-level run combining turns into one touch per run -- so the same
+    // path is taken again; the partitioned form is for a caller's hint or a sample that saw every group several times)
+    const bool remembered_hash = op->expected_groups <= 0 && L.ag.path == 2;
+    if (!done && (strat == "radix" || (strat == "auto" && !remembered_hash && ((n >= (1ll << 22) && op->expected_groups >= (1ll << 20)) ||
+                                                            (n >= (1ll << 20) && known_groups >= 4096))))) { done = run_radix(strat, known_groups); if (done) path_done = 3; }
     if (!done) {
       // global hash table; grow on FLAG_TABLE_FULL
       // the group count this operator produced last time (another partition of the same stage, the same query again) stands in
@@ -1188,26 +1199,12 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
       const i64 known = known_groups >= 0 ? (op->expected_groups > 0 ? known_groups : std::max<i64>(known_groups + known_groups / 4, 64)) : -1;
       u64 est = known > 0 ? (u64)std::min<i64>(known, std::max<i64>(n, 1)) : (u64)std::min<i64>(std::max<i64>(n, 1), 1ll << 24);
       if (est < 64) est = 64;
-      HashTable T{};
-      T.key_words = op->keys.key_words; T.slot_words = 1 + T.key_words + 2 * na;
       // medium cardinality (known, and a block's LDS table holds a good share of the groups): fold rows inside the block first
       const uint32_t lslots = agg_lds_slots(T);
       const bool use_lds = strat == "lds" || (strat == "auto" && lslots > 0 && n >= (1ll << 17) && known > 0 && known <= (i64)lslots * 4);
       if (strat == "lds" && !lslots) throw Unsupported("lds aggregate: the group state does not fit an LDS table");
       for (;;) {
-        T.n_slots = next_pow2(est * agg_slot_pct(known_groups >= 0 && op->expected_groups <= 0 && est == (u64)known) / 100);
-        T.slots = (u64*)op->ws[5].ensure((size_t)T.n_slots * T.slot_words * 8);
-        launch_ht_init(s, T, &op->agg);
-        reset_flags(op, s);
-        if (use_lds) {
-          // float partial sums are parked per (table slot, sum, block) and added up in block order afterwards
-          int n_fsum = 0; for (int a = 0; a < na; ++a) n_fsum += op->agg.acc_kind[a] == ACC_FSUM;
-          u64* fstage = nullptr;
-          const size_t fbytes = (size_t)T.n_slots * (size_t)n_fsum * (size_t)agg_lds_grid(n) * 8;
-          if (n_fsum > 0 && fbytes <= ((size_t)256 << 20)) { fstage = (u64*)op->ws[8].ensure(fbytes); HIPCHECK(hipMemsetAsync(fstage, 0, fbytes, s)); }
-          JitScope js(op, op->prog, 13, n); ProfScope ps(op, s); launch_agg_lds(s, P, n, op->keys, op->agg, T, fstage, n_fsum);
-        }
-        else { JitScope js(op, op->prog, 4, n); ProfScope ps(op, s); launch_agg_hash(s, P, n, op->keys, op->agg, T); }
+        launch_table(est, agg_slot_pct(known_groups >= 0 && op->expected_groups <= 0 && est == (u64)known), use_lds, true);
         HIPCHECK(hipGetLastError());
         const uint32_t f = (n <= (1ll << 20) && est >= (u64)n) ? 0u : read_flags(op, s);   // a 2n-slot table cannot fill up; other flags surface after extract
         if (f & FLAG_TABLE_FULL) { if (est >= (u64)std::max<i64>(n, 1024)) throw std::runtime_error("hash aggregate: table full at maximum size"); est = std::min<u64>(est * 4, (u64)std::max<i64>(n, 1024)); continue; }
@@ -1233,8 +1230,8 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         // Size the raw result from what this operator produced last time (the partitions of a stage, or the same query again,
         // have similar cardinalities) and extract once; an unknown or outgrown count costs a counting pass first.
         bool done = false;
-        if (op->last_groups > 0) {
-          alloc_raw(op->last_groups + op->last_groups / 4 + 1024);
+        if (L.ag.groups > 0) {
+          alloc_raw(L.ag.groups + L.ag.groups / 4 + 1024);
           launch_agg_hash_extract(s, op->keys, op->agg, T, raw, op->flags_dev.as<uint32_t>());
           HIPCHECK(hipGetLastError());
           uint32_t fw[4] = {0, 0, 0, 0};
@@ -1258,9 +1255,8 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         }
       }
     }
-    op->last_groups = (i64)ng;
-    op->last_path = path_done;
-    if (path_done == 1 || path_done == 2) { op->ag.valid = true; op->ag.path = path_done; op->ag.gmax = gmax_done; op->ag.est = est_done; op->ag.use_lds = lds_done; op->ag.groups = (i64)ng; op->expect_flags = 0; }
+    L.ag = {path_done == 1 || path_done == 2, path_done, gmax_done, est_done, lds_done, (i64)ng};
+    if (L.ag.valid) L.expect_flags = 0;
     if (n_groups_out) *n_groups_out = ng;
     if ((i64)ng > cap) throw Capacity("aggregate produced " + std::to_string(ng) + " groups, output capacity is " + std::to_string(cap));
     for (int i = 0; i < n_outs; ++i) outs[i].length = ng;
@@ -1352,8 +1348,9 @@ static int join_build_impl(gpuq_op* op, void* stream, const gpuq_input* in, int 
     };
     auto attempt = [&](const int mode) -> bool {
     const bool guess = mode == 1, memo = mode == 2;
-    bool dense = false; i64 kmin = 0; u64 krange = 0, kcount = 0;
-    if (memo) { dense = op->jb.dense; kmin = op->jb.kmin; krange = op->jb.krange; }
+    auto& jb = op->learned.jb;
+    bool dense = false, sparse_bits = false; i64 kmin = 0; u64 krange = 0;
+    if (memo) { dense = jb.dense; sparse_bits = jb.sparse_bits; kmin = jb.kmin; krange = jb.krange; }
     else if (narrow_key) {
       u64* kr = (u64*)op->ws[0].ensure(32);
       const u64 init[3] = {0x7FFFFFFFFFFFFFFFull, 0x8000000000000000ull, 0};
@@ -1376,16 +1373,14 @@ static int join_build_impl(gpuq_op* op, void* stream, const gpuq_input* in, int 
           cnt = std::min<u64>(cnt * (u64)wstep, (u64)n);
         }
         const u64 lim = std::max<u64>((u64)cnt * (u64)dense_ratio, 1ull << 16);
-        if (span < (1ull << 31) && span < lim && (span + 1) * 4 <= op->ctx->hbm / 8) { dense = true; kmin = lo; krange = span + 1; kcount = cnt; }
+        // sparse domain (fewer than one value in four is a key): presence bitmap + uninitialised row array (gpuq_kernels.h)
+        if (span < (1ull << 31) && span < lim && (span + 1) * 4 <= op->ctx->hbm / 8) { dense = true; kmin = lo; krange = span + 1; sparse_bits = cnt * 4 < krange; }
       }
     }
-    bool sparse_bits = false;
     t->T.dense = nullptr; t->T.dense_bits = nullptr; t->T.dense_min = 0; t->T.dense_range = 0;      // (a second attempt starts from a clean descriptor)
     if (dense) {
       t->T.n_slots = 0; t->T.slots = nullptr;
       t->T.dense = (uint32_t*)t->dense.ensure((size_t)krange * 4 + 16); t->T.dense_min = kmin; t->T.dense_range = krange;
-      // sparse domain (fewer than one value in four is a key): presence bitmap + uninitialised row array (gpuq_kernels.h)
-      sparse_bits = memo ? op->jb.sparse_bits : kcount * 4 < krange;
       if (sparse_bits) {
         const size_t bb = ((size_t)krange + 63) / 64 * 8 + 8;
         t->T.dense_bits = (uint32_t*)t->dense_bits.ensure(bb);
@@ -1395,59 +1390,47 @@ static int join_build_impl(gpuq_op* op, void* stream, const gpuq_input* in, int 
       t->T.n_slots = next_pow2(std::max<u64>((u64)n * 3, 1024));   // load factor in (0.17, 0.33]: a miss ends after ~1.5 slot visits (2.5 at 0.5)
       t->T.slots = (u64*)t->slots.ensure((size_t)t->T.n_slots * t->T.slot_words * 8);
     }
-    if (memo) {
-      // unique keys remembered: no chain array (a duplicate raises the status word and the run is redone with one)
-      uint32_t* next = op->jb.has_dups ? (uint32_t*)t->next.ensure((size_t)std::max<i64>(build_rows_bound, 1) * 4) : nullptr;
-      const size_t bm = ((size_t)build_rows_bound + 63) / 64 * 8 + 8;
-      uint32_t* present = nullptr;
-      if (op->build_side_rows) { present = (uint32_t*)t->present.ensure(bm); HIPCHECK(hipMemsetAsync(present, 0, bm, s)); }
-      t->has_present = op->build_side_rows;
-      if (!dense) launch_ht_init(s, t->T, nullptr);
-      if (rows_out) HIPCHECK(hipMemsetAsync(rows_out, 0, 8, s));      // (a build that is redone counts its survivors again)
-      { JitScope js(op, op->prog, 5, n, semi_spec(t->T, present)); ProfScope ps(op, s); if (!launch_join_build(s, P, n, op->keys, t->T, next, present, payload_via, op->null_eq, semi_p)) throw Unsupported("join build over a semi table: more than 8 input columns without the specialised kernel"); }
-      HIPCHECK(hipGetLastError());
-      t->has_dups = op->jb.has_dups;
-      return true;
-    }
-    uint32_t* next = (uint32_t*)t->next.ensure((size_t)std::max<i64>(build_rows_bound, 1) * 4);
+    // unique keys remembered: no chain array (a duplicate raises the status word and the run is redone with one)
+    uint32_t* next = (!memo || jb.has_dups) ? (uint32_t*)t->next.ensure((size_t)std::max<i64>(build_rows_bound, 1) * 4) : nullptr;
     const size_t bm = ((size_t)build_rows_bound + 63) / 64 * 8 + 8;
     // `present` (which build rows passed the side's predicate) only serves gpuq_join_build_side_rows: a build whose descriptor says
     // "build_side_rows": false (Inner / Right / RightSemi / RightAnti joins) skips it -- one device-scope atomic per row less when
     // the rows come through an index vector (SF100 q3: 14.6 M of them)
-    uint32_t* present = nullptr;
-    if (op->build_side_rows) { present = (uint32_t*)t->present.ensure(bm); HIPCHECK(hipMemsetAsync(present, 0, bm, s)); }
+    uint32_t* present = op->build_side_rows ? (uint32_t*)t->present.ensure(bm) : nullptr;
     t->has_present = op->build_side_rows;
-    if (!dense) launch_ht_init(s, t->T, nullptr);
-    reset_flags(op, s);
-    if (rows_out) HIPCHECK(hipMemsetAsync(rows_out, 0, 8, s));      // (a build that is redone counts its survivors again)
+    // the table is laid out: clear what a build writes into and launch it (the remembered, the first and the rebuilding launch)
+    auto build = [&]() {
+      if (present) HIPCHECK(hipMemsetAsync(present, 0, bm, s));
+      if (!dense) launch_ht_init(s, t->T, nullptr);
+      if (!memo) reset_flags(op, s);
+      if (rows_out) HIPCHECK(hipMemsetAsync(rows_out, 0, 8, s));      // (a build that is redone counts its survivors again)
       { JitScope js(op, op->prog, 5, n, semi_spec(t->T, present)); ProfScope ps(op, s); if (!launch_join_build(s, P, n, op->keys, t->T, next, present, payload_via, op->null_eq, semi_p)) throw Unsupported("join build over a semi table: more than 8 input columns without the specialised kernel"); }
-    HIPCHECK(hipGetLastError());
+      HIPCHECK(hipGetLastError());
+    };
+    build();
+    if (memo) { t->has_dups = jb.has_dups; return true; }
     uint32_t f = read_flags(op, s);
     if (guess && (f & FLAG_TABLE_FULL)) { reset_flags(op, s); return false; }      // a key outside the guessed range
     if (sparse_bits && (f & FLAG_DUP_BUILD_KEY)) {
       // duplicate keys: chains need defined heads -- rebuild over the initialised array
       t->T.dense_bits = nullptr;
       HIPCHECK(hipMemsetAsync(t->T.dense, 0xFF, (size_t)krange * 4, s));
-      if (present) HIPCHECK(hipMemsetAsync(present, 0, bm, s));
-      reset_flags(op, s);
-      if (rows_out) HIPCHECK(hipMemsetAsync(rows_out, 0, 8, s));      // (a build that is redone counts its survivors again)
-      { JitScope js(op, op->prog, 5, n, semi_spec(t->T, present)); ProfScope ps(op, s); if (!launch_join_build(s, P, n, op->keys, t->T, next, present, payload_via, op->null_eq, semi_p)) throw Unsupported("join build over a semi table: more than 8 input columns without the specialised kernel"); }
-      HIPCHECK(hipGetLastError());
+      build();
       f = read_flags(op, s);
     }
     if (f & ~FLAG_DUP_BUILD_KEY) { reset_flags(op, s); raise_flags(f & ~FLAG_DUP_BUILD_KEY); }
     if (f) reset_flags(op, s);
     t->has_dups = (f & FLAG_DUP_BUILD_KEY) != 0;
     // what a deferred run goes by next time (a guessed range is remembered widened, as it was used)
-    op->jb.valid = true; op->jb.dense = dense; op->jb.sparse_bits = t->T.dense_bits != nullptr; op->jb.has_dups = t->has_dups; op->jb.kmin = kmin; op->jb.krange = krange;
-    op->expect_flags = t->has_dups ? FLAG_DUP_BUILD_KEY : 0u;
+    jb = {true, dense, t->T.dense_bits != nullptr, t->has_dups, kmin, krange};
+    op->learned.expect_flags = t->has_dups ? FLAG_DUP_BUILD_KEY : 0u;
     return true;
     };
     bool built = false;
     static const bool trace = getenv("GPUQ_TRACE_JOIN_BUILD") != nullptr;
-    if (op->deferred && op->jb.valid) { built = attempt(2); if (trace) fprintf(stderr, "[gpuq] join build: %lld rows (bound), deferred with the remembered layout\n", (long long)n); }
+    if (op->deferred && op->learned.jb.valid) { built = attempt(2); if (trace) fprintf(stderr, "[gpuq] join build: %lld rows (bound), deferred with the remembered layout\n", (long long)n); }
     else if (in->n_rows_dev) throw std::runtime_error("join build: a device-side row count needs a deferred operator with a completed synchronous run (gpuq_op_can_defer)");
-    if (!built && spec_on && narrow_key && n >= (1ll << 21) && !op->join_guess_failed) { built = attempt(true); if (!built) op->join_guess_failed = true; if (trace) fprintf(stderr, "[gpuq] join build: %lld rows, guessed range %s\n", (long long)n, built ? "held" : "did not hold"); }
+    if (!built && spec_on && narrow_key && n >= (1ll << 21) && !op->learned.join_guess_failed) { built = attempt(true); if (!built) op->learned.join_guess_failed = true; if (trace) fprintf(stderr, "[gpuq] join build: %lld rows, guessed range %s\n", (long long)n, built ? "held" : "did not hold"); }
     if (!built) { attempt(false); if (trace) fprintf(stderr, "[gpuq] join build: %lld rows, measured range, %s\n", (long long)n, t->T.dense ? (t->T.dense_bits ? "array + bitmap" : "array") : "hash table"); }
     *out = t;
   });
@@ -1685,25 +1668,25 @@ int gpuq_sort_run(gpuq_op* op, void* stream, const gpuq_input* in, uint32_t* per
       if (string_key) { const uint32_t f = read_flags(op, s); if (f) { reset_flags(op, s); raise_flags(f); } }      // a value beyond 15 bytes: refuse, do not sort by a prefix
       // a client that defers (gpuq_op_set_deferred was called on this operator) will come back with a BOUND instead of a count, and
       // the bound of a handful of groups is easily beyond what one block sorts: learn the key layout now, while reading back is allowed
-      if (op->defer_client) { int total = 0; const SortPack K = sort_key_plan(op, s, P, n, &total); op->so.valid = true; op->so.K = K; op->so.total = total; op->expect_flags = 0; }
+      if (op->defer_client) { int total = 0; const SortPack K = sort_key_plan(op, s, P, n, &total); op->learned.so = {true, K, total}; op->learned.expect_flags = 0; }
       return;
     }
     int total = 0;
     // deferred: the key layout of the last completed synchronous run, verified row by row by the pack kernel (FLAG_SORT_LAYOUT); rows
     // beyond the device-side count become padding records that sort behind everything
-    if (op->deferred && op->so.valid) {
-      SortPack K = op->so.K; K.check = 2;
-      sort_with_plan(op, s, P, n, K, op->so.total, perm_out);
+    if (op->deferred && op->learned.so.valid) {
+      SortPack K = op->learned.so.K; K.check = 2;
+      sort_with_plan(op, s, P, n, K, op->learned.so.total, perm_out);
       return;
     }
     if (in->n_rows_dev) throw std::runtime_error("sort: a device-side row count needs a deferred operator with a completed synchronous run (gpuq_op_can_defer)");
-    op->so.valid = false;
+    op->learned.so.valid = false;
     // Large inputs: the exact min/max pass reads every key once more (0.48 of 3.15 ms at 2^27 Decimal128 keys).  Guess the layout from
     // 2^18 sampled rows instead, let the pack kernel verify it on the way, and read one word back at the end; a guess that does not
     // hold (outliers beyond the margin, a NULL the sample did not see) costs the pack + passes again, so an operator whose guess
     // failed stops guessing.  Packed strings are left out (their layout depends on the longest value).
     static const bool spec_on = []() { const char* e = getenv("GPUQ_SORT_SPECULATE"); return !(e && e[0] == '0'); }();
-    bool spec = spec_on && n >= (1ll << 22) && !op->sort_guess_failed;
+    bool spec = spec_on && n >= (1ll << 22) && !op->learned.sort_guess_failed;
     for (int k = 0; k < S.n_keys; ++k) if (S.kind[k] == 2) spec = false;
     if (spec) {
       const i64 wstep = std::max<i64>(1, ((n + 63) >> 6) >> 12);      // ~4096 words of 64 rows
@@ -1715,13 +1698,13 @@ int gpuq_sort_run(gpuq_op* op, void* stream, const gpuq_input* in, uint32_t* per
         HIPCHECK(hipMemcpyAsync(&eflags, op->flags_dev.p, 4, hipMemcpyDeviceToHost, s));      // the pack kernel evaluated every row
         HIPCHECK(hipStreamSynchronize(s));
         if (eflags) { reset_flags(op, s); raise_flags(eflags); }
-        if (!failed) { op->so.valid = true; op->so.K = G; op->so.total = total; op->expect_flags = 0; return; }
-        op->sort_guess_failed = true;
+        if (!failed) { op->learned.so = {true, G, total}; op->learned.expect_flags = 0; return; }
+        op->learned.sort_guess_failed = true;
       }
     }
     const SortPack K = sort_key_plan(op, s, P, n, &total);
     sort_with_plan(op, s, P, n, K, total, perm_out);
-    op->so.valid = true; op->so.K = K; op->so.total = total; op->expect_flags = 0;
+    op->learned.so = {true, K, total}; op->learned.expect_flags = 0;
   });
 }
 

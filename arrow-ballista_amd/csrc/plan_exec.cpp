@@ -467,11 +467,12 @@ void strip_code_columns(PTable& t) {
     if (t.cols[i].name.rfind("__code_", 0) == 0) { t.cols.erase(t.cols.begin() + (long)i); t.sides.erase(t.sides.begin() + (long)i); t.record_cap = 0; }
 }
 
-static PTable project_impl(Exec& x, const PTable& t_in, const std::vector<Json>& exprs_in, const std::vector<std::string>& names, const void* site, int tag, bool long_cmp);
-PTable project(Exec& x, const PTable& t_in, const std::vector<Json>& exprs_in, const std::vector<std::string>& names, const void* site, int tag) {
-  try { return project_impl(x, t_in, exprs_in, names, site, tag, false); }
+// run(tag, long_cmp); when a string comparison met a value beyond 15 bytes (the loud failure above), once more with the comparisons
+// lowered to helper columns (lower_strcmp), as an operator of its own in the cache (tag + 64)
+template <class F> auto retry_long_cmp(const int tag, F&& run) -> decltype(run(tag, false)) {
+  try { return run(tag, false); }
   catch (const Unsupported& e) { if (!is_long_string_failure(e)) throw; }
-  return project_impl(x, t_in, exprs_in, names, site, tag + 64, true);      // string comparisons beyond 15 bytes: lowered to helper columns (lower_strcmp)
+  return run(tag + 64, true);
 }
 static PTable project_impl(Exec& x, const PTable& t_in, const std::vector<Json>& exprs_in, const std::vector<std::string>& names, const void* site, int tag, const bool long_cmp) {
   std::vector<Json> exprs = exprs_in;
@@ -500,6 +501,9 @@ static PTable project_impl(Exec& x, const PTable& t_in, const std::vector<Json>&
   for (auto& e : exprs) computed = computed || !(e.is_obj() && e.o.size() == 1 && (e.o[0].first == "column" || e.o[0].first == "literal"));
   if (has_utf8 && computed) check(x, gpuq_op_check(op, x.stream));
   return out;
+}
+PTable project(Exec& x, const PTable& t_in, const std::vector<Json>& exprs_in, const std::vector<std::string>& names, const void* site, int tag) {
+  return retry_long_cmp(tag, [&](int tg, bool long_cmp) { return project_impl(x, t_in, exprs_in, names, site, tg, long_cmp); });
 }
 
 // new[j] = vec[idx[j]] with NULL_ROW propagated
@@ -611,12 +615,6 @@ PTable materialize(Exec& x, const PTable& t_in, bool force) {
 }
 
 // the passing driving positions of `source` (in order) and their number
-static int64_t filter_sel_impl(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag, BufP& sel_out, bool long_cmp);
-int64_t filter_sel(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag, BufP& sel_out) {
-  try { return filter_sel_impl(x, source_in, predicate_in, site, tag, sel_out, false); }
-  catch (const Unsupported& e) { if (!is_long_string_failure(e)) throw; }
-  return filter_sel_impl(x, source_in, predicate_in, site, tag + 64, sel_out, true);
-}
 static int64_t filter_sel_impl(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag, BufP& sel_out, const bool long_cmp) {
   std::vector<Json> pe{predicate_in};
   PTable source = source_in; resolve(x, source);      // (the callers of this form need the exact count back)
@@ -634,13 +632,10 @@ static int64_t filter_sel_impl(Exec& x, const PTable& source_in, const Json& pre
   check(x, gpuq_op_check(op, x.stream));
   return k;
 }
-
-static PTable filter_table_impl(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag, bool long_cmp);
-PTable filter_table(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag) {
-  try { return filter_table_impl(x, source_in, predicate_in, site, tag, false); }
-  catch (const Unsupported& e) { if (!is_long_string_failure(e)) throw; }
-  return filter_table_impl(x, source_in, predicate_in, site, tag + 64, true);      // string comparisons beyond 15 bytes: lowered to helper columns (lower_strcmp)
+int64_t filter_sel(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag, BufP& sel_out) {
+  return retry_long_cmp(tag, [&](int tg, bool long_cmp) { return filter_sel_impl(x, source_in, predicate_in, site, tg, sel_out, long_cmp); });
 }
+
 static PTable filter_table_impl(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag, const bool long_cmp) {
   std::vector<Json> pe{predicate_in};
   PTable source = source_in;
@@ -663,6 +658,9 @@ static PTable filter_table_impl(Exec& x, const PTable& source_in, const Json& pr
   const int64_t k = (int64_t)read_u64(x, cnt->p);
   check(x, gpuq_op_check(op, x.stream));
   return select_view(x, source, (const uint32_t*)sel->p, k, sel);
+}
+PTable filter_table(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag) {
+  return retry_long_cmp(tag, [&](int tg, bool long_cmp) { return filter_table_impl(x, source_in, predicate_in, site, tg, long_cmp); });
 }
 
 // the stable permutation that puts `t` in `sort_exprs` order (one gpuq_sort_run: <= 4 keys whose composite fits 128 bits)

@@ -107,7 +107,11 @@ def test_join_build_side_changes_under_the_plan(tc):
     lt3 = _kv(k3, np.arange(3000))
     p.set_input(0, g.DeviceTable.from_arrow(lt3, tc.device)); p.set_input(1, g.DeviceTable.from_arrow(rt, tc.device))
     run(p, lt3, rt)
-    run(p, lt3, rt)
+    assert p.exec_stats()["retries"] == 2
+    for _ in range(2):      # the duplicates are remembered now: the chained table is built deferred, its status bit is expected
+        run(p, lt3, rt)
+        st = p.exec_stats()
+        assert st["deferred"] and st["retries"] == 2, st
     # (c) every probe row matches now: more pairs than the vectors sized from the last run
     rt4 = pa.table({"rk": pa.array(rng.choice(k3, 40_000), pa.int64()), "rv": pa.array(np.arange(40_000), pa.int64())})
     p.set_input(1, g.DeviceTable.from_arrow(rt4, tc.device))
@@ -169,3 +173,65 @@ def test_filter_view_then_consumers(tc):
     exp = [(int(k), int(k) // 2, sv, int(k), int(v)) for sv, k, v in zip(t["s"].to_pylist(), t["k"].to_pylist(), t["v"].to_pylist()) if "special" in sv and k % 2 == 0]
     assert sorted(rows[0]) == sorted(exp)
     assert p.exec_stats()["deferred"]
+
+
+def _replays(p, runs=3, norm=list):
+    """First (synchronous) result of `p`, after checking that `runs` further executions are deferred, hold, and return the same rows
+    (norm=sorted where the operator promises no row order)."""
+    first = norm(arrow_rows(p.execute(0).to_arrow()))
+    assert not p.exec_stats()["deferred"]
+    for _ in range(runs):
+        again = norm(arrow_rows(p.execute(0).to_arrow()))
+        st = p.exec_stats()
+        assert again == first
+        assert st["deferred"] and st["settles"] == 1 and st["retries"] == 0, st
+    return first
+
+
+@pytest.mark.parametrize("layout", ["array", "array_bitmap", "hash_table", "duplicates"])
+def test_join_build_layouts_replay(tc, layout):
+    """Every table layout a join build can remember is replayed by the deferred runs: a direct-addressed array (dense key domain), the
+    array behind its presence bitmap (fewer than one value in four is a key), the hash table (a domain too wide for an array), and
+    chains (duplicate build keys, whose status bit a deferred run is allowed to raise)."""
+    rng = np.random.default_rng(17)
+    nb = 3000
+    if layout == "array":
+        keys = rng.permutation(5000)[:nb] + 100
+    elif layout == "array_bitmap":
+        keys = rng.permutation(60_000)[:nb] + 100
+    elif layout == "hash_table":
+        keys = np.unique(rng.integers(0, 10**12, 2 * nb))[:nb]
+    else:
+        keys = np.concatenate([rng.permutation(5000)[:nb - 500] + 100] * 2)[:nb]
+    lt = _kv(keys, np.arange(nb))
+    probe = np.where(rng.random(40_000) < 0.5, rng.choice(keys, 40_000), rng.integers(0, 10**12, 40_000))
+    rt = pa.table({"rk": pa.array(probe, pa.int64()), "rv": pa.array(np.arange(40_000), pa.int64())})
+    L, R = g.MemoryExec([lt]), g.MemoryExec([rt])
+    p = g.NativePlan(g.HashJoinExec(L, R, [(col("k", L.schema()), col("rk", R.schema()))], None, "Inner", "CollectLeft", False), tc)
+    rows = _replays(p, norm=sorted)
+    import collections
+    by_key = collections.defaultdict(list)
+    for k, v in zip(keys.tolist(), range(nb)):
+        by_key[k].append(v)
+    exp = [(k, v, k, rv) for rv, k in enumerate(probe.tolist()) for v in by_key.get(k, ())]
+    assert rows == sorted(exp) and len(exp) > 0
+
+
+@pytest.mark.parametrize("shape", ["lds_dictionary", "block_local_float_sum"])
+def test_aggregate_strategies_replay(tc, shape):
+    """The aggregate strategies a deferred run replays besides q3's plain global table: the LDS dictionary (a handful of groups, as
+    in q1) and the global table behind block-local pre-aggregation with a float SUM (partial sums staged per block)."""
+    rng = np.random.default_rng(23)
+    n, ngroups = (100_000, 6) if shape == "lds_dictionary" else (1_200_000, 300)
+    k = rng.integers(0, ngroups, n)
+    v = rng.integers(-1000, 1000, n)
+    f = rng.integers(-300, 800, n) / 8.0      # eighths: every partial sum is exact, so the result does not depend on the order of the additions
+    src = g.MemoryExec([pa.table({"k": pa.array(k, pa.int64()), "v": pa.array(v, pa.int64()), "f": pa.array(f, pa.float64())})])
+    s = src.schema()
+    agg = g.AggregateExec("Single", [(col("k", s), "k")], [{"fn": "SUM", "expr": col("v", s), "name": "s"}, {"fn": "SUM", "expr": col("f", s), "name": "fs"},
+                                                        {"fn": "COUNT", "expr": lit(1), "name": "c"}], src)
+    rows = _replays(g.NativePlan(agg, tc), norm=sorted)
+    assert [r[0] for r in rows] == list(range(ngroups))
+    assert [r[1] for r in rows] == np.bincount(k, weights=v, minlength=ngroups).astype(np.int64).tolist()      # (exact in doubles: |sum| < 2^53)
+    assert [r[3] for r in rows] == np.bincount(k, minlength=ngroups).tolist()
+    assert [r[2] for r in rows] == np.bincount(k, weights=f, minlength=ngroups).tolist()
