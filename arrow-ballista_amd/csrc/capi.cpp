@@ -176,6 +176,7 @@ void read_status(gpuq_op* op, hipStream_t s, uint32_t* out, int n) {
 uint32_t read_flags(gpuq_op* op, hipStream_t s) { uint32_t f = 0; read_status(op, s, &f, 1); return f; }
 void raise_flags(uint32_t f) {
   if (f & FLAG_STR_TRUNC) throw Unsupported("a Utf8 value longer than 15 bytes reached a device string comparison/key (PACKED15 limit)");
+  if (f & FLAG_DEC_OVERFLOW) throw std::runtime_error("decimal arithmetic overflow: a result or a rescaled operand does not fit Decimal128 (38 digits / 127 bits)");
   if (f & FLAG_WIDE_MINMAX) throw Unsupported("MIN/MAX over a value outside the int64 range is not supported on device");
   if (f & FLAG_DUP_BUILD_KEY) throw Unsupported("duplicate build keys without a chain buffer");
   if (f & FLAG_OUT_OVERFLOW) throw Capacity("join output capacity exceeded; see the pair count for the required size");
@@ -953,6 +954,9 @@ int gpuq_project_run(gpuq_op* op, void* stream, const gpuq_input* in, gpuq_colum
     for (int i = 0; i < n_outs; ++i) outs[i].length = in->n_rows;
     { JitScope js(op, op->prog, 2, in->n_rows); ProfScope ps(op, s); launch_project(s, P, in->n_rows, O); }
     HIPCHECK(hipGetLastError());
+    // a projection is otherwise never read back; one that holds checked decimal arithmetic must not hand out a wrapped value (a deferred
+    // run's status word is read when it is settled)
+    if (op->prog.checks_overflow && !op->deferred) { const uint32_t f = read_flags(op, s); if (f) { reset_flags(op, s); raise_flags(f); } }
   });
 }
 

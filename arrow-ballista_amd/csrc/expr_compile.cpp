@@ -174,7 +174,10 @@ NodeP ExprCompiler::column(int fi) {
   auto n = std::make_shared<Node>();
   n->kind = Node::COL; n->col = fi; n->type = schema_.fields[fi].type; n->nullable = schema_.fields[fi].nullable || (schema_.fields[fi].side > 0 && !schema_.fields[fi].dense);
   n->bits = type_bits(n->type); n->key = "c" + std::to_string(fi);
-  return intern(n);
+  n = intern(n);
+  // an 8-byte load sign-extends into the 128-bit register: a UInt64 of 2^63 or more is that value only after its upper half is cleared
+  if (n->type.id == T_UINT64 && !schema_.fields[fi].raw128) return raw(OP_WRAP, n->type, n->nullable, type_bits(n->type), {n}, 64u | 0x100u);
+  return n;
 }
 NodeP ExprCompiler::lit_int(DType t, i128 v) {
   auto n = std::make_shared<Node>();
@@ -232,6 +235,17 @@ static DType as_decimal(const DType& t) {
 }
 static DType mk(int id) { DType t; t.id = id; return t; }
 
+// An integer node wraps at its type's width (DataFusion's *_wrapping kernels wrap at every node, and a consumer inside the same expression
+// -- a comparison, an aggregate argument, a cast -- must see the wrapped value, not only the column it is stored to).  `bits` is the
+// UNCLAMPED bound of e's value (|v| < 2^bits); no instruction is emitted where that bound already fits the type.
+NodeP ExprCompiler::wrap_to(NodeP e, DType t, int bits, bool may_be_negative) {
+  if (!(t.is_int() || t.is_temporal())) return e;
+  const int w = type_width(t) * 8;
+  const bool fits = t.is_unsigned() ? (!may_be_negative && bits <= w + 1) : bits <= w;
+  if (fits) return e;
+  return raw(OP_WRAP, t, e->nullable, type_bits(t), {e}, (uint32_t)w | (t.is_unsigned() ? 0x100u : 0u));
+}
+
 NodeP ExprCompiler::rescale(NodeP e, int new_scale) {
   DType d = as_decimal(e->type);
   if (d.s == new_scale) {
@@ -246,7 +260,9 @@ NodeP ExprCompiler::rescale(NodeP e, int new_scale) {
       return lit_int(dec_type(d.p + k, new_scale), v * pow10_i128(k));
     }
     NodeP f = lit_int(dec_type(k + 1, 0), pow10_i128(k));
-    const int op = (e->bits <= 63 && f->bits <= 63) ? OP_MULW : OP_MUL;
+    // beyond 127 bits the product can wrap: checked at run time (the bound is from the declared types -- q14's Decimal(38,6) / Decimal(38,4)
+    // holds small values and must run)
+    const int op = e->bits + f->bits > 127 ? OP_MULC : (e->bits <= 63 && f->bits <= 63) ? OP_MULW : OP_MUL;
     return raw(op, dec_type(d.p + k, new_scale), e->nullable, e->bits + f->bits, {e, f});
   }
   // reducing scale: divide, round half away from zero (arrow cast_decimal_to_decimal) [UPSTREAM-KNOWLEDGE]
@@ -322,8 +338,12 @@ NodeP ExprCompiler::cast(NodeP e, DType to) {
   }
   if (to.is_int() || to.is_temporal()) {
     // the storage integer of a temporal type casts to and from plain integers unchanged
-    if ((from.is_int() || from.id == T_BOOL || from.is_temporal()) && (to.is_int() || from.is_int())) return raw(OP_MOV, to, e->nullable, std::min(e->bits, type_bits(to)), {e});
-    if (from.is_decimal()) { NodeP r = rescale(e, 0); return raw(OP_MOV, to, e->nullable, std::min(r->bits, type_bits(to)), {r}); }
+    // (a narrowing or sign-changing integer cast wraps: arrow's unchecked cast)
+    if ((from.is_int() || from.id == T_BOOL || from.is_temporal()) && (to.is_int() || from.is_int())) {
+      NodeP w = wrap_to(e, to, e->bits, !(from.is_unsigned() || from.id == T_BOOL));
+      return w != e ? w : raw(OP_MOV, to, e->nullable, e->bits, {e});
+    }
+    if (from.is_decimal()) { NodeP r = rescale(e, 0); NodeP w = wrap_to(r, to, r->bits, true); return w != r ? w : raw(OP_MOV, to, e->nullable, r->bits, {r}); }
     if (from.is_float()) return raw(OP_F2I, to, e->nullable, type_bits(to), {e});
   }
   if (to.id == T_BOOL && from.is_int()) return raw(OP_NE, to, e->nullable, 2, {e, lit_int(from, 0)});
@@ -399,39 +419,52 @@ NodeP ExprCompiler::binary(const std::string& op_in, NodeP l, NodeP r) {
       const int s = std::max(dl.s, dr.s);
       const int p = std::min(38, std::max(dl.p - dl.s, dr.p - dr.s) + s + 1);
       NodeP a = rescale(l, s), b = rescale(r, s);
+      // the precision rule capped at 38, or operands beyond 126 bits: the exact result may not fit -> checked (OVERFLOW, as arrow-arith raises)
+      const bool capped = std::max(dl.p - dl.s, dr.p - dr.s) + s + 1 > 38;
+      if (capped || std::max(a->bits, b->bits) + 1 > 127) return raw(op == "+" ? OP_ADDC : OP_SUBC, dec_type(p, s), nullable, 127, {a, b}, capped ? 1u : 0u);
       return raw(op == "+" ? OP_ADD : OP_SUB, dec_type(p, s), nullable, std::max(a->bits, b->bits) + 1, {a, b});
     }
     if (op == "*") {
       const DType rt = dec_type(std::min(38, dl.p + dl.s * 0 + dr.p + 1), std::min(38, dl.s + dr.s));
       NodeP a = rescale(l, dl.s), b = rescale(r, dr.s);
+      if (a->bits + b->bits > 127) return raw(OP_MULC, rt, nullable, 127, {a, b}, dl.p + dr.p > 38 ? 1u : 0u);      // checked: see OP_MULC
       const int o = (a->bits <= 63 && b->bits <= 63) ? OP_MULW : OP_MUL;
       return raw(o, rt, nullable, a->bits + b->bits, {a, b});
     }
     // arrow-arith 49 numeric.rs decimal_op [UPSTREAM-KNOWLEDGE]: Div -> scale s1+4, precision p1+(4+s2), l*10^(4+s2) / r
     // truncated toward zero; Rem -> scale max(s1,s2), precision min(p1-s1,p2-s2)+scale.  x/0 -> NULL (see the integer case).
+    // A rescaled operand that leaves 127 bits is an OVERFLOW error at run time (rescale() emits the checked multiply: the bound from the
+    // declared types alone would refuse q14's Decimal(38,6) / Decimal(38,4), whose values are small).
     if (op == "/") {
       const int rs = std::min(38, dl.s + 4), k = rs - dl.s + dr.s;
       NodeP a = rescale(l, dl.s + k), b = rescale(r, dr.s);
-      if (a->bits > 127) throw std::runtime_error("decimal division " + l->type.to_string() + " / " + r->type.to_string() + " can overflow 128 bits on device");
       return raw(OP_DIV, dec_type(std::min(38, dl.p + k), rs), true, a->bits, {a, b});
     }
     if (op == "%") {
       const int s = std::max(dl.s, dr.s);
       NodeP a = rescale(l, s), b = rescale(r, s);
-      if (a->bits > 127 || b->bits > 127) throw std::runtime_error("decimal modulo operands can overflow 128 bits on device");
       return raw(OP_MOD, dec_type(std::min(38, std::min(dl.p - dl.s, dr.p - dr.s) + s), s), true, b->bits, {a, b});
     }
     throw std::runtime_error("decimal operator '" + op + "' is not supported on device yet");
   }
   if ((l->type.is_int() || l->type.id == T_DATE32) && (r->type.is_int() || r->type.id == T_DATE32)) {
     DType rt = mk((l->type.id == T_INT64 || r->type.id == T_INT64 || l->type.id == T_UINT64 || r->type.id == T_UINT64) ? T_INT64 : T_INT32);
-    if (l->type == r->type && l->type.is_int()) rt = l->type;      // the planner has coerced both sides: the result wraps to that width where it is stored
+    if (l->type == r->type && l->type.is_int()) rt = l->type;      // the planner has coerced both sides: the result keeps that type (and wraps to its width at this node, below)
     if (l->type.id == T_DATE32 && r->type.id == T_DATE32 && op == "-") rt = mk(T_INT32);
     else if (l->type.id == T_DATE32 || r->type.id == T_DATE32) rt = mk(T_DATE32);
-    if (op == "+") return raw(OP_ADD, rt, nullable, std::max(l->bits, r->bits) + 1, {l, r});
-    if (op == "-") return raw(OP_SUB, rt, nullable, std::max(l->bits, r->bits) + 1, {l, r});
-    if (op == "*") return raw((l->bits <= 63 && r->bits <= 63) ? OP_MULW : OP_MUL, rt, nullable, l->bits + r->bits, {l, r});
-    if (op == "/") return raw(OP_DIV, rt, true, l->bits, {l, r});   // x/0 -> NULL (arrow raises DivideByZero)
+    // + - * wrap at rt's width AT THIS NODE (wrap_to): the value a comparison, an aggregate or a cast above sees is the one a store would keep
+    const bool neg_in = !(l->type.is_unsigned() && r->type.is_unsigned());
+    if (op == "+") return wrap_to(raw(OP_ADD, rt, nullable, std::max(l->bits, r->bits) + 1, {l, r}), rt, std::max(l->bits, r->bits) + 1, neg_in);
+    if (op == "-") return wrap_to(raw(OP_SUB, rt, nullable, std::max(l->bits, r->bits) + 1, {l, r}), rt, std::max(l->bits, r->bits) + 1, true);
+    if (op == "*") return wrap_to(raw((l->bits <= 63 && r->bits <= 63) ? OP_MULW : OP_MUL, rt, nullable, l->bits + r->bits, {l, r}), rt, l->bits + r->bits, neg_in);
+    // x/0 -> NULL (arrow raises DivideByZero).  INT_MIN / -1 -> INT_MIN and INT_MIN % -1 -> 0: the wrapping answer (the exact quotient
+    // 2^(w-1) wrapped to w bits; arrow's checked kernels raise Overflow there, a device row cannot raise and nothing else defines a value)
+    // (only a signed quotient can leave its type, and only through a divisor of -1: an unsigned division and one by any other literal stay one instruction)
+    if (op == "/") {
+      NodeP q = raw(OP_DIV, rt, true, l->bits, {l, r});
+      const bool lit_not_m1 = r->kind == Node::LIT && !r->lit_null && !(r->lit_lo == ~0ull && r->lit_hi == ~0ull);
+      return (rt.is_unsigned() || lit_not_m1) ? q : wrap_to(q, rt, l->bits + 1, true);
+    }
     if (op == "%") return raw(OP_MOD, rt, true, r->bits, {l, r});
   }
   throw std::runtime_error("unsupported operands for '" + op + "': " + l->type.to_string() + ", " + r->type.to_string());
@@ -444,7 +477,7 @@ NodeP ExprCompiler::not_(NodeP e) {
 NodeP ExprCompiler::is_null(NodeP e, bool negate) { return raw(negate ? OP_ISNOTNULL : OP_ISNULL, mk(T_BOOL), false, 2, {e}); }
 NodeP ExprCompiler::negative(NodeP e) {
   if (e->type.is_float()) return raw(OP_FNEG, e->type, e->nullable, 127, {e});
-  return raw(OP_NEG, e->type, e->nullable, e->bits + 1, {e});
+  return wrap_to(raw(OP_NEG, e->type, e->nullable, e->bits + 1, {e}), e->type, e->bits + 1, true);      // -(INT_MIN) wraps to INT_MIN
 }
 NodeP ExprCompiler::select(NodeP c, NodeP t, NodeP f) {
   if (t->type.id == T_NULL) t = lit_null(f->type);
@@ -668,6 +701,7 @@ CompiledProgram ExprCompiler::finish() {
   for (auto& o : outs_) {
     C.out_reg.push_back(reg.at(rep(o.get()))); C.out_type.push_back(o->type); C.out_nullable.push_back(o->nullable); C.out_key.push_back(o->key); C.out_bits.push_back((o->type.is_int() || o->type.is_decimal() || o->type.id == T_DATE32) ? o->bits : 127);
   }
+  for (Node* n : order) if (n->kind == Node::OPN && (n->op == OP_ADDC || n->op == OP_SUBC || n->op == OP_MULC)) C.checks_overflow = true;
   C.jit_src = jit_source(C, order, reg);
   return C;
 }
@@ -879,7 +913,9 @@ std::string ExprCompiler::jit_source(const CompiledProgram& C, const std::vector
       case OP_DIV: case OP_MOD: {
         const bool narrow = !wide(rep(a.get())) && !wide(rep(b.get()));
         L("const bool " + t + "_z = (" + V(b) + " == 0);");
-        if (narrow) e = "(" + t + "_z ? (i64)0 : (i64)(" + V(a) + (n->op == OP_DIV ? " / " : " % ") + "(" + t + "_z ? (i64)1 : (i64)" + V(b) + ")))";
+        // a divisor of 0 or -1 never reaches the hardware sequence: INT64_MIN / -1 is undefined in C++ (here: the wrapped negation, and 0 for %)
+        if (narrow) { L("const bool " + t + "_m = (" + V(b) + " == -1);");
+                      e = "(" + t + "_z ? (i64)0 : " + t + "_m ? " + (n->op == OP_DIV ? "(i64)(0ull - (u64)" + V(a) + ")" : std::string("(i64)0")) + " : (i64)(" + V(a) + (n->op == OP_DIV ? " / " : " % ") + "((" + t + "_z || " + t + "_m) ? (i64)1 : (i64)" + V(b) + ")))"; }
         else { L("i128 " + t + "_q = 0, " + t + "_r = 0; if (!" + t + "_z) divmod128(" + as128(a) + ", " + as128(b) + ", " + t + "_q, " + t + "_r);");
                e = std::string("(") + T + ")" + t + (n->op == OP_DIV ? "_q" : "_r"); }
         ne = orn({N(a), N(b), t + "_z"});
@@ -898,7 +934,7 @@ std::string ExprCompiler::jit_source(const CompiledProgram& C, const std::vector
         Node* ra = rep(a.get());
         if (is_b(ra)) e = "(double)(int)" + V(a);
         else if (!wide(ra)) e = "(double)" + V(a);
-        else e = "(((i64)((u128)" + V(a) + " >> 64) == ((i64)(u64)" + V(a) + " >> 63)) ? (double)(i64)(u64)" + V(a) + " : ((double)(i64)((u128)" + V(a) + " >> 64) * 18446744073709551616.0 + (double)(u64)" + V(a) + "))";
+        else e = "i128_to_f64(" + V(a) + ")";      // one rounding (gpuq_dev.h)
         ne = N(a); break;
       }
       case OP_F2I: e = "(i64)" + V(a); ne = N(a); break;
@@ -932,6 +968,12 @@ std::string ExprCompiler::jit_source(const CompiledProgram& C, const std::vector
         two_vars = true; ne = N(a); break;
       }
       case OP_BOR: e = "(" + as128(a) + " | " + as128(b) + ")"; break;
+      case OP_WRAP: e = "wrap_int((i128)" + V(a) + ", " + std::to_string(n->imm) + "u)"; ne = N(a); break;
+      case OP_ADDC: case OP_SUBC: case OP_MULC: {
+        L("bool " + t + "_o; const i128 " + t + "_v = checked_arith(" + std::to_string(n->op) + ", " + as128(a) + ", " + as128(b) + ", " + ((n->imm & 1u) ? "true" : "false") + ", " + t + "_o);");
+        L("if (" + t + "_o && !(" + ne + ") && P.flags) atomicOr(P.flags, FLAG_DEC_OVERFLOW);");
+        e = t + "_v"; break;
+      }
       case OP_NULLIF0: {
         Node* rb = rep(b.get());
         const std::string bz = is_str(rb) ? "(" + V(b) + "_lo == 0 && " + V(b) + "_hi == 0)" : (is_f(rb) ? "(__double_as_longlong(" + V(b) + ") == 0)" : "(" + V(b) + " == 0)");

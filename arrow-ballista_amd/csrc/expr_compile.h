@@ -10,6 +10,10 @@
 //   SUM(decimal(p,s)) -> Decimal128(min(38,p+10), s);  AVG -> Decimal128(min(38,p+4), min(38,s+4)),
 //   AVG value = sum * 10^(s_avg - s) / count with truncating i128 division
 //   SUM/AVG over integers: SUM -> Int64 (wrapping), AVG -> Float64 (f64 sum / count)
+//   integer + - *, NEGATIVE and integer casts wrap at the node's type width at every node (OP_WRAP); x/0 -> NULL,
+//   INT_MIN / -1 -> INT_MIN, INT_MIN % -1 -> 0
+//   a decimal result beyond the 38 digits its type is capped at, or an operand whose rescale by 10^k leaves 127 bits,
+//   is an error at run time (OP_ADDC / OP_SUBC / OP_MULC raise FLAG_DEC_OVERFLOW; arrow-arith raises there)
 #pragma once
 #include "gpuq_dev.h"
 #include "json.h"
@@ -90,6 +94,7 @@ struct CompiledProgram {
   std::vector<bool> out_nullable;
   std::vector<std::string> out_key;
   std::vector<int> out_bits;    // |value| < 2^bits for every output (from the declared types; 127 = unknown)
+  bool checks_overflow = false; // holds a checked decimal instruction (OP_ADDC / OP_SUBC / OP_MULC): a run may raise FLAG_DEC_OVERFLOW
   std::string jit_src;          // C++ source of gpuq_jit_eval() for this program (typed, straight-line)
 };
 
@@ -114,6 +119,7 @@ class ExprCompiler {
   NodeP select(NodeP c, NodeP t, NodeP f);
   NodeP raw(int op, DType t, bool nullable, int bits, std::vector<NodeP> ch, uint32_t imm = 0);
   NodeP rescale(NodeP e, int new_scale);         // decimal scale change (exact when increasing)
+  NodeP wrap_to(NodeP e, DType t, int bits, bool may_be_negative);   // e wrapped to integer type t where its bound 2^bits does not fit it
   NodeP coalesce0(NodeP e);
   NodeP nullif0(NodeP e, NodeP guard);
   // --- program assembly

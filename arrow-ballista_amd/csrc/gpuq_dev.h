@@ -14,7 +14,9 @@
 #include <stdint.h>
 #else
 // hiprtc keeps the fixed-width integer names inside __hip_internal
+typedef signed char int8_t;          // (the generated code sign-extends Int8 / Int16 columns through these)
 typedef unsigned char uint8_t;
+typedef signed short int16_t;
 typedef unsigned short uint16_t;
 typedef signed int int32_t;
 typedef unsigned int uint32_t;
@@ -75,6 +77,14 @@ enum Op : uint8_t {
   OP_DATEPART,  // dst <- field imm (0 year, 1 month, 2 day) of the Date32 a (days since 1970-01-01), as an integer
   OP_SUBSTR,    // dst <- substr(a, start, len) of a packed Utf8 value, ASCII only; imm = (start - 1) | len << 8 (len 255 = to the end)
   OP_F32R,      // dst <- (double)(float)a: a double rounded to the nearest Float32 (Float32 arithmetic and casts)
+  OP_WRAP,      // dst <- a wrapped to an integer type's width: imm = bits (8/16/32/64) | 0x100 when the type is unsigned (zero- instead of sign-extended)
+  // Checked decimal arithmetic, emitted only where the operand bounds allow the exact result to leave 127 bits or 38 digits: the value is
+  // the wrapped one, FLAG_DEC_OVERFLOW is raised for a non-NULL row whose exact result does not fit (imm bit 0: the limit is 10^38, else 2^127)
+  // Which rows raise: every non-NULL row on which the instruction RUNS.  Both evaluators compute both branches of a CASE, so an
+  // untaken branch that overflows raises too (arrow evaluates a branch only for the rows that take it).  Under a fused predicate the
+  // interpreter runs the whole program before it looks at the predicate and raises for rows the predicate drops as well; the generated
+  // code returns at the predicate and does not.  The flag can therefore be raised where arrow would not raise, never the other way round.
+  OP_ADDC, OP_SUBC, OP_MULC,
 };
 
 struct DevInsn { uint8_t op, dst, a, b; uint32_t imm; };
@@ -127,6 +137,7 @@ constexpr uint32_t FLAG_TABLE_FULL = 4u;
 constexpr uint32_t FLAG_DUP_BUILD_KEY = 8u;
 constexpr uint32_t FLAG_OUT_OVERFLOW = 16u;
 constexpr uint32_t FLAG_WIDE_MINMAX = 32u;  // MIN/MAX over a value outside the int64 range
+constexpr uint32_t FLAG_DEC_OVERFLOW = 128u;  // a decimal result (or an operand rescaled by a power of ten) left 127 bits / its 38 digits: arrow-arith raises there
 constexpr uint32_t FLAG_SORT_LAYOUT = 64u;  // a row does not fit the composite sort key layout remembered from the previous run (deferred execution)
 
 // Per-lane register file.  lo/hi MUST be separate plain u64 arrays local to the kernel: hipcc then
@@ -185,7 +196,8 @@ __device__ __forceinline__ i64 date_part_of_days(i64 days, int which) {
 }
 // substr over the packed form (<= 15 bytes big-endian in bits 127..8, true length in bits 7..0): `skip` leading bytes dropped, at most
 // `len` kept (255 = the rest).  Exact whenever skip + kept <= 15 even for a longer value (its first 15 bytes are all there); `bad`
-// is raised when bytes beyond the packed prefix would be needed, or when a kept byte is not ASCII (SQL counts characters).
+// is raised when bytes beyond the packed prefix would be needed, or when a byte up to the end of the kept part is not ASCII (SQL counts
+// characters: a multi-byte character in the SKIPPED prefix moves the kept part as well).
 __device__ __forceinline__ u128 substr_packed(u128 x, uint32_t skip, uint32_t len, bool& bad) {
   const uint32_t L = (uint32_t)x & 0xFFu;
   uint32_t keep = L > skip ? L - skip : 0u;
@@ -195,7 +207,9 @@ __device__ __forceinline__ u128 substr_packed(u128 x, uint32_t skip, uint32_t le
   const u128 shifted = skip >= 16u ? (u128)0 : (body << (8u * skip));
   const u128 mask = keep ? (~(u128)0 << (128u - 8u * keep)) : (u128)0;
   const u128 out = shifted & mask;
-  if ((out >> 8) & ((u128)0x80808080808080ull << 64 | (u128)0x8080808080808080ull)) bad = true;
+  const uint32_t used = !keep ? 0u : (skip + keep < 15u ? skip + keep : 15u);      // skipped and kept bytes (nothing kept: '' whatever was skipped)
+  const u128 head = used ? (body & (~(u128)0 << (128u - 8u * used))) : (u128)0;
+  if ((head >> 8) & ((u128)0x80808080808080ull << 64 | (u128)0x8080808080808080ull)) bad = true;
   return out | (u128)keep;
 }
 
@@ -218,6 +232,54 @@ __device__ inline void divmod128(i128 n, i128 d, i128& q, i128& r) {
   }
   q = (nn != dn) ? -(i128)uq : (i128)uq;
   r = nn ? -(i128)ur : (i128)ur;
+}
+
+// i128 -> f64 with ONE rounding (arrow-rs casts with `x as f64`).  (double)hi * 2^64 + (double)lo rounds lo first and the sum again: for
+// 2^64 + 2^63 + 2^11 + 1 that gives 2^64 + 2^63 where the correctly rounded value is 2^64 + 2^63 + 4096.  Here the magnitude's top 64
+// bits, with a sticky bit for what was shifted out (11 bits below the rounding position, so it only breaks ties), are converted once
+// and scaled by an exact power of two.
+__device__ __forceinline__ double i128_to_f64(i128 v) {
+  const bool neg = v < 0;
+  const u128 m = neg ? (u128)0 - (u128)v : (u128)v;
+  const u64 hi = (u64)(m >> 64), lo = (u64)m;
+  double d;
+  if (hi == 0) d = (double)lo;
+  else {
+    const int sh = 64 - __clzll((long long)hi);                                   // 1..64 bits lie above the low 64
+    const u64 top = (u64)(m >> sh) | (u64)((lo << (64 - sh)) != 0);               // sh >= 1: the shift count stays below 64
+    d = (double)top * __longlong_as_double((i64)(1023 + sh) << 52);
+  }
+  return neg ? -d : d;
+}
+// Whether the exact product a * b leaves 127 bits (the i128 product wraps silently).
+__device__ __forceinline__ bool mul128_overflows(i128 a, i128 b) {
+  const u128 ua = a < 0 ? (u128)0 - (u128)a : (u128)a, ub = b < 0 ? (u128)0 - (u128)b : (u128)b;
+  const u64 ah = (u64)(ua >> 64), al = (u64)ua, bh = (u64)(ub >> 64), bl = (u64)ub;
+  if (ah != 0 && bh != 0) return true;
+  const u128 cross = (u128)ah * bl + (u128)al * bh;                                // one of the two terms is zero
+  if (cross >> 63) return true;                                                   // cross * 2^64 >= 2^127
+  const u128 low = (u128)al * bl, sum = low + (cross << 64);
+  return sum < low || (sum >> 127) != 0;
+}
+// |v| >= 10^38: beyond what Decimal128(38, s) holds
+__device__ __forceinline__ bool beyond_38_digits(i128 v) {
+  const i128 p38 = mk128(0x098A224000000000ull, 0x4B3B4CA85A86C47Aull);
+  return v >= p38 || v <= -p38;
+}
+// OP_ADDC / OP_SUBC / OP_MULC: the wrapped result, and whether the exact one is out of range (limit38: of 38 digits, else of 127 bits)
+__device__ __forceinline__ i128 checked_arith(int op, i128 a, i128 b, bool limit38, bool& over) {
+  i128 z;
+  if (op == OP_MULC) { z = (i128)((u128)a * (u128)b); over = mul128_overflows(a, b); }
+  else if (op == OP_ADDC) over = __builtin_add_overflow(a, b, &z);
+  else over = __builtin_sub_overflow(a, b, &z);
+  if (limit38 && beyond_38_digits(z)) over = true;
+  return z;
+}
+__device__ __forceinline__ i128 wrap_int(i128 v, uint32_t imm) {
+  const uint32_t w = imm & 0xFFu;
+  const u64 lo = (u64)v;
+  if (imm & 0x100u) return (i128)(u128)(w >= 64u ? lo : (lo & ((1ull << w) - 1)));
+  return (i128)(w >= 64u ? (i64)lo : ((i64)(lo << (64u - w)) >> (64u - w)));
 }
 
 #ifndef GPUQ_JIT
@@ -397,9 +459,8 @@ __device__ __forceinline__ void run_program(const DevProgram& P, GPUQ_REGS_PARAM
       case OP_FGT: zlo = f64_total_key(alo) > f64_total_key(blo); break;
       case OP_FGE: zlo = f64_total_key(alo) >= f64_total_key(blo); break;
       case OP_I2F: {
-        // i128 -> f64, correctly rounded for |a| < 2^64 (hi is sign extension), else via two halves
-        double v = ((i64)ahi == ((i64)alo >> 63)) ? (double)(i64)alo
-                                                  : ((double)(i64)ahi * 18446744073709551616.0 + (double)alo);
+        // i128 -> f64, one rounding (hi is the sign extension for |a| < 2^63: the hardware conversion)
+        double v = ((i64)ahi == ((i64)alo >> 63)) ? (double)(i64)alo : i128_to_f64(mk128(alo, ahi));
         zlo = (u64)__double_as_longlong(v); zn = an; break;
       }
       case OP_F2I: { i64 v = (i64)__longlong_as_double((i64)alo); zlo = (u64)v; zhi = (u64)(v >> 63); zn = an; break; }
@@ -430,6 +491,12 @@ __device__ __forceinline__ void run_program(const DevProgram& P, GPUQ_REGS_PARAM
       case OP_BOR: zlo = alo | blo; zhi = ahi | bhi; break;
       case OP_NULLIF0: zlo = alo; zhi = ahi; zn = an || bn || (blo == 0 && bhi == 0); break;
       case OP_COALESCE0: zlo = an ? 0 : alo; zhi = an ? 0 : ahi; zn = false; break;
+      case OP_WRAP: { const i128 z = wrap_int(mk128(alo, ahi), imm); zlo = (u64)z; zhi = (u64)((u128)z >> 64); zn = an; break; }
+      case OP_ADDC: case OP_SUBC: case OP_MULC: {
+        bool over; const i128 z = checked_arith(op, mk128(alo, ahi), mk128(blo, bhi), (imm & 1u) != 0, over);
+        zlo = (u64)z; zhi = (u64)((u128)z >> 64);
+        if (over && !zn && P.flags) atomicOr(P.flags, FLAG_DEC_OVERFLOW); break;
+      }
       default: zn = false; break;
     }
     rlo[d] = zlo; rhi[d] = zhi;

@@ -1,0 +1,258 @@
+"""Pins tests/expr_exact.py, the exact reference of the expression layer, without a GPU: against pyarrow.compute where Arrow C++ has
+the same semantics (decimal + - *, unchecked integer + - *, year / month / day, Kleene AND / OR, integer -> Float64), against
+hand-computed answers where it has not (decimal / and %, scale-reducing casts, decimal -> Float64), and the value tables of
+test_gpu_expr_extremes.py against their own conditions (no OVERFLOW row outside the overflow plans, nothing but OVERFLOW inside)."""
+import math
+
+import pyarrow as pa
+import pyarrow.compute as pc
+import pytest
+
+import expr_exact as X
+import expr_extreme_cases as K
+from arrow_ballista_amd import binding as B
+from arrow_ballista_amd import expr as E
+from arrow_ballista_amd.expr import Operator as Op
+from arrow_ballista_amd.expr import binary, cast, col, lit
+
+
+def unscaled(arr, s):
+    import decimal
+    ctx = decimal.Context(prec=80)
+    return [None if v is None else int(v.scaleb(s, context=ctx)) for v in arr.to_pylist()]
+
+
+def one(e):
+    """An expression over literals only, evaluated on one row."""
+    t, v = X.evaluate(e, [{"name": "x", "type": "Int32"}], {"x": [0]})
+    return t, v[0]
+
+
+def dl(v, p, s):
+    return lit(v, ("Decimal128", p, s))
+
+
+# ------------------------------------------------------------------------------------------------ against pyarrow.compute
+@pytest.mark.parametrize("pair", K.DEC_PAIRS)
+def test_decimal_add_subtract_multiply_match_arrow(pair):
+    (p1, s1), (p2, s2) = pair
+    t = K.cross_table("t", K.D(p1, s1), K.dec_vector(p1), K.D(p2, s2), K.dec_vector(p2), tiles=1)
+    at = t.arrow()
+    for op, f in ((Op.Plus, pc.add), (Op.Minus, pc.subtract), (Op.Multiply, pc.multiply)):
+        ty, vals = X.evaluate(binary(col("a", t.schema), op, col("b", t.schema)), t.schema, t.cols)
+        want = f(at["a"], at["b"]).combine_chunks()
+        p, s = ty["Decimal128"]
+        assert want.type == pa.decimal128(p, s), (op, want.type, ty)
+        assert vals == unscaled(want, s), op
+    assert X.evaluate(binary(lit(1, K.D(15, 2)), Op.Plus, lit(1, K.D(18, 4))), t.schema, t.cols)[0] == {"Decimal128": [19, 4]}
+    assert X.evaluate(binary(lit(1, K.D(15, 2)), Op.Multiply, lit(1, K.D(18, 4))), t.schema, t.cols)[0] == {"Decimal128": [34, 6]}
+
+
+@pytest.mark.parametrize("ty", K.INT_TYPES)
+def test_integer_add_subtract_multiply_wrap_like_arrow(ty):
+    v = K.int_vector(ty)
+    t = K.cross_table("t", ty, v, ty, v, tiles=1)
+    at = t.arrow()
+    for op, f in ((Op.Plus, pc.add), (Op.Minus, pc.subtract), (Op.Multiply, pc.multiply)):
+        rt, vals = X.evaluate(binary(col("a", t.schema), op, col("b", t.schema)), t.schema, t.cols)
+        want = f(at["a"], at["b"]).combine_chunks()
+        assert rt == ty and vals == want.to_pylist(), (ty, op)
+    if X._INT[ty][1]:
+        rt, vals = X.evaluate(E.negative(col("a", t.schema)), t.schema, t.cols)
+        assert vals == pc.negate(at["a"]).to_pylist()
+    # narrowing and sign-changing casts wrap (pyarrow's unsafe cast)
+    for to, pt in (("Int8", pa.int8()), ("UInt16", pa.uint16()), ("Int32", pa.int32()), ("UInt64", pa.uint64())):
+        if to != ty:
+            assert X.evaluate(cast(col("a", t.schema), to), t.schema, t.cols)[1] == pc.cast(at["a"], pt, safe=False).to_pylist(), (ty, to)
+    # integer -> Float64: one correctly rounded conversion
+    got = X.evaluate(cast(col("a", t.schema), "Float64"), t.schema, t.cols)[1]
+    assert got == pc.cast(at["a"], pa.float64(), safe=False).to_pylist()
+
+
+def test_integer_division_pins():
+    """x/0 -> NULL; / truncates toward zero, % takes the sign of the dividend; INT_MIN / -1 = INT_MIN and INT_MIN % -1 = 0 (wrapping)."""
+    for ty, lo in (("Int8", -2**7), ("Int16", -2**15), ("Int32", -2**31), ("Int64", -2**63)):
+        assert one(binary(lit(lo, ty), Op.Divide, lit(-1, ty))) == (ty, lo)
+        assert one(binary(lit(lo, ty), Op.Modulo, lit(-1, ty))) == (ty, 0)
+        assert one(E.negative(lit(lo, ty))) == (ty, lo)
+        assert one(binary(lit(lo, ty), Op.Divide, lit(0, ty))) == (ty, None)
+        assert one(binary(lit(lo, ty), Op.Modulo, lit(0, ty))) == (ty, None)
+    assert one(binary(lit(-7, "Int32"), Op.Divide, lit(2, "Int32")))[1] == -3       # -3.5 -> -3
+    assert one(binary(lit(7, "Int32"), Op.Divide, lit(-2, "Int32")))[1] == -3
+    assert one(binary(lit(-7, "Int32"), Op.Modulo, lit(2, "Int32")))[1] == -1       # -7 - 2 * -3
+    assert one(binary(lit(7, "Int32"), Op.Modulo, lit(-2, "Int32")))[1] == 1        # 7 - -2 * -3
+
+
+def test_date_parts_match_arrow():
+    v = K.date_vector()
+    t = K.cross_table("t", "Date32", v, "Date32", v, tiles=1)
+    at = t.arrow()
+    for part, f in (("YEAR", pc.year), ("MONTH", pc.month), ("DAY", pc.day)):
+        ty, vals = X.evaluate(E.date_part(part, col("a", t.schema)), t.schema, t.cols)
+        want = [None if x is None else float(x) for x in f(at["a"]).to_pylist()]
+        assert ty == "Float64" and vals == want, part
+
+
+def test_kleene_logic_matches_arrow():
+    vs = [True, False, None]
+    a = [x for x in vs for _ in vs]
+    b = [y for _ in vs for y in vs]
+    schema = [{"name": "a", "type": "Boolean"}, {"name": "b", "type": "Boolean"}]
+    cols = {"a": a, "b": b}
+    A, Bc = col("a", schema), col("b", schema)
+    assert X.evaluate(binary(A, Op.And, Bc), schema, cols)[1] == pc.and_kleene(pa.array(a), pa.array(b)).to_pylist()
+    assert X.evaluate(binary(A, Op.Or, Bc), schema, cols)[1] == pc.or_kleene(pa.array(a), pa.array(b)).to_pylist()
+    assert X.evaluate(E.not_(A), schema, cols)[1] == pc.invert(pa.array(a)).to_pylist()
+    assert X.evaluate(E.is_null(A), schema, cols)[1] == [x is None for x in a]
+    assert X.evaluate(E.is_not_null(A), schema, cols)[1] == [x is not None for x in a]
+
+
+def test_float_comparisons_use_the_total_order():
+    nan = float("nan")
+    assert one(binary(lit(nan), Op.Eq, lit(nan)))[1] is True
+    assert one(binary(lit(-0.0), Op.Lt, lit(0.0)))[1] is True
+    assert one(binary(lit(-0.0), Op.Eq, lit(0.0)))[1] is False
+    assert one(binary(lit(float("inf")), Op.Lt, lit(nan)))[1] is True
+    assert one(binary(lit(2**53 + 1, "Int64"), Op.Eq, lit(float(2**53))))[1] is True      # the integer side is cast: 2^53 + 1 -> 2^53
+
+
+# ------------------------------------------------------------------------------------------------ hand-computed answers
+DIV_KATS = [   # l / r: scale s1 + 4, precision p1 + 4 + s2, value l * 10^(4 + s2) / r truncated toward zero
+    (dl(100, 15, 2), dl(300, 15, 2), [21, 6], 333333),            #  1.00 /  3.00: 100 * 10^6 / 300 = 333333.33..  ->  0.333333
+    (dl(-100, 15, 2), dl(300, 15, 2), [21, 6], -333333),          # -1.00 /  3.00: toward zero, not floor
+    (dl(100, 15, 2), dl(-300, 15, 2), [21, 6], -333333),          #  1.00 / -3.00
+    (dl(-700, 15, 2), dl(-200, 15, 2), [21, 6], 3500000),         # -7.00 / -2.00: 700 * 10^6 / 200 = 3500000  ->  3.500000
+    (dl(200, 15, 2), dl(300, 15, 2), [21, 6], 666666),            #  2.00 /  3.00: 666666.67 truncates, does not round
+    (dl(-200, 15, 2), dl(300, 15, 2), [21, 6], -666666),
+    (dl(1, 15, 2), dl(99999999999999, 15, 2), [21, 6], 0),        #  0.01 / 999999999999.99: 10^6 / 99999999999999 = 0
+    (dl(7, 9, 0), dl(2, 9, 3), [16, 4], 35000000),                #  7 / 0.002: k = 4 + 3, 7 * 10^7 / 2  ->  3500.0000
+    (dl(-7, 9, 0), dl(2, 9, 3), [16, 4], -35000000),
+    (dl(123, 15, 2), dl(0, 15, 2), [21, 6], None),                #  x / 0 -> NULL
+]
+MOD_KATS = [   # l % r at scale max(s1, s2), sign of the dividend
+    (dl(750, 15, 2), dl(200, 15, 2), [15, 2], 150),               #  7.50 %  2.00 =  1.50
+    (dl(-750, 15, 2), dl(200, 15, 2), [15, 2], -150),             # -7.50 %  2.00 = -1.50
+    (dl(750, 15, 2), dl(-200, 15, 2), [15, 2], 150),              #  7.50 % -2.00 =  1.50
+    (dl(-750, 15, 2), dl(-200, 15, 2), [15, 2], -150),
+    (dl(600, 15, 2), dl(300, 15, 2), [15, 2], 0),
+    (dl(75, 9, 1), dl(200, 9, 3), [9, 3], 100),                   #  7.5 % 0.200: 7500 % 200 = 100  ->  0.100; precision min(8, 6) + 3
+    (dl(-75, 9, 1), dl(200, 9, 3), [9, 3], -100),
+    (dl(75, 9, 1), dl(0, 9, 3), [9, 3], None),                    #  x % 0 -> NULL
+]
+DOWN_KATS = [  # a cast that reduces the scale rounds half away from zero
+    (dl(250, 15, 2), (13, 0), 3), (dl(-250, 15, 2), (13, 0), -3),         #  2.50 ->  3, -2.50 -> -3
+    (dl(249, 15, 2), (13, 0), 2), (dl(-249, 15, 2), (13, 0), -2),         #  2.49 ->  2
+    (dl(50, 15, 2), (13, 0), 1), (dl(-50, 15, 2), (13, 0), -1), (dl(49, 15, 2), (13, 0), 0), (dl(-49, 15, 2), (13, 0), 0),
+    (dl(12345, 18, 4), (16, 2), 123), (dl(12350, 18, 4), (16, 2), 124), (dl(-12350, 18, 4), (16, 2), -124), (dl(-12349, 18, 4), (16, 2), -123),
+]
+TWICE = 2**64 + 2**63 + 2**11 + 1      # between 2^64 + 2^63 and 2^64 + 2^63 + 4096 (the spacing of doubles there), above the midpoint by 1
+F64_KATS = [   # float(int) / 10.0**s
+    (dl(TWICE, 20, 0), float(2**64 + 2**63 + 4096)),              # one rounding goes up; hi * 2^64 + lo rounds lo to 2^63 first and loses the 1
+    (dl(-TWICE, 20, 0), -float(2**64 + 2**63 + 4096)),
+    (dl(TWICE, 22, 2), float(2**64 + 2**63 + 4096) / 100.0),
+    (dl(2**53 + 1, 18, 0), float(2**53)),                         # a tie: to even
+    (dl(2**53 + 3, 18, 0), float(2**53 + 4)),
+    (dl(-(2**53 + 1), 18, 0), -float(2**53)),
+    (dl(12345, 15, 2), 123.45), (dl(-1, 15, 2), -0.01), (dl(10**38 - 1, 38, 0), 1e38), (dl(-(10**38 - 1), 38, 6), -1e38 / 1e6),
+]
+
+
+def test_decimal_division_known_answers():
+    assert len(DIV_KATS) >= 6
+    for l, r, ps, want in DIV_KATS:
+        assert one(binary(l, Op.Divide, r)) == ({"Decimal128": ps}, want), (l, r)
+
+
+def test_decimal_modulo_known_answers():
+    assert len(MOD_KATS) >= 6
+    for l, r, ps, want in MOD_KATS:
+        assert one(binary(l, Op.Modulo, r)) == ({"Decimal128": ps}, want), (l, r)
+
+
+def test_scale_reducing_cast_known_answers():
+    for e, (p, s), want in DOWN_KATS:
+        assert one(cast(e, ("Decimal128", p, s))) == ({"Decimal128": [p, s]}, want), e
+
+
+def test_decimal_to_float64_known_answers():
+    assert float(TWICE) == float(2**64 + 2**63 + 4096) and float(2**64) * 1.0 + float(2**63 + 2**11 + 1) == float(2**64 + 2**63)
+    for e, want in F64_KATS:
+        t, v = one(cast(e, "Float64"))
+        assert t == "Float64" and X.f64_bits(v) == X.f64_bits(want), (e, v, want)
+
+
+def test_overflow_is_reported_not_wrapped():
+    big = 10**38 - 1
+    assert one(binary(dl(big, 38, 6), Op.Divide, dl(10**8, 38, 4)))[1] is X.OVERFLOW           # big * 10^8 >= 2^127
+    assert one(binary(dl(big, 38, 0), Op.Plus, dl(1, 38, 0)))[1] is X.OVERFLOW                 # 10^38 needs 39 digits
+    assert one(binary(dl(big, 38, 0), Op.Plus, dl(-1, 38, 0)))[1] == big - 1
+    assert one(binary(dl(10**19, 20, 0), Op.Multiply, dl(10**19, 20, 0)))[1] is X.OVERFLOW     # 10^38
+    assert one(binary(dl(10**19, 20, 0), Op.Multiply, dl(10**18, 20, 0)))[1] == 10**37
+    assert one(binary(dl(big, 38, 0), Op.Lt, dl(1, 38, 2)))[1] is X.OVERFLOW                   # big * 10^2 for the comparison
+    assert one(E.is_null(binary(dl(big, 38, 0), Op.Plus, dl(1, 38, 0))))[1] is X.OVERFLOW      # sticky
+    assert one(binary(dl(big, 38, 0), Op.Plus, lit(None, ("Decimal128", 38, 0))))[1] is None
+
+
+def test_substr_counts_characters():
+    schema = [{"name": "s", "type": "Utf8"}]
+    cols = {"s": ["éabc", "abc", "", None, "日本語x"]}
+    assert X.evaluate(E.substr(col("s", schema), 3, 1), schema, cols) == ("Utf8", ["b", "c", "", None, "語"])
+    assert X.evaluate(E.substr(col("s", schema), 2), schema, cols) == ("Utf8", ["abc", "bc", "", None, "本語x"])
+    assert X.evaluate(E.substr(col("s", schema), 1, 0), schema, cols) == ("Utf8", ["", "", "", None, ""])
+
+
+# ------------------------------------------------------------------------------------------------ the tables of the device test
+@pytest.mark.parametrize("name", K.TABLES)
+def test_extreme_tables_hold_no_overflow_row_and_types_agree_with_the_compiler(name):
+    """Outside the overflow plans the reference marks zero rows OVERFLOW; the compiler declares the reference's result types."""
+    t, exprs = K.table_and_exprs(name)
+    ref = K.reference(name)
+    assert t.n % 64 != 0 and all(any(v is None for v in t.cols[c]) for c in ("a", "b", "f"))
+    assert sum(v is X.OVERFLOW for _, vals in ref.values() for v in vals) == 0
+    for n, e in exprs:
+        d = B.compile_check({"op": "project", "input": {"fields": t.schema}, "exprs": [{"expr": E.rebind(e, t.schema), "name": n}]})
+        assert d["outputs"][0]["type"] == type_name(ref[n][0]), n
+
+
+def type_name(t):
+    return t if isinstance(t, str) else "Decimal128(%d,%d)" % tuple(t["Decimal128"])
+
+
+def test_overflow_plans_hold_nothing_but_overflow():
+    for n, t, e in K.overflow_cases():
+        _, vals = X.evaluate(e, t.schema, t.cols)
+        assert all(v is X.OVERFLOW or v is None for v in vals) and sum(v is X.OVERFLOW for v in vals) >= t.n - 2, n
+
+
+def test_boundary_vectors_hold_what_they_claim():
+    assert {2**63 - 1, 2**63, 2**63 + 1, -(2**63) - 1} <= set(K.dec_vector(19)) and 2**64 not in K.dec_vector(19)
+    assert {2**64 - 1, 2**64, 2**64 + 1, 2**64 * 4 + K.PATTERN, -(2**64 + K.PATTERN)} <= set(K.dec_vector(20))
+    assert {10**38 - 1, -(10**38 - 1), 2**64 * (2**62 - 1) + K.PATTERN} <= set(K.dec_vector(38))
+    assert {-2**63, 2**63 - 1, 2**53 + 1, -2**31 - 1, 2**32 + 1} <= set(K.int_vector("Int64"))
+    assert K.int_vector("UInt8")[:-1] == [0, 1, 254, 255] and K.int_vector("Int8")[:-1] == [-128, -127, -1, 0, 1, 126, 127]
+    assert {K._days(2000, 2, 29), K._days(1900, 2, 28), K._days(1900, 3, 1), K._days(2400, 2, 29), -719162, 2932896} <= set(K.date_vector())
+    assert math.isnan(K.FLOATS[2]) and K.FLOATS[5] == 5e-324
+
+
+def test_each_late_overflow_plan_overflows_in_one_place():
+    """The sum, the difference and the product cases overflow in the checked instruction itself: their operands fit their types, the
+    sums and differences fit 128 bits but not 38 digits, the products lie between 10^38 and 2^127."""
+    cases = {n: (t, e) for n, t, e in K.overflow_cases()}
+    for n, f in (("add_38_digits", lambda a, b: a + b), ("sub_38_digits", lambda a, b: a - b), ("mul_between_38_digits_and_127_bits", lambda a, b: a * b)):
+        t, _ = cases[n]
+        p = t.schema[2]["type"]["Decimal128"][0]
+        rows = [(a, b) for a, b in zip(t.cols["a"], t.cols["b"]) if a is not None and b is not None]
+        assert all(abs(a) < 10**p and abs(b) < 10**p and abs(f(a, b)) >= 10**38 for a, b in rows), n
+        if n.startswith("mul"):
+            assert all(abs(a * b) < 2**127 for a, b in rows)
+        else:
+            assert any(abs(f(a, b)) < 2**127 for a, b in rows) and any(abs(f(a, b)) == 10**38 for a, b in rows)
+
+
+def test_decimal_to_integer_cast_known_answers():
+    """To scale 0 as a decimal cast does (half away from zero), then as an integer cast: wraps."""
+    for e, to, want in ((dl(250, 15, 2), "Int32", 3), (dl(-250, 15, 2), "Int32", -3), (dl(249, 15, 2), "Int64", 2), (dl(-49, 15, 2), "Int8", 0),
+                        (dl(12850, 15, 2), "Int8", -127),                 # 128.50 -> 129 -> 129 - 256
+                        (dl(25549, 15, 2), "UInt8", 255), (dl(25550, 15, 2), "UInt8", 0), (dl(-100, 15, 2), "UInt8", 255),
+                        (dl(2**63 * 10, 25, 1), "Int64", -2**63), (dl(10**19, 20, 0), "Int64", 10**19 - 2**64)):
+        assert one(cast(e, to)) == (to, want), (e, to)
