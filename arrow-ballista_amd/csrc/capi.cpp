@@ -215,11 +215,11 @@ struct ProfTotal {
   ~ProfTotal() { if (on) { (void)hipEventRecord(op->ev3, s); op->ev_total_pending = true; } }
 };
 
-// Route the next launch of sink kernel `kernel_id` to the hiprtc-specialised function when the context's
-// policy asks for it.  force: failures are errors.  auto: fall back to the (always present) interpreter kernels.
-struct JitScope {
-  bool active = false;
-  JitScope(gpuq_op* op, const CompiledProgram& cp, int kernel_id, i64 n, const std::string& spec = std::string()) {
+// Resolve the hiprtc-specialised function of sink `kernel_id` (GPUQ_SINK_*) when the context's policy asks for it: `fn` is what the
+// sink's launcher runs, nullptr = its AOT kernel.  force: failures are errors.  auto: fall back to the (always present) interpreter kernels.
+struct SinkJit {
+  void* fn = nullptr;
+  SinkJit(gpuq_op* op, const CompiledProgram& cp, int kernel_id, i64 n, const std::string& spec = std::string()) {
     gpuq_ctx* c = op->ctx;
     if (cp.jit_src.empty() || c->jit_mode == 0) return;
     const bool big = c->jit_mode == 1 && n >= c->jit_min_rows;
@@ -244,13 +244,12 @@ struct JitScope {
         if (f) op->jit_fns[fkey] = f;
       }
       if (!f) return;
-      jit_override().fn = f->fn; jit_override().kernel_id = kernel_id; active = true; c->jit_launches++;
+      fn = f->fn; c->jit_launches++;
     } catch (const std::exception& e) {
       if (c->jit_mode == 2) throw Unsupported(e.what());
       c->last_jit_error = e.what();
     }
   }
-  ~JitScope() { jit_override().fn = nullptr; jit_override().kernel_id = 0; }
 };
 
 // ---------------------------------------------------------------- key layout
@@ -832,7 +831,7 @@ int gpuq_compile_jit_source(const char* json, int kernel_id, char* buf, size_t c
     compile_op(op, d);
     g_upload = true;
     std::string eval = op->prog.jit_src;
-    if (kernel_id == 3 && op->kind == K_AGG) eval += agg_tiny_spec(op, (int)d.get_i64("jit_gmax", 4));   // what the run-time path appends
+    if (kernel_id == GPUQ_SINK_AGG_TINY && op->kind == K_AGG) eval += agg_tiny_spec(op, (int)d.get_i64("jit_gmax", 4));   // what the run-time path appends
     const std::string src = jit_full_source(eval, kernel_id);
     if (src.size() + 1 > cap) throw Capacity("source needs " + std::to_string(src.size() + 1) + " bytes");
     std::memcpy(buf, src.c_str(), src.size() + 1);
@@ -934,7 +933,7 @@ int gpuq_filter_run(gpuq_op* op, void* stream, const gpuq_input* in, int payload
     u64* bitmap = (u64*)op->ws[0].ensure((size_t)nwords * 8);
     uint32_t* counts = (uint32_t*)op->ws[1].ensure((size_t)nblocks * 4 + 16);
     u64* total = count_out ? (u64*)count_out : (u64*)op->ws[2].ensure(8);
-    { JitScope js(op, op->prog, 1, n); ProfScope ps(op, s); launch_filter_bitmap(s, P, n, bitmap, counts, nblocks, wpb); }
+    { SinkJit jit(op, op->prog, GPUQ_SINK_FILTER_BITMAP, n); ProfScope ps(op, s); launch_filter_bitmap(s, jit.fn, P, n, bitmap, counts, nblocks, wpb); }
     launch_scan_block_counts(s, counts, nblocks, total);
     if (sel_out) launch_compact(s, bitmap, counts, nblocks, wpb, n, payload_via > 0 ? in->via[payload_via - 1] : nullptr, sel_out);
     HIPCHECK(hipGetLastError());
@@ -952,7 +951,7 @@ int gpuq_project_run(gpuq_op* op, void* stream, const gpuq_input* in, gpuq_colum
     DevProgram P = bind_program(op->prog, op->in_schema, op->code_dev.as<DevCode>(), op->flags_dev.as<uint32_t>(), in);
     OutSpec O = make_outspec(op->prog, outs, n_outs, op->out_fields);
     for (int i = 0; i < n_outs; ++i) outs[i].length = in->n_rows;
-    { JitScope js(op, op->prog, 2, in->n_rows); ProfScope ps(op, s); launch_project(s, P, in->n_rows, O); }
+    { SinkJit jit(op, op->prog, GPUQ_SINK_PROJECT, in->n_rows); ProfScope ps(op, s); launch_project(s, jit.fn, P, in->n_rows, O); }
     HIPCHECK(hipGetLastError());
     // a projection is otherwise never read back; one that holds checked decimal arithmetic must not hand out a wrapped value (a deferred
     // run's status word is read when it is settled)
@@ -1021,7 +1020,7 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         const int no = (int)pc.prog.out_reg.size();
         std::vector<gpuq_field_info> fi(op->out_fields.begin() + pc.first_out, op->out_fields.begin() + pc.first_out + no);
         OutSpec O = make_outspec(pc.prog, outs + pc.first_out, no, fi);
-        { JitScope js(op, pc.prog, 2, rows); launch_project(s, PP, rows, O); }
+        { SinkJit jit(op, pc.prog, GPUQ_SINK_PROJECT, rows); launch_project(s, jit.fn, PP, rows, O); }
       }
     };
     // ---- the launch sequences, one per strategy: the synchronous form (reset: the status word is cleared first and read afterwards) and
@@ -1034,7 +1033,7 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
       if (reset) reset_flags(op, s);
       // the LDS aggregate is specialised on its whole shape (keys, accumulators, group capacity)
       const std::string spec = agg_tiny_spec(op, gmax);
-      { JitScope js(op, op->prog, 3, n, spec); ProfScope ps(op, s); launch_agg_tiny(s, P, n, op->agg, gmax, wsp); }
+      { SinkJit jit(op, op->prog, GPUQ_SINK_AGG_TINY, n, spec); ProfScope ps(op, s); launch_agg_tiny(s, jit.fn, P, n, op->agg, gmax, wsp); }
       launch_agg_tiny_merge(s, P, n, op->agg, gmax, wsp, raw);
     };
     // global hash table (path 2) of est * slot_pct / 100 slots (rounded up to a power of two), filled by the block-local kernel (use_lds:
@@ -1052,9 +1051,9 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         u64* fstage = nullptr;
         const size_t fbytes = (size_t)T.n_slots * (size_t)n_fsum * (size_t)agg_lds_grid(n) * 8;
         if (n_fsum > 0 && fbytes <= ((size_t)256 << 20)) { fstage = (u64*)op->ws[8].ensure(fbytes); HIPCHECK(hipMemsetAsync(fstage, 0, fbytes, s)); }
-        JitScope js(op, op->prog, 13, n); ProfScope ps(op, s); launch_agg_lds(s, P, n, op->keys, op->agg, T, fstage, n_fsum);
+        SinkJit jit(op, op->prog, GPUQ_SINK_AGG_LDS, n); ProfScope ps(op, s); launch_agg_lds(s, jit.fn, P, n, op->keys, op->agg, T, fstage, n_fsum);
       }
-      else { JitScope js(op, op->prog, 4, n); ProfScope ps(op, s); launch_agg_hash(s, P, n, op->keys, op->agg, T); }
+      else { SinkJit jit(op, op->prog, GPUQ_SINK_AGG_HASH, n); ProfScope ps(op, s); launch_agg_hash(s, jit.fn, P, n, op->keys, op->agg, T); }
     };
     // radix-partitioned (path 3).  High cardinality: partition the rows by key hash into buckets whose groups fit an LDS table, aggregate
     // every bucket inside one block (kernels_hash.hip).  false: on to the global table -- a bucket overflowed (skew, or more groups than
@@ -1078,7 +1077,7 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         void* lws = b_look.ensure(lwb);
         uint32_t* bounds = (uint32_t*)b_bounds.ensure((size_t)(nbk + 2) * 4);
         reset_flags(op, s);
-        { JitScope js(op, op->prog, 11, n); launch_agg_bucket_id(s, P, n, op->keys, nbk - 1, bid, nullptr); }
+        { SinkJit jit(op, op->prog, GPUQ_SINK_AGG_BUCKET_ID, n); launch_agg_bucket_id(s, jit.fn, P, n, op->keys, nbk - 1, bid, nullptr); }
         const int npass = std::max(1, (bits + 7) / 8);
         launch_radix_ghist(s, bid, n, 32, npass, ghist);
         for (int p = 0; p < npass; ++p) {
@@ -1087,7 +1086,7 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         }
         launch_bucket_bounds(s, bid, n, nbk, bounds, 32);
         alloc_raw((i64)std::min<u64>((u64)std::max<i64>(n, 1), std::max<u64>(est + est / 4, 1ull << 20)));
-        { JitScope js(op, op->prog, 12, n); ProfScope ps(op, s); launch_agg_bucket(s, P, op->keys, op->agg, ids, bounds, (uint32_t)nbk, capslots, slot_words, raw); }
+        { SinkJit jit(op, op->prog, GPUQ_SINK_AGG_BUCKET, n); ProfScope ps(op, s); launch_agg_bucket(s, jit.fn, P, op->keys, op->agg, ids, bounds, (uint32_t)nbk, capslots, slot_words, raw); }
         HIPCHECK(hipGetLastError());
         uint32_t fw[4] = {0, 0, 0, 0};
         read_status(op, s, fw, 4);
@@ -1360,7 +1359,7 @@ static int join_build_impl(gpuq_op* op, void* stream, const gpuq_input* in, int 
       const u64 init[3] = {0x7FFFFFFFFFFFFFFFull, 0x8000000000000000ull, 0};
       const i64 wstep = guess ? std::max<i64>(1, ((n + 63) >> 6) >> 12) : 1;
       HIPCHECK(hipMemcpyAsync(kr, init, sizeof(init), hipMemcpyHostToDevice, s));
-      { JitScope js(op, op->prog, 14, n); launch_join_keyrange(s, P, n, op->keys, op->null_eq, kr, wstep); }
+      { SinkJit jit(op, op->prog, GPUQ_SINK_JOIN_KEYRANGE, n); launch_join_keyrange(s, jit.fn, P, n, op->keys, op->null_eq, kr, wstep); }
       HIPCHECK(hipGetLastError());
       u64 got[3];
       HIPCHECK(hipMemcpyAsync(got, kr, sizeof(got), hipMemcpyDeviceToHost, s));
@@ -1408,7 +1407,7 @@ static int join_build_impl(gpuq_op* op, void* stream, const gpuq_input* in, int 
       if (!dense) launch_ht_init(s, t->T, nullptr);
       if (!memo) reset_flags(op, s);
       if (rows_out) HIPCHECK(hipMemsetAsync(rows_out, 0, 8, s));      // (a build that is redone counts its survivors again)
-      { JitScope js(op, op->prog, 5, n, semi_spec(t->T, present)); ProfScope ps(op, s); if (!launch_join_build(s, P, n, op->keys, t->T, next, present, payload_via, op->null_eq, semi_p)) throw Unsupported("join build over a semi table: more than 8 input columns without the specialised kernel"); }
+      { SinkJit jit(op, op->prog, GPUQ_SINK_JOIN_BUILD, n, semi_spec(t->T, present)); ProfScope ps(op, s); if (!launch_join_build(s, jit.fn, P, n, op->keys, t->T, next, present, payload_via, op->null_eq, semi_p)) throw Unsupported("join build over a semi table: more than 8 input columns without the specialised kernel"); }
       HIPCHECK(hipGetLastError());
     };
     build();
@@ -1507,8 +1506,8 @@ int gpuq_join_probe_run(gpuq_op* op, void* stream, gpuq_join_table* t, const gpu
         if (want_build) seg_build = (uint32_t*)op->ws[0].ensure((size_t)rsegs * rwpw * 256 + 16);
         seg_probe = (uint32_t*)op->ws[1].ensure((size_t)rsegs * rwpw * 256 + 16);
         counts = (uint32_t*)op->ws[2].ensure((size_t)rsegs * 4 + 16);
-        JitScope js(op, op->prog, 15, n); ProfScope ps(op, s);
-        launch_rj_partition(s, P, n, op->keys, t->T, payload_via, g, rec, rec2, hist, sws, swb);
+        SinkJit jit(op, op->prog, GPUQ_SINK_RJ_PACK, n); ProfScope ps(op, s);
+        launch_rj_partition(s, jit.fn, P, n, op->keys, t->T, payload_via, g, rec, rec2, hist, sws, swb);
         launch_rj_probe(s, rec2, hist + (size_t)g.nparts * g.nblocks, t->T, jt, seg_build, seg_probe, counts, rblocks, rwpw);
         launch_scan_block_counts(s, counts, rsegs, (u64*)count_out);
         launch_copy_segments(s, seg_build, seg_probe, counts, rsegs, rwpw, n, (const u64*)count_out, out_build, out_probe, out_cap, op->flags_dev.as<uint32_t>());
@@ -1518,18 +1517,18 @@ int gpuq_join_probe_run(gpuq_op* op, void* stream, gpuq_join_table* t, const gpu
       std::string spec;
       if (op->keys.n_keys == 1 && op->keys.key_words == 1 && (t->T.slot_words == 2 || t->T.dense))     // one narrow key: 16-byte slots or direct addressing
         spec = "#define GPUQ_JIT_PROBE1 1\nconstexpr int JIT_KEY_REG0 = " + std::to_string(op->keys.key_reg[0]) + ";\n";
-      { JitScope js(op, op->prog, 7, n, spec);
+      { SinkJit jit(op, op->prog, GPUQ_SINK_JOIN_PROBE_UNIQUE, n, spec);
         // the profile events bracket the probe kernel alone (what rocprofv3 reports for it); the 30 us scan of the segment counts and
         // the compaction of the segments (20-50 us) follow outside the bracket
-        { ProfScope ps(op, s); launch_join_probe_unique(s, P, n, op->keys, t->T, jt, op->null_eq, payload_via, seg_build, seg_probe, counts, nsegs, wpw, visited); }
+        { ProfScope ps(op, s); launch_join_probe_unique(s, jit.fn, P, n, op->keys, t->T, jt, op->null_eq, payload_via, seg_build, seg_probe, counts, nsegs, wpw, visited); }
         launch_scan_block_counts(s, counts, nsegs, (u64*)count_out);
         if (out_probe) launch_copy_segments(s, seg_build, seg_probe, counts, nsegs, wpw, n, (const u64*)count_out, out_build, out_probe, out_cap, op->flags_dev.as<uint32_t>()); }
       HIPCHECK(hipGetLastError());
       return;
     }
     HIPCHECK(hipMemsetAsync(count_out, 0, 8, s));
-    { JitScope js(op, op->prog, 6, in->n_rows); ProfScope ps(op, s);
-      launch_join_probe(s, P, in->n_rows, op->keys, t->T, t->next.as<uint32_t>(), jt, payload_via, op->null_eq, out_build, out_probe, out_cap, (u64*)count_out, visited); }
+    { SinkJit jit(op, op->prog, GPUQ_SINK_JOIN_PROBE, in->n_rows); ProfScope ps(op, s);
+      launch_join_probe(s, jit.fn, P, in->n_rows, op->keys, t->T, t->next.as<uint32_t>(), jt, payload_via, op->null_eq, out_build, out_probe, out_cap, (u64*)count_out, visited); }
     HIPCHECK(hipGetLastError());
   });
 }
@@ -1571,7 +1570,7 @@ static SortPack sort_key_plan(gpuq_op* op, hipStream_t s, const DevProgram& P, i
     const i64 n_seen = wstep > 1 ? ((((n + 63) >> 6) + wstep - 1) / wstep + 1) << 6 : n;
     const int mb = sort_minmax_blocks(n_seen);
     u64* mm = (u64*)op->ws[0].ensure((size_t)mb * MAX_SORT_KEYS * 5 * 8);
-    { JitScope js(op, op->prog, 8, n); launch_sort_minmax(s, P, n, S, mm, mb, wstep); }
+    { SinkJit jit(op, op->prog, GPUQ_SINK_SORT_MINMAX, n); launch_sort_minmax(s, jit.fn, P, n, S, mm, mb, wstep); }
     std::vector<u64> hmm((size_t)mb * MAX_SORT_KEYS * 5);
     HIPCHECK(hipMemcpyAsync(hmm.data(), mm, hmm.size() * 8, hipMemcpyDeviceToHost, s));
     // the pass has evaluated the key expressions of every row it saw: what they could not do (a Utf8 value beyond the 15 bytes a
@@ -1732,7 +1731,7 @@ static void sort_with_plan(gpuq_op* op, hipStream_t s, const DevProgram& P, cons
     // gpuq_sort_run_keys: one integer-like key whose field IS value - base (no string shift), at most one 64-bit word of composite
     const int dec_width = (op->sort_dec.data && S.n_keys == 1 && S.kind[0] == 0 && K.rshift[0] == 0 && total >= 1 && total <= 64 && !small) ? type_width(op->sort_key0) : 0;
     const bool decode = dec_width == 1 || dec_width == 2 || dec_width == 4 || dec_width == 8 || (dec_width == 16 && op->sort_key0.id == T_DECIMAL128);
-    { JitScope js(op, op->prog, 9, n); launch_sort_pack(s, P, n, S, K, klo, khi, ids, small || total == 0 ? nullptr : ghist, np_all); }
+    { SinkJit jit(op, op->prog, GPUQ_SINK_SORT_PACK, n); launch_sort_pack(s, jit.fn, P, n, S, K, klo, khi, ids, small || total == 0 ? nullptr : ghist, np_all); }
     if (small) {      // one block sorts it in LDS: no histogram / scan / scatter launches
       launch_sort_small(s, klo, khi, ids, n, perm_out);
       HIPCHECK(hipGetLastError());
@@ -1804,7 +1803,7 @@ int gpuq_merge_run(gpuq_op* op, void* stream, const gpuq_input* in, const int64_
     uint32_t* ids = (uint32_t*)op->ws[4].ensure((size_t)n * 4);
     uint32_t* ids2 = (uint32_t*)op->ws[5].ensure((size_t)n * 4);
     ProfScope ps(op, s);
-    { JitScope js(op, op->prog, 9, n); launch_sort_pack(s, P, n, op->sort, K, klo, khi, ids, nullptr, 0); }
+    { SinkJit jit(op, op->prog, GPUQ_SINK_SORT_PACK, n); launch_sort_pack(s, jit.fn, P, n, op->sort, K, klo, khi, ids, nullptr, 0); }
     // runs -> pairs, round by round (empty runs drop out; an odd run is carried as a pair with an empty right side)
     std::vector<i64> bounds; bounds.push_back(0);
     for (int r = 0; r < n_runs; ++r) if (run_offsets[r + 1] > run_offsets[r]) bounds.push_back(run_offsets[r + 1]);
@@ -1853,7 +1852,7 @@ int gpuq_partition_run(gpuq_op* op, void* stream, const gpuq_input* in, uint32_t
     const size_t lwb = onesweep_ws_bytes(n);
     void* lws = op->ws[7].ensure(lwb);
     ProfScope ps(op, s);
-    { JitScope js(op, op->prog, 10, n); launch_part_pid(s, P, n, op->keys, np, pid, nullptr); }
+    { SinkJit jit(op, op->prog, GPUQ_SINK_PART_PID, n); launch_part_pid(s, jit.fn, P, n, op->keys, np, pid, nullptr); }
     launch_part_offsets(s, pid, n, np, counts, (u64*)part_offsets_out, 32);
     int bits = 0; while ((1u << bits) < np) ++bits;
     const int npass = std::max(1, (bits + 7) / 8);

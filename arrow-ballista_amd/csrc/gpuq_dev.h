@@ -122,15 +122,6 @@ __device__ __forceinline__ i64 rows_of(const DevProgram& P, const i64 n_bound) {
   return n_bound;
 }
 
-// launcher-side dispatch over the column-slot template parameter
-#define GPUQ_DISPATCH_MAXC(ncols, CALL)          \
-  do {                                           \
-    if ((ncols) <= 2) { CALL(2); }               \
-    else if ((ncols) <= 4) { CALL(4); }          \
-    else if ((ncols) <= 8) { CALL(8); }          \
-    else { CALL(16); }                           \
-  } while (0)
-
 constexpr uint32_t FLAG_STR_TRUNC = 1u;
 constexpr uint32_t FLAG_GROUP_OVERFLOW = 2u;
 constexpr uint32_t FLAG_TABLE_FULL = 4u;

@@ -1,6 +1,10 @@
 // Internal C++ launch interface between the C ABI (capi.cpp) and the HIP kernels.
 #pragma once
 #include "gpuq_dev.h"
+#ifndef GPUQ_JIT
+#include <type_traits>
+#include "devbuf.h"      // HIPCHECK (launch_sink)
+#endif
 
 namespace gpuq {
 
@@ -107,40 +111,78 @@ struct AggSoA {
 // deferred execution: up to 64 device words gathered into one contiguous block (gpuq_ops_settle)
 struct GatherWords { int32_t n; int32_t pad; const u64* src[64]; };
 
+// ----- sinks: the kernels that evaluate a compiled expression program.  Each exists as the AOT template k_X<MAXC> and as a
+// hiprtc-specialised gpuq_jit_entry (the same .hip text under GPUQ_JIT_KERNEL == id).  The ids are ABI (gpuq_compile_jit_source,
+// gpuq_op_jit_source); GPUQ_SINKS below gives each its source file and entry-point name.
+#define GPUQ_SINK_FILTER_BITMAP 1
+#define GPUQ_SINK_PROJECT 2
+#define GPUQ_SINK_AGG_TINY 3
+#define GPUQ_SINK_AGG_HASH 4
+#define GPUQ_SINK_JOIN_BUILD 5
+#define GPUQ_SINK_JOIN_PROBE 6
+#define GPUQ_SINK_JOIN_PROBE_UNIQUE 7
+#define GPUQ_SINK_SORT_MINMAX 8
+#define GPUQ_SINK_SORT_PACK 9
+#define GPUQ_SINK_PART_PID 10
+#define GPUQ_SINK_AGG_BUCKET_ID 11
+#define GPUQ_SINK_AGG_BUCKET 12
+#define GPUQ_SINK_AGG_LDS 13
+#define GPUQ_SINK_JOIN_KEYRANGE 14
+#define GPUQ_SINK_RJ_PACK 15
+
 #ifndef GPUQ_JIT
 // ---- host launch interface (AOT build only)
+struct SinkInfo { int id; const char* file; const char* entry; };
+constexpr SinkInfo GPUQ_SINKS[] = {
+    {GPUQ_SINK_FILTER_BITMAP, "kernels_scan.hip", "gpuq_jit_filter_bitmap"},
+    {GPUQ_SINK_PROJECT, "kernels_scan.hip", "gpuq_jit_project"},
+    {GPUQ_SINK_AGG_TINY, "kernels_scan.hip", "gpuq_jit_agg_tiny"},
+    {GPUQ_SINK_AGG_HASH, "kernels_hash.hip", "gpuq_jit_agg_hash"},
+    {GPUQ_SINK_JOIN_BUILD, "kernels_hash.hip", "gpuq_jit_join_build"},
+    {GPUQ_SINK_JOIN_PROBE, "kernels_hash.hip", "gpuq_jit_join_probe"},
+    {GPUQ_SINK_JOIN_PROBE_UNIQUE, "kernels_hash.hip", "gpuq_jit_join_probe_unique"},
+    {GPUQ_SINK_SORT_MINMAX, "kernels_sort.hip", "gpuq_jit_sort_minmax"},
+    {GPUQ_SINK_SORT_PACK, "kernels_sort.hip", "gpuq_jit_sort_pack"},
+    {GPUQ_SINK_PART_PID, "kernels_sort.hip", "gpuq_jit_part_pid"},
+    {GPUQ_SINK_AGG_BUCKET_ID, "kernels_hash.hip", "gpuq_jit_agg_bucket_id"},
+    {GPUQ_SINK_AGG_BUCKET, "kernels_hash.hip", "gpuq_jit_agg_bucket"},
+    {GPUQ_SINK_AGG_LDS, "kernels_hash.hip", "gpuq_jit_agg_lds"},
+    {GPUQ_SINK_JOIN_KEYRANGE, "kernels_hash.hip", "gpuq_jit_join_keyrange"},
+    {GPUQ_SINK_RJ_PACK, "kernels_hash.hip", "gpuq_jit_rj_pack"},
+};
+// The launchers of the sinks take `jit_fn`: the specialised function to run (capi.cpp's SinkJit resolves it), or nullptr for the AOT kernel.
 void launch_gather_words(hipStream_t s, const GatherWords& g, u64* out);
 void set_num_cus(int n);
 int num_cus();
-void launch_filter_bitmap(hipStream_t s, const DevProgram& P, i64 n, u64* bitmap, uint32_t* block_counts, int nblocks, i64 words_per_block);
+void launch_filter_bitmap(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, u64* bitmap, uint32_t* block_counts, int nblocks, i64 words_per_block);
 void launch_scan_block_counts(hipStream_t s, uint32_t* block_counts, int nblocks, u64* total_out);
 void launch_compact(hipStream_t s, const u64* bitmap, const uint32_t* block_offsets, int nblocks, i64 words_per_block, i64 n,
                     const uint32_t* sel_in, uint32_t* sel_out);
-void launch_project(hipStream_t s, const DevProgram& P, i64 n, const OutSpec& O);
+void launch_project(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const OutSpec& O);
 int agg_tiny_max_groups(int n_accs);
 size_t agg_tiny_workspace_bytes(int gmax, int n_keys, int n_accs, int* nblocks_out);
-void launch_agg_tiny(hipStream_t s, const DevProgram& P, i64 n, const AggSpec& A, int gmax, void* workspace);
+void launch_agg_tiny(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const AggSpec& A, int gmax, void* workspace);
 void launch_agg_tiny_merge(hipStream_t s, const DevProgram& P, i64 n, const AggSpec& A, int gmax, void* workspace, const AggOut& out);
 void launch_ht_init(hipStream_t s, const HashTable& T, const AggSpec* A);
-void launch_agg_hash(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, const AggSpec& A, const HashTable& T);
+void launch_agg_hash(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const AggSpec& A, const HashTable& T);
 void launch_key_sample(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, i64 stride, i64 nsample, uint32_t* bitmap, u64 nbits, unsigned long long* passed);
 uint32_t agg_lds_slots(const HashTable& T);
 int agg_lds_grid(i64 n);
-void launch_agg_lds(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, const AggSpec& A, const HashTable& T, u64* fstage, int n_fsum);
-void launch_agg_bucket_id(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, u64 bucket_mask, u64* bid, uint32_t* ids);
+void launch_agg_lds(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const AggSpec& A, const HashTable& T, u64* fstage, int n_fsum);
+void launch_agg_bucket_id(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, u64 bucket_mask, u64* bid, uint32_t* ids);
 void launch_bucket_bounds(hipStream_t s, const u64* sorted_bid, i64 n, u64 nbuckets, uint32_t* bounds, int shift);
-void launch_agg_bucket(hipStream_t s, const DevProgram& P, const KeySpec& K, const AggSpec& A, const uint32_t* ids, const uint32_t* bounds, uint32_t nbuckets,
+void launch_agg_bucket(hipStream_t s, void* jit_fn, const DevProgram& P, const KeySpec& K, const AggSpec& A, const uint32_t* ids, const uint32_t* bounds, uint32_t nbuckets,
                        uint32_t cap, int slot_words, const AggOut& out);
 void launch_agg_hash_extract(hipStream_t s, const KeySpec& K, const AggSpec& A, const HashTable& T, const AggOut& out, uint32_t* flags);
 // false: no interpreter kernel for this shape (chain fusion over more than 8 input columns)
-bool launch_join_build(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, uint32_t* next, uint32_t* present,
+bool launch_join_build(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, uint32_t* next, uint32_t* present,
                        int payload_via, int null_equals_null, const SemiProbe* semi = nullptr);
 // key range of the rows a join build would insert: out = {min (i64), max (i64), count (u64)}, pre-set by the caller to {INT64_MAX, INT64_MIN, 0}
-void launch_join_keyrange(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, int null_equals_null, u64* out, i64 wstep = 1);   // wstep > 1: every wstep-th 64-row word
+void launch_join_keyrange(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, int null_equals_null, u64* out, i64 wstep = 1);   // wstep > 1: every wstep-th 64-row word
 // unique build keys: every wave owns `wpw` consecutive 64-row words (segment g = words [g*wpw, (g+1)*wpw)) and writes its pairs, in probe
 // order, to seg_build / seg_probe starting at row g*wpw*64; seg_counts[g] = pairs of the segment.  launch_copy_segments then moves
 // the segments to their final places (seg_counts already scanned to exclusive offsets).
-void launch_join_probe_unique(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, int join_type, int null_equals_null, int payload_via,
+void launch_join_probe_unique(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, int join_type, int null_equals_null, int payload_via,
                               uint32_t* seg_build, uint32_t* seg_probe, uint32_t* seg_counts, int nsegs, i64 wpw, uint32_t* visited);
 void launch_copy_segments(hipStream_t s, const uint32_t* seg_build, const uint32_t* seg_probe, const uint32_t* seg_offsets, int nsegs, i64 wpw, i64 n,
                           const u64* total, uint32_t* out_build, uint32_t* out_probe, u64 out_cap, uint32_t* flags);
@@ -150,21 +192,21 @@ void launch_join_locality(hipStream_t s, const DevProgram& P, i64 n, const KeySp
 struct RjGeomHost { uint32_t nparts, shift; i64 tile; int32_t nblocks; };
 void rj_geometry(i64 n, u64 range, int slice_log2, RjGeomHost* g);
 size_t rj_hist_entries(const RjGeomHost& g);
-void launch_rj_partition(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, int payload_via, const RjGeomHost& g,
+void launch_rj_partition(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, int payload_via, const RjGeomHost& g,
                          u64* rec, u64* rec_out, int32_t* hist, void* scan_ws, size_t scan_ws_bytes);
 int rj_probe_geometry(i64 n, i64* wpw_out);
 void launch_rj_probe(hipStream_t s, const u64* rec, const int32_t* n_live, const HashTable& T, int join_type, uint32_t* seg_build, uint32_t* seg_probe,
                      uint32_t* seg_counts, int nblocks, i64 wpw);
 void launch_bitmap_select(hipStream_t s, const u64* present, const u64* visited, int matched, i64 nwords, i64 n, u64* bitmap,
                           uint32_t* block_counts, int nblocks, i64 wpb);
-void launch_join_probe(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, const uint32_t* next,
+void launch_join_probe(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, const uint32_t* next,
                        int join_type, int payload_via, int null_equals_null, uint32_t* out_build, uint32_t* out_probe,
                        u64 out_cap, u64* out_count, uint32_t* visited);
 int sort_minmax_blocks(i64 n);
-void launch_sort_minmax(hipStream_t s, const DevProgram& P, i64 n, const SortSpec& S, u64* out, int nblocks, i64 wstep = 1);   // wstep > 1: every wstep-th 64-row word only (a sample)
+void launch_sort_minmax(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const SortSpec& S, u64* out, int nblocks, i64 wstep = 1);   // wstep > 1: every wstep-th 64-row word only (a sample)
 int sort_max_passes();
-void launch_sort_pack(hipStream_t s, const DevProgram& P, i64 n, const SortSpec& S, const SortPack& K, u64* key_lo, u64* key_hi, uint32_t* ids, u64* hist, int hist_passes);
-void launch_part_pid(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, uint32_t nparts, u64* pid_out, uint32_t* ids);
+void launch_sort_pack(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const SortSpec& S, const SortPack& K, u64* key_lo, u64* key_hi, uint32_t* ids, u64* hist, int hist_passes);
+void launch_part_pid(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, uint32_t nparts, u64* pid_out, uint32_t* ids);
 void launch_part_offsets(hipStream_t s, const u64* pid, i64 n, uint32_t nparts, uint32_t* counts_ws, u64* offsets_out, int shift);
 void launch_counts_to_ghist(hipStream_t s, const uint32_t* counts, uint32_t np, u64* ghist);
 void launch_gather_u64(hipStream_t s, const u64* src, const uint32_t* idx, i64 n, u64* dst);
@@ -275,14 +317,21 @@ void launch_pq_copy_strings(hipStream_t s, const uint8_t* file, const uint8_t* d
 void launch_pq_dict_strings(hipStream_t s, const uint8_t* file, i64 src, int32_t bytes, int32_t n, int32_t* offsets, uint8_t* out, uint32_t* flags);
 void launch_pq_dict_fixed(hipStream_t s, const uint8_t* file, i64 src, int32_t n, int32_t phys, int32_t flba_len, int32_t width, uint8_t* out);
 
-// JIT redirection: while a JitOverride is alive on this thread, the next launch of the kernel family it
-// names goes to the hiprtc-compiled function instead of the AOT template instantiation.
-struct JitOverride { void* fn = nullptr; int kernel_id = 0; };
-JitOverride& jit_override();
-template <class... Args>
-inline hipError_t jit_launch(void* fn, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
-  void* a[] = {(void*)&args...};
-  return hipModuleLaunchKernel((hipFunction_t)fn, grid.x, grid.y, grid.z, block.x, block.y, block.z, (unsigned)lds, s, a, nullptr);
+// Launch a kernel that exists once per column-slot count: `pick(MaxC<M>{})` returns &k_X<M> (GPUQ_PICK(k_X) is that function), and
+// the instantiation is chosen from the program's n_cols.  With `jit_fn` the hiprtc-specialised entry of the same sink runs instead,
+// on the same arguments: it reads them as raw bytes, so they must have exactly the kernel's parameter types (the caller casts, once).
+template <int M> using MaxC = std::integral_constant<int, M>;
+#define GPUQ_PICK(KERNEL) [](auto M) { return &KERNEL<decltype(M)::value>; }
+template <class Pick, class... Args>
+inline void launch_sink(void* jit_fn, int n_cols, Pick pick, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
+  static_assert(std::is_same_v<decltype(pick(MaxC<2>{})), void (*)(Args...)>, "launch_sink: argument types differ from the kernel's parameter types");
+  if (jit_fn) {
+    void* a[] = {(void*)&args...};
+    HIPCHECK(hipModuleLaunchKernel((hipFunction_t)jit_fn, grid.x, grid.y, grid.z, block.x, block.y, block.z, (unsigned)lds, s, a, nullptr));
+  } else if (n_cols <= 2) hipLaunchKernelGGL(pick(MaxC<2>{}), grid, block, lds, s, args...);
+  else if (n_cols <= 4) hipLaunchKernelGGL(pick(MaxC<4>{}), grid, block, lds, s, args...);
+  else if (n_cols <= 8) hipLaunchKernelGGL(pick(MaxC<8>{}), grid, block, lds, s, args...);
+  else hipLaunchKernelGGL(pick(MaxC<16>{}), grid, block, lds, s, args...);
 }
 #endif  // GPUQ_JIT
 

@@ -6,6 +6,7 @@
 // one gfx950 code object.  hiprtc is loaded with dlopen, so the library still loads where it is absent;
 // the interpreter kernels are always there.
 #include "jit_runtime.h"
+#include "gpuq_kernels.h"
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
@@ -62,11 +63,9 @@ Rtc& rtc() {
   });
   return r;
 }
-const char* file_of(int kernel_id) {
-  if (kernel_id >= 1 && kernel_id <= 3) return "kernels_scan.hip";
-  if ((kernel_id >= 4 && kernel_id <= 7) || (kernel_id >= 11 && kernel_id <= 15)) return "kernels_hash.hip";
-  if (kernel_id >= 8 && kernel_id <= 10) return "kernels_sort.hip";
-  throw std::runtime_error("jit: bad kernel id");
+const SinkInfo& sink_of(int kernel_id) {
+  for (const SinkInfo& k : GPUQ_SINKS) if (k.id == kernel_id) return k;
+  throw std::runtime_error("jit: bad kernel id " + std::to_string(kernel_id));
 }
 std::mutex g_mu;
 std::map<std::string, JitFn> g_cache;
@@ -88,18 +87,11 @@ static std::string env_defines() {
   return r;
 }
 
-// the entry point carries the sink's name so that profiles tell the specialised kernels apart
-static const char* jit_entry_name(int kernel_id) {
-  static const char* n[] = {"gpuq_jit_entry", "gpuq_jit_filter_bitmap", "gpuq_jit_project", "gpuq_jit_agg_tiny", "gpuq_jit_agg_hash", "gpuq_jit_join_build",
-                            "gpuq_jit_join_probe", "gpuq_jit_join_probe_unique", "gpuq_jit_sort_minmax", "gpuq_jit_sort_pack", "gpuq_jit_part_pid",
-                            "gpuq_jit_agg_bucket_id", "gpuq_jit_agg_bucket", "gpuq_jit_agg_lds", "gpuq_jit_join_keyrange", "gpuq_jit_rj_pack"};
-  return (kernel_id >= 1 && kernel_id <= 15) ? n[kernel_id] : n[0];
-}
-
+// The entry point carries the sink's name so that profiles tell the specialised kernels apart.
 // "//@label xyz" anywhere in the front-end source (an operator's descriptor "label": a plan node id) is appended to the entry point's name:
 // two call sites of one sink kernel -- the two probes of q3 -- then show up as two kernels in a profile
 static std::string entry_name(const std::string& eval_src, int kernel_id) {
-  std::string n = jit_entry_name(kernel_id);
+  std::string n = sink_of(kernel_id).entry;
   const size_t p = eval_src.find("//@label ");
   if (p != std::string::npos) {
     std::string l;
@@ -110,7 +102,7 @@ static std::string entry_name(const std::string& eval_src, int kernel_id) {
 }
 std::string jit_full_source(const std::string& eval_src, int kernel_id) {
   return env_defines() + "#define gpuq_jit_entry " + entry_name(eval_src, kernel_id) + "\n#define GPUQ_JIT 1\n#define GPUQ_JIT_KERNEL " + std::to_string(kernel_id) +
-         "\n#include \"gpuq_kernels.h\"\nnamespace gpuq {\n" + eval_src + "}\n#include \"" + file_of(kernel_id) + "\"\n";
+         "\n#include \"gpuq_kernels.h\"\nnamespace gpuq {\n" + eval_src + "}\n#include \"" + sink_of(kernel_id).file + "\"\n";
 }
 
 // ---- on-disk code-object cache.  A one-shot task must not pay 0.3-1.9 s of hiprtc for a pipeline some earlier process on this

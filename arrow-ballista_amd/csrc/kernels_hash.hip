@@ -313,10 +313,8 @@ __device__ __forceinline__ void k_agg_hash_body(const DevProgram P, const i64 n_
 }
 #ifndef GPUQ_JIT
 template <int MAXC>
-#ifndef GPUQ_JIT
 __global__ void __launch_bounds__(HBLOCK) k_agg_hash(const DevProgram P, const i64 n, const KeySpec K, const AggSpec A, const HashTable T) { k_agg_hash_body<MAXC>(P, n, K, A, T); }
-#endif
-#elif GPUQ_JIT_KERNEL == 4
+#elif GPUQ_JIT_KERNEL == GPUQ_SINK_AGG_HASH
 extern "C" __global__ void __launch_bounds__(HBLOCK) gpuq_jit_entry(const DevProgram P, const i64 n, const KeySpec K, const AggSpec A, const HashTable T) { k_agg_hash_body<0>(P, n, K, A, T); }
 #endif
 
@@ -415,7 +413,7 @@ __global__ void __launch_bounds__(HBLOCK) k_bucket_bounds(const u64* __restrict_
     bounds[b] = (uint32_t)lo;
   }
 }
-#elif GPUQ_JIT_KERNEL == 11
+#elif GPUQ_JIT_KERNEL == GPUQ_SINK_AGG_BUCKET_ID
 extern "C" __global__ void __launch_bounds__(HBLOCK) gpuq_jit_entry(const DevProgram P, const i64 n, const KeySpec K, const u64 bucket_mask,
                                                           u64* __restrict__ bid, uint32_t* __restrict__ ids) { k_agg_bucket_id_body<0>(P, n, K, bucket_mask, bid, ids); }
 #endif
@@ -701,7 +699,7 @@ __global__ void __launch_bounds__(HBLOCK) k_fsum_stage_reduce(const HashTable T,
 template <int MAXC>
 __global__ void __launch_bounds__(HBLOCK) k_agg_lds(const DevProgram P, const i64 n, const KeySpec K, const AggSpec A, const HashTable T, const uint32_t lcap,
                                                     u64* fstage, const int n_fsum) { k_agg_lds_body<MAXC>(P, n, K, A, T, lcap, fstage, n_fsum); }
-#elif GPUQ_JIT_KERNEL == 13
+#elif GPUQ_JIT_KERNEL == GPUQ_SINK_AGG_LDS
 extern "C" __global__ void __launch_bounds__(HBLOCK) gpuq_jit_entry(const DevProgram P, const i64 n, const KeySpec K, const AggSpec A, const HashTable T, const uint32_t lcap,
                                                                      u64* fstage, const int n_fsum) { k_agg_lds_body<0>(P, n, K, A, T, lcap, fstage, n_fsum); }
 #endif
@@ -837,7 +835,7 @@ template <int MAXC>
 __global__ void __launch_bounds__(HBLOCK) k_agg_bucket(const DevProgram P, const KeySpec K, const AggSpec A, const uint32_t* __restrict__ ids,
                                                        const uint32_t* __restrict__ bounds, const uint32_t nbuckets, const uint32_t cap, const int slot_words,
                                                        const AggOut out) { k_agg_bucket_body<MAXC>(P, K, A, ids, bounds, nbuckets, cap, slot_words, out); }
-#elif GPUQ_JIT_KERNEL == 12
+#elif GPUQ_JIT_KERNEL == GPUQ_SINK_AGG_BUCKET
 extern "C" __global__ void __launch_bounds__(HBLOCK) gpuq_jit_entry(const DevProgram P, const KeySpec K, const AggSpec A, const uint32_t* __restrict__ ids,
                                                        const uint32_t* __restrict__ bounds, const uint32_t nbuckets, const uint32_t cap, const int slot_words,
                                                        const AggOut out) { k_agg_bucket_body<0>(P, K, A, ids, bounds, nbuckets, cap, slot_words, out); }
@@ -875,7 +873,7 @@ __device__ __forceinline__ void k_join_keyrange_body(const DevProgram P, const i
 #ifndef GPUQ_JIT
 template <int MAXC>
 __global__ void __launch_bounds__(HBLOCK) k_join_keyrange(const DevProgram P, const i64 n, const KeySpec K, const int null_eq, u64* __restrict__ out, const i64 wstep) { k_join_keyrange_body<MAXC>(P, n, K, null_eq, out, wstep); }
-#elif GPUQ_JIT_KERNEL == 14
+#elif GPUQ_JIT_KERNEL == GPUQ_SINK_JOIN_KEYRANGE
 extern "C" __global__ void __launch_bounds__(HBLOCK) gpuq_jit_entry(const DevProgram P, const i64 n, const KeySpec K, const int null_eq, u64* __restrict__ out, const i64 wstep) { k_join_keyrange_body<0>(P, n, K, null_eq, out, wstep); }
 #endif
 
@@ -1137,7 +1135,7 @@ template <int MAXC, bool SEMI>
 __global__ void __launch_bounds__(HBLOCK) k_join_build(const DevProgram P, const i64 n, const KeySpec K, const HashTable T,
                                                        uint32_t* __restrict__ next, uint32_t* __restrict__ present, const int payload_via,
                                                        const int null_eq, const SemiProbe S) { k_join_build_body<MAXC, SEMI>(P, n, K, T, next, present, payload_via, null_eq, S); }
-#elif GPUQ_JIT_KERNEL == 5
+#elif GPUQ_JIT_KERNEL == GPUQ_SINK_JOIN_BUILD
 #ifndef GPUQ_JIT_SEMI
 #define GPUQ_JIT_SEMI 0
 #endif
@@ -1222,13 +1220,11 @@ __device__ __forceinline__ void k_join_probe_body(const DevProgram P, const i64 
 }
 #ifndef GPUQ_JIT
 template <int MAXC>
-#ifndef GPUQ_JIT
 __global__ void __launch_bounds__(HBLOCK) k_join_probe(const DevProgram P, const i64 n, const KeySpec K, const HashTable T,
                                                        const uint32_t* __restrict__ next, const int join_type, const int payload_via,
                                                        const int null_eq, uint32_t* __restrict__ out_build, uint32_t* __restrict__ out_probe,
                                                        const u64 out_cap, u64* __restrict__ out_count, uint32_t* __restrict__ visited) { k_join_probe_body<MAXC>(P, n, K, T, next, join_type, payload_via, null_eq, out_build, out_probe, out_cap, out_count, visited); }
-#endif
-#elif GPUQ_JIT_KERNEL == 6
+#elif GPUQ_JIT_KERNEL == GPUQ_SINK_JOIN_PROBE
 extern "C" __global__ void __launch_bounds__(HBLOCK) gpuq_jit_entry(const DevProgram P, const i64 n, const KeySpec K, const HashTable T,
                                                        const uint32_t* __restrict__ next, const int join_type, const int payload_via,
                                                        const int null_eq, uint32_t* __restrict__ out_build, uint32_t* __restrict__ out_probe,
@@ -1488,7 +1484,7 @@ __global__ void __launch_bounds__(HBLOCK) k_join_probe_unique(const DevProgram P
                                                               uint32_t* __restrict__ seg_build, uint32_t* __restrict__ seg_probe,
                                                               uint32_t* __restrict__ seg_counts, const int nsegs, const i64 wpw,
                                                               uint32_t* __restrict__ visited) { k_join_probe_unique_body<MAXC>(P, n, K, T, join_type, null_eq, payload_via, seg_build, seg_probe, seg_counts, nsegs, wpw, visited); }
-#elif GPUQ_JIT_KERNEL == 7
+#elif GPUQ_JIT_KERNEL == GPUQ_SINK_JOIN_PROBE_UNIQUE
 extern "C" __global__ void __launch_bounds__(HBLOCK) gpuq_jit_entry(const DevProgram P, const i64 n, const KeySpec K, const HashTable T,
                                                               const int join_type, const int null_eq, const int payload_via,
                                                               uint32_t* __restrict__ seg_build, uint32_t* __restrict__ seg_probe,
@@ -1570,7 +1566,7 @@ __device__ __forceinline__ void k_rj_pack_body(const DevProgram P, const i64 n_a
 template <int MAXC>
 __global__ void __launch_bounds__(HBLOCK) k_rj_pack(const DevProgram P, const i64 n, const KeySpec K, const HashTable T, const int payload_via, const RjGeom G,
                                                     u64* __restrict__ rec, int32_t* __restrict__ hist) { k_rj_pack_body<MAXC>(P, n, K, T, payload_via, G, rec, hist); }
-#elif GPUQ_JIT_KERNEL == 15
+#elif GPUQ_JIT_KERNEL == GPUQ_SINK_RJ_PACK
 extern "C" __global__ void __launch_bounds__(HBLOCK) gpuq_jit_entry(const DevProgram P, const i64 n, const KeySpec K, const HashTable T, const int payload_via, const RjGeom G,
                                                     u64* __restrict__ rec, int32_t* __restrict__ hist) { k_rj_pack_body<0>(P, n, K, T, payload_via, G, rec, hist); }
 #endif
@@ -1714,21 +1710,13 @@ void launch_ht_init(hipStream_t s, const HashTable& T, const AggSpec* A) {
   const int grid = (int)(need < cap ? (need ? need : 1) : cap);
   hipLaunchKernelGGL(k_ht_init, dim3(grid), dim3(HBLOCK), 0, s, T, A ? *A : dummy, A ? 1 : 0);
 }
-void launch_agg_hash(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, const AggSpec& A, const HashTable& T) {
+void launch_agg_hash(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const AggSpec& A, const HashTable& T) {
   if (n <= 0) return;
-  if (jit_override().fn && jit_override().kernel_id == 4) {
-    (void)jit_launch(jit_override().fn, dim3(hgrid(n, 8)), dim3(HBLOCK), 0, s, P, n, K, A, T);
-  } else {
-#define CALL(M) hipLaunchKernelGGL(k_agg_hash<M>, dim3(hgrid(n, 8)), dim3(HBLOCK), 0, s, P, n, K, A, T)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
-  }
+  launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_agg_hash), dim3(hgrid(n, 8)), dim3(HBLOCK), 0, s, P, n, K, A, T);
 }
 void launch_key_sample(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, i64 stride, i64 nsample, uint32_t* bitmap, u64 nbits, unsigned long long* passed) {
   if (n <= 0 || nsample <= 0) return;
-#define CALL(M) hipLaunchKernelGGL(k_key_sample<M>, dim3(hgrid(nsample, 8)), dim3(HBLOCK), 0, s, P, n, K, stride, nsample, bitmap, nbits - 1, passed)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
+  launch_sink(nullptr, P.n_cols, GPUQ_PICK(k_key_sample), dim3(hgrid(nsample, 8)), dim3(HBLOCK), 0, s, P, n, K, stride, nsample, bitmap, nbits - 1, passed);
 }
 uint32_t agg_lds_slots(const HashTable& T) {      // LDS table size (slots) of the pre-aggregating kernel, 0 = a slot is too wide for it
   const size_t bytes = (size_t)(T.slot_words + 1) * 8;
@@ -1737,18 +1725,12 @@ uint32_t agg_lds_slots(const HashTable& T) {      // LDS table size (slots) of t
 }
 int agg_lds_grid(i64 n) { return hgrid(n, 4); }
 // fstage: nullptr, or T.n_slots * n_fsum * agg_lds_grid(n) zeroed words for the blocks' float partial sums
-void launch_agg_lds(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, const AggSpec& A, const HashTable& T, u64* fstage, int n_fsum) {
+void launch_agg_lds(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const AggSpec& A, const HashTable& T, u64* fstage, int n_fsum) {
   if (n <= 0) return;
   const uint32_t lcap = agg_lds_slots(T);
   const size_t lds = (size_t)lcap * (T.slot_words + 1) * 8;
   const int grid = agg_lds_grid(n);
-  if (jit_override().fn && jit_override().kernel_id == 13) {
-    (void)jit_launch(jit_override().fn, dim3(grid), dim3(HBLOCK), lds, s, P, n, K, A, T, lcap, fstage, n_fsum);
-  } else {
-#define CALL(M) hipLaunchKernelGGL(k_agg_lds<M>, dim3(grid), dim3(HBLOCK), lds, s, P, n, K, A, T, lcap, fstage, n_fsum)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
-  }
+  launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_agg_lds), dim3(grid), dim3(HBLOCK), lds, s, P, n, K, A, T, lcap, fstage, n_fsum);
   if (fstage && n_fsum > 0) {
     const u64 items = T.n_slots * (u64)n_fsum;
     const u64 need = (items + HWAVES - 1) / HWAVES, cap = (u64)num_cus() * 8;
@@ -1761,50 +1743,31 @@ void launch_agg_hash_extract(hipStream_t s, const KeySpec& K, const AggSpec& A, 
   const int grid = (int)(need < cap ? (need ? need : 1) : cap);
   hipLaunchKernelGGL(k_agg_hash_extract, dim3(grid), dim3(HBLOCK), 0, s, K, A, T, out, flags);
 }
-void launch_agg_bucket_id(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, u64 bucket_mask, u64* bid, uint32_t* ids) {
+void launch_agg_bucket_id(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, u64 bucket_mask, u64* bid, uint32_t* ids) {
   if (n <= 0) return;
-  if (jit_override().fn && jit_override().kernel_id == 11) {
-    (void)jit_launch(jit_override().fn, dim3(hgrid(n, 8)), dim3(HBLOCK), 0, s, P, n, K, bucket_mask, bid, ids);
-  } else {
-#define CALL(M) hipLaunchKernelGGL(k_agg_bucket_id<M>, dim3(hgrid(n, 8)), dim3(HBLOCK), 0, s, P, n, K, bucket_mask, bid, ids)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
-  }
+  launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_agg_bucket_id), dim3(hgrid(n, 8)), dim3(HBLOCK), 0, s, P, n, K, bucket_mask, bid, ids);
 }
 void launch_bucket_bounds(hipStream_t s, const u64* sorted_bid, i64 n, u64 nbuckets, uint32_t* bounds, int shift) {
   const u64 need = (nbuckets + 1 + HBLOCK - 1) / HBLOCK;
   hipLaunchKernelGGL(k_bucket_bounds, dim3((unsigned)(need < 4096 ? need : 4096)), dim3(HBLOCK), 0, s, sorted_bid, n, nbuckets, bounds, shift);
 }
-void launch_agg_bucket(hipStream_t s, const DevProgram& P, const KeySpec& K, const AggSpec& A, const uint32_t* ids, const uint32_t* bounds, uint32_t nbuckets,
+void launch_agg_bucket(hipStream_t s, void* jit_fn, const DevProgram& P, const KeySpec& K, const AggSpec& A, const uint32_t* ids, const uint32_t* bounds, uint32_t nbuckets,
                        uint32_t cap, int slot_words, const AggOut& out) {
   const size_t lds = (size_t)cap * slot_words * 8;
   u64 grid = nbuckets; const u64 gcap = (u64)num_cus() * 8; if (grid > gcap) grid = gcap; if (grid < 1) grid = 1;
-  if (jit_override().fn && jit_override().kernel_id == 12) {
-    (void)jit_launch(jit_override().fn, dim3((unsigned)grid), dim3(HBLOCK), lds, s, P, K, A, ids, bounds, nbuckets, cap, slot_words, out);
-  } else {
-#define CALL(M) hipLaunchKernelGGL(k_agg_bucket<M>, dim3((unsigned)grid), dim3(HBLOCK), lds, s, P, K, A, ids, bounds, nbuckets, cap, slot_words, out)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
-  }
+  launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_agg_bucket), dim3((unsigned)grid), dim3(HBLOCK), lds, s, P, K, A, ids, bounds, nbuckets, cap, slot_words, out);
 }
-bool launch_join_build(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, uint32_t* next, uint32_t* present,
+bool launch_join_build(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, uint32_t* next, uint32_t* present,
                        int payload_via, int null_equals_null, const SemiProbe* semi) {
   if (n <= 0) return true;
   SemiProbe S{}; if (semi) S = *semi;
-  if (jit_override().fn && jit_override().kernel_id == 5) {
-    (void)jit_launch(jit_override().fn, dim3(hgrid(n, 8)), dim3(HBLOCK), 0, s, P, n, K, T, next, present, payload_via, null_equals_null, S);
-  } else {
-    if (semi) {      // chain fusion: the interpreter form exists for up to 8 input columns (the specialised form for any)
-      if (P.n_cols > 8) return false;
-#define CALLS(M) hipLaunchKernelGGL((k_join_build<M, true>), dim3(hgrid(n, 8)), dim3(HBLOCK), 0, s, P, n, K, T, next, present, payload_via, null_equals_null, S)
-      if (P.n_cols <= 2) { CALLS(2); } else if (P.n_cols <= 4) { CALLS(4); } else { CALLS(8); }
-#undef CALLS
-      return true;
-    }
-#define CALL(M) hipLaunchKernelGGL((k_join_build<M, false>), dim3(hgrid(n, 8)), dim3(HBLOCK), 0, s, P, n, K, T, next, present, payload_via, null_equals_null, S)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
-  }
+  // chain fusion: the interpreter form exists for up to 8 input columns (the specialised form for any), so 16 slots never reach `semi_pick`
+  if (semi && !jit_fn && P.n_cols > 8) return false;
+  const auto semi_pick = [](auto M) { return &k_join_build<(decltype(M)::value < 8 ? decltype(M)::value : 8), true>; };
+  const auto plain_pick = [](auto M) { return &k_join_build<decltype(M)::value, false>; };
+  const dim3 grid(hgrid(n, 8)), block(HBLOCK);
+  if (semi) launch_sink(jit_fn, P.n_cols, semi_pick, grid, block, 0, s, P, n, K, T, next, present, payload_via, null_equals_null, S);
+  else launch_sink(jit_fn, P.n_cols, plain_pick, grid, block, 0, s, P, n, K, T, next, present, payload_via, null_equals_null, S);
   return true;
 }
 
@@ -1832,41 +1795,25 @@ void launch_bitmap_select(hipStream_t s, const u64* present, const u64* visited,
                           uint32_t* block_counts, int nblocks, i64 wpb) {
   hipLaunchKernelGGL(k_bitmap_select, dim3(nblocks), dim3(HBLOCK), 0, s, present, visited, matched, nwords, n, bitmap, block_counts, wpb);
 }
-void launch_join_probe(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, const uint32_t* next,
+void launch_join_probe(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, const uint32_t* next,
                        int join_type, int payload_via, int null_equals_null, uint32_t* out_build, uint32_t* out_probe,
                        u64 out_cap, u64* out_count, uint32_t* visited) {
   if (n <= 0) return;
-  if (jit_override().fn && jit_override().kernel_id == 6) {
-    (void)jit_launch(jit_override().fn, dim3(hgrid(n, 8)), dim3(HBLOCK), 0, s, P, n, K, T, next, join_type, payload_via, null_equals_null, out_build, out_probe, out_cap, out_count, visited);
-  } else {
-#define CALL(M) hipLaunchKernelGGL(k_join_probe<M>, dim3(hgrid(n, 8)), dim3(HBLOCK), 0, s, P, n, K, T, next, join_type, payload_via, null_equals_null,                                     out_build, out_probe, out_cap, out_count, visited)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
-  }
+  launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_join_probe), dim3(hgrid(n, 8)), dim3(HBLOCK), 0, s, P, n, K, T, next, join_type, payload_via, null_equals_null, out_build, out_probe,
+              out_cap, out_count, visited);
 }
 
-void launch_join_keyrange(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, int null_equals_null, u64* out, i64 wstep) {
+void launch_join_keyrange(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, int null_equals_null, u64* out, i64 wstep) {
   if (n <= 0) return;
   if (wstep < 1) wstep = 1;
   const int grid = hgrid((n + wstep - 1) / wstep, 8);
-  if (jit_override().fn && jit_override().kernel_id == 14) {
-    (void)jit_launch(jit_override().fn, dim3(grid), dim3(HBLOCK), 0, s, P, n, K, null_equals_null, out, wstep);
-  } else {
-#define CALL(M) hipLaunchKernelGGL(k_join_keyrange<M>, dim3(grid), dim3(HBLOCK), 0, s, P, n, K, null_equals_null, out, wstep)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
-  }
+  launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_join_keyrange), dim3(grid), dim3(HBLOCK), 0, s, P, n, K, null_equals_null, out, wstep);
 }
-void launch_join_probe_unique(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, int join_type, int null_equals_null, int payload_via,
+void launch_join_probe_unique(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, int join_type, int null_equals_null, int payload_via,
                               uint32_t* seg_build, uint32_t* seg_probe, uint32_t* seg_counts, int nsegs, i64 wpw, uint32_t* visited) {
   const int nblocks = (nsegs + HWAVES - 1) / HWAVES;
-  if (jit_override().fn && jit_override().kernel_id == 7) {
-    (void)jit_launch(jit_override().fn, dim3(nblocks), dim3(HBLOCK), 0, s, P, n, K, T, join_type, null_equals_null, payload_via, seg_build, seg_probe, seg_counts, nsegs, wpw, visited);
-  } else {
-#define CALL(M) hipLaunchKernelGGL(k_join_probe_unique<M>, dim3(nblocks), dim3(HBLOCK), 0, s, P, n, K, T, join_type, null_equals_null, payload_via, seg_build, seg_probe, seg_counts, nsegs, wpw, visited)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
-  }
+  launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_join_probe_unique), dim3(nblocks), dim3(HBLOCK), 0, s, P, n, K, T, join_type, null_equals_null, payload_via, seg_build, seg_probe, seg_counts,
+              nsegs, wpw, visited);
 }
 void launch_copy_segments(hipStream_t s, const uint32_t* seg_build, const uint32_t* seg_probe, const uint32_t* seg_offsets, int nsegs, i64 wpw, i64 n,
                           const u64* total, uint32_t* out_build, uint32_t* out_probe, u64 out_cap, uint32_t* flags) {
@@ -1879,9 +1826,7 @@ void launch_copy_segments(hipStream_t s, const uint32_t* seg_build, const uint32
 void launch_join_locality(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, i64 stride, i64 nsample, u64* out) {
   if (n <= 0 || nsample <= 0) return;
   const int grid = (int)std::min<i64>((nsample + HWAVES - 1) / HWAVES, (i64)num_cus() * 4);
-#define CALL(M) hipLaunchKernelGGL(k_join_locality<M>, dim3(grid), dim3(HBLOCK), 0, s, P, n, K, T, stride < 1 ? 1 : stride, nsample, out)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
+  launch_sink(nullptr, P.n_cols, GPUQ_PICK(k_join_locality), dim3(grid), dim3(HBLOCK), 0, s, P, n, K, T, stride < 1 ? 1 : stride, nsample, out);
 }
 // ---- partitioned probe
 void rj_geometry(i64 n, u64 range, int slice_log2, RjGeomHost* g) {
@@ -1893,16 +1838,10 @@ void rj_geometry(i64 n, u64 range, int slice_log2, RjGeomHost* g) {
   g->tile = t; g->nblocks = (int32_t)((n + t - 1) / t); if (g->nblocks < 1) g->nblocks = 1;
 }
 size_t rj_hist_entries(const RjGeomHost& g) { return (size_t)(g.nparts + 1) * g.nblocks + 1; }
-void launch_rj_partition(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, int payload_via, const RjGeomHost& g,
+void launch_rj_partition(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, int payload_via, const RjGeomHost& g,
                          u64* rec, u64* rec_out, int32_t* hist, void* scan_ws, size_t scan_ws_bytes) {
   RjGeom G{g.nparts, g.shift, g.tile, g.nblocks, 0};
-  if (jit_override().fn && jit_override().kernel_id == 15) {
-    (void)jit_launch(jit_override().fn, dim3(g.nblocks), dim3(HBLOCK), 0, s, P, n, K, T, payload_via, G, rec, hist);
-  } else {
-#define CALL(M) hipLaunchKernelGGL(k_rj_pack<M>, dim3(g.nblocks), dim3(HBLOCK), 0, s, P, n, K, T, payload_via, G, rec, hist)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
-  }
+  launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_rj_pack), dim3(g.nblocks), dim3(HBLOCK), 0, s, P, n, K, T, payload_via, G, rec, hist);
   launch_exclusive_scan_i32(s, hist, (i64)(g.nparts + 1) * g.nblocks, scan_ws, scan_ws_bytes);
   hipLaunchKernelGGL(k_rj_scatter, dim3(g.nblocks), dim3(HBLOCK), 0, s, (const u64*)rec, n, G, (const int32_t*)hist, rec_out);
 }

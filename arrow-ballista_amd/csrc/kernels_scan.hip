@@ -54,11 +54,9 @@ __device__ __forceinline__ void k_filter_bitmap_body(const DevProgram P, const i
 }
 #ifndef GPUQ_JIT
 template <int MAXC>
-#ifndef GPUQ_JIT
 __global__ void __launch_bounds__(BLOCK) k_filter_bitmap(const DevProgram P, const i64 n, u64* __restrict__ bitmap,
                                                          uint32_t* __restrict__ block_counts, const i64 wpb) { k_filter_bitmap_body<MAXC>(P, n, bitmap, block_counts, wpb); }
-#endif
-#elif GPUQ_JIT_KERNEL == 1
+#elif GPUQ_JIT_KERNEL == GPUQ_SINK_FILTER_BITMAP
 extern "C" __global__ void __launch_bounds__(BLOCK) gpuq_jit_entry(const DevProgram P, const i64 n, u64* __restrict__ bitmap,
                                                          uint32_t* __restrict__ block_counts, const i64 wpb) { k_filter_bitmap_body<0>(P, n, bitmap, block_counts, wpb); }
 #endif
@@ -169,10 +167,8 @@ __device__ __forceinline__ void k_project_body(const DevProgram P, const i64 n_a
 }
 #ifndef GPUQ_JIT
 template <int MAXC>
-#ifndef GPUQ_JIT
 __global__ void __launch_bounds__(BLOCK) k_project(const DevProgram P, const i64 n, const OutSpec O) { k_project_body<MAXC>(P, n, O); }
-#endif
-#elif GPUQ_JIT_KERNEL == 2
+#elif GPUQ_JIT_KERNEL == GPUQ_SINK_PROJECT
 extern "C" __global__ void __launch_bounds__(BLOCK) gpuq_jit_entry(const DevProgram P, const i64 n, const OutSpec O) { k_project_body<0>(P, n, O); }
 #endif
 
@@ -608,11 +604,9 @@ pipeline_done:
 #undef SPEC_UNROLL
 #ifndef GPUQ_JIT
 template <int MAXC>
-#ifndef GPUQ_JIT
 __global__ void __launch_bounds__(BLOCK) k_agg_tiny(const DevProgram P, const i64 n, const AggSpec A, const int gmax,
                                                     char* __restrict__ workspace, const size_t partial_stride) { k_agg_tiny_body<MAXC>(P, n, A, gmax, workspace, partial_stride); }
-#endif
-#elif GPUQ_JIT_KERNEL == 3
+#elif GPUQ_JIT_KERNEL == GPUQ_SINK_AGG_TINY
 extern "C" __global__ void __launch_bounds__(BLOCK) gpuq_jit_entry(const DevProgram P, const i64 n, const AggSpec A, const int gmax,
                                                     char* __restrict__ workspace, const size_t partial_stride) { k_agg_tiny_body<0>(P, n, A, gmax, workspace, partial_stride); }
 #endif
@@ -909,7 +903,6 @@ __global__ void __launch_bounds__(BLOCK) k_scan_downsweep(int32_t* __restrict__ 
 #ifndef GPUQ_JIT
 // ------------------------------------------------------------------ launchers
 static int g_num_cus = 256;
-JitOverride& jit_override() { static thread_local JitOverride o; return o; }
 void set_num_cus(int n) { if (n > 0) g_num_cus = n; }
 int num_cus() { return g_num_cus; }
 
@@ -921,14 +914,8 @@ static int grid_for(i64 n, int blocks_per_cu) {
   return (int)(need < cap ? need : cap);
 }
 
-void launch_filter_bitmap(hipStream_t s, const DevProgram& P, i64 n, u64* bitmap, uint32_t* block_counts, int nblocks, i64 wpb) {
-  if (jit_override().fn && jit_override().kernel_id == 1) {
-    (void)jit_launch(jit_override().fn, dim3(nblocks), dim3(BLOCK), 0, s, P, n, bitmap, block_counts, wpb);
-  } else {
-#define CALL(M) hipLaunchKernelGGL(k_filter_bitmap<M>, dim3(nblocks), dim3(BLOCK), 0, s, P, n, bitmap, block_counts, wpb)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
-  }
+void launch_filter_bitmap(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, u64* bitmap, uint32_t* block_counts, int nblocks, i64 wpb) {
+  launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_filter_bitmap), dim3(nblocks), dim3(BLOCK), 0, s, P, n, bitmap, block_counts, wpb);
 }
 void launch_scan_block_counts(hipStream_t s, uint32_t* block_counts, int nblocks, u64* total_out) {
   hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, block_counts, nblocks, total_out);
@@ -937,15 +924,9 @@ void launch_compact(hipStream_t s, const u64* bitmap, const uint32_t* block_offs
                     const uint32_t* sel_in, uint32_t* sel_out) {
   hipLaunchKernelGGL(k_compact, dim3(nblocks), dim3(BLOCK), 0, s, bitmap, block_offsets, wpb, n, sel_in, sel_out);
 }
-void launch_project(hipStream_t s, const DevProgram& P, i64 n, const OutSpec& O) {
+void launch_project(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const OutSpec& O) {
   if (n <= 0) return;
-  if (jit_override().fn && jit_override().kernel_id == 2) {
-    (void)jit_launch(jit_override().fn, dim3(grid_for(n, 8)), dim3(BLOCK), 0, s, P, n, O);
-  } else {
-#define CALL(M) hipLaunchKernelGGL(k_project<M>, dim3(grid_for(n, 8)), dim3(BLOCK), 0, s, P, n, O)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
-  }
+  launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_project), dim3(grid_for(n, 8)), dim3(BLOCK), 0, s, P, n, O);
 }
 
 // LDS budget: keep one block within 64 KiB so at least two blocks (8 waves) share a CU.
@@ -966,7 +947,7 @@ size_t agg_tiny_workspace_bytes(int gmax, int n_keys, int n_accs, int* nblocks_o
   if (nblocks_out) *nblocks_out = nb;
   return (size_t)nb * ((tiny_partial_bytes(gmax, n_keys, n_accs) + 15) & ~(size_t)15);
 }
-void launch_agg_tiny(hipStream_t s, const DevProgram& P, i64 n, const AggSpec& A, int gmax, void* workspace) {
+void launch_agg_tiny(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const AggSpec& A, int gmax, void* workspace) {
   const size_t stride = (tiny_partial_bytes(gmax, A.n_keys, A.n_accs) + 15) & ~(size_t)15;
   int nb_cap = g_num_cus * tiny_blocks_per_cu(gmax, A.n_keys, A.n_accs);
   int nb = grid_for(n, 64);
@@ -977,21 +958,16 @@ void launch_agg_tiny(hipStream_t s, const DevProgram& P, i64 n, const AggSpec& A
   }
   // > 64 KiB of dynamic LDS needs an explicit opt-in (per template instantiation); the JIT'd function is
   // only used while the request stays within the default 64 KiB
-  if (jit_override().fn && jit_override().kernel_id == 3 && lds <= 60 * 1024) {
-    (void)jit_launch(jit_override().fn, dim3(nb), dim3(BLOCK), lds, s, P, n, A, gmax, (char*)workspace, stride);
-  } else {
-#define CALL(M)                                                                                                                          \
-  do {                                                                                                                                   \
-    static size_t attr_main = 0;                                                                                                         \
-    if (lds > 60 * 1024 && lds > attr_main) {                                                                                            \
-      if (hipFuncSetAttribute((const void*)k_agg_tiny<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) attr_main = lds; \
-      else (void)hipGetLastError();                                                                                                      \
-    }                                                                                                                                    \
-    hipLaunchKernelGGL(k_agg_tiny<M>, dim3(nb), dim3(BLOCK), lds, s, P, n, A, gmax, (char*)workspace, stride);                           \
-  } while (0)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
-  }
+  const auto pick = [lds](auto M) {
+    const auto k = &k_agg_tiny<decltype(M)::value>;
+    static size_t attr_main = 0;      // one per instantiation
+    if (lds > 60 * 1024 && lds > attr_main) {
+      if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) attr_main = lds;
+      else (void)hipGetLastError();
+    }
+    return k;
+  };
+  launch_sink(lds <= 60 * 1024 ? jit_fn : nullptr, P.n_cols, pick, dim3(nb), dim3(BLOCK), lds, s, P, n, A, gmax, (char*)workspace, stride);
 }
 
 void launch_agg_tiny_merge(hipStream_t s, const DevProgram& P, i64 n, const AggSpec& A, int gmax, void* workspace, const AggOut& out) {

@@ -93,10 +93,8 @@ __device__ __forceinline__ void k_sort_minmax_body(const DevProgram P, const i64
 }
 #ifndef GPUQ_JIT
 template <int MAXC>
-#ifndef GPUQ_JIT
 __global__ void __launch_bounds__(SBLOCK) k_sort_minmax(const DevProgram P, const i64 n, const SortSpec S, u64* __restrict__ out, const i64 wstep) { k_sort_minmax_body<MAXC>(P, n, S, out, wstep); }
-#endif
-#elif GPUQ_JIT_KERNEL == 8
+#elif GPUQ_JIT_KERNEL == GPUQ_SINK_SORT_MINMAX
 extern "C" __global__ void __launch_bounds__(SBLOCK) gpuq_jit_entry(const DevProgram P, const i64 n, const SortSpec S, u64* __restrict__ out, const i64 wstep) { k_sort_minmax_body<0>(P, n, S, out, wstep); }
 #endif
 
@@ -167,11 +165,9 @@ __device__ __forceinline__ void k_sort_pack_body(const DevProgram P, const i64 n
 }
 #ifndef GPUQ_JIT
 template <int MAXC>
-#ifndef GPUQ_JIT
 __global__ void __launch_bounds__(SBLOCK) k_sort_pack(const DevProgram P, const i64 n, const SortSpec S, const SortPack K,
                                                       u64* __restrict__ key_lo, u64* __restrict__ key_hi, uint32_t* __restrict__ ids, u64* __restrict__ hist, const int hist_passes) { k_sort_pack_body<MAXC>(P, n, S, K, key_lo, key_hi, ids, hist, hist_passes); }
-#endif
-#elif GPUQ_JIT_KERNEL == 9
+#elif GPUQ_JIT_KERNEL == GPUQ_SINK_SORT_PACK
 extern "C" __global__ void __launch_bounds__(SBLOCK) gpuq_jit_entry(const DevProgram P, const i64 n, const SortSpec S, const SortPack K,
                                                       u64* __restrict__ key_lo, u64* __restrict__ key_hi, uint32_t* __restrict__ ids, u64* __restrict__ hist, const int hist_passes) { k_sort_pack_body<0>(P, n, S, K, key_lo, key_hi, ids, hist, hist_passes); }
 #endif
@@ -284,11 +280,9 @@ __device__ __forceinline__ void k_part_pid_body(const DevProgram P, const i64 n_
 }
 #ifndef GPUQ_JIT
 template <int MAXC>
-#ifndef GPUQ_JIT
 __global__ void __launch_bounds__(SBLOCK) k_part_pid(const DevProgram P, const i64 n, const KeySpec K, const uint32_t nparts,
                                                      u64* __restrict__ pid_out, uint32_t* __restrict__ ids) { k_part_pid_body<MAXC>(P, n, K, nparts, pid_out, ids); }
-#endif
-#elif GPUQ_JIT_KERNEL == 10
+#elif GPUQ_JIT_KERNEL == GPUQ_SINK_PART_PID
 extern "C" __global__ void __launch_bounds__(SBLOCK) gpuq_jit_entry(const DevProgram P, const i64 n, const KeySpec K, const uint32_t nparts,
                                                      u64* __restrict__ pid_out, uint32_t* __restrict__ ids) { k_part_pid_body<0>(P, n, K, nparts, pid_out, ids); }
 #endif
@@ -598,38 +592,20 @@ static int sgrid(i64 n, int blocks_per_cu) {
   return (int)(need < cap ? need : cap);
 }
 int sort_minmax_blocks(i64 n) { return sgrid(n, 4); }
-void launch_sort_minmax(hipStream_t s, const DevProgram& P, i64 n, const SortSpec& S, u64* out, int nblocks, i64 wstep) {
+void launch_sort_minmax(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const SortSpec& S, u64* out, int nblocks, i64 wstep) {
   if (wstep < 1) wstep = 1;
-  if (jit_override().fn && jit_override().kernel_id == 8) {
-    (void)jit_launch(jit_override().fn, dim3(nblocks), dim3(SBLOCK), 0, s, P, n, S, out, wstep);
-  } else {
-#define CALL(M) hipLaunchKernelGGL(k_sort_minmax<M>, dim3(nblocks), dim3(SBLOCK), 0, s, P, n, S, out, wstep)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
-  }
+  launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_sort_minmax), dim3(nblocks), dim3(SBLOCK), 0, s, P, n, S, out, wstep);
 }
 int sort_max_passes() { return SORT_MAX_PASSES; }
-void launch_sort_pack(hipStream_t s, const DevProgram& P, i64 n, const SortSpec& S, const SortPack& K, u64* key_lo, u64* key_hi, uint32_t* ids, u64* hist, int hist_passes) {
+void launch_sort_pack(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const SortSpec& S, const SortPack& K, u64* key_lo, u64* key_hi, uint32_t* ids, u64* hist, int hist_passes) {
   if (n <= 0) return;
   if (hist) (void)hipMemsetAsync(hist, 0, (size_t)hist_passes * RADIX * 8, s);
   if (hist && K.check == 1) (void)hipMemsetAsync(hist + (size_t)SORT_MAX_PASSES * RADIX, 0, 8, s);      // the "layout does not hold" word
-  if (jit_override().fn && jit_override().kernel_id == 9) {
-    (void)jit_launch(jit_override().fn, dim3(sgrid(n, 8)), dim3(SBLOCK), 0, s, P, n, S, K, key_lo, key_hi, ids, hist, hist_passes);
-  } else {
-#define CALL(M) hipLaunchKernelGGL(k_sort_pack<M>, dim3(sgrid(n, 8)), dim3(SBLOCK), 0, s, P, n, S, K, key_lo, key_hi, ids, hist, hist_passes)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
-  }
+  launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_sort_pack), dim3(sgrid(n, 8)), dim3(SBLOCK), 0, s, P, n, S, K, key_lo, key_hi, ids, hist, hist_passes);
 }
-void launch_part_pid(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, uint32_t nparts, u64* pid_out, uint32_t* ids) {
+void launch_part_pid(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, uint32_t nparts, u64* pid_out, uint32_t* ids) {
   if (n <= 0) return;
-  if (jit_override().fn && jit_override().kernel_id == 10) {
-    (void)jit_launch(jit_override().fn, dim3(sgrid(n, 8)), dim3(SBLOCK), 0, s, P, n, K, nparts, pid_out, ids);
-  } else {
-#define CALL(M) hipLaunchKernelGGL(k_part_pid<M>, dim3(sgrid(n, 8)), dim3(SBLOCK), 0, s, P, n, K, nparts, pid_out, ids)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
-  }
+  launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_part_pid), dim3(sgrid(n, 8)), dim3(SBLOCK), 0, s, P, n, K, nparts, pid_out, ids);
 }
 // counts (u32[np]) -> the 256 u64 digit counts of a single 8-bit pass (np <= 256: the digit IS the partition)
 __global__ void __launch_bounds__(RADIX) k_counts_to_ghist(const uint32_t* __restrict__ counts, const uint32_t np, u64* __restrict__ ghist) {
@@ -685,9 +661,7 @@ int sort_small_max() { return SMALL_SORT_MAX; }
 int sort_direct_max() { return SORT_DIRECT_MAX; }
 void launch_sort_direct(hipStream_t s, const DevProgram& P, i64 n, const SortSpec& S, uint32_t* perm) {
   if (n <= 0) return;
-#define CALL(M) hipLaunchKernelGGL(k_sort_direct<M>, dim3(1), dim3(SORT_DIRECT_MAX), 0, s, P, (int)n, S, perm)
-  GPUQ_DISPATCH_MAXC(P.n_cols, CALL);
-#undef CALL
+  launch_sink(nullptr, P.n_cols, GPUQ_PICK(k_sort_direct), dim3(1), dim3(SORT_DIRECT_MAX), 0, s, P, (int)n, S, perm);
 }
 void launch_sort_small(hipStream_t s, const u64* klo, const u64* khi, const uint32_t* ids, i64 n, uint32_t* out) {
   if (n > 0) hipLaunchKernelGGL(k_sort_small, dim3(1), dim3(1024), 0, s, klo, khi, ids, (int)n, out);

@@ -391,8 +391,10 @@ int gpuq_ops_settle(gpuq_ctx* ctx, void* stream, gpuq_op* const* ops, int n_ops,
 /* Waits for `stream`, then reports device-side conditions raised by the op's kernels since the last
    check (string longer than 15 bytes in a packed comparison, output capacity overflow, ...). */
 int gpuq_op_check(gpuq_op* op, void* stream);
-/* Debug: the full source handed to hiprtc for sink kernel `kernel_id` (1 filter, 2 project, 3 aggregate-LDS,
-   4 aggregate-hash, 5 join build, 6 probe chained, 7 probe unique, 8 sort min/max, 9 sort pack, 10 partition, 14 join key range). */
+/* Debug: the full source handed to hiprtc for sink kernel `kernel_id`: 1 filter bitmap, 2 project, 3 tiny aggregate,
+   4 hash aggregate, 5 join build, 6 chained probe, 7 unique probe, 8 sort min/max, 9 sort pack, 10 partition ids,
+   11 radix-aggregate bucket ids, 12 radix-aggregate buckets, 13 block-local (LDS) aggregate, 14 join key range,
+   15 partitioned-probe pack (GPUQ_SINK_* in csrc/gpuq_kernels.h). */
 int gpuq_op_jit_source(gpuq_op* op, int kernel_id, char* buf, size_t cap);
 
 /* arrow `take` for Utf8 payload columns of ANY string length (datafusion's materialisation of a join / filter / sort output):

@@ -58,6 +58,38 @@ def test_tpch_jit(jit):
     M.test_q5(jit, 120_000)
 
 
+def test_aggregate_radix_jit(jit):
+    """The radix aggregate's two sinks (bucket ids, per-bucket aggregation): several buckets, NULL keys."""
+    import test_gpu_operators as M
+    M.test_aggregate_radix_strategy(jit, 700, 0.15)
+
+
+def test_aggregate_lds_jit(jit):
+    """The block-local (LDS) aggregate's sink."""
+    import test_gpu_operators as M
+    M.test_aggregate_lds_strategy(jit, 700, 0.15)
+
+
+def test_chain_fused_build_jit(jit, mirror_layer):
+    """The join build that looks its rows up in another join's table (chain fusion), in both specialised forms: one narrow key on
+    either join (GPUQ_JIT_SEMI 2), and a two-column key on the outer join (GPUQ_JIT_SEMI 1), where a pair that agrees on the
+    first key column alone is no match."""
+    import numpy as np
+    import pyarrow as pa
+    import arrow_ballista_amd as g
+    import test_gpu_join_chain as M
+    M.test_chain_equals_two_step(jit, "Inner", True, False)
+    A, B, C = M._tables(17, 700, 5000, 9000)
+    r = np.random.default_rng(3)
+    B = B.append_column("bk2", pa.array(r.integers(0, 2, len(B)), pa.int64()))
+    C = C.append_column("ck2", pa.array(r.integers(0, 2, len(C)), pa.int64()))
+    exp = [x for x in M._expected(A, B, C, "Inner", lambda x: x[1] < 80, lambda x: x[2] >= 100, lambda x: x[1] != 3) if x[5] == x[8]]
+    assert len(exp) > 0
+    p = g.NativePlan(M._plan(A, B, C, "Inner", True, on2=("bk2", "ck2")), jit)
+    for run in range(2):          # synchronous, then deferred
+        assert M.norm(M.arrow_rows(p.execute(0).to_arrow())) == M.norm(exp), run
+
+
 @pytest.mark.parametrize("jt", ["Inner", "Left", "Right", "Full", "RightSemi", "RightAnti"])
 def test_clustered_probe_keys_jit(jit, jt):
     """Foreign keys arrive clustered (the lines of one order are neighbours): the specialised unique-key probe looks a run

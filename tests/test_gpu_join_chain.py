@@ -66,7 +66,8 @@ def _expected(A, B, C, jt, a_pred=None, b_pred=None, c_pred=None):
     return out
 
 
-def _plan(A, B, C, jt, filters=False):
+def _plan(A, B, C, jt, filters=False, on2=None):
+    """on2 = (column of B, column of C): a second key pair of the outer join"""
     a, b, c = g.MemoryExec([A]), g.MemoryExec([B]), g.MemoryExec([C])
     as_, bs, cs = a.schema(), b.schema(), c.schema()
     la = g.FilterExec(binary(col("av", as_), Op.Lt, lit(80)), a) if filters else a
@@ -74,7 +75,8 @@ def _plan(A, B, C, jt, filters=False):
     lc = g.FilterExec(binary(col("cv", cs), Op.NotEq, lit(3)), c) if filters else c
     j1 = g.HashJoinExec(la, g.CoalesceBatchesExec(lb), [(col("ak", as_), col("bka", bs))], None, "Inner", "CollectLeft", False)
     j1s = j1.schema()
-    return g.HashJoinExec(g.CoalesceBatchesExec(j1), lc, [(col("bkc", j1s), col("ck", cs))], None, jt, "CollectLeft", False)
+    on = [(col("bkc", j1s), col("ck", cs))] + ([(col(on2[0], j1s), col(on2[1], cs))] if on2 else [])
+    return g.HashJoinExec(g.CoalesceBatchesExec(j1), lc, on, None, jt, "CollectLeft", False)
 
 
 @pytest.mark.parametrize("jt", ["Inner", "Right", "RightSemi", "RightAnti"])

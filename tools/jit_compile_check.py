@@ -1,7 +1,6 @@
-"""Compile (hipcc, gfx950, no GPU needed) the run-time sources the JIT path would hand to hiprtc, one per kernel id:
-filter (1), project (2), tiny aggregate (3), hash aggregate (4, 11-13), join build (5), key range (14), radix-join pack (15),
-chained probe (6), unique probe (7, generic and the one-narrow-key specialisation), sort min/max (8), sort pack (9),
-partition ids (10).  A source that does not compile makes the operator fall back to its AOT kernel -- silently slower."""
+"""Compile (hipcc, gfx950, no GPU needed) the run-time sources the JIT path would hand to hiprtc, one per sink kernel id (the list:
+gpuq_op_jit_source in include/gpuq.h), plus the specialisations of the join build (GPUQ_JIT_SEMI 1 and 2) and of the unique probe
+(one narrow key).  A source that does not compile makes the operator fall back to its AOT kernel -- silently slower."""
 import os, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
