@@ -77,6 +77,147 @@ enum JoinType : int32_t { JT_INNER = 0, JT_LEFT = 1, JT_RIGHT = 2, JT_FULL = 3, 
 
 // build: payload = payload_via ? via[payload_via-1][pos] : pos.  next == nullptr => unique keys only (FLAG_DUP_BUILD_KEY on a duplicate)
 
+// ----- accumulator algebra: what an AccKind IS, stated once for every aggregate kernel (k_agg_tiny + k_agg_tiny_merge, k_agg_hash,
+// k_agg_lds, k_agg_bucket).  A cell is two u64 words (lo, hi): SUM is a 128-bit integer, COUNT / MIN / MAX a 64-bit one in lo, the
+// float kinds a double's bit pattern in lo.  A new kind is added here; a new aggregate kernel is a loop around these helpers.
+// (k_agg_tiny's per-row accumulate into lane-private slots is its own algorithm and stays in kernels_scan.hip.)
+constexpr uint32_t NIL = 0xFFFFFFFFu;      // no row / no slot
+__device__ __forceinline__ uint32_t tag_of(u64 h) { return (uint32_t)(h >> 32) | 2u; }
+
+// identity of a cell, word `half`
+__device__ __forceinline__ u64 acc_identity(const int kind, const int half) {
+  switch (kind) {
+    case ACC_MIN: return half ? 0 : 0x7FFFFFFFFFFFFFFFull;
+    case ACC_MAX: return half ? ~0ull : 0x8000000000000000ull;
+    case ACC_FMIN: return half ? 0 : 0x7FF0000000000000ull;  // +inf
+    case ACC_FMAX: return half ? 0 : 0xFFF0000000000000ull;  // -inf
+    default: return 0;
+  }
+}
+// initial value of word w of a table slot whose cells start at word cell0: state, hash and key words are 0
+__device__ __forceinline__ u64 slot_word_identity(const AggSpec& A, const int w, const int cell0) {
+  const int a = (w - cell0) >> 1;
+  return (w >= cell0 && a < A.n_accs) ? acc_identity(A.acc_kind[a], (w - cell0) & 1) : 0;
+}
+// a block of `nthreads` empties its LDS table
+__device__ __forceinline__ void lds_table_init(u64* slots, const uint32_t cap, const int slot_words, const int cell0, const AggSpec& A, const uint32_t nthreads) {
+  for (uint32_t i = threadIdx.x; i < cap * (uint32_t)slot_words; i += nthreads) slots[i] = slot_word_identity(A, (int)(i % (uint32_t)slot_words), cell0);
+}
+// What accumulator a takes from the current row: its argument register (COUNT and COUNT(*): 1 -- a count is a sum of ones).
+// false: the row does not contribute (the argument is NULL).
+__device__ __forceinline__ bool acc_operand(const AggSpec& A, const int a, GPUQ_REGS_CPARAM, u64& vlo, u64& vhi) {
+  const int kind = A.acc_kind[a];
+  vlo = 1; vhi = 0;
+  if (kind == ACC_COUNT_STAR) return true;
+  const int r = __builtin_amdgcn_readfirstlane(A.acc_reg[a]);
+  if (kind != ACC_COUNT) { vlo = rlo[r]; vhi = rhi[r]; }
+  return !((rnulls >> r) & 1);
+}
+// MIN / MAX keep 64 bits: an operand outside int64 has to be refused (FLAG_WIDE_MINMAX), never folded
+__device__ __forceinline__ bool acc_wide_minmax(const int kind, const u64 vlo, const u64 vhi) {
+  return (kind == ACC_MIN || kind == ACC_MAX) && (i64)vhi != ((i64)vlo >> 63);
+}
+// partial (olo, ohi) combined into partial (lo, hi), no atomics (registers, or memory one thread owns)
+__device__ __forceinline__ void acc_combine(const int kind, u64& lo, u64& hi, const u64 olo, const u64 ohi) {
+  switch (kind) {
+    case ACC_SUM: case ACC_COUNT: case ACC_COUNT_STAR: { const u64 s = lo + olo; hi = hi + ohi + (s < lo ? 1 : 0); lo = s; break; }
+    case ACC_MIN: if ((i64)olo < (i64)lo) lo = olo; break;
+    case ACC_MAX: if ((i64)olo > (i64)lo) lo = olo; break;
+    case ACC_FSUM: lo = (u64)__double_as_longlong(__longlong_as_double((i64)lo) + __longlong_as_double((i64)olo)); break;
+    case ACC_FMIN: if (f64_total_key(olo) < f64_total_key(lo)) lo = olo; break;
+    case ACC_FMAX: if (f64_total_key(olo) > f64_total_key(lo)) lo = olo; break;
+    default: break;
+  }
+}
+// (vlo, vhi) folded into a cell other threads fold into too: SCOPE = __HIP_MEMORY_SCOPE_AGENT for a cell in device memory,
+// __HIP_MEMORY_SCOPE_WORKGROUP for one in LDS.  Integer adds commute, so SUM's carry can trail; adding zero is skipped.
+template <int SCOPE>
+__device__ __forceinline__ void acc_fold(u64* c, const int kind, const u64 vlo, const u64 vhi) {
+  switch (kind) {
+    case ACC_COUNT: case ACC_COUNT_STAR: if (vlo) __hip_atomic_fetch_add(c, vlo, __ATOMIC_RELAXED, SCOPE); break;
+    case ACC_SUM: {
+      if (!(vlo | vhi)) break;
+      const u64 old = __hip_atomic_fetch_add(c, vlo, __ATOMIC_RELAXED, SCOPE);
+      const u64 carry = (old + vlo < old) ? 1 : 0;
+      if (vhi + carry) __hip_atomic_fetch_add(c + 1, vhi + carry, __ATOMIC_RELAXED, SCOPE);
+      break;
+    }
+    case ACC_MIN: __hip_atomic_fetch_min((i64*)c, (i64)vlo, __ATOMIC_RELAXED, SCOPE); break;
+    case ACC_MAX: __hip_atomic_fetch_max((i64*)c, (i64)vlo, __ATOMIC_RELAXED, SCOPE); break;
+    case ACC_FSUM: unsafeAtomicAdd((double*)c, __longlong_as_double((i64)vlo)); break;      // (a CAS loop or a fetch_add cost the same: measured)
+    case ACC_FMIN: case ACC_FMAX: {
+      // total-order min/max through a CAS loop on the bit pattern
+      u64 cur = __hip_atomic_load(c, __ATOMIC_RELAXED, SCOPE);
+      for (;;) {
+        const bool better = (kind == ACC_FMIN) ? (f64_total_key(vlo) < f64_total_key(cur)) : (f64_total_key(vlo) > f64_total_key(cur));
+        if (!better || __hip_atomic_compare_exchange_strong(c, &cur, vlo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, SCOPE)) break;
+      }
+      break;
+    }
+    default: break;
+  }
+}
+// high word of a finished cell as the result carries it: MIN / MAX are sign-extended to 128 bits
+__device__ __forceinline__ u64 acc_result_hi(const int kind, const u64 lo, const u64 hi) {
+  return (kind == ACC_MIN || kind == ACC_MAX) ? (u64)((i64)lo >> 63) : hi;
+}
+
+// LDS open-addressing table of one block: slot = [state (0 empty, 1 being written, else tag), hash if STORE_HASH, key words, cells].
+// Finds the key's slot or claims one, starting at slot `start & (cap - 1)` and giving up (NIL) after max_probes occupied slots.
+template <bool STORE_HASH>
+__device__ __forceinline__ uint32_t lds_find_or_insert(u64* slots, const uint32_t cap, const int slot_words, const int key_words, const u64 (&kw)[MAX_KW], const u64 h,
+                                                       const uint32_t start, const uint32_t max_probes) {
+  constexpr int key0 = STORE_HASH ? 2 : 1;
+  const uint32_t mask = cap - 1;
+  uint32_t s = start & mask;
+  const u64 tag = (u64)tag_of(h);
+  for (uint32_t probes = 0; probes < max_probes;) {
+    u64* slot = slots + (size_t)s * slot_words;
+    u64 st = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (st == 0) {
+      u64 expected = 0;
+      if (__hip_atomic_compare_exchange_strong(slot, &expected, 1ull, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
+        if (STORE_HASH) __hip_atomic_store(slot + 1, h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#pragma unroll
+        for (int q = 0; q < MAX_KW; ++q) if (q < key_words) __hip_atomic_store(slot + key0 + q, kw[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+        __hip_atomic_store(slot, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        return s;
+      }
+      st = expected;
+    }
+    if (st == 1) continue;                           // being published by another lane: look again
+    if (st == tag) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+      bool eq = !STORE_HASH || __hip_atomic_load(slot + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == h;
+#pragma unroll
+      for (int q = 0; q < MAX_KW; ++q) if (q < key_words) eq = eq && (__hip_atomic_load(slot + key0 + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == kw[q]);
+      if (eq) return s;
+    }
+    s = (s + 1) & mask; ++probes;
+  }
+  return NIL;
+}
+
+// a finished table slot ([state, key words, cells from word cell0]) written as row g of the result
+__device__ __forceinline__ void emit_group(const u64* slot, const int cell0, const KeySpec& K, const AggSpec& A, const AggOut& out, const uint32_t g) {
+  const int kstride = K.n_keys > 0 ? K.n_keys : 1;
+  int w = 0;
+  for (int k = 0; k < K.n_keys; ++k) {
+    const u64 lo = slot[1 + w]; ++w;
+    u64 hi = (u64)((i64)lo >> 63);
+    if (K.key_wide[k]) { hi = slot[1 + w]; ++w; }
+    out.keys[((size_t)g * kstride + k) * 2] = lo;
+    out.keys[((size_t)g * kstride + k) * 2 + 1] = hi;
+  }
+  out.key_nulls[g] = K.null_word ? (uint32_t)slot[1 + w] : 0u;
+  for (int a = 0; a < A.n_accs; ++a) {
+    const u64 lo = slot[cell0 + 2 * a];
+    out.cells[((size_t)g * A.n_accs + a) * 2] = lo;
+    out.cells[((size_t)g * A.n_accs + a) * 2 + 1] = acc_result_hi(A.acc_kind[a], lo, slot[cell0 + 2 * a + 1]);
+  }
+}
+
 // sort / partition (kernels_sort.hip)
 constexpr int MAX_SORT_KEYS = 4;
 struct SortSpec {

@@ -18,7 +18,6 @@ namespace gpuq {
 
 constexpr int HBLOCK = 256;
 constexpr int HWAVES = HBLOCK / 64;
-constexpr uint32_t NIL = 0xFFFFFFFFu;
 
 __device__ __forceinline__ int hlane() { return threadIdx.x & 63; }
 __device__ __forceinline__ int hwave() { return threadIdx.x >> 6; }
@@ -64,8 +63,6 @@ __device__ __forceinline__ bool make_key(const KeySpec& K, GPUQ_REGS_CPARAM, u64
   hash = h;
   return knull != 0;
 }
-
-__device__ __forceinline__ uint32_t tag_of(u64 h) { return (uint32_t)(h >> 32) | 2u; }
 
 // Find the slot of a key or claim a new one.  Returns slot index, or ~0 when the table is full.
 __device__ __forceinline__ u64 ht_find_or_insert(const HashTable& T, const u64 (&kw)[MAX_KW], u64 h, uint32_t payload, bool& inserted) {
@@ -135,21 +132,7 @@ __global__ void __launch_bounds__(HBLOCK) k_ht_init(const HashTable T, const Agg
   const u64 total = T.n_slots * (u64)T.slot_words;
   const int cell0 = 1 + T.key_words;
   for (u64 i = (u64)blockIdx.x * HBLOCK + threadIdx.x; i < total; i += (u64)gridDim.x * HBLOCK) {
-    const int w = (int)(i % (u64)T.slot_words);
-    u64 v = 0;
-    if (has_agg && w >= cell0) {
-      const int a = (w - cell0) >> 1, half = (w - cell0) & 1;
-      if (a < A.n_accs) {
-        switch (A.acc_kind[a]) {
-          case ACC_MIN: v = half ? 0 : 0x7FFFFFFFFFFFFFFFull; break;
-          case ACC_MAX: v = half ? ~0ull : 0x8000000000000000ull; break;
-          case ACC_FMIN: v = half ? 0 : 0x7FF0000000000000ull; break;
-          case ACC_FMAX: v = half ? 0 : 0xFFF0000000000000ull; break;
-          default: break;
-        }
-      }
-    }
-    T.slots[i] = v;
+    T.slots[i] = has_agg ? slot_word_identity(A, (int)(i % (u64)T.slot_words), cell0) : 0;
   }
 }
 #endif
@@ -243,24 +226,11 @@ __device__ __forceinline__ void k_agg_hash_body(const DevProgram P, const i64 n_
     const bool upd = tail && s != ~0ull;
     for (int a = 0; a < A.n_accs; ++a) {
       const int kind = A.acc_kind[a];
-      u64 vlo = 1, vhi = 0; bool vnull = false;
-      if (kind != ACC_COUNT_STAR) {
-        const int r = __builtin_amdgcn_readfirstlane(A.acc_reg[a]);
-        vlo = rlo[r]; vhi = rhi[r]; vnull = (rnulls >> r) & 1;
-      }
-      if (!active) vnull = true;
-      bool wide = false;      // MIN/MAX over a value outside int64
-      // identity for rows that do not contribute
-      switch (kind) {
-        case ACC_COUNT: case ACC_COUNT_STAR: vlo = vnull ? 0 : 1; vhi = 0; break;
-        case ACC_SUM: if (vnull) { vlo = 0; vhi = 0; } break;
-        case ACC_MIN: wide = !vnull && (i64)vhi != ((i64)vlo >> 63); if (vnull) vlo = 0x7FFFFFFFFFFFFFFFull; break;
-        case ACC_MAX: wide = !vnull && (i64)vhi != ((i64)vlo >> 63); if (vnull) vlo = 0x8000000000000000ull; break;
-        case ACC_FSUM: if (vnull) vlo = 0; break;
-        default: break;
-      }
+      u64 vlo, vhi;
+      bool any = acc_operand(A, a, GPUQ_REGS, vlo, vhi) && active;        // does the run hold at least one contributing row
+      const bool wide = any && acc_wide_minmax(kind, vlo, vhi);
       if (__ballot(wide)) { if (wide) atomicOr(P.flags, FLAG_WIDE_MINMAX); continue; }
-      bool any = !vnull;        // does the run hold at least one contributing row
+      if (!any) { vlo = acc_identity(kind, 0); vhi = acc_identity(kind, 1); }      // rows that do not contribute hold the identity
       if (combine) {
         bool f = head;
 #pragma unroll
@@ -268,46 +238,14 @@ __device__ __forceinline__ void k_agg_hash_body(const DevProgram P, const i64 n_
           const u64 ulo = __shfl_up(vlo, off), uhi = __shfl_up(vhi, off);
           const bool uf = __shfl_up((int)f, off) != 0, uany = __shfl_up((int)any, off) != 0;
           if (lane >= off && !f) {
-            switch (kind) {
-              case ACC_COUNT: case ACC_COUNT_STAR: vlo += ulo; break;
-              case ACC_SUM: { const u64 sl = vlo + ulo; vhi = vhi + uhi + (sl < vlo ? 1 : 0); vlo = sl; break; }
-              case ACC_MIN: if ((i64)ulo < (i64)vlo) vlo = ulo; break;
-              case ACC_MAX: if ((i64)ulo > (i64)vlo) vlo = ulo; break;
-              case ACC_FSUM: vlo = (u64)__double_as_longlong(__longlong_as_double((i64)ulo) + __longlong_as_double((i64)vlo)); break;
-              default: break;
-            }
+            acc_combine(kind, vlo, vhi, ulo, uhi);
             any = any || uany;
             f = uf;
           }
         }
       }
-      if (!upd || !any) continue;
-      u64* c = cells + 2 * a;
-      switch (kind) {
-        case ACC_COUNT: case ACC_COUNT_STAR: a_add(c, vlo); break;
-        case ACC_SUM: {
-          const u64 old = a_add(c, vlo);
-          const u64 carry = (old + vlo < old) ? 1 : 0;
-          if (vhi + carry) a_add(c + 1, vhi + carry);
-          break;
-        }
-        case ACC_MIN: __hip_atomic_fetch_min((i64*)c, (i64)vlo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break;
-        case ACC_MAX: __hip_atomic_fetch_max((i64*)c, (i64)vlo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break;
-        case ACC_FSUM: unsafeAtomicAdd((double*)c, __longlong_as_double((i64)vlo)); break;
-        case ACC_FMIN: case ACC_FMAX: {
-          // total-order min/max through a CAS loop on the bit pattern (never combined: every row is its own run)
-          u64 cur = a_load(c);
-          for (;;) {
-            const bool better = (kind == ACC_FMIN) ? (f64_total_key(vlo) < f64_total_key(cur)) : (f64_total_key(vlo) > f64_total_key(cur));
-            if (!better) break;
-            const u64 seen = a_cas(c, cur, vlo);
-            if (seen == cur) break;
-            cur = seen;
-          }
-          break;
-        }
-        default: break;
-      }
+      // (FMIN / FMAX are never combined: every row is its own run)
+      if (upd && any) acc_fold<__HIP_MEMORY_SCOPE_AGENT>(cells + 2 * a, kind, vlo, vhi);
     }
   });
 }
@@ -325,7 +263,6 @@ __global__ void __launch_bounds__(HBLOCK) k_agg_hash_extract(const KeySpec K, co
   // 2^26-slot table cost 18 ms: ~17 ns per serialised device-scope atomic).  Output order is arbitrary anyway.
   constexpr int XSUB = 16;
   const int cell0 = 1 + T.key_words;
-  const int kstride = K.n_keys > 0 ? K.n_keys : 1;
   const u64 chunk_slots = 64ull * XSUB;
   const u64 nchunks = (T.n_slots + chunk_slots - 1) / chunk_slots;
   const u64 wave0 = (u64)blockIdx.x * HWAVES + hwave(), nwaves = (u64)gridDim.x * HWAVES;
@@ -351,24 +288,7 @@ __global__ void __launch_bounds__(HBLOCK) k_agg_hash_extract(const KeySpec K, co
         const u64 s = c * chunk_slots + (u64)j * 64 + hlane();
         const u64* slot = T.slots + s * (u64)T.slot_words;
         const uint32_t g = base + (uint32_t)__popcll(m & ltmask);
-        if (g < (uint32_t)out.cap) {
-          int w = 0;
-          for (int k = 0; k < K.n_keys; ++k) {
-            const u64 lo = slot[1 + w]; ++w;
-            u64 hi = (u64)((i64)lo >> 63);
-            if (K.key_wide[k]) { hi = slot[1 + w]; ++w; }
-            out.keys[((size_t)g * kstride + k) * 2] = lo;
-            out.keys[((size_t)g * kstride + k) * 2 + 1] = hi;
-          }
-          out.key_nulls[g] = K.null_word ? (uint32_t)slot[1 + w] : 0u;
-          for (int a = 0; a < A.n_accs; ++a) {
-            u64 lo = slot[cell0 + 2 * a], hi = slot[cell0 + 2 * a + 1];
-            const int kind = A.acc_kind[a];
-            if (kind == ACC_MIN || kind == ACC_MAX) hi = (u64)((i64)lo >> 63);
-            out.cells[((size_t)g * A.n_accs + a) * 2] = lo;
-            out.cells[((size_t)g * A.n_accs + a) * 2 + 1] = hi;
-          }
-        }
+        if (g < (uint32_t)out.cap) emit_group(slot, cell0, K, A, out, g);
       }
       base += (uint32_t)__popcll(m);
     }
@@ -418,38 +338,6 @@ extern "C" __global__ void __launch_bounds__(HBLOCK) gpuq_jit_entry(const DevPro
                                                           u64* __restrict__ bid, uint32_t* __restrict__ ids) { k_agg_bucket_id_body<0>(P, n, K, bucket_mask, bid, ids); }
 #endif
 
-// LDS table slot: word 0 = state (0 empty, 1 being written, else tag), then key words, then 2 words per accumulator
-__device__ __forceinline__ uint32_t lds_slot_find_or_insert(u64* slots, const uint32_t cap, const int slot_words, const int key_words, const u64 (&kw)[MAX_KW], const u64 h) {
-  const uint32_t mask = cap - 1;
-  uint32_t s = (uint32_t)(h >> 20) & mask;          // bits the bucket id did not use
-  const u64 tag = (u64)tag_of(h);
-  for (uint32_t probes = 0; probes < cap;) {
-    u64* slot = slots + (size_t)s * slot_words;
-    u64 st = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (st == 0) {
-      u64 expected = 0;
-      if (__hip_atomic_compare_exchange_strong(slot, &expected, 1ull, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
-#pragma unroll
-        for (int q = 0; q < MAX_KW; ++q) if (q < key_words) __hip_atomic_store(slot + 1 + q, kw[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        __hip_atomic_store(slot, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return s;
-      }
-      st = expected;
-    }
-    if (st == 1) continue;                           // being published by another lane: look again
-    if (st == tag) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-      bool eq = true;
-#pragma unroll
-      for (int q = 0; q < MAX_KW; ++q) if (q < key_words) eq = eq && (__hip_atomic_load(slot + 1 + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == kw[q]);
-      if (eq) return s;
-    }
-    s = (s + 1) & mask; ++probes;
-  }
-  return 0xFFFFFFFFu;
-}
-
 // ------------------------------------------------------------------ cardinality estimate
 // Which aggregate kernel is right depends on the number of groups, which nobody tells a first run.  A strided sample of the
 // input (every stride-th row, so clustered keys do not fool it) is hashed into a bitmap (linear counting: with far more bits
@@ -495,65 +383,6 @@ __global__ void __launch_bounds__(HBLOCK) k_key_sample(const DevProgram P, const
 // hash, key words, 2 words per accumulator]; a block whose table runs full sends its remaining rows straight to the global
 // table, so the kernel is correct for any cardinality -- the host only picks it when the group count is known to be small.
 constexpr uint32_t LDS_PROBES = 32;
-__device__ __forceinline__ uint32_t lds_group_slot(u64* slots, const uint32_t cap, const int lw, const int key_words, const u64 (&kw)[MAX_KW], const u64 h) {
-  const uint32_t mask = cap - 1;
-  uint32_t s = (uint32_t)(h >> 17) & mask;
-  const u64 tag = (u64)tag_of(h);
-  for (uint32_t probes = 0; probes < LDS_PROBES;) {
-    u64* slot = slots + (size_t)s * lw;
-    u64 st = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (st == 0) {
-      u64 expected = 0;
-      if (__hip_atomic_compare_exchange_strong(slot, &expected, 1ull, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
-        __hip_atomic_store(slot + 1, h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#pragma unroll
-        for (int q = 0; q < MAX_KW; ++q) if (q < key_words) __hip_atomic_store(slot + 2 + q, kw[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        __hip_atomic_store(slot, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return s;
-      }
-      st = expected;
-    }
-    if (st == 1) continue;                           // being published by another lane: look again
-    if (st == tag) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-      bool eq = __hip_atomic_load(slot + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == h;
-#pragma unroll
-      for (int q = 0; q < MAX_KW; ++q) if (q < key_words) eq = eq && (__hip_atomic_load(slot + 2 + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == kw[q]);
-      if (eq) return s;
-    }
-    s = (s + 1) & mask; ++probes;
-  }
-  return NIL;
-}
-// one accumulator value folded into a GLOBAL cell (device-scope atomics); FMIN/FMAX through a CAS loop on the total order
-__device__ __forceinline__ void global_fold(u64* c, const int kind, const u64 vlo, const u64 vhi) {
-  switch (kind) {
-    case ACC_COUNT: case ACC_COUNT_STAR: if (vlo) a_add(c, vlo); break;
-    case ACC_SUM: {
-      if (!(vlo | vhi)) break;
-      const u64 old = a_add(c, vlo);
-      const u64 carry = (old + vlo < old) ? 1 : 0;
-      if (vhi + carry) a_add(c + 1, vhi + carry);
-      break;
-    }
-    case ACC_MIN: __hip_atomic_fetch_min((i64*)c, (i64)vlo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break;
-    case ACC_MAX: __hip_atomic_fetch_max((i64*)c, (i64)vlo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break;
-    case ACC_FSUM: unsafeAtomicAdd((double*)c, __longlong_as_double((i64)vlo)); break;
-    case ACC_FMIN: case ACC_FMAX: {
-      u64 cur = a_load(c);
-      for (;;) {
-        const bool better = (kind == ACC_FMIN) ? (f64_total_key(vlo) < f64_total_key(cur)) : (f64_total_key(vlo) > f64_total_key(cur));
-        if (!better) break;
-        const u64 seen = a_cas(c, cur, vlo);
-        if (seen == cur) break;
-        cur = seen;
-      }
-      break;
-    }
-    default: break;
-  }
-}
 
 template <int MAXC>
 __device__ __forceinline__ void k_agg_lds_body(const DevProgram P, const i64 n_arg, const KeySpec K, const AggSpec A, const HashTable T, const uint32_t lcap,
@@ -563,23 +392,7 @@ __device__ __forceinline__ void k_agg_lds_body(const DevProgram P, const i64 n_a
   __shared__ uint32_t lfull;
   const int key_words = K.key_words;
   const int lw = T.slot_words + 1, lcell0 = 2 + key_words, gcell0 = 1 + key_words;
-  for (uint32_t i = threadIdx.x; i < lcap * (uint32_t)lw; i += HBLOCK) {
-    const int w = (int)(i % (uint32_t)lw);
-    u64 v = 0;
-    if (w >= lcell0) {
-      const int a = (w - lcell0) >> 1, half = (w - lcell0) & 1;
-      if (a < A.n_accs) {
-        switch (A.acc_kind[a]) {
-          case ACC_MIN: v = half ? 0 : 0x7FFFFFFFFFFFFFFFull; break;
-          case ACC_MAX: v = half ? ~0ull : 0x8000000000000000ull; break;
-          case ACC_FMIN: v = half ? 0 : 0x7FF0000000000000ull; break;
-          case ACC_FMAX: v = half ? 0 : 0xFFF0000000000000ull; break;
-          default: break;
-        }
-      }
-    }
-    lslots[i] = v;
-  }
+  lds_table_init(lslots, lcap, lw, lcell0, A, HBLOCK);
   if (threadIdx.x == 0) lfull = 0;
   __syncthreads();
   const i64 nwords = (n + 63) >> 6;
@@ -595,7 +408,7 @@ __device__ __forceinline__ void k_agg_lds_body(const DevProgram P, const i64 n_a
     make_key(K, GPUQ_REGS, kw, h);
     uint32_t ls = NIL;
     if (!__hip_atomic_load(&lfull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
-      ls = lds_group_slot(lslots, lcap, lw, key_words, kw, h);
+      ls = lds_find_or_insert<true>(lslots, lcap, lw, key_words, kw, h, (uint32_t)(h >> 17), LDS_PROBES);
       if (ls == NIL) __hip_atomic_store(&lfull, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     u64* gcells = nullptr;
@@ -608,40 +421,11 @@ __device__ __forceinline__ void k_agg_lds_body(const DevProgram P, const i64 n_a
     u64* cells = lslots + (size_t)(ls == NIL ? 0 : ls) * lw + lcell0;
     for (int a = 0; a < A.n_accs; ++a) {
       const int kind = A.acc_kind[a];
-      u64 vlo = 1, vhi = 0; bool vnull = false;
-      if (kind != ACC_COUNT_STAR) {
-        const int r = __builtin_amdgcn_readfirstlane(A.acc_reg[a]);
-        vlo = rlo[r]; vhi = rhi[r]; vnull = (rnulls >> r) & 1;
-      }
-      if (vnull) continue;
-      if (kind == ACC_COUNT) { vlo = 1; vhi = 0; }
-      if ((kind == ACC_MIN || kind == ACC_MAX) && (i64)vhi != ((i64)vlo >> 63)) { atomicOr(P.flags, FLAG_WIDE_MINMAX); continue; }
-      if (gcells) { global_fold(gcells + 2 * a, kind, vlo, vhi); continue; }
-      u64* c = cells + 2 * a;
-      switch (kind) {
-        case ACC_COUNT: case ACC_COUNT_STAR: atomicAdd((unsigned long long*)c, 1ull); break;
-        case ACC_SUM: {
-          const u64 old = atomicAdd((unsigned long long*)c, (unsigned long long)vlo);
-          const u64 carry = (old + vlo < old) ? 1 : 0;
-          if (vhi + carry) atomicAdd((unsigned long long*)(c + 1), (unsigned long long)(vhi + carry));
-          break;
-        }
-        case ACC_MIN: atomicMin((long long*)c, (long long)vlo); break;
-        case ACC_MAX: atomicMax((long long*)c, (long long)vlo); break;
-        case ACC_FSUM: unsafeAtomicAdd((double*)c, __longlong_as_double((i64)vlo)); break;      // (a CAS loop or a fetch_add cost the same: measured)
-        case ACC_FMIN: case ACC_FMAX: {
-          u64 cur = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          for (;;) {
-            const bool better = (kind == ACC_FMIN) ? (f64_total_key(vlo) < f64_total_key(cur)) : (f64_total_key(vlo) > f64_total_key(cur));
-            if (!better) break;
-            const u64 seen = atomicCAS((unsigned long long*)c, (unsigned long long)cur, (unsigned long long)vlo);
-            if (seen == cur) break;
-            cur = seen;
-          }
-          break;
-        }
-        default: break;
-      }
+      u64 vlo, vhi;
+      if (!acc_operand(A, a, GPUQ_REGS, vlo, vhi)) continue;
+      if (acc_wide_minmax(kind, vlo, vhi)) { atomicOr(P.flags, FLAG_WIDE_MINMAX); continue; }
+      if (gcells) acc_fold<__HIP_MEMORY_SCOPE_AGENT>(gcells + 2 * a, kind, vlo, vhi);
+      else acc_fold<__HIP_MEMORY_SCOPE_WORKGROUP>(cells + 2 * a, kind, vlo, vhi);
     }
   }
   __syncthreads();
@@ -664,7 +448,7 @@ __device__ __forceinline__ void k_agg_lds_body(const DevProgram P, const i64 n_a
       // and k_fsum_stage_reduce adds the blocks up in block order afterwards -- which also makes the sum reproducible.
       if (kind == ACC_FSUM && fstage) { fstage[((gs * (u64)n_fsum + (u64)kf) * gridDim.x) + blockIdx.x] = slot[lcell0 + 2 * a]; ++kf; continue; }
       if (kind == ACC_FSUM) ++kf;
-      global_fold(g + 2 * a, kind, slot[lcell0 + 2 * a], slot[lcell0 + 2 * a + 1]);
+      acc_fold<__HIP_MEMORY_SCOPE_AGENT>(g + 2 * a, kind, slot[lcell0 + 2 * a], slot[lcell0 + 2 * a + 1]);
     }
   }
 }
@@ -712,28 +496,10 @@ __device__ __forceinline__ void k_agg_bucket_body(const DevProgram P, const KeyS
   __shared__ uint32_t cnt[2]; __shared__ uint32_t gbase;
   const int key_words = K.key_words;
   const int cell0 = 1 + key_words;
-  const int kstride = K.n_keys > 0 ? K.n_keys : 1;
   for (uint32_t bk = blockIdx.x; bk < nbuckets; bk += gridDim.x) {
     const uint32_t b0 = bounds[bk], b1 = bounds[bk + 1];
     if (b0 == b1) continue;                          // uniform for the block
-    // table init
-    for (uint32_t i = threadIdx.x; i < cap * (uint32_t)slot_words; i += HBLOCK) {
-      const int w = (int)(i % (uint32_t)slot_words);
-      u64 v = 0;
-      if (w >= cell0) {
-        const int a = (w - cell0) >> 1, half = (w - cell0) & 1;
-        if (a < A.n_accs) {
-          switch (A.acc_kind[a]) {
-            case ACC_MIN: v = half ? 0 : 0x7FFFFFFFFFFFFFFFull; break;
-            case ACC_MAX: v = half ? ~0ull : 0x8000000000000000ull; break;
-            case ACC_FMIN: v = half ? 0 : 0x7FF0000000000000ull; break;
-            case ACC_FMAX: v = half ? 0 : 0xFFF0000000000000ull; break;
-            default: break;
-          }
-        }
-      }
-      bslots[i] = v;
-    }
+    lds_table_init(bslots, cap, slot_words, cell0, A, HBLOCK);
     if (threadIdx.x == 0) { cnt[0] = 0; cnt[1] = 0; }
     __syncthreads();
     // aggregate the bucket's rows
@@ -749,45 +515,15 @@ __device__ __forceinline__ void k_agg_bucket_body(const DevProgram P, const KeyS
 #pragma unroll
       for (int q = 0; q < MAX_KW; ++q) kw[q] = 0;
       make_key(K, GPUQ_REGS, kw, h);
-      const uint32_t s = lds_slot_find_or_insert(bslots, cap, slot_words, key_words, kw, h);
-      if (s == 0xFFFFFFFFu) { atomicOr(P.flags, FLAG_TABLE_FULL); continue; }
+      const uint32_t s = lds_find_or_insert<false>(bslots, cap, slot_words, key_words, kw, h, (uint32_t)(h >> 20), cap);      // bits the bucket id did not use
+      if (s == NIL) { atomicOr(P.flags, FLAG_TABLE_FULL); continue; }
       u64* cells = bslots + (size_t)s * slot_words + cell0;
       for (int a = 0; a < A.n_accs; ++a) {
         const int kind = A.acc_kind[a];
-        u64 vlo = 1, vhi = 0; bool vnull = false;
-        if (kind != ACC_COUNT_STAR) {
-          const int r = __builtin_amdgcn_readfirstlane(A.acc_reg[a]);
-          vlo = rlo[r]; vhi = rhi[r]; vnull = (rnulls >> r) & 1;
-        }
-        if (vnull) continue;
-        u64* c = cells + 2 * a;
-        switch (kind) {
-          case ACC_COUNT: case ACC_COUNT_STAR: atomicAdd((unsigned long long*)c, 1ull); break;
-          case ACC_SUM: {
-            const u64 old = atomicAdd((unsigned long long*)c, (unsigned long long)vlo);
-            const u64 carry = (old + vlo < old) ? 1 : 0;
-            if (vhi + carry) atomicAdd((unsigned long long*)(c + 1), (unsigned long long)(vhi + carry));
-            break;
-          }
-          case ACC_MIN: case ACC_MAX: {
-            if ((i64)vhi != ((i64)vlo >> 63)) { atomicOr(P.flags, FLAG_WIDE_MINMAX); break; }
-            if (kind == ACC_MIN) atomicMin((long long*)c, (long long)vlo); else atomicMax((long long*)c, (long long)vlo);
-            break;
-          }
-          case ACC_FSUM: unsafeAtomicAdd((double*)c, __longlong_as_double((i64)vlo)); break;
-          case ACC_FMIN: case ACC_FMAX: {
-            u64 cur = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            for (;;) {
-              const bool better = (kind == ACC_FMIN) ? (f64_total_key(vlo) < f64_total_key(cur)) : (f64_total_key(vlo) > f64_total_key(cur));
-              if (!better) break;
-              const u64 seen = atomicCAS((unsigned long long*)c, (unsigned long long)cur, (unsigned long long)vlo);
-              if (seen == cur) break;
-              cur = seen;
-            }
-            break;
-          }
-          default: break;
-        }
+        u64 vlo, vhi;
+        if (!acc_operand(A, a, GPUQ_REGS, vlo, vhi)) continue;
+        if (acc_wide_minmax(kind, vlo, vhi)) { atomicOr(P.flags, FLAG_WIDE_MINMAX); continue; }
+        acc_fold<__HIP_MEMORY_SCOPE_WORKGROUP>(cells + 2 * a, kind, vlo, vhi);
       }
     }
     __syncthreads();
@@ -804,22 +540,7 @@ __device__ __forceinline__ void k_agg_bucket_body(const DevProgram P, const KeyS
         if (pass == 1 && live) {
           const uint32_t g = gbase + wbase + (uint32_t)__popcll(m & ((1ull << hlane()) - 1));
           if (g >= (uint32_t)out.cap) atomicOr(P.flags, FLAG_GROUP_OVERFLOW);
-          else {
-            int w = 0;
-            for (int k = 0; k < K.n_keys; ++k) {
-              const u64 lo = slot[1 + w]; ++w;
-              u64 hi = (u64)((i64)lo >> 63);
-              if (K.key_wide[k]) { hi = slot[1 + w]; ++w; }
-              out.keys[((size_t)g * kstride + k) * 2] = lo; out.keys[((size_t)g * kstride + k) * 2 + 1] = hi;
-            }
-            out.key_nulls[g] = K.null_word ? (uint32_t)slot[1 + w] : 0u;
-            for (int a = 0; a < A.n_accs; ++a) {
-              u64 lo = slot[cell0 + 2 * a], hi = slot[cell0 + 2 * a + 1];
-              const int kind = A.acc_kind[a];
-              if (kind == ACC_MIN || kind == ACC_MAX) hi = (u64)((i64)lo >> 63);
-              out.cells[((size_t)g * A.n_accs + a) * 2] = lo; out.cells[((size_t)g * A.n_accs + a) * 2 + 1] = hi;
-            }
-          }
+          else emit_group(slot, cell0, K, A, out, g);
         }
       }
       __syncthreads();

@@ -200,16 +200,6 @@ static size_t tiny_lds_bytes(int gmax, int n_keys, int n_accs) {
   return cells * BLOCK * 8 + cells * 16 + (size_t)gmax * (n_keys > 0 ? n_keys : 1) * 16 + (size_t)gmax * 4 + 16;
 }
 
-__device__ __forceinline__ u64 acc_identity(int kind) {
-  switch (kind) {
-    case ACC_MIN: return 0x7FFFFFFFFFFFFFFFull;
-    case ACC_MAX: return 0x8000000000000000ull;
-    case ACC_FMIN: return 0x7FF0000000000000ull;  // +inf
-    case ACC_FMAX: return 0xFFF0000000000000ull;  // -inf
-    default: return 0;
-  }
-}
-
 __device__ __forceinline__ void wide_add(u64* wide, int cell, u64 lo, u64 hi) {
   // 128-bit add into an LDS cell with two 64-bit atomics (adds commute, so the carry can trail)
   const u64 old = atomicAdd(&wide[2 * cell], lo);
@@ -270,7 +260,7 @@ __device__ __forceinline__ void k_agg_tiny_body(const DevProgram P, const i64 n_
   const int cells = gmax * n_accs;
   const int tid = threadIdx.x;
 #ifndef GPUQ_EXP_LOADS_ONLY
-  for (int c = 0; c < cells; ++c) L.lane_acc[c * BLOCK + tid] = acc_identity(SPEC_ACC_KIND(c % n_accs));
+  for (int c = 0; c < cells; ++c) L.lane_acc[c * BLOCK + tid] = acc_identity(SPEC_ACC_KIND(c % n_accs), 0);
   for (int c = tid; c < cells * 2; c += BLOCK) L.wide[c] = 0;
 #endif
   // an aggregate without GROUP BY always has exactly one group, even over zero rows
@@ -559,40 +549,15 @@ pipeline_done:
     if (kind == ACC_SUM) { lo = v; hi = (u64)((i64)v >> 63); } else { lo = v; hi = 0; }
     for (int off = 32; off > 0; off >>= 1) {
       const u64 olo = __shfl_xor(lo, off), ohi = __shfl_xor(hi, off);
-      switch (kind) {
-        case ACC_SUM: case ACC_COUNT: case ACC_COUNT_STAR: { const u64 s = lo + olo; hi = hi + ohi + (s < lo ? 1 : 0); lo = s; break; }
-        case ACC_MIN: if ((i64)olo < (i64)lo) lo = olo; break;
-        case ACC_MAX: if ((i64)olo > (i64)lo) lo = olo; break;
-        // lanes combine in a fixed butterfly order -> bitwise reproducible run to run
-        case ACC_FSUM: lo = (u64)__double_as_longlong(__longlong_as_double((i64)lo) + __longlong_as_double((i64)olo)); break;
-        case ACC_FMIN: if (f64_total_key(olo) < f64_total_key(lo)) lo = olo; break;
-        case ACC_FMAX: if (f64_total_key(olo) > f64_total_key(lo)) lo = olo; break;
-        default: break;
-      }
+      acc_combine(kind, lo, hi, olo, ohi);      // lanes combine in a fixed butterfly order -> float sums are bitwise reproducible run to run
     }
     if (lane_id() == 0) { red[wave_id() * 2] = lo; red[wave_id() * 2 + 1] = hi; }
     __syncthreads();
     if (tid == 0) {
       u64 rlo = red[0], rhi = red[1];
-      for (int k = 1; k < WAVES; ++k) {
-        const u64 olo = red[2 * k], ohi = red[2 * k + 1];
-        switch (kind) {
-          case ACC_SUM: case ACC_COUNT: case ACC_COUNT_STAR: { const u64 s = rlo + olo; rhi = rhi + ohi + (s < rlo ? 1 : 0); rlo = s; break; }
-          case ACC_MIN: if ((i64)olo < (i64)rlo) rlo = olo; break;
-          case ACC_MAX: if ((i64)olo > (i64)rlo) rlo = olo; break;
-          case ACC_FSUM: rlo = (u64)__double_as_longlong(__longlong_as_double((i64)rlo) + __longlong_as_double((i64)olo)); break;
-          case ACC_FMIN: if (f64_total_key(olo) < f64_total_key(rlo)) rlo = olo; break;
-          case ACC_FMAX: if (f64_total_key(olo) > f64_total_key(rlo)) rlo = olo; break;
-          default: break;
-        }
-      }
-      if (kind == ACC_SUM) {
-        const u64 wlo = L.wide[2 * c], whi = L.wide[2 * c + 1];
-        const u64 s = rlo + wlo; rhi = rhi + whi + (s < rlo ? 1 : 0); rlo = s;
-      } else if (kind == ACC_MIN || kind == ACC_MAX) {
-        rhi = (u64)((i64)rlo >> 63);
-      }
-      out_cells[2 * c] = rlo; out_cells[2 * c + 1] = rhi;
+      for (int k = 1; k < WAVES; ++k) acc_combine(kind, rlo, rhi, red[2 * k], red[2 * k + 1]);
+      if (kind == ACC_SUM) acc_combine(kind, rlo, rhi, L.wide[2 * c], L.wide[2 * c + 1]);      // the wide spill cell
+      out_cells[2 * c] = rlo; out_cells[2 * c + 1] = acc_result_hi(kind, rlo, rhi);
     }
     __syncthreads();
   }
@@ -683,11 +648,7 @@ __global__ void __launch_bounds__(MERGE_BLOCK) k_agg_tiny_merge(const AggSpec A,
   // phase 2: integer cells are folded with LDS atomics (any order gives the same bits); float sums
   // are folded by one thread per cell in block order so that results are reproducible run to run.
   u64* fcells = (u64*)(lock + 3);   // [cap][n_accs][2], 8-byte aligned by construction
-  for (int c = tid; c < nf * n_accs; c += MERGE_BLOCK) {
-    const int kind = A.acc_kind[c % n_accs];
-    fcells[2 * c] = acc_identity(kind);
-    fcells[2 * c + 1] = (kind == ACC_MAX) ? ~0ull : 0;
-  }
+  for (int c = tid; c < nf * n_accs * 2; c += MERGE_BLOCK) fcells[c] = acc_identity(A.acc_kind[(c >> 1) % n_accs], c & 1);
   __syncthreads();
   bool has_float = false;
   for (int a = 0; a < n_accs; ++a) has_float = has_float || A.acc_kind[a] == ACC_FSUM;
@@ -698,30 +659,8 @@ __global__ void __launch_bounds__(MERGE_BLOCK) k_agg_tiny_merge(const AggSpec A,
     const u64* cellsb = (const u64*)(workspace + (size_t)b * partial_stride + cells_off);
     for (int a = 0; a < n_accs; ++a) {
       const int kind = A.acc_kind[a];
-      const u64 olo = cellsb[(size_t)(g * n_accs + a) * 2], ohi = cellsb[(size_t)(g * n_accs + a) * 2 + 1];
-      u64* dst = &fcells[((size_t)f * n_accs + a) * 2];
-      switch (kind) {
-        case ACC_SUM: case ACC_COUNT: case ACC_COUNT_STAR: {
-          const u64 old = atomicAdd(dst, olo);
-          const u64 carry = (old + olo < old) ? 1 : 0;
-          if (ohi + carry) atomicAdd(dst + 1, ohi + carry);
-          break;
-        }
-        case ACC_MIN: atomicMin((long long*)dst, (long long)olo); break;
-        case ACC_MAX: atomicMax((long long*)dst, (long long)olo); break;
-        case ACC_FMIN: case ACC_FMAX: {
-          u64 cur = lds_ld(dst);
-          for (;;) {
-            const bool better = (kind == ACC_FMIN) ? (f64_total_key(olo) < f64_total_key(cur)) : (f64_total_key(olo) > f64_total_key(cur));
-            if (!better) break;
-            const u64 seen = atomicCAS(dst, cur, olo);
-            if (seen == cur) break;
-            cur = seen;
-          }
-          break;
-        }
-        default: break;
-      }
+      if (kind == ACC_FSUM) continue;      // not here: float sums are added in block order below, exactly once
+      acc_fold<__HIP_MEMORY_SCOPE_WORKGROUP>(&fcells[((size_t)f * n_accs + a) * 2], kind, cellsb[(size_t)(g * n_accs + a) * 2], cellsb[(size_t)(g * n_accs + a) * 2 + 1]);
     }
   }
   __syncthreads();
@@ -740,10 +679,8 @@ __global__ void __launch_bounds__(MERGE_BLOCK) k_agg_tiny_merge(const AggSpec A,
     __syncthreads();
   }
   for (int c = tid; c < nf * n_accs; c += MERGE_BLOCK) {
-    const int kind = A.acc_kind[c % n_accs];
-    u64 lo = fcells[2 * c], hi = fcells[2 * c + 1];
-    if (kind == ACC_MIN || kind == ACC_MAX) hi = (u64)((i64)lo >> 63);
-    out.cells[(size_t)c * 2] = lo; out.cells[(size_t)c * 2 + 1] = hi;
+    const u64 lo = fcells[2 * c];
+    out.cells[(size_t)c * 2] = lo; out.cells[(size_t)c * 2 + 1] = acc_result_hi(A.acc_kind[c % n_accs], lo, fcells[2 * c + 1]);
   }
   for (int i = tid; i < nf * kstride * 2; i += MERGE_BLOCK) out.keys[i] = fkeys[i];
   for (int i = tid; i < nf; i += MERGE_BLOCK) out.key_nulls[i] = fnulls[i];

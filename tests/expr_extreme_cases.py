@@ -324,3 +324,62 @@ def substr_is_exact(values, start, length):
         if keep and (skip + keep > 15 or any(x >= 0x80 for x in b[:skip + keep])):
             return False
     return True
+
+
+# ------------------------------------------------------------------------------------------------ float accumulators, every strategy
+FLOAT_ACC_RUNS = (1, 2, 63, 64, 65, 130)      # key runs that start, end and span a 64-lane wave
+_FMAX = 1.7976931348623157e308
+_FX_ALL = [0.0, -0.0, float("inf"), float("-inf"), 5e-324, _FMAX, -_FMAX, float("nan"), None]
+# fx by group: 0-2 everything; 3 the zeros and the subnormal; 4 the two zeros alone (MIN is -0.0, MAX +0.0 only under the total
+# order); 5 everything but NaN; 6 NULL in every row
+_FX_BY_GROUP = [_FX_ALL, _FX_ALL, _FX_ALL, [5e-324, 0.0, -0.0, None], [0.0, -0.0, None, -0.0, 0.0], [v for v in _FX_ALL if v == v], [None]]
+_ACC_INTS = [-2**63, 2**63 - 1, 0, -1, 1, 2**62, -2**62, 2**53 + 1, None, 7]
+_ACC_TABLES = {}
+
+
+def float_acc_table(order):
+    """2275 rows, 7 groups.  "clustered": key runs of every FLOAT_ACC_RUNS length for every key, neighbouring runs under different
+    keys; "shuffled": the same rows in a fixed random order.  fx: Float64 specials (_FX_BY_GROUP), fs: Float64 multiples of 2^-10
+    below 2^20 in magnitude (any sum of them in any order is exact), i: Int64 with both bounds.  id is the clustered row number."""
+    if order not in _ACC_TABLES:
+        import random
+        g = [r % 7 for r in range(42) for _ in range(FLOAT_ACC_RUNS[r % 6])]
+        n = len(g)
+        fx = [_FX_BY_GROUP[k][i % len(_FX_BY_GROUP[k])] for i, k in enumerate(g)]
+        fs = [None if i % 13 == 5 else ((i * 2654435761) % (2**30) - 2**29) / 1024.0 for i in range(n)]
+        iv = [None if k == 6 else _ACC_INTS[i % len(_ACC_INTS)] for i, k in enumerate(g)]
+        rows = list(range(n))
+        if order == "shuffled":
+            random.Random(20240607).shuffle(rows)
+        else:
+            assert order == "clustered"
+        cols = {"id": rows, "g": [g[r] for r in rows], "fx": [fx[r] for r in rows], "fs": [fs[r] for r in rows], "i": [iv[r] for r in rows]}
+        _ACC_TABLES[order] = Table("float_acc_" + order, [("id", "Int32"), ("g", "Int32"), ("fx", "Float64"), ("fs", "Float64"), ("i", "Int64")], cols)
+    return _ACC_TABLES[order]
+
+
+def f64_total_key(x):
+    """IEEE-754 totalOrder of a double as a signed integer, from its bit pattern: what the project defines MIN / MAX of Float64 by."""
+    b = X.f64_bits(x)
+    s = b - 2**64 if b >= 2**63 else b
+    return s ^ 0x7FFFFFFFFFFFFFFF if s < 0 else s
+
+
+def fkey_or(x):
+    """A value as something == compares bit for bit: a double's bit pattern (NaN included), anything else itself."""
+    return X.f64_bits(x) if isinstance(x, float) else x
+
+
+def float_acc_reference(t):
+    """{group: {accumulator name: value}}: MIN / MAX of fx by the total order, SUM of fs in exact rationals, MIN / MAX of i, the counts."""
+    import fractions
+    out = {}
+    for k in sorted(set(t.cols["g"])):
+        at = [j for j, gk in enumerate(t.cols["g"]) if gk == k]
+        fx, fs, iv = ([t.cols[c][j] for j in at if t.cols[c][j] is not None] for c in ("fx", "fs", "i"))
+        total = sum(fractions.Fraction(v) for v in fs)
+        assert fractions.Fraction(float(total)) == total
+        out[k] = {"min_fx": min(fx, key=f64_total_key) if fx else None, "max_fx": max(fx, key=f64_total_key) if fx else None,
+                  "sum_fs": float(total) if fs else None, "cnt_fs": len(fs), "cnt_all": len(at),
+                  "min_i": min(iv) if iv else None, "max_i": max(iv) if iv else None, "cnt_i": len(iv)}
+    return out

@@ -256,3 +256,41 @@ def test_decimal_to_integer_cast_known_answers():
                         (dl(25549, 15, 2), "UInt8", 255), (dl(25550, 15, 2), "UInt8", 0), (dl(-100, 15, 2), "UInt8", 255),
                         (dl(2**63 * 10, 25, 1), "Int64", -2**63), (dl(10**19, 20, 0), "Int64", 10**19 - 2**64)):
         assert one(cast(e, to)) == (to, want), (e, to)
+
+
+def test_float_accumulator_tables_hold_what_they_claim():
+    """The table of test_float_accumulators_under_every_strategy: its run lengths, its special groups, and float sums that are exact
+    whatever the order of the adds (every prefix sum, per group and overall, in both row orders)."""
+    import fractions
+    c, sh = K.float_acc_table("clustered"), K.float_acc_table("shuffled")
+    assert c.n == sh.n <= 4096 and sorted(sh.cols["id"]) == c.cols["id"] and sh.cols["id"] != c.cols["id"]
+    for name in ("g", "fx", "fs", "i"):
+        by_id = dict(zip(sh.cols["id"], sh.cols[name]))
+        assert [K.fkey_or(v) for v in c.cols[name]] == [K.fkey_or(by_id[i]) for i in c.cols["id"]]          # the same rows
+    runs, start = {}, 0
+    for j in range(1, c.n + 1):
+        if j == c.n or c.cols["g"][j] != c.cols["g"][start]:
+            runs.setdefault(c.cols["g"][start], set()).add(j - start)
+            start = j
+    assert all(runs[k] == set(K.FLOAT_ACC_RUNS) for k in range(7))
+    fx = {k: [v for v, gk in zip(c.cols["fx"], c.cols["g"]) if gk == k] for k in range(7)}
+    assert all(v is None for v in fx[6]) and not any(v is not None and v != v for v in fx[5]) and any(v is not None and v != v for v in fx[0])
+    seen = {K.fkey_or(v) for v in c.cols["fx"]}
+    assert {K.fkey_or(v) for v in (0.0, -0.0, float("inf"), float("-inf"), 5e-324, 1.7976931348623157e308, -1.7976931348623157e308, float("nan"), None)} <= seen
+    assert X.f64_bits(pa.array([float("nan")], pa.float64())[0].as_py()) == 0x7FF8000000000000
+    assert {-2**63, 2**63 - 1, None} <= set(c.cols["i"])
+    for t in (c, sh):
+        for group in [None] + list(range(7)):
+            acc, exact = 0.0, fractions.Fraction(0)
+            for v, gk in zip(t.cols["fs"], t.cols["g"]):
+                if v is None or (group is not None and gk != group):
+                    continue
+                assert float(v * 1024).is_integer() and abs(v * 1024) < 2**30
+                acc += v
+                exact += fractions.Fraction(v)
+                assert fractions.Fraction(acc) == exact
+    ref, ref_sh = K.float_acc_reference(c), K.float_acc_reference(sh)
+    assert all(K.fkey_or(ref[k][n]) == K.fkey_or(ref_sh[k][n]) for k in range(7) for n in ref[k])          # the order of the rows changes no answer
+    assert X.f64_bits(ref[4]["min_fx"]) == 1 << 63 and X.f64_bits(ref[4]["max_fx"]) == 0 and ref[0]["max_fx"] != ref[0]["max_fx"] and ref[5]["max_fx"] == float("inf")
+    ladder = [K.f64_total_key(v) for v in (float("-inf"), -1.7976931348623157e308, -1.0, -0.0, 0.0, 5e-324, 1.7976931348623157e308, float("inf"), float("nan"))]
+    assert ladder == sorted(set(ladder))

@@ -251,8 +251,18 @@ def _agg_table(name, ty, vals):
     return K.Table(name, [("id", "Int32"), ("g", "Int32"), ("a", ty), ("b", ty), ("f", "Float64")], cols)
 
 
-@pytest.mark.parametrize("grouped", [False, True], ids=["ungrouped", "grouped"])
-def test_sum_beyond_64_bits_and_of_mixed_sign_extremes(ev, grouped):
+STRATEGIES = ["tiny", "lds", "hash", "radix", "auto"]
+
+
+def strategy_args(strategy, groups):
+    """AggregateExec keywords that force one strategy; the radix path is sized by the expected number of groups."""
+    return {"strategy": strategy, "expected_groups": groups} if strategy == "radix" else {"strategy": strategy}
+
+
+@pytest.mark.parametrize("grouped,strategy", [(False, "auto")] + [(True, s) for s in STRATEGIES], ids=lambda v: v if isinstance(v, str) else ("grouped" if v else "ungrouped"))
+def test_sum_beyond_64_bits_and_of_mixed_sign_extremes(ev, grouped, strategy):
+    """The carry across 2^64 and the mixed-sign 128-bit sums through every strategy's fold and combine (7 groups x 2 accumulators fit the
+    tiny path; an aggregate without keys has one strategy)."""
     near = [10**18 - 1 - i for i in range(190)] + [None, -(10**18 - 1), 10**17]               # total ~ 1.9e20 > 2^64; per group > 2^64 too
     assert sum(v for v in near if v is not None) > 2**64 * 7
     mixed38 = ([10**38 - 1, -(10**38 - 1), 2**64 + K.PATTERN, -(2**64) - 1, 2**126, -(2**126) + 5, None, 1] * 7 * 3 + [10**37, -3])      # period 8: every group meets every value
@@ -268,9 +278,31 @@ def test_sum_beyond_64_bits_and_of_mixed_sign_extremes(ev, grouped):
             want[k] = X.wrap(sum(vs), "Int64") if st == "Int64" else sum(vs)
             assert st == "Int64" or abs(want[k]) < 10**38
         aggs = [{"fn": "SUM", "expr": col("a", t.schema), "name": "s"}, {"fn": "COUNT", "expr": col("a", t.schema), "name": "c"}]
-        for out in run(ev, g.AggregateExec("Single", [(col("g", t.schema), "g")] if grouped else [], aggs, source(t))):
+        for out in run(ev, g.AggregateExec("Single", [(col("g", t.schema), "g")] if grouped else [], aggs, source(t), **strategy_args(strategy, 7))):
             keys = out["g"].to_pylist() if grouped else [0]
             assert dict(zip(keys, values(out["s"], st))) == want, name
+
+
+@pytest.mark.parametrize("strategy", STRATEGIES)
+@pytest.mark.parametrize("order", ["clustered", "shuffled"])
+def test_float_accumulators_under_every_strategy(ev, order, strategy):
+    """Every accumulator kind over K.float_acc_table under every strategy, bit for bit: MIN / MAX of Float64 specials by the IEEE total
+    order (zeros of both signs, infinities, the subnormal, +-max, NaN, an all-NULL group), a float SUM whose every partial sum is exact,
+    MIN / MAX / COUNT of Int64 at its bounds, COUNT(*).  Clustered keys run through the wave scan of the hash kernel with runs that start,
+    end and span the 64-lane boundary; shuffled keys make every row its own run.  Three plans of three device accumulators each."""
+    t = K.float_acc_table(order)
+    want = K.float_acc_reference(t)
+    s = t.schema
+    plans = [[("MIN", "fx", "min_fx", "Float64"), ("MAX", "fx", "max_fx", "Float64")],
+             [("SUM", "fs", "sum_fs", "Float64"), ("COUNT", "fs", "cnt_fs", "Int64"), ("COUNT", None, "cnt_all", "Int64")],
+             [("MIN", "i", "min_i", "Int64"), ("MAX", "i", "max_i", "Int64"), ("COUNT", "i", "cnt_i", "Int64")]]
+    for accs in plans:
+        aggs = [{"fn": fn, "expr": lit(1) if c is None else col(c, s), "name": n} for fn, c, n, _ in accs]
+        for out in run(ev, g.AggregateExec("Single", [(col("g", s), "g")], aggs, source(t), **strategy_args(strategy, len(want)))):
+            keys = out["g"].to_pylist()
+            assert sorted(keys) == sorted(want)
+            for _, _, n, ty in accs:
+                assert dict(zip(keys, values(out[n], ty))) == {k: (fkey(r[n]) if ty == "Float64" else r[n]) for k, r in want.items()}, (n, strategy, order)
 
 
 @pytest.mark.parametrize("strategy", ["tiny", "lds", "hash", "radix", "auto"])
