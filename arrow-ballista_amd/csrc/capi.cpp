@@ -3,6 +3,7 @@
 // data path runs in the HIP kernels (kernels_*.hip).  There is deliberately no CPU fallback.
 #include "../../include/gpuq.h"
 #include "expr_compile.h"
+#include "agg_compile.h"
 #include "gpuq_kernels.h"
 #include "jit_runtime.h"
 #include "devbuf.h"
@@ -112,15 +113,6 @@ template <class F> int guarded(gpuq_ctx* ctx, F&& f) {
   catch (const Retry& e) { set_err(ctx, e.what()); return GPUQ_ERR_RETRY; }
   catch (const std::bad_alloc&) { set_err(ctx, "out of host memory"); return GPUQ_ERR_INTERNAL; }
   catch (const std::exception& e) { set_err(ctx, e.what()); return GPUQ_ERR_INVALID; }
-}
-
-gpuq_field_info make_field(const std::string& name, const DType& t, bool nullable) {
-  gpuq_field_info f{};
-  std::snprintf(f.name, sizeof(f.name), "%s", name.c_str());
-  f.type = t.id; f.precision = t.p; f.scale = t.s; f.nullable = nullable;
-  f.repr = (t.id == T_UTF8) ? GPUQ_REPR_PACKED15 : GPUQ_REPR_ARROW;
-  f.width = (t.id == T_BOOL) ? 0 : type_width(t);
-  return f;
 }
 
 thread_local bool g_upload = true;   // false inside gpuq_compile_check (no device); per thread: other threads create operators meanwhile
@@ -252,356 +244,6 @@ struct SinkJit {
   }
 };
 
-// ---------------------------------------------------------------- key layout
-KeySpec make_keyspec(const std::vector<int>& regs, const std::vector<DType>& types, bool null_word) {
-  if (regs.size() > (size_t)MAX_KEYS) throw Unsupported("more than " + std::to_string(MAX_KEYS) + " key columns");
-  KeySpec K{};
-  K.n_keys = (int)regs.size(); K.null_word = null_word ? 1 : 0;
-  int w = 0;
-  for (size_t k = 0; k < regs.size(); ++k) {
-    K.key_reg[k] = regs[k];
-    const bool wide = types[k].id == T_DECIMAL128 || types[k].id == T_UTF8;
-    K.key_wide[k] = wide;
-    K.word_reg[w] = regs[k]; K.word_half[w] = 0; ++w;
-    if (wide) { K.word_reg[w] = regs[k]; K.word_half[w] = 1; ++w; }
-  }
-  if (null_word) { K.word_reg[w] = 0; K.word_half[w] = 2; ++w; }
-  K.key_words = w;
-  return K;
-}
-
-// ---------------------------------------------------------------- aggregate compilation
-struct AccDef { int kind; NodeP arg; DType type; };
-
-int find_or_add_acc(std::vector<AccDef>& accs, int kind, NodeP arg, const DType& type) {
-  for (size_t i = 0; i < accs.size(); ++i)
-    if (accs[i].kind == kind && ((!arg && !accs[i].arg) || (arg && accs[i].arg && arg->key == accs[i].arg->key))) return (int)i;
-  if ((int)accs.size() >= MAX_ACCS) throw Unsupported("aggregate needs more than " + std::to_string(MAX_ACCS) + " accumulators");
-  accs.push_back({kind, arg, type}); return (int)accs.size() - 1;
-}
-DType t_of(int id) { DType t; t.id = id; return t; }
-DType dec_t(int p, int s) { DType t; t.id = T_DECIMAL128; t.p = std::min(p, 38); t.s = std::min(s, 38); return t; }
-
-// How one SQL aggregate maps to accumulators (indices into accs) and to output columns.
-struct AggPlan {
-  std::string fn, name;
-  DType arg_type; bool arg_nullable = false;
-  int acc_sum = -1, acc_cnt = -1, acc_mm = -1;   // sum / count / min-max accumulators
-  int acc_sx = -1, acc_sy = -1, acc_sxx = -1, acc_syy = -1, acc_sxy = -1;   // variance family: f64 power sums
-  bool is_float = false;
-};
-
-// VARIANCE / STDDEV / COVARIANCE / CORRELATION (datafusion.proto:639-645).  The reference keeps Welford-style
-// running (count, mean, m2[, algo_const]) states [UPSTREAM-KNOWLEDGE]; a data-parallel device cannot follow a
-// row order, so the accumulators are the order-free power sums n, Sx, Sy, Sxx, Syy, Sxy in f64 and the
-// reference's state columns are derived from them (mean = Sx/n, m2 = Sxx - Sx^2/n, algo = Sxy - Sx*Sy/n).
-// Results agree with the reference to f64 rounding (tolerance stated in tests/test_gpu_operators.py).
-int var_family(const std::string& fn) {   // 1: one-argument (x), 2: two-argument (x, y)
-  if (fn == "VARIANCE" || fn == "VAR" || fn == "VAR_SAMP" || fn == "VARIANCE_POP" || fn == "VAR_POP" ||
-      fn == "STDDEV" || fn == "STDDEV_SAMP" || fn == "STDDEV_POP") return 1;
-  if (fn == "COVARIANCE" || fn == "COVAR" || fn == "COVAR_SAMP" || fn == "COVARIANCE_POP" || fn == "COVAR_POP" ||
-      fn == "CORRELATION" || fn == "CORR") return 2;
-  return 0;
-}
-bool var_is_pop(const std::string& fn) { return fn.size() > 4 && fn.compare(fn.size() - 4, 4, "_POP") == 0; }
-bool var_is_corr(const std::string& fn) { return fn == "CORRELATION" || fn == "CORR"; }
-bool var_is_stddev(const std::string& fn) { return fn.compare(0, 6, "STDDEV") == 0; }
-
-void compile_aggregate(gpuq_op* op, const Json& d) {
-  op->mode = d.get_str("mode", "Single");
-  const bool is_final = (op->mode == "Final" || op->mode == "FinalPartitioned");
-  const bool emit_state = (op->mode == "Partial");
-  if (!is_final && !emit_state && op->mode != "Single") throw std::runtime_error("unknown aggregate mode '" + op->mode + "'");
-  op->strategy = d.get_str("strategy", "auto");
-  op->expected_groups = d.get_i64("expected_groups", 0);
-  ExprCompiler ec(op->in_schema);
-  if (d.has("predicate")) ec.add_predicate(ec.from_json(d.at("predicate")));
-  std::vector<NodeP> key_nodes; std::vector<std::string> key_names;
-  if (d.has("group_expr")) for (const Json& g : d.at("group_expr").a) {
-    NodeP n = ec.from_json(g.at("expr"));
-    key_nodes.push_back(n); key_names.push_back(g.get_str("name", "group" + std::to_string(key_nodes.size() - 1)));
-  }
-  std::vector<AccDef> accs; std::vector<AggPlan> plans;
-  // More than MAX_KEYS group columns (q10 groups by seven, q18 by five): the table still holds at most MAX_KEYS keys of up to 128 bits, so
-  // narrow keys are PACKED -- each biased to a non-negative number of `bits + 1` bits (+ 1 bit "is NULL"), shifted and OR-ed into 126-bit
-  // composites -- and the table groups by the composites.  The declared key columns are unpacked again over the GROUPS (the result
-  // projection divides by powers of two), so the table carries no extra state.  Utf8 / float keys take a slot of their own (the
-  // executor hands long or many Utf8 keys over as dictionary codes, which pack well).
-  std::vector<NodeP> orig_keys = key_nodes; std::vector<std::string> orig_names = key_names;
-  struct Packed { int slot = -1, shift = 0, width = 0; bool own = false; };      // own: the key IS column `slot` of the result
-  std::vector<Packed> pk(orig_keys.size());
-  const bool packed = orig_keys.size() > (size_t)MAX_KEYS;
-  if (packed) {
-    struct Slot { std::vector<size_t> ks; int bits = 0; bool solo = false; };
-    std::vector<Slot> slots;
-    for (size_t k = 0; k < orig_keys.size(); ++k) {
-      const NodeP& n = orig_keys[k];
-      const int b = (n->type.id == T_UTF8 || n->type.is_float() || n->type.id == T_BOOL) ? 0 : n->bits + 1 + (n->nullable ? 1 : 0);
-      if (b == 0 || b > 126) { Slot sl; sl.ks.push_back(k); sl.solo = true; slots.push_back(sl); continue; }
-      bool placed = false;
-      for (auto& sl : slots) if (!sl.solo && sl.bits + b <= 126) { sl.ks.push_back(k); sl.bits += b; placed = true; break; }
-      if (!placed) { Slot sl; sl.ks.push_back(k); sl.bits = b; slots.push_back(sl); }
-    }
-    if (slots.size() > (size_t)MAX_KEYS) op->refuse = std::to_string(orig_keys.size()) + " group-by columns need " + std::to_string(slots.size()) + " packed keys (" + std::to_string(MAX_KEYS) + " are held)";
-    key_nodes.clear(); key_names.clear();
-    const DType wide = dec_t(38, 0);
-    for (size_t si = 0; si < slots.size() && si < (size_t)MAX_KEYS; ++si) {
-      const Slot& sl = slots[si];
-      if (sl.solo) { pk[sl.ks[0]].slot = (int)key_nodes.size(); pk[sl.ks[0]].own = true; key_nodes.push_back(orig_keys[sl.ks[0]]); key_names.push_back(orig_names[sl.ks[0]]); continue; }
-      NodeP acc; int shift = 0;
-      for (size_t k : sl.ks) {
-        const NodeP& n = orig_keys[k];
-        NodeP v = ec.raw(OP_ADD, wide, n->nullable, n->bits + 1, {n, ec.lit_int(wide, (i128)1 << n->bits)});      // |value| < 2^bits  ->  [0, 2^(bits+1))
-        if (n->nullable) {
-          v = ec.coalesce0(v);
-          NodeP flag = ec.raw(OP_SHL, wide, false, n->bits + 2, {ec.raw(OP_MOV, wide, false, 1, {ec.is_null(n, false)})}, (uint32_t)(n->bits + 1));
-          v = ec.raw(OP_BOR, wide, false, n->bits + 2, {v, flag});
-        }
-        NodeP sh = shift ? ec.raw(OP_SHL, wide, false, 127, {v}, (uint32_t)shift) : v;
-        acc = acc ? ec.raw(OP_BOR, wide, false, 127, {acc, sh}) : sh;
-        pk[k].slot = (int)key_nodes.size(); pk[k].shift = shift; pk[k].width = n->bits + 1 + (n->nullable ? 1 : 0);
-        shift += pk[k].width;
-      }
-      key_nodes.push_back(acc); key_names.push_back("__packed" + std::to_string(si));
-    }
-  }
-  size_t state_col = orig_keys.size();   // Final modes: state columns follow the group columns positionally
-  const Json& aggs = d.at("aggr_expr");
-  for (const Json& a : aggs.a) {
-    AggPlan pl; pl.fn = a.at("fn").str(); pl.name = a.get_str("name", pl.fn);
-    for (auto& ch : pl.fn) ch = (char)std::toupper(ch);
-    if (a.get_bool("distinct", false)) throw Unsupported("DISTINCT aggregates are not supported on device");
-    if (!is_final) {
-      NodeP arg = a.has("expr") ? ec.from_json(a.at("expr")) : nullptr;
-      // per-aggregate FILTER (AggregateExecNode.filter_expr, datafusion.proto:1437-1450): agg(x) FILTER (WHERE p) is agg over the rows
-      // where p is true, i.e. agg(CASE WHEN p THEN x END) -- every accumulator here skips NULL arguments; COUNT(*) counts the 1s
-      if (a.has("filter") && !a.at("filter").is_null()) {
-        NodeP p = ec.from_json(a.at("filter"));
-        if (p->type.id != T_BOOL) throw std::runtime_error("aggregate FILTER must be boolean");
-        if (!arg) arg = ec.lit_int(t_of(T_INT64), 1);
-        arg = ec.select(p, arg, ec.lit_null(arg->type));
-        if (a.has("expr2")) throw Unsupported("FILTER on a two-argument aggregate");
-      }
-      if (pl.fn == "COUNT") {
-        if (!arg || !arg->nullable) pl.acc_cnt = find_or_add_acc(accs, ACC_COUNT_STAR, nullptr, t_of(T_INT64));
-        else pl.acc_cnt = find_or_add_acc(accs, ACC_COUNT, arg, t_of(T_INT64));
-        pl.arg_type = t_of(T_INT64);
-      } else {
-        if (!arg) throw std::runtime_error(pl.fn + " needs an argument");
-        pl.arg_type = arg->type; pl.arg_nullable = arg->nullable || key_nodes.empty();   // ungrouped: zero input rows -> NULL
-        auto count_of = [&](NodeP x) { return x->nullable ? find_or_add_acc(accs, ACC_COUNT, x, t_of(T_INT64)) : find_or_add_acc(accs, ACC_COUNT_STAR, nullptr, t_of(T_INT64)); };
-        if (pl.fn == "SUM" || pl.fn == "AVG") {
-          if (arg->type.is_decimal()) {
-            pl.acc_sum = find_or_add_acc(accs, ACC_SUM, arg, dec_t(arg->type.p + 10, arg->type.s));
-          } else if (arg->type.is_int() && pl.fn == "SUM") {
-            // sum_return_type [UPSTREAM-KNOWLEDGE]: signed integers of any width -> Int64, unsigned -> UInt64
-            const DType st = t_of(arg->type.is_unsigned() ? T_UINT64 : T_INT64);
-            NodeP x = ec.cast(arg, st);
-            pl.acc_sum = find_or_add_acc(accs, ACC_SUM, x, st);
-          } else if (arg->type.is_float() || arg->type.is_int()) {
-            NodeP x = ec.cast(arg, t_of(T_FLOAT64)); pl.is_float = true;
-            pl.acc_sum = find_or_add_acc(accs, ACC_FSUM, x, t_of(T_FLOAT64));
-          } else throw Unsupported(pl.fn + " over " + arg->type.to_string());
-          if (pl.fn == "AVG" || pl.arg_nullable) pl.acc_cnt = count_of(arg);
-        } else if (pl.fn == "MIN" || pl.fn == "MAX") {
-          const bool mn = pl.fn == "MIN";
-          if (arg->type.is_float()) { pl.is_float = true; pl.acc_mm = find_or_add_acc(accs, mn ? ACC_FMIN : ACC_FMAX, arg, arg->type); }
-          else if (arg->type.is_int() || arg->type.is_decimal() || arg->type.is_temporal()) pl.acc_mm = find_or_add_acc(accs, mn ? ACC_MIN : ACC_MAX, arg, arg->type);
-          else throw Unsupported(pl.fn + " over " + arg->type.to_string());
-          if (pl.arg_nullable) pl.acc_cnt = count_of(arg);
-        } else if (var_family(pl.fn)) {
-          const DType f64 = t_of(T_FLOAT64);
-          if (!(arg->type.is_float() || arg->type.is_int() || arg->type.is_decimal())) throw Unsupported(pl.fn + " over " + arg->type.to_string());
-          NodeP x = ec.cast(arg, f64), y;
-          pl.is_float = true;
-          if (var_family(pl.fn) == 2) {
-            if (!a.has("expr2")) throw std::runtime_error(pl.fn + " needs two arguments (expr, expr2)");
-            y = ec.cast(ec.from_json(a.at("expr2")), f64);
-            // rows where either argument is NULL are skipped for every sum
-            NodeP both = ec.binary("AND", ec.is_null(x, true), ec.is_null(y, true));
-            if (x->nullable || y->nullable) { NodeP x2 = ec.select(both, x, ec.lit_null(f64)); NodeP y2 = ec.select(both, y, ec.lit_null(f64)); x = x2; y = y2; }
-          }
-          pl.acc_cnt = count_of(x);
-          pl.acc_sx = find_or_add_acc(accs, ACC_FSUM, x, f64);
-          if (var_family(pl.fn) == 1 || var_is_corr(pl.fn)) pl.acc_sxx = find_or_add_acc(accs, ACC_FSUM, ec.binary("*", x, x), f64);
-          if (y) {
-            pl.acc_sy = find_or_add_acc(accs, ACC_FSUM, y, f64);
-            pl.acc_sxy = find_or_add_acc(accs, ACC_FSUM, ec.binary("*", x, y), f64);
-            if (var_is_corr(pl.fn)) pl.acc_syy = find_or_add_acc(accs, ACC_FSUM, ec.binary("*", y, y), f64);
-          }
-        } else throw Unsupported("aggregate function " + pl.fn);
-      }
-    } else {
-      // merge of partial states: columns arrive positionally after the group columns
-      auto state = [&](void) { if (state_col >= op->in_schema.fields.size()) throw std::runtime_error("Final aggregate: input has too few state columns"); return ec.column((int)state_col++); };
-      if (pl.fn == "COUNT") { NodeP c = state(); pl.acc_cnt = find_or_add_acc(accs, ACC_SUM, ec.cast(c, t_of(T_INT64)), t_of(T_INT64)); pl.arg_type = t_of(T_INT64); }
-      else if (pl.fn == "SUM") {
-        NodeP s = state(); pl.arg_type = s->type; pl.arg_nullable = s->nullable || key_nodes.empty();
-        if (s->type.is_float()) { pl.is_float = true; pl.acc_sum = find_or_add_acc(accs, ACC_FSUM, ec.coalesce0(s), s->type); }
-        else pl.acc_sum = find_or_add_acc(accs, ACC_SUM, s, s->type);
-        if (pl.arg_nullable) pl.acc_cnt = s->nullable ? find_or_add_acc(accs, ACC_COUNT, s, t_of(T_INT64)) : find_or_add_acc(accs, ACC_COUNT_STAR, nullptr, t_of(T_INT64));
-      } else if (pl.fn == "AVG") {
-        NodeP c = state(); NodeP s = state(); pl.arg_type = s->type;
-        pl.acc_cnt = find_or_add_acc(accs, ACC_SUM, ec.cast(c, t_of(T_INT64)), t_of(T_INT64));
-        if (s->type.is_float()) { pl.is_float = true; pl.acc_sum = find_or_add_acc(accs, ACC_FSUM, ec.coalesce0(s), s->type); }
-        else pl.acc_sum = find_or_add_acc(accs, ACC_SUM, s, s->type);
-      } else if (pl.fn == "MIN" || pl.fn == "MAX") {
-        NodeP s = state(); const bool mn = pl.fn == "MIN"; pl.arg_type = s->type; pl.arg_nullable = s->nullable || key_nodes.empty();
-        if (s->type.is_float()) { pl.is_float = true; pl.acc_mm = find_or_add_acc(accs, mn ? ACC_FMIN : ACC_FMAX, s, s->type); }
-        else pl.acc_mm = find_or_add_acc(accs, mn ? ACC_MIN : ACC_MAX, s, s->type);
-        if (pl.arg_nullable) pl.acc_cnt = s->nullable ? find_or_add_acc(accs, ACC_COUNT, s, t_of(T_INT64)) : find_or_add_acc(accs, ACC_COUNT_STAR, nullptr, t_of(T_INT64));
-      } else if (var_family(pl.fn)) {
-        // reference state columns: VAR/STDDEV [count, mean, m2]; COVAR [count, mean1, mean2, algo_const];
-        // CORR [count, mean1, m2_1, mean2, m2_2, algo_const] [UPSTREAM-KNOWLEDGE].  Back to power sums, then add.
-        const DType f64 = t_of(T_FLOAT64); pl.is_float = true;
-        NodeP c = state(); NodeP cf = ec.cast(c, f64);
-        auto fs = [&](NodeP e) { return find_or_add_acc(accs, ACC_FSUM, ec.coalesce0(e), f64); };
-        auto mul = [&](NodeP l, NodeP r) { return ec.binary("*", l, r); };
-        auto add = [&](NodeP l, NodeP r) { return ec.binary("+", l, r); };
-        pl.acc_cnt = find_or_add_acc(accs, ACC_SUM, ec.cast(c, t_of(T_INT64)), t_of(T_INT64));
-        if (var_family(pl.fn) == 1) {
-          NodeP mean = ec.cast(state(), f64), m2 = ec.cast(state(), f64);
-          pl.acc_sx = fs(mul(cf, mean)); pl.acc_sxx = fs(add(m2, mul(cf, mul(mean, mean))));
-        } else if (!var_is_corr(pl.fn)) {
-          NodeP m1 = ec.cast(state(), f64), m2 = ec.cast(state(), f64), al = ec.cast(state(), f64);
-          pl.acc_sx = fs(mul(cf, m1)); pl.acc_sy = fs(mul(cf, m2)); pl.acc_sxy = fs(add(al, mul(cf, mul(m1, m2))));
-        } else {
-          NodeP m1 = ec.cast(state(), f64), v1 = ec.cast(state(), f64), m2 = ec.cast(state(), f64), v2 = ec.cast(state(), f64), al = ec.cast(state(), f64);
-          pl.acc_sx = fs(mul(cf, m1)); pl.acc_sxx = fs(add(v1, mul(cf, mul(m1, m1))));
-          pl.acc_sy = fs(mul(cf, m2)); pl.acc_syy = fs(add(v2, mul(cf, mul(m2, m2))));
-          pl.acc_sxy = fs(add(al, mul(cf, mul(m1, m2))));
-        }
-      } else throw Unsupported("aggregate function " + pl.fn);
-    }
-    plans.push_back(pl);
-  }
-  if (accs.empty()) find_or_add_acc(accs, ACC_COUNT_STAR, nullptr, t_of(T_INT64));   // GROUP BY without aggregates still needs a cell
-  // scan program outputs: keys then accumulator arguments
-  std::vector<int> key_slots, acc_slots(accs.size(), -1);
-  for (auto& k : key_nodes) key_slots.push_back(ec.add_output(k));
-  for (size_t i = 0; i < accs.size(); ++i) if (accs[i].arg) acc_slots[i] = ec.add_output(accs[i].arg);
-  op->prog = ec.finish();
-  upload_code(op->prog, op->code_dev);
-  op->agg = AggSpec{};
-  op->agg.n_keys = (int)key_nodes.size(); op->agg.n_accs = (int)accs.size();
-  std::vector<int> kregs; bool any_null_key = false;
-  for (size_t k = 0; k < key_nodes.size(); ++k) {
-    op->agg.key_reg[k] = op->prog.out_reg[key_slots[k]]; kregs.push_back(op->agg.key_reg[k]);
-    op->key_types.push_back(key_nodes[k]->type); any_null_key = any_null_key || key_nodes[k]->nullable;
-    if (key_nodes[k]->type.id == T_BOOL || key_nodes[k]->type.id == T_NULL) throw Unsupported("group-by key of type " + key_nodes[k]->type.to_string());
-  }
-  for (size_t i = 0; i < accs.size(); ++i) {
-    op->agg.acc_kind[i] = accs[i].kind; op->agg.acc_reg[i] = accs[i].arg ? op->prog.out_reg[acc_slots[i]] : 0;
-    op->acc_types.push_back(accs[i].type);
-    op->acc_bits.push_back(accs[i].arg ? op->prog.out_bits[acc_slots[i]] : 1);
-  }
-  op->keys = make_keyspec(kregs, op->key_types, any_null_key);
-
-  // post program over the SoA result: [key_0.., acc_0..] as raw (lo,hi) columns
-  for (size_t k = 0; k < key_nodes.size(); ++k) { Field f; f.name = key_names[k]; f.type = key_nodes[k]->type; f.nullable = key_nodes[k]->nullable; f.raw128 = 1; op->post_schema.fields.push_back(f); }
-  for (size_t i = 0; i < accs.size(); ++i) { Field f; f.name = "acc" + std::to_string(i); f.type = accs[i].type; f.nullable = false; f.raw128 = 1; op->post_schema.fields.push_back(f); }
-  const int nk = (int)key_nodes.size();
-  // The post program runs in the same 16-register machine: when all outputs do not fit, the plan list is split and
-  // each chunk becomes its own program over the same SoA columns (a few extra launches over <= n_groups rows).
-  auto build_chunk = [&](ExprCompiler& pc, size_t lo, size_t hi, bool with_keys, std::vector<std::string>& out_names) {
-  if (with_keys && !packed) for (int k = 0; k < nk; ++k) { pc.add_output(pc.column(k)); out_names.push_back(key_names[k]); }
-  if (with_keys && packed) for (size_t k = 0; k < orig_keys.size(); ++k) {      // the group columns in their declared order, unpacked
-    const NodeP& n = orig_keys[k];
-    if (pk[k].slot < 0) { pc.add_output(pc.lit_null(n->type)); out_names.push_back(orig_names[k]); continue; }      // (refused operator: types only)
-    if (pk[k].own) { pc.add_output(pc.column(pk[k].slot)); out_names.push_back(orig_names[k]); continue; }
-    const DType wide = dec_t(38, 0);
-    NodeP f = pc.column(pk[k].slot);      // non-negative, < 2^126: truncating division is the shift
-    if (pk[k].shift) f = pc.raw(OP_DIV, wide, false, 127, {f, pc.lit_int(wide, (i128)1 << pk[k].shift)});
-    f = pc.raw(OP_MOD, wide, false, pk[k].width, {f, pc.lit_int(wide, (i128)1 << pk[k].width)});
-    NodeP v = pc.raw(OP_SUB, n->type, false, n->bits, {f, pc.lit_int(wide, (i128)1 << n->bits)});
-    if (n->nullable) v = pc.select(pc.raw(OP_GE, t_of(T_BOOL), false, 2, {f, pc.lit_int(wide, (i128)1 << (n->bits + 1))}), pc.lit_null(n->type), v);
-    pc.add_output(v); out_names.push_back(orig_names[k]);
-  }
-  for (size_t pi = lo; pi < hi; ++pi) {
-    const AggPlan& pl = plans[pi];
-    auto acc = [&](int i) { return pc.column(nk + i); };
-    auto guard = [&](NodeP v) { return pl.acc_cnt >= 0 && (pl.arg_nullable) ? pc.nullif0(v, acc(pl.acc_cnt)) : v; };
-    if (pl.fn == "COUNT") { pc.add_output(acc(pl.acc_cnt)); out_names.push_back(emit_state ? pl.name + "[count]" : pl.name); }
-    else if (pl.fn == "SUM") { pc.add_output(guard(acc(pl.acc_sum))); out_names.push_back(emit_state ? pl.name + "[sum]" : pl.name); }
-    else if (pl.fn == "MIN" || pl.fn == "MAX") { pc.add_output(guard(acc(pl.acc_mm))); out_names.push_back(emit_state ? pl.name + (pl.fn == "MIN" ? "[min]" : "[max]") : pl.name); }
-    else if (var_family(pl.fn)) {
-      const DType f64 = t_of(T_FLOAT64);
-      auto F = [&](int op_, NodeP l, NodeP r) { return pc.raw(op_, f64, false, 127, {l, r}); };
-      NodeP n = acc(pl.acc_cnt), nf = pc.cast(n, f64), zero = pc.lit_f64(0.0);
-      NodeP n_is0 = pc.binary("=", n, pc.lit_int(t_of(T_INT64), 0));
-      NodeP n_le1 = pc.binary("<=", n, pc.lit_int(t_of(T_INT64), 1));
-      auto when0 = [&](NodeP v) { return pc.select(n_is0, zero, v); };                    // state columns of an empty group are 0
-      auto centred = [&](int sab, int sa, int sb) { return when0(F(OP_FSUB, acc(sab), F(OP_FDIV, F(OP_FMUL, acc(sa), acc(sb)), nf))); };
-      auto nonneg = [&](NodeP v) { return pc.select(pc.raw(OP_FLT, t_of(T_BOOL), false, 1, {v, zero}), zero, v); };   // rounding can leave -eps
-      NodeP mean_x = when0(F(OP_FDIV, acc(pl.acc_sx), nf));
-      NodeP m2x = pl.acc_sxx >= 0 ? nonneg(centred(pl.acc_sxx, pl.acc_sx, pl.acc_sx)) : nullptr;
-      NodeP mean_y = pl.acc_sy >= 0 ? when0(F(OP_FDIV, acc(pl.acc_sy), nf)) : nullptr;
-      NodeP m2y = pl.acc_syy >= 0 ? nonneg(centred(pl.acc_syy, pl.acc_sy, pl.acc_sy)) : nullptr;
-      NodeP cxy = pl.acc_sxy >= 0 ? centred(pl.acc_sxy, pl.acc_sx, pl.acc_sy) : nullptr;
-      auto out = [&](NodeP v, const std::string& nm) { pc.add_output(v); out_names.push_back(nm); };
-      if (emit_state) {
-        out(pc.cast(n, t_of(T_UINT64)), pl.name + "[count]");
-        if (var_family(pl.fn) == 1) { out(mean_x, pl.name + "[mean]"); out(m2x, pl.name + "[m2]"); }
-        else if (!var_is_corr(pl.fn)) { out(mean_x, pl.name + "[mean1]"); out(mean_y, pl.name + "[mean2]"); out(cxy, pl.name + "[algoConst]"); }
-        else { out(mean_x, pl.name + "[mean1]"); out(m2x, pl.name + "[m2_1]"); out(mean_y, pl.name + "[mean2]"); out(m2y, pl.name + "[m2_2]"); out(cxy, pl.name + "[algoConst]"); }
-      } else {
-        const bool pop = var_is_pop(pl.fn);
-        NodeP null64 = pc.lit_null(f64);
-        NodeP denom = pop ? nf : F(OP_FSUB, nf, pc.lit_f64(1.0));
-        NodeP undefined = pop ? n_is0 : n_le1;                                            // sample statistics need n >= 2, population n >= 1
-        if (var_family(pl.fn) == 1) {
-          NodeP v = F(OP_FDIV, m2x, denom);
-          if (var_is_stddev(pl.fn)) v = pc.raw(OP_FSQRT, f64, false, 127, {v});
-          out(pc.select(undefined, null64, v), pl.name);
-        } else if (!var_is_corr(pl.fn)) {
-          out(pc.select(undefined, null64, F(OP_FDIV, cxy, denom)), pl.name);
-        } else {
-          // corr = cov_pop / (sd_pop_x * sd_pop_y); 0 when either deviation is 0; NULL over no rows
-          NodeP sx = pc.raw(OP_FSQRT, f64, false, 127, {F(OP_FDIV, m2x, nf)}), sy = pc.raw(OP_FSQRT, f64, false, 127, {F(OP_FDIV, m2y, nf)});
-          NodeP flat = pc.binary("OR", pc.raw(OP_FEQ, t_of(T_BOOL), false, 1, {sx, zero}), pc.raw(OP_FEQ, t_of(T_BOOL), false, 1, {sy, zero}));
-          NodeP v = F(OP_FDIV, F(OP_FDIV, F(OP_FDIV, cxy, nf), sx), sy);
-          out(pc.select(n_is0, null64, pc.select(flat, zero, v)), pl.name);
-        }
-      }
-    }
-    else if (pl.fn == "AVG") {
-      if (emit_state) {
-        pc.add_output(pc.cast(acc(pl.acc_cnt), t_of(T_UINT64))); out_names.push_back(pl.name + "[count]");
-        pc.add_output(guard(acc(pl.acc_sum))); out_names.push_back(pl.name + "[sum]");
-      } else if (pl.is_float) {
-        NodeP cnt = pc.cast(acc(pl.acc_cnt), t_of(T_FLOAT64));
-        pc.add_output(pc.nullif0(pc.raw(OP_FDIV, t_of(T_FLOAT64), true, 127, {acc(pl.acc_sum), cnt}), acc(pl.acc_cnt))); out_names.push_back(pl.name);
-      } else {
-        // Decimal AVG: sum * 10^(s_avg - s_sum) / count, truncating; count == 0 -> NULL (OP_DIV by zero)
-        const DType st = op->acc_types[pl.acc_sum];
-        // the sum state is Decimal(min(38,p+10), s); the argument was Decimal(p, s)
-        const int arg_p = is_final ? std::max(1, st.p - 10) : pl.arg_type.p;
-        const DType rt = dec_t(arg_p + 4, st.s + 4);
-        NodeP scaled = pc.raw(OP_MUL, rt, false, 127, {acc(pl.acc_sum), pc.lit_int(dec_t(38, 0), pow10_i128(rt.s - st.s))});
-        pc.add_output(pc.raw(OP_DIV, rt, true, 127, {scaled, acc(pl.acc_cnt)})); out_names.push_back(pl.name);
-      }
-    }
-  }
-  };
-  std::function<void(size_t, size_t, bool)> emit = [&](size_t lo, size_t hi, bool with_keys) {
-    ExprCompiler pc(op->post_schema);
-    std::vector<std::string> names; CompiledProgram cp;
-    try { build_chunk(pc, lo, hi, with_keys, names); cp = pc.finish(); }
-    catch (const Unsupported&) { throw; }
-    catch (const std::runtime_error&) {
-      if (hi - lo + (with_keys ? 1 : 0) <= 1) throw;
-      if (with_keys && hi > lo) { emit(lo, lo, true); emit(lo, hi, false); }
-      else { const size_t mid = lo + (hi - lo) / 2; emit(lo, mid, with_keys); emit(mid, hi, false); }
-      return;
-    }
-    if (cp.out_reg.empty()) return;
-    op->posts.emplace_back(); gpuq_op::PostChunk& pcn = op->posts.back();
-    pcn.prog = cp; upload_code(pcn.prog, pcn.code); pcn.first_out = (int)op->out_fields.size();
-    for (size_t i = 0; i < cp.out_type.size(); ++i) op->out_fields.push_back(make_field(names[i], cp.out_type[i], cp.out_nullable[i]));
-  };
-  emit(0, plans.size(), true);
-}
-
 OutSpec make_outspec(const CompiledProgram& cp, gpuq_column* outs, int n_outs, const std::vector<gpuq_field_info>& fields) {
   if (n_outs != (int)cp.out_reg.size()) throw std::runtime_error("expected " + std::to_string(cp.out_reg.size()) + " output columns, got " + std::to_string(n_outs));
   if (n_outs > MAX_OUTS) throw Unsupported("more than " + std::to_string(MAX_OUTS) + " output columns in one call");
@@ -688,7 +330,17 @@ static void compile_op(gpuq_op* op, const Json& d) {
       op->prog = ec.finish(); upload_code(op->prog, op->code_dev);
       for (size_t i = 0; i < names.size(); ++i) op->out_fields.push_back(make_field(names[i], op->prog.out_type[i], op->prog.out_nullable[i]));
     } else if (kind == "aggregate") {
-      op->kind = K_AGG; compile_aggregate(op, d);
+      op->kind = K_AGG;
+      AggCompiled c = compile_aggregate(op->in_schema, d);
+      op->mode = c.mode; op->strategy = c.strategy; op->expected_groups = c.expected_groups; op->refuse = c.refuse;
+      op->prog = std::move(c.prog); upload_code(op->prog, op->code_dev);
+      op->agg = c.agg; op->keys = c.keys;
+      op->key_types = std::move(c.key_types); op->acc_types = std::move(c.acc_types); op->acc_bits = std::move(c.acc_bits);
+      op->post_schema = std::move(c.post_schema); op->out_fields = std::move(c.out_fields);
+      for (AggCompiled::Post& p : c.posts) {
+        op->posts.emplace_back(); gpuq_op::PostChunk& pc = op->posts.back();
+        pc.prog = std::move(p.prog); pc.first_out = p.first_out; upload_code(pc.prog, pc.code);
+      }
     } else if (kind == "join_build" || kind == "join_probe") {
       op->kind = kind == "join_build" ? K_JOIN_BUILD : K_JOIN_PROBE;
       ExprCompiler ec(op->in_schema);
@@ -802,7 +454,9 @@ int gpuq_compile_check(const char* json, char* buf, size_t cap) {
     g_upload = true;
     std::string r = "{\"program\":" + describe_program(op->prog, op->in_schema);
     if (op->kind == K_AGG) {
-      r += ",\"post\":" + describe_program(op->posts.front().prog, op->post_schema) + ",\"post_programs\":" + std::to_string(op->posts.size()) + ",\"acc_kinds\":[";
+      r += ",\"post\":" + describe_program(op->posts.front().prog, op->post_schema) + ",\"post_programs\":" + std::to_string(op->posts.size()) + ",\"posts\":[";
+      for (size_t i = 0; i < op->posts.size(); ++i) { if (i) r += ","; r += describe_program(op->posts[i].prog, op->post_schema); }
+      r += "],\"acc_kinds\":[";
       for (int a = 0; a < op->agg.n_accs; ++a) { if (a) r += ","; r += std::to_string(op->agg.acc_kind[a]); }
       r += "]";
     }

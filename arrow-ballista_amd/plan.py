@@ -612,9 +612,9 @@ def _field_from_desc(o):
 
 class AggregateExec(ExecutionPlan):
     """AggregateExec(mode, group_expr, aggr_expr, input) -- datafusion.proto:1405-1450.
-    group_expr: [(expr, name)];  aggr_expr: [{"fn": "SUM"|"AVG"|"COUNT"|"MIN"|"MAX"|"VARIANCE[_POP]"|"STDDEV[_POP]"|
-    "COVARIANCE[_POP]"|"CORRELATION", "expr": e[, "expr2": e2], "name": n}]  (function names: datafusion.proto:631-669).
-    Modes: Partial (emits state columns), Final / FinalPartitioned (merge states), Single."""
+    group_expr: [(expr, name)];  aggr_expr: [{"fn": f, "expr": e[, "expr2": e2], "name": n}]; the function names (those of
+    datafusion.proto:631-669 and their aliases) and each function's state columns are listed with the operator descriptors in
+    include/gpuq.h.  Modes: Partial (emits state columns), Final / FinalPartitioned (merge states), Single."""
 
     def __init__(self, mode, group_expr, aggr_expr, input, strategy="auto", expected_groups=0):
         super().__init__()

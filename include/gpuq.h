@@ -240,7 +240,18 @@ const char* gpuq_scan_last_error(void);
      "filter"      FilterExec        {input, predicate}
      "project"     ProjectionExec    {input, exprs:[{expr,name}]}
      "aggregate"   AggregateExec     {input, mode:Partial|Final|FinalPartitioned|Single, group_expr:[{expr,name}],
-                                      aggr_expr:[{fn:SUM|AVG|COUNT|MIN|MAX, expr, name}], predicate?, strategy?:auto|tiny|hash|lds|radix, expected_groups?}
+                                      aggr_expr:[{fn, expr, expr2?, name, filter?}], predicate?, strategy?:auto|tiny|hash|lds|radix, expected_groups?}
+                   fn (any letter case; one row of AGG_FNS in csrc/agg_compile.cpp each) and the state columns "<name>[..]" its Partial emits
+                   and its Final reads, by position, after the group columns:
+                     COUNT (expr optional: COUNT(*))                   [count]
+                     SUM                                               [sum]
+                     AVG                                               [count] [sum]
+                     MIN | MAX                                         [min] | [max]
+                     VARIANCE = VAR = VAR_SAMP, VARIANCE_POP = VAR_POP,
+                     STDDEV = STDDEV_SAMP, STDDEV_POP                  [count] [mean] [m2]
+                     COVARIANCE = COVAR = COVAR_SAMP,
+                     COVARIANCE_POP = COVAR_POP   (expr, expr2)        [count] [mean1] [mean2] [algoConst]
+                     CORRELATION = CORR           (expr, expr2)        [count] [mean1] [m2_1] [mean2] [m2_2] [algoConst]
      "join_build"  HashJoinExec build (left) side  {input, on:[expr], predicate?, null_equals_null?,
                                                      build_side_rows?: false = gpuq_join_build_side_rows will not be called (Inner / Right / RightSemi / RightAnti)}
      "join_probe"  HashJoinExec probe (right) side {input, on:[expr], predicate?, join_type, null_equals_null?}
@@ -250,7 +261,8 @@ const char* gpuq_scan_last_error(void);
    through index vector k of the call (late materialisation after a filter or join). */
 int gpuq_op_create(gpuq_ctx* ctx, const char* json, gpuq_op** out);
 /* Host-only: compiles the descriptor without a device and writes a JSON description (program
-   listing, output schema) to buf.  Used for plan validation and by the CPU test-suite. */
+   listing, output schema; an aggregate also "posts": every program of its result projection, in order, "post" being the first
+   and "post_programs" their number) to buf.  Used for plan validation and by the CPU test-suite. */
 int gpuq_compile_check(const char* json, char* buf, size_t cap);
 /* Host-only: the source the JIT path would hand to hiprtc for this descriptor and sink kernel id. */
 int gpuq_compile_jit_source(const char* json, int kernel_id, char* buf, size_t cap);
