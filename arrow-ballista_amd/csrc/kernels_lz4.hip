@@ -738,17 +738,19 @@ void launch_unpack_pages_pj(hipStream_t s, const uint8_t* src, uint8_t* dst, con
   if (n_jobs <= 0) return;
   // front: which positions of the compressed streams are elements, and where their output goes
   hipLaunchKernelGGL(k_sn_head, dim3((unsigned)n_jobs), dim3(64), 0, s, src, dst, jobs, n_jobs, B.mark, B.resolve, status);
-  if (B.n_cblocks <= 0 || B.n_blocks <= 0) return;
-  hipLaunchKernelGGL(k_sn_next, dim3((unsigned)B.n_cblocks), dim3(256), 0, s, src, B.cmap, jobs, B.jump_a, B.olen);
-  uint32_t* ja = B.jump_a; uint32_t* jb = B.jump_b;
-  for (int r = 0; r < B.mark_rounds; ++r) {
-    hipLaunchKernelGGL(k_sn_mark, dim3((unsigned)B.n_cblocks), dim3(256), 0, s, B.cmap, jobs, (const uint32_t*)ja, jb, B.mark, B.counts + (size_t)r * n_jobs, B.counts + (size_t)(r + 1) * n_jobs, r == 0 ? 1 : 0);
-    std::swap(ja, jb);
+  if (B.n_blocks <= 0) return;
+  if (B.n_cblocks > 0) {      // (none: a linked LZ4 frame of stored blocks only -- k_sn_head has written every word, k_snappy_emit still has to write the bytes)
+    hipLaunchKernelGGL(k_sn_next, dim3((unsigned)B.n_cblocks), dim3(256), 0, s, src, B.cmap, jobs, B.jump_a, B.olen);
+    uint32_t* ja = B.jump_a; uint32_t* jb = B.jump_b;
+    for (int r = 0; r < B.mark_rounds; ++r) {
+      hipLaunchKernelGGL(k_sn_mark, dim3((unsigned)B.n_cblocks), dim3(256), 0, s, B.cmap, jobs, (const uint32_t*)ja, jb, B.mark, B.counts + (size_t)r * n_jobs, B.counts + (size_t)(r + 1) * n_jobs, r == 0 ? 1 : 0);
+      std::swap(ja, jb);
+    }
+    int32_t* pos = (int32_t*)B.jump_b;      // (both jump arrays are free now)
+    hipLaunchKernelGGL(k_sn_lens, dim3((unsigned)B.n_cblocks), dim3(256), 0, s, B.cmap, jobs, (const uint8_t*)B.mark, (const uint32_t*)B.olen, pos, status);
+    launch_exclusive_scan_i32(s, pos, B.c_slots, B.scan_ws, B.scan_ws_bytes);
+    hipLaunchKernelGGL(k_sn_fill, dim3((unsigned)B.n_cblocks), dim3(256), 0, s, src, B.cmap, jobs, (const uint8_t*)B.mark, (const int32_t*)pos, B.resolve, status);
   }
-  int32_t* pos = (int32_t*)B.jump_b;      // (both jump arrays are free now)
-  hipLaunchKernelGGL(k_sn_lens, dim3((unsigned)B.n_cblocks), dim3(256), 0, s, B.cmap, jobs, (const uint8_t*)B.mark, (const uint32_t*)B.olen, pos, status);
-  launch_exclusive_scan_i32(s, pos, B.c_slots, B.scan_ws, B.scan_ws_bytes);
-  hipLaunchKernelGGL(k_sn_fill, dim3((unsigned)B.n_cblocks), dim3(256), 0, s, src, B.cmap, jobs, (const uint8_t*)B.mark, (const int32_t*)pos, B.resolve, status);
   // back: copies resolved by pointer jumping, then the bytes
   uint32_t* c2 = B.counts + (size_t)(B.mark_rounds + 1) * n_jobs;
   for (int r = 0; r < B.rounds; ++r)

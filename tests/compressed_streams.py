@@ -1,0 +1,865 @@
+"""Hand-assembled Snappy and LZ4 streams for the device decompressors (csrc/kernels_lz4.hip, shuffle_codec.cpp, scanfmt.cpp).
+
+An encoder emits only the part of a format it likes; these emitters write any legal element -- and, for the malformed cases, one
+targeted illegal edit -- and build the plaintext alongside, so the expected output is known by construction.  The small reference
+decoders below check every bound explicitly and are compared with liblz4 / libsnappy (through pyarrow) in
+test_cpu_compressed_streams.py before any kernel sees a stream.  Plain Python and numpy: nothing here touches the GPU.
+
+Formats: Snappy raw block (google/snappy format_description.txt), LZ4 block and LZ4 frame (lz4 doc/lz4_Block_format.md,
+lz4_Frame_format.md), Parquet's Thrift-compact metadata (parquet-format/src/main/thrift/parquet.thrift), Arrow IPC (format/Message.fbs).
+"""
+import functools
+import struct
+from collections import namedtuple
+
+import numpy as np
+import xxhash
+
+
+class Malformed(ValueError):
+    pass
+
+
+class Unsupported(ValueError):
+    pass
+
+
+def rnd_bytes(seed, n):
+    return np.random.default_rng(seed).integers(0, 256, n, dtype=np.uint8).tobytes()
+
+
+def varint(v, width=None):
+    """LEB128; width forces a (non-minimal) encoding of exactly that many bytes."""
+    out = bytearray()
+    while True:
+        b = v & 0x7F
+        v >>= 7
+        more = v != 0 if width is None else len(out) + 1 < width
+        out.append(b | (0x80 if more else 0))
+        if not more:
+            assert v == 0, "value does not fit the forced width"
+            return bytes(out)
+
+
+def _append_copy(out, start, n):
+    """out += n bytes starting at out[start], byte by byte semantics (the source may overlap what is being written)."""
+    period = len(out) - start
+    if period >= n:
+        out += out[start:start + n]
+    else:
+        pat = bytes(out[start:])
+        out += (pat * (n // period + 1))[:n]
+
+
+# ---------------------------------------------------------------- Snappy
+class Snappy:
+    """Element-by-element writer.  `elems` records (position in the body, kind, header bytes) of every element for targeted edits."""
+
+    def __init__(self):
+        self.body, self.out, self.elems = bytearray(), bytearray(), []
+
+    def lit(self, data, nb=None):
+        n = len(data)
+        assert n >= 1
+        if nb is None:
+            nb = 0 if n <= 60 else 1 if n <= 1 << 8 else 2 if n <= 1 << 16 else 3 if n <= 1 << 24 else 4
+        at = len(self.body)
+        if nb == 0:
+            assert n <= 60
+            self.body.append((n - 1) << 2)
+        else:
+            assert n - 1 < 1 << (8 * nb)
+            self.body.append((59 + nb) << 2)
+            self.body += (n - 1).to_bytes(nb, "little")
+        self.elems.append((at, "lit%d" % nb, 1 + nb))
+        self.body += data
+        self.out += data
+        return self
+
+    def _copy(self, kind, hdr, off, n):
+        assert 1 <= off <= len(self.out), (off, len(self.out))
+        self.elems.append((len(self.body), kind, len(hdr)))
+        self.body += hdr
+        _append_copy(self.out, len(self.out) - off, n)
+        return self
+
+    def copy1(self, off, n):
+        assert 4 <= n <= 11 and off < 2048
+        return self._copy("copy1", bytes([1 | ((n - 4) << 2) | ((off >> 8) << 5), off & 0xFF]), off, n)
+
+    def copy2(self, off, n):
+        assert 1 <= n <= 64 and off < 1 << 16
+        return self._copy("copy2", bytes([2 | ((n - 1) << 2)]) + off.to_bytes(2, "little"), off, n)
+
+    def copy4(self, off, n):
+        assert 1 <= n <= 64 and off < 1 << 32
+        return self._copy("copy4", bytes([3 | ((n - 1) << 2)]) + off.to_bytes(4, "little"), off, n)
+
+    def pad4(self, seed=99):
+        """literal filler up to a multiple of 4 output bytes (the containers carry int32 values)"""
+        k = -len(self.out) % 4
+        if k:
+            self.lit(rnd_bytes(seed, k))
+        return self
+
+    def stream(self, preamble_width=None, declared=None):
+        return varint(len(self.out) if declared is None else declared, preamble_width) + bytes(self.body)
+
+    def plain(self):
+        return bytes(self.out)
+
+
+def snappy_decode(stream):
+    """Reference decoder: every bound explicit, Malformed on any violation."""
+    s, L = bytes(stream), len(stream)
+    ulen, sh, ip = 0, 0, 0
+    while True:
+        if ip >= L or sh > 28:
+            raise Malformed("preamble runs past the stream or beyond 5 bytes")
+        c = s[ip]
+        ip += 1
+        if sh == 28 and (c & 0x7F) > 15:
+            raise Malformed("preamble beyond 32 bits")
+        ulen |= (c & 0x7F) << sh
+        if not c & 0x80:
+            break
+        sh += 7
+    out = bytearray()
+    while ip < L:
+        tag = s[ip]
+        ip += 1
+        kind = tag & 3
+        if kind == 0:
+            n = (tag >> 2) + 1
+            if n > 60:
+                nb = n - 60
+                if ip + nb > L:
+                    raise Malformed("literal length field past the end")
+                n = int.from_bytes(s[ip:ip + nb], "little") + 1
+                ip += nb
+            if n > L - ip:
+                raise Malformed("literal runs past the end of the stream")
+            if n > ulen - len(out):
+                raise Malformed("literal runs past the announced length")
+            out += s[ip:ip + n]
+            ip += n
+            continue
+        nbytes = (1, 2, 4)[kind - 1]
+        if ip + nbytes > L:
+            raise Malformed("copy offset past the end")
+        if kind == 1:
+            n, off = 4 + ((tag >> 2) & 7), ((tag >> 5) << 8) | s[ip]
+        else:
+            n, off = (tag >> 2) + 1, int.from_bytes(s[ip:ip + nbytes], "little")
+        ip += nbytes
+        if off == 0:
+            raise Malformed("copy offset 0")
+        if off > len(out):
+            raise Malformed("copy from before the start of the output")
+        if n > ulen - len(out):
+            raise Malformed("copy runs past the announced length")
+        _append_copy(out, len(out) - off, n)
+    if len(out) != ulen:
+        raise Malformed("stream produced %d bytes, announced %d" % (len(out), ulen))
+    return bytes(out)
+
+
+# ---------------------------------------------------------------- LZ4 block
+def _lz4_len(n):
+    """the 255-run that follows a nibble of 15: n is what remains after the nibble"""
+    return b"\xff" * (n // 255) + bytes([n % 255])
+
+
+class Lz4Block:
+    """Sequence-by-sequence writer.  `history`: the frame's output before this block (linked blocks match into it).
+    `seqs` records (position of the token, position of the offset or None) for targeted edits."""
+
+    def __init__(self, history=b""):
+        self.hist = bytes(history)
+        self.body, self.out, self.seqs = bytearray(), bytearray(), []
+
+    def seq(self, literals=b"", offset=None, match_len=None):
+        """offset None: the literals-only sequence that ends a block."""
+        nl = len(literals)
+        tok_at = len(self.body)
+        ml = 0 if offset is None else match_len - 4
+        assert ml >= 0
+        self.body.append((min(nl, 15) << 4) | min(ml, 15))
+        if nl >= 15:
+            self.body += _lz4_len(nl - 15)
+        self.body += literals
+        self.out += literals
+        if offset is None:
+            self.seqs.append((tok_at, None))
+            return self
+        assert 1 <= offset <= min(65535, len(self.hist) + len(self.out)), (offset, len(self.hist) + len(self.out))
+        self.seqs.append((tok_at, len(self.body)))
+        self.body += offset.to_bytes(2, "little")
+        if ml >= 15:
+            self.body += _lz4_len(ml - 15)
+        if offset <= len(self.out):
+            _append_copy(self.out, len(self.out) - offset, match_len)
+        else:                      # starts in the history: through a joined buffer
+            joined = bytearray(self.hist[len(self.hist) - (offset - len(self.out)):]) + self.out
+            base = len(joined) - len(self.out)
+            _append_copy(joined, len(joined) - offset, match_len)
+            self.out = joined[base:]
+        return self
+
+    def end(self, n_literals=12, seed=98):
+        """final literals so that the output is a multiple of 4 and liblz4's end-of-block rules (last match >= 12 bytes before
+        the end, last 5 bytes literals) hold"""
+        n = n_literals + (-(len(self.out) + n_literals) % 4)
+        return self.seq(rnd_bytes(seed, n))
+
+    def block(self):
+        return bytes(self.body)
+
+    def plain(self):
+        return bytes(self.out)
+
+
+def lz4_block_decode(block, history=b"", max_out=None):
+    """Reference decoder of one block: returns the block's own output.  A block is sequences of (token, literal length run,
+    literals, offset, match length run); the last sequence ends after its literals."""
+    s, L = bytes(block), len(block)
+    out = bytearray(history)
+    base = len(out)
+    ip = 0
+    if L == 0:
+        raise Malformed("empty block")
+    while True:
+        if ip >= L:
+            raise Malformed("block ends where a token is expected")
+        token = s[ip]
+        ip += 1
+        nl = token >> 4
+        if nl == 15:
+            while True:
+                if ip >= L:
+                    raise Malformed("literal length run cut by the block end")
+                x = s[ip]
+                ip += 1
+                nl += x
+                if x != 255:
+                    break
+        if nl > L - ip:
+            raise Malformed("literals run past the block end")
+        if max_out is not None and nl > max_out - (len(out) - base):
+            raise Malformed("literals run past the output size")
+        out += s[ip:ip + nl]
+        ip += nl
+        if ip == L:
+            break                                   # the last sequence has no match
+        if ip + 2 > L:
+            raise Malformed("offset cut by the block end")
+        off = s[ip] | (s[ip + 1] << 8)
+        ip += 2
+        ml = token & 15
+        if ml == 15:
+            while True:
+                if ip >= L:
+                    raise Malformed("match length run cut by the block end")
+                x = s[ip]
+                ip += 1
+                ml += x
+                if x != 255:
+                    break
+        ml += 4
+        if off == 0:
+            raise Malformed("match offset 0")
+        if off > len(out):
+            raise Malformed("match reaches before the start of the output")
+        if max_out is not None and ml > max_out - (len(out) - base):
+            raise Malformed("match runs past the output size")
+        _append_copy(out, len(out) - off, ml)
+    return bytes(out[base:])
+
+
+def lz4_raw_decode(block, size):
+    out = lz4_block_decode(block, b"", size)
+    if len(out) != size:
+        raise Malformed("block produced %d bytes, expected %d" % (len(out), size))
+    return out
+
+
+# ---------------------------------------------------------------- LZ4 frame
+LZ4_MAGIC = 0x184D2204
+
+
+class Lz4Frame:
+    """Block-by-block writer.  `marks` records where every block header sits in the frame, for targeted edits."""
+
+    def __init__(self, linked=True, bsid=4, block_checksum=False, content_size=False, content_checksum=False, dict_id=None):
+        self.linked, self.bsid, self.bchk, self.csize, self.cchk, self.dict_id = linked, bsid, block_checksum, content_size, content_checksum, dict_id
+        self.bmax = 1 << (8 + 2 * bsid)
+        self.blocks, self.out = [], bytearray()      # (stored, payload, plain length)
+
+    def new_block(self):
+        return Lz4Block(bytes(self.out[-65535:]) if self.linked else b"")
+
+    def add(self, blk):
+        assert 0 < len(blk.out) <= self.bmax
+        self.blocks.append((False, blk.block(), len(blk.out)))
+        self.out += blk.out
+        return self
+
+    def stored(self, data):
+        assert 0 < len(data) <= self.bmax
+        self.blocks.append((True, bytes(data), len(data)))
+        self.out += data
+        return self
+
+    def frame(self):
+        flg = (1 << 6) | ((0 if self.linked else 1) << 5) | (int(self.bchk) << 4) | (int(self.csize) << 3) | (int(self.cchk) << 2) | (1 if self.dict_id is not None else 0)
+        desc = bytes([flg, self.bsid << 4])
+        if self.csize:
+            desc += struct.pack("<Q", len(self.out))
+        if self.dict_id is not None:
+            desc += struct.pack("<I", self.dict_id)
+        f = bytearray(struct.pack("<I", LZ4_MAGIC) + desc + bytes([(xxhash.xxh32(desc, seed=0).intdigest() >> 8) & 0xFF]))
+        self.marks = []
+        for stored, payload, _ in self.blocks:
+            self.marks.append(len(f))
+            f += struct.pack("<I", len(payload) | (0x80000000 if stored else 0)) + payload
+            if self.bchk:
+                f += struct.pack("<I", xxhash.xxh32(payload, seed=0).intdigest())
+        f += struct.pack("<I", 0)
+        if self.cchk:
+            f += struct.pack("<I", xxhash.xxh32(bytes(self.out), seed=0).intdigest())
+        return bytes(f)
+
+    def plain(self):
+        return bytes(self.out)
+
+
+def lz4_frame_decode(frame):
+    """Reference decoder of one frame: header, blocks (linked blocks see the 64 KiB before them), checksums, EndMark."""
+    f, L = bytes(frame), len(frame)
+    if L < 7 or struct.unpack_from("<I", f, 0)[0] != LZ4_MAGIC:
+        raise Malformed("not an LZ4 frame")
+    flg, bd = f[4], f[5]
+    if flg >> 6 != 1 or flg & 2 or bd & 0x8F:
+        raise Malformed("bad version / reserved bits")
+    linked, bchk, csize, cchk, has_dict = not (flg >> 5) & 1, (flg >> 4) & 1, (flg >> 3) & 1, (flg >> 2) & 1, flg & 1
+    bsid = (bd >> 4) & 7
+    if bsid < 4:
+        raise Malformed("bad block size id")
+    bmax = 1 << (8 + 2 * bsid)
+    ip = 6 + 8 * csize + 4 * has_dict
+    if ip + 1 > L:
+        raise Malformed("truncated frame header")
+    if f[ip] != (xxhash.xxh32(f[4:ip], seed=0).intdigest() >> 8) & 0xFF:
+        raise Malformed("header checksum")
+    if has_dict:
+        raise Unsupported("frame with a dictionary id")
+    announced = struct.unpack_from("<Q", f, 6)[0] if csize else None
+    ip += 1
+    out = bytearray()
+    while True:
+        if ip + 4 > L:
+            raise Malformed("frame ends without an EndMark")
+        h = struct.unpack_from("<I", f, ip)[0]
+        ip += 4
+        if h == 0:
+            break
+        bs = h & 0x7FFFFFFF
+        if bs > L - ip:
+            raise Malformed("block larger than the rest of the frame")
+        if bs > bmax:
+            raise Malformed("block larger than the frame's block size")
+        payload = f[ip:ip + bs]
+        ip += bs
+        if bchk:
+            if ip + 4 > L or struct.unpack_from("<I", f, ip)[0] != xxhash.xxh32(payload, seed=0).intdigest():
+                raise Malformed("block checksum")
+            ip += 4
+        out += payload if h & 0x80000000 else lz4_block_decode(payload, bytes(out[-65535:]) if linked else b"", bmax)
+    if cchk:
+        if ip + 4 > L or struct.unpack_from("<I", f, ip)[0] != xxhash.xxh32(bytes(out), seed=0).intdigest():
+            raise Malformed("content checksum")
+        ip += 4
+    if ip != L:
+        raise Malformed("bytes after the frame")
+    if announced is not None and announced != len(out):
+        raise Malformed("content size")
+    return bytes(out)
+
+
+# ---------------------------------------------------------------- Thrift compact + Parquet
+def _zz(v):
+    return varint((v << 1) ^ (v >> 63))
+
+
+class _Struct:
+    """Thrift compact struct writer: fields in ascending id order."""
+
+    def __init__(self):
+        self.b, self.last = bytearray(), 0
+
+    def _hdr(self, fid, typ):
+        d = fid - self.last
+        self.b += bytes([(d << 4) | typ]) if 0 < d <= 15 else bytes([typ]) + _zz(fid)
+        self.last = fid
+
+    def i32(self, fid, v):
+        self._hdr(fid, 5)
+        self.b += _zz(v)
+        return self
+
+    def i64(self, fid, v):
+        self._hdr(fid, 6)
+        self.b += _zz(v)
+        return self
+
+    def string(self, fid, s):
+        self._hdr(fid, 8)
+        self.b += varint(len(s)) + s
+        return self
+
+    def struct(self, fid, st):
+        self._hdr(fid, 12)
+        self.b += st.bytes()
+        return self
+
+    def list(self, fid, etype, items):
+        """items: already encoded elements"""
+        self._hdr(fid, 9)
+        self.b += bytes([(len(items) << 4) | etype]) if len(items) < 15 else bytes([0xF0 | etype]) + varint(len(items))
+        for it in items:
+            self.b += it
+        return self
+
+    def bytes(self):
+        return bytes(self.b) + b"\x00"
+
+
+PQ_CODECS = {"none": 0, "snappy": 1, "lz4_raw": 7}
+
+
+def parquet_one_column(pages, codec, name="v"):
+    """A Parquet file with one REQUIRED INT32 PLAIN column in one row group of v1 data pages.
+    pages: [(n_values, uncompressed_len, payload)]; codec: 0 UNCOMPRESSED, 1 SNAPPY, 7 LZ4_RAW."""
+    body = bytearray(b"PAR1")
+    first = len(body)
+    n_total, u_total = 0, 0
+    for n_values, ulen, payload in pages:
+        dph = _Struct().i32(1, n_values).i32(2, 0).i32(3, 3).i32(4, 3)                # PLAIN values, RLE levels (there are none: REQUIRED)
+        hdr = _Struct().i32(1, 0).i32(2, ulen).i32(3, len(payload)).struct(5, dph).bytes()
+        body += hdr + payload
+        n_total += n_values
+        u_total += len(hdr) + ulen
+    c_total = len(body) - first
+    cmeta = (_Struct().i32(1, 1).list(2, 5, [_zz(0), _zz(3)]).list(3, 8, [varint(len(name)) + name.encode()]).i32(4, codec).i64(5, n_total)
+             .i64(6, u_total).i64(7, c_total).i64(9, first))
+    chunk = _Struct().i64(2, first).struct(3, cmeta)
+    group = _Struct().list(1, 12, [chunk.bytes()]).i64(2, u_total).i64(3, n_total)
+    root = _Struct().string(4, b"schema").i32(5, 1)
+    leaf = _Struct().i32(1, 1).i32(3, 0).string(4, name.encode())
+    meta = _Struct().i32(1, 1).list(2, 12, [root.bytes(), leaf.bytes()]).i64(3, n_total).list(4, 12, [group.bytes()]).string(6, b"compressed_streams.py").bytes()
+    return bytes(body) + meta + struct.pack("<I", len(meta)) + b"PAR1"
+
+
+# ---------------------------------------------------------------- Arrow IPC
+def _fb_field(buf, table, k):
+    """position of field k of the flatbuffer table at `table`, or None when the field is absent"""
+    vt = table - struct.unpack_from("<i", buf, table)[0]
+    if 4 + 2 * k + 2 > struct.unpack_from("<H", buf, vt)[0]:
+        return None
+    o = struct.unpack_from("<H", buf, vt + 4 + 2 * k)[0]
+    return table + o if o else None
+
+
+def _split_messages(raw):
+    """[(metadata bytes incl. the 8-byte prefix, body)] of an encapsulated-message stream, up to the end-of-stream marker"""
+    out, pos = [], 0
+    while pos + 8 <= len(raw):
+        cont, mlen = struct.unpack_from("<Ii", raw, pos)
+        assert cont == 0xFFFFFFFF
+        if mlen == 0:
+            break
+        meta = bytearray(raw[pos:pos + 8 + mlen])
+        msg = 8 + struct.unpack_from("<I", meta, 8)[0]
+        blen = struct.unpack_from("<q", meta, _fb_field(meta, msg, 3))[0] if _fb_field(meta, msg, 3) else 0
+        out.append((meta, raw[pos + 8 + mlen:pos + 8 + mlen + blen]))
+        pos += 8 + mlen + blen
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _ipc_template(n_rows):
+    """(schema message, RecordBatch metadata) as pyarrow writes them for one non-null Int32 column of n_rows with LZ4 bodies"""
+    import io
+    import pyarrow as pa
+    t = pa.table({"v": pa.array(np.zeros(n_rows, np.int32))}).cast(pa.schema([pa.field("v", pa.int32(), False)]))
+    sink = io.BytesIO()
+    with pa.ipc.new_stream(sink, t.schema, options=pa.ipc.IpcWriteOptions(compression="lz4")) as w:
+        w.write_batch(t.to_batches()[0])
+    (schema, sbody), (batch, _) = _split_messages(sink.getvalue())
+    assert not sbody
+    return bytes(schema), bytes(batch)
+
+
+def ipc_int32_stream(buffers):
+    """An Arrow IPC stream of one non-null Int32 column "v": one RecordBatch message per (uncompressed_len, frame) entry, its body
+    `int64 uncompressed_len` + frame, padded to 8.  The metadata is pyarrow's own for that row count with the data Buffer and
+    bodyLength (fixed-width int64 fields) patched in place."""
+    out = bytearray()
+    for k, (ulen, frame) in enumerate(buffers):
+        assert ulen % 4 == 0
+        schema, batch = _ipc_template(ulen // 4)
+        if k == 0:
+            out += schema
+        meta = bytearray(batch)
+        body = struct.pack("<q", ulen) + bytes(frame)
+        padded = body + b"\x00" * (-len(body) % 8)
+        msg = 8 + struct.unpack_from("<I", meta, 8)[0]
+        struct.pack_into("<q", meta, _fb_field(meta, msg, 3), len(padded))
+        hdr_at = _fb_field(meta, msg, 2)
+        rb = hdr_at + struct.unpack_from("<I", meta, hdr_at)[0]
+        assert struct.unpack_from("<q", meta, _fb_field(meta, rb, 0))[0] == ulen // 4
+        bv = _fb_field(meta, rb, 2)
+        bv += struct.unpack_from("<I", meta, bv)[0]
+        assert struct.unpack_from("<I", meta, bv)[0] == 2                            # validity (absent), data
+        struct.pack_into("<qqqq", meta, bv + 4, 0, 0, 0, len(body))
+        out += meta + padded
+    out += struct.pack("<Ii", 0xFFFFFFFF, 0)
+    return bytes(out)
+
+
+# ---------------------------------------------------------------- the corpus
+Case = namedtuple("Case", "name plaintext stream kind expect reason")      # kind: snappy | lz4_raw | lz4_frame; expect: valid | malformed | unsupported
+
+
+def _snappy_fixed():
+    C = []
+
+    def add(name, s, reason, **kw):
+        C.append(Case("snappy/" + name, s.plain(), s.stream(**kw), "snappy", "valid", reason))
+    R = rnd_bytes
+    add("lit_len1_x4", Snappy().lit(b"a").lit(b"b").lit(b"c").lit(b"d"), "shortest literal, tag 0x00")
+    add("lit_len60", Snappy().lit(R(1, 60)), "longest length held in the tag")
+    add("lit_w1_61_and_256", Snappy().lit(R(2, 61)).lit(R(3, 256)).pad4(), "both ends of the 1-byte length field")
+    add("lit_w2_257_and_65536", Snappy().lit(R(4, 257)).lit(R(5, 65536)).pad4(), "both ends of the 2-byte length field")
+    add("lit_w3_65537", Snappy().lit(R(6, 65537)).pad4(), "3-byte length field at its low end (its high end, 16 MiB, is beyond the size cap)")
+    add("lit_w4_3bytes", Snappy().lit(b"xyz", nb=4).lit(b"!"), "a 3-byte literal under a 4-byte length field: libsnappy never writes one")
+    add("lit_w4_70000", Snappy().lit(R(7, 70000), nb=4), "4-byte length field with a value that needs 3 of its bytes")
+    add("lit_nonminimal_w1_w2_w3", Snappy().lit(R(8, 5), nb=1).lit(R(9, 7), nb=2).lit(R(10, 60), nb=3), "non-minimal length fields of every width")
+    s = Snappy().lit(R(11, 2048))
+    s.copy1(2047, 4).copy1(1, 11).copy1(2047, 11).copy1(1, 4).copy1(256, 5).copy1(255, 6).pad4()
+    add("copy1_ends", s, "copy-1 at both ends of its length (4, 11) and offset (1, 2047) range, and across the offset's high bits")
+    s = Snappy().lit(R(12, 65535))
+    s.copy2(65535, 64).copy2(1, 1).copy2(65535, 1).copy2(1, 64).copy2(256, 33).pad4()
+    add("copy2_ends", s, "copy-2 at both ends of its length (1, 64) and offset (1, 65535) range")
+    s = Snappy().lit(R(13, 70000))
+    s.copy4(70000, 64).copy4(65536, 1).copy4(70065, 64).copy4(1, 64).copy4(3, 7).copy4(2047, 11).copy4(65535, 2).pad4()
+    add("copy4_far_and_near", s, "copy-4 beyond 65535 (libsnappy's 64 KiB fragments never need one) and at offsets a shorter tag would hold")
+    for off in (1, 2, 3, 5, 63, 64, 65):
+        s = Snappy().lit(R(14 + off, 65))
+        s.copy2(off, 64).copy1(off, 11).copy4(off, 64).copy2(off, 7).pad4()
+        add("overlap_off%d" % off, s, "copies with off < len repeat a period of %d" % off)
+    add("copy_to_position0", Snappy().lit(R(30, 8)).copy2(8, 8).copy4(16, 16).copy1(32, 8), "offsets equal to the output so far: the source starts at byte 0")
+    s = Snappy().lit(R(31, 4094 - 2 - 3)).copy4(100, 64).lit(R(32, 2))
+    assert len(varint(len(s.out))) == 2 and 2 + s.elems[1][0] == 4094
+    add("straddle_c4096_copy4", s, "a copy-4 whose tag sits at compressed byte 4094 and whose offset crosses the 4096-byte block edge of k_sn_next / k_sn_fill")
+    s = Snappy().lit(R(33, 4093 - 2 - 3)).lit(R(34, 300), nb=4).lit(R(35, 1))
+    assert 2 + s.elems[1][0] == 4093
+    add("straddle_c4096_literal_header", s, "a literal whose 4-byte length field crosses compressed byte 4096")
+    s = Snappy().lit(R(36, 4090)).copy2(100, 64).lit(R(37, 2))
+    add("straddle_o4096_copy", s, "a copy whose output covers bytes 4090..4153: two 4096-byte blocks of k_snappy_round / k_snappy_emit")
+    s = Snappy().lit(R(38, 4000)).lit(R(39, 200)).pad4()
+    add("straddle_o4096_literal", s, "a literal whose output crosses byte 4096")
+    for short in (1, 2, 3, 5):
+        s = Snappy().lit(R(40 + short, 4090)).copy2(7, 64)
+        s.lit(R(50 + short, 4160 + 8 - short - len(s.out)))
+        assert (len(s.out) + short) % 4 == 0
+        add("tail_short%d" % short, s, "output %d bytes short of a multiple of 4: the byte-wise tail of k_snappy_emit" % short)
+    s = Snappy().lit(b"\x5a")
+    for _ in range(1100):
+        s.copy2(1, 64)
+    s.copy2(1, 3)
+    add("chain_1100_copies", s, "1100 copies each reading the last byte of the one before: the resolve rounds have to halve a chain 1100 deep")
+    for w in (2, 3, 4, 5):
+        add("preamble_w%d" % w, Snappy().lit(R(60 + w, 24)).copy1(8, 8), "length preamble in a non-minimal varint of %d bytes" % w, preamble_width=w)
+    return C
+
+
+def _lz4_raw_fixed():
+    C = []
+
+    def add(name, b, reason):
+        C.append(Case("lz4_raw/" + name, b.plain(), b.block(), "lz4_raw", "valid", reason))
+    R = rnd_bytes
+    add("zero_literal_sequences", Lz4Block().seq(R(1, 8), 4, 4).seq(b"", 8, 4).seq(b"", 1, 5).seq(b"", 16, 16).end(), "sequences without literals back to back (token high nibble 0)")
+    add("min_match", Lz4Block().seq(R(2, 4), 4, 4).end(), "minimum match length 4 (nibble 0)")
+    for n in (15, 270, 525):
+        add("literal_run_%d" % n, Lz4Block().seq(R(3, n), 3, 4).end(), "literal length %d: nibble 15 then %s" % (n, "255," * ((n - 15) // 255) + "0"))
+        add("match_run_%d" % (n + 4), Lz4Block().seq(R(4, 20), 7, n + 4).end(), "match length %d: nibble 15 then %s" % (n + 4, "255," * ((n - 15) // 255) + "0"))
+    add("match_long_66000", Lz4Block().seq(R(5, 100), 33, 66000).end(), "a 258-byte run of match length bytes")
+    add("offset_65535", Lz4Block().seq(R(6, 65535), 65535, 40).seq(R(7, 3), 65535, 4).end(), "the largest offset")
+    add("offset_eq_position", Lz4Block().seq(R(8, 8), 8, 8).seq(b"", 16, 16).seq(R(9, 1), 33, 40).end(), "offsets equal to the output so far: the source starts at byte 0")
+    for off in (1, 2, 3, 5, 63, 64, 65):
+        add("overlap_off%d" % off, Lz4Block().seq(R(10 + off, 65), off, 200).seq(b"", off, 4).seq(R(20 + off, 2), off, 67).end(), "matches with off < len repeat a period of %d" % off)
+    add("straddle_c4096_sequence", _lz4_straddle(), "a sequence whose offset and match length run cross compressed byte 4096, the block edge of k_sn_next / k_sn_fill")
+    add("straddle_o4096_match", Lz4Block().seq(R(31, 4090), 100, 64).end(), "a match whose output covers bytes 4090..4153")
+    add("straddle_o4096_literals", Lz4Block().seq(R(32, 4000), 9, 40).seq(R(33, 200), 9, 5).end(), "literals whose output crosses byte 4096")
+    for short in (1, 2, 3, 5):
+        b = Lz4Block().seq(R(40 + short, 4090), 7, 64)
+        b.seq(R(50 + short, 4160 + 8 - short - len(b.out)))
+        assert (len(b.out) + short) % 4 == 0
+        add("tail_short%d" % short, b, "output %d bytes short of a multiple of 4: the byte-wise tail of k_snappy_emit" % short)
+    b = Lz4Block().seq(b"\x5a", 1, 64)
+    for _ in range(1099):
+        b.seq(b"", 1, 64)
+    add("chain_1100_matches", b.end(), "1100 matches each reading the last byte of the one before: a chain 1100 deep for the resolve rounds")
+    return C
+
+
+def _lz4_straddle():
+    """first sequence: token at 0, 16 literal-run bytes, literals; its offset at compressed 4095..4096, match run after"""
+    for nl in range(4000, 4100):
+        b = Lz4Block().seq(rnd_bytes(30, nl), 100, 600)
+        if b.seqs[0][1] == 4095:
+            return b.end()
+    raise AssertionError("no literal length puts the offset on the block edge")
+
+
+def _random_block(rng, blk, n, final=12):
+    """sequences of random literal and match lengths until the block has produced exactly n bytes (n >= final)"""
+    assert n >= final
+    while True:
+        room = n - len(blk.out) - final
+        avail = len(blk.hist) + len(blk.out)
+        nl = int(rng.choice([0, 0, 1, 2, 3, 7, 14, 15, 16, 40, 270])) if avail else int(rng.integers(1, 20))
+        ml = int(rng.choice([4, 4, 5, 8, 18, 19, 20, 64, 273, 274, 300]))
+        if nl + ml > room:
+            break
+        lits = rng.integers(0, 256, nl, dtype=np.uint8).tobytes()
+        pick = rng.integers(0, 4)
+        hi = min(65535, avail + nl)
+        off = hi if pick == 0 else int(rng.integers(1, min(hi, 70) + 1)) if pick == 1 else int(rng.integers(1, hi + 1))
+        blk.seq(lits, off, ml)
+    blk.seq(rng.integers(0, 256, n - len(blk.out), dtype=np.uint8).tobytes())
+    assert len(blk.out) == n
+    return blk
+
+
+def _frames_fixed():
+    C = []
+
+    def add(name, f, reason):
+        assert len(f.out) % 4 == 0
+        C.append(Case("lz4_frame/" + name, f.plain(), f.frame(), "lz4_frame", "valid", reason))
+    R = rnd_bytes
+    B = 65536
+    rng = np.random.default_rng(7)
+    add("linked_stored_x2", Lz4Frame().stored(R(1, B)).stored(R(2, 1000)),
+        "linked frame of two stored blocks, the last partial: no compressed block, so launch_unpack_pages_pj has an empty cmap (ADVICE: output left unwritten, status 0)")
+    add("linked_stored_x3", Lz4Frame().stored(R(3, B)).stored(R(4, B)).stored(R(5, 4)), "three stored blocks, a 4-byte last one")
+    f = Lz4Frame().stored(R(6, B))
+    f.add(f.new_block().seq(b"", 65535, 400).seq(R(7, 5), 65535, 4).seq(b"", 1, 70).end())
+    add("linked_stored_then_match_65535", f, "a compressed block whose first match reaches 65535 bytes back into a stored block (byte 1 of the frame)")
+    f = Lz4Frame().stored(R(8, 30000))
+    f.add(f.new_block().seq(b"", 30000, 100).seq(R(9, 3), 30103, 30103).end())
+    add("linked_short_stored_then_match_to_byte0", f, "a non-full stored inner block and matches that reach the first byte of the frame: only the linked whole-frame walk decodes it")
+    f = Lz4Frame()
+    f.add(_random_block(rng, f.new_block().seq(R(10, 9), 9, 9), B)).stored(R(11, B))
+    f.add(_random_block(rng, f.new_block().seq(b"", 65535, 8).seq(b"", B - 1, 300), 5000))
+    add("linked_comp_stored_comp", f, "compressed, stored, compressed: matches of the third block reach through the stored one; the first block matches at offset == position")
+    f = Lz4Frame()
+    f.add(_random_block(rng, f.new_block(), 40000)).add(_random_block(rng, f.new_block().seq(b"", 40000, 64), 50000))
+    add("linked_nonfull_inner_two_blocks", f, "blocks of 40000 + 50000 bytes: the host's block index assumes 65536 + 24464, the parallel path flags the frame and the linked whole-frame walk is the fallback")
+    f = Lz4Frame()
+    f.add(_random_block(rng, f.new_block(), 30000)).add(_random_block(rng, f.new_block(), B)).add(_random_block(rng, f.new_block(), 5000))
+    add("linked_nonfull_inner_three_blocks", f, "a flushed first block and a third block the host's index does not expect: straight to the whole-frame walk")
+    for nm, kw, why in (("block_checksums", dict(block_checksum=True), "4 checksum bytes after every block have to be stepped over"),
+                        ("content_size", dict(content_size=True), "8 more header bytes before the first block"),
+                        ("content_checksum", dict(content_checksum=True), "4 bytes after the EndMark"),
+                        ("all_optional_fields", dict(block_checksum=True, content_size=True, content_checksum=True), "every optional field at once")):
+        f = Lz4Frame(**kw)
+        f.add(_random_block(rng, f.new_block(), B)).stored(R(12, B)).add(_random_block(rng, f.new_block(), 3000))
+        add("linked_" + nm, f, why + " (three linked blocks: the parallel path)")
+        f = Lz4Frame(**kw)
+        f.add(_random_block(rng, f.new_block(), 2000))
+        add("single_" + nm, f, why + " (one block: the whole-frame walk)")
+        f = Lz4Frame(linked=False, **kw)
+        f.add(_random_block(rng, f.new_block(), B)).add(_random_block(rng, f.new_block(), 3000))
+        add("independent_" + nm, f, why + " (independent blocks: one unit per block)")
+    f = Lz4Frame(bsid=5)
+    big = np.random.default_rng(13)
+    f.add(_random_block(big, f.new_block().seq(big.integers(0, 256, 200000, dtype=np.uint8).tobytes(), 65535, 4000), 1 << 18))
+    f.add(_random_block(big, f.new_block().seq(b"", 65535, 1000).seq(big.integers(0, 256, 200000, dtype=np.uint8).tobytes(), 3, 20000), 258000))
+    add("linked_bsid5_two_blocks", f, "256 KiB blocks: every job spans 64 resolve blocks and the second block matches into the first")
+    for bsid in (6, 7):
+        f = Lz4Frame(bsid=bsid)
+        f.add(_random_block(rng, f.new_block(), 70000))
+        add("linked_bsid%d_one_block" % bsid, f, "block-size id %d: one 70000-byte block, more than 64 KiB in one LZ4 block" % bsid)
+    f = Lz4Frame(bsid=6, linked=False)
+    f.stored(R(14, 70000)).add(_random_block(rng, f.new_block(), 1000))
+    add("independent_bsid6_nonfull", f, "independent non-full blocks under a 1 MiB block size: the per-block units are flagged, the frame walk decodes it")
+    f = Lz4Frame(linked=False)
+    f.add(_random_block(rng, f.new_block(), B)).stored(R(15, B)).add(_random_block(rng, f.new_block(), 1000))
+    add("independent_stored_in_the_middle", f, "independent blocks, the middle one stored")
+    return C
+
+
+def _random_snappy(rng, n_out):
+    s = Snappy()
+    while len(s.out) < n_out:
+        k = int(rng.integers(0, 5)) if s.out else 0
+        have = len(s.out)
+        if k == 0:
+            n = int(rng.choice([1, 2, 5, 59, 60, 61, 62, 100, 257]))
+            nb = None if rng.integers(0, 2) else int(rng.integers(max(1, 0 if n <= 60 else 1 if n <= 256 else 2), 5))
+            s.lit(rng.integers(0, 256, n, dtype=np.uint8).tobytes(), nb)
+        elif k == 1:
+            s.copy1(int(rng.integers(1, min(have, 2047) + 1)), int(rng.integers(4, 12)))
+        elif k == 2:
+            s.copy2(int(rng.integers(1, min(have, 65535) + 1)), int(rng.integers(1, 65)))
+        elif k == 3:
+            s.copy4(int(rng.integers(1, have + 1)), int(rng.integers(1, 65)))
+        else:
+            s.copy2(int(rng.integers(1, min(have, 8) + 1)), int(rng.integers(1, 65)))       # short periods
+    return s.pad4(int(rng.integers(0, 1 << 30)))
+
+
+def _random_cases(seed=2024, n=200):
+    C = []
+    rng = np.random.default_rng(seed)
+    for i in range(n):
+        s = _random_snappy(rng, int(rng.integers(50, 1700)))
+        C.append(Case("snappy/random_%03d" % i, s.plain(), s.stream(preamble_width=int(rng.integers(2, 6)) if i % 7 == 0 else None), "snappy", "valid", "seeded random program"))
+    for i in range(n):
+        size = int(rng.integers(13, 500)) * 4
+        b = _random_block(rng, Lz4Block().seq(rng.integers(0, 256, int(rng.integers(1, 30)), dtype=np.uint8).tobytes(), 1, 4), size, final=int(rng.integers(12, 40)))
+        C.append(Case("lz4_raw/random_%03d" % i, b.plain(), b.block(), "lz4_raw", "valid", "seeded random program"))
+    for i in range(n):
+        # even i: one block (decoded at the first attempt); odd i: several non-full blocks (the frame-by-frame fallback)
+        f = Lz4Frame(linked=bool(rng.integers(0, 2)), bsid=int(rng.integers(4, 8)), block_checksum=bool(rng.integers(0, 2)), content_size=bool(rng.integers(0, 2)),
+                     content_checksum=bool(rng.integers(0, 2)))
+        for _ in range(1 if i % 2 == 0 else int(rng.integers(2, 5))):
+            size = int(rng.integers(13, 125)) * 4
+            if rng.integers(0, 4) == 0:
+                f.stored(rng.integers(0, 256, size, dtype=np.uint8).tobytes())
+            else:
+                f.add(_random_block(rng, f.new_block(), size, final=int(rng.integers(12, 40))))
+        C.append(Case("lz4_frame/random_%03d" % i, f.plain(), f.frame(), "lz4_frame", "valid", "seeded random program, %s" % ("one block" if i % 2 == 0 else "non-full blocks")))
+    for i in range(4):                              # frames of full 64 KiB linked blocks: the parallel path under random programs
+        f = Lz4Frame(block_checksum=bool(i & 1), content_size=bool(i & 2))
+        for k in range(int(rng.integers(2, 4))):
+            if rng.integers(0, 3) == 0:
+                f.stored(rng.integers(0, 256, 65536, dtype=np.uint8).tobytes())
+            else:
+                f.add(_random_block(rng, f.new_block(), 65536))
+        f.add(_random_block(rng, f.new_block(), int(rng.integers(13, 5000)) * 4))
+        C.append(Case("lz4_frame/random_linked_full_%d" % i, f.plain(), f.frame(), "lz4_frame", "valid", "seeded random program, full linked blocks"))
+    return C
+
+
+def _edit(data, at, new):
+    b = bytearray(data)
+    b[at:at + len(new)] = new
+    return bytes(b)
+
+
+def _malformed():
+    """One targeted edit of a valid stream each.  The reason names the line that refuses it (parallel path, the default;
+    K = csrc/kernels_lz4.hip, H = csrc/shuffle_codec.cpp); both CPU judges reject every one of them.
+
+    Taken out because the judges disagree (reference decoder / library):
+      lz4_raw offset 0 and lz4_frame offset 0 (one block, and in the second linked block): Malformed / liblz4 1.10 decodes
+        them without an error, to other bytes (it treats offset 0 as a run of zeros);
+      lz4_raw block that produces one byte less than the page announces: Malformed / Arrow's Lz4 raw codec returns the shorter
+        buffer without an error;
+      a block that ends with a match and a final token 0x00 (asked for "only if liblz4 accepts it"): accepted / liblz4 refuses it
+        (its end-of-block rules want the last 5 bytes to be literals), so it is not among the valid cases either."""
+    C = []
+    R = rnd_bytes
+    # -- Snappy pages: preamble (1 byte) | lit 8 | copy2(off 4, len 8) | lit 4
+    s = Snappy().lit(R(1, 8)).copy2(4, 8).lit(R(2, 4))
+    good, plain = s.stream(), s.plain()
+    cp = 1 + s.elems[1][0]
+
+    def sn(name, stream, reason):
+        C.append(Case("snappy/bad_" + name, plain, stream, "snappy", "malformed", reason))
+    sn("offset0", _edit(good, cp + 1, b"\x00\x00"), "K k_sn_fill: `e.off == 0`")
+    sn("offset_position_plus1", _edit(good, cp + 1, b"\x09\x00"), "K k_sn_fill: `(int64_t)e.off > o` (9 bytes back from output position 8)")
+    sn("preamble_plus1", _edit(good, 0, bytes([len(plain) + 1])), "K k_sn_head: `(int64_t)ulen != out_len` (the page header announces the true length)")
+    sn("preamble_minus1", _edit(good, 0, bytes([len(plain) - 1])), "K k_sn_head: `(int64_t)ulen != out_len`")
+    sn("last_literal_truncated", good[:-1], "K k_sn_next: `p + e.size > L` marks the element SN_BAD, k_sn_lens flags it on the path")
+    s2 = Snappy().lit(R(3, 8)).copy2(4, 8)
+    C.append(Case("snappy/bad_last_copy_truncated", s2.plain(), s2.stream()[:-1], "snappy", "malformed", "K k_sn_next: `p + e.size > L` (a copy-2 with one offset byte), flagged by k_sn_lens"))
+    s4 = Snappy().lit(R(3, 8)).copy4(4, 8)
+    C.append(Case("snappy/bad_last_copy4_truncated", s4.plain(), s4.stream()[:-1], "snappy", "malformed", "K k_sn_next: `p + e.size > L` (a copy-4 with three offset bytes), flagged by k_sn_lens"))
+    sn("literal_past_page", _edit(good, 1 + s.elems[2][0], bytes([(30 - 1) << 2])), "K k_sn_next: `p + e.size > L` (a 30-byte literal with 4 bytes left), flagged by k_sn_lens")
+    sn("literal_w4_past_page", good[:1 + s.elems[2][0]] + bytes([63 << 2]) + b"\xff\xff\xff\x7f" + R(2, 4), "K k_sn_next: `p + e.size > L` with a 2^31-byte length field")
+    sn("copy4_offset_2_31", good[:cp] + bytes([3 | (7 << 2)]) + b"\x00\x00\x00\x80" + good[cp + 3:], "K k_sn_fill: `(int64_t)e.off > o` with offset 2^31 (unsigned compare)")
+    sn("output_one_short", good[:1 + s.elems[2][0]] + bytes([(3 - 1) << 2]) + R(2, 3), "K k_sn_fill: `o != out_len` at the terminal position")
+    # -- LZ4_RAW pages: seq(lit 8, off 4, ml 8) | final literals 12
+    b = Lz4Block().seq(R(4, 8), 4, 8).end()
+    goodb, plainb = b.block(), b.plain()
+    op = b.seqs[0][1]
+
+    def lz(name, stream, reason, plain=plainb):
+        C.append(Case("lz4_raw/bad_" + name, plain, stream, "lz4_raw", "malformed", reason))
+    lz("offset_position_plus1", _edit(goodb, op, b"\x09\x00"), "K k_sn_fill: `(int64_t)e.off > at`")
+    lz("last_literals_truncated", goodb[:-1], "K lz4_element: `lit > L - q`, so k_sn_next marks SN_BAD and k_sn_lens flags it")
+    lz("literal_length_past_page", _edit(goodb, b.seqs[1][0], b"\xf0\x40"), "K lz4_element: `lit > L - q` (79 literals announced, 12 present)")
+    b2 = Lz4Block().seq(R(5, 8), 4, 300)
+    lz("match_run_cut_by_block_end", b2.block()[:-1], "K lz4_element: `if (q >= L) return e` inside the match length run", b2.plain())
+    b3 = Lz4Block().seq(R(5, 8), 4, 8)
+    lz("offset_cut_by_block_end", b3.block()[:-1], "K lz4_element: `q + 2 > L`", b3.plain())
+    # -- LZ4 frames
+    f = Lz4Frame()
+    f.add(f.new_block().seq(R(7, 8), 4, 300).end())
+    goodf, plainf = f.frame(), f.plain()
+    blk0 = f.marks[0] + 4
+
+    def fr(name, stream, reason, plain=plainf, expect="malformed"):
+        C.append(Case("lz4_frame/bad_" + name, plain, stream, "lz4_frame", expect, reason))
+    fr("match_before_frame_start", _edit(goodf, blk0 + 9, b"\x09\x00"), "K lz4_decode_block: `offset > op - out_lo`")
+    fr("block_size_past_frame", _edit(goodf, f.marks[0], struct.pack("<I", len(goodf))), "K k_lz4_decode: `bs > iend - ip` (H emit: a one-block frame is a whole-frame unit)")
+    g2 = Lz4Frame()
+    g2.add(g2.new_block().seq(R(8, 8), 4, 300))
+    fr("match_run_cut_by_block_end", _edit(g2.frame(), g2.marks[0], struct.pack("<I", len(g2.blocks[0][1]) - 1))[:g2.marks[0] + 4 + len(g2.blocks[0][1]) - 1] + b"\x00\x00\x00\x00",
+       "K lz4_decode_block: `ip >= iend` inside the match length run", g2.plain())
+    fr("missing_endmark", goodf[:-4], "K k_lz4_decode: `ip + 4 > iend` where a block header or the EndMark is expected")
+    g3 = Lz4Frame()
+    first = g3.new_block().seq(R(9, 8), 4, 300)
+    g3x = first.seqs[0][1]
+    g3.add(_random_block(np.random.default_rng(3), first, 65536)).add(g3.new_block().seq(R(9, 8), 4, 300).end())
+    fr("linked_first_block_match_before_frame_start", _edit(g3.frame(), g3.marks[0] + 4 + g3x, b"\x09\x00"),
+       "K k_sn_fill: `(int64_t)e.off > at` on the parallel path, then lz4_decode_block: `offset > op - out_lo` in the fallback walk", g3.plain())
+    g4 = Lz4Frame()
+    g4.stored(R(10, 65536)).stored(R(11, 1000))
+    fr("linked_stored_block_size_past_frame", _edit(g4.frame(), g4.marks[1], struct.pack("<I", 0x80000000 | 5000)),
+       "H emit: `bs > flen - ip` keeps the frame off the parallel path, then K k_lz4_decode: `bs > iend - ip`", g4.plain())
+    g5 = Lz4Frame(dict_id=0x11223344)
+    g5.add(g5.new_block().seq(R(7, 8), 4, 300).end())
+    fr("dictionary_id", g5.frame(), "H emit: `if (has_dict) throw Unsupported`", g5.plain(), expect="unsupported")
+    return C
+
+
+@functools.lru_cache(maxsize=None)
+def corpus():
+    """Every case as Case(name, plaintext, stream, kind, expect, reason): the fixed table, the seeded random programs, the malformed edits."""
+    return tuple(_snappy_fixed() + _lz4_raw_fixed() + _frames_fixed() + _random_cases() + _malformed())
+
+
+def cases(kind=None, expect=None, random=None):
+    return [c for c in corpus() if (kind is None or c.kind == kind) and (expect is None or c.expect == expect)
+            and (random is None or ("/random_" in c.name) == random)]
+
+
+def int32_of(plain):
+    """what an INT32 PLAIN page of these bytes holds: the whole values (a tail of 1-3 bytes is carried by the page and ignored)"""
+    return np.frombuffer(plain[:len(plain) // 4 * 4], dtype="<i4")
+
+
+def parquet_of(cs, codec):
+    """the cases as pages of one column chunk"""
+    return parquet_one_column([(len(c.plaintext) // 4, len(c.plaintext), c.stream) for c in cs], PQ_CODECS[codec])
+
+
+def ipc_of(cs):
+    return ipc_int32_stream([(len(c.plaintext), c.stream) for c in cs])

@@ -259,8 +259,10 @@ def test_reference_single_nan_parquet_snappy(tc):
 
 
 def test_snappy_streams_with_long_literals_and_overlapping_copies(tc):
-    """Snappy's element kinds: highly repetitive columns (copies whose offset is shorter than their length), incompressible ones
-    (literals with 2- and 3-byte length fields), and pages far beyond 64 KiB (2- and 4-byte offset copies)."""
+    """Snappy's element kinds as libsnappy emits them: highly repetitive columns (copies whose offset is shorter than their length),
+    incompressible ones (literals with 1- and 2-byte length fields) and pages far beyond 64 KiB (1- and 2-byte offset copies).
+    libsnappy compresses in 64 KiB fragments, so it never writes a 4-byte offset copy or a 3- / 4-byte literal length field: those
+    are hand-assembled in test_gpu_compressed_streams.py (compressed_streams.py)."""
     n = 300_000
     r = np.random.default_rng(4)
     t = pa.table({"same": pa.array(np.full(n, 123456789, np.int64)), "ramp": pa.array(np.arange(n, dtype=np.int64) % 7),
