@@ -481,6 +481,23 @@ AggCompiled compile_aggregate(const Schema& in, const Json& d) {
     R.acc_bits.push_back(accs[i].arg ? R.prog.out_bits[acc_slots[i]] : 1);
   }
   R.keys = make_keyspec(kregs, R.key_types, any_null_key);
+  // The whole key in at most 62 bits (narrow integer / date columns, one NULL flag per nullable one): the global hash table keeps it in
+  // the slot's state word (gpuq_kernels.h KeySpec::state_key).  Int64 and wider keys, strings and packed composites keep their key words.
+  {
+    int total = 0; bool narrow = nk > 0;
+    for (int k = 0; k < nk && narrow; ++k) {
+      int bits = 0; bool sgn = false;
+      switch (keys.nodes[k]->type.id) {
+        case T_INT8: bits = 8; sgn = true; break;   case T_UINT8: bits = 8; break;
+        case T_INT16: bits = 16; sgn = true; break; case T_UINT16: bits = 16; break;
+        case T_INT32: case T_DATE32: bits = 32; sgn = true; break; case T_UINT32: bits = 32; break;
+        default: narrow = false;
+      }
+      R.keys.sk_bits[k] = bits; R.keys.sk_signed[k] = sgn; R.keys.sk_null[k] = keys.nodes[k]->nullable ? 1 : 0;
+      total += bits + R.keys.sk_null[k];
+    }
+    R.keys.state_key = narrow && total <= 62;
+  }
 
   // post programs over the SoA result: [key_0.., acc_0..] as raw (lo,hi) columns
   for (int k = 0; k < nk; ++k) { Field f; f.name = keys.names[k]; f.type = keys.nodes[k]->type; f.nullable = keys.nodes[k]->nullable; f.raw128 = 1; R.post_schema.fields.push_back(f); }

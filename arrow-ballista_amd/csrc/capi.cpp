@@ -458,7 +458,7 @@ int gpuq_compile_check(const char* json, char* buf, size_t cap) {
       for (size_t i = 0; i < op->posts.size(); ++i) { if (i) r += ","; r += describe_program(op->posts[i].prog, op->post_schema); }
       r += "],\"acc_kinds\":[";
       for (int a = 0; a < op->agg.n_accs; ++a) { if (a) r += ","; r += std::to_string(op->agg.acc_kind[a]); }
-      r += "]";
+      r += std::string("],\"state_key\":") + (op->keys.state_key ? "true" : "false");      // the key fits the slot's state word (hash strategy)
     }
     r += ",\"outputs\":[";
     for (size_t i = 0; i < op->out_fields.size(); ++i) {
@@ -637,11 +637,15 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
     const int nk = op->agg.n_keys, na = op->agg.n_accs, kstride = nk > 0 ? nk : 1;
     uint32_t ng = 0;
     AggOut raw{};
+    // the keys as the table of THIS run holds them: state_key only when the plain global-table kernel fills it (launch_table)
+    KeySpec Krun = op->keys; Krun.state_key = 0;
     auto alloc_raw = [&](i64 rcap) {
       raw.cap = (int32_t)rcap;
-      raw.keys = (u64*)op->ws[0].ensure((size_t)rcap * kstride * 16);
-      raw.key_nulls = (uint32_t*)op->ws[1].ensure((size_t)rcap * 4);
-      raw.cells = (u64*)op->ws[2].ensure((size_t)rcap * na * 16);
+      if (!Krun.state_key) {      // (a table with state-word keys is extracted into the result columns directly)
+        raw.keys = (u64*)op->ws[0].ensure((size_t)rcap * kstride * 16);
+        raw.key_nulls = (uint32_t*)op->ws[1].ensure((size_t)rcap * 4);
+        raw.cells = (u64*)op->ws[2].ensure((size_t)rcap * na * 16);
+      }
       raw.n_groups = op->flags_dev.as<uint32_t>() + 2;     // next to the flags word: one copy reads both
       HIPCHECK(hipMemsetAsync(raw.n_groups, 0, 8, s));
     };
@@ -650,11 +654,14 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
     bool posted = false;
     // AoS -> SoA, then the final projection into the caller's typed columns.  rows: host-side bound on the group count;
     // rows_dev (optional): the device word holding the actual count.
-    auto run_post = [&](uint32_t rows, const uint32_t* rows_dev) {
+    AggSoA soa{}; std::vector<gpuq_column> pcols; bool soa_filled = false;
+    auto layout_soa = [&](uint32_t rows, const bool all_valid) {
       const size_t colbytes = (size_t)std::max<uint32_t>(rows, 1) * 16, vbytes = ((size_t)rows + 63) / 64 * 8 + 8;
       char* soa_mem = (char*)op->ws[6].ensure((size_t)(nk + na) * colbytes + (size_t)nk * vbytes);
-      AggSoA soa{};
-      std::vector<gpuq_column> pcols(nk + na);
+      bool any_null = false; for (int k = 0; k < nk; ++k) any_null = any_null || op->keys.sk_null[k];
+      if (all_valid && any_null) HIPCHECK(hipMemsetAsync(soa_mem + (size_t)(nk + na) * colbytes, 0xFF, (size_t)nk * vbytes, s));      // (only a NULL key clears a bit)
+      soa = AggSoA{};
+      pcols.assign(nk + na, gpuq_column{});
       for (int k = 0; k < nk; ++k) {
         soa.key_col[k] = (ulonglong2*)(soa_mem + (size_t)k * colbytes);
         soa.key_valid[k] = (u64*)(soa_mem + (size_t)(nk + na) * colbytes + (size_t)k * vbytes);
@@ -666,7 +673,10 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         const DType& t = op->acc_types[a];
         pcols[nk + a] = gpuq_column{t.id, t.p, t.s, 0, soa.acc_col[a], nullptr, nullptr, (int64_t)rows};
       }
-      launch_agg_emit(s, raw, nk, na, rows, soa, rows_dev);
+    };
+    auto run_post = [&](uint32_t rows, const uint32_t* rows_dev) {
+      if (!soa_filled) { layout_soa(rows, false); launch_agg_emit(s, raw, nk, na, rows, soa, rows_dev); }
+      else for (auto& c : pcols) c.length = (int64_t)rows;      // (the extract wrote the columns, laid out for its capacity)
       gpuq_input pin{}; pin.cols = pcols.data(); pin.n_cols = nk + na; pin.n_rows = rows; pin.n_via = 0;
       for (auto& pc : op->posts) {
         DevProgram PP = bind_program(pc.prog, op->post_schema, pc.code.as<DevCode>(), op->flags_dev.as<uint32_t>(), &pin);
@@ -695,6 +705,10 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
     HashTable T{};
     T.key_words = op->keys.key_words; T.slot_words = 1 + T.key_words + 2 * na;
     auto launch_table = [&](const u64 est, const u64 slot_pct, const bool use_lds, const bool reset) {
+      // a key that fits the state word needs no key words -- in the table the plain kernel fills (the block-local kernel keeps its layout)
+      Krun.state_key = (op->keys.state_key && !use_lds) ? 1 : 0;
+      Krun.key_words = Krun.state_key ? 0 : op->keys.key_words;      // (make_key then builds no key words: the kernel packs the one it needs)
+      T.key_words = Krun.state_key ? 0 : op->keys.key_words; T.slot_words = 1 + T.key_words + 2 * na;
       T.n_slots = next_pow2(est * slot_pct / 100);
       T.slots = (u64*)op->ws[5].ensure((size_t)T.n_slots * T.slot_words * 8);
       launch_ht_init(s, T, &op->agg);
@@ -707,7 +721,13 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         if (n_fsum > 0 && fbytes <= ((size_t)256 << 20)) { fstage = (u64*)op->ws[8].ensure(fbytes); HIPCHECK(hipMemsetAsync(fstage, 0, fbytes, s)); }
         SinkJit jit(op, op->prog, GPUQ_SINK_AGG_LDS, n); ProfScope ps(op, s); launch_agg_lds(s, jit.fn, P, n, op->keys, op->agg, T, fstage, n_fsum);
       }
-      else { SinkJit jit(op, op->prog, GPUQ_SINK_AGG_HASH, n); ProfScope ps(op, s); launch_agg_hash(s, jit.fn, P, n, op->keys, op->agg, T); }
+      else { SinkJit jit(op, op->prog, GPUQ_SINK_AGG_HASH, n); ProfScope ps(op, s); launch_agg_hash(s, jit.fn, P, n, Krun, op->agg, T); }
+    };
+    // the table's groups into the raw result (alloc_raw) -- or, with state-word keys, straight into the result columns
+    auto extract = [&]() {
+      const bool direct = Krun.state_key && raw.cap > 0;
+      if (direct) { layout_soa((uint32_t)raw.cap, true); soa_filled = true; }
+      launch_agg_hash_extract(s, Krun, op->agg, T, raw, op->flags_dev.as<uint32_t>(), direct ? &soa : nullptr);
     };
     // radix-partitioned (path 3).  High cardinality: partition the rows by key hash into buckets whose groups fit an LDS table, aggregate
     // every bucket inside one block (kernels_hash.hip).  false: on to the global table -- a bucket overflowed (skew, or more groups than
@@ -773,7 +793,7 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         if (rcap >= 1 && rcap <= 0x7FFFFFFFll) {
           launch_table(est, agg_slot_pct(true), L.ag.use_lds, false);
           alloc_raw(rcap);
-          launch_agg_hash_extract(s, op->keys, op->agg, T, raw, op->flags_dev.as<uint32_t>());
+          extract();
           finish_on_device();
           return;
         }
@@ -872,7 +892,7 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
       if (n <= (1ll << 20)) {
         // small input: groups <= rows, so size the raw result by n and extract once (one sync instead of three)
         alloc_raw(std::max<i64>(n, 1));
-        launch_agg_hash_extract(s, op->keys, op->agg, T, raw, op->flags_dev.as<uint32_t>());
+        extract();
         HIPCHECK(hipGetLastError());
         // as on the LDS path: queue the result projection before the group count is known on the host (it reads the count on
         // the device) when the caller's columns can hold any outcome -- one host round trip instead of two
@@ -889,7 +909,7 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         bool done = false;
         if (L.ag.groups > 0) {
           alloc_raw(L.ag.groups + L.ag.groups / 4 + 1024);
-          launch_agg_hash_extract(s, op->keys, op->agg, T, raw, op->flags_dev.as<uint32_t>());
+          extract();
           HIPCHECK(hipGetLastError());
           uint32_t fw[4] = {0, 0, 0, 0};
           read_status(op, s, fw, 4);
@@ -900,13 +920,13 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         } else {
           alloc_raw(1);
           raw.cap = 0;      // counting pass
-          launch_agg_hash_extract(s, op->keys, op->agg, T, raw, op->flags_dev.as<uint32_t>());
+          extract();
           ng = read_ng();
           reset_flags(op, s);
         }
         if (!done) {
           alloc_raw(std::max<i64>(ng, 1));
-          launch_agg_hash_extract(s, op->keys, op->agg, T, raw, op->flags_dev.as<uint32_t>());
+          extract();
           HIPCHECK(hipGetLastError());
           ng = read_ng();
         }

@@ -49,11 +49,19 @@ struct KeySpec {
   int32_t key_words;           // total u64 key words per slot
   int32_t word_reg[MAX_KW];    // key word q comes from register word_reg[q] ...
   int32_t word_half[MAX_KW];   // ... half 0 = lo, 1 = hi, 2 = the key null mask
+  // Hash aggregate only.  state_key = 1: the whole key, NULL flags included, packs into one word of at most 62 bits and lives in the
+  // slot's state word (HashTable below): key k is the low sk_bits[k] bits of its register (its type's width; sk_signed[k]: sign-extended
+  // on the way out) and, when sk_null[k], one bit above them that says NULL; the fields follow each other from bit 0.
+  int32_t state_key;
+  int32_t sk_bits[MAX_KEYS], sk_signed[MAX_KEYS], sk_null[MAX_KEYS];
 };
 // Open-addressing table, linear probing, one slot = slot_words u64:
 //   [0]            low 32 bits state (0 empty, 1 locked, else hash tag|2); high 32 bits payload (join: chain head row)
 //   [1..key_words] key words
 //   [1+key_words..] aggregate cells, two u64 (lo,hi) per accumulator
+// A hash aggregate whose key fits the state word (KeySpec::state_key) has key_words = 0 and slots of 1 + 2 * n_accs words:
+//   [0]            0 empty, else (packed key << 2) | 2 -- one compare-and-swap claims the slot and publishes the key
+//   [1..]          aggregate cells
 // Join tables over ONE narrow (<= 64-bit) integer key whose values span a bounded range use direct addressing instead:
 // dense[key - dense_min] = chain head row (0xFFFFFFFF = no such key), dense_range entries.  One load per probe, no probing
 // loop, and a probe side that is clustered / sorted by the key (fact-table foreign keys) walks the table sequentially.
@@ -314,7 +322,8 @@ void launch_agg_bucket_id(hipStream_t s, void* jit_fn, const DevProgram& P, i64 
 void launch_bucket_bounds(hipStream_t s, const u64* sorted_bid, i64 n, u64 nbuckets, uint32_t* bounds, int shift);
 void launch_agg_bucket(hipStream_t s, void* jit_fn, const DevProgram& P, const KeySpec& K, const AggSpec& A, const uint32_t* ids, const uint32_t* bounds, uint32_t nbuckets,
                        uint32_t cap, int slot_words, const AggOut& out);
-void launch_agg_hash_extract(hipStream_t s, const KeySpec& K, const AggSpec& A, const HashTable& T, const AggOut& out, uint32_t* flags);
+// soa: state-word keys only (K.state_key): the groups are written as result columns directly (out gives the capacity and the count word)
+void launch_agg_hash_extract(hipStream_t s, const KeySpec& K, const AggSpec& A, const HashTable& T, const AggOut& out, uint32_t* flags, const AggSoA* soa = nullptr);
 // false: no interpreter kernel for this shape (chain fusion over more than 8 input columns)
 bool launch_join_build(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, uint32_t* next, uint32_t* present,
                        int payload_via, int null_equals_null, const SemiProbe* semi = nullptr);

@@ -12,6 +12,9 @@
 // with one more atomic store.  Readers poll the state with a relaxed atomic load and read the key
 // words with atomic loads only after they saw the tag.  Correctness never depends on dispatch
 // order or XCD placement; every probe sequence is bounded by n_slots.
+// A hash aggregate whose whole key fits 62 bits keeps it IN the state word (KeySpec::state_key):
+// CAS(state: EMPTY -> key) claims and publishes at once, a failed CAS returns the occupant's key --
+// no LOCKED state, no key words, nothing to drain or to wait for; still 8-byte agent atomics only.
 #include "gpuq_kernels.h"
 
 namespace gpuq {
@@ -99,6 +102,55 @@ __device__ __forceinline__ u64 ht_find_or_insert(const HashTable& T, const u64 (
   }
   return ~0ull;
 }
+
+// ---- keys that live in the state word (KeySpec::state_key, hash aggregate)
+// the packed key of the current row: per key its value bits and, for a nullable key, the NULL flag above them
+__device__ __forceinline__ u64 pack_state_key(const KeySpec& K, GPUQ_REGS_CPARAM) {
+  u64 p = 0; int shift = 0;
+#pragma unroll
+  for (int k = 0; k < MAX_KEYS; ++k) {
+    if (k < K.n_keys) {
+      const int r = __builtin_amdgcn_readfirstlane(K.key_reg[k]);
+      const int b = __builtin_amdgcn_readfirstlane(K.sk_bits[k]), nb = __builtin_amdgcn_readfirstlane(K.sk_null[k]);
+      const bool isn = nb && ((rnulls >> r) & 1);
+      const u64 f = isn ? (1ull << b) : (rlo[r] & ((1ull << b) - 1));
+      p |= f << shift;
+      shift += b + nb;
+    }
+  }
+  return p;
+}
+// Slot of `key` (< 2^62), found or claimed: ONE compare-and-swap per slot visited.  ~0 when the table is full.
+__device__ __forceinline__ u64 ht_state_find_or_insert(const HashTable& T, const u64 key, const u64 h) {
+  const u64 mask = T.n_slots - 1, want = (key << 2) | 2ull;
+  u64 s = h & mask;
+  for (u64 probes = 0; probes < T.n_slots; ++probes) {
+    const u64 old = a_cas(T.slots + s * (u64)T.slot_words, 0ull, want);
+    if (old == 0ull || old == want) return s;
+    s = (s + 1) & mask;
+  }
+  return ~0ull;
+}
+#ifndef GPUQ_JIT
+// a finished slot of such a table written as row g of the result COLUMNS (validity words start as all ones: a NULL key clears its bit)
+__device__ __forceinline__ void emit_state_group(const u64* slot, const KeySpec& K, const AggSpec& A, const AggSoA& soa, const uint32_t g) {
+  const u64 st = slot[0] >> 2;
+  int shift = 0;
+  for (int k = 0; k < K.n_keys; ++k) {
+    const int b = K.sk_bits[k];
+    u64 lo = (st >> shift) & ((1ull << b) - 1);
+    const bool isn = K.sk_null[k] && ((st >> (shift + b)) & 1);
+    if (K.sk_signed[k]) lo = (u64)((i64)(lo << (64 - b)) >> (64 - b));
+    shift += b + K.sk_null[k];
+    soa.key_col[k][g] = make_ulonglong2(lo, (u64)((i64)lo >> 63));
+    if (isn) atomicAnd((unsigned long long*)(soa.key_valid[k] + (g >> 6)), ~(1ull << (g & 63)));
+  }
+  for (int a = 0; a < A.n_accs; ++a) {
+    const u64 lo = slot[1 + 2 * a];
+    soa.acc_col[a][g] = make_ulonglong2(lo, acc_result_hi(A.acc_kind[a], lo, slot[2 + 2 * a]));
+  }
+}
+#endif
 
 // Read-only lookup (table finished by an earlier kernel): plain loads.
 __device__ __forceinline__ bool ht_find(const HashTable& T, const u64 (&kw)[MAX_KW], u64 h, uint32_t& payload) {
@@ -189,6 +241,8 @@ __device__ __forceinline__ void k_agg_hash_body(const DevProgram P, const i64 n_
   const i64 n = rows_of(P, n_arg);      // deferred execution: the row count is a device word, n_arg its host-side bound
   const i64 nwords = (n + 63) >> 6;
   const int cell0 = 1 + T.key_words;
+  const bool state_key = K.state_key != 0;             // the key is one word and lives in the slot's state word (T.key_words == 0)
+  const int cmp_words = state_key ? 1 : T.key_words;
   // Rows with equal keys in neighbouring lanes (clustered input: lineitem rows of one order, a join's probe-ordered
   // output) are combined inside the wave by a segmented scan; only the last lane of each run touches the table.  Every
   // table access is a device-scope transaction (~10 G/s on this part), so a run of r rows costs 1/r of the traffic.
@@ -200,7 +254,10 @@ __device__ __forceinline__ void k_agg_hash_body(const DevProgram P, const i64 n_
     u64 kw[MAX_KW]; u64 h = 0;
 #pragma unroll
     for (int q = 0; q < MAX_KW; ++q) kw[q] = 0;
-    if (active) make_key(K, GPUQ_REGS, kw, h);
+    if (active) {
+      make_key(K, GPUQ_REGS, kw, h);
+      if (state_key) kw[0] = pack_state_key(K, GPUQ_REGS);      // (the words beyond cmp_words are not looked at)
+    }
     // head[i]: lane i starts a run (its key differs from lane i-1's, or lane i-1 is not an active row)
     // every cross-lane read below is executed by ALL lanes and only then combined: a shuffle under a short-circuit
     // (`lane > 0 && shfl(..)`) runs with some lanes masked off, and a masked-off source lane reads as 0
@@ -210,7 +267,7 @@ __device__ __forceinline__ void k_agg_hash_body(const DevProgram P, const i64 n_
       const u64 ph = __shfl_up(h, 1);
       bool eq = (pa != 0) & (lane > 0) & (ph == h);
 #pragma unroll
-      for (int q = 0; q < MAX_KW; ++q) { const u64 pk = __shfl_up(kw[q], 1); if (q < T.key_words) eq = eq & (pk == kw[q]); }
+      for (int q = 0; q < MAX_KW; ++q) { const u64 pk = __shfl_up(kw[q], 1); if (q < cmp_words) eq = eq & (pk == kw[q]); }
       head = !(active & eq);
     }
     const int nh = __shfl_down((int)head, 1);
@@ -219,7 +276,7 @@ __device__ __forceinline__ void k_agg_hash_body(const DevProgram P, const i64 n_
     u64 s = ~0ull;
     if (tail) {
       bool inserted;
-      s = ht_find_or_insert(T, kw, h, 0u, inserted);
+      s = state_key ? ht_state_find_or_insert(T, kw[0], h) : ht_find_or_insert(T, kw, h, 0u, inserted);
       if (s == ~0ull) atomicOr(P.flags, FLAG_TABLE_FULL);
     }
     u64* cells = T.slots + (s == ~0ull ? 0 : s) * (u64)T.slot_words + cell0;
@@ -258,7 +315,7 @@ extern "C" __global__ void __launch_bounds__(HBLOCK) gpuq_jit_entry(const DevPro
 
 #ifndef GPUQ_JIT
 __global__ void __launch_bounds__(HBLOCK) k_agg_hash_extract(const KeySpec K, const AggSpec A, const HashTable T, const AggOut out,
-                                                             uint32_t* __restrict__ flags) {
+                                                             uint32_t* __restrict__ flags, const AggSoA soa) {
   // A wave claims output rows for XSUB x 64 slots with ONE atomic on the group counter (one atomic per 64 slots made a
   // 2^26-slot table cost 18 ms: ~17 ns per serialised device-scope atomic).  Output order is arbitrary anyway.
   constexpr int XSUB = 16;
@@ -288,7 +345,7 @@ __global__ void __launch_bounds__(HBLOCK) k_agg_hash_extract(const KeySpec K, co
         const u64 s = c * chunk_slots + (u64)j * 64 + hlane();
         const u64* slot = T.slots + s * (u64)T.slot_words;
         const uint32_t g = base + (uint32_t)__popcll(m & ltmask);
-        if (g < (uint32_t)out.cap) emit_group(slot, cell0, K, A, out, g);
+        if (g < (uint32_t)out.cap) { if (K.state_key) emit_state_group(slot, K, A, soa, g); else emit_group(slot, cell0, K, A, out, g); }
       }
       base += (uint32_t)__popcll(m);
     }
@@ -956,8 +1013,8 @@ extern "C" __global__ void __launch_bounds__(HBLOCK) gpuq_jit_entry(const DevPro
 // No output atomics and no per-row match vector: every wave owns a SEGMENT of `wpw` consecutive 64-row words, probes it in
 // order and appends its (build_row, probe_row) pairs to seg_build / seg_probe starting at the segment's first row (a segment
 // of r rows emits at most r pairs, so segments never collide); seg_counts[g] = pairs of segment g.  A scan of the counts and
-// k_copy_segments then move the segments to their final, PROBE-ORDERED places.  A selective join (TPC-H q3: 14.6 M pairs
-// from 600 M probe rows) writes and re-reads only its pairs; the first version wrote a 4-byte match word per probe ROW and
+// k_copy_segments then move the segments to their final, PROBE-ORDERED places.  A selective join (TPC-H q3 at SF100: 3.0 M pairs
+// from 600 M probe rows, measured -- 14.6 M is the count of the FIRST join, customer |x| orders) writes and re-reads only its pairs; the first version wrote a 4-byte match word per probe ROW and
 // read all of them back in the compaction pass (4.8 GB of the kernel pair's 14 GB at SF100).  A single global counter would
 // serialise the whole probe (measured: 51 ms for 2^28 probes whatever the table size -- one device-scope atomic per wave step).
 __device__ __forceinline__ uint32_t emit_pairs(const bool emit, const uint32_t hit, const uint32_t prow, const u64 seg_base, const uint32_t cnt,
@@ -987,8 +1044,8 @@ __device__ __forceinline__ void k_join_probe_unique_body(const DevProgram P, con
 #endif
   constexpr int U = GPUQ_PROBE_ROWS;
   // Hit queue (sparse domain, Inner / RightSemi): a probe that finds its key's bit set still has to fetch the build row from the row
-  // array and write the pair -- a third dependent memory round trip per step that one row in twenty needs (SF100 q3: 14.6 M hits in
-  // 323 M probes).  Hits go to a FIFO in LDS (table index, probe row: first in, first out keeps probe order) and are resolved 64 at a
+  // array and write the pair -- a third dependent memory round trip per step that one row in a hundred needs (SF100 q3: 3.0 M hits in
+  // 323 M probes, measured; the 14.6 M quoted elsewhere are the first join's pairs).  Hits go to a FIFO in LDS (table index, probe row: first in, first out keeps probe order) and are resolved 64 at a
   // time with every lane busy and full-wave coalesced pair stores; the per-step chain is columns -> bitmap.
   constexpr int QC = 64 * (U + 1);
   __shared__ uint32_t hq_idx[HWAVES][QC], hq_row[HWAVES][QC];
@@ -1458,11 +1515,12 @@ void launch_agg_lds(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, con
     hipLaunchKernelGGL(k_fsum_stage_reduce, dim3((unsigned)(need < cap ? (need ? need : 1) : cap)), dim3(HBLOCK), 0, s, T, A, (const u64*)fstage, n_fsum, (uint32_t)grid);
   }
 }
-void launch_agg_hash_extract(hipStream_t s, const KeySpec& K, const AggSpec& A, const HashTable& T, const AggOut& out, uint32_t* flags) {
+void launch_agg_hash_extract(hipStream_t s, const KeySpec& K, const AggSpec& A, const HashTable& T, const AggOut& out, uint32_t* flags, const AggSoA* soa) {
+  AggSoA none{};
   u64 need = (T.n_slots + (u64)HBLOCK * 16 - 1) / ((u64)HBLOCK * 16);      // a wave takes 16 x 64 slots per step
   const u64 cap = (u64)num_cus() * 16;
   const int grid = (int)(need < cap ? (need ? need : 1) : cap);
-  hipLaunchKernelGGL(k_agg_hash_extract, dim3(grid), dim3(HBLOCK), 0, s, K, A, T, out, flags);
+  hipLaunchKernelGGL(k_agg_hash_extract, dim3(grid), dim3(HBLOCK), 0, s, K, A, T, out, flags, soa ? *soa : none);
 }
 void launch_agg_bucket_id(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, u64 bucket_mask, u64* bid, uint32_t* ids) {
   if (n <= 0) return;

@@ -68,6 +68,7 @@ Json type_json_of(int tid, int p, int s) {
 }
 
 struct PCol { std::string name; Json type; bool nullable = true; gpuq_column c{}; };
+struct BuildRows;
 struct PTable {
   std::vector<PCol> cols; int64_t n = 0;
   std::vector<const uint32_t*> via; std::vector<int> sides; bool dense = false;
@@ -78,9 +79,21 @@ struct PTable {
   // can run deferred pass both on (gpuq_input.n_rows_dev); everything else calls resolve() first, which settles the plan's
   // pending operators and makes n exact.
   const uint64_t* n_dev = nullptr; BufP n_keep;
+  // set by an Inner hash join over unique build keys whose output is its pair list (BuildRows below): row i came from ONE known build row
+  std::shared_ptr<const BuildRows> by_build;
   bool is_view() const { return !via.empty(); }
   void own(const PTable& o) { keep.insert(keep.end(), o.keep.begin(), o.keep.end()); }
   void count_from(const PTable& o) { n_dev = o.n_dev; n_keep = o.n_keep; }
+};
+
+// What an Inner join over unique build keys (no JoinFilter, the pair list is the output) says about its output: pair i joins row
+// rows[i] of `build` -- so two output rows agree on the join keys and on every build-side column exactly when rows[] agrees.
+// An aggregate directly above whose group columns are the join keys plus build-side columns groups by rows[] alone (AggregateExec::run).
+struct BuildRows {
+  const uint32_t* rows = nullptr; BufP rows_keep;      // the pair list's build-side half: as long as the output (its count is the output's)
+  PTable build;                                        // the build-side input the rows address
+  std::vector<std::string> build_keys, probe_keys;     // the join keys, pairwise: plain columns of either side
+  size_t n_build_cols = 0, n_cols = 0;                 // the output's columns [0, n_build_cols) are the build side's; n_cols in all
 };
 
 // field list of a table as an operator sees it (side / raw128 / dense annotations)
@@ -526,6 +539,7 @@ PTable materialize(Exec& x, const PTable& t, bool force = false);
 // address `t`'s rows through idx[0..n): a view
 // drop the columns nothing above reads (PNode::require): what a join carries along is what its materialisations gather
 void prune_columns(PTable& t, const std::set<std::string>& keep) {
+  t.by_build = nullptr;      // (column positions change)
   for (size_t i = t.cols.size(); i-- > 0;)
     if (!keep.count(t.cols[i].name)) { t.cols.erase(t.cols.begin() + (long)i); t.sides.erase(t.sides.begin() + (long)i); t.record_cap = 0; }
 }
@@ -813,6 +827,7 @@ struct PNode {
   virtual ~PNode() {}
   virtual std::vector<PNode*> children() { return {}; }
   virtual int partitions() { auto c = children(); return c.empty() ? 1 : c[0]->partitions(); }
+  virtual bool is_hash_join() const { return false; }
   // output schema, known before anything runs (QueryStageExecutor::schema(), execution_engine.rs:59; executor_server.rs:530-534
   // parses the output partitioning from it before the task executes).  Default: the input's.
   virtual PSchema schema() { auto c = children(); if (c.empty()) throw std::runtime_error("plan: node without a schema"); return c[0]->schema(); }
@@ -980,6 +995,10 @@ PTable ProjectionExec::execute(int part, Exec& x) {
   return timed(x, t0, project(x, t, ex, names, this, 1));
 }
 
+bool is_bare_column(const Json& e, std::string& name) {
+  if (!(e.is_obj() && e.o.size() == 1 && e.o[0].first == "column" && e.o[0].second.is_obj() && e.o[0].second.find("name"))) return false;
+  name = e.o[0].second.at("name").str(); return true;
+}
 struct AggregateExec : PNode {
   PNodeP input; std::string mode, strategy = "auto"; Json group_expr, aggr_expr; int64_t expected_groups = 0, output_capacity = 0;
   std::vector<PNode*> children() override { return {input.get()}; }
@@ -1013,6 +1032,9 @@ struct AggregateExec : PNode {
     const bool final_ = mode == "Final" || mode == "FinalPartitioned";
     Fused f; if (final_) f.src = input.get(); else f = fuse(input.get());
     PTable t = f.src->execute(part, x);
+    // a join's word about its build rows (BuildRows) is taken from the join itself, directly below (through fused filters / projections)
+    // -- never from a table some node in between has handed on
+    if (final_ || !f.src->is_hash_join()) t.by_build = nullptr;
     auto t0 = std::chrono::steady_clock::now();
     // (more group columns than the table holds keys, some of them strings: codes from the start -- a 128-bit packed string takes a key
     // slot of its own, a 32-bit code is packed with its neighbours, see compile_aggregate)
@@ -1033,13 +1055,81 @@ struct AggregateExec : PNode {
     PTable t2 = filter_table(x, t, f.pred, this, 9);
     return timed(x, t0, run(x, t2, f2, true));
   }
+  // Grouping by the build row (BuildRows).  The input is the pair list of an Inner join over unique build keys, and every group expression
+  // is a join-key column (of either side: they are equal on every joined row) or an expression over build-side columns, with all join
+  // keys of one side among them: two rows are then in one group exactly when they came from one build row, and the table groups by that
+  // ONE UInt32 instead of by the declared columns (which are read back from the build side, one row per group, afterwards).
+  // Returns the mark and fills `over_build` with the group expressions as expressions over the build-side table; nullptr: not this shape.
+  const BuildRows* build_row_grouping(const PTable& t, const ColMap* cm, std::vector<Json>& over_build) const {
+    const BuildRows* br = t.by_build.get();
+    if (!br || mode != "Single" || group_expr.a.empty() || t.cols.size() != br->n_cols || br->build.cols.size() != br->n_build_cols) return nullptr;
+    auto first_named = [](const PTable& tt, const std::string& n) { for (size_t i = 0; i < tt.cols.size(); ++i) if (tt.cols[i].name == n) return (int)i; return -1; };
+    const size_t nkeys = br->build_keys.size();
+    std::vector<bool> got_build(nkeys, false), got_probe(nkeys, false);
+    for (auto& g : group_expr.a) {
+      const Json e = inline_projection(g.at("expr"), cm);
+      std::string bare; const bool is_bare = is_bare_column(e, bare);
+      if (is_bare) {
+        const int ci = first_named(t, bare);
+        if (ci < 0) return nullptr;
+        if ((size_t)ci >= br->n_build_cols) {
+          // a probe-side column: only a join key, served by its build-side partner -- when that has exactly its type
+          size_t k = 0; while (k < nkeys && br->probe_keys[k] != bare) ++k;
+          if (k == nkeys) return nullptr;
+          const int bi = first_named(br->build, br->build_keys[k]);
+          if (bi < 0 || first_named(t, br->build_keys[k]) != bi || br->build.cols[(size_t)bi].type.dump() != t.cols[(size_t)ci].type.dump()) return nullptr;
+          // integer-like and date keys only: equal means identical there (a float key's 0.0 would stand in for a probe row's -0.0)
+          switch (t.cols[(size_t)ci].c.type) {
+            case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: case T_DATE32: case T_DATE64: case T_TIMESTAMP: break;
+            default: return nullptr;
+          }
+          got_probe[k] = true;
+          over_build.push_back(jobj({{"column", jobj({{"name", jstr(br->build_keys[k])}})}}));
+          continue;
+        }
+        for (size_t k = 0; k < nkeys; ++k) if (br->build_keys[k] == bare) got_build[k] = true;
+      }
+      std::set<std::string> used; collect_columns(e, used);
+      for (auto& n : used) {
+        const int ci = first_named(t, n);
+        // (strings stay with the declared keys: a value beyond 15 bytes takes the dictionary-code path there)
+        if (ci < 0 || (size_t)ci >= br->n_build_cols || first_named(br->build, n) != ci || t.cols[(size_t)ci].c.type == T_UTF8) return nullptr;
+      }
+      over_build.push_back(e);
+    }
+    const bool all_build = std::find(got_build.begin(), got_build.end(), false) == got_build.end();
+    const bool all_probe = std::find(got_probe.begin(), got_probe.end(), false) == got_probe.end();
+    return (all_build || all_probe) ? br : nullptr;
+  }
+  // the result of the aggregate over the build row (column 0: the row of every group) with the declared group columns in its place
+  PTable with_group_columns(Exec& x, const PTable& out, const BuildRows& br, const std::vector<Json>& over_build) {
+    std::vector<std::string> names; for (auto& g : group_expr.a) names.push_back(g.at("name").str());
+    PTable v = select_view(x, br.build, (const uint32_t*)out.cols[0].c.data, out.n, nullptr, out.n_dev ? &out : nullptr);
+    v.own(out);
+    PTable keys = project(x, v, over_build, names, this, 11);
+    PTable r; r.n = keys.n; r.count_from(keys); r.own(keys); r.own(v);      // (the projection reads the build side and the rows asynchronously)
+    r.cols = keys.cols; r.sides.assign(keys.cols.size(), 0);
+    for (size_t i = 1; i < out.cols.size(); ++i) { PCol c = out.cols[i]; c.c.length = keys.n; r.cols.push_back(c); r.sides.push_back(0); }
+    return r;
+  }
   PTable run(Exec& x, PTable t, const Fused& f, const bool long_keys) {
     const ColMap* cm0 = f.has_map ? &f.map : nullptr;
+    std::vector<Json> over_build;
+    const BuildRows* br = long_keys ? nullptr : build_row_grouping(t, cm0, over_build);
+    const std::shared_ptr<const BuildRows> br_keep = br ? t.by_build : nullptr;
+    if (br) {
+      PCol c; c.name = "__build_row"; c.type = jstr("UInt32"); c.nullable = false;
+      c.c.type = T_UINT32; c.c.repr = GPUQ_REPR_ARROW; c.c.data = br->rows; c.c.length = t.n;
+      t.cols.push_back(c); t.sides.push_back(0); t.keep.push_back(br->rows_keep); t.record_cap = 0; t.by_build = nullptr;
+    }
     // group expressions over the source table; with long_keys every plain Arrow-layout Utf8 key column is replaced by its codes
     std::vector<Json> gexprs; std::vector<int> coded;      // coded[k] = column of `t` key k's strings come from, or -1
     Utf8DictGuard dicts[8]; int nd = 0;
     const PTable t_src = t;
-    for (auto& g : group_expr.a) {
+    std::vector<std::string> gnames;
+    if (br) { gexprs.push_back(jobj({{"column", jobj({{"name", jstr("__build_row")}})}})); coded.push_back(-1); gnames.push_back("__build_row"); }
+    else for (auto& g : group_expr.a) {
+      gnames.push_back(g.at("name").str());
       Json e = inline_projection(g.at("expr"), cm0); int ci = -1;
       if (long_keys && (ci = long_key_column(t_src, e)) >= 0 && nd < 8) {
         const std::string nm = "__code_" + std::to_string(gexprs.size());
@@ -1051,11 +1141,11 @@ struct AggregateExec : PNode {
       } else ci = -1;
       gexprs.push_back(e); coded.push_back(ci);
     }
-    gpuq_op* op = cached_op(x, this, long_keys ? 6 : 0, table_sig(t), [&]() {
+    gpuq_op* op = cached_op(x, this, long_keys ? 6 : (br ? 10 : 0), table_sig(t), [&]() {
     const auto nm = names_of(t);
     const ColMap* cm = f.has_map ? &f.map : nullptr;
     Json ge = jarr(), ae = jarr();
-    for (size_t k = 0; k < group_expr.a.size(); ++k) ge.a.push_back(jobj({{"expr", rebind(gexprs[k], nm)}, {"name", group_expr.a[k].at("name")}}));
+    for (size_t k = 0; k < gexprs.size(); ++k) ge.a.push_back(jobj({{"expr", rebind(gexprs[k], nm)}, {"name", jstr(gnames[k])}}));
     for (auto& a : aggr_expr.a) {
       std::vector<std::pair<std::string, Json>> o = {{"fn", a.at("fn")}, {"name", a.at("name")}};
       for (const char* k : {"expr", "expr2", "filter"}) if (a.has(k)) o.push_back({k, rebind(inline_projection(a.at(k), cm), nm)});
@@ -1065,6 +1155,7 @@ struct AggregateExec : PNode {
                                                    {"strategy", jstr(strategy)}, {"group_expr", ge}, {"aggr_expr", ae}};
     if (f.has_pred) d.push_back({"predicate", rebind(f.pred, nm)});
     if (expected_groups) d.push_back({"expected_groups", jnum(expected_groups)});
+    if (br) d.push_back({"group_by", jstr("build_row")});      // (read by nobody but whoever looks at the plan's profile)
     return jobj(d);
     });
     const bool deferred = !long_keys && prep(x, op, t);
@@ -1085,6 +1176,7 @@ struct AggregateExec : PNode {
         HIPCHECK(hipMemcpyAsync(cnt->p, ndev, 8, hipMemcpyDeviceToDevice, (hipStream_t)x.stream));
         out.n_dev = (const uint64_t*)cnt->p; out.n_keep = cnt;
       }
+      if (br) { out.own(t); return with_group_columns(x, out, *br, over_build); }
       return out;
     }
     for (;;) {
@@ -1106,6 +1198,7 @@ struct AggregateExec : PNode {
         sc.name = out.cols[k].name; out.cols[k] = sc; out.record_cap = 0;
         HIPCHECK(hipStreamSynchronize((hipStream_t)x.stream));      // `rows` dies here
       }
+      if (br) return with_group_columns(x, out, *br, over_build);
       return out;       // synchronous call: the input buffers are no longer referenced
     }
   }
@@ -1134,6 +1227,7 @@ struct SortExec : PNode {
 struct HashJoinExec : PNode {
   PNodeP left, right; Json on; std::string join_type = "Inner", partition_mode = "CollectLeft"; bool null_equals_null = false; bool has_filter = false; Json filter;
   std::vector<PNode*> children() override { return {left.get(), right.get()}; }
+  bool is_hash_join() const override { return true; }
   bool out_need_all = true; Names out_need;      // what is read of this join's output (require())
   void require(const Names* need) override {
     out_need_all = need == nullptr; if (need) out_need = *need;
@@ -1163,10 +1257,13 @@ struct HashJoinExec : PNode {
     return s;
   }
   int64_t last_pairs = -1;      // pairs the last synchronous run of this call site emitted: sizes the pair vectors of a deferred run
-  PTable join_view(Exec& x, const PTable& lt, const PTable& rt, const uint32_t* ob, const uint32_t* opb, int64_t k, const BufP& ob_own, const BufP& opb_own, const PTable* count = nullptr) {
+  PTable join_view(Exec& x, const PTable& lt, const PTable& rt, const uint32_t* ob, const uint32_t* opb, int64_t k, const BufP& ob_own, const BufP& opb_own, const PTable* count = nullptr,
+                   bool* materialised = nullptr) {
     PTable lv = select_view(x, lt, ob, k, ob_own, count), rv = select_view(x, rt, opb, k, opb_own, count);
+    if (materialised) *materialised = false;
     if (lv.via.size() + rv.via.size() > 3) {
       if (lv.via.size() >= rv.via.size()) lv = materialize(x, lv); else rv = materialize(x, rv);
+      if (materialised) *materialised = true;
     }
     PTable out; out.n = k; out.own(lv); out.own(rv);
     if (count) out.count_from(*count);
@@ -1175,6 +1272,18 @@ struct HashJoinExec : PNode {
     for (size_t i = 0; i < rv.cols.size(); ++i) { out.cols.push_back(rv.cols[i]); out.sides.push_back(rv.sides[i] == 0 ? 0 : rv.sides[i] + shift); }
     for (auto v : rv.via) out.via.push_back(v);
     return out;
+  }
+  // `out` is the pair list of this Inner join and `lt`'s keys are unique: pair i came from row ob[i] of lt (BuildRows)
+  void mark_build_rows(PTable& out, const PTable& lt, const uint32_t* ob, const BufP& ob_own) const {
+    auto m = std::make_shared<BuildRows>();
+    for (auto& o : on.a) {
+      std::string l, r;
+      if (!is_plain_column(o.at("left"), l) || !is_plain_column(o.at("right"), r)) return;
+      m->build_keys.push_back(l); m->probe_keys.push_back(r);
+    }
+    m->rows = ob; m->rows_keep = ob_own; m->build = lt; m->build.by_build = nullptr;
+    m->n_build_cols = lt.cols.size(); m->n_cols = out.cols.size();
+    out.by_build = m;
   }
   // positions of [0, n) that occur (want_marked) / do not occur in rows[0..k)
   int64_t marked_rows(Exec& x, const uint32_t* rows, int64_t k, int64_t n, bool want_marked, int tag, BufP& out) {
@@ -1418,6 +1527,7 @@ struct HashJoinExec : PNode {
     // sizes nothing on the host -- the pair vectors are as long as the count this call site produced last time allows (+ 1/8), an
     // overflow raises the probe's status word.  Only the join types whose output is the pair list itself run this way.
     const bool plain = !long_keys && !residual && !has_filter && (jt == "Inner" || jt == "Right" || jt == "RightSemi" || jt == "RightAnti");
+    const bool by_rows = join_type == "Inner" && !has_filter && !long_keys && !null_equals_null;      // the output is the pair list of an Inner join
     bool deferred = false;
     if (chain) deferred = chain->deferred && plain && use_deferred(x, pop);      // (the table is there already: chain_build)
     else if (plain && x.deferred && last_pairs >= 0 && gpuq_op_can_defer(bop)) deferred = use_deferred(x, bop) && use_deferred(x, pop);
@@ -1442,7 +1552,12 @@ struct HashJoinExec : PNode {
       check(x, gpuq_join_probe_run(pop, x.stream, jtab, &ric.in, 0, pairs ? (uint32_t*)ob->p : nullptr, (uint32_t*)opb->p, (uint64_t)cap, (uint64_t*)cnt->p));
       PTable c; c.n_dev = (const uint64_t*)cnt->p; c.n_keep = cnt;
       if (!pairs) return select_view(x, R.t, (const uint32_t*)opb->p, cap, opb, &c);
-      return join_view(x, L.t, R.t, (const uint32_t*)ob->p, (const uint32_t*)opb->p, cap, ob, opb, &c);
+      bool mat = false;
+      PTable out = join_view(x, L.t, R.t, (const uint32_t*)ob->p, (const uint32_t*)opb->p, cap, ob, opb, &c, &mat);
+      // (unique keys are what the last synchronous build found: a duplicate now raises FLAG_DUP_BUILD_KEY in the build's status word -- the
+      // plain build and the chain-fused one alike -- and the settle sends the plan back through the synchronous path)
+      if (by_rows && !mat && !gpuq_join_table_has_duplicates(jtab)) mark_build_rows(out, L.t, (const uint32_t*)ob->p, ob);
+      return out;
     }
     for (;;) {
       ob = dev_alloc((size_t)cap * 4 + 16); opb = dev_alloc((size_t)cap * 4 + 16);
@@ -1469,7 +1584,9 @@ struct HashJoinExec : PNode {
       k += mrows;
     }
     if (jt == "RightSemi" || jt == "RightAnti") return select_view(x, R.t, (const uint32_t*)opb->p, k, opb);
-    PTable out = join_view(x, L.t, R.t, (const uint32_t*)ob->p, (const uint32_t*)opb->p, k, ob, opb);
+    bool mat = false;
+    PTable out = join_view(x, L.t, R.t, (const uint32_t*)ob->p, (const uint32_t*)opb->p, k, ob, opb, nullptr, &mat);
+    if (by_rows && !mat && !gpuq_join_table_has_duplicates(jtab)) mark_build_rows(out, L.t, (const uint32_t*)ob->p, ob);
     if (residual) return residual_join(x, L.t, R.t, out, ob, opb, k);
     if (has_filter) out = filter_table(x, out, filter, this, 2);
     // the probe kernels read the build table asynchronously; results were read back (synchronised) above
@@ -1572,6 +1689,7 @@ PTable concat_tables(Exec& x, std::vector<PTable> parts) {
 
 // rows [skip, skip + count) of a table
 PTable slice_table(Exec& x, PTable t, int64_t skip, int64_t count) {
+  t.by_build = nullptr;      // (rows move: the pair list the mark points to is not sliced with them)
   resolve(x, t);
   skip = std::min(std::max<int64_t>(skip, 0), t.n);
   count = (count < 0 || skip + count > t.n) ? t.n - skip : count;
