@@ -48,6 +48,14 @@ Json jbool(bool b) { Json j; j.kind = Json::BOOL; j.b = b; return j; }
 Json jarr(std::vector<Json> a = {}) { Json j; j.kind = Json::ARR; j.a = std::move(a); return j; }
 Json jobj(std::vector<std::pair<std::string, Json>> o = {}) { Json j; j.kind = Json::OBJ; j.o = std::move(o); return j; }
 Json jcol(const std::string& name, int index) { return jobj({{"column", jobj({{"name", jstr(name)}, {"index", jnum(index)}})}}); }
+// a column by NAME: no "index" member (jcol's by-position form dumps differently, and descriptor text is the operator cache's key)
+Json jcolname(const Json& name) { return jobj({{"column", jobj({{"name", name}})}}); }
+Json jcolname(const std::string& name) { return jcolname(jstr(name)); }
+// the name `e` refers to when it is a bare column reference -- an object with the one key "column" whose value is an object that has "name" -- else nullptr
+const std::string* bare_column(const Json& e) {
+  if (!(e.is_obj() && e.o.size() == 1 && e.o[0].first == "column" && e.o[0].second.is_obj() && e.o[0].second.find("name"))) return nullptr;
+  return &e.o[0].second.at("name").str();
+}
 Json jand(const Json& l, const Json& r) { return jobj({{"binary_expr", jobj({{"l", l}, {"r", r}, {"op", jstr("AND")}})}}); }
 
 // ---------------------------------------------------------------- schema / tables
@@ -108,9 +116,30 @@ Json table_fields(const PTable& t) {
   }
   return f;
 }
+Json input_of(const PTable& t) { return jobj({{"fields", table_fields(t)}}); }      // the "input" member of an operator descriptor
+// ---- reading column i of a table
+int find_column(const PTable& t, const std::string& name) { for (size_t i = 0; i < t.cols.size(); ++i) if (t.cols[i].name == name) return (int)i; return -1; }      // the first of that name
+const uint32_t* via_of(const PTable& t, size_t i) { const int sd = t.sides[i]; return sd > 0 ? t.via[(size_t)sd - 1] : nullptr; }      // the index vector it is read through
+bool nullable_in(const PTable& t, size_t i) { return t.cols[i].nullable || (t.sides[i] > 0 && !t.dense); }      // declared so, or an index vector may hold NULL_ROW_ID
+DType dtype_of(const gpuq_column& c) { DType dt; dt.id = c.type; dt.p = c.precision; dt.s = c.scale; return dt; }
+size_t width_of(const gpuq_column& c) { return (size_t)type_width(dtype_of(c)); }
+size_t bitmap_bytes(int64_t n) { return (size_t)((n + 63) / 64) * 8 + 8; }
+gpuq_field_info field_info_of(const PCol& c) {
+  gpuq_field_info f{};
+  std::snprintf(f.name, sizeof(f.name), "%s", c.name.c_str());
+  f.type = c.c.type; f.precision = c.c.precision; f.scale = c.c.scale; f.nullable = c.nullable; f.repr = c.c.repr;
+  f.width = c.c.type == T_BOOL ? 0 : type_width(dtype_of(c.c));
+  return f;
+}
+// a declared field as a column without data: Arrow layout
+PCol column_of(const PField& f) {
+  PCol c; c.name = f.name; c.type = f.type; c.nullable = f.nullable;
+  c.c.type = type_id_of(f.type, c.c.precision, c.c.scale); c.c.repr = GPUQ_REPR_ARROW;
+  return c;
+}
 PSchema plain_schema(const PTable& t) {
   PSchema s;
-  for (size_t i = 0; i < t.cols.size(); ++i) s.push_back({t.cols[i].name, t.cols[i].type, t.cols[i].nullable || (t.sides[i] > 0 && !t.dense)});
+  for (size_t i = 0; i < t.cols.size(); ++i) s.push_back({t.cols[i].name, t.cols[i].type, nullable_in(t, i)});
   return s;
 }
 std::string table_sig(const PTable& t) {
@@ -121,15 +150,25 @@ std::string table_sig(const PTable& t) {
 }
 
 // ---------------------------------------------------------------- expression trees (PhysicalExprNode mirror)
-Json rewrite_columns(const Json& e, const std::function<Json(const Json&)>& fn) {
+// The one tree walk: every single-key object {kind: v} is offered to `fn`, which either fills `out` with its replacement (true; the
+// replacement is not walked again) or declines; everything else is copied, objects and arrays member by member.
+typedef std::function<bool(const std::string& kind, const Json& v, Json& out)> NodeFn;
+Json rewrite_nodes(const Json& e, const NodeFn& fn) {
   if (e.is_obj()) {
-    if (e.o.size() == 1 && e.o[0].first == "column" && e.o[0].second.is_obj() && e.o[0].second.find("name")) return fn(e.o[0].second);
+    Json out;
+    if (e.o.size() == 1 && fn(e.o[0].first, e.o[0].second, out)) return out;
     Json r = jobj();
-    for (auto& kv : e.o) r.o.emplace_back(kv.first, rewrite_columns(kv.second, fn));
+    for (auto& kv : e.o) r.o.emplace_back(kv.first, rewrite_nodes(kv.second, fn));
     return r;
   }
-  if (e.is_arr()) { Json r = jarr(); for (auto& v : e.a) r.a.push_back(rewrite_columns(v, fn)); return r; }
+  if (e.is_arr()) { Json r = jarr(); for (auto& v : e.a) r.a.push_back(rewrite_nodes(v, fn)); return r; }
   return e;
+}
+Json rewrite_columns(const Json& e, const std::function<Json(const Json&)>& fn) {
+  return rewrite_nodes(e, [&](const std::string& kind, const Json& v, Json& out) {
+    if (!(kind == "column" && v.is_obj() && v.find("name"))) return false;
+    out = fn(v); return true;
+  });
 }
 typedef std::map<std::string, Json> ColMap;      // output column of a ProjectionExec -> expression over its input
 Json inline_projection(const Json& e, const ColMap* m) {
@@ -154,44 +193,28 @@ bool has_like(const Json& e) {
 // (gpuq_like_utf8) -- so the comparison becomes a like_expr whose pattern is the literal with its % and _ escaped.  NULL semantics
 // are the same (NULL operand -> NULL).  Applied to the whole plan when it is created; shorter literals are left alone.
 Json lower_long_string_eq(const Json& e) {
-  if (e.is_obj()) {
-    if (e.o.size() == 1 && e.o[0].first == "binary_expr" && e.o[0].second.is_obj()) {
-      const Json& b = e.o[0].second;
-      const std::string op = b.get_str("op", "");
-      if ((op == "=" || op == "!=" || op == "Eq" || op == "NotEq") && b.find("l") && b.find("r")) {
-        auto is_col = [](const Json& v) { return v.is_obj() && v.o.size() == 1 && v.o[0].first == "column"; };
-        auto long_lit = [](const Json& v) {
-          if (!(v.is_obj() && v.o.size() == 1 && v.o[0].first == "literal" && v.o[0].second.is_obj())) return false;
-          const Json& l = v.o[0].second;
-          return l.get_str("type", "") == "Utf8" && l.find("value") && !l.at("value").is_null() && l.at("value").str().size() > 15;
-        };
-        const Json* c = nullptr; const Json* l = nullptr;
-        if (is_col(b.at("l")) && long_lit(b.at("r"))) { c = &b.at("l"); l = &b.at("r"); }
-        else if (is_col(b.at("r")) && long_lit(b.at("l"))) { c = &b.at("r"); l = &b.at("l"); }
-        if (c) {
-          std::string pat;
-          for (char ch : l->o[0].second.at("value").str()) { if (ch == '%' || ch == '_') pat += '\\'; pat += ch; }
-          return jobj({{"like_expr", jobj({{"negated", jbool(op == "!=" || op == "NotEq")}, {"case_insensitive", jbool(false)}, {"expr", *c},
-                                           {"pattern", jobj({{"literal", jobj({{"type", jstr("Utf8")}, {"value", jstr(pat)}})}})}})}});
-        }
-      }
-    }
-    Json r = jobj();
-    for (auto& kv : e.o) r.o.emplace_back(kv.first, lower_long_string_eq(kv.second));
-    return r;
-  }
-  if (e.is_arr()) { Json r = jarr(); for (auto& v : e.a) r.a.push_back(lower_long_string_eq(v)); return r; }
-  return e;
+  return rewrite_nodes(e, [](const std::string& kind, const Json& b, Json& out) {
+    if (!(kind == "binary_expr" && b.is_obj())) return false;
+    const std::string op = b.get_str("op", "");
+    if (!((op == "=" || op == "!=" || op == "Eq" || op == "NotEq") && b.find("l") && b.find("r"))) return false;
+    auto long_lit = [](const Json& v) {
+      if (!(v.is_obj() && v.o.size() == 1 && v.o[0].first == "literal" && v.o[0].second.is_obj())) return false;
+      const Json& l = v.o[0].second;
+      return l.get_str("type", "") == "Utf8" && l.find("value") && !l.at("value").is_null() && l.at("value").str().size() > 15;
+    };
+    const Json* c = nullptr; const Json* l = nullptr;
+    if (bare_column(b.at("l")) && long_lit(b.at("r"))) { c = &b.at("l"); l = &b.at("r"); }
+    else if (bare_column(b.at("r")) && long_lit(b.at("l"))) { c = &b.at("r"); l = &b.at("l"); }
+    if (!c) return false;
+    std::string pat;
+    for (char ch : l->o[0].second.at("value").str()) { if (ch == '%' || ch == '_') pat += '\\'; pat += ch; }
+    out = jobj({{"like_expr", jobj({{"negated", jbool(op == "!=" || op == "NotEq")}, {"case_insensitive", jbool(false)}, {"expr", *c},
+                                    {"pattern", jobj({{"literal", jobj({{"type", jstr("Utf8")}, {"value", jstr(pat)}})}})}})}});
+    return true;
+  });
 }
 Json rewrite_like(const Json& e, const std::function<Json(const Json&)>& fn) {
-  if (e.is_obj()) {
-    if (e.o.size() == 1 && e.o[0].first == "like_expr") return fn(e.o[0].second);
-    Json r = jobj();
-    for (auto& kv : e.o) r.o.emplace_back(kv.first, rewrite_like(kv.second, fn));
-    return r;
-  }
-  if (e.is_arr()) { Json r = jarr(); for (auto& v : e.a) r.a.push_back(rewrite_like(v, fn)); return r; }
-  return e;
+  return rewrite_nodes(e, [&](const std::string& kind, const Json& v, Json& out) { if (kind != "like_expr") return false; out = fn(v); return true; });
 }
 
 // ---------------------------------------------------------------- execution context
@@ -271,6 +294,14 @@ bool use_deferred(Exec& x, gpuq_op* op) {
   return true;
 }
 BufP dev_alloc(size_t bytes) { BufP b = std::make_shared<DevBuf>(); b->ensure(bytes ? bytes : 16); return b; }
+BufP alloc_rows(int64_t n) { return dev_alloc((size_t)std::max<int64_t>(n, 1) * 4 + 16); }      // room for n row ids (a selection, a permutation, one half of a pair list)
+BufP zeroed_bitmap(Exec& x, int64_t n) { const size_t nb = bitmap_bytes(n); BufP b = dev_alloc(nb); HIPCHECK(hipMemsetAsync(b->p, 0, nb, (hipStream_t)x.stream)); return b; }
+// a small host array into `dst`; wait: the source may die as soon as this returns (callers that upload several arrays wait once, themselves)
+void upload(Exec& x, const BufP& dst, const void* src, size_t nbytes, bool wait = true) {
+  if (!nbytes) return;
+  HIPCHECK(hipMemcpyAsync(dst->p, src, nbytes, hipMemcpyHostToDevice, (hipStream_t)x.stream));
+  if (wait) HIPCHECK(hipStreamSynchronize((hipStream_t)x.stream));
+}
 
 // ONE host round trip for everything deferred so far: the status words of the pending operators, the count behind `t` (made exact)
 // and the counts behind the metrics booked with a bound.
@@ -313,7 +344,7 @@ PTable alloc_outputs(gpuq_op* op, int64_t n, std::vector<gpuq_column>& carr) {
   const int nf = gpuq_op_num_outputs(op);
   std::vector<gpuq_field_info> f((size_t)nf);
   for (int i = 0; i < nf; ++i) if (gpuq_op_output_field(op, i, &f[(size_t)i]) != GPUQ_OK) throw std::runtime_error("plan: output field query failed");
-  const size_t bm = (size_t)((n + 63) / 64) * 8 + 8;
+  const size_t bm = bitmap_bytes(n);
   std::vector<size_t> doff((size_t)nf), voff((size_t)nf);
   size_t off = 256;
   for (int i = 0; i < nf; ++i) {
@@ -337,6 +368,26 @@ PTable alloc_outputs(gpuq_op* op, int64_t n, std::vector<gpuq_column>& carr) {
   return t;
 }
 
+// ---- helper columns: computed on the device next to a table's own columns, for one operator to read
+// appends one to `t`: read as it lies (side 0), alive as long as the table (data_keep / valid; valid's bits are its validity)
+void append_column(PTable& t, const std::string& name, int tid, const void* data, const BufP& data_keep, const BufP& valid, int64_t length, bool nullable, int p = 0, int s = 0) {
+  PCol c; c.name = name; c.type = type_json_of(tid, p, s); c.nullable = nullable;
+  c.c.type = tid; c.c.precision = p; c.c.scale = s; c.c.repr = GPUQ_REPR_ARROW; c.c.data = data; c.c.validity = valid ? (const uint8_t*)valid->p : nullptr; c.c.length = length;
+  t.cols.push_back(c); t.sides.push_back(0); t.record_cap = 0;
+  if (data_keep) t.keep.push_back(data_keep);
+  if (valid) t.keep.push_back(valid);
+}
+// the zeroed result bitmap of a Boolean helper over n rows, and its validity bitmap when it can be NULL
+void alloc_bool_helper(Exec& x, int64_t n, bool nullable, BufP& bits, BufP& valid) { bits = zeroed_bitmap(x, n); valid = nullable ? zeroed_bitmap(x, n) : nullptr; }
+// a PACKED15 string column of m values (what an operator writes) back to Arrow layout: offsets + bytes
+void unpack_utf8(Exec& x, gpuq_column& c, int64_t m, std::vector<BufP>& keep) {
+  BufP offs = dev_alloc((size_t)(m + 4) * 4), data = dev_alloc((size_t)m * 15 + 16);
+  int64_t dl = 0;
+  check(x, gpuq_unpack_utf8(x.ctx, x.stream, c.data, m, (int32_t*)offs->p, (uint8_t*)data->p, m * 15 + 16, &dl));
+  c.repr = GPUQ_REPR_ARROW; c.data = data->p; c.offsets = (const int32_t*)offs->p;
+  keep.push_back(offs); keep.push_back(data);
+}
+
 // LIKE runs as its own kernel over the Arrow-layout bytes (gpuq_like_utf8): every like_expr node becomes a reference to a Boolean
 // column appended to a copy of the table.  The operand must be a column of `t`, the pattern a Utf8 literal.
 PTable lower_like(Exec& x, const PTable& t, std::vector<Json>& exprs) {
@@ -347,37 +398,25 @@ PTable lower_like(Exec& x, const PTable& t, std::vector<Json>& exprs) {
   for (auto& e : exprs)
     e = rewrite_like(e, [&](const Json& v) {
       const Json& operand = v.at("expr"); const Json& pat = v.at("pattern");
-      if (!(operand.is_obj() && operand.o.size() == 1 && operand.o[0].first == "column")) throw Unsupported("LIKE over a computed expression is not supported on device (operand must be a column)");
+      const std::string* col = bare_column(operand);
+      if (!col) throw Unsupported("LIKE over a computed expression is not supported on device (operand must be a column)");
       if (!(pat.is_obj() && pat.find("literal") && pat.at("literal").get_str("type", "") == "Utf8" && pat.at("literal").find("value") && !pat.at("literal").at("value").is_null()))
         throw Unsupported("LIKE needs a non-NULL Utf8 literal pattern");
-      found.push_back({operand.o[0].second.at("name").str(), pat.at("literal").at("value").str(), v.get_bool("negated", false), v.get_bool("case_insensitive", false)});
-      return jobj({{"column", jobj({{"name", jstr("__like_" + std::to_string(found.size() - 1))}})}});
+      found.push_back({*col, pat.at("literal").at("value").str(), v.get_bool("negated", false), v.get_bool("case_insensitive", false)});
+      return jcolname("__like_" + std::to_string(found.size() - 1));
     });
   PTable out = t;
-  hipStream_t s = (hipStream_t)x.stream;
   for (size_t k = 0; k < found.size(); ++k) {
-    size_t i = 0; while (i < t.cols.size() && t.cols[i].name != found[k].col) ++i;
-    if (i == t.cols.size()) throw std::runtime_error("plan: column '" + found[k].col + "' not found in the input schema");
-    PCol c = t.cols[i]; const int sd = t.sides[i];
+    const int i = find_column(t, found[k].col);
+    if (i < 0) throw std::runtime_error("plan: column '" + found[k].col + "' not found in the input schema");
+    PCol c = t.cols[(size_t)i];
     if (c.c.type != T_UTF8) throw std::runtime_error("LIKE over a non-Utf8 column '" + c.name + "'");
-    if (c.c.repr == GPUQ_REPR_PACKED15) {      // a string produced by an operator: back to offsets + bytes first
-      const int64_t m = c.c.length;
-      BufP offs = dev_alloc((size_t)(m + 4) * 4), data = dev_alloc((size_t)m * 15 + 16);
-      int64_t dl = 0;
-      check(x, gpuq_unpack_utf8(x.ctx, x.stream, c.c.data, m, (int32_t*)offs->p, (uint8_t*)data->p, m * 15 + 16, &dl));
-      c.c.repr = GPUQ_REPR_ARROW; c.c.data = data->p; c.c.offsets = (const int32_t*)offs->p;
-      out.keep.push_back(offs); out.keep.push_back(data);
-    }
-    const size_t nb = (size_t)((t.n + 63) / 64) * 8 + 8;
-    const bool nullable = c.nullable || (sd > 0 && !t.dense);
-    BufP bits = dev_alloc(nb), valid = nullable ? dev_alloc(nb) : nullptr;
-    HIPCHECK(hipMemsetAsync(bits->p, 0, nb, s)); if (valid) HIPCHECK(hipMemsetAsync(valid->p, 0, nb, s));
-    check(x, gpuq_like_utf8(x.ctx, x.stream, &c.c, sd > 0 ? t.via[(size_t)sd - 1] : nullptr, t.n, found[k].pattern.c_str(), found[k].negated, found[k].ci,
+    if (c.c.repr == GPUQ_REPR_PACKED15) unpack_utf8(x, c.c, c.c.length, out.keep);      // a string produced by an operator: back to offsets + bytes first
+    const bool nullable = nullable_in(t, (size_t)i);
+    BufP bits, valid; alloc_bool_helper(x, t.n, nullable, bits, valid);
+    check(x, gpuq_like_utf8(x.ctx, x.stream, &c.c, via_of(t, (size_t)i), t.n, found[k].pattern.c_str(), found[k].negated, found[k].ci,
                             (uint8_t*)bits->p, valid ? (uint8_t*)valid->p : nullptr));
-    PCol b; b.name = "__like_" + std::to_string(k); b.type = jstr("Boolean"); b.nullable = nullable;
-    b.c.type = T_BOOL; b.c.repr = GPUQ_REPR_ARROW; b.c.data = bits->p; b.c.validity = valid ? (const uint8_t*)valid->p : nullptr; b.c.length = t.n;
-    out.cols.push_back(b); out.sides.push_back(0);
-    out.keep.push_back(bits); if (valid) out.keep.push_back(valid);
+    append_column(out, "__like_" + std::to_string(k), T_BOOL, bits->p, bits, valid, t.n, nullable);
   }
   return out;
 }
@@ -386,14 +425,16 @@ PTable lower_like(Exec& x, const PTable& t, std::vector<Json>& exprs) {
 // column, `=` / `!=` between two columns.  The register program refuses them at run time (a value longer than 15 bytes reached the
 // comparison); the executor then runs the expression again with every such comparison lowered to a Boolean helper column computed over
 // the Arrow-layout bytes (gpuq_utf8_compare) -- the same move LIKE makes.  Operands must be bare columns of `t` / Utf8 literals.
+// index of the column `e` names when `e` is a bare column reference to an Arrow-layout Utf8 column of `t`, else -1
+int long_key_column(const PTable& t, const Json& e) {
+  const std::string* n = bare_column(e);
+  const int i = n ? find_column(t, *n) : -1;
+  return (i >= 0 && t.cols[(size_t)i].c.type == T_UTF8 && t.cols[(size_t)i].c.repr == GPUQ_REPR_ARROW) ? i : -1;
+}
 bool strcmp_operand(const PTable& t, const Json& e, int& col, std::string& lit) {
-  col = -1;
+  col = long_key_column(t, e);
+  if (col >= 0) return true;
   if (!(e.is_obj() && e.o.size() == 1)) return false;
-  if (e.o[0].first == "column" && e.o[0].second.is_obj() && e.o[0].second.find("name")) {
-    const std::string& n = e.o[0].second.at("name").str();
-    for (size_t i = 0; i < t.cols.size(); ++i) if (t.cols[i].name == n) { if (t.cols[i].c.type == T_UTF8 && t.cols[i].c.repr == GPUQ_REPR_ARROW) { col = (int)i; return true; } return false; }
-    return false;
-  }
   if (e.o[0].first == "literal") {
     const Json& v = e.o[0].second;
     const Json* ty = v.find("type"); const Json* val = v.find("value");
@@ -404,46 +445,31 @@ bool strcmp_operand(const PTable& t, const Json& e, int& col, std::string& lit) 
 PTable lower_strcmp(Exec& x, const PTable& t, std::vector<Json>& exprs) {
   struct Found { int a, b; std::string lit; int op; };
   std::vector<Found> found;
-  std::function<Json(const Json&)> walk = [&](const Json& e) -> Json {
-    if (e.is_obj()) {
-      if (e.o.size() == 1 && e.o[0].first == "binary_expr") {
-        const Json& v = e.o[0].second;
-        static const std::map<std::string, int> ops = {{"=", 0}, {"Eq", 0}, {"==", 0}, {"!=", 1}, {"NotEq", 1}, {"<>", 1}, {"<", 2}, {"Lt", 2}, {"<=", 3}, {"LtEq", 3}, {">", 4}, {"Gt", 4}, {">=", 5}, {"GtEq", 5}};
-        auto it = ops.find(v.get_str("op", ""));
-        int ca = -1, cb = -1; std::string la, lb;
-        if (it != ops.end() && strcmp_operand(t, v.at("l"), ca, la) && strcmp_operand(t, v.at("r"), cb, lb) && (ca >= 0 || cb >= 0)) {
-          static const int mirror[6] = {0, 1, 4, 5, 2, 3};      // literal OP column  ==  column mirror(OP) literal
-          Found f;
-          if (ca >= 0) { f.a = ca; f.b = cb; f.lit = lb; f.op = it->second; } else { f.a = cb; f.b = -1; f.lit = la; f.op = mirror[it->second]; }
-          found.push_back(f);
-          return jobj({{"column", jobj({{"name", jstr("__cmp_" + std::to_string(found.size() - 1))}})}});
-        }
-      }
-      Json r = jobj();
-      for (auto& kv : e.o) r.o.emplace_back(kv.first, walk(kv.second));
-      return r;
-    }
-    if (e.is_arr()) { Json r = jarr(); for (auto& v : e.a) r.a.push_back(walk(v)); return r; }
-    return e;
+  const NodeFn lower = [&](const std::string& kind, const Json& v, Json& out) {
+    if (kind != "binary_expr") return false;
+    static const std::map<std::string, int> ops = {{"=", 0}, {"Eq", 0}, {"==", 0}, {"!=", 1}, {"NotEq", 1}, {"<>", 1}, {"<", 2}, {"Lt", 2}, {"<=", 3}, {"LtEq", 3}, {">", 4}, {"Gt", 4}, {">=", 5}, {"GtEq", 5}};
+    auto it = ops.find(v.get_str("op", ""));
+    int ca = -1, cb = -1; std::string la, lb;
+    if (!(it != ops.end() && strcmp_operand(t, v.at("l"), ca, la) && strcmp_operand(t, v.at("r"), cb, lb) && (ca >= 0 || cb >= 0))) return false;
+    static const int mirror[6] = {0, 1, 4, 5, 2, 3};      // literal OP column  ==  column mirror(OP) literal
+    Found f;
+    if (ca >= 0) { f.a = ca; f.b = cb; f.lit = lb; f.op = it->second; } else { f.a = cb; f.b = -1; f.lit = la; f.op = mirror[it->second]; }
+    found.push_back(f);
+    out = jcolname("__cmp_" + std::to_string(found.size() - 1));
+    return true;
   };
-  for (auto& e : exprs) e = walk(e);
+  for (auto& e : exprs) e = rewrite_nodes(e, lower);
   if (found.empty()) return t;
   PTable out = t;
-  hipStream_t s = (hipStream_t)x.stream;
-  const size_t nb = (size_t)((t.n + 63) / 64) * 8 + 8;
   for (size_t k = 0; k < found.size(); ++k) {
     const Found& f = found[k];
-    const PCol& a = t.cols[(size_t)f.a]; const int sa = t.sides[(size_t)f.a];
-    const PCol* b = f.b >= 0 ? &t.cols[(size_t)f.b] : nullptr; const int sb = f.b >= 0 ? t.sides[(size_t)f.b] : 0;
-    const bool nullable = a.nullable || (sa > 0 && !t.dense) || (b && (b->nullable || (sb > 0 && !t.dense)));
-    BufP bits = dev_alloc(nb), valid = nullable ? dev_alloc(nb) : nullptr;
-    HIPCHECK(hipMemsetAsync(bits->p, 0, nb, s)); if (valid) HIPCHECK(hipMemsetAsync(valid->p, 0, nb, s));
-    check(x, gpuq_utf8_compare(x.ctx, x.stream, &a.c, sa > 0 ? t.via[(size_t)sa - 1] : nullptr, b ? &b->c : nullptr, sb > 0 ? t.via[(size_t)sb - 1] : nullptr,
+    const PCol& a = t.cols[(size_t)f.a];
+    const PCol* b = f.b >= 0 ? &t.cols[(size_t)f.b] : nullptr;
+    const bool nullable = nullable_in(t, (size_t)f.a) || (b && nullable_in(t, (size_t)f.b));
+    BufP bits, valid; alloc_bool_helper(x, t.n, nullable, bits, valid);
+    check(x, gpuq_utf8_compare(x.ctx, x.stream, &a.c, via_of(t, (size_t)f.a), b ? &b->c : nullptr, b ? via_of(t, (size_t)f.b) : nullptr,
                                b ? nullptr : f.lit.data(), b ? 0 : (int64_t)f.lit.size(), t.n, f.op, (uint8_t*)bits->p, valid ? (uint8_t*)valid->p : nullptr));
-    PCol c; c.name = "__cmp_" + std::to_string(k); c.type = jstr("Boolean"); c.nullable = nullable;
-    c.c.type = T_BOOL; c.c.repr = GPUQ_REPR_ARROW; c.c.data = bits->p; c.c.validity = valid ? (const uint8_t*)valid->p : nullptr; c.c.length = t.n;
-    out.cols.push_back(c); out.sides.push_back(0);
-    out.keep.push_back(bits); if (valid) out.keep.push_back(valid);
+    append_column(out, "__cmp_" + std::to_string(k), T_BOOL, bits->p, bits, valid, t.n, nullable);
   }
   return out;
 }
@@ -454,26 +480,15 @@ PTable lower_strcmp(Exec& x, const PTable& t, std::vector<Json>& exprs) {
 // that is a plain Utf8 column in Arrow layout is replaced by an Int64 code column appended to (a copy of) the table; strings come
 // back with a take through the codes.  Nothing is paid on the common path: the rewrite only happens after the loud failure.
 bool is_long_string_failure(const std::exception& e) { return std::string(e.what()).find("longer than 15 bytes reached") != std::string::npos; }
-// index of the column `e` names when `e` is a bare column reference to an Arrow-layout Utf8 column of `t`, else -1
-int long_key_column(const PTable& t, const Json& e) {
-  if (!(e.is_obj() && e.o.size() == 1 && e.o[0].first == "column" && e.o[0].second.is_obj() && e.o[0].second.find("name"))) return -1;
-  const std::string& n = e.o[0].second.at("name").str();
-  for (size_t i = 0; i < t.cols.size(); ++i)
-    if (t.cols[i].name == n) return (t.cols[i].c.type == T_UTF8 && t.cols[i].c.repr == GPUQ_REPR_ARROW) ? (int)i : -1;
-  return -1;
-}
 struct Utf8DictGuard { gpuq_utf8_dict* d = nullptr; ~Utf8DictGuard() { if (d) gpuq_utf8_dict_free(d); } };
+struct JoinTableGuard { gpuq_join_table* t = nullptr; ~JoinTableGuard() { if (t) gpuq_join_table_free(t); } };
 // appends the code column of t.cols[ci] (insert: fills `dict` from it; else looks it up in `dict`) under `name`
 void append_code_column(Exec& x, PTable& t, int ci, gpuq_utf8_dict* dict, bool insert, const std::string& name) {
-  const PCol& c = t.cols[(size_t)ci]; const int sd = t.sides[(size_t)ci];
-  const size_t nb = (size_t)((t.n + 63) / 64) * 8 + 8;
-  BufP codes = dev_alloc((size_t)std::max<int64_t>(t.n, 1) * 8 + 16), valid = dev_alloc(nb);
-  HIPCHECK(hipMemsetAsync(valid->p, 0, nb, (hipStream_t)x.stream));
-  const int rc = gpuq_utf8_intern(dict, x.stream, &c.c, sd > 0 ? t.via[(size_t)sd - 1] : nullptr, t.n, insert ? 1 : 0, (int64_t*)codes->p, (uint8_t*)valid->p);
+  const PCol& c = t.cols[(size_t)ci];
+  BufP codes = dev_alloc((size_t)std::max<int64_t>(t.n, 1) * 8 + 16), valid = zeroed_bitmap(x, t.n);
+  const int rc = gpuq_utf8_intern(dict, x.stream, &c.c, via_of(t, (size_t)ci), t.n, insert ? 1 : 0, (int64_t*)codes->p, (uint8_t*)valid->p);
   check(x, rc);
-  PCol k; k.name = name; k.type = jstr("Int64"); k.nullable = true;
-  k.c.type = T_INT64; k.c.repr = GPUQ_REPR_ARROW; k.c.data = codes->p; k.c.validity = (const uint8_t*)valid->p; k.c.length = t.n;
-  t.cols.push_back(k); t.sides.push_back(0); t.keep.push_back(codes); t.keep.push_back(valid); t.record_cap = 0;
+  append_column(t, name, T_INT64, codes->p, codes, valid, t.n, true);
 }
 void strip_code_columns(PTable& t) {
   for (size_t i = t.cols.size(); i-- > 0;)
@@ -487,18 +502,33 @@ template <class F> auto retry_long_cmp(const int tag, F&& run) -> decltype(run(t
   catch (const Unsupported& e) { if (!is_long_string_failure(e)) throw; }
   return run(tag + 64, true);
 }
+// ---------------------------------------------------------------- operator descriptors: one builder per kind, called on a cached_op miss (or from a static schema())
+// in_names: the input's column names the expressions are bound to by name; nullptr: they are by-position references already
+Json project_desc(const Json& input, const std::vector<Json>& exprs, const std::vector<std::string>& names, const std::vector<std::string>* in_names) {
+  Json ex = jarr();
+  for (size_t i = 0; i < exprs.size(); ++i) ex.a.push_back(jobj({{"expr", in_names ? rebind(exprs[i], *in_names) : exprs[i]}, {"name", jstr(names[i])}}));
+  return jobj({{"op", jstr("project")}, {"input", input}, {"exprs", ex}});
+}
+Json filter_desc(const PTable& t, const Json& predicate) { return jobj({{"op", jstr("filter")}, {"input", input_of(t)}, {"predicate", rebind(predicate, names_of(t))}}); }
+// one ORDER BY entry `s` with its defaults spelled out, over `expr`
+Json sort_key(const Json& s, const Json& expr) {
+  const bool asc = s.get_bool("asc", true);
+  return jobj({{"expr", expr}, {"asc", jbool(asc)}, {"nulls_first", jbool(s.get_bool("nulls_first", !asc))}});
+}
+Json sort_desc(const PTable& t, const Json& sort_exprs) {
+  const auto nm = names_of(t);
+  Json ex = jarr();
+  for (auto& s : sort_exprs.a) ex.a.push_back(sort_key(s, rebind(s.at("expr"), nm)));
+  return jobj({{"op", jstr("sort")}, {"input", input_of(t)}, {"expr", ex}});
+}
+
 static PTable project_impl(Exec& x, const PTable& t_in, const std::vector<Json>& exprs_in, const std::vector<std::string>& names, const void* site, int tag, const bool long_cmp) {
   std::vector<Json> exprs = exprs_in;
   bool any_like = false; for (auto& e : exprs) any_like = any_like || has_like(e);
   PTable t_res = t_in; if (any_like || long_cmp) resolve(x, t_res);      // the LIKE / compare kernels take an exact row count
   PTable t = lower_like(x, t_res, exprs);
   if (long_cmp) t = lower_strcmp(x, t, exprs);
-  gpuq_op* op = cached_op(x, site, tag, table_sig(t), [&]() {
-    Json ex = jarr();
-    const auto nm = names_of(t);
-    for (size_t i = 0; i < exprs.size(); ++i) ex.a.push_back(jobj({{"expr", rebind(exprs[i], nm)}, {"name", jstr(names[i])}}));
-    return jobj({{"op", jstr("project")}, {"input", jobj({{"fields", table_fields(t)}})}, {"exprs", ex}});
-  });
+  gpuq_op* op = cached_op(x, site, tag, table_sig(t), [&]() { const auto nm = names_of(t); return project_desc(input_of(t), exprs, names, &nm); });
   const bool deferred = prep(x, op, t);
   std::vector<gpuq_column> carr;
   PTable out = alloc_outputs(op, t.n, carr);
@@ -511,7 +541,7 @@ static PTable project_impl(Exec& x, const PTable& t_in, const std::vector<Json>&
   // caught later, when its bytes are needed (gpuq_unpack_utf8).  Projections of numeric tables stay asynchronous.
   bool has_utf8 = false, computed = false;
   for (auto& c : t.cols) has_utf8 = has_utf8 || c.c.type == T_UTF8;
-  for (auto& e : exprs) computed = computed || !(e.is_obj() && e.o.size() == 1 && (e.o[0].first == "column" || e.o[0].first == "literal"));
+  for (auto& e : exprs) computed = computed || !(bare_column(e) || (e.is_obj() && e.o.size() == 1 && e.o[0].first == "literal"));
   if (has_utf8 && computed) check(x, gpuq_op_check(op, x.stream));
   return out;
 }
@@ -567,7 +597,7 @@ PTable select_view(Exec& x, const PTable& t, const uint32_t* idx, int64_t n, con
 
 // Arrow-layout Utf8 column read through an index vector (or as it lies) into a fresh Arrow-layout column: any string length
 PCol take_utf8(Exec& x, const PCol& c, const uint32_t* idx, int64_t n, bool nullable, std::vector<BufP>& keep) {
-  BufP offs = dev_alloc((size_t)(n + 4) * 4), valid = dev_alloc((size_t)((n + 63) / 64) * 8 + 8);
+  BufP offs = dev_alloc((size_t)(n + 4) * 4), valid = dev_alloc(bitmap_bytes(n));
   int64_t dl = 0;
   int rc = gpuq_take_utf8(x.ctx, x.stream, &c.c, idx, n, (int32_t*)offs->p, (uint8_t*)valid->p, nullptr, 0, &dl);
   if (rc != GPUQ_OK && rc != GPUQ_ERR_CAPACITY) check(x, rc);
@@ -598,7 +628,7 @@ PTable materialize(Exec& x, const PTable& t_in, bool force) {
     const PCol& c = t.cols[i];
     if (c.c.offsets && !pack_strings) {
       if (!t.is_view()) out.cols[i] = c;
-      else out.cols[i] = take_utf8(x, c, t.sides[i] > 0 ? t.via[(size_t)t.sides[i] - 1] : nullptr, t.n, c.nullable || (t.sides[i] > 0 && !t.dense), out.keep);
+      else out.cols[i] = take_utf8(x, c, via_of(t, i), t.n, nullable_in(t, i), out.keep);
     } else fixed.push_back(i);
   }
   for (size_t a = 0; a < fixed.size(); a += 12) {
@@ -609,11 +639,7 @@ PTable materialize(Exec& x, const PTable& t_in, bool force) {
     for (size_t i = 0; i < sub.cols.size(); ++i) { ex.push_back(jcol(sub.cols[i].name, (int)i)); nm.push_back(sub.cols[i].name); }
     // rebind by position, not by name: duplicate names (join outputs) must keep their own column
     static const int mat_site = 0;
-    gpuq_op* op = cached_op(x, &mat_site, 0, table_sig(sub), [&]() {
-      Json exj = jarr();
-      for (size_t i = 0; i < ex.size(); ++i) exj.a.push_back(jobj({{"expr", ex[i]}, {"name", jstr(nm[i])}}));
-      return jobj({{"op", jstr("project")}, {"input", jobj({{"fields", table_fields(sub)}})}, {"exprs", exj}});
-    });
+    gpuq_op* op = cached_op(x, &mat_site, 0, table_sig(sub), [&]() { return project_desc(input_of(sub), ex, nm, nullptr); });
     prep(x, op, sub);
     if (!sub.n_dev && t.n_dev) { t.n = sub.n; t.count_from(sub); out.n = sub.n; out.count_from(sub); }      // (resolved on the way)
     std::vector<gpuq_column> carr;
@@ -628,22 +654,33 @@ PTable materialize(Exec& x, const PTable& t_in, bool force) {
   return out;
 }
 
-// the passing driving positions of `source` (in order) and their number
-static int64_t filter_sel_impl(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag, BufP& sel_out, const bool long_cmp) {
+// The front the two filter forms share: the predicate's LIKE / long-string comparisons become helper columns (visible to the predicate
+// only: `source` stays the table a view is built over), the filter operator runs, `sel` holds the passing driving positions of
+// `source` (in order) and the device word `cnt` their number.  exact: the caller reads the count back -- source's own count is made
+// exact first and the operator is not offered a deferred run; otherwise it may run deferred (`deferred`), over `n` rows at most.
+struct FilterRun { gpuq_op* op = nullptr; BufP sel, cnt; int64_t n = 0; bool deferred = false; PTable t; };      // t: what the operator read (helper columns live as long as this)
+static FilterRun run_filter(Exec& x, PTable& source, const Json& predicate_in, const void* site, int tag, const bool long_cmp, const bool exact) {
   std::vector<Json> pe{predicate_in};
-  PTable source = source_in; resolve(x, source);      // (the callers of this form need the exact count back)
-  PTable t = lower_like(x, source, pe);
+  if (exact || has_like(predicate_in) || long_cmp) resolve(x, source);      // the LIKE / compare kernels take an exact row count
+  FilterRun r; PTable& t = r.t;
+  t = lower_like(x, source, pe);
   if (long_cmp) t = lower_strcmp(x, t, pe);
   const Json& predicate = pe[0];
-  gpuq_op* op = cached_op(x, site, tag, table_sig(t), [&]() {
-    return jobj({{"op", jstr("filter")}, {"input", jobj({{"fields", table_fields(t)}})}, {"predicate", rebind(predicate, names_of(t))}});
-  });
-  sel_out = dev_alloc((size_t)std::max<int64_t>(t.n, 1) * 4 + 16);
-  BufP cnt = dev_alloc(16);
+  r.op = cached_op(x, site, tag, table_sig(t), [&]() { return filter_desc(t, predicate); });
+  r.deferred = !exact && prep(x, r.op, t);
+  if (!t.n_dev && source.n_dev) { source.n = t.n; source.count_from(t); }
+  r.sel = alloc_rows(t.n); r.cnt = dev_alloc(16); r.n = t.n;
   InputC ic; make_input(t, ic);
-  check(x, gpuq_filter_run(op, x.stream, &ic.in, 0, (uint32_t*)sel_out->p, (uint64_t*)cnt->p));
-  const int64_t k = (int64_t)read_u64(x, cnt->p);
-  check(x, gpuq_op_check(op, x.stream));
+  check(x, gpuq_filter_run(r.op, x.stream, &ic.in, 0, (uint32_t*)r.sel->p, (uint64_t*)r.cnt->p));
+  return r;
+}
+// the passing driving positions of `source` (in order) and their number
+static int64_t filter_sel_impl(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag, BufP& sel_out, const bool long_cmp) {
+  PTable source = source_in;
+  const FilterRun r = run_filter(x, source, predicate_in, site, tag, long_cmp, true);      // (the callers of this form need the exact count back)
+  sel_out = r.sel;
+  const int64_t k = (int64_t)read_u64(x, r.cnt->p);
+  check(x, gpuq_op_check(r.op, x.stream));
   return k;
 }
 int64_t filter_sel(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag, BufP& sel_out) {
@@ -651,27 +688,15 @@ int64_t filter_sel(Exec& x, const PTable& source_in, const Json& predicate_in, c
 }
 
 static PTable filter_table_impl(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag, const bool long_cmp) {
-  std::vector<Json> pe{predicate_in};
   PTable source = source_in;
-  if (has_like(predicate_in) || long_cmp) resolve(x, source);      // the LIKE / compare kernels take an exact row count
-  PTable t = lower_like(x, source, pe);          // helper columns are visible to the predicate only: the view is over `source`
-  if (long_cmp) t = lower_strcmp(x, t, pe);
-  const Json& predicate = pe[0];
-  gpuq_op* op = cached_op(x, site, tag, table_sig(t), [&]() {
-    return jobj({{"op", jstr("filter")}, {"input", jobj({{"fields", table_fields(t)}})}, {"predicate", rebind(predicate, names_of(t))}});
-  });
-  const bool deferred = prep(x, op, t);
-  if (!t.n_dev && source.n_dev) { source.n = t.n; source.count_from(t); }
-  BufP sel = dev_alloc((size_t)std::max<int64_t>(t.n, 1) * 4 + 16), cnt = dev_alloc(16);
-  InputC ic; make_input(t, ic);
-  check(x, gpuq_filter_run(op, x.stream, &ic.in, 0, (uint32_t*)sel->p, (uint64_t*)cnt->p));
-  if (deferred && t.n > 0) {      // the survivors' count stays on the device: the view is as long as its input at most
-    PTable c; c.n_dev = (const uint64_t*)cnt->p; c.n_keep = cnt;
-    return select_view(x, source, (const uint32_t*)sel->p, t.n, sel, &c);
+  const FilterRun r = run_filter(x, source, predicate_in, site, tag, long_cmp, false);
+  if (r.deferred && r.n > 0) {      // the survivors' count stays on the device: the view is as long as its input at most
+    PTable c; c.n_dev = (const uint64_t*)r.cnt->p; c.n_keep = r.cnt;
+    return select_view(x, source, (const uint32_t*)r.sel->p, r.n, r.sel, &c);
   }
-  const int64_t k = (int64_t)read_u64(x, cnt->p);
-  check(x, gpuq_op_check(op, x.stream));
-  return select_view(x, source, (const uint32_t*)sel->p, k, sel);
+  const int64_t k = (int64_t)read_u64(x, r.cnt->p);
+  check(x, gpuq_op_check(r.op, x.stream));
+  return select_view(x, source, (const uint32_t*)r.sel->p, k, r.sel);
 }
 PTable filter_table(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag) {
   return retry_long_cmp(tag, [&](int tg, bool long_cmp) { return filter_table_impl(x, source_in, predicate_in, site, tg, long_cmp); });
@@ -682,25 +707,16 @@ PTable filter_table(Exec& x, const PTable& source_in, const Json& predicate_in, 
 // gpuq_sort_run_keys) -- the view over the sorted table then reads it directly instead of through the permutation.
 struct SortedKey { int col = -1; BufP data, valid; bool decoded = false; };
 static BufP sort_perm(Exec& x, PTable& t, const Json& sort_exprs, const void* site, int tag, SortedKey* sk = nullptr) {      // (t's count is made exact when the operator cannot run deferred)
-  gpuq_op* op = cached_op(x, site, tag, table_sig(t), [&]() {
-    const auto nm = names_of(t);
-    Json ex = jarr();
-    for (auto& s : sort_exprs.a) {
-      const bool asc = s.get_bool("asc", true);
-      ex.a.push_back(jobj({{"expr", rebind(s.at("expr"), nm)}, {"asc", jbool(asc)}, {"nulls_first", jbool(s.get_bool("nulls_first", !asc))}}));
-    }
-    return jobj({{"op", jstr("sort")}, {"input", jobj({{"fields", table_fields(t)}})}, {"expr", ex}});
-  });
+  gpuq_op* op = cached_op(x, site, tag, table_sig(t), [&]() { return sort_desc(t, sort_exprs); });
   prep(x, op, t);
-  BufP perm = dev_alloc((size_t)std::max<int64_t>(t.n, 1) * 4 + 16);
+  BufP perm = alloc_rows(t.n);
   InputC ic; make_input(t, ic);
   if (sk && sk->col >= 0) {
     const PCol& kc = t.cols[(size_t)sk->col];
     DType dt = dtype_from_json(kc.type);
     const size_t w = (size_t)type_width(dt);
     sk->data = dev_alloc((size_t)std::max<int64_t>(t.n, 1) * w + 16);
-    const bool nullable = kc.nullable || (t.sides[(size_t)sk->col] > 0 && !t.dense);
-    if (nullable) sk->valid = dev_alloc((size_t)((t.n + 63) / 64) * 8 + 8);
+    if (nullable_in(t, (size_t)sk->col)) sk->valid = dev_alloc(bitmap_bytes(t.n));
     int decoded = 0;
     check(x, gpuq_sort_run_keys(op, x.stream, &ic.in, (uint32_t*)perm->p, sk->data->p, sk->valid ? (uint8_t*)sk->valid->p : nullptr, &decoded));
     sk->decoded = decoded != 0;
@@ -724,21 +740,15 @@ static PermOut sort_perm_long(Exec& x, const PTable& t, const Json& sort_exprs, 
   for (auto& s : sort_exprs.a) {
     const int ci = long_key_column(t, s.at("expr"));
     int32_t maxlen = 0;
-    if (ci >= 0) { const int sd = t.sides[(size_t)ci]; check(x, gpuq_utf8_max_len(x.ctx, x.stream, &t.cols[(size_t)ci].c, sd > 0 ? t.via[(size_t)sd - 1] : nullptr, t.n, &maxlen)); }
+    if (ci >= 0) check(x, gpuq_utf8_max_len(x.ctx, x.stream, &t.cols[(size_t)ci].c, via_of(t, (size_t)ci), t.n, &maxlen));
     if (ci < 0 || maxlen <= 15) { cur.a.push_back(s); if (cur.a.size() >= max_group) flush(); continue; }
     flush();
-    const bool asc = s.get_bool("asc", true);
     for (int j = 0; j < (maxlen + 13) / 14; ++j) {
       const std::string name = "__sortpiece_" + std::to_string(np++);
-      const PCol& c = w.cols[(size_t)ci]; const int sd = w.sides[(size_t)ci];
-      const size_t nb = (size_t)((w.n + 63) / 64) * 8 + 8;
-      BufP keys = dev_alloc((size_t)std::max<int64_t>(w.n, 1) * 16 + 16), valid = dev_alloc(nb);
-      HIPCHECK(hipMemsetAsync(valid->p, 0, nb, (hipStream_t)x.stream));
-      check(x, gpuq_utf8_sort_piece(x.ctx, x.stream, &c.c, sd > 0 ? w.via[(size_t)sd - 1] : nullptr, w.n, j, keys->p, (uint8_t*)valid->p));
-      PCol k; k.name = name; k.type = jobj({{"Decimal128", jarr({jnum(38), jnum(0)})}}); k.nullable = true;
-      k.c.type = T_DECIMAL128; k.c.precision = 38; k.c.scale = 0; k.c.repr = GPUQ_REPR_ARROW; k.c.data = keys->p; k.c.validity = (const uint8_t*)valid->p; k.c.length = w.n;
-      w.cols.push_back(k); w.sides.push_back(0); w.keep.push_back(keys); w.keep.push_back(valid); w.record_cap = 0;
-      groups.push_back(jarr({jobj({{"expr", jcol(name, (int)w.cols.size() - 1)}, {"asc", jbool(asc)}, {"nulls_first", jbool(s.get_bool("nulls_first", !asc))}})}));
+      BufP keys = dev_alloc((size_t)std::max<int64_t>(w.n, 1) * 16 + 16), valid = zeroed_bitmap(x, w.n);
+      check(x, gpuq_utf8_sort_piece(x.ctx, x.stream, &w.cols[(size_t)ci].c, via_of(w, (size_t)ci), w.n, j, keys->p, (uint8_t*)valid->p));
+      append_column(w, name, T_DECIMAL128, keys->p, keys, valid, w.n, true, 38, 0);
+      groups.push_back(jarr({sort_key(s, jcol(name, (int)w.cols.size() - 1))}));
     }
   }
   flush();
@@ -762,15 +772,12 @@ PTable sort_table(Exec& x, const PTable& t_in, const Json& sort_exprs, int64_t f
     // one key that is a plain fixed-width column of a materialised table with enough rows for the radix passes: ask for it in order
     SortedKey sk;
     if (sort_exprs.a.size() == 1 && !t.is_view() && t.n >= (1 << 20)) {
-      const Json& e = sort_exprs.a[0].at("expr");
-      if (e.is_obj() && e.o.size() == 1 && e.o[0].first == "column" && e.o[0].second.find("name")) {
-        const std::string& nm = e.o[0].second.at("name").str();
-        for (size_t i = 0; i < t.cols.size(); ++i) if (t.cols[i].name == nm) {
-          const int ty = t.cols[i].c.type;
-          if (ty == T_INT8 || ty == T_INT16 || ty == T_INT32 || ty == T_INT64 || ty == T_UINT8 || ty == T_UINT16 || ty == T_UINT32 || ty == T_DATE32 || ty == T_DATE64 ||
-              ty == T_TIMESTAMP || ty == T_DECIMAL128) sk.col = (int)i;
-          break;
-        }
+      const std::string* nm = bare_column(sort_exprs.a[0].at("expr"));
+      const int i = nm ? find_column(t, *nm) : -1;
+      if (i >= 0) {
+        const int ty = t.cols[(size_t)i].c.type;
+        if (ty == T_INT8 || ty == T_INT16 || ty == T_INT32 || ty == T_INT64 || ty == T_UINT8 || ty == T_UINT16 || ty == T_UINT32 || ty == T_DATE32 || ty == T_DATE64 ||
+            ty == T_TIMESTAMP || ty == T_DECIMAL128) sk.col = i;
       }
     }
     BufP perm = sort_perm(x, t, sort_exprs, site, tag, sk.col >= 0 ? &sk : nullptr);
@@ -803,16 +810,8 @@ PTable concat_tables(Exec& x, std::vector<PTable> parts);
 PTable merge_table(Exec& x, const PTable& t_in, const std::vector<int64_t>& run_offsets, const Json& sort_exprs, int64_t fetch, const void* site, int tag) {
   if (run_offsets.size() <= 2) return sort_table(x, t_in, sort_exprs, fetch, site, tag);
   PTable t = t_in; resolve(x, t);      // one partition (e.g. gathered by BroadcastExec: several runs inside): sort
-  gpuq_op* op = cached_op(x, site, tag, table_sig(t), [&]() {
-    const auto nm = names_of(t);
-    Json ex = jarr();
-    for (auto& s : sort_exprs.a) {
-      const bool asc = s.get_bool("asc", true);
-      ex.a.push_back(jobj({{"expr", rebind(s.at("expr"), nm)}, {"asc", jbool(asc)}, {"nulls_first", jbool(s.get_bool("nulls_first", !asc))}}));
-    }
-    return jobj({{"op", jstr("sort")}, {"input", jobj({{"fields", table_fields(t)}})}, {"expr", ex}});
-  });
-  BufP perm = dev_alloc((size_t)std::max<int64_t>(t.n, 1) * 4 + 16);
+  gpuq_op* op = cached_op(x, site, tag, table_sig(t), [&]() { return sort_desc(t, sort_exprs); });
+  BufP perm = alloc_rows(t.n);
   InputC ic; make_input(t, ic);
   check(x, gpuq_merge_run(op, x.stream, &ic.in, run_offsets.data(), (int)run_offsets.size() - 1, (uint32_t*)perm->p));
   const int64_t k = (fetch < 0 || fetch > t.n) ? t.n : fetch;
@@ -877,6 +876,7 @@ Json schema_fields(const PSchema& s) {
   for (auto& c : s) f.a.push_back(jobj({{"name", jstr(c.name)}, {"type", c.type}, {"nullable", jbool(c.nullable)}, {"side", jnum(0)}}));
   return f;
 }
+Json input_of(const PSchema& s) { return jobj({{"fields", schema_fields(s)}}); }
 std::vector<std::string> schema_names(const PSchema& s) { std::vector<std::string> v; for (auto& c : s) v.push_back(c.name); return v; }
 Json type_json_from_string(const std::string& t) {      // DType::to_string(): "Int64", "Decimal128(15, 2)" ...
   if (t.rfind("Decimal128", 0) == 0) {
@@ -921,9 +921,7 @@ struct ProjectionExec : PNode {
     std::vector<Json> ex = exprs;
     // LikeExpr is lowered to a Boolean column at run time: for typing, a like_expr is Boolean with its operand's nullability
     for (auto& e : ex) e = rewrite_like(e, [&](const Json& v) { return jobj({{"is_not_null_expr", jobj({{"expr", jobj({{"not_expr", jobj({{"expr", jobj({{"is_null_expr", jobj({{"expr", v.at("expr")}})}})}})}})}})}}); });
-    Json exj = jarr();
-    for (size_t i = 0; i < ex.size(); ++i) exj.a.push_back(jobj({{"expr", rebind(ex[i], nm)}, {"name", jstr(names[i])}}));
-    PSchema out = compiled_outputs(jobj({{"op", jstr("project")}, {"input", jobj({{"fields", schema_fields(in)}})}, {"exprs", exj}}));
+    PSchema out = compiled_outputs(project_desc(input_of(in), ex, names, &nm));
     for (size_t i = 0; i < exprs.size() && i < out.size(); ++i) if (has_like(exprs[i])) out[i].nullable = true;
     return out;
   }
@@ -979,11 +977,8 @@ PTable ProjectionExec::execute(int part, Exec& x) {
   // (the project kernel writes Utf8 results as 16-byte PACKED15 values)
   std::vector<int> pick;
   for (auto& e : ex) {
-    int ci = -1;
-    if (e.is_obj() && e.o.size() == 1 && e.o[0].first == "column" && e.o[0].second.is_obj() && e.o[0].second.find("name")) {
-      const std::string& n = e.o[0].second.at("name").str();
-      for (size_t i = 0; i < t.cols.size(); ++i) if (t.cols[i].name == n) { ci = (int)i; break; }
-    }
+    const std::string* n = bare_column(e);
+    const int ci = n ? find_column(t, *n) : -1;
     if (ci < 0) { pick.clear(); break; }
     pick.push_back(ci);
   }
@@ -995,9 +990,17 @@ PTable ProjectionExec::execute(int part, Exec& x) {
   return timed(x, t0, project(x, t, ex, names, this, 1));
 }
 
-bool is_bare_column(const Json& e, std::string& name) {
-  if (!(e.is_obj() && e.o.size() == 1 && e.o[0].first == "column" && e.o[0].second.is_obj() && e.o[0].second.find("name"))) return false;
-  name = e.o[0].second.at("name").str(); return true;
+// the arguments an aggregate expression `a` may carry, in descriptor order
+template <class F> void for_each_agg_arg(const Json& a, F&& f) { for (const char* k : {"expr", "expr2", "filter"}) if (a.has(k)) f(k, a.at(k)); }
+// aggr_expr as the operator takes it: every argument inlined through the projection below (cm, or nullptr) and bound to the input's columns
+Json bound_aggr_exprs(const Json& aggr_expr, const ColMap* cm, const std::vector<std::string>& nm) {
+  Json ae = jarr();
+  for (auto& a : aggr_expr.a) {
+    std::vector<std::pair<std::string, Json>> o = {{"fn", a.at("fn")}, {"name", a.at("name")}};
+    for_each_agg_arg(a, [&](const char* k, const Json& e) { o.push_back({k, rebind(inline_projection(e, cm), nm)}); });
+    ae.a.push_back(jobj(o));
+  }
+  return ae;
 }
 struct AggregateExec : PNode {
   PNodeP input; std::string mode, strategy = "auto"; Json group_expr, aggr_expr; int64_t expected_groups = 0, output_capacity = 0;
@@ -1006,20 +1009,15 @@ struct AggregateExec : PNode {
     if (mode == "Final" || mode == "FinalPartitioned") { input->require(nullptr); return; }      // reads its input's state columns by position
     Names n;
     for (auto& g : group_expr.a) collect_columns(g.at("expr"), n);
-    for (auto& a : aggr_expr.a) for (const char* k : {"expr", "expr2", "filter"}) if (a.has(k)) collect_columns(a.at(k), n);
+    for (auto& a : aggr_expr.a) for_each_agg_arg(a, [&](const char*, const Json& e) { collect_columns(e, n); });
     input->require(&n);
   }
   PSchema schema() override {
     const PSchema in = input->schema(); const auto nm = schema_names(in);
-    Json ge = jarr(), ae = jarr();
+    Json ge = jarr();
     for (auto& g : group_expr.a) ge.a.push_back(jobj({{"expr", rebind(g.at("expr"), nm)}, {"name", g.at("name")}}));
-    for (auto& a : aggr_expr.a) {
-      std::vector<std::pair<std::string, Json>> o = {{"fn", a.at("fn")}, {"name", a.at("name")}};
-      for (const char* k : {"expr", "expr2", "filter"}) if (a.has(k)) o.push_back({k, rebind(a.at(k), nm)});
-      ae.a.push_back(jobj(o));
-    }
-    PSchema out = compiled_outputs(jobj({{"op", jstr("aggregate")}, {"mode", jstr(mode)}, {"input", jobj({{"fields", schema_fields(in)}})}, {"strategy", jstr("hash")},
-                                         {"group_expr", ge}, {"aggr_expr", ae}}));
+    PSchema out = compiled_outputs(jobj({{"op", jstr("aggregate")}, {"mode", jstr(mode)}, {"input", input_of(in)}, {"strategy", jstr("hash")},
+                                         {"group_expr", ge}, {"aggr_expr", bound_aggr_exprs(aggr_expr, nullptr, nm)}}));
     // DataFusion declares every aggregate but COUNT nullable (an empty group has no SUM / MIN / MAX / AVG) [UPSTREAM-KNOWLEDGE:
     // Sum::field etc.]; the operator may type a column tighter when its inputs cannot be NULL -- announce the declared form
     // (COUNT too: the merged count of a two-phase aggregate comes back through a nullable state column here; announcing
@@ -1063,37 +1061,36 @@ struct AggregateExec : PNode {
   const BuildRows* build_row_grouping(const PTable& t, const ColMap* cm, std::vector<Json>& over_build) const {
     const BuildRows* br = t.by_build.get();
     if (!br || mode != "Single" || group_expr.a.empty() || t.cols.size() != br->n_cols || br->build.cols.size() != br->n_build_cols) return nullptr;
-    auto first_named = [](const PTable& tt, const std::string& n) { for (size_t i = 0; i < tt.cols.size(); ++i) if (tt.cols[i].name == n) return (int)i; return -1; };
     const size_t nkeys = br->build_keys.size();
     std::vector<bool> got_build(nkeys, false), got_probe(nkeys, false);
     for (auto& g : group_expr.a) {
       const Json e = inline_projection(g.at("expr"), cm);
-      std::string bare; const bool is_bare = is_bare_column(e, bare);
-      if (is_bare) {
-        const int ci = first_named(t, bare);
+      if (const std::string* bare_p = bare_column(e)) {
+        const std::string& bare = *bare_p;
+        const int ci = find_column(t, bare);
         if (ci < 0) return nullptr;
         if ((size_t)ci >= br->n_build_cols) {
           // a probe-side column: only a join key, served by its build-side partner -- when that has exactly its type
           size_t k = 0; while (k < nkeys && br->probe_keys[k] != bare) ++k;
           if (k == nkeys) return nullptr;
-          const int bi = first_named(br->build, br->build_keys[k]);
-          if (bi < 0 || first_named(t, br->build_keys[k]) != bi || br->build.cols[(size_t)bi].type.dump() != t.cols[(size_t)ci].type.dump()) return nullptr;
+          const int bi = find_column(br->build, br->build_keys[k]);
+          if (bi < 0 || find_column(t, br->build_keys[k]) != bi || br->build.cols[(size_t)bi].type.dump() != t.cols[(size_t)ci].type.dump()) return nullptr;
           // integer-like and date keys only: equal means identical there (a float key's 0.0 would stand in for a probe row's -0.0)
           switch (t.cols[(size_t)ci].c.type) {
             case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: case T_DATE32: case T_DATE64: case T_TIMESTAMP: break;
             default: return nullptr;
           }
           got_probe[k] = true;
-          over_build.push_back(jobj({{"column", jobj({{"name", jstr(br->build_keys[k])}})}}));
+          over_build.push_back(jcolname(br->build_keys[k]));
           continue;
         }
         for (size_t k = 0; k < nkeys; ++k) if (br->build_keys[k] == bare) got_build[k] = true;
       }
       std::set<std::string> used; collect_columns(e, used);
       for (auto& n : used) {
-        const int ci = first_named(t, n);
+        const int ci = find_column(t, n);
         // (strings stay with the declared keys: a value beyond 15 bytes takes the dictionary-code path there)
-        if (ci < 0 || (size_t)ci >= br->n_build_cols || first_named(br->build, n) != ci || t.cols[(size_t)ci].c.type == T_UTF8) return nullptr;
+        if (ci < 0 || (size_t)ci >= br->n_build_cols || find_column(br->build, n) != ci || t.cols[(size_t)ci].c.type == T_UTF8) return nullptr;
       }
       over_build.push_back(e);
     }
@@ -1117,17 +1114,13 @@ struct AggregateExec : PNode {
     std::vector<Json> over_build;
     const BuildRows* br = long_keys ? nullptr : build_row_grouping(t, cm0, over_build);
     const std::shared_ptr<const BuildRows> br_keep = br ? t.by_build : nullptr;
-    if (br) {
-      PCol c; c.name = "__build_row"; c.type = jstr("UInt32"); c.nullable = false;
-      c.c.type = T_UINT32; c.c.repr = GPUQ_REPR_ARROW; c.c.data = br->rows; c.c.length = t.n;
-      t.cols.push_back(c); t.sides.push_back(0); t.keep.push_back(br->rows_keep); t.record_cap = 0; t.by_build = nullptr;
-    }
+    if (br) { append_column(t, "__build_row", T_UINT32, br->rows, br->rows_keep, nullptr, t.n, false); t.by_build = nullptr; }
     // group expressions over the source table; with long_keys every plain Arrow-layout Utf8 key column is replaced by its codes
     std::vector<Json> gexprs; std::vector<int> coded;      // coded[k] = column of `t` key k's strings come from, or -1
     Utf8DictGuard dicts[8]; int nd = 0;
     const PTable t_src = t;
     std::vector<std::string> gnames;
-    if (br) { gexprs.push_back(jobj({{"column", jobj({{"name", jstr("__build_row")}})}})); coded.push_back(-1); gnames.push_back("__build_row"); }
+    if (br) { gexprs.push_back(jcolname("__build_row")); coded.push_back(-1); gnames.push_back("__build_row"); }
     else for (auto& g : group_expr.a) {
       gnames.push_back(g.at("name").str());
       Json e = inline_projection(g.at("expr"), cm0); int ci = -1;
@@ -1135,7 +1128,7 @@ struct AggregateExec : PNode {
         const std::string nm = "__code_" + std::to_string(gexprs.size());
         check(x, gpuq_utf8_dict_create(x.ctx, x.stream, std::min<int64_t>(t_src.n, t_src.cols[(size_t)ci].c.length), &dicts[nd].d));
         append_code_column(x, t, ci, dicts[nd].d, true, nm); ++nd;
-        e = jobj({{"column", jobj({{"name", jstr(nm)}})}});
+        e = jcolname(nm);
         // a code is a row id: as UInt32 it takes 35 bits of a packed key instead of 66 (more group columns than key slots, compile_aggregate)
         if (group_expr.a.size() > 4) e = jobj({{"cast", jobj({{"expr", e}, {"arrow_type", jstr("UInt32")}})}});
       } else ci = -1;
@@ -1144,15 +1137,10 @@ struct AggregateExec : PNode {
     gpuq_op* op = cached_op(x, this, long_keys ? 6 : (br ? 10 : 0), table_sig(t), [&]() {
     const auto nm = names_of(t);
     const ColMap* cm = f.has_map ? &f.map : nullptr;
-    Json ge = jarr(), ae = jarr();
+    Json ge = jarr();
     for (size_t k = 0; k < gexprs.size(); ++k) ge.a.push_back(jobj({{"expr", rebind(gexprs[k], nm)}, {"name", jstr(gnames[k])}}));
-    for (auto& a : aggr_expr.a) {
-      std::vector<std::pair<std::string, Json>> o = {{"fn", a.at("fn")}, {"name", a.at("name")}};
-      for (const char* k : {"expr", "expr2", "filter"}) if (a.has(k)) o.push_back({k, rebind(inline_projection(a.at(k), cm), nm)});
-      ae.a.push_back(jobj(o));
-    }
-    std::vector<std::pair<std::string, Json>> d = {{"op", jstr("aggregate")}, {"mode", jstr(mode)}, {"input", jobj({{"fields", table_fields(t)}})},
-                                                   {"strategy", jstr(strategy)}, {"group_expr", ge}, {"aggr_expr", ae}};
+    std::vector<std::pair<std::string, Json>> d = {{"op", jstr("aggregate")}, {"mode", jstr(mode)}, {"input", input_of(t)},
+                                                   {"strategy", jstr(strategy)}, {"group_expr", ge}, {"aggr_expr", bound_aggr_exprs(aggr_expr, cm, nm)}};
     if (f.has_pred) d.push_back({"predicate", rebind(f.pred, nm)});
     if (expected_groups) d.push_back({"expected_groups", jnum(expected_groups)});
     if (br) d.push_back({"group_by", jstr("build_row")});      // (read by nobody but whoever looks at the plan's profile)
@@ -1191,7 +1179,7 @@ struct AggregateExec : PNode {
       // coded keys: the code IS the row of a representative string in the source column -- take the strings back
       for (size_t k = 0; k < coded.size(); ++k) {
         if (coded[k] < 0) continue;
-        BufP rows = dev_alloc((size_t)std::max<int64_t>(ng, 1) * 4 + 16);
+        BufP rows = alloc_rows(ng);
         check(x, gpuq_utf8_code_rows(x.ctx, x.stream, &out.cols[k].c, ng, (uint32_t*)rows->p));
         const PCol& src = t_src.cols[(size_t)coded[k]];
         PCol sc = take_utf8(x, src, (const uint32_t*)rows->p, ng, true, out.keep);
@@ -1277,9 +1265,9 @@ struct HashJoinExec : PNode {
   void mark_build_rows(PTable& out, const PTable& lt, const uint32_t* ob, const BufP& ob_own) const {
     auto m = std::make_shared<BuildRows>();
     for (auto& o : on.a) {
-      std::string l, r;
-      if (!is_plain_column(o.at("left"), l) || !is_plain_column(o.at("right"), r)) return;
-      m->build_keys.push_back(l); m->probe_keys.push_back(r);
+      const std::string* l = bare_column(o.at("left")); const std::string* r = bare_column(o.at("right"));
+      if (!l || !r) return;
+      m->build_keys.push_back(*l); m->probe_keys.push_back(*r);
     }
     m->rows = ob; m->rows_keep = ob_own; m->build = lt; m->build.by_build = nullptr;
     m->n_build_cols = lt.cols.size(); m->n_cols = out.cols.size();
@@ -1287,13 +1275,10 @@ struct HashJoinExec : PNode {
   }
   // positions of [0, n) that occur (want_marked) / do not occur in rows[0..k)
   int64_t marked_rows(Exec& x, const uint32_t* rows, int64_t k, int64_t n, bool want_marked, int tag, BufP& out) {
-    const size_t nb = (size_t)((n + 63) / 64) * 8 + 8;
-    BufP bits = dev_alloc(nb);
-    HIPCHECK(hipMemsetAsync(bits->p, 0, nb, (hipStream_t)x.stream));
+    BufP bits = zeroed_bitmap(x, n);
     check(x, gpuq_mark_rows(x.ctx, x.stream, rows, k, (uint8_t*)bits->p));
-    PTable t; t.n = n; t.keep.push_back(bits);
-    PCol c; c.name = "m"; c.type = jstr("Boolean"); c.nullable = false; c.c.type = T_BOOL; c.c.repr = GPUQ_REPR_ARROW; c.c.data = bits->p; c.c.length = n;
-    t.cols.push_back(c); t.sides.push_back(0);
+    PTable t; t.n = n;
+    append_column(t, "m", T_BOOL, bits->p, bits, nullptr, n, false);
     const Json m = jcol("m", 0);
     return filter_sel(x, t, want_marked ? m : jobj({{"not_expr", jobj({{"expr", m}})}}), this, tag, out);
   }
@@ -1312,7 +1297,7 @@ struct HashJoinExec : PNode {
     if (jt == "Left" || jt == "Full") ml = marked_rows(x, ob2, k2, lt.n, false, 5, lrows);
     if (jt == "Right" || jt == "Full") mr = marked_rows(x, opb2, k2, rt.n, false, 6, rrows);
     const int64_t k3 = k2 + ml + mr;
-    BufP ob3 = dev_alloc((size_t)std::max<int64_t>(k3, 1) * 4 + 16), opb3 = dev_alloc((size_t)std::max<int64_t>(k3, 1) * 4 + 16);
+    BufP ob3 = alloc_rows(k3), opb3 = alloc_rows(k3);
     uint32_t* a = (uint32_t*)ob3->p; uint32_t* b = (uint32_t*)opb3->p;
     if (k2) { HIPCHECK(hipMemcpyAsync(a, ob2, (size_t)k2 * 4, hipMemcpyDeviceToDevice, s)); HIPCHECK(hipMemcpyAsync(b, opb2, (size_t)k2 * 4, hipMemcpyDeviceToDevice, s)); }
     if (ml) { HIPCHECK(hipMemcpyAsync(a + k2, lrows->p, (size_t)ml * 4, hipMemcpyDeviceToDevice, s)); HIPCHECK(hipMemsetAsync(b + k2, 0xFF, (size_t)ml * 4, s)); }
@@ -1333,7 +1318,7 @@ struct HashJoinExec : PNode {
       auto t0 = std::chrono::steady_clock::now();
       Chain ch;
       if (chain_build(x, inner, Li, Ri, ch)) {
-        struct Guard { gpuq_join_table* t; ~Guard() { if (t) gpuq_join_table_free(t); } } guard{ch.table};
+        JoinTableGuard guard{ch.table};
         Side Lv; Lv.t = ch.view;
         return timed(x, t0, join_sides(x, Lv, R, false, &ch));
       }
@@ -1375,9 +1360,25 @@ struct HashJoinExec : PNode {
   // their key in A's table ARE this join's build side, so the build kernel looks them up on the way: one pass over B instead of
   // probe + pair emit + compaction + a build through an index vector (SF100 q3: the orders side 0.83 + 0.08 + 0.71 ms -> one kernel).
   struct Chain { gpuq_join_table* table = nullptr; PTable view; bool deferred = false; };
-  static bool is_plain_column(const Json& e, std::string& name) {
-    if (!(e.is_obj() && e.o.size() == 1 && e.o[0].first == "column" && e.o[0].second.is_obj() && e.o[0].second.find("name"))) return false;
-    name = e.o[0].second.at("name").str(); return true;
+  // the keys of one side ("left" / "right") of an ON list, bound to that side's columns
+  static Json join_keys(const Json& on_list, const char* side, const std::vector<std::string>& names) {
+    Json k = jarr(); for (auto& o : on_list.a) k.a.push_back(rebind(o.at(side), names)); return k;
+  }
+  // semi_on: the chain-fused build also looks its rows up in another table, under the "right" keys of that ON list
+  static Json join_build_desc(const Side& s, const Json& on_list, const Json* semi_on, bool nulls_equal, bool side_rows, const std::string& label) {
+    const auto nm = names_of(s.t);
+    std::vector<std::pair<std::string, Json>> bd = {{"op", jstr("join_build")}, {"input", input_of(s.t)}, {"on", join_keys(on_list, "left", nm)}};
+    if (semi_on) bd.push_back({"semi_on", join_keys(*semi_on, "right", nm)});
+    bd.insert(bd.end(), {{"null_equals_null", jbool(nulls_equal)}, {"build_side_rows", jbool(side_rows)}, {"label", jstr(label)}});
+    if (s.has_pred) bd.push_back({"predicate", rebind(s.pred, nm)});
+    return jobj(bd);
+  }
+  static Json join_probe_desc(const Side& s, const Json& on_list, const std::string& jt, bool nulls_equal, const std::string& label) {
+    const auto nm = names_of(s.t);
+    std::vector<std::pair<std::string, Json>> pd = {{"op", jstr("join_probe")}, {"input", input_of(s.t)}, {"on", join_keys(on_list, "right", nm)}, {"join_type", jstr(jt)},
+                                                   {"null_equals_null", jbool(nulls_equal)}, {"label", jstr(label)}};
+    if (s.has_pred) pd.push_back({"predicate", rebind(s.pred, nm)});
+    return jobj(pd);
   }
   int chain_checked = 0;      // 0 not looked at yet, 1 candidate, -1 no
   HashJoinExec* chain_inner() {
@@ -1396,9 +1397,9 @@ struct HashJoinExec : PNode {
     for (auto& f : in->left->schema()) ln.push_back(f.name);
     for (auto& f : in->right->schema()) rn.push_back(f.name);
     for (auto& o : on.a) {
-      std::string nm;
-      if (!is_plain_column(o.at("left"), nm)) return nullptr;
-      if (std::count(rn.begin(), rn.end(), nm) != 1 || std::count(ln.begin(), ln.end(), nm) != 0) return nullptr;
+      const std::string* nm = bare_column(o.at("left"));
+      if (!nm) return nullptr;
+      if (std::count(rn.begin(), rn.end(), *nm) != 1 || std::count(ln.begin(), ln.end(), *nm) != 0) return nullptr;
     }
     chain_checked = 1;
     return in;
@@ -1418,39 +1419,23 @@ struct HashJoinExec : PNode {
       Li.t = materialize(x, Li.t);
     }
     // 1. A's table, exactly as the inner join would build it
-    gpuq_op* bop1 = cached_op(x, in, 0, table_sig(Li.t), [&]() {
-      const auto ln = names_of(Li.t);
-      Json lk = jarr(); for (auto& o : in->on.a) lk.a.push_back(rebind(o.at("left"), ln));
-      std::vector<std::pair<std::string, Json>> bd = {{"op", jstr("join_build")}, {"input", jobj({{"fields", table_fields(Li.t)}})}, {"on", lk}, {"null_equals_null", jbool(false)},
-                                                     {"build_side_rows", jbool(false)}, {"label", jstr(in->label("build"))}};
-      if (Li.has_pred) bd.push_back({"predicate", rebind(Li.pred, ln)});
-      return jobj(bd);
-    });
+    gpuq_op* bop1 = cached_op(x, in, 0, table_sig(Li.t), [&]() { return join_build_desc(Li, in->on, nullptr, false, false, in->label("build")); });
     // 2. this join's table from B's rows that are in A's table
-    gpuq_op* bop2 = cached_op(x, this, 12, table_sig(Ri.t), [&]() {
-      const auto rn = names_of(Ri.t);
-      Json lk = jarr(), sk = jarr();
-      for (auto& o : on.a) lk.a.push_back(rebind(o.at("left"), rn));
-      for (auto& o : in->on.a) sk.a.push_back(rebind(o.at("right"), rn));
-      std::vector<std::pair<std::string, Json>> bd = {{"op", jstr("join_build")}, {"input", jobj({{"fields", table_fields(Ri.t)}})}, {"on", lk}, {"semi_on", sk},
-                                                     {"null_equals_null", jbool(false)}, {"build_side_rows", jbool(false)}, {"label", jstr(label("chain_build"))}};
-      if (Ri.has_pred) bd.push_back({"predicate", rebind(Ri.pred, rn)});
-      return jobj(bd);
-    });
+    gpuq_op* bop2 = cached_op(x, this, 12, table_sig(Ri.t), [&]() { return join_build_desc(Ri, on, &in->on, false, false, label("chain_build")); });
     bool deferred = x.deferred && last_pairs >= 0 && gpuq_op_can_defer(bop1) && gpuq_op_can_defer(bop2);
     if (deferred) deferred = use_deferred(x, bop1) && use_deferred(x, bop2);
     if (!deferred) { use_sync(x, bop1); use_sync(x, bop2); resolve(x, Li.t); resolve(x, Ri.t); }
     InputC lic, ric; make_input(Li.t, lic); make_input(Ri.t, ric);
     gpuq_join_table* t1 = nullptr;
     check(x, gpuq_join_build_run(bop1, x.stream, &lic.in, 0, Li.t.n, &t1));
-    struct Guard { gpuq_join_table* t; ~Guard() { if (t) gpuq_join_table_free(t); } } g1{t1};
+    JoinTableGuard g1{t1};
     if (!deferred) x.host_syncs += 2;
     if (gpuq_join_table_has_duplicates(t1)) return false;
     // A's row of every surviving position of B (A's columns are read through it) -- not formed at all when nothing above the inner
     // join reads a column of A (its keys have done their work in A's table): two scattered accesses per surviving row less
     bool want_hits = in->out_need_all;
     for (auto& c : Li.t.cols) want_hits = want_hits || in->out_need.count(c.name) > 0;
-    BufP hits = want_hits ? dev_alloc((size_t)std::max<int64_t>(Ri.t.n, 1) * 4 + 16) : nullptr, rows = dev_alloc(16);
+    BufP hits = want_hits ? alloc_rows(Ri.t.n) : nullptr, rows = dev_alloc(16);
     gpuq_join_table* t2 = nullptr;
     check(x, gpuq_join_build_run_semi(bop2, x.stream, &ric.in, 0, Ri.t.n, t1, want_hits ? (uint32_t*)hits->p : nullptr, (uint64_t*)rows->p, &t2));
     ch.table = t2; ch.deferred = deferred;
@@ -1500,29 +1485,15 @@ struct HashJoinExec : PNode {
         append_code_column(x, L.t, li, dicts[nd].d, true, nm + "l");
         append_code_column(x, R.t, ri, dicts[nd].d, false, nm + "r");
         ++nd;
-        on_eff.a[k] = jobj({{"left", jobj({{"column", jobj({{"name", jstr(nm + "l")}})}})}, {"right", jobj({{"column", jobj({{"name", jstr(nm + "r")}})}})}});
+        on_eff.a[k] = jobj({{"left", jcolname(nm + "l")}, {"right", jcolname(nm + "r")}});
       }
     }
     gpuq_op* bop = chain ? nullptr : cached_op(x, this, long_keys ? 7 : 0, table_sig(L.t), [&]() {
-      const auto ln = names_of(L.t);
-      Json lk = jarr();
-      for (auto& o : on_eff.a) lk.a.push_back(rebind(o.at("left"), ln));
       // only Left / Full / LeftSemi / LeftAnti ask the table for its build side's rows afterwards
       const bool side_rows = jt == "Left" || jt == "Full" || jt == "LeftSemi" || jt == "LeftAnti";
-      std::vector<std::pair<std::string, Json>> bd = {{"op", jstr("join_build")}, {"input", jobj({{"fields", table_fields(L.t)}})}, {"on", lk}, {"null_equals_null", jbool(null_equals_null)},
-                                                     {"build_side_rows", jbool(side_rows)}, {"label", jstr(label("build"))}};
-      if (L.has_pred) bd.push_back({"predicate", rebind(L.pred, ln)});
-      return jobj(bd);
+      return join_build_desc(L, on_eff, nullptr, null_equals_null, side_rows, label("build"));
     });
-    gpuq_op* pop = cached_op(x, this, long_keys ? 8 : 1, table_sig(R.t), [&]() {
-      const auto rn = names_of(R.t);
-      Json rk = jarr();
-      for (auto& o : on_eff.a) rk.a.push_back(rebind(o.at("right"), rn));
-      std::vector<std::pair<std::string, Json>> pd = {{"op", jstr("join_probe")}, {"input", jobj({{"fields", table_fields(R.t)}})}, {"on", rk}, {"join_type", jstr(jt)},
-                                                     {"null_equals_null", jbool(null_equals_null)}, {"label", jstr(label("probe"))}};
-      if (R.has_pred) pd.push_back({"predicate", rebind(R.pred, rn)});
-      return jobj(pd);
-    });
+    gpuq_op* pop = cached_op(x, this, long_keys ? 8 : 1, table_sig(R.t), [&]() { return join_probe_desc(R, on_eff, jt, null_equals_null, label("probe")); });
     // Deferred (a plan's second run on): the build keeps the table layout it remembers, the probe's pair count stays on the device and
     // sizes nothing on the host -- the pair vectors are as long as the count this call site produced last time allows (+ 1/8), an
     // overflow raises the probe's status word.  Only the join types whose output is the pair list itself run this way.
@@ -1538,7 +1509,7 @@ struct HashJoinExec : PNode {
       check(x, gpuq_join_build_run(bop, x.stream, &lic.in, 0, L.t.n, &jtab));
       if (!deferred) x.host_syncs += 2;
     }
-    struct Guard { gpuq_join_table* t; ~Guard() { if (t) gpuq_join_table_free(t); } } guard{chain ? nullptr : jtab};
+    JoinTableGuard guard{chain ? nullptr : jtab};
     const bool lout = jt == "Left" || jt == "Full";
     const int64_t extra_cap = lout ? L.t.n : 0;
     int64_t cap = std::max<int64_t>(R.t.n, 1) + extra_cap;
@@ -1547,7 +1518,7 @@ struct HashJoinExec : PNode {
       // (unique build keys: no more pairs than probe rows; duplicate keys can multiply them)
       cap = gpuq_join_table_has_duplicates(jtab) ? last_pairs + last_pairs / 8 + 4096 : std::min<int64_t>(cap, last_pairs + last_pairs / 8 + 4096);
       { static const bool trace = getenv("GPUQ_TRACE_DEFER") != nullptr; if (trace) fprintf(stderr, "[gpuq] deferred %s join: build bound %lld, probe bound %lld, pair capacity %lld (last run %lld pairs), dups %d\n", jt.c_str(), (long long)L.t.n, (long long)R.t.n, (long long)cap, (long long)last_pairs, gpuq_join_table_has_duplicates(jtab)); }
-      ob = dev_alloc((size_t)cap * 4 + 16); opb = dev_alloc((size_t)cap * 4 + 16);
+      ob = alloc_rows(cap); opb = alloc_rows(cap);
       const bool pairs = jt == "Inner" || jt == "Right";
       check(x, gpuq_join_probe_run(pop, x.stream, jtab, &ric.in, 0, pairs ? (uint32_t*)ob->p : nullptr, (uint32_t*)opb->p, (uint64_t)cap, (uint64_t*)cnt->p));
       PTable c; c.n_dev = (const uint64_t*)cnt->p; c.n_keep = cnt;
@@ -1560,7 +1531,7 @@ struct HashJoinExec : PNode {
       return out;
     }
     for (;;) {
-      ob = dev_alloc((size_t)cap * 4 + 16); opb = dev_alloc((size_t)cap * 4 + 16);
+      ob = alloc_rows(cap); opb = alloc_rows(cap);
       check(x, gpuq_join_probe_run(pop, x.stream, jtab, &ric.in, 0, (uint32_t*)ob->p, (uint32_t*)opb->p, (uint64_t)(cap - extra_cap), (uint64_t*)cnt->p));
       k = (int64_t)read_u64(x, cnt->p);
       const int rc = gpuq_op_check(pop, x.stream);
@@ -1573,7 +1544,7 @@ struct HashJoinExec : PNode {
     if (jt == "LeftSemi" || jt == "LeftAnti" || lout) {
       BufP extra = dev_alloc(16);
       if (!lout) {
-        BufP rows = dev_alloc((size_t)std::max<int64_t>(L.t.n, 1) * 4 + 16);
+        BufP rows = alloc_rows(L.t.n);
         check(x, gpuq_join_build_side_rows(jtab, x.stream, jt == "LeftSemi" ? 1 : 0, (uint32_t*)rows->p, (uint64_t*)extra->p));
         const int64_t mrows = (int64_t)read_u64(x, extra->p);
         return select_view(x, L.t, (const uint32_t*)rows->p, mrows, rows);
@@ -1619,16 +1590,15 @@ PTable concat_tables(Exec& x, std::vector<PTable> parts) {
   for (auto& p : live) p = materialize(x, p);        // views -> plain columns; Arrow-layout strings stay as they are
   int64_t n = 0; for (auto& p : live) n += p.n;
   const size_t nc = live[0].cols.size();
-  const size_t bm = (size_t)((n + 63) / 64) * 8 + 8;
+  const size_t bm = bitmap_bytes(n);
   std::vector<size_t> doff(nc), voff(nc, 0), dbytes(nc);
   size_t off = 256;
   for (size_t i = 0; i < nc; ++i) {
     const PCol& c0 = live[0].cols[i];
     for (auto& p : live) if (p.cols[i].c.type != c0.c.type || p.cols[i].c.repr != c0.c.repr) throw std::runtime_error("concat: column '" + c0.name + "' has different layouts across partitions");
-    DType dt; dt.id = c0.c.type; dt.p = c0.c.precision; dt.s = c0.c.scale;
     for (auto& p : live) if ((p.cols[i].c.offsets != nullptr) != (c0.c.offsets != nullptr)) throw std::runtime_error("concat: column '" + c0.name + "' has different layouts across partitions");
     if (c0.c.offsets) dbytes[i] = (size_t)(n + 4) * 4;          // Arrow-layout Utf8: this slot holds the joined offsets, the bytes get their own buffer
-    else dbytes[i] = c0.c.type == T_BOOL ? bm : (size_t)std::max<int64_t>(n, 1) * (size_t)type_width(dt) + 16;
+    else dbytes[i] = c0.c.type == T_BOOL ? bm : (size_t)std::max<int64_t>(n, 1) * width_of(c0.c) + 16;
     doff[i] = off; off += (dbytes[i] + 255) & ~(size_t)255;
     bool any_valid = false; for (auto& p : live) any_valid = any_valid || p.cols[i].c.validity != nullptr;
     if (any_valid) { voff[i] = off; off += (bm + 255) & ~(size_t)255; }
@@ -1638,7 +1608,6 @@ PTable concat_tables(Exec& x, std::vector<PTable> parts) {
   PTable out; out.n = n; out.keep.push_back(buf); out.record_cap = std::max<int64_t>(n, 1);
   for (size_t i = 0; i < nc; ++i) {
     PCol c = live[0].cols[i];
-    DType dt; dt.id = c.c.type; dt.p = c.c.precision; dt.s = c.c.scale;
     char* d = (char*)buf->p + doff[i];
     uint8_t* v = voff[i] ? (uint8_t*)buf->p + voff[i] : nullptr;
     if (c.c.type == T_BOOL) HIPCHECK(hipMemsetAsync(d, 0, bm, s));
@@ -1675,7 +1644,7 @@ PTable concat_tables(Exec& x, std::vector<PTable> parts) {
       nullable = nullable || pc.nullable;
       if (p.n > 0) {
         if (c.c.type == T_BOOL) check(x, gpuq_copy_bits(x.ctx, x.stream, (uint8_t*)d, row, (const uint8_t*)pc.c.data, 0, p.n));
-        else { const size_t w = (size_t)type_width(dt); HIPCHECK(hipMemcpyAsync(d + (size_t)row * w, pc.c.data, (size_t)p.n * w, hipMemcpyDeviceToDevice, s)); }
+        else { const size_t w = width_of(c.c); HIPCHECK(hipMemcpyAsync(d + (size_t)row * w, pc.c.data, (size_t)p.n * w, hipMemcpyDeviceToDevice, s)); }
         if (v) check(x, gpuq_copy_bits(x.ctx, x.stream, v, row, pc.c.validity, 0, p.n));      // NULL source = all valid
       }
       row += p.n;
@@ -1697,17 +1666,14 @@ PTable slice_table(Exec& x, PTable t, int64_t skip, int64_t count) {
   bool has0 = false; if (t.is_view()) for (int sd : t.sides) has0 = has0 || sd == 0;
   if (t.is_view() && !has0) { for (auto& v : t.via) v += skip; t.n = count; return t; }      // every column goes through an index vector
   t = materialize(x, t, true);
-  hipStream_t s = (hipStream_t)x.stream;
-  const size_t bm = (size_t)((count + 63) / 64) * 8 + 8;
   for (auto& c : t.cols) {
-    DType dt; dt.id = c.c.type; dt.p = c.c.precision; dt.s = c.c.scale;
     if (c.c.type == T_BOOL) {
-      BufP b = dev_alloc(bm); HIPCHECK(hipMemsetAsync(b->p, 0, bm, s));
+      BufP b = zeroed_bitmap(x, count);
       check(x, gpuq_copy_bits(x.ctx, x.stream, (uint8_t*)b->p, 0, (const uint8_t*)c.c.data, skip, count));
       c.c.data = b->p; t.keep.push_back(b);
-    } else c.c.data = (const char*)c.c.data + (size_t)skip * (size_t)type_width(dt);
+    } else c.c.data = (const char*)c.c.data + (size_t)skip * width_of(c.c);
     if (c.c.validity) {
-      BufP b = dev_alloc(bm); HIPCHECK(hipMemsetAsync(b->p, 0, bm, s));
+      BufP b = zeroed_bitmap(x, count);
       check(x, gpuq_copy_bits(x.ctx, x.stream, (uint8_t*)b->p, 0, c.c.validity, skip, count));
       c.c.validity = (const uint8_t*)b->p; t.keep.push_back(b);
     }
@@ -1729,7 +1695,7 @@ struct CrossJoinExec : HashJoinExec {
     PTable rt = right->execute(part, x); resolve(x, rt);
     auto t0 = std::chrono::steady_clock::now();
     const int64_t k = lt.n * rt.n;
-    BufP ob = dev_alloc((size_t)std::max<int64_t>(k, 1) * 4 + 16), opb = dev_alloc((size_t)std::max<int64_t>(k, 1) * 4 + 16);
+    BufP ob = alloc_rows(k), opb = alloc_rows(k);
     check(x, gpuq_cross_pairs(x.ctx, x.stream, lt.n, rt.n, (uint32_t*)ob->p, (uint32_t*)opb->p));
     return timed(x, t0, join_view(x, lt, rt, (const uint32_t*)ob->p, (const uint32_t*)opb->p, k, ob, opb));
   }
@@ -1827,15 +1793,27 @@ PTable arrow_layout(Exec& x, const PTable& in_) {
   PTable in = in_; resolve(x, in);
   PTable t = materialize(x, in);
   for (auto& c : t.cols) {
-    if (c.c.repr != GPUQ_REPR_PACKED15) continue;
-    const int64_t n = t.n;
-    BufP offs = dev_alloc((size_t)(n + 4) * 4), data = dev_alloc((size_t)n * 15 + 16);
-    int64_t dl = 0;
-    check(x, gpuq_unpack_utf8(x.ctx, x.stream, c.c.data, n, (int32_t*)offs->p, (uint8_t*)data->p, n * 15 + 16, &dl));
-    c.c.repr = GPUQ_REPR_ARROW; c.c.data = data->p; c.c.offsets = (const int32_t*)offs->p;
-    t.keep.push_back(offs); t.keep.push_back(data);
+    if (c.c.repr == GPUQ_REPR_PACKED15) unpack_utf8(x, c.c, t.n, t.keep);
   }
   return t;
+}
+
+// hash-partitions t's rows `count` ways: the permutation that groups them by partition, and the count + 1 offsets into it (read back)
+struct Partitioned { BufP perm; std::vector<uint64_t> offs; };
+Partitioned partition_rows(Exec& x, const PTable& t, const Json& hash_expr, int64_t count, const void* site) {
+  gpuq_op* op = cached_op(x, site, 0, table_sig(t), [&]() {
+    const auto names = names_of(t);
+    Json he = jarr(); for (auto& e : hash_expr.a) he.a.push_back(rebind(e, names));
+    return jobj({{"op", jstr("partition")}, {"input", input_of(t)}, {"hash_expr", he}, {"partition_count", jnum(count)}});
+  });
+  Partitioned r;
+  r.perm = dev_alloc((size_t)std::max<int64_t>(1, t.n) * 4); BufP offs = dev_alloc((size_t)(count + 2) * 8);
+  InputC ic; make_input(t, ic);
+  check(x, gpuq_partition_run(op, x.stream, &ic.in, (uint32_t*)r.perm->p, (uint64_t*)offs->p));
+  r.offs.resize((size_t)count + 1);
+  HIPCHECK(hipMemcpyAsync(r.offs.data(), offs->p, r.offs.size() * 8, hipMemcpyDeviceToHost, (hipStream_t)x.stream));
+  HIPCHECK(hipStreamSynchronize((hipStream_t)x.stream));
+  return r;
 }
 
 struct ShuffleFile { int64_t partition; std::string path; int64_t rows, batches, bytes; };
@@ -1851,13 +1829,9 @@ struct ShuffleWriterExec : PNode {
 
   ShuffleFile write_file(Exec& x, const PTable& view, int64_t partition, const std::string& path) {
     PTable t = arrow_layout(x, view);
-    std::vector<gpuq_field_info> fields(t.cols.size());
+    std::vector<gpuq_field_info> fields;
     size_t raw = 0;
-    for (size_t i = 0; i < t.cols.size(); ++i) {
-      gpuq_field_info& f = fields[i]; f = gpuq_field_info{};
-      std::snprintf(f.name, sizeof(f.name), "%s", t.cols[i].name.c_str());
-      f.type = t.cols[i].c.type; f.precision = t.cols[i].c.precision; f.scale = t.cols[i].c.scale; f.nullable = t.cols[i].nullable; f.repr = GPUQ_REPR_ARROW;
-    }
+    for (auto& c : t.cols) fields.push_back(field_info_of(c));      // (Arrow layout throughout: arrow_layout)
     mkdirs(path.substr(0, path.rfind('/')));
     FILE* fp = std::fopen(path.c_str(), "wb");
     if (!fp) throw std::runtime_error("cannot create " + path + ": " + std::strerror(errno));
@@ -1880,11 +1854,10 @@ struct ShuffleWriterExec : PNode {
         raw = 4096;
         for (auto& c : t.cols) {
           gpuq_column v = c.c; v.length = k;
-          DType dt; dt.id = v.type; dt.p = v.precision; dt.s = v.scale;
           if (v.validity) v.validity += lo / 8;
           if (v.type == T_UTF8) { v.offsets += lo; raw += (size_t)(k + 1) * 4 + 64; }
           else if (v.type == T_BOOL) { v.data = (const uint8_t*)v.data + lo / 8; raw += (size_t)k / 8 + 64; }
-          else { v.data = (const char*)v.data + (size_t)lo * (size_t)type_width(dt); raw += (size_t)k * (size_t)type_width(dt) + 64; }
+          else { v.data = (const char*)v.data + (size_t)lo * width_of(v); raw += (size_t)k * width_of(v) + 64; }
           raw += (size_t)k / 8 + 64;
           cols.push_back(v);
         }
@@ -1919,18 +1892,8 @@ struct ShuffleWriterExec : PNode {
       write_ns += ns(tw, now());
     } else {
       auto tr = now();
-      PSchema ps = plain_schema(t);
-      std::vector<std::string> names; for (auto& f : ps) names.push_back(f.name);
-      gpuq_op* op = cached_op(x, this, 0, table_sig(t), [&]() {
-        Json he = jarr(); for (auto& e : hash_expr.a) he.a.push_back(rebind(e, names));
-        return jobj({{"op", jstr("partition")}, {"input", jobj({{"fields", table_fields(t)}})}, {"hash_expr", he}, {"partition_count", jnum(partition_count)}});
-      });
-      BufP perm = dev_alloc((size_t)std::max<int64_t>(1, t.n) * 4), offs = dev_alloc((size_t)(partition_count + 2) * 8);
-      InputC ic; make_input(t, ic);
-      check(x, gpuq_partition_run(op, x.stream, &ic.in, (uint32_t*)perm->p, (uint64_t*)offs->p));
-      std::vector<uint64_t> o((size_t)partition_count + 1);
-      HIPCHECK(hipMemcpyAsync(o.data(), offs->p, o.size() * 8, hipMemcpyDeviceToHost, (hipStream_t)x.stream));
-      HIPCHECK(hipStreamSynchronize((hipStream_t)x.stream));
+      const Partitioned pt = partition_rows(x, t, hash_expr, partition_count, this);
+      const BufP& perm = pt.perm; const std::vector<uint64_t>& o = pt.offs;
       repart_ns += ns(tr, now());
       auto tw = now();
       for (int64_t q = 0; q < partition_count; ++q) {
@@ -1946,18 +1909,12 @@ struct ShuffleWriterExec : PNode {
     std::vector<uint32_t> pid; std::vector<int32_t> poff{0}; std::string pdata; std::vector<uint64_t> rows, batches, bytes;
     for (auto& f : files) { pid.push_back((uint32_t)f.partition); pdata += f.path; poff.push_back((int32_t)pdata.size()); rows.push_back((uint64_t)f.rows); batches.push_back((uint64_t)f.batches); bytes.push_back((uint64_t)f.bytes); }
     PTable out; out.n = n;
-    auto up = [&](const void* src, size_t nbytes) -> BufP {
-      BufP b = dev_alloc(nbytes + 16);
-      if (nbytes) HIPCHECK(hipMemcpyAsync(b->p, src, nbytes, hipMemcpyHostToDevice, (hipStream_t)x.stream));
-      out.keep.push_back(b); return b;
-    };
-    auto fixed = [&](const char* name, int tid, const void* src, size_t w) {
-      PCol c; c.name = name; c.type = type_json_of(tid, 0, 0); c.nullable = false; c.c.type = tid; c.c.repr = GPUQ_REPR_ARROW; c.c.length = n; c.c.data = up(src, (size_t)n * w)->p;
-      out.cols.push_back(c); out.sides.push_back(0);
-    };
+    auto up = [&](const void* src, size_t nbytes) -> BufP { BufP b = dev_alloc(nbytes + 16); upload(x, b, src, nbytes, false); return b; };      // (waited for once, below)
+    auto fixed = [&](const char* name, int tid, const void* src, size_t w) { BufP b = up(src, (size_t)n * w); append_column(out, name, tid, b->p, b, nullptr, n, false); };
     fixed("partition", T_UINT32, pid.data(), 4);
-    { PCol c; c.name = "path"; c.type = jstr("Utf8"); c.nullable = false; c.c.type = T_UTF8; c.c.repr = GPUQ_REPR_ARROW; c.c.length = n;
-      c.c.offsets = (const int32_t*)up(poff.data(), poff.size() * 4)->p; c.c.data = up(pdata.data(), pdata.size())->p; out.cols.push_back(c); out.sides.push_back(0); }
+    { BufP o = up(poff.data(), poff.size() * 4), d = up(pdata.data(), pdata.size());      // (a Utf8 column: offsets + bytes)
+      PCol c; c.name = "path"; c.type = jstr("Utf8"); c.nullable = false; c.c.type = T_UTF8; c.c.repr = GPUQ_REPR_ARROW; c.c.length = n;
+      c.c.offsets = (const int32_t*)o->p; c.c.data = d->p; out.cols.push_back(c); out.sides.push_back(0); out.keep.push_back(o); out.keep.push_back(d); }
     fixed("num_rows", T_UINT64, rows.data(), 8); fixed("num_batches", T_UINT64, batches.data(), 8); fixed("num_bytes", T_UINT64, bytes.data(), 8);
     HIPCHECK(hipStreamSynchronize((hipStream_t)x.stream));      // the uploads read host vectors that die with this frame
     m.elapsed_ns += ns(t0, now());
@@ -1976,12 +1933,8 @@ struct ShuffleReaderExec : PNode {
   PTable execute(int part, Exec& x) override {
     auto t0 = std::chrono::steady_clock::now();
     if (part < 0 || part >= (int)locations.size()) throw std::runtime_error("ShuffleReaderExec: partition out of range");
-    std::vector<gpuq_field_info> fields(schema_.size());
-    for (size_t i = 0; i < schema_.size(); ++i) {
-      gpuq_field_info& f = fields[i]; f = gpuq_field_info{};
-      std::snprintf(f.name, sizeof(f.name), "%s", schema_[i].name.c_str());
-      int p, s; f.type = type_id_of(schema_[i].type, p, s); f.precision = p; f.scale = s; f.nullable = schema_[i].nullable; f.repr = GPUQ_REPR_ARROW;
-    }
+    std::vector<gpuq_field_info> fields;
+    for (auto& f : schema_) fields.push_back(field_info_of(column_of(f)));
     std::vector<PTable> parts;
     std::vector<uint8_t> bytes;
     std::string part_fn;
@@ -2058,20 +2011,20 @@ template <class F> auto announce_failures(Exec& x, F&& local_part) -> decltype(l
     throw AgreedFailure(e.what(), rc);
   }
 }
-void table_c_arrays(const PTable& t, std::vector<gpuq_column>& cols, std::vector<gpuq_field_info>& fields) {
+// What an exchange sends and what it hands back, as the plan declares them.  A column read through an index vector may carry NULLs:
+// nullability is the plan's (ps: plain_schema of the node's input, identical on every rank), not the materialised column's.
+void table_c_arrays(const PTable& t, const PSchema& ps, std::vector<gpuq_column>& cols, std::vector<gpuq_field_info>& fields) {
   cols.clear(); fields.clear();
-  for (auto& c : t.cols) {
-    gpuq_field_info f{};
-    std::snprintf(f.name, sizeof(f.name), "%s", c.name.c_str());
-    f.type = c.c.type; f.precision = c.c.precision; f.scale = c.c.scale; f.nullable = c.nullable; f.repr = c.c.repr;
-    cols.push_back(c.c); fields.push_back(f);
+  for (size_t i = 0; i < t.cols.size(); ++i) {
+    cols.push_back(t.cols[i].c); fields.push_back(field_info_of(t.cols[i]));
+    fields.back().nullable = ps[i].nullable ? 1 : 0;
   }
 }
-PTable table_from_owned(gpuq_table* tab, const PTable& like) {
+PTable table_from_owned(gpuq_table* tab, const PTable& like, const PSchema& ps) {
   PTable out; out.n = gpuq_table_num_rows(tab);
   out.keep.push_back(BufP(new DevBuf(), [tab](DevBuf* d) { delete d; gpuq_table_free(tab); }));
   for (size_t i = 0; i < like.cols.size(); ++i) {
-    PCol c; c.name = like.cols[i].name; c.type = like.cols[i].type; c.nullable = like.cols[i].nullable;
+    PCol c; c.name = like.cols[i].name; c.type = like.cols[i].type; c.nullable = ps[i].nullable;
     gpuq_table_column(tab, (int)i, &c.c, nullptr);
     out.cols.push_back(c); out.sides.push_back(0);
   }
@@ -2099,32 +2052,18 @@ struct RepartitionExec : PNode {
     if (!need_all) prune_columns(t, need);
     t0 = std::chrono::steady_clock::now();
     ps = plain_schema(t);
-    std::vector<std::string> names; for (auto& f : ps) names.push_back(f.name);
-    gpuq_op* op = cached_op(x, this, 0, table_sig(t), [&]() {
-      Json he = jarr(); for (auto& e : hash_expr.a) he.a.push_back(rebind(e, names));
-      return jobj({{"op", jstr("partition")}, {"input", jobj({{"fields", table_fields(t)}})}, {"hash_expr", he}, {"partition_count", jnum(partition_count)}});
-    });
-    BufP perm = dev_alloc((size_t)std::max<int64_t>(1, t.n) * 4), offs = dev_alloc((size_t)(partition_count + 2) * 8);
-    InputC ic; make_input(t, ic);
-    check(x, gpuq_partition_run(op, x.stream, &ic.in, (uint32_t*)perm->p, (uint64_t*)offs->p));
-    std::vector<uint64_t> o((size_t)partition_count + 1);
-    HIPCHECK(hipMemcpyAsync(o.data(), offs->p, o.size() * 8, hipMemcpyDeviceToHost, (hipStream_t)x.stream));
-    HIPCHECK(hipStreamSynchronize((hipStream_t)x.stream));
+    const Partitioned pt = partition_rows(x, t, hash_expr, partition_count, this);
     ++x.host_syncs;
     // one take groups the rows by destination rank
-    grouped = materialize(x, select_view(x, t, (const uint32_t*)perm->p, t.n, perm));
+    grouped = materialize(x, select_view(x, t, (const uint32_t*)pt.perm->p, t.n, pt.perm));
     resolve(x, grouped);
-    table_c_arrays(grouped, cols, fields);
-    // a column read through an index vector may carry NULLs: nullability as the plan sees it (identical on every rank)
-    for (size_t i = 0; i < fields.size(); ++i) fields[i].nullable = ps[i].nullable ? 1 : 0;
-    doff.assign(o.begin(), o.end());
+    table_c_arrays(grouped, ps, cols, fields);
+    doff.assign(pt.offs.begin(), pt.offs.end());
     return 0;
     });
     gpuq_table* tab = nullptr;
     xcheck(gpuq_exchange_partitions(x.comm, x.stream, cols.data(), fields.data(), (int)cols.size(), doff.data(), &tab));
-    PTable out = table_from_owned(tab, grouped);
-    for (size_t i = 0; i < out.cols.size(); ++i) out.cols[i].nullable = ps[i].nullable;
-    return timed(x, t0, out);
+    return timed(x, t0, table_from_owned(tab, grouped, ps));
   }
 };
 struct BroadcastExec : PNode {
@@ -2146,15 +2085,12 @@ struct BroadcastExec : PNode {
     ps = plain_schema(t);
     plain = materialize(x, t);
     resolve(x, plain);
-    table_c_arrays(plain, cols, fields);
-    for (size_t i = 0; i < fields.size(); ++i) fields[i].nullable = ps[i].nullable ? 1 : 0;
+    table_c_arrays(plain, ps, cols, fields);
     return 0;
     });
     gpuq_table* tab = nullptr;
     xcheck(gpuq_allgather_table(x.comm, x.stream, cols.data(), fields.data(), (int)cols.size(), plain.n, &tab));
-    PTable out = table_from_owned(tab, plain);
-    for (size_t i = 0; i < out.cols.size(); ++i) out.cols[i].nullable = ps[i].nullable;
-    return timed(x, t0, out);
+    return timed(x, t0, table_from_owned(tab, plain, ps));
   }
 };
 
@@ -2171,20 +2107,15 @@ struct RangeRepartitionExec : PNode {
   PNodeP input; Json expr; int64_t partition_count = 0, samples = 1024;
   std::vector<PNode*> children() override { return {input.get()}; }
   int partitions() override { return input->partitions(); }
-  static PCol tag_column(Exec& x, int64_t n, int32_t value, std::vector<BufP>& keep) {
-    BufP b = dev_alloc((size_t)std::max<int64_t>(n, 1) * 4 + 16);
-    if (value == 0) HIPCHECK(hipMemsetAsync(b->p, 0, (size_t)std::max<int64_t>(n, 1) * 4, (hipStream_t)x.stream));
-    else { std::vector<int32_t> h((size_t)std::max<int64_t>(n, 1), value); HIPCHECK(hipMemcpyAsync(b->p, h.data(), h.size() * 4, hipMemcpyHostToDevice, (hipStream_t)x.stream)); HIPCHECK(hipStreamSynchronize((hipStream_t)x.stream)); }
-    keep.push_back(b);
-    PCol c; c.name = "__gpuq_splitter"; c.type = jstr("Int32"); c.nullable = false;
-    c.c.type = T_INT32; c.c.repr = GPUQ_REPR_ARROW; c.c.data = b->p; c.c.length = n;
-    return c;
+  // every column of `t` nullable, and the tag column (0: a row, 1: a splitter) appended
+  static void tag_column(Exec& x, PTable& t, int32_t value) {
+    for (auto& c : t.cols) c.nullable = true;
+    BufP b = alloc_rows(t.n);
+    if (value == 0) HIPCHECK(hipMemsetAsync(b->p, 0, (size_t)std::max<int64_t>(t.n, 1) * 4, (hipStream_t)x.stream));
+    else { std::vector<int32_t> h((size_t)std::max<int64_t>(t.n, 1), value); upload(x, b, h.data(), h.size() * 4); }
+    append_column(t, "__gpuq_splitter", T_INT32, b->p, b, nullptr, t.n, false);
   }
-  static BufP upload_u32(Exec& x, const std::vector<uint32_t>& v) {
-    BufP b = dev_alloc(std::max<size_t>(v.size(), 1) * 4 + 16);
-    if (!v.empty()) { HIPCHECK(hipMemcpyAsync(b->p, v.data(), v.size() * 4, hipMemcpyHostToDevice, (hipStream_t)x.stream)); HIPCHECK(hipStreamSynchronize((hipStream_t)x.stream)); }
-    return b;
-  }
+  static BufP upload_u32(Exec& x, const std::vector<uint32_t>& v) { BufP b = alloc_rows((int64_t)v.size()); upload(x, b, v.data(), v.size() * 4); return b; }
   PTable execute(int part, Exec& x) override {
     if (!x.comm) throw Unsupported("RangeRepartitionExec needs the ranks of the node (gpuq_plan_set_comm)");
     const int W = gpuq_comm_world(x.comm);
@@ -2203,8 +2134,7 @@ struct RangeRepartitionExec : PNode {
       std::vector<uint32_t> idx((size_t)k); for (int64_t i = 0; i < k; ++i) idx[(size_t)i] = (uint32_t)(i * stride);
       BufP di = upload_u32(x, idx);
       samp = materialize(x, select_view(x, t, (const uint32_t*)di->p, k, di), true);
-      table_c_arrays(samp, cols, fields);
-      for (size_t i = 0; i < fields.size(); ++i) fields[i].nullable = ps[i].nullable ? 1 : 0;
+      table_c_arrays(samp, ps, cols, fields);
       return 0;
     });
     gpuq_table* gathered = nullptr;
@@ -2212,26 +2142,24 @@ struct RangeRepartitionExec : PNode {
     // ---- 2. splitters -> range boundaries of the locally sorted run
     PTable grouped; std::vector<int64_t> doff;
     announce_failures(x, [&]() {
-      PTable all = table_from_owned(gathered, samp);
-      for (size_t i = 0; i < all.cols.size(); ++i) all.cols[i].nullable = ps[i].nullable;
+      PTable all = table_from_owned(gathered, samp, ps);
       PTable ssorted = materialize(x, sort_table(x, all, expr, -1, this, 0), true);
       const int64_t m = ssorted.n;
       std::vector<uint32_t> cut;
       if (m > 0) for (int j = 1; j < W; ++j) cut.push_back((uint32_t)std::min<int64_t>(m - 1, std::max<int64_t>(0, (int64_t)j * m / W)));
       std::vector<PTable> parts;
-      { PTable a = t; for (auto& c : a.cols) c.nullable = true; a.cols.push_back(tag_column(x, a.n, 0, a.keep)); a.sides.push_back(0); a.record_cap = 0; parts.push_back(a); }
+      { PTable a = t; tag_column(x, a, 0); parts.push_back(a); }
       if (!cut.empty()) {
         BufP dc = upload_u32(x, cut);
         PTable spl = materialize(x, select_view(x, ssorted, (const uint32_t*)dc->p, (int64_t)cut.size(), dc), true);
-        for (auto& c : spl.cols) c.nullable = true;
-        spl.cols.push_back(tag_column(x, spl.n, 1, spl.keep)); spl.sides.push_back(0); spl.record_cap = 0;
+        tag_column(x, spl, 1);
         parts.push_back(spl);
       }
       PTable both = parts.size() == 1 ? parts[0] : concat_tables(x, parts);
-      Json keys = expr; keys.a.push_back(jobj({{"expr", jobj({{"column", jobj({{"name", jstr("__gpuq_splitter")}})}})}, {"asc", jbool(true)}, {"nulls_first", jbool(false)}}));
+      const Json tagc = jcolname("__gpuq_splitter");
+      Json keys = expr; keys.a.push_back(jobj({{"expr", tagc}, {"asc", jbool(true)}, {"nulls_first", jbool(false)}}));
       PTable run = sort_table(x, both, keys, -1, this, 1);
       // positions of the splitters in the sorted run: filter on the tag, read the W-1 positions back
-      const Json tagc = jobj({{"column", jobj({{"name", jstr("__gpuq_splitter")}})}});
       auto lit_i32 = [](int v) { return jobj({{"literal", jobj({{"type", jstr("Int32")}, {"value", jstr(std::to_string(v))}})}}); };
       PTable run_m = materialize(x, run);
       BufP sel; const int64_t ns = filter_sel(x, run_m, jobj({{"binary_expr", jobj({{"l", tagc}, {"r", lit_i32(1)}, {"op", jstr("=")}})}}), this, 2, sel);
@@ -2245,15 +2173,13 @@ struct RangeRepartitionExec : PNode {
       rows_only.cols.pop_back(); rows_only.sides.pop_back();
       grouped = materialize(x, rows_only, true);
       resolve(x, grouped);
-      table_c_arrays(grouped, cols, fields);
-      for (size_t i = 0; i < fields.size(); ++i) fields[i].nullable = ps[i].nullable ? 1 : 0;
+      table_c_arrays(grouped, ps, cols, fields);
       return 0;
     });
     // ---- 3. one exchange of ranges, then an ordered fan-in of the received runs
     gpuq_table* tab = nullptr;
     xcheck(gpuq_exchange_partitions(x.comm, x.stream, cols.data(), fields.data(), (int)cols.size(), doff.data(), &tab));
-    PTable mine = table_from_owned(tab, grouped);
-    for (size_t i = 0; i < mine.cols.size(); ++i) mine.cols[i].nullable = ps[i].nullable;
+    PTable mine = table_from_owned(tab, grouped, ps);
     std::vector<int64_t> pr((size_t)W, 0); int np = 0;
     xcheck(gpuq_table_piece_rows(tab, pr.data(), W, &np));
     std::vector<int64_t> offs{0}; for (int i = 0; i < np; ++i) offs.push_back(offs.back() + pr[(size_t)i]);
@@ -2302,8 +2228,8 @@ PNodeP build_node(const Json& j) {
         inner->group_expr.a.push_back(jobj({{"expr", arg}, {"name", jstr("__distinct")}}));
         inner->aggr_expr = jarr({jobj({{"fn", jstr("COUNT")}, {"expr", jobj({{"literal", jobj({{"type", jstr("Int64")}, {"value", jstr("1")}})}})}, {"name", jstr("__n")}})});
         Json outer_groups = jarr(), outer_aggs = jarr();
-        for (auto& g : n->group_expr.a) outer_groups.a.push_back(jobj({{"expr", jobj({{"column", jobj({{"name", g.at("name")}})}})}, {"name", g.at("name")}}));
-        for (auto& a : n->aggr_expr.a) outer_aggs.a.push_back(jobj({{"fn", a.at("fn")}, {"expr", jobj({{"column", jobj({{"name", jstr("__distinct")}})}})}, {"name", a.at("name")}}));
+        for (auto& g : n->group_expr.a) outer_groups.a.push_back(jobj({{"expr", jcolname(g.at("name"))}, {"name", g.at("name")}}));
+        for (auto& a : n->aggr_expr.a) outer_aggs.a.push_back(jobj({{"fn", a.at("fn")}, {"expr", jcolname("__distinct")}, {"name", a.at("name")}}));
         n->input = std::move(inner); n->group_expr = outer_groups; n->aggr_expr = outer_aggs;
       }
     }
@@ -2464,14 +2390,7 @@ static int plan_execute_impl(gpuq_plan* p, void* stream, int partition, const gp
     ++p->completed;
     p->last_settles = x.settles; p->last_host_syncs = x.host_syncs; p->last_deferred = was_deferred && x.deferred ? 1 : 0;
     std::unique_ptr<gpuq_result> r(new gpuq_result());
-    for (auto& c : t.cols) {
-      gpuq_field_info f{};
-      std::snprintf(f.name, sizeof(f.name), "%s", c.name.c_str());
-      f.type = c.c.type; f.precision = c.c.precision; f.scale = c.c.scale; f.nullable = c.nullable; f.repr = c.c.repr;
-      DType dt; dt.id = c.c.type; dt.p = c.c.precision; dt.s = c.c.scale;
-      f.width = c.c.type == T_BOOL ? 0 : type_width(dt);
-      r->fields.push_back(f);
-    }
+    for (auto& c : t.cols) r->fields.push_back(field_info_of(c));
     // inputs are the caller's: only library-owned buffers are kept
     r->t = std::move(t);
     *out = r.release();
@@ -2556,14 +2475,7 @@ int gpuq_plan_schema(gpuq_plan* p, gpuq_field_info* fields_out, int cap, int* n_
     const PSchema s = p->root->schema();
     *n_out = (int)s.size();
     if (!fields_out || cap < (int)s.size()) { if (!fields_out && cap == 0) return; throw Capacity("plan schema has " + std::to_string(s.size()) + " fields"); }
-    for (size_t i = 0; i < s.size(); ++i) {
-      gpuq_field_info f{};
-      std::snprintf(f.name, sizeof(f.name), "%s", s[i].name.c_str());
-      int pr = 0, sc = 0; f.type = type_id_of(s[i].type, pr, sc); f.precision = pr; f.scale = sc; f.nullable = s[i].nullable ? 1 : 0;
-      f.repr = GPUQ_REPR_ARROW;
-      DType dt; dt.id = f.type; dt.p = pr; dt.s = sc; f.width = (f.type == T_BOOL) ? 0 : type_width(dt);
-      fields_out[i] = f;
-    }
+    for (size_t i = 0; i < s.size(); ++i) fields_out[i] = field_info_of(column_of(s[i]));
   });
 }
 

@@ -36,7 +36,13 @@ def native_rows(tc, plan, partition=0):
     """(rows, NativePlan) of a plan executed by the native executor.  Every plan that goes through here also checks
     gpuq_plan_schema: the schema announced BEFORE execution (QueryStageExecutor::schema(), execution_engine.rs:59) is the schema
     of what execution returns: names and types, column by column (the nullable flag of an executed column only says whether a
-    validity bitmap was materialised -- the declared nullability is the plan's)."""
+    validity bitmap was materialised -- the declared nullability is the plan's).
+
+    Recording hook: when the environment variable GPUQ_PLAN_TRACE names a file, every call appends one JSON line to it --
+    PYTEST_CURRENT_TEST, the sorted descriptor texts of the operators the plan compiled (NativePlan.profile_all()) and
+    exec_stats() after the first and after the last execution.  Two builds of the library that send the same requests to the
+    operator layer write equal files.  It records only: nothing is asserted on it."""
+    import json, os
     from arrow_ballista_amd.table import type_json
     np_ = g.NativePlan(plan, tc)
     announced = np_.schema()
@@ -45,6 +51,8 @@ def native_rows(tc, plan, partition=0):
     got = [(fields[i].name.decode(), type_json(fields[i].type, fields[i].precision, fields[i].scale), bool(fields[i].nullable)) for i in range(r.num_columns)]
     assert [(n, t) for n, t, _ in announced] == [(n, t) for n, t, _ in got], (announced, got)
     rows = arrow_rows(r.to_arrow())
+    trace = os.environ.get("GPUQ_PLAN_TRACE")
+    first_stats = np_.exec_stats() if trace else None
     # Every plan that goes through here is executed twice more: from its second execution on a plan runs DEFERRED (operators keep
     # what their synchronous run learned, row counts travel as device words, one host round trip settles everything; DESIGN.md
     # section 2) and must return the same rows in the same order.  Plans that write files are left alone.
@@ -54,6 +62,10 @@ def native_rows(tc, plan, partition=0):
         for _ in range(2):
             again = arrow_rows(np_.execute(partition).to_arrow())
             close_rows(key(again), key(rows))      # (float sums: atomics add in any order, 1e-9 relative as everywhere)
+    if trace:
+        with open(trace, "a") as f:
+            f.write(json.dumps({"test": os.environ.get("PYTEST_CURRENT_TEST", ""), "desc": sorted(o["desc"] for o in np_.profile_all()),
+                                "first": first_stats, "last": np_.exec_stats()}, sort_keys=True) + "\n")
     return rows, np_
 
 
