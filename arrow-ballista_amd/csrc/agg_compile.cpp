@@ -155,6 +155,8 @@ struct Scan {
     refuse_type(x->type);
   }
   int fsum(const NodeP& x) { return acc(ACC_FSUM, x, F64); }
+  // BIT_AND / BIT_OR / BIT_XOR keep the low 64 bits of the argument's two's-complement pattern; the declared type is the argument's
+  int bitwise(int kind, const NodeP& x) { return acc(kind, x, x->type); }
   int minmax(const NodeP& x, bool minimum) { return x->type.is_float() ? acc(minimum ? ACC_FMIN : ACC_FMAX, x, x->type) : acc(minimum ? ACC_MIN : ACC_MAX, x, x->type); }
   // the variance family works in f64
   NodeP f64_arg(const NodeP& x) {
@@ -193,6 +195,8 @@ struct Post {
   NodeP acc(int i) { return pc.column(nk + i); }
   NodeP guard(const AggPlan& pl, NodeP v) { return pl.cnt >= 0 && pl.arg_nullable ? pc.nullif0(v, acc(pl.cnt)) : v; }
   void out(NodeP v, const std::string& name) { pc.add_output(v); names.push_back(name); }
+  // a bitwise cell (lo = 64 pattern bits, hi = 0) as a value of its accumulator's integer type: sign- or zero-extended from that type's width
+  NodeP bits_of(int i) { const DType& t = accs[i].type; return pc.raw(OP_WRAP, t, false, acc(i)->bits, {acc(i)}, (uint32_t)(type_width(t) * 8) | (t.is_unsigned() ? 0x100u : 0u)); }
 };
 
 // VARIANCE / STDDEV / COVARIANCE / CORRELATION (datafusion.proto:639-645).  The reference keeps Welford-style
@@ -233,6 +237,7 @@ struct AggFn {
   AggParts parts;
   int args;                            // 1, 2, or 0: the argument may be left out (COUNT(*))
   bool minimum, population, stddev;    // MIN not MAX; divide by n not n - 1; the square root of the variance
+  int kind = 0; const char* state = "";      // the bitwise family: its accumulator kind and its state column's suffix (format_state_name [UPSTREAM-KNOWLEDGE])
 };
 template <class D> AggParts parts() { return {D::from_args, D::from_states, D::states, D::value}; }
 
@@ -301,6 +306,31 @@ struct MinMax {
   }
   static void states(Post& p, const AggPlan& pl) { p.out(p.guard(pl, p.acc(pl.mm)), pl.name + (pl.fn->minimum ? "[min]" : "[max]")); }
   static void value(Post& p, const AggPlan& pl) { p.out(p.guard(pl, p.acc(pl.mm)), pl.name); }
+};
+// BIT_AND / BIT_OR / BIT_XOR (datafusion.proto:650-652) over the eight integer types: result and state have the argument's type
+struct Bitwise {
+  static void from_args(Scan& s, AggPlan& pl, NodeP x) {
+    if (!x->type.is_int()) s.refuse_type(x->type);
+    pl.arg_nullable = s.may_be_null(x);
+    pl.mm = s.bitwise(pl.fn->kind, x);
+    if (pl.arg_nullable) pl.cnt = s.count(x);
+  }
+  static void from_states(Scan& s, AggPlan& pl, States& st) { from_args(s, pl, st.take()); }      // the state merges as the argument folds
+  static void states(Post& p, const AggPlan& pl) { p.out(p.guard(pl, p.bits_of(pl.mm)), pl.name + pl.fn->state); }
+  static void value(Post& p, const AggPlan& pl) { p.out(p.guard(pl, p.bits_of(pl.mm)), pl.name); }
+};
+// BOOL_AND / BOOL_OR (datafusion.proto:653-654): the AND / OR of the 0/1 register value in an Int64-typed cell; the value is cell != 0
+struct BoolAgg {
+  static void from_args(Scan& s, AggPlan& pl, NodeP x) {
+    if (x->type.id != T_BOOL) s.refuse_type(x->type);
+    pl.arg_nullable = s.may_be_null(x);
+    pl.mm = s.bitwise(pl.fn->kind, s.ec.cast(x, I64));
+    if (pl.arg_nullable) pl.cnt = s.count(x);
+  }
+  static void from_states(Scan& s, AggPlan& pl, States& st) { from_args(s, pl, st.take()); }
+  static NodeP truth(Post& p, const AggPlan& pl) { return p.guard(pl, p.pc.raw(OP_NE, BOOL, false, 2, {p.acc(pl.mm), p.pc.lit_int(I64, 0)})); }
+  static void states(Post& p, const AggPlan& pl) { p.out(truth(p, pl), pl.name + pl.fn->state); }
+  static void value(Post& p, const AggPlan& pl) { p.out(truth(p, pl), pl.name); }
 };
 // the two-argument functions skip a row where either argument is NULL, for every sum
 void pair_up(ExprCompiler& ec, NodeP& x, NodeP& y) {
@@ -404,6 +434,11 @@ const AggFn AGG_FNS[] = {
   {{"COVARIANCE", "COVAR", "COVAR_SAMP"},       parts<Covariance>(),  2,    false,  false,     false},
   {{"COVARIANCE_POP", "COVAR_POP"},             parts<Covariance>(),  2,    false,  true,      false},
   {{"CORRELATION", "CORR"},                     parts<Correlation>(), 2,    false,  false,     false},
+  {{"BIT_AND"},                                 parts<Bitwise>(),     1,    false,  false,     false,  ACC_BAND, "[bit_and]"},
+  {{"BIT_OR"},                                  parts<Bitwise>(),     1,    false,  false,     false,  ACC_BOR,  "[bit_or]"},
+  {{"BIT_XOR"},                                 parts<Bitwise>(),     1,    false,  false,     false,  ACC_BXOR, "[bit_xor]"},
+  {{"BOOL_AND"},                                parts<BoolAgg>(),     1,    false,  false,     false,  ACC_BAND, "[bool_and]"},
+  {{"BOOL_OR"},                                 parts<BoolAgg>(),     1,    false,  false,     false,  ACC_BOR,  "[bool_or]"},
 };
 const AggFn* find_agg_fn(const std::string& upper_name) {
   for (const AggFn& f : AGG_FNS) for (const char* n : f.names) if (upper_name == n) return &f;

@@ -354,7 +354,8 @@ NodeP ExprCompiler::cast(NodeP e, DType to) {
 static std::string norm_op(const std::string& op) {
   static const std::map<std::string, std::string> m = {
       {"Plus", "+"}, {"Minus", "-"}, {"Multiply", "*"}, {"Divide", "/"}, {"Modulo", "%"}, {"Eq", "="}, {"NotEq", "!="},
-      {"Lt", "<"}, {"LtEq", "<="}, {"Gt", ">"}, {"GtEq", ">="}, {"And", "AND"}, {"Or", "OR"}, {"and", "AND"}, {"or", "OR"}, {"<>", "!="}, {"==", "="}};
+      {"Lt", "<"}, {"LtEq", "<="}, {"Gt", ">"}, {"GtEq", ">="}, {"And", "AND"}, {"Or", "OR"}, {"and", "AND"}, {"or", "OR"}, {"<>", "!="}, {"==", "="},
+      {"BitwiseAnd", "&"}, {"BitwiseOr", "|"}, {"BitwiseXor", "^"}, {"BIT_XOR", "^"}};
   auto it = m.find(op); return it == m.end() ? op : it->second;
 }
 
@@ -367,10 +368,17 @@ NodeP ExprCompiler::binary(const std::string& op_in, NodeP l, NodeP r) {
   }
   const bool is_cmp = (op == "=" || op == "!=" || op == "<" || op == "<=" || op == ">" || op == ">=");
   const bool is_arith = (op == "+" || op == "-" || op == "*" || op == "/" || op == "%");
-  if (!is_cmp && !is_arith) throw std::runtime_error("unsupported binary operator '" + op_in + "'");
+  const bool is_bitwise = (op == "&" || op == "|" || op == "^");
+  if (!is_cmp && !is_arith && !is_bitwise) throw std::runtime_error("unsupported binary operator '" + op_in + "'");
   // NULL literal operand adopts the other side's type
   if (l->type.id == T_NULL && r->type.id != T_NULL) l = lit_null(r->type);
   if (r->type.id == T_NULL && l->type.id != T_NULL) r = lit_null(l->type);
+  if (is_bitwise) {
+    // two integers of ONE type (the planner has inserted the casts): both 128-bit registers hold the value sign- or zero-extended, and
+    // & | ^ of two such patterns is such a pattern again -- no wrap, the result is a value of that type
+    if (!(l->type.is_int() && l->type == r->type)) throw std::runtime_error("unsupported operands for '" + op + "': " + l->type.to_string() + ", " + r->type.to_string());
+    return raw(op == "&" ? OP_BAND : op == "|" ? OP_BOR : OP_BXOR, l->type, nullable, type_bits(l->type), {l, r});
+  }
   if (is_cmp) {
     static const std::map<std::string, std::pair<int, int>> ops = {
         {"=", {OP_EQ, OP_FEQ}}, {"!=", {OP_NE, OP_FNE}}, {"<", {OP_LT, OP_FLT}}, {"<=", {OP_LE, OP_FLE}}, {">", {OP_GT, OP_FGT}}, {">=", {OP_GE, OP_FGE}}};
@@ -968,6 +976,8 @@ std::string ExprCompiler::jit_source(const CompiledProgram& C, const std::vector
         two_vars = true; ne = N(a); break;
       }
       case OP_BOR: e = "(" + as128(a) + " | " + as128(b) + ")"; break;
+      case OP_BAND: e = "(" + as128(a) + " & " + as128(b) + ")"; break;
+      case OP_BXOR: e = "(" + as128(a) + " ^ " + as128(b) + ")"; break;
       case OP_WRAP: e = "wrap_int((i128)" + V(a) + ", " + std::to_string(n->imm) + "u)"; ne = N(a); break;
       case OP_ADDC: case OP_SUBC: case OP_MULC: {
         L("bool " + t + "_o; const i128 " + t + "_v = checked_arith(" + std::to_string(n->op) + ", " + as128(a) + ", " + as128(b) + ", " + ((n->imm & 1u) ? "true" : "false") + ", " + t + "_o);");

@@ -12,6 +12,7 @@
 //   SUM/AVG over integers: SUM -> Int64 (wrapping), AVG -> Float64 (f64 sum / count)
 //   integer + - *, NEGATIVE and integer casts wrap at the node's type width at every node (OP_WRAP); x/0 -> NULL,
 //   INT_MIN / -1 -> INT_MIN, INT_MIN % -1 -> 0
+//   & | ^ take two integers of one type and give that type (OP_BAND / OP_BOR / OP_BXOR over both register halves: no wrap needed)
 //   a decimal result beyond the 38 digits its type is capped at, or an operand whose rescale by 10^k leaves 127 bits,
 //   is an error at run time (OP_ADDC / OP_SUBC / OP_MULC raise FLAG_DEC_OVERFLOW; arrow-arith raises there)
 #pragma once

@@ -71,7 +71,7 @@ enum Op : uint8_t {
   OP_ISNULL, OP_ISNOTNULL,
   OP_SELECT,  // dst <- (a is true) ? b : reg[imm]
   OP_SHL,     // dst <- a << imm   (imm 0..127)
-  OP_BOR,     // dst <- a | b      (bitwise; key packing)
+  OP_BOR,     // dst <- a | b      (bitwise; key packing, and the scalar | of two integers of one type)
   OP_NULLIF0, // dst <- a, NULL when b == 0 (guards OP_DIV by zero -> NULL)
   OP_COALESCE0, // dst <- a, or 0 (non-null) when a is NULL
   OP_DATEPART,  // dst <- field imm (0 year, 1 month, 2 day) of the Date32 a (days since 1970-01-01), as an integer
@@ -85,6 +85,10 @@ enum Op : uint8_t {
   // interpreter runs the whole program before it looks at the predicate and raises for rows the predicate drops as well; the generated
   // code returns at the predicate and does not.  The flag can therefore be raised where arrow would not raise, never the other way round.
   OP_ADDC, OP_SUBC, OP_MULC,
+  // OP_BOR's siblings (numbered after the checked ops so that no earlier opcode moves): the scalar & and ^ of two integers of one type.
+  // Both halves are combined, so two correctly sign- / zero-extended values give a correctly extended result.  NULL if either side is.
+  OP_BAND,    // dst <- a & b
+  OP_BXOR,    // dst <- a ^ b
 };
 
 struct DevInsn { uint8_t op, dst, a, b; uint32_t imm; };
@@ -480,6 +484,8 @@ __device__ __forceinline__ void run_program(const DevProgram& P, GPUQ_REGS_PARAM
       case OP_SUBSTR: { bool bad = false; const u128 z = substr_packed((u128)mk128(alo, ahi), imm & 0xFFu, (imm >> 8) & 0xFFu, bad); zlo = (u64)z; zhi = (u64)(z >> 64); zn = an;
                         if (bad && !an && P.flags) atomicOr(P.flags, FLAG_STR_TRUNC); break; }
       case OP_BOR: zlo = alo | blo; zhi = ahi | bhi; break;
+      case OP_BAND: zlo = alo & blo; zhi = ahi & bhi; break;
+      case OP_BXOR: zlo = alo ^ blo; zhi = ahi ^ bhi; break;
       case OP_NULLIF0: zlo = alo; zhi = ahi; zn = an || bn || (blo == 0 && bhi == 0); break;
       case OP_COALESCE0: zlo = an ? 0 : alo; zhi = an ? 0 : ahi; zn = false; break;
       case OP_WRAP: { const i128 z = wrap_int(mk128(alo, ahi), imm); zlo = (u64)z; zhi = (u64)((u128)z >> 64); zn = an; break; }

@@ -21,7 +21,8 @@ struct OutSpec { int32_t n_out; int32_t pad; OutCol cols[MAX_OUTS]; };
 // ----- aggregate
 constexpr int MAX_ACCS = 12;
 constexpr int MAX_KEYS = 4;
-enum AccKind : int32_t { ACC_SUM = 0, ACC_COUNT = 1, ACC_COUNT_STAR = 2, ACC_MIN = 3, ACC_MAX = 4, ACC_FSUM = 5, ACC_FMIN = 6, ACC_FMAX = 7 };
+enum AccKind : int32_t { ACC_SUM = 0, ACC_COUNT = 1, ACC_COUNT_STAR = 2, ACC_MIN = 3, ACC_MAX = 4, ACC_FSUM = 5, ACC_FMIN = 6, ACC_FMAX = 7,
+                         ACC_BAND = 8, ACC_BOR = 9, ACC_BXOR = 10 /* bitwise: the low 64 bits of the argument's two's-complement pattern */ };
 struct AggSpec {
   int32_t n_keys, n_accs;
   int32_t key_reg[MAX_KEYS];
@@ -87,7 +88,8 @@ enum JoinType : int32_t { JT_INNER = 0, JT_LEFT = 1, JT_RIGHT = 2, JT_FULL = 3, 
 
 // ----- accumulator algebra: what an AccKind IS, stated once for every aggregate kernel (k_agg_tiny + k_agg_tiny_merge, k_agg_hash,
 // k_agg_lds, k_agg_bucket).  A cell is two u64 words (lo, hi): SUM is a 128-bit integer, COUNT / MIN / MAX a 64-bit one in lo, the
-// float kinds a double's bit pattern in lo.  A new kind is added here; a new aggregate kernel is a loop around these helpers.
+// float kinds a double's bit pattern in lo, the bitwise kinds (BAND / BOR / BXOR) the low 64 bits of the argument's pattern in lo, hi 0
+// (the result projection re-extends them to the argument's type).  A new kind is added here; a new aggregate kernel is a loop around these helpers.
 // (k_agg_tiny's per-row accumulate into lane-private slots is its own algorithm and stays in kernels_scan.hip.)
 constexpr uint32_t NIL = 0xFFFFFFFFu;      // no row / no slot
 __device__ __forceinline__ uint32_t tag_of(u64 h) { return (uint32_t)(h >> 32) | 2u; }
@@ -99,7 +101,8 @@ __device__ __forceinline__ u64 acc_identity(const int kind, const int half) {
     case ACC_MAX: return half ? ~0ull : 0x8000000000000000ull;
     case ACC_FMIN: return half ? 0 : 0x7FF0000000000000ull;  // +inf
     case ACC_FMAX: return half ? 0 : 0xFFF0000000000000ull;  // -inf
-    default: return 0;
+    case ACC_BAND: return half ? 0 : ~0ull;
+    default: return 0;      // (BOR, BXOR: 0)
   }
 }
 // initial value of word w of a table slot whose cells start at word cell0: state, hash and key words are 0
@@ -134,11 +137,15 @@ __device__ __forceinline__ void acc_combine(const int kind, u64& lo, u64& hi, co
     case ACC_FSUM: lo = (u64)__double_as_longlong(__longlong_as_double((i64)lo) + __longlong_as_double((i64)olo)); break;
     case ACC_FMIN: if (f64_total_key(olo) < f64_total_key(lo)) lo = olo; break;
     case ACC_FMAX: if (f64_total_key(olo) > f64_total_key(lo)) lo = olo; break;
+    case ACC_BAND: lo &= olo; break;
+    case ACC_BOR: lo |= olo; break;
+    case ACC_BXOR: lo ^= olo; break;
     default: break;
   }
 }
 // (vlo, vhi) folded into a cell other threads fold into too: SCOPE = __HIP_MEMORY_SCOPE_AGENT for a cell in device memory,
-// __HIP_MEMORY_SCOPE_WORKGROUP for one in LDS.  Integer adds commute, so SUM's carry can trail; adding zero is skipped.
+// __HIP_MEMORY_SCOPE_WORKGROUP for one in LDS.  Integer adds commute, so SUM's carry can trail; adding zero is skipped, and so is
+// a bitwise operand that is its kind's identity (the untouched cells of a flushed LDS table).
 template <int SCOPE>
 __device__ __forceinline__ void acc_fold(u64* c, const int kind, const u64 vlo, const u64 vhi) {
   switch (kind) {
@@ -162,10 +169,13 @@ __device__ __forceinline__ void acc_fold(u64* c, const int kind, const u64 vlo, 
       }
       break;
     }
+    case ACC_BAND: if (~vlo) __hip_atomic_fetch_and(c, vlo, __ATOMIC_RELAXED, SCOPE); break;
+    case ACC_BOR: if (vlo) __hip_atomic_fetch_or(c, vlo, __ATOMIC_RELAXED, SCOPE); break;
+    case ACC_BXOR: if (vlo) __hip_atomic_fetch_xor(c, vlo, __ATOMIC_RELAXED, SCOPE); break;
     default: break;
   }
 }
-// high word of a finished cell as the result carries it: MIN / MAX are sign-extended to 128 bits
+// high word of a finished cell as the result carries it: MIN / MAX are sign-extended to 128 bits (the bitwise kinds never write hi: 0)
 __device__ __forceinline__ u64 acc_result_hi(const int kind, const u64 lo, const u64 hi) {
   return (kind == ACC_MIN || kind == ACC_MAX) ? (u64)((i64)lo >> 63) : hi;
 }

@@ -450,6 +450,9 @@ __device__ __forceinline__ void k_agg_tiny_body(const DevProgram P, const i64 n_
           case ACC_FSUM: *slot = (u64)__double_as_longlong(__longlong_as_double((i64)*slot) + __longlong_as_double((i64)vlo)); break;
           case ACC_FMIN: if (f64_total_key(vlo) < f64_total_key(*slot)) *slot = vlo; break;
           case ACC_FMAX: if (f64_total_key(vlo) > f64_total_key(*slot)) *slot = vlo; break;
+          case ACC_BAND: *slot &= vlo; break;
+          case ACC_BOR: *slot |= vlo; break;
+          case ACC_BXOR: *slot ^= vlo; break;
           default: break;
         }
       }

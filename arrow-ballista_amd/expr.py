@@ -10,6 +10,7 @@ class Operator:
     Plus, Minus, Multiply, Divide, Modulo = "+", "-", "*", "/", "%"
     Eq, NotEq, Lt, LtEq, Gt, GtEq = "=", "!=", "<", "<=", ">", ">="
     And, Or = "AND", "OR"
+    BitwiseAnd, BitwiseOr, BitwiseXor = "&", "|", "^"      # two integers of one type; the result has that type
 
 
 def _type_json(t):

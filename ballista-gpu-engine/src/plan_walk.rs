@@ -16,7 +16,7 @@ use datafusion::physical_plan::aggregates::{AggregateExec, AggregateMode};
 use datafusion::physical_plan::coalesce_batches::CoalesceBatchesExec;
 use datafusion::physical_plan::coalesce_partitions::CoalescePartitionsExec;
 use datafusion::physical_plan::expressions::{
-    Avg, BinaryExpr, CaseExpr, CastExpr, Column, Count, InListExpr, IsNotNullExpr, IsNullExpr, LikeExpr, Literal, Max, Min, NegativeExpr, NotExpr,
+    Avg, BinaryExpr, BitAnd, BitOr, BitXor, BoolAnd, BoolOr, CaseExpr, CastExpr, Column, Count, InListExpr, IsNotNullExpr, IsNullExpr, LikeExpr, Literal, Max, Min, NegativeExpr, NotExpr,
     PhysicalSortExpr, Sum, TryCastExpr,
 };
 use datafusion::physical_plan::filter::FilterExec;
@@ -116,6 +116,8 @@ fn binary_op(op: &Operator) -> Result<&'static str> {
         Operator::Plus => "Plus", Operator::Minus => "Minus", Operator::Multiply => "Multiply", Operator::Divide => "Divide", Operator::Modulo => "Modulo",
         Operator::Eq => "Eq", Operator::NotEq => "NotEq", Operator::Lt => "Lt", Operator::LtEq => "LtEq", Operator::Gt => "Gt", Operator::GtEq => "GtEq",
         Operator::And => "And", Operator::Or => "Or",
+        // two integers of one type (the planner has inserted the casts); the shifts stay on the host
+        Operator::BitwiseAnd => "BitwiseAnd", Operator::BitwiseOr => "BitwiseOr", Operator::BitwiseXor => "BitwiseXor",
         other => return unsupported(format!("binary operator {other:?}")),
     })
 }
@@ -174,6 +176,8 @@ fn sort_exprs(v: &[PhysicalSortExpr]) -> Result<Value> {
 fn aggregate_fn(a: &Arc<dyn AggregateExpr>) -> Result<&'static str> {
     let x = a.as_any();
     Ok(if x.is::<Sum>() { "SUM" } else if x.is::<Avg>() { "AVG" } else if x.is::<Count>() { "COUNT" } else if x.is::<Min>() { "MIN" } else if x.is::<Max>() { "MAX" }
+       else if x.is::<BitAnd>() { "BIT_AND" } else if x.is::<BitOr>() { "BIT_OR" } else if x.is::<BitXor>() { "BIT_XOR" }
+       else if x.is::<BoolAnd>() { "BOOL_AND" } else if x.is::<BoolOr>() { "BOOL_OR" }
        else { return unsupported(format!("aggregate {}", a.name())) })
 }
 

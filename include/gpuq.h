@@ -234,7 +234,8 @@ const char* gpuq_scan_last_error(void);
 
 /* ---- compiled operators ------------------------------------------------------------------ */
 /* Descriptor JSON (see INTEGRATION.md for the grammar).  Expression nodes mirror PhysicalExprNode
-   (datafusion.proto:1142-1180): column, literal, binary_expr, cast, try_cast, not_expr, is_null_expr,
+   (datafusion.proto:1142-1180): column, literal, binary_expr (+ - * / %, the comparisons, AND / OR, and & | ^ over two integers
+   of one type), cast, try_cast, not_expr, is_null_expr,
    is_not_null_expr, negative, in_list, case_ (like_expr is evaluated by gpuq_like_utf8 and lowered to a Boolean column by the plan
    executor).  "op" is one of
      "filter"      FilterExec        {input, predicate}
@@ -252,6 +253,9 @@ const char* gpuq_scan_last_error(void);
                      COVARIANCE = COVAR = COVAR_SAMP,
                      COVARIANCE_POP = COVAR_POP   (expr, expr2)        [count] [mean1] [mean2] [algoConst]
                      CORRELATION = CORR           (expr, expr2)        [count] [mean1] [m2_1] [mean2] [m2_2] [algoConst]
+                     BIT_AND | BIT_OR | BIT_XOR  (Int8..Int64, UInt8..UInt64; result and state: the argument's type)
+                                                                       [bit_and] | [bit_or] | [bit_xor]
+                     BOOL_AND | BOOL_OR          (Boolean)             [bool_and] | [bool_or]
      "join_build"  HashJoinExec build (left) side  {input, on:[expr], predicate?, null_equals_null?,
                                                      build_side_rows?: false = gpuq_join_build_side_rows will not be called (Inner / Right / RightSemi / RightAnti)}
      "join_probe"  HashJoinExec probe (right) side {input, on:[expr], predicate?, join_type, null_equals_null?}
