@@ -13,6 +13,7 @@
 #include <memory>
 #include <mutex>
 #include <cctype>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -37,6 +38,17 @@ u64 next_pow2(u64 v) { u64 r = 1; while (r < v) r <<= 1; return r; }
 struct gpuq_timer { hipEvent_t a = nullptr, b = nullptr; };
 
 enum OpKind { K_FILTER, K_PROJECT, K_AGG, K_JOIN_BUILD, K_JOIN_PROBE, K_SORT, K_PARTITION };
+
+// What the single-read passes of kernels_sort.hip work in (the sort, the merge, the partition, the radix aggregate): the digit counts of
+// every pass, 256 u64 each, and the look-back workspace of one pass.  A sort whose pack kernel verifies a guessed key layout has it
+// report into the word behind the counts.
+struct PassBufs {
+  DevBuf hist, look; size_t look_bytes = 0;
+  static size_t guess_word_at() { return (size_t)sort_max_passes() * 256; }
+  u64* counts(bool with_guess_word = false) { return (u64*)hist.ensure((guess_word_at() + (with_guess_word ? 1 : 0)) * 8); }
+  const u64* guess_word() const { return hist.as<u64>() + guess_word_at(); }      // "the guessed layout does not hold"
+  void* lookback(i64 n) { look_bytes = onesweep_ws_bytes(n); return look.ensure(look_bytes); }
+};
 
 struct gpuq_op {
   gpuq_ctx* ctx = nullptr;
@@ -79,8 +91,15 @@ struct gpuq_op {
     uint32_t expect_flags = 0;      // status bits a deferred run is allowed to raise (a build side known to hold duplicate keys)
     void forget() { jb.valid = ag.valid = so.valid = false; }
   } learned;
-  // scratch
-  DevBuf ws[10];
+  // scratch, by operator kind (an operator has one): kept across calls, grown when a call needs more
+  struct { DevBuf bitmap, counts, total; } w_filter;
+  // raw result (keys, key_nulls, cells), partials of the LDS dictionary, hash table, result columns, cardinality sample, parked float sums
+  struct { DevBuf keys, key_nulls, cells, tiny, table, soa, sample, fstage; } w_agg;
+  struct { DevBuf key_range; } w_build;
+  struct { DevBuf seg_build, seg_probe, counts, rec, rec2, hist, scan, locality; } w_probe;      // rec .. scan: the partitioned probe
+  // blocks: the min/max blocks of the key plan, then the split points of a merge round (the plan has been read back by then)
+  struct { DevBuf blocks, klo, klo2, khi, ids, ids2; PassBufs pass; DevBuf khi2, pairs; } w_sort;
+  struct { DevBuf pid, pid2; PassBufs pass; DevBuf counts; } w_part;
   // pinned host words for the small device->host reads (flags, counts): a pageable destination makes every such copy a
   // staged, blocking transfer
   uint32_t* pin = nullptr;
@@ -103,17 +122,8 @@ struct gpuq_join_table {
 
 namespace {
 
-void set_err(gpuq_ctx*, const std::string& m) { g_last_error = m; }      // per calling thread, like errno: contexts are shared between task threads
-
-template <class F> int guarded(gpuq_ctx* ctx, F&& f) {
-  try { f(); return GPUQ_OK; }
-  catch (const HipError& e) { set_err(ctx, e.what()); return GPUQ_ERR_HIP; }
-  catch (const Unsupported& e) { set_err(ctx, e.what()); return GPUQ_ERR_UNSUPPORTED; }
-  catch (const Capacity& e) { set_err(ctx, e.what()); return GPUQ_ERR_CAPACITY; }
-  catch (const Retry& e) { set_err(ctx, e.what()); return GPUQ_ERR_RETRY; }
-  catch (const std::bad_alloc&) { set_err(ctx, "out of host memory"); return GPUQ_ERR_INTERNAL; }
-  catch (const std::exception& e) { set_err(ctx, e.what()); return GPUQ_ERR_INVALID; }
-}
+// (the message is kept per calling thread, like errno: contexts are shared between task threads)
+template <class F> int guarded(gpuq_ctx*, F&& f) { return guarded_into(g_last_error, f); }
 
 thread_local bool g_upload = true;   // false inside gpuq_compile_check (no device); per thread: other threads create operators meanwhile
 void upload_code(const CompiledProgram& p, DevBuf& dst) {
@@ -153,19 +163,28 @@ DevProgram bind_program(const CompiledProgram& cp, const Schema& schema, const D
   return P;
 }
 
+DevProgram bind_input(gpuq_op* op, const gpuq_input* in) { return bind_program(op->prog, op->in_schema, op->code_dev.as<DevCode>(), op->flags_dev.as<uint32_t>(), in); }
+void check_payload_via(int payload_via, const gpuq_input* in) { if (payload_via < 0 || payload_via > in->n_via) throw std::runtime_error("payload_via out of range"); }
+void check_row_limit(i64 n, const char* what) { if (n >= (1ll << 31)) throw Unsupported(std::string(what) + " of >= 2^31 rows in one call"); }
 // entry points that decide things on the host from the exact row count cannot take a device-side one
 void need_exact_rows(const gpuq_input* in, const char* what) {
   if (in && in->n_rows_dev) throw std::runtime_error(std::string(what) + ": the input carries a device-side row count (n_rows_dev); this entry point needs the exact count");
 }
+// The operator's status block (the head of flags_dev): the word its kernels raise FLAG_* bits in and, next to it so that one copy reads
+// both, the group count of an aggregate's result.  The count is zeroed together with the pad behind it: the result projection reads it
+// on the device as a u64 row count (DevProgram::n_dev).
+struct OpStatus { uint32_t flags = 0, pad0 = 0, n_groups = 0, pad1 = 0; };
+uint32_t* n_groups_dev(gpuq_op* op) { return op->flags_dev.as<uint32_t>() + offsetof(OpStatus, n_groups) / 4; }
 void reset_flags(gpuq_op* op, hipStream_t s) { HIPCHECK(hipMemsetAsync(op->flags_dev.p, 0, 4, s)); }
-// words [0, n) of the op's status block (flags, pad, n_groups, pad) -> host
-void read_status(gpuq_op* op, hipStream_t s, uint32_t* out, int n) {
-  uint32_t* h = op->pinned();
-  HIPCHECK(hipMemcpyAsync(h ? h : out, op->flags_dev.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+// its first `words` words -> host: one copy, one synchronise
+OpStatus read_status(gpuq_op* op, hipStream_t s, int words = 4) {
+  OpStatus st; uint32_t* h = op->pinned();
+  HIPCHECK(hipMemcpyAsync(h ? (void*)h : (void*)&st, op->flags_dev.p, (size_t)words * 4, hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
-  if (h) for (int i = 0; i < n; ++i) out[i] = h[i];
+  if (h) std::memcpy(&st, h, (size_t)words * 4);
+  return st;
 }
-uint32_t read_flags(gpuq_op* op, hipStream_t s) { uint32_t f = 0; read_status(op, s, &f, 1); return f; }
+uint32_t read_flags(gpuq_op* op, hipStream_t s) { return read_status(op, s, 1).flags; }
 void raise_flags(uint32_t f) {
   if (f & FLAG_STR_TRUNC) throw Unsupported("a Utf8 value longer than 15 bytes reached a device string comparison/key (PACKED15 limit)");
   if (f & FLAG_DEC_OVERFLOW) throw std::runtime_error("decimal arithmetic overflow: a result or a rescaled operand does not fit Decimal128 (38 digits / 127 bits)");
@@ -175,6 +194,15 @@ void raise_flags(uint32_t f) {
   if (f & FLAG_TABLE_FULL) throw std::runtime_error("hash table full");
   if (f & FLAG_GROUP_OVERFLOW) throw Capacity("group capacity exceeded");
   if (f & FLAG_SORT_LAYOUT) throw std::runtime_error("a row does not fit the remembered sort key layout");
+}
+// What follows a status read: a bit outside `tolerated` is an error -- the word is cleared for the next run and the bit raised.  The
+// tolerated bits are handed back and are still set on the device: the site says whether it clears them or its next launch does.
+// Only the tolerated bits are kept from raise_flags.  One aggregate site used to hand it the whole word; that is the same, because
+// raise_flags tests FLAG_GROUP_OVERFLOW (what an aggregate tolerates) behind every other bit an aggregate's kernels raise: only
+// FLAG_SORT_LAYOUT follows it.
+uint32_t raise_unless(gpuq_op* op, hipStream_t s, uint32_t f, uint32_t tolerated = 0) {
+  if (f & ~tolerated) { reset_flags(op, s); raise_flags(f & ~tolerated); }
+  return f & tolerated;
 }
 
 struct ProfScope {
@@ -272,6 +300,38 @@ std::string agg_tiny_spec(const gpuq_op* op, int gmax) {
 }
 
 void check_ctx(gpuq_ctx* c) { if (!c) throw std::runtime_error("ctx is NULL"); HIPCHECK(hipSetDevice(c->device)); }
+
+// The head of every run call of an operator: the handle, the device, the operator's kind, the calling thread's stream.  The call's own
+// argument checks and its ProfTotal follow in `body`, in the order each entry point wants them (merge and partition record no total).
+template <class F> int run_op(gpuq_op* op, OpKind kind, void* stream, F&& body) {
+  static const char* const a_kind[] = {"a filter", "a project", "an aggregate", "a join_build", "a join_probe", "a sort", "a partition"};
+  if (!op) return GPUQ_ERR_INVALID;
+  return guarded(op->ctx, [&]() {
+    check_ctx(op->ctx);
+    if (op->kind != kind) throw std::runtime_error(std::string("not ") + a_kind[kind] + " operator");
+    body(use_stream(stream));
+  });
+}
+
+// Block geometry of a selection over n rows (bitmap -> per-block counts -> scan -> compact): at most 8 blocks per CU, at least 16 words each
+struct SelGeom { i64 nwords, wpb; int nblocks; };
+SelGeom selection_geometry(const gpuq_ctx* ctx, i64 n) {
+  const i64 nwords = (i64)words_of(n), maxb = (i64)ctx->cus * 8;
+  const i64 wpb = std::max<i64>((nwords + maxb - 1) / maxb, 16);
+  return {nwords, wpb, (int)((nwords + wpb - 1) / wpb)};
+}
+
+// Bucket 8-byte (id << 32 | row) records by id: one single-read pass (kernels_sort.hip) per 8 bits of the id, from bit 32 up.  The
+// caller has put the digit counts of the `npass` passes into pass.hist (from the ids, or from counts it has anyway).  The last pass
+// writes the row ids to `ids_out`: last_mode 1 = only those, 2 = the records as well.  Returns where the last pass left its records.
+u64* bucket_records(hipStream_t s, u64* rec, u64* rec2, i64 n, int npass, const PassBufs& pass, uint32_t* ids_out, int last_mode) {
+  for (int p = 0; p < npass; ++p) {
+    const bool last = p + 1 == npass;
+    launch_onesweep_pass(s, rec, nullptr, n, 32 + 8 * p, pass.hist.as<u64>() + (size_t)p * 256, pass.look.p, pass.look_bytes, rec2, last ? ids_out : nullptr, last ? last_mode : 0);
+    std::swap(rec, rec2);
+  }
+  return rec;
+}
 
 }  // namespace
 
@@ -502,7 +562,7 @@ int gpuq_op_output_field(gpuq_op* op, int i, gpuq_field_info* out) {
 }
 int gpuq_op_check(gpuq_op* op, void* stream) {
   if (!op) return GPUQ_ERR_INVALID;
-  return guarded(op->ctx, [&]() { check_ctx(op->ctx); const uint32_t f = read_flags(op, use_stream(stream)); if (f) { reset_flags(op, use_stream(stream)); raise_flags(f); } });
+  return guarded(op->ctx, [&]() { check_ctx(op->ctx); hipStream_t s = use_stream(stream); raise_unless(op, s, read_flags(op, s)); });
 }
 int gpuq_op_set_deferred(gpuq_op* op, int on) { if (!op) return GPUQ_ERR_INVALID; op->deferred = on != 0; op->defer_client = true; return GPUQ_OK; }
 int gpuq_op_can_defer(gpuq_op* op) {
@@ -570,23 +630,16 @@ int gpuq_op_profile_total(gpuq_op* op, float* total_ms_out) {      // of the int
 
 // ---------------------------------------------------------------- filter
 int gpuq_filter_run(gpuq_op* op, void* stream, const gpuq_input* in, int payload_via, uint32_t* sel_out, uint64_t* count_out) {
-  if (!op) return GPUQ_ERR_INVALID;
-  return guarded(op->ctx, [&]() {
-    check_ctx(op->ctx);
-    if (op->kind != K_FILTER) throw std::runtime_error("not a filter operator");
-    hipStream_t s = use_stream(stream);
+  return run_op(op, K_FILTER, stream, [&](hipStream_t s) {
     ProfTotal ptot(op, s);
-    DevProgram P = bind_program(op->prog, op->in_schema, op->code_dev.as<DevCode>(), op->flags_dev.as<uint32_t>(), in);
-    if (payload_via < 0 || payload_via > in->n_via) throw std::runtime_error("payload_via out of range");
+    DevProgram P = bind_input(op, in);
+    check_payload_via(payload_via, in);
     const i64 n = in->n_rows;
     if (n == 0) { if (count_out) HIPCHECK(hipMemsetAsync(count_out, 0, 8, s)); return; }
-    const i64 nwords = (n + 63) >> 6;
-    const i64 maxb = (i64)op->ctx->cus * 8;
-    i64 wpb = (nwords + maxb - 1) / maxb; if (wpb < 16) wpb = 16;
-    const int nblocks = (int)((nwords + wpb - 1) / wpb);
-    u64* bitmap = (u64*)op->ws[0].ensure((size_t)nwords * 8);
-    uint32_t* counts = (uint32_t*)op->ws[1].ensure((size_t)nblocks * 4 + 16);
-    u64* total = count_out ? (u64*)count_out : (u64*)op->ws[2].ensure(8);
+    const auto [nwords, wpb, nblocks] = selection_geometry(op->ctx, n);
+    u64* bitmap = (u64*)op->w_filter.bitmap.ensure((size_t)nwords * 8);
+    uint32_t* counts = (uint32_t*)op->w_filter.counts.ensure((size_t)nblocks * 4 + 16);
+    u64* total = count_out ? (u64*)count_out : (u64*)op->w_filter.total.ensure(8);
     { SinkJit jit(op, op->prog, GPUQ_SINK_FILTER_BITMAP, n); ProfScope ps(op, s); launch_filter_bitmap(s, jit.fn, P, n, bitmap, counts, nblocks, wpb); }
     launch_scan_block_counts(s, counts, nblocks, total);
     if (sel_out) launch_compact(s, bitmap, counts, nblocks, wpb, n, payload_via > 0 ? in->via[payload_via - 1] : nullptr, sel_out);
@@ -596,20 +649,16 @@ int gpuq_filter_run(gpuq_op* op, void* stream, const gpuq_input* in, int payload
 
 // ---------------------------------------------------------------- project
 int gpuq_project_run(gpuq_op* op, void* stream, const gpuq_input* in, gpuq_column* outs, int n_outs) {
-  if (!op) return GPUQ_ERR_INVALID;
-  return guarded(op->ctx, [&]() {
-    check_ctx(op->ctx);
-    if (op->kind != K_PROJECT) throw std::runtime_error("not a project operator");
-    hipStream_t s = use_stream(stream);
+  return run_op(op, K_PROJECT, stream, [&](hipStream_t s) {
     ProfTotal ptot(op, s);
-    DevProgram P = bind_program(op->prog, op->in_schema, op->code_dev.as<DevCode>(), op->flags_dev.as<uint32_t>(), in);
+    DevProgram P = bind_input(op, in);
     OutSpec O = make_outspec(op->prog, outs, n_outs, op->out_fields);
     for (int i = 0; i < n_outs; ++i) outs[i].length = in->n_rows;
     { SinkJit jit(op, op->prog, GPUQ_SINK_PROJECT, in->n_rows); ProfScope ps(op, s); launch_project(s, jit.fn, P, in->n_rows, O); }
     HIPCHECK(hipGetLastError());
     // a projection is otherwise never read back; one that holds checked decimal arithmetic must not hand out a wrapped value (a deferred
     // run's status word is read when it is settled)
-    if (op->prog.checks_overflow && !op->deferred) { const uint32_t f = read_flags(op, s); if (f) { reset_flags(op, s); raise_flags(f); } }
+    if (op->prog.checks_overflow && !op->deferred) raise_unless(op, s, read_flags(op, s));
   });
 }
 
@@ -624,15 +673,11 @@ static u64 agg_slot_pct(const bool from_last_run) {
   return env ? (u64)env : (from_last_run ? 130u : 200u);
 }
 static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, gpuq_column* outs, int n_outs, int64_t cap, int64_t* n_groups_out, const uint64_t** ndev_out) {
-  if (!op) return GPUQ_ERR_INVALID;
   if (ndev_out) *ndev_out = nullptr;
-  return guarded(op->ctx, [&]() {
-    check_ctx(op->ctx);
-    if (op->kind != K_AGG) throw std::runtime_error("not an aggregate operator");
+  return run_op(op, K_AGG, stream, [&](hipStream_t s) {
     if (!op->refuse.empty()) throw Unsupported(op->refuse);
-    hipStream_t s = use_stream(stream);
     ProfTotal ptot(op, s);
-    DevProgram P = bind_program(op->prog, op->in_schema, op->code_dev.as<DevCode>(), op->flags_dev.as<uint32_t>(), in);
+    DevProgram P = bind_input(op, in);
     const i64 n = in->n_rows;
     const int nk = op->agg.n_keys, na = op->agg.n_accs, kstride = nk > 0 ? nk : 1;
     uint32_t ng = 0;
@@ -642,22 +687,22 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
     auto alloc_raw = [&](i64 rcap) {
       raw.cap = (int32_t)rcap;
       if (!Krun.state_key) {      // (a table with state-word keys is extracted into the result columns directly)
-        raw.keys = (u64*)op->ws[0].ensure((size_t)rcap * kstride * 16);
-        raw.key_nulls = (uint32_t*)op->ws[1].ensure((size_t)rcap * 4);
-        raw.cells = (u64*)op->ws[2].ensure((size_t)rcap * na * 16);
+        raw.keys = (u64*)op->w_agg.keys.ensure((size_t)rcap * kstride * 16);
+        raw.key_nulls = (uint32_t*)op->w_agg.key_nulls.ensure((size_t)rcap * 4);
+        raw.cells = (u64*)op->w_agg.cells.ensure((size_t)rcap * na * 16);
       }
-      raw.n_groups = op->flags_dev.as<uint32_t>() + 2;     // next to the flags word: one copy reads both
-      HIPCHECK(hipMemsetAsync(raw.n_groups, 0, 8, s));
+      raw.n_groups = n_groups_dev(op);
+      HIPCHECK(hipMemsetAsync(raw.n_groups, 0, 8, s));      // (the count and its pad: OpStatus)
     };
-    auto read_ng = [&]() { uint32_t v[3] = {0, 0, 0}; read_status(op, s, v, 3); return v[2]; };
+    auto read_ng = [&]() { return read_status(op, s, 3).n_groups; };
     if (n_outs != (int)op->out_fields.size()) throw std::runtime_error("expected " + std::to_string(op->out_fields.size()) + " output columns, got " + std::to_string(n_outs));
     bool posted = false;
     // AoS -> SoA, then the final projection into the caller's typed columns.  rows: host-side bound on the group count;
     // rows_dev (optional): the device word holding the actual count.
     AggSoA soa{}; std::vector<gpuq_column> pcols; bool soa_filled = false;
     auto layout_soa = [&](uint32_t rows, const bool all_valid) {
-      const size_t colbytes = (size_t)std::max<uint32_t>(rows, 1) * 16, vbytes = ((size_t)rows + 63) / 64 * 8 + 8;
-      char* soa_mem = (char*)op->ws[6].ensure((size_t)(nk + na) * colbytes + (size_t)nk * vbytes);
+      const size_t colbytes = (size_t)std::max<uint32_t>(rows, 1) * 16, vbytes = bitmap_bytes(rows);
+      char* soa_mem = (char*)op->w_agg.soa.ensure((size_t)(nk + na) * colbytes + (size_t)nk * vbytes);
       bool any_null = false; for (int k = 0; k < nk; ++k) any_null = any_null || op->keys.sk_null[k];
       if (all_valid && any_null) HIPCHECK(hipMemsetAsync(soa_mem + (size_t)(nk + na) * colbytes, 0xFF, (size_t)nk * vbytes, s));      // (only a NULL key clears a bit)
       soa = AggSoA{};
@@ -680,7 +725,7 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
       gpuq_input pin{}; pin.cols = pcols.data(); pin.n_cols = nk + na; pin.n_rows = rows; pin.n_via = 0;
       for (auto& pc : op->posts) {
         DevProgram PP = bind_program(pc.prog, op->post_schema, pc.code.as<DevCode>(), op->flags_dev.as<uint32_t>(), &pin);
-        PP.n_dev = (const u64*)rows_dev;      // (the 8 bytes at raw.n_groups are zeroed together: the u32 count reads as a u64)
+        PP.n_dev = (const u64*)rows_dev;      // (the u32 count reads as a u64: OpStatus)
         const int no = (int)pc.prog.out_reg.size();
         std::vector<gpuq_field_info> fi(op->out_fields.begin() + pc.first_out, op->out_fields.begin() + pc.first_out + no);
         OutSpec O = make_outspec(pc.prog, outs + pc.first_out, no, fi);
@@ -692,7 +737,7 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
     // LDS dictionary of `gmax` groups (path 1)
     auto launch_tiny = [&](const int gmax, const bool reset) {
       int nb = 0; const size_t wsb = agg_tiny_workspace_bytes(gmax, nk, na, &nb);
-      void* wsp = op->ws[4].ensure(wsb);
+      void* wsp = op->w_agg.tiny.ensure(wsb);
       alloc_raw(64);
       if (reset) reset_flags(op, s);
       // the LDS aggregate is specialised on its whole shape (keys, accumulators, group capacity)
@@ -710,7 +755,7 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
       Krun.key_words = Krun.state_key ? 0 : op->keys.key_words;      // (make_key then builds no key words: the kernel packs the one it needs)
       T.key_words = Krun.state_key ? 0 : op->keys.key_words; T.slot_words = 1 + T.key_words + 2 * na;
       T.n_slots = next_pow2(est * slot_pct / 100);
-      T.slots = (u64*)op->ws[5].ensure((size_t)T.n_slots * T.slot_words * 8);
+      T.slots = (u64*)op->w_agg.table.ensure((size_t)T.n_slots * T.slot_words * 8);
       launch_ht_init(s, T, &op->agg);
       if (reset) reset_flags(op, s);
       if (use_lds) {
@@ -718,7 +763,7 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         int n_fsum = 0; for (int a = 0; a < na; ++a) n_fsum += op->agg.acc_kind[a] == ACC_FSUM;
         u64* fstage = nullptr;
         const size_t fbytes = (size_t)T.n_slots * (size_t)n_fsum * (size_t)agg_lds_grid(n) * 8;
-        if (n_fsum > 0 && fbytes <= ((size_t)256 << 20)) { fstage = (u64*)op->ws[8].ensure(fbytes); HIPCHECK(hipMemsetAsync(fstage, 0, fbytes, s)); }
+        if (n_fsum > 0 && fbytes <= ((size_t)256 << 20)) { fstage = (u64*)op->w_agg.fstage.ensure(fbytes); HIPCHECK(hipMemsetAsync(fstage, 0, fbytes, s)); }
         SinkJit jit(op, op->prog, GPUQ_SINK_AGG_LDS, n); ProfScope ps(op, s); launch_agg_lds(s, jit.fn, P, n, op->keys, op->agg, T, fstage, n_fsum);
       }
       else { SinkJit jit(op, op->prog, GPUQ_SINK_AGG_HASH, n); ProfScope ps(op, s); launch_agg_hash(s, jit.fn, P, n, Krun, op->agg, T); }
@@ -743,29 +788,23 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         int bits = 0; while ((1ull << bits) < nbk) ++bits;
         // 8-byte (bucket << 32 | row) records, bucketed by single-read radix passes (kernels_sort.hip); the last pass also writes the
         // row ids the bucket kernel walks
-        DevBuf b_bid, b_bid2, b_ids, b_hist, b_look, b_bounds;
+        DevBuf b_bid, b_bid2, b_ids; PassBufs pass; DevBuf b_bounds;      // (per run: nothing of it is kept)
         u64* bid = (u64*)b_bid.ensure((size_t)n * 8); u64* bid2 = (u64*)b_bid2.ensure((size_t)n * 8);
         uint32_t* ids = (uint32_t*)b_ids.ensure((size_t)n * 4 + 16);
-        u64* ghist = (u64*)b_hist.ensure((size_t)sort_max_passes() * 256 * 8);
-        const size_t lwb = onesweep_ws_bytes(n);
-        void* lws = b_look.ensure(lwb);
+        u64* ghist = pass.counts();
+        pass.lookback(n);
         uint32_t* bounds = (uint32_t*)b_bounds.ensure((size_t)(nbk + 2) * 4);
         reset_flags(op, s);
         { SinkJit jit(op, op->prog, GPUQ_SINK_AGG_BUCKET_ID, n); launch_agg_bucket_id(s, jit.fn, P, n, op->keys, nbk - 1, bid, nullptr); }
         const int npass = std::max(1, (bits + 7) / 8);
         launch_radix_ghist(s, bid, n, 32, npass, ghist);
-        for (int p = 0; p < npass; ++p) {
-          launch_onesweep_pass(s, bid, nullptr, n, 32 + 8 * p, ghist + (size_t)p * 256, lws, lwb, bid2, ids, p + 1 == npass ? 2 : 0);
-          std::swap(bid, bid2);
-        }
+        bid = bucket_records(s, bid, bid2, n, npass, pass, ids, 2);
         launch_bucket_bounds(s, bid, n, nbk, bounds, 32);
         alloc_raw((i64)std::min<u64>((u64)std::max<i64>(n, 1), std::max<u64>(est + est / 4, 1ull << 20)));
         { SinkJit jit(op, op->prog, GPUQ_SINK_AGG_BUCKET, n); ProfScope ps(op, s); launch_agg_bucket(s, jit.fn, P, op->keys, op->agg, ids, bounds, (uint32_t)nbk, capslots, slot_words, raw); }
         HIPCHECK(hipGetLastError());
-        uint32_t fw[4] = {0, 0, 0, 0};
-        read_status(op, s, fw, 4);
-        if (fw[0] & ~(FLAG_TABLE_FULL | FLAG_GROUP_OVERFLOW)) { reset_flags(op, s); raise_flags(fw[0] & ~(FLAG_TABLE_FULL | FLAG_GROUP_OVERFLOW)); }
-        if (!(fw[0] & (FLAG_TABLE_FULL | FLAG_GROUP_OVERFLOW))) { ng = fw[2]; return true; }
+        const OpStatus st = read_status(op, s);
+        if (!raise_unless(op, s, st.flags, FLAG_TABLE_FULL | FLAG_GROUP_OVERFLOW)) { ng = st.n_groups; return true; }
         if (strat == "radix" && op->expected_groups > 0 && est < (u64)n) throw Capacity("radix aggregate: a bucket overflowed; raise expected_groups or use strategy hash/auto");
         reset_flags(op, s);
       } else if (strat == "radix") throw Unsupported("radix aggregate: the group state does not fit an LDS table");
@@ -817,7 +856,7 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
       // bits), 20-40 us against the milliseconds a wrong strategy costs
       const i64 nsample = 1ll << 20, stride = std::max<i64>(1, n / nsample);
       const u64 nbits = 1ull << 24;
-      uint32_t* bm = (uint32_t*)op->ws[7].ensure(nbits / 8 + 64);
+      uint32_t* bm = (uint32_t*)op->w_agg.sample.ensure(nbits / 8 + 64);
       unsigned long long* cnt = (unsigned long long*)((char*)bm + nbits / 8);
       HIPCHECK(hipMemsetAsync(bm, 0, nbits / 8 + 64, s));
       launch_key_sample(s, P, n, op->keys, stride, nsample, bm, nbits, cnt + 1);
@@ -852,11 +891,8 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
           // count on the device): one host round trip per aggregate instead of two.  An overflowing try is simply redone.
           const bool ahead = (i64)raw.cap <= cap;
           if (ahead) run_post((uint32_t)raw.cap, raw.n_groups);
-          uint32_t fw[4] = {0, 0, 0, 0};
-          read_status(op, s, fw, 4);
-          const uint32_t f = fw[0];
-          if (f & ~FLAG_GROUP_OVERFLOW) { reset_flags(op, s); raise_flags(f & ~FLAG_GROUP_OVERFLOW); }
-          if (!(f & FLAG_GROUP_OVERFLOW)) { ng = fw[2]; done = true; posted = ahead; path_done = 1; gmax_done = gmax; break; }
+          const OpStatus st = read_status(op, s);
+          if (!raise_unless(op, s, st.flags, FLAG_GROUP_OVERFLOW)) { ng = st.n_groups; done = true; posted = ahead; path_done = 1; gmax_done = gmax; break; }
         }
         if (!done && strat == "tiny") throw Capacity("more groups than the LDS aggregate holds; use strategy hash/auto");
       }
@@ -885,7 +921,7 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         HIPCHECK(hipGetLastError());
         const uint32_t f = (n <= (1ll << 20) && est >= (u64)n) ? 0u : read_flags(op, s);   // a 2n-slot table cannot fill up; other flags surface after extract
         if (f & FLAG_TABLE_FULL) { if (est >= (u64)std::max<i64>(n, 1024)) throw std::runtime_error("hash aggregate: table full at maximum size"); est = std::min<u64>(est * 4, (u64)std::max<i64>(n, 1024)); continue; }
-        if (f) { reset_flags(op, s); raise_flags(f); }
+        raise_unless(op, s, f);
         break;
       }
       path_done = 2; est_done = est; lds_done = use_lds;
@@ -898,10 +934,9 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         // the device) when the caller's columns can hold any outcome -- one host round trip instead of two
         const bool ahead = (i64)raw.cap <= cap;
         if (ahead) run_post((uint32_t)raw.cap, raw.n_groups);
-        uint32_t fw[4] = {0, 0, 0, 0};
-        read_status(op, s, fw, 4);
-        if (fw[0]) { reset_flags(op, s); raise_flags(fw[0]); }
-        ng = fw[2];
+        const OpStatus st = read_status(op, s);
+        raise_unless(op, s, st.flags);
+        ng = st.n_groups;
         posted = ahead;
       } else {
         // Size the raw result from what this operator produced last time (the partitions of a stage, or the same query again,
@@ -911,11 +946,9 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
           alloc_raw(L.ag.groups + L.ag.groups / 4 + 1024);
           extract();
           HIPCHECK(hipGetLastError());
-          uint32_t fw[4] = {0, 0, 0, 0};
-          read_status(op, s, fw, 4);
-          ng = fw[2];
-          if (fw[0] & ~FLAG_GROUP_OVERFLOW) { reset_flags(op, s); raise_flags(fw[0]); }
-          done = !(fw[0] & FLAG_GROUP_OVERFLOW);
+          const OpStatus st = read_status(op, s);
+          ng = st.n_groups;
+          done = !raise_unless(op, s, st.flags, FLAG_GROUP_OVERFLOW);
           if (!done) { reset_flags(op, s); HIPCHECK(hipMemsetAsync(raw.n_groups, 0, 4, s)); }
         } else {
           alloc_raw(1);
@@ -958,9 +991,9 @@ namespace {
 // Do neighbouring probe rows hit neighbouring table entries?  A strided sample of 64-row words; "local" when most adjacent
 // pairs of live rows are within 2^14 entries (64 KiB of table) of each other -- clustered / sorted foreign keys.
 bool probe_keys_local(gpuq_op* op, hipStream_t s, const DevProgram& P, i64 n, const HashTable& T) {
-  u64* c = (u64*)op->ws[7].ensure(32);
+  u64* c = (u64*)op->w_probe.locality.ensure(32);
   HIPCHECK(hipMemsetAsync(c, 0, 16, s));
-  const i64 nwords = (n + 63) >> 6;
+  const i64 nwords = (i64)words_of(n);
   const i64 nsample = std::min<i64>(nwords, 4096);
   launch_join_locality(s, P, n, op->keys, T, nwords / nsample, nsample, c);
   HIPCHECK(hipGetLastError());
@@ -972,13 +1005,9 @@ bool probe_keys_local(gpuq_op* op, hipStream_t s, const DevProgram& P, i64 n, co
 }  // namespace
 static int join_build_impl(gpuq_op* op, void* stream, const gpuq_input* in, int payload_via, int64_t build_rows_bound, gpuq_join_table* semi_table,
                            uint32_t* semi_hits_out, uint64_t* rows_out, gpuq_join_table** out) {
-  if (!op) return GPUQ_ERR_INVALID;
   gpuq_join_table* t = nullptr;
-  int rc = guarded(op->ctx, [&]() {
-    check_ctx(op->ctx);
-    if (op->kind != K_JOIN_BUILD) throw std::runtime_error("not a join_build operator");
+  int rc = run_op(op, K_JOIN_BUILD, stream, [&](hipStream_t s) {
     if (!out) throw std::runtime_error("out is NULL");
-    hipStream_t s = use_stream(stream);
     ProfTotal ptot(op, s);
     SemiProbe semi{}; const SemiProbe* semi_p = nullptr;
     if (semi_table) {
@@ -990,8 +1019,8 @@ static int join_build_impl(gpuq_op* op, void* stream, const gpuq_input* in, int 
       semi.T = semi_table->T; semi.K = op->semi_keys; semi.null_eq = semi_table->null_eq; semi.on = 1; semi.hit_out = semi_hits_out; semi.rows_out = (u64*)rows_out;
       semi_p = &semi;
     } else if (op->has_semi) throw std::runtime_error("join build: this operator was compiled with \"semi_on\" keys: call gpuq_join_build_run_semi");
-    DevProgram P = bind_program(op->prog, op->in_schema, op->code_dev.as<DevCode>(), op->flags_dev.as<uint32_t>(), in);
-    if (payload_via < 0 || payload_via > in->n_via) throw std::runtime_error("payload_via out of range");
+    DevProgram P = bind_input(op, in);
+    check_payload_via(payload_via, in);
     const i64 n = in->n_rows;
     if (build_rows_bound < n && payload_via == 0) build_rows_bound = n;
     if (build_rows_bound < 0 || build_rows_bound > 0xFFFFFFFEll) throw std::runtime_error("build_rows_bound out of range");
@@ -1029,9 +1058,9 @@ static int join_build_impl(gpuq_op* op, void* stream, const gpuq_input* in, int 
     bool dense = false, sparse_bits = false; i64 kmin = 0; u64 krange = 0;
     if (memo) { dense = jb.dense; sparse_bits = jb.sparse_bits; kmin = jb.kmin; krange = jb.krange; }
     else if (narrow_key) {
-      u64* kr = (u64*)op->ws[0].ensure(32);
+      u64* kr = (u64*)op->w_build.key_range.ensure(32);
       const u64 init[3] = {0x7FFFFFFFFFFFFFFFull, 0x8000000000000000ull, 0};
-      const i64 wstep = guess ? std::max<i64>(1, ((n + 63) >> 6) >> 12) : 1;
+      const i64 wstep = guess ? std::max<i64>(1, (i64)words_of(n) >> 12) : 1;
       HIPCHECK(hipMemcpyAsync(kr, init, sizeof(init), hipMemcpyHostToDevice, s));
       { SinkJit jit(op, op->prog, GPUQ_SINK_JOIN_KEYRANGE, n); launch_join_keyrange(s, jit.fn, P, n, op->keys, op->null_eq, kr, wstep); }
       HIPCHECK(hipGetLastError());
@@ -1059,7 +1088,7 @@ static int join_build_impl(gpuq_op* op, void* stream, const gpuq_input* in, int 
       t->T.n_slots = 0; t->T.slots = nullptr;
       t->T.dense = (uint32_t*)t->dense.ensure((size_t)krange * 4 + 16); t->T.dense_min = kmin; t->T.dense_range = krange;
       if (sparse_bits) {
-        const size_t bb = ((size_t)krange + 63) / 64 * 8 + 8;
+        const size_t bb = bitmap_bytes((int64_t)krange);
         t->T.dense_bits = (uint32_t*)t->dense_bits.ensure(bb);
         HIPCHECK(hipMemsetAsync(t->T.dense_bits, 0, bb, s));
       } else HIPCHECK(hipMemsetAsync(t->T.dense, 0xFF, (size_t)krange * 4, s));
@@ -1069,7 +1098,7 @@ static int join_build_impl(gpuq_op* op, void* stream, const gpuq_input* in, int 
     }
     // unique keys remembered: no chain array (a duplicate raises the status word and the run is redone with one)
     uint32_t* next = (!memo || jb.has_dups) ? (uint32_t*)t->next.ensure((size_t)std::max<i64>(build_rows_bound, 1) * 4) : nullptr;
-    const size_t bm = ((size_t)build_rows_bound + 63) / 64 * 8 + 8;
+    const size_t bm = bitmap_bytes(build_rows_bound);
     // `present` (which build rows passed the side's predicate) only serves gpuq_join_build_side_rows: a build whose descriptor says
     // "build_side_rows": false (Inner / Right / RightSemi / RightAnti joins) skips it -- one device-scope atomic per row less when
     // the rows come through an index vector (SF100 q3: 14.6 M of them)
@@ -1095,7 +1124,7 @@ static int join_build_impl(gpuq_op* op, void* stream, const gpuq_input* in, int 
       build();
       f = read_flags(op, s);
     }
-    if (f & ~FLAG_DUP_BUILD_KEY) { reset_flags(op, s); raise_flags(f & ~FLAG_DUP_BUILD_KEY); }
+    f = raise_unless(op, s, f, FLAG_DUP_BUILD_KEY);
     if (f) reset_flags(op, s);
     t->has_dups = (f & FLAG_DUP_BUILD_KEY) != 0;
     // what a deferred run goes by next time (a guessed range is remembered widened, as it was used)
@@ -1127,24 +1156,20 @@ void gpuq_join_table_free(gpuq_join_table* t) { delete t; }
 
 int gpuq_join_probe_run(gpuq_op* op, void* stream, gpuq_join_table* t, const gpuq_input* in, int payload_via, uint32_t* out_build,
                         uint32_t* out_probe, uint64_t out_cap, uint64_t* count_out) {
-  if (!op) return GPUQ_ERR_INVALID;
-  return guarded(op->ctx, [&]() {
-    check_ctx(op->ctx);
-    if (op->kind != K_JOIN_PROBE) throw std::runtime_error("not a join_probe operator");
+  return run_op(op, K_JOIN_PROBE, stream, [&](hipStream_t s) {
     if (!t || !count_out) throw std::runtime_error("table/count_out is NULL");
     if (op->keys.n_keys != t->keys.n_keys || op->keys.key_words != t->keys.key_words) throw std::runtime_error("probe keys do not match the build keys (count / width)");
     for (int k = 0; k < op->keys.n_keys; ++k) if (op->keys.key_wide[k] != t->keys.key_wide[k]) throw std::runtime_error("probe key " + std::to_string(k) + " width class differs from the build key; cast one side");
-    hipStream_t s = use_stream(stream);
     ProfTotal ptot(op, s);
-    DevProgram P = bind_program(op->prog, op->in_schema, op->code_dev.as<DevCode>(), op->flags_dev.as<uint32_t>(), in);
-    if (payload_via < 0 || payload_via > in->n_via) throw std::runtime_error("payload_via out of range");
+    DevProgram P = bind_input(op, in);
+    check_payload_via(payload_via, in);
     const int jt = op->join_type;
     const bool need_pairs = (jt == JT_INNER || jt == JT_LEFT || jt == JT_RIGHT || jt == JT_FULL);
     if (need_pairs && (!out_build || !out_probe) && out_cap > 0) throw std::runtime_error("pair outputs are NULL");
     if ((jt == JT_RIGHT_SEMI || jt == JT_RIGHT_ANTI) && !out_probe && out_cap > 0) throw std::runtime_error("out_probe is NULL");
     uint32_t* visited = nullptr;
     if (jt == JT_LEFT || jt == JT_FULL || jt == JT_LEFT_SEMI || jt == JT_LEFT_ANTI) {
-      const size_t bm = ((size_t)t->bound + 63) / 64 * 8 + 8;
+      const size_t bm = bitmap_bytes(t->bound);
       visited = (uint32_t*)t->visited.ensure(bm);
       if (!t->visited_ready) { HIPCHECK(hipMemsetAsync(visited, 0, bm, s)); t->visited_ready = true; }
     }
@@ -1152,7 +1177,7 @@ int gpuq_join_probe_run(gpuq_op* op, void* stream, gpuq_join_table* t, const gpu
       // unique build keys: atomic-free two-pass probe, output in probe order
       const i64 n = in->n_rows;
       if (n == 0) { HIPCHECK(hipMemsetAsync(count_out, 0, 8, s)); return; }
-      const i64 nwords = (n + 63) >> 6;
+      const i64 nwords = (i64)words_of(n);
       // segments: one wave each, small enough that the scheduler evens out waves that finish early (>= 32 segments per resident
       // wave slot would be wasted scan work; 4 per slot keeps the tail short)
       const i64 target = (i64)op->ctx->cus * 8 * 4 * 4;
@@ -1160,9 +1185,9 @@ int gpuq_join_probe_run(gpuq_op* op, void* stream, gpuq_join_table* t, const gpu
       wpw = (wpw + 3) & ~(i64)3;
       const int nsegs = (int)((nwords + wpw - 1) / wpw);
       const bool want_build = out_build != nullptr;
-      uint32_t* seg_build = want_build ? (uint32_t*)op->ws[0].ensure((size_t)nwords * 256 + 16) : nullptr;
-      uint32_t* seg_probe = (uint32_t*)op->ws[1].ensure((size_t)nwords * 256 + 16);
-      uint32_t* counts = (uint32_t*)op->ws[2].ensure((size_t)nsegs * 4 + 16);
+      uint32_t* seg_build = want_build ? (uint32_t*)op->w_probe.seg_build.ensure((size_t)nwords * 256 + 16) : nullptr;
+      uint32_t* seg_probe = (uint32_t*)op->w_probe.seg_probe.ensure((size_t)nwords * 256 + 16);
+      uint32_t* counts = (uint32_t*)op->w_probe.counts.ensure((size_t)nsegs * 4 + 16);
       // Partitioned probe (kernels_hash.hip): pays when the table is beyond the caches AND the probe keys arrive in random
       // order; the pairs then come out in partition order, so whatever reads probe-side columns through them gathers at random
       // -- "auto" therefore asks for a big table, a big probe side and keys without locality (sampled), "force" is for measurements.
@@ -1171,15 +1196,15 @@ int gpuq_join_probe_run(gpuq_op* op, void* stream, gpuq_join_table* t, const gpu
       if (use_rj && rjm == 1) use_rj = n >= (1ll << 24) && t->T.dense_range * 4 >= ((u64)64 << 20) && !probe_keys_local(op, s, P, n, t->T);
       if (use_rj) {
         RjGeomHost g; rj_geometry(n, t->T.dense_range, op->ctx->join_radix_slice_log2, &g);
-        u64* rec = (u64*)op->ws[3].ensure((size_t)n * 8 + 16);
-        u64* rec2 = (u64*)op->ws[4].ensure((size_t)n * 8 + 16);
-        int32_t* hist = (int32_t*)op->ws[5].ensure(rj_hist_entries(g) * 4 + 16);
+        u64* rec = (u64*)op->w_probe.rec.ensure((size_t)n * 8 + 16);
+        u64* rec2 = (u64*)op->w_probe.rec2.ensure((size_t)n * 8 + 16);
+        int32_t* hist = (int32_t*)op->w_probe.hist.ensure(rj_hist_entries(g) * 4 + 16);
         const size_t swb = exclusive_scan_ws_bytes((i64)rj_hist_entries(g));
-        void* sws = op->ws[6].ensure(swb);
+        void* sws = op->w_probe.scan.ensure(swb);
         i64 rwpw = 0; const int rblocks = rj_probe_geometry(n, &rwpw); const int rsegs = rblocks * 4;
-        if (want_build) seg_build = (uint32_t*)op->ws[0].ensure((size_t)rsegs * rwpw * 256 + 16);
-        seg_probe = (uint32_t*)op->ws[1].ensure((size_t)rsegs * rwpw * 256 + 16);
-        counts = (uint32_t*)op->ws[2].ensure((size_t)rsegs * 4 + 16);
+        if (want_build) seg_build = (uint32_t*)op->w_probe.seg_build.ensure((size_t)rsegs * rwpw * 256 + 16);
+        seg_probe = (uint32_t*)op->w_probe.seg_probe.ensure((size_t)rsegs * rwpw * 256 + 16);
+        counts = (uint32_t*)op->w_probe.counts.ensure((size_t)rsegs * 4 + 16);
         SinkJit jit(op, op->prog, GPUQ_SINK_RJ_PACK, n); ProfScope ps(op, s);
         launch_rj_partition(s, jit.fn, P, n, op->keys, t->T, payload_via, g, rec, rec2, hist, sws, swb);
         launch_rj_probe(s, rec2, hist + (size_t)g.nparts * g.nblocks, t->T, jt, seg_build, seg_probe, counts, rblocks, rwpw);
@@ -1215,12 +1240,9 @@ int gpuq_join_build_side_rows(gpuq_join_table* t, void* stream, int matched, uin
     const i64 n = t->bound;
     if (!t->has_present) throw std::runtime_error("this join table was built with \"build_side_rows\": false: it does not know its build side's rows");
     if (n == 0) { if (count_out) HIPCHECK(hipMemsetAsync(count_out, 0, 8, s)); return; }
-    const size_t bm = ((size_t)n + 63) / 64 * 8 + 8;
+    const size_t bm = bitmap_bytes(n);
     if (!t->visited_ready) { HIPCHECK(hipMemsetAsync(t->visited.ensure(bm), 0, bm, s)); t->visited_ready = true; }
-    const i64 nwords = (n + 63) >> 6;
-    const i64 maxb = (i64)t->ctx->cus * 8;
-    i64 wpb = (nwords + maxb - 1) / maxb; if (wpb < 16) wpb = 16;
-    const int nblocks = (int)((nwords + wpb - 1) / wpb);
+    const auto [nwords, wpb, nblocks] = selection_geometry(t->ctx, n);
     u64* bitmap = (u64*)t->ws_bitmap.ensure((size_t)nwords * 8);
     uint32_t* counts = (uint32_t*)t->ws_counts.ensure((size_t)nblocks * 4 + 16 + 8);
     u64* total = count_out ? (u64*)count_out : (u64*)((char*)counts + (size_t)nblocks * 4 + 8 - ((size_t)nblocks * 4) % 8);
@@ -1241,9 +1263,9 @@ static int bitlen128(u128 v) { int b = 0; while (v) { ++b; v >>= 1; } return b; 
 // sides if that is free, by 1/4096 if not, and always spread over the whole 2^bits its width has anyway.
 static SortPack sort_key_plan(gpuq_op* op, hipStream_t s, const DevProgram& P, i64 n, int* total_out, i64 wstep = 1) {
     const SortSpec& S = op->sort;
-    const i64 n_seen = wstep > 1 ? ((((n + 63) >> 6) + wstep - 1) / wstep + 1) << 6 : n;
+    const i64 n_seen = wstep > 1 ? (((i64)words_of(n) + wstep - 1) / wstep + 1) << 6 : n;
     const int mb = sort_minmax_blocks(n_seen);
-    u64* mm = (u64*)op->ws[0].ensure((size_t)mb * MAX_SORT_KEYS * 5 * 8);
+    u64* mm = (u64*)op->w_sort.blocks.ensure((size_t)mb * MAX_SORT_KEYS * 5 * 8);
     { SinkJit jit(op, op->prog, GPUQ_SINK_SORT_MINMAX, n); launch_sort_minmax(s, jit.fn, P, n, S, mm, mb, wstep); }
     std::vector<u64> hmm((size_t)mb * MAX_SORT_KEYS * 5);
     HIPCHECK(hipMemcpyAsync(hmm.data(), mm, hmm.size() * 8, hipMemcpyDeviceToHost, s));
@@ -1252,7 +1274,7 @@ static SortPack sort_key_plan(gpuq_op* op, hipStream_t s, const DevProgram& P, i
     uint32_t eflags = 0;
     HIPCHECK(hipMemcpyAsync(&eflags, op->flags_dev.p, 4, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
-    if (eflags) { reset_flags(op, s); raise_flags(eflags); }
+    raise_unless(op, s, eflags);
     const i128 I128_MAX = ((i128)0x7FFFFFFFFFFFFFFFll << 64) | (i128)0xFFFFFFFFFFFFFFFFull, I128_MIN = -I128_MAX - 1;
     i128 mn[MAX_SORT_KEYS], mx[MAX_SORT_KEYS]; u64 fl[MAX_SORT_KEYS] = {0, 0, 0, 0}; int rshift[MAX_SORT_KEYS] = {0, 0, 0, 0};
     for (int k = 0; k < S.n_keys; ++k) {
@@ -1323,16 +1345,12 @@ int gpuq_sort_run_keys(gpuq_op* op, void* stream, const gpuq_input* in, uint32_t
   return rc;
 }
 int gpuq_sort_run(gpuq_op* op, void* stream, const gpuq_input* in, uint32_t* perm_out) {
-  if (!op) return GPUQ_ERR_INVALID;
-  return guarded(op->ctx, [&]() {
-    check_ctx(op->ctx);
-    if (op->kind != K_SORT) throw std::runtime_error("not a sort operator");
-    hipStream_t s = use_stream(stream);
+  return run_op(op, K_SORT, stream, [&](hipStream_t s) {
     ProfTotal ptot(op, s);
-    DevProgram P = bind_program(op->prog, op->in_schema, op->code_dev.as<DevCode>(), op->flags_dev.as<uint32_t>(), in);
+    DevProgram P = bind_input(op, in);
     const i64 n = in->n_rows;
     if (n == 0) return;
-    if (n >= (1ll << 31)) throw Unsupported("sort of >= 2^31 rows in one call");
+    check_row_limit(n, "sort");
     if (!perm_out) throw std::runtime_error("perm_out is NULL");
     const SortSpec& S = op->sort;
     bool string_key = false;
@@ -1342,7 +1360,7 @@ int gpuq_sort_run(gpuq_op* op, void* stream, const gpuq_input* in, uint32_t* per
       HIPCHECK(hipGetLastError());
       if (op->deferred) return;      // (the status word is read by gpuq_ops_settle)
       if (in->n_rows_dev) throw std::runtime_error("sort: a device-side row count needs a deferred operator (gpuq_op_set_deferred)");
-      if (string_key) { const uint32_t f = read_flags(op, s); if (f) { reset_flags(op, s); raise_flags(f); } }      // a value beyond 15 bytes: refuse, do not sort by a prefix
+      if (string_key) raise_unless(op, s, read_flags(op, s));      // a value beyond 15 bytes: refuse, do not sort by a prefix
       // a client that defers (gpuq_op_set_deferred was called on this operator) will come back with a BOUND instead of a count, and
       // the bound of a handful of groups is easily beyond what one block sorts: learn the key layout now, while reading back is allowed
       if (op->defer_client) { int total = 0; const SortPack K = sort_key_plan(op, s, P, n, &total); op->learned.so = {true, K, total}; op->learned.expect_flags = 0; }
@@ -1366,15 +1384,15 @@ int gpuq_sort_run(gpuq_op* op, void* stream, const gpuq_input* in, uint32_t* per
     bool spec = spec_on && n >= (1ll << 22) && !op->learned.sort_guess_failed;
     for (int k = 0; k < S.n_keys; ++k) if (S.kind[k] == 2) spec = false;
     if (spec) {
-      const i64 wstep = std::max<i64>(1, ((n + 63) >> 6) >> 12);      // ~4096 words of 64 rows
+      const i64 wstep = std::max<i64>(1, (i64)words_of(n) >> 12);      // ~4096 words of 64 rows
       const SortPack G = sort_key_plan(op, s, P, n, &total, wstep);
       if (total > 0) {      // (no key bits: the pack kernel takes no counts and has nowhere to report to)
         sort_with_plan(op, s, P, n, G, total, perm_out);
         u64 failed = 0; uint32_t eflags = 0;
-        HIPCHECK(hipMemcpyAsync(&failed, (const u64*)op->ws[6].p + (size_t)sort_max_passes() * 256, 8, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipMemcpyAsync(&failed, op->w_sort.pass.guess_word(), 8, hipMemcpyDeviceToHost, s));
         HIPCHECK(hipMemcpyAsync(&eflags, op->flags_dev.p, 4, hipMemcpyDeviceToHost, s));      // the pack kernel evaluated every row
         HIPCHECK(hipStreamSynchronize(s));
-        if (eflags) { reset_flags(op, s); raise_flags(eflags); }
+        raise_unless(op, s, eflags);
         if (!failed) { op->learned.so = {true, G, total}; op->learned.expect_flags = 0; return; }
         op->learned.sort_guess_failed = true;
       }
@@ -1392,15 +1410,16 @@ static void sort_with_plan(gpuq_op* op, hipStream_t s, const DevProgram& P, cons
     const SortSpec& S = op->sort;
     // 2. pack + LSD radix passes.  <= 32 key bits: one u64 (key << 32 | row) record per row, no separate id array.
     const bool packed = total >= 1 && total <= 32 && n > sort_small_max();
-    u64* klo = (u64*)op->ws[1].ensure((size_t)n * 8);
-    u64* klo2 = (u64*)op->ws[2].ensure((size_t)n * 8);
-    u64* khi = total > 64 ? (u64*)op->ws[3].ensure((size_t)n * 8) : nullptr;
-    uint32_t* ids = packed ? nullptr : (uint32_t*)op->ws[4].ensure((size_t)n * 4);
-    uint32_t* ids2 = packed ? nullptr : (uint32_t*)op->ws[5].ensure((size_t)n * 4);
+    auto& W = op->w_sort;
+    u64* klo = (u64*)W.klo.ensure((size_t)n * 8);
+    u64* klo2 = (u64*)W.klo2.ensure((size_t)n * 8);
+    u64* khi = total > 64 ? (u64*)W.khi.ensure((size_t)n * 8) : nullptr;
+    uint32_t* ids = packed ? nullptr : (uint32_t*)W.ids.ensure((size_t)n * 4);
+    uint32_t* ids2 = packed ? nullptr : (uint32_t*)W.ids2.ensure((size_t)n * 4);
     ProfScope ps(op, s);
     // digit counts of every pass (256 u64 each), taken by the pack kernel on the way
     const int np_all = (total + 7) / 8;
-    u64* ghist = (u64*)op->ws[6].ensure(((size_t)sort_max_passes() * 256 + 1) * 8);      // + the "guessed layout does not hold" word
+    u64* ghist = W.pass.counts(true);      // + the "guessed layout does not hold" word
     const bool small = n <= sort_small_max();
     // gpuq_sort_run_keys: one integer-like key whose field IS value - base (no string shift), at most one 64-bit word of composite
     const int dec_width = (op->sort_dec.data && S.n_keys == 1 && S.kind[0] == 0 && K.rshift[0] == 0 && total >= 1 && total <= 64 && !small) ? type_width(op->sort_key0) : 0;
@@ -1412,8 +1431,7 @@ static void sort_with_plan(gpuq_op* op, hipStream_t s, const DevProgram& P, cons
       return;
     }
     // single-read passes (kernels_sort.hip): one look-back kernel per 8 key bits, the last one writes the row ids straight into perm_out
-    const size_t lwb = onesweep_ws_bytes(n);
-    void* lws = op->ws[7].ensure(lwb);
+    void* lws = W.pass.lookback(n); const size_t lwb = W.pass.look_bytes;
     auto run_passes = [&](int bits, int shift0, int pass0, bool last_word) {
       const int np = (bits + 7) / 8;
       if (np == 0) { if (last_word) HIPCHECK(hipMemcpyAsync(perm_out, ids, (size_t)n * 4, hipMemcpyDeviceToDevice, s)); return; }
@@ -1443,20 +1461,16 @@ static void sort_with_plan(gpuq_op* op, hipStream_t s, const DevProgram& P, cons
 
 // ---------------------------------------------------------------- ordered fan-in
 int gpuq_merge_run(gpuq_op* op, void* stream, const gpuq_input* in, const int64_t* run_offsets, int n_runs, uint32_t* perm_out) {
-  if (!op) return GPUQ_ERR_INVALID;
-  return guarded(op->ctx, [&]() {
-    check_ctx(op->ctx);
-    if (op->kind != K_SORT) throw std::runtime_error("not a sort operator");
+  return run_op(op, K_SORT, stream, [&](hipStream_t s) {
     if (!run_offsets || n_runs < 1) throw std::runtime_error("run_offsets is NULL / no runs");
-    hipStream_t s = use_stream(stream);
     need_exact_rows(in, "merge");
     const i64 n = in->n_rows;
     if (run_offsets[0] != 0 || run_offsets[n_runs] != n) throw std::runtime_error("run_offsets must start at 0 and end at the row count");
     for (int r = 0; r < n_runs; ++r) if (run_offsets[r] > run_offsets[r + 1]) throw std::runtime_error("run_offsets must not decrease");
     if (n == 0) return;
-    if (n >= (1ll << 31)) throw Unsupported("merge of >= 2^31 rows in one call");
+    check_row_limit(n, "merge");
     if (!perm_out) throw std::runtime_error("perm_out is NULL");
-    DevProgram P = bind_program(op->prog, op->in_schema, op->code_dev.as<DevCode>(), op->flags_dev.as<uint32_t>(), in);
+    DevProgram P = bind_input(op, in);
     int total = 0;
     const SortPack K = sort_key_plan(op, s, P, n, &total);
     // Rounds or passes?  Both give the same permutation (the stable sort of the concatenation IS the merge that prefers the lower
@@ -1470,18 +1484,19 @@ int gpuq_merge_run(gpuq_op* op, void* stream, const gpuq_input* in, const int64_
       static const bool force_rounds = []() { const char* e = std::getenv("GPUQ_MERGE_ROUNDS"); return e && std::string(e) == "force"; }();      // measurement switch
       if (live > 1 && est_passes < est_merge && !force_rounds) { sort_with_plan(op, s, P, n, K, total, perm_out); return; }
     }
-    u64* klo = (u64*)op->ws[1].ensure((size_t)n * 8);
-    u64* klo2 = (u64*)op->ws[2].ensure((size_t)n * 8);
-    u64* khi = total > 64 ? (u64*)op->ws[3].ensure((size_t)n * 8) : nullptr;
-    u64* khi2 = total > 64 ? (u64*)op->ws[8].ensure((size_t)n * 8) : nullptr;
-    uint32_t* ids = (uint32_t*)op->ws[4].ensure((size_t)n * 4);
-    uint32_t* ids2 = (uint32_t*)op->ws[5].ensure((size_t)n * 4);
+    auto& W = op->w_sort;
+    u64* klo = (u64*)W.klo.ensure((size_t)n * 8);
+    u64* klo2 = (u64*)W.klo2.ensure((size_t)n * 8);
+    u64* khi = total > 64 ? (u64*)W.khi.ensure((size_t)n * 8) : nullptr;
+    u64* khi2 = total > 64 ? (u64*)W.khi2.ensure((size_t)n * 8) : nullptr;
+    uint32_t* ids = (uint32_t*)W.ids.ensure((size_t)n * 4);
+    uint32_t* ids2 = (uint32_t*)W.ids2.ensure((size_t)n * 4);
     ProfScope ps(op, s);
     { SinkJit jit(op, op->prog, GPUQ_SINK_SORT_PACK, n); launch_sort_pack(s, jit.fn, P, n, op->sort, K, klo, khi, ids, nullptr, 0); }
     // runs -> pairs, round by round (empty runs drop out; an odd run is carried as a pair with an empty right side)
     std::vector<i64> bounds; bounds.push_back(0);
     for (int r = 0; r < n_runs; ++r) if (run_offsets[r + 1] > run_offsets[r]) bounds.push_back(run_offsets[r + 1]);
-    i64* dpairs = (i64*)op->ws[9].ensure((size_t)(bounds.size() + 2) * 3 * 8);
+    i64* dpairs = (i64*)W.pairs.ensure((size_t)(bounds.size() + 2) * 3 * 8);
     while (bounds.size() > 2) {
       std::vector<i64> pairs, next; next.push_back(0); i64 max_len = 0;
       for (size_t r = 0; r + 1 < bounds.size(); r += 2) {
@@ -1492,7 +1507,7 @@ int gpuq_merge_run(gpuq_op* op, void* stream, const gpuq_input* in, const int64_
       HIPCHECK(hipStreamSynchronize(s));      // the previous round has read its descriptors
       HIPCHECK(hipMemcpyAsync(dpairs, pairs.data(), pairs.size() * 8, hipMemcpyHostToDevice, s));
       HIPCHECK(hipStreamSynchronize(s));      // (pageable source)
-      i64* splits = (i64*)op->ws[0].ensure(merge_splits_entries(max_len, (int)(pairs.size() / 3)) * 8 + 64);
+      i64* splits = (i64*)W.blocks.ensure(merge_splits_entries(max_len, (int)(pairs.size() / 3)) * 8 + 64);
       launch_merge_pairs(s, klo, khi, ids, dpairs, (int)(pairs.size() / 3), max_len, splits, klo2, khi2, ids2);
       std::swap(klo, klo2); std::swap(khi, khi2); std::swap(ids, ids2);
       bounds.swap(next);
@@ -1504,27 +1519,23 @@ int gpuq_merge_run(gpuq_op* op, void* stream, const gpuq_input* in, const int64_
 
 // ---------------------------------------------------------------- partition
 int gpuq_partition_run(gpuq_op* op, void* stream, const gpuq_input* in, uint32_t* perm_out, uint64_t* part_offsets_out) {
-  if (!op) return GPUQ_ERR_INVALID;
-  return guarded(op->ctx, [&]() {
-    check_ctx(op->ctx);
-    if (op->kind != K_PARTITION) throw std::runtime_error("not a partition operator");
+  return run_op(op, K_PARTITION, stream, [&](hipStream_t s) {
     need_exact_rows(in, "partition");
-    hipStream_t s = use_stream(stream);
-    DevProgram P = bind_program(op->prog, op->in_schema, op->code_dev.as<DevCode>(), op->flags_dev.as<uint32_t>(), in);
+    DevProgram P = bind_input(op, in);
     const i64 n = in->n_rows;
     const uint32_t np = op->nparts;
     if (!part_offsets_out) throw std::runtime_error("part_offsets_out is NULL");
     if (n == 0) { HIPCHECK(hipMemsetAsync(part_offsets_out, 0, (size_t)(np + 1) * 8, s)); return; }
-    if (n >= (1ll << 31)) throw Unsupported("partition of >= 2^31 rows in one call");
+    check_row_limit(n, "partition");
     if (!perm_out) throw std::runtime_error("perm_out is NULL");
     // one 8-byte (partition << 32 | row) record per row; the partition sizes double as the digit counts of the single-read pass
     // (<= 256 partitions: one pass that reads 8 and writes 4 bytes per row; more: one pass per 8 bits of the partition id)
-    u64* pid = (u64*)op->ws[1].ensure((size_t)n * 8);
-    u64* pid2 = (u64*)op->ws[2].ensure((size_t)n * 8);
-    uint32_t* counts = (uint32_t*)op->ws[8].ensure((size_t)(np + 1) * 4 + 16);
-    u64* ghist = (u64*)op->ws[6].ensure((size_t)sort_max_passes() * 256 * 8);
-    const size_t lwb = onesweep_ws_bytes(n);
-    void* lws = op->ws[7].ensure(lwb);
+    auto& W = op->w_part;
+    u64* pid = (u64*)W.pid.ensure((size_t)n * 8);
+    u64* pid2 = (u64*)W.pid2.ensure((size_t)n * 8);
+    uint32_t* counts = (uint32_t*)W.counts.ensure((size_t)(np + 1) * 4 + 16);
+    u64* ghist = W.pass.counts();
+    W.pass.lookback(n);
     ProfScope ps(op, s);
     { SinkJit jit(op, op->prog, GPUQ_SINK_PART_PID, n); launch_part_pid(s, jit.fn, P, n, op->keys, np, pid, nullptr); }
     launch_part_offsets(s, pid, n, np, counts, (u64*)part_offsets_out, 32);
@@ -1532,11 +1543,7 @@ int gpuq_partition_run(gpuq_op* op, void* stream, const gpuq_input* in, uint32_t
     const int npass = std::max(1, (bits + 7) / 8);
     if (npass == 1) launch_counts_to_ghist(s, counts, np, ghist);
     else launch_radix_ghist(s, pid, n, 32, npass, ghist);
-    for (int p = 0; p < npass; ++p) {
-      const bool final_pass = p + 1 == npass;
-      launch_onesweep_pass(s, pid, nullptr, n, 32 + 8 * p, ghist + (size_t)p * 256, lws, lwb, pid2, final_pass ? perm_out : nullptr, final_pass ? 1 : 0);
-      std::swap(pid, pid2);
-    }
+    bucket_records(s, pid, pid2, n, npass, W.pass, perm_out, 1);
     HIPCHECK(hipGetLastError());
   });
 }

@@ -73,12 +73,8 @@ void nccl_check(int rc, const char* what) {
 struct PeerFailed : std::runtime_error { using std::runtime_error::runtime_error; };      // a rank of the node failed: GPUQ_ERR_PEER on all of them
 template <class F> int guarded_x(F&& f) {
   try { f(); return GPUQ_OK; }
-  catch (const HipError& e) { g_xerr = e.what(); return GPUQ_ERR_HIP; }
-  catch (const Unsupported& e) { g_xerr = e.what(); return GPUQ_ERR_UNSUPPORTED; }
-  catch (const Capacity& e) { g_xerr = e.what(); return GPUQ_ERR_CAPACITY; }
-  catch (const Retry& e) { g_xerr = e.what(); return GPUQ_ERR_RETRY; }
   catch (const PeerFailed& e) { g_xerr = e.what(); return GPUQ_ERR_PEER; }
-  catch (const std::exception& e) { g_xerr = e.what(); return GPUQ_ERR_INVALID; }
+  catch (...) { return status_of_exception(g_xerr); }
 }
 
 struct PinnedHost {

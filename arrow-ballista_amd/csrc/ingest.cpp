@@ -25,13 +25,7 @@ using namespace gpuq;
 
 namespace {
 thread_local std::string g_ierr;
-template <class F> int guarded_i(F&& f) {
-  try { f(); return GPUQ_OK; }
-  catch (const HipError& e) { g_ierr = e.what(); return GPUQ_ERR_HIP; }
-  catch (const Unsupported& e) { g_ierr = e.what(); return GPUQ_ERR_UNSUPPORTED; }
-  catch (const Capacity& e) { g_ierr = e.what(); return GPUQ_ERR_CAPACITY; }
-  catch (const std::exception& e) { g_ierr = e.what(); return GPUQ_ERR_INVALID; }
-}
+template <class F> int guarded_i(F&& f) { return guarded_into(g_ierr, f); }
 // bits [src_off, src_off + n) of src -> bits [dst_off, ...) of dst (dst bytes beyond the range are preserved by OR-ing into zeroed memory)
 void copy_bits_host(uint8_t* dst, int64_t dst_off, const uint8_t* src, int64_t src_off, int64_t n) {
   if (((dst_off | src_off) & 7) == 0) { std::memcpy(dst + (dst_off >> 3), src + (src_off >> 3), (size_t)((n + 7) >> 3)); return; }

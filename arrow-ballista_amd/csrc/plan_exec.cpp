@@ -123,7 +123,6 @@ const uint32_t* via_of(const PTable& t, size_t i) { const int sd = t.sides[i]; r
 bool nullable_in(const PTable& t, size_t i) { return t.cols[i].nullable || (t.sides[i] > 0 && !t.dense); }      // declared so, or an index vector may hold NULL_ROW_ID
 DType dtype_of(const gpuq_column& c) { DType dt; dt.id = c.type; dt.p = c.precision; dt.s = c.scale; return dt; }
 size_t width_of(const gpuq_column& c) { return (size_t)type_width(dtype_of(c)); }
-size_t bitmap_bytes(int64_t n) { return (size_t)((n + 63) / 64) * 8 + 8; }
 gpuq_field_info field_info_of(const PCol& c) {
   gpuq_field_info f{};
   std::snprintf(f.name, sizeof(f.name), "%s", c.name.c_str());
@@ -2308,11 +2307,7 @@ template <class F> int plan_guarded(F&& f) {
   try { f(); return GPUQ_OK; }
   catch (const Cancelled& e) { g_plan_error = e.what(); return GPUQ_ERR_CANCELLED; }
   catch (const AgreedFailure& e) { g_plan_error = e.what(); return e.rc; }
-  catch (const HipError& e) { g_plan_error = e.what(); return GPUQ_ERR_HIP; }
-  catch (const Unsupported& e) { g_plan_error = e.what(); return GPUQ_ERR_UNSUPPORTED; }
-  catch (const Capacity& e) { g_plan_error = e.what(); return GPUQ_ERR_CAPACITY; }
-  catch (const std::bad_alloc&) { g_plan_error = "out of host memory"; return GPUQ_ERR_INTERNAL; }
-  catch (const std::exception& e) { g_plan_error = e.what(); return GPUQ_ERR_INVALID; }
+  catch (...) { return status_of_exception(g_plan_error); }
 }
 }  // namespace
 

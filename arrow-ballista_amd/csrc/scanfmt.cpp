@@ -15,13 +15,7 @@ using namespace gpuq;
 
 namespace {
 thread_local std::string g_ferr;
-template <class F> int guarded_f(F&& f) {
-  try { f(); return GPUQ_OK; }
-  catch (const HipError& e) { g_ferr = e.what(); return GPUQ_ERR_HIP; }
-  catch (const Unsupported& e) { g_ferr = e.what(); return GPUQ_ERR_UNSUPPORTED; }
-  catch (const Capacity& e) { g_ferr = e.what(); return GPUQ_ERR_CAPACITY; }
-  catch (const std::exception& e) { g_ferr = e.what(); return GPUQ_ERR_INVALID; }
-}
+template <class F> int guarded_f(F&& f) { return guarded_into(g_ferr, f); }
 // File bytes are pageable host memory: one thread staging them through a pinned buffer moves ~6-10 GB/s, a sixth of the link.
 // Bulk uploads therefore go through a few staging lanes (thread + stream + two pinned slots each, kept for the process lifetime):
 // lanes pull 4 MiB chunks off a shared counter, memcpy into a free slot and queue the DMA, so memcpys and DMAs of all lanes overlap.

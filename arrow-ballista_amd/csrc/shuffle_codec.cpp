@@ -26,14 +26,7 @@ using namespace gpuq;
 namespace {
 thread_local std::string g_ipc_error;
 
-template <class F> int guarded_ipc(F&& f) {
-  try { f(); return GPUQ_OK; }
-  catch (const HipError& e) { g_ipc_error = e.what(); return GPUQ_ERR_HIP; }
-  catch (const Unsupported& e) { g_ipc_error = e.what(); return GPUQ_ERR_UNSUPPORTED; }
-  catch (const Capacity& e) { g_ipc_error = e.what(); return GPUQ_ERR_CAPACITY; }
-  catch (const std::bad_alloc&) { g_ipc_error = "out of host memory"; return GPUQ_ERR_INTERNAL; }
-  catch (const std::exception& e) { g_ipc_error = e.what(); return GPUQ_ERR_INVALID; }
-}
+template <class F> int guarded_ipc(F&& f) { return guarded_into(g_ipc_error, f); }
 
 // ---------------------------------------------------------------- flatbuffer access (read side: generic; write side: one fixed layout)
 struct FbView {
