@@ -471,6 +471,9 @@ struct PqPage { i64 src; int32_t bytes; int32_t n_values; i64 row0; int32_t enc;
 struct PqDict { i64 values; i64 str_offsets; int32_t n; int32_t pad; };
 struct PqCol { int32_t phys, width; int32_t flba_len, optional; void* data; u64* valid; int32_t* str_len; i64* str_src; };
 constexpr uint32_t PQF_MALFORMED = 1u, PQF_UNSUPPORTED = 2u;
+// the status word of the page decompression kernels (Snappy, LZ4, ZSTD): this bit is a ZSTD frame that names a dictionary, which the
+// device does not decode (unsupported); every other bit is a page whose compressed bytes are damaged
+constexpr uint32_t UNPACKF_ZSTD_DICTIONARY = 8u;
 void launch_pq_decode(hipStream_t s, const uint8_t* file, i64 file_bytes, const PqPage* pages, int n_pages, const PqCol& C, const PqDict* dicts, const uint8_t* dict_values,
                       const int32_t* dict_str_offsets, uint32_t* scratch, i64 scratch_stride, uint32_t* flags);
 void launch_pq_copy_strings(hipStream_t s, const uint8_t* file, const uint8_t* dict_values, const i64* src, const int32_t* offsets, i64 n, uint8_t* out);

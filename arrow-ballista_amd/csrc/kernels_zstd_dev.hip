@@ -22,7 +22,8 @@ extern "C" __global__ __launch_bounds__(64) void gpuq_k_zstd_pages(const uint8_t
   if (b >= n) return;
   const UnpackJob J = jobs[which[b]];
   if (J.mode != 4 || J.raw_prefix < 0 || J.raw_prefix > J.src_len || J.raw_prefix > J.dst_len) { if (threadIdx.x == 0) atomicOr(status, 1u); return; }
+  bool dictionary = false;
   const bool ok = zs::decode_frames(src_base + J.src + J.raw_prefix, J.src_len - J.raw_prefix, dst_base + J.dst + J.raw_prefix, J.dst_len - J.raw_prefix,
-                                    scratch + (size_t)b * (size_t)(zs::BLOCK_MAX + 64), S, zs::Lds{nullptr, litw, bitw, hufw});
-  if (!ok && threadIdx.x == 0) atomicOr(status, 1u);
+                                    scratch + (size_t)b * (size_t)(zs::BLOCK_MAX + 64), S, zs::Lds{nullptr, litw, bitw, hufw}, &dictionary);
+  if (!ok && threadIdx.x == 0) atomicOr(status, dictionary ? UNPACKF_ZSTD_DICTIONARY : 1u);
 }

@@ -580,7 +580,8 @@ int gpuq_parquet_decode_groups(gpuq_ctx* ctx, void* stream, const uint8_t* file,
       if (gt == T_UTF8) {
         // lengths and positions of a malformed page are garbage: look at the flags BEFORE anything copies through them
         uint32_t early[2]; HIPCHECK(hipMemcpyAsync(early, flags.p, 8, hipMemcpyDeviceToHost, s)); HIPCHECK(hipStreamSynchronize(s));
-        if (early[1]) throw std::runtime_error("parquet: malformed Snappy data in a page");
+        if (early[1] & ~UNPACKF_ZSTD_DICTIONARY) throw std::runtime_error("parquet: malformed compressed data in a page");
+        if (early[1] & UNPACKF_ZSTD_DICTIONARY) throw Unsupported("parquet: a ZSTD frame names a dictionary");
         if (early[0] & PQF_MALFORMED) throw std::runtime_error("parquet: malformed page (levels / indices / lengths run past the page, or an index beyond its dictionary)");
         const uint8_t* df = pages_base; const uint8_t* dv = (const uint8_t*)P.dvalues.p; const i64* src = (const i64*)P.str_src.p;
         finish_strings(s, *ic, (int32_t*)ic->offsets.p, n_rows, [&](const int32_t* offs, uint8_t* dst, int64_t) { launch_pq_copy_strings(s, df, dv, src, offs, n_rows, dst); });
@@ -588,7 +589,8 @@ int gpuq_parquet_decode_groups(gpuq_ctx* ctx, void* stream, const uint8_t* file,
       t->cols.push_back(std::move(ic));
     }
     uint32_t fl2[2]; HIPCHECK(hipMemcpyAsync(fl2, flags.p, 8, hipMemcpyDeviceToHost, s)); HIPCHECK(hipStreamSynchronize(s));      // synchronises: the plans' host vectors and scratch may go
-    if (fl2[1]) throw std::runtime_error("parquet: malformed Snappy data in a page");
+    if (fl2[1] & ~UNPACKF_ZSTD_DICTIONARY) throw std::runtime_error("parquet: malformed compressed data in a page");
+    if (fl2[1] & UNPACKF_ZSTD_DICTIONARY) throw Unsupported("parquet: a ZSTD frame names a dictionary");
     const uint32_t fl = fl2[0];
     if (fl & PQF_MALFORMED) throw std::runtime_error("parquet: malformed page (levels / indices / lengths run past the page, or an index beyond its dictionary)");
     if (fl & PQF_UNSUPPORTED) throw Unsupported("parquet: a page holds a value type the device does not decode");

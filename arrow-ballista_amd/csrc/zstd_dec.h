@@ -451,8 +451,10 @@ ZS_FN bool decode_block(const uint8_t* bp, int64_t bsz, uint8_t* out, int64_t& o
   return true;
 }
 
-// every frame of in[0, in_len) -> out[0, out_len), exactly; scratch: BLOCK_MAX bytes of this wave's own
-ZS_FN bool decode_frames(const uint8_t* in, int64_t in_len, uint8_t* out, int64_t out_len, uint8_t* scratch, Shared& S, const Lds W = Lds{nullptr, nullptr, nullptr, nullptr}) {
+// every frame of in[0, in_len) -> out[0, out_len), exactly; scratch: BLOCK_MAX bytes of this wave's own.  A refusal sets *dictionary
+// (every lane alike) when its cause is a frame that names a dictionary: input the decoder leaves out, not a damaged one.
+ZS_FN bool decode_frames(const uint8_t* in, int64_t in_len, uint8_t* out, int64_t out_len, uint8_t* scratch, Shared& S, const Lds W = Lds{nullptr, nullptr, nullptr, nullptr},
+                         bool* dictionary = nullptr) {
   const int lane = ZS_LANE;
   int64_t ip = 0, op = 0;
   auto le = [&](int64_t at, int n) -> uint64_t { uint64_t v = 0; for (int i = 0; i < n; ++i) v |= (uint64_t)in[at + i] << (8 * i); return v; };
@@ -468,7 +470,7 @@ ZS_FN bool decode_frames(const uint8_t* in, int64_t in_len, uint8_t* out, int64_
     const int did_bytes = did == 3 ? 4 : did, fcs_bytes = fcs_flag == 0 ? single : (fcs_flag == 1 ? 2 : (fcs_flag == 2 ? 4 : 8));
     if (in_len - ip < (single ? 0 : 1) + did_bytes + fcs_bytes) return false;
     if (!single) ip += 1;
-    if (did_bytes && le(ip, did_bytes) != 0) return false;      // a dictionary: not something a Parquet page carries
+    if (did_bytes && le(ip, did_bytes) != 0) { if (dictionary) *dictionary = true; return false; }      // a dictionary: not something a Parquet page carries
     ip += did_bytes;
     int64_t fcs = -1;
     if (fcs_bytes) { fcs = (int64_t)le(ip, fcs_bytes); if (fcs_bytes == 2) fcs += 256; ip += fcs_bytes; }

@@ -434,12 +434,12 @@ class _Struct:
         return bytes(self.b) + b"\x00"
 
 
-PQ_CODECS = {"none": 0, "snappy": 1, "lz4_raw": 7}
+PQ_CODECS = {"none": 0, "snappy": 1, "zstd": 6, "lz4_raw": 7}
 
 
 def parquet_one_column(pages, codec, name="v"):
     """A Parquet file with one REQUIRED INT32 PLAIN column in one row group of v1 data pages.
-    pages: [(n_values, uncompressed_len, payload)]; codec: 0 UNCOMPRESSED, 1 SNAPPY, 7 LZ4_RAW."""
+    pages: [(n_values, uncompressed_len, payload)]; codec: 0 UNCOMPRESSED, 1 SNAPPY, 6 ZSTD, 7 LZ4_RAW."""
     body = bytearray(b"PAR1")
     first = len(body)
     n_total, u_total = 0, 0
