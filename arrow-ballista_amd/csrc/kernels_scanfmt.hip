@@ -242,8 +242,11 @@ __device__ __forceinline__ uint32_t pq_unpack(const uint8_t* base, const uint8_t
   return (uint32_t)((w >> (bit & 7)) & ((bw >= 32) ? 0xFFFFFFFFull : ((1ull << bw) - 1)));
 }
 // Decode an RLE / bit-packed hybrid stream of `n` values into out[0..n) (LDS or global), the whole wave cooperating on each run.
+// false: the stream ends before `n` values do, a run has count 0, the bytes of a run's value (or of the bit-packed values read) do
+// not lie inside the stream, or an RLE run's value exceeds `vmax` (levels: the column's maximum level; a bit-packed value of `bw`
+// bits cannot exceed it).  All checks are per run.
 template <class Sink>
-__device__ __forceinline__ bool pq_hybrid(const uint8_t* p, const uint8_t* end, int bw, int n, Sink sink) {
+__device__ __forceinline__ bool pq_hybrid(const uint8_t* p, const uint8_t* end, int bw, int n, uint32_t vmax, Sink sink) {
   BitReader b{p, end};
   int done = 0;
   while (done < n) {
@@ -253,6 +256,8 @@ __device__ __forceinline__ bool pq_hybrid(const uint8_t* p, const uint8_t* end, 
       const i64 cnt = (i64)(h >> 1) * 8;      // 64-bit: a corrupt header must not wrap into a negative count
       if (cnt == 0) return false;
       const int take = cnt < (i64)(n - done) ? (int)cnt : n - done;
+      // the values read must be there; the zero padding of a last group beyond them may be cut (old parquet-mr writers did, Arrow C++ reads it)
+      if (((i64)take * bw + 7) / 8 > b.end - b.p) return false;
       for (int i = flane(); i < take; i += 64) sink(done + i, pq_unpack(b.p, b.end, bw, (uint32_t)i));
       const i64 adv = (cnt * bw + 7) / 8;
       b.p = adv < b.end - b.p ? b.p + adv : b.end; done += take;
@@ -260,7 +265,9 @@ __device__ __forceinline__ bool pq_hybrid(const uint8_t* p, const uint8_t* end, 
       const i64 cnt = (i64)(h >> 1);
       if (cnt == 0) return false;
       uint32_t v = 0; const int nb = (bw + 7) / 8;
-      for (int k = 0; k < nb; ++k) if (b.p + k < b.end) v |= (uint32_t)b.p[k] << (8 * k);
+      if (nb > b.end - b.p) return false;      // a run header without its value: not a run of zeros
+      for (int k = 0; k < nb; ++k) v |= (uint32_t)b.p[k] << (8 * k);
+      if (v > vmax) return false;
       b.p += nb;
       const int take = cnt < (i64)(n - done) ? (int)cnt : n - done;
       for (int i = flane(); i < take; i += 64) sink(done + i, v);
@@ -299,7 +306,7 @@ __global__ void __launch_bounds__(64) k_pq_decode(const uint8_t* __restrict__ fi
       dp = p + 4; dend = dp + len; p = dend;
     }
     if (dend > end) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
-    const bool ok = pq_hybrid(dp, dend, 1, n, [&](int i, uint32_t v) { vidx[i] = v; });
+    const bool ok = pq_hybrid(dp, dend, 1, n, 1u /* max definition level of a flat optional column */, [&](int i, uint32_t v) { vidx[i] = v; });
     if (!ok) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
     // exclusive prefix of the levels = value index; validity bits by ballot (rows of a page start at any bit: atomicOr)
@@ -327,7 +334,7 @@ __global__ void __launch_bounds__(64) k_pq_decode(const uint8_t* __restrict__ fi
     p += 4;
     if ((i64)len > end - p) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
     uint32_t* bits = vidx + n;
-    if (!pq_hybrid(p, p + len, 1, n_present, [&](int i, uint32_t v) { bits[i] = v; })) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
+    if (!pq_hybrid(p, p + len, 1, n_present, 0xFFFFFFFFu, [&](int i, uint32_t v) { bits[i] = v; })) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
     for (int i = flane(); i < n; i += 64) {
       const uint32_t vi = C.optional ? vidx[i] : (uint32_t)i;
@@ -338,14 +345,15 @@ __global__ void __launch_bounds__(64) k_pq_decode(const uint8_t* __restrict__ fi
     return;
   }
   if (P.enc == PQE_DICT) {
-    if (P.dict < 0 || p >= end) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
+    // a page without a present value needs no index stream, not even the width byte (an all-NULL v2 page may end with its levels)
+    if (P.dict < 0 || (p >= end && n_present > 0)) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
     const PqDict D = dicts[P.dict];
-    const int bw = (int)*p++;
+    const int bw = p < end ? (int)*p++ : 0;
     if (bw > 32) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
-    // indices of the present values, decoded into the tail of the scratch row (n_present <= n)
+    // indices of the present values, decoded into the tail of the scratch row (n_present <= n).  Width 0 (parquet-rs writes it for a
+    // one-entry dictionary) is a stream like any other: runs whose values take no bytes; its headers must still announce n_present values
     uint32_t* ix = vidx + n;
-    const bool ok = bw == 0 ? true : pq_hybrid(p, end, bw, n_present, [&](int i, uint32_t v) { ix[i] = v; });
-    if (bw == 0) for (int i = flane(); i < n_present; i += 64) ix[i] = 0;
+    const bool ok = pq_hybrid(p, end, bw, n_present, 0xFFFFFFFFu, [&](int i, uint32_t v) { ix[i] = v; });
     if (!ok) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
     for (int i = flane(); i < n; i += 64) {
@@ -353,7 +361,7 @@ __global__ void __launch_bounds__(64) k_pq_decode(const uint8_t* __restrict__ fi
       const i64 r = P.row0 + i;
       if (vi == NULL_ROW) { if (C.phys == PQ_BYTE_ARRAY) { C.str_len[r] = 0; C.str_src[r] = -1; } continue; }
       const uint32_t k = ix[vi];
-      if ((int)k >= D.n) { atomicOr(flags, PQF_MALFORMED); continue; }
+      if (k >= (uint32_t)D.n) { atomicOr(flags, PQF_MALFORMED); continue; }      // unsigned: a 32-bit index of 0xFFFFFFFF is not -1 (D.n >= 0: the host refuses a negative count)
       if (C.phys == PQ_BYTE_ARRAY) { const int32_t* so = dict_str_offsets + D.str_offsets; C.str_len[r] = so[k + 1] - so[k]; C.str_src[r] = -(2 + (D.values + so[k])); }   // negative: position in the dictionary bytes
       else if (C.width == 1) ((uint8_t*)C.data)[r] = ((const uint8_t*)(dict_values + D.values))[k];
       else if (C.width == 2) ((uint16_t*)C.data)[r] = ((const uint16_t*)(dict_values + D.values))[k];

@@ -334,13 +334,20 @@ PqFileMeta read_footer(const uint8_t* file, int64_t n) {
   }
   return m;
 }
-struct PqPageHeader { int type = -1, uncompressed = 0, compressed = 0, num_values = 0, encoding = 0, def_v2 = 0, rep_v2 = 0; bool v2_compressed = true; int64_t header_bytes = 0; };
+struct PqPageHeader { int type = -1, uncompressed = 0, compressed = 0, num_values = 0, encoding = 0, def_v2 = 0, rep_v2 = 0; bool v2_compressed = true; int64_t header_bytes = 0;
+                      int def_enc = 3; };      // DataPageHeader.definition_level_encoding (3 = RLE; v2 levels are always RLE)
 PqPageHeader read_page_header(const uint8_t* p, const uint8_t* e) {
   TReader r{p, e}; PqPageHeader h; int t, id, last = 0;
   while (r.field(t, id, last)) {
     switch (id) {
       case 1: h.type = (int)r.zigzag(); break; case 2: h.uncompressed = (int)r.zigzag(); break; case 3: h.compressed = (int)r.zigzag(); break;
-      case 5: case 7: { int t2, id2, last2 = 0; while (r.field(t2, id2, last2)) { if (id2 == 1) h.num_values = (int)r.zigzag(); else if (id2 == 2) h.encoding = (int)r.zigzag(); else r.skip(t2); } break; }
+      case 5: case 7: { int t2, id2, last2 = 0;      // DataPageHeader / DictionaryPageHeader (its field 3 is the bool is_sorted)
+        while (r.field(t2, id2, last2)) {
+          if (id2 == 1) h.num_values = (int)r.zigzag(); else if (id2 == 2) h.encoding = (int)r.zigzag();
+          else if (id == 5 && id2 == 3 && t2 == 5) h.def_enc = (int)r.zigzag();
+          else r.skip(t2);
+        }
+        break; }
       case 8: { int t2, id2, last2 = 0;
         while (r.field(t2, id2, last2)) {
           if (id2 == 1) h.num_values = (int)r.zigzag(); else if (id2 == 4) h.encoding = (int)r.zigzag(); else if (id2 == 5) h.def_v2 = (int)r.zigzag();
@@ -449,7 +456,12 @@ int gpuq_parquet_decode_groups(gpuq_ctx* ctx, void* stream, const uint8_t* file,
             G2.n_values = H.num_values; G2.row0 = row + seen; G2.dict = dict_id;
             if (H.encoding == 0) G2.enc = PQE_PLAIN; else if (H.encoding == 2 || H.encoding == 8) G2.enc = PQE_DICT; else if (H.encoding == 3 && L.type == 0) G2.enc = PQE_RLE;
             else throw Unsupported("parquet: data page encoding " + std::to_string(H.encoding) + " in '" + L.name + "' (PLAIN, RLE_DICTIONARY and RLE booleans are decoded)");
-            if (H.type == 3) { if (H.rep_v2 != 0) throw Unsupported("parquet: repetition levels"); G2.def_v2 = H.def_v2; }
+            // (nested and repeated columns were refused above: this column is flat, and repetition-level bytes in it are not levels of anything)
+            if (H.type == 3) { if (H.rep_v2 != 0) throw std::runtime_error("parquet: repetition levels in a page of the flat column '" + L.name + "'"); G2.def_v2 = H.def_v2; }
+            // a v1 page of an optional column carries its definition levels as a length-prefixed RLE stream; the deprecated BIT_PACKED
+            // levels have no length prefix and pack from the most significant bit (a flat column has no repetition levels to encode)
+            if (H.type == 0 && P->optional && H.def_enc != 3)
+              throw Unsupported("parquet: definition_level_encoding " + std::to_string(H.def_enc) + (H.def_enc == 4 ? " (BIT_PACKED)" : "") + " in '" + L.name + "' (RLE levels are decoded)");
             if (H.type == 3 && P->optional && H.def_v2 == 0 && H.num_values > 0) throw std::runtime_error("parquet: v2 page of an optional column without definition levels");
             if (G2.enc == PQE_DICT && dict_id < 0) throw std::runtime_error("parquet: dictionary-encoded page before any dictionary page");
             P->pages.push_back(G2); seen += H.num_values; P->max_values = std::max(P->max_values, H.num_values);
@@ -582,7 +594,7 @@ int gpuq_parquet_decode_groups(gpuq_ctx* ctx, void* stream, const uint8_t* file,
         uint32_t early[2]; HIPCHECK(hipMemcpyAsync(early, flags.p, 8, hipMemcpyDeviceToHost, s)); HIPCHECK(hipStreamSynchronize(s));
         if (early[1] & ~UNPACKF_ZSTD_DICTIONARY) throw std::runtime_error("parquet: malformed compressed data in a page");
         if (early[1] & UNPACKF_ZSTD_DICTIONARY) throw Unsupported("parquet: a ZSTD frame names a dictionary");
-        if (early[0] & PQF_MALFORMED) throw std::runtime_error("parquet: malformed page (levels / indices / lengths run past the page, or an index beyond its dictionary)");
+        if (early[0] & PQF_MALFORMED) throw std::runtime_error("parquet: malformed page (levels / indices / lengths run past the page, a level above the column's maximum, or an index beyond its dictionary)");
         const uint8_t* df = pages_base; const uint8_t* dv = (const uint8_t*)P.dvalues.p; const i64* src = (const i64*)P.str_src.p;
         finish_strings(s, *ic, (int32_t*)ic->offsets.p, n_rows, [&](const int32_t* offs, uint8_t* dst, int64_t) { launch_pq_copy_strings(s, df, dv, src, offs, n_rows, dst); });
       }
@@ -592,7 +604,7 @@ int gpuq_parquet_decode_groups(gpuq_ctx* ctx, void* stream, const uint8_t* file,
     if (fl2[1] & ~UNPACKF_ZSTD_DICTIONARY) throw std::runtime_error("parquet: malformed compressed data in a page");
     if (fl2[1] & UNPACKF_ZSTD_DICTIONARY) throw Unsupported("parquet: a ZSTD frame names a dictionary");
     const uint32_t fl = fl2[0];
-    if (fl & PQF_MALFORMED) throw std::runtime_error("parquet: malformed page (levels / indices / lengths run past the page, or an index beyond its dictionary)");
+    if (fl & PQF_MALFORMED) throw std::runtime_error("parquet: malformed page (levels / indices / lengths run past the page, a level above the column's maximum, or an index beyond its dictionary)");
     if (fl & PQF_UNSUPPORTED) throw Unsupported("parquet: a page holds a value type the device does not decode");
     *out = t.release();
   });

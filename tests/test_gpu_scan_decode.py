@@ -215,8 +215,15 @@ def parquet_table(n, seed):
         "nb": pa.array(r.integers(0, 2, n).astype(bool), mask=r.random(n) < 0.3),
         "ns": pa.array(words[r.integers(0, len(words), n)], mask=r.random(n) < 0.2),
         "allnull": pa.array([None] * n, type=pa.int32()),
+        "i8": pa.array(r.integers(-128, 128, n).astype(np.int8)),
+        "i16": pa.array(r.integers(-2**15, 2**15, n).astype(np.int16)),
+        "u8": pa.array(r.integers(0, 256, n).astype(np.uint8)),
+        "u16": pa.array(r.integers(0, 2**16, n).astype(np.uint16), mask=r.random(n) < 0.25),
+        "u32": pa.array(r.integers(0, 2**32, n).astype(np.uint32)),
+        "u64": pa.array(r.integers(0, 2**64, n, dtype=np.uint64)),
+        "f32": pa.array(r.normal(0, 1e3, n).astype(np.float32)),
     })
-    req = ("k", "lowcard", "i", "d", "f", "dec", "dec38", "b", "s", "u")
+    req = ("k", "lowcard", "i", "d", "f", "dec", "dec38", "b", "s", "u", "i8", "i16", "u8", "u32", "u64", "f32")
     return t.cast(pa.schema([pa.field(f.name, f.type, nullable=f.name not in req) for f in t.schema]))
 
 
@@ -241,11 +248,17 @@ def write(t, **kw):
     dict(use_dictionary=True, data_page_version="1.0", compression="ZSTD", data_page_size=16384),
     dict(use_dictionary=["lowcard", "s"], data_page_version="2.0", compression="ZSTD", data_page_size=4096, row_group_size=25_000),
     dict(use_dictionary=False, data_page_version="1.0", compression="ZSTD", compression_level=19),
+    # a codec per column: uncompressed chunks are routed through the stored unpack job beside the Snappy, LZ4 and ZSTD batches
+    dict(use_dictionary=["lowcard", "s", "ns", "u8"], data_page_version="2.0", data_page_size=8192, row_group_size=30_000,
+         compression={"k": "SNAPPY", "lowcard": "ZSTD", "i": "NONE", "d": "LZ4", "f": "SNAPPY", "dec": "NONE", "dec38": "ZSTD", "b": "NONE", "s": "ZSTD", "u": "LZ4",
+                      "nk": "SNAPPY", "nb": "LZ4", "ns": "NONE", "allnull": "ZSTD", "i8": "NONE", "i16": "SNAPPY", "u8": "LZ4", "u16": "NONE", "u32": "ZSTD", "u64": "SNAPPY",
+                      "f32": "NONE"}),
 ], ids=["dict-v1", "plain-v1", "dict-v2-smallpages", "plain-v2-rowgroups", "mixed-dict-fallback", "snappy-v1", "snappy-v2", "lz4raw-v1", "lz4raw-v2",
-        "zstd-v1", "zstd-v2", "zstd-19-bigpages"])
+        "zstd-v1", "zstd-v2", "zstd-19-bigpages", "codec-per-column"])
 def test_pyarrow_written_files(tc, n, opts):
     """Required and optional columns of every decoded type; dictionary and PLAIN pages, v1 and v2 headers, many small pages, several
-    row groups, a dictionary that overflows and falls back to PLAIN mid-chunk; decimals as FIXED_LEN_BYTE_ARRAY (15,2) and (38,2)."""
+    row groups, a dictionary that overflows and falls back to PLAIN mid-chunk; decimals as FIXED_LEN_BYTE_ARRAY (15,2) and (38,2); the
+    narrow and unsigned integers and Float32 (INT32 / INT64 / FLOAT with an annotation), one of them nullable."""
     t = parquet_table(n, 5 + n) if n else parquet_table(10, 5).slice(0, 0)
     data = write(t, **opts)
     got = scan.read_parquet(tc, data).to_arrow(tc.ctx)
