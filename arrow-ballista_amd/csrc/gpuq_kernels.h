@@ -425,25 +425,46 @@ void launch_utf8_piece_starts(hipStream_t s, Utf8Piece* pieces, int n_pieces, ui
 void launch_utf8_piece_offsets(hipStream_t s, const Utf8Piece* pieces, int n_pieces, int64_t max_rows);
 void launch_utf8_piece_validate(hipStream_t s, const Utf8Piece* pieces, int n_pieces, int64_t max_rows, uint32_t* status);
 void launch_utf8_piece_compact(hipStream_t s, const Utf8Piece* pieces, int n_pieces, int64_t max_bytes, const uint8_t* from, uint8_t* to);
-// one Parquet page, or one block of a linked LZ4 frame (kernels_lz4.hip).  mode: 0 stored, 1 Snappy, 2 LZ4 block of a linked frame, 3 stored block of a
-// linked frame (its bytes can be the source of later blocks' matches).  s_off / c_off: the job's place in the resolve array / the per-position arrays;
-// linked frames: f_off = the FRAME's place in the resolve array and p_base = the block's position in the frame's output (copies may reach back
-// across blocks; s_off = f_off + p_base), elsewhere f_off = s_off and p_base = 0
+// ----- page / shuffle-block decompression (kernels_lz4.hip, kernels_zstd_dev.hip; host side: unpack_launch.cpp)
+// One job: a Parquet page, or one block of a linked LZ4 frame.  [src, +src_len) -> [dst, +dst_len); the first `raw_prefix` bytes of both are
+// copied verbatim (a v2 data page's levels) and `mode` says what the rest is:
+//   UNPACK_STORED         the bytes themselves
+//   UNPACK_SNAPPY         one raw Snappy stream
+//   UNPACK_LZ4_BLOCK      one LZ4 block: an LZ4_RAW page, or a compressed block of a linked frame
+//   UNPACK_LINKED_STORED  a stored block of a linked frame (its bytes can be the source of later blocks' matches)
+//   UNPACK_ZSTD           ZSTD frames: the unpack kernels copy the prefix and leave the rest to launch_zstd_pages
+// The four placement fields are read by the parallel decoder only.  s_off: the job's place in the resolve array (one 32-bit word per output
+// byte behind the prefix, a multiple of 4); c_off: its place in the per-position arrays (one slot per compressed byte behind the prefix, + 1),
+// the compressed jobs of a call back to back in job order.  Copies point into a FRAME: f_off is the frame's place in the resolve array and
+// p_base the job's position in the frame's output (s_off = f_off + p_base); a page is its own frame (f_off = s_off, p_base = 0).
+enum UnpackMode : int32_t { UNPACK_STORED = 0, UNPACK_SNAPPY = 1, UNPACK_LZ4_BLOCK = 2, UNPACK_LINKED_STORED = 3, UNPACK_ZSTD = 4 };
+// the status word of these kernels (Snappy, LZ4, ZSTD): a job whose compressed bytes are damaged, and a ZSTD frame that names a dictionary,
+// which the device does not decode (unsupported).  Callers treat every bit but the second as damage.
+constexpr uint32_t UNPACKF_MALFORMED = 1u, UNPACKF_ZSTD_DICTIONARY = 8u;
 struct UnpackJob { int64_t src, dst, src_len, dst_len, raw_prefix; int32_t mode, pad; int64_t s_off, c_off, f_off, p_base; };
+// The serial decoder: one wave per job walks the elements and moves the bytes (stored, Snappy and -- prefix only -- ZSTD jobs)
 void launch_unpack_pages(hipStream_t s, const uint8_t* src, uint8_t* dst, const UnpackJob* jobs, int n_jobs, uint32_t* status);
-// mode 4 = ZSTD frames (kernels_zstd_dev.hip + zstd_launch.cpp; the unpack kernels copy such a job's raw prefix and leave the rest to this launch);
-// `which`: indices of the mode-4 jobs, `scratch`: zstd_scratch_bytes(n) bytes
+// `which`: indices of the UNPACK_ZSTD jobs, `scratch`: zstd_scratch_bytes(n) bytes
 size_t zstd_scratch_bytes(int n_pages);
 void launch_zstd_pages(hipStream_t s, const uint8_t* src, uint8_t* dst, const UnpackJob* jobs, const int32_t* which, int n, uint8_t* scratch, uint32_t* status);
-// Snappy without a serial element walk (kernels_lz4.hip).  resolve: one 32-bit word per uncompressed byte of the Snappy jobs (s_off); blkmap: (job, first
-// byte) per 4096 of them.  jump_a / jump_b / olen (32-bit) and mark (8-bit): one entry per compressed byte + one per job (c_off; c_slots in all, + 1 for the
-// scan); cmap: (job, first position) per 4096 of those.  counts: (mark_rounds + rounds + 3) * n_jobs zeroed words.
-struct SnappyPjBuffers {
-  uint32_t* resolve; const uint2* blkmap; int n_blocks; int rounds;
-  uint32_t* jump_a; uint32_t* jump_b; uint32_t* olen; uint8_t* mark; const uint2* cmap; int n_cblocks; int mark_rounds; int64_t c_slots;
-  void* scan_ws; size_t scan_ws_bytes; uint32_t* counts;
-};
-void launch_unpack_pages_pj(hipStream_t s, const uint8_t* src, uint8_t* dst, const UnpackJob* jobs, int n_jobs, const SnappyPjBuffers& B, uint32_t* status);
+// The parallel decoder (no serial element walk; every mode but UNPACK_ZSTD's body).  `jobs`: n HOST jobs with their placement fields set;
+// everything else -- the block maps, the round counts, the scratch, what is zeroed, the launches -- follows from the jobs.  Synchronises the
+// stream before it returns.  `X` is reused from call to call (the batches of one file); nothing in it outlives a call.
+struct UnpackScratch { DevBuf jobs, resolve, blkmap, cmap, counts, jump_a, jump_b, olen, mark, scan; };
+inline bool unpack_job_is_compressed(const UnpackJob& j) { return j.mode == UNPACK_SNAPPY || j.mode == UNPACK_LZ4_BLOCK; }
+void unpack_pages_parallel(hipStream_t s, const uint8_t* src, uint8_t* dst, const UnpackJob* jobs, int n, UnpackScratch& X, uint32_t* status);
+// its kernels, one launch each (unpack_launch.cpp holds the order and the scratch contract).  The maps name (job, first byte) per
+// PJ_BLOCK_BYTES of output (blkmap) / of compressed positions (cmap); cnt_prev / cnt_cur: one zeroed word per job and round
+constexpr int PJ_BLOCK_BYTES = 4096;
+void launch_sn_head(hipStream_t s, const uint8_t* src, uint8_t* dst, const UnpackJob* jobs, int n_jobs, uint8_t* mark, uint32_t* resolve, uint32_t* status);
+void launch_sn_next(hipStream_t s, const uint8_t* src, const uint2* cmap, int n_cblocks, const UnpackJob* jobs, uint32_t* jump, uint32_t* olen);
+void launch_sn_mark(hipStream_t s, const uint2* cmap, int n_cblocks, const UnpackJob* jobs, const uint32_t* jump_in, uint32_t* jump_out, uint8_t* mark, const uint32_t* cnt_prev,
+                    uint32_t* cnt_cur, bool first);
+void launch_sn_lens(hipStream_t s, const uint2* cmap, int n_cblocks, const UnpackJob* jobs, const uint8_t* mark, const uint32_t* olen, int32_t* pos, uint32_t* status);
+void launch_sn_fill(hipStream_t s, const uint8_t* src, const uint2* cmap, int n_cblocks, const UnpackJob* jobs, const uint8_t* mark, const int32_t* pos, uint32_t* resolve,
+                    uint32_t* status);
+void launch_snappy_round(hipStream_t s, uint32_t* resolve, const uint2* blkmap, int n_blocks, const UnpackJob* jobs, const uint32_t* cnt_prev, uint32_t* cnt_cur, bool first);
+void launch_snappy_emit(hipStream_t s, const uint32_t* resolve, const uint2* blkmap, int n_blocks, const UnpackJob* jobs, uint8_t* dst, uint32_t* status);
 void launch_utf8_code_rows(hipStream_t s, const void* codes, int width, const uint8_t* validity, i64 n, uint32_t* rows);      // width 8 (Int64) or 4 (UInt32)
 void launch_utf8_sort_piece(hipStream_t s, const uint8_t* data, const int32_t* offsets, const uint8_t* validity, const uint32_t* idx, i64 n, int piece, void* out, u64* valid_out);
 void launch_utf8_max_len(hipStream_t s, const int32_t* offsets, const uint8_t* validity, const uint32_t* idx, i64 n, int32_t* out);
@@ -471,9 +492,6 @@ struct PqPage { i64 src; int32_t bytes; int32_t n_values; i64 row0; int32_t enc;
 struct PqDict { i64 values; i64 str_offsets; int32_t n; int32_t pad; };
 struct PqCol { int32_t phys, width; int32_t flba_len, optional; void* data; u64* valid; int32_t* str_len; i64* str_src; };
 constexpr uint32_t PQF_MALFORMED = 1u, PQF_UNSUPPORTED = 2u;
-// the status word of the page decompression kernels (Snappy, LZ4, ZSTD): this bit is a ZSTD frame that names a dictionary, which the
-// device does not decode (unsupported); every other bit is a page whose compressed bytes are damaged
-constexpr uint32_t UNPACKF_ZSTD_DICTIONARY = 8u;
 void launch_pq_decode(hipStream_t s, const uint8_t* file, i64 file_bytes, const PqPage* pages, int n_pages, const PqCol& C, const PqDict* dicts, const uint8_t* dict_values,
                       const int32_t* dict_str_offsets, uint32_t* scratch, i64 scratch_stride, uint32_t* flags);
 void launch_pq_copy_strings(hipStream_t s, const uint8_t* file, const uint8_t* dict_values, const i64* src, const int32_t* offsets, i64 n, uint8_t* out);

@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "gpuq_kernels.h"
+#include "lz_elements.h"
 
 namespace gpuq {
 
@@ -252,6 +253,7 @@ __device__ __forceinline__ int win_byte(InWin& W, int64_t a /* byte address rela
 }
 
 // one LZ4 block: in [ip, iend) -> out at op; returns the new op or -1 on a malformed stream
+// (the sequence format is stated here a second time, beside lz::lz4_sequence: see the head of lz_elements.h for what the shared form cost this loop)
 __device__ __forceinline__ int64_t lz4_decode_block(InWin& W, const uint8_t* in8, int64_t ip, int64_t iend, uint8_t* out, int64_t op, int64_t out_lo, int64_t out_hi) {
   const int lane = lane_id();
   while (ip < iend) {
@@ -292,6 +294,8 @@ __global__ __launch_bounds__(64) void k_lz4_decode(const uint8_t* __restrict__ s
   } else if (U.mode == LZ4_UNIT_STORED) {
     if (U.src_len != U.dst_len) bad = true; else wave_copy(out, src_base + U.src, (int)U.dst_len);
   } else {      // LZ4_UNIT_FRAME_BLOCKS: walk the block headers of one frame (linked blocks: matches reach into earlier blocks)
+    // (the block index a second time beside lz::lz4_frame_blocks, which the host uses: lz4_decode_block inlined into the shared walk's
+    // callback measured 1.5 % slower over many small frames)
     int64_t ip = U.src, op = 0;
     const int64_t iend = U.src + U.src_len;
     while (true) {
@@ -314,7 +318,7 @@ __global__ __launch_bounds__(64) void k_lz4_decode(const uint8_t* __restrict__ s
     }
     if (!bad && op != U.dst_len) bad = true;
   }
-  if (bad && lane_id() == 0) atomicOr(status, 1u);
+  if (bad && lane_id() == 0) atomicOr(status, UNPACKF_MALFORMED);
 }
 
 __global__ void k_popcount_bits(const u64* __restrict__ bits, int64_t n_bits, unsigned long long* __restrict__ out) {
@@ -372,13 +376,26 @@ __global__ __launch_bounds__(256) void k_utf8_piece_compact(const Utf8Piece* __r
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < P.used; i += (int64_t)gridDim.x * 256) d[i] = s[i];
 }
 
-// ---------------------------------------------------------------- Snappy (Parquet pages; kernels_scanfmt.hip decodes what this unpacks)
-// Raw Snappy block format [UPSTREAM-KNOWLEDGE: google/snappy format_description.txt]: varint uncompressed length, then elements --
-// tag & 3 == 0 literal (length (tag >> 2) + 1, or 1-4 length bytes when that is 61-64), 1 copy with 11-bit offset and length 4-11,
-// 2 copy with 16-bit offset, 3 copy with 32-bit offset (length (tag >> 2) + 1).  One wave per page: every lane reads the same tag
-// bytes (uniform loads), literals and copies are moved by all lanes; a copy whose offset is shorter than its length repeats the
-// period (source byte i % offset lies before the copy).  mode 0 = stored (plain copy).  `raw_prefix` bytes in front of the
-// compressed stream are copied verbatim (a v2 data page's levels).
+// ---------------------------------------------------------------- unpack jobs (Parquet pages; kernels_scanfmt.hip decodes what this unpacks)
+// What every kernel that takes a job per wave does first (k_unpack_pages, k_sn_head): the raw prefix is checked and copied, a ZSTD job is
+// left to k_zstd_pages, a stored one is copied.  -> true: `V` is a compressed stream (or a linked frame's stored block) for the caller
+struct JobBody { const uint8_t* in; uint8_t* out; int64_t in_len, out_len; };
+__device__ __forceinline__ bool unpack_job_begin(const UnpackJob& J, const uint8_t* __restrict__ src_base, uint8_t* __restrict__ dst_base, uint32_t* __restrict__ status, JobBody& V) {
+  const int lane = lane_id();
+  const uint8_t* in = src_base + J.src; uint8_t* out = dst_base + J.dst;
+  if (J.raw_prefix > J.src_len || J.raw_prefix > J.dst_len) { if (lane == 0) atomicOr(status, UNPACKF_MALFORMED); return false; }
+  for (int64_t i = lane; i < J.raw_prefix; i += 64) out[i] = in[i];
+  V = JobBody{in + J.raw_prefix, out + J.raw_prefix, J.src_len - J.raw_prefix, J.dst_len - J.raw_prefix};
+  if (J.mode == UNPACK_ZSTD) return false;
+  if (J.mode != UNPACK_STORED) return true;
+  if (V.in_len != V.out_len) { if (lane == 0) atomicOr(status, UNPACKF_MALFORMED); return false; }
+  for (int64_t i = lane; i < V.in_len; i += 64) V.out[i] = V.in[i];
+  return false;
+}
+
+// ---------------------------------------------------------------- Snappy, serial (the format: lz_elements.h)
+// One wave per page: every lane reads the same tag bytes (uniform loads), literals and copies are moved by all lanes; a copy whose
+// offset is shorter than its length repeats the period (source byte i % offset lies before the copy).
 // The element stream is read through a 4 KiB window in LDS (refilled with coalesced 16-byte loads) and the last 32 KiB of output
 // are mirrored in an LDS ring: a tag byte or a short back-reference fetched from global memory costs a full L2 round trip
 // (~0.7 us, and a copy's source was written only moments ago).  Copies that reach further back than the ring read global memory.
@@ -395,17 +412,11 @@ __global__ __launch_bounds__(64) void k_unpack_pages(const uint8_t* __restrict__
   if (u >= n_jobs) return;
   const UnpackJob J = jobs[u];
   const int lane = lane_id();
-  const uint8_t* in = src_base + J.src; uint8_t* out = dst_base + J.dst;
-  if (J.raw_prefix > J.src_len || J.raw_prefix > J.dst_len) { if (lane == 0) atomicOr(status, 1u); return; }
-  for (int64_t i = lane; i < J.raw_prefix; i += 64) out[i] = in[i];
-  in += J.raw_prefix; out += J.raw_prefix;
-  if (J.mode == 4) return;      // ZSTD frames: k_zstd_pages
-  const int64_t in_len = J.src_len - J.raw_prefix, out_len = J.dst_len - J.raw_prefix;
-  if (J.mode == 0) {
-    if (in_len != out_len) { if (lane == 0) atomicOr(status, 1u); return; }
-    for (int64_t i = lane; i < in_len; i += 64) out[i] = in[i];
-    return;
-  }
+  JobBody V;
+  if (!unpack_job_begin(J, src_base, dst_base, status, V)) return;
+  if (J.mode != UNPACK_SNAPPY) { if (lane == 0) atomicOr(status, UNPACKF_MALFORMED); return; }      // (LZ4 jobs are the parallel decoder's: the host never sends one here)
+  const uint8_t* const in = V.in; uint8_t* const out = V.out;
+  const int64_t in_len = V.in_len, out_len = V.out_len;
   // input window: bytes [wbase, wbase + SNAPPY_INWIN) of `in`
   int64_t wbase = -(int64_t)SNAPPY_INWIN - 16;
   auto want = [&](int64_t pos, int nbytes) {      // wave-uniform
@@ -420,15 +431,15 @@ __global__ __launch_bounds__(64) void k_unpack_pages(const uint8_t* __restrict__
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
   };
   auto ib = [&](int64_t pos) -> uint32_t { return inw[pos - wbase]; };
-  int64_t ip = 0, op = 0;
+  int64_t op = 0;
   bool bad = false;
-  // preamble: uncompressed length
-  want(0, 8);
-  uint64_t ulen = 0; int sh = 0;
-  for (;;) { if (ip >= in_len || sh > 35) { bad = true; break; } const uint32_t c = ib(ip++); ulen |= (uint64_t)(c & 0x7F) << sh; if (!(c & 0x80)) break; sh += 7; }
-  if (bad || (int64_t)ulen != out_len) { if (lane == 0) atomicOr(status, 1u); return; }
+  want(0, 8);                                          // the preamble: at most 6 bytes
+  const lz::SnHead H = lz::sn_preamble(ib, in_len);
+  if (!H.ok || H.ulen != out_len) { if (lane == 0) atomicOr(status, UNPACKF_MALFORMED); return; }
+  int64_t ip = H.start;
   while (ip < in_len) {
     want(ip, 5);                                       // a tag and up to four length / offset bytes
+    // (the element format, a second time beside lz::sn_element: see the head of lz_elements.h for what the shared form cost this loop)
     const uint32_t tag = ib(ip++);
     int64_t len; int64_t off = 0;
     if ((tag & 3) == 0) {
@@ -458,7 +469,7 @@ __global__ __launch_bounds__(64) void k_unpack_pages(const uint8_t* __restrict__
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
     op += len;
   }
-  if (bad || op != out_len) { if (lane == 0) atomicOr(status, 1u); }
+  if (bad || op != out_len) { if (lane == 0) atomicOr(status, UNPACKF_MALFORMED); }
 }
 
 // ---------------------------------------------------------------- launchers
@@ -517,7 +528,6 @@ void launch_popcount_bits(hipStream_t s, const uint8_t* bits, int64_t n_bits, un
 // far, lengths past either end); a word still unresolved after ceil(log2(page bytes)) + 1 rounds cannot happen for a checked stream and
 // is reported as malformed.
 constexpr uint32_t PJ_DONE = 0x80000000u;
-constexpr int PJ_BLOCK_BYTES = 4096;
 // -- the front half, parallel too.  An element's size and output length depend only on the bytes at its own position, so next(p) and
 // olen(p) are computed for EVERY position of the compressed stream as if an element started there; the real elements are the positions on
 // the path start -> next(start) -> ... -> end, found by doubling: marked positions mark jump(p), then jump = jump o jump (ping-pong arrays; a
@@ -525,45 +535,6 @@ constexpr int PJ_BLOCK_BYTES = 4096;
 // in the output, and the elements are expanded into resolve words all at once.  (Walking the elements one after the other, as
 // k_unpack_pages and a first version of this path did, costs ~1000 cycles per element on a lone wave: 112 ms for a 1 MB page of sorted
 // keys, whatever the copying costs.)
-struct SnElem { int64_t size; uint32_t olen; int kind; uint32_t off; int64_t lit; };      // kind 0 literal (lit = first data byte), 1 copy
-__device__ __forceinline__ SnElem sn_element(const uint8_t* __restrict__ in, const int64_t p, const int64_t L) {
-  SnElem e{1, 0u, 0, 0u, 0};
-  uint32_t b[5];
-#pragma unroll
-  for (int k = 0; k < 5; ++k) b[k] = p + k < L ? in[p + k] : 0u;
-  const uint32_t tag = b[0];
-  if ((tag & 3) == 0) {
-    int64_t len = (int64_t)(tag >> 2) + 1; int nb = 0;
-    if (len > 60) { nb = (int)len - 60; uint32_t v = 0; for (int k = 0; k < nb; ++k) v |= b[1 + k] << (8 * k); len = (int64_t)v + 1; }
-    e.size = 1 + nb + len; e.olen = (uint32_t)len; e.kind = 0; e.lit = p + 1 + nb;
-  } else if ((tag & 3) == 1) { e.size = 2; e.olen = 4 + ((tag >> 2) & 7); e.kind = 1; e.off = ((tag >> 5) << 8) | b[1]; }
-  else if ((tag & 3) == 2) { e.size = 3; e.olen = (tag >> 2) + 1; e.kind = 1; e.off = b[1] | (b[2] << 8); }
-  else { e.size = 5; e.olen = (tag >> 2) + 1; e.kind = 1; e.off = b[1] | (b[2] << 8) | (b[3] << 16) | (b[4] << 24); }
-  return e;
-}
-// one LZ4 sequence starting at p of a block [0, L): token, literal length (+255-runs), literals, then -- unless the literals end the block -- a
-// 2-byte offset and the match length (+255-runs, + 4).  lit = first literal byte, olen = literals + match
-struct Lz4Elem { int64_t size; int64_t lit_len, match_len; uint32_t off; int64_t lit; bool ok; };
-__device__ __forceinline__ Lz4Elem lz4_element(const uint8_t* __restrict__ in, const int64_t p, const int64_t L) {
-  Lz4Elem e{0, 0, 0, 0u, 0, false};
-  int64_t q = p;
-  const uint32_t token = in[q++];
-  int64_t lit = token >> 4;
-  // (a length cannot legitimately run longer than the block; positions that are NOT sequence starts -- inside a run of 0xFF bytes, say --
-  // must not walk it to its end each: the bound keeps the all-positions pass linear in practice)
-  const int max_run = (int)(L / 255) + 2;
-  if (lit == 15) { uint32_t x; int guard = 0; do { if (q >= L || ++guard > max_run) return e; x = in[q++]; lit += x; } while (x == 255); }
-  e.lit = q; e.lit_len = lit;
-  if (lit > L - q) return e;
-  q += lit;
-  if (q == L) { e.size = q - p; e.ok = true; return e; }      // the last sequence of a block: literals only
-  if (q + 2 > L) return e;
-  e.off = (uint32_t)in[q] | ((uint32_t)in[q + 1] << 8); q += 2;
-  int64_t ml = token & 15;
-  if (ml == 15) { uint32_t x; int guard = 0; do { if (q >= L) return e; x = in[q++]; ml += x; (void)guard; } while (x == 255); }      // (bounded by the block's end; positions inside a 0xFF run leave through the literal bound above)
-  e.match_len = ml + 4; e.size = q - p; e.ok = true;
-  return e;
-}
 constexpr uint32_t SN_BAD = 0xFFFFFFFFu;
 // per job (one wave): the raw prefix and stored pages are copied; a Snappy page's length preamble is read and its first element marked
 __global__ __launch_bounds__(64) void k_sn_head(const uint8_t* __restrict__ src_base, uint8_t* __restrict__ dst_base, const UnpackJob* __restrict__ jobs, int n_jobs,
@@ -572,29 +543,21 @@ __global__ __launch_bounds__(64) void k_sn_head(const uint8_t* __restrict__ src_
   if (u >= n_jobs) return;
   const UnpackJob J = jobs[u];
   const int lane = lane_id();
-  const uint8_t* in = src_base + J.src; uint8_t* out = dst_base + J.dst;
-  if (J.raw_prefix > J.src_len || J.raw_prefix > J.dst_len) { if (lane == 0) atomicOr(status, 1u); return; }
-  for (int64_t i = lane; i < J.raw_prefix; i += 64) out[i] = in[i];
-  in += J.raw_prefix; out += J.raw_prefix;
-  const int64_t L = J.src_len - J.raw_prefix, out_len = J.dst_len - J.raw_prefix;
-  if (J.mode == 4) return;      // ZSTD frames: k_zstd_pages
-  if (J.mode == 0) {
-    if (L != out_len) { if (lane == 0) atomicOr(status, 1u); return; }
-    for (int64_t i = lane; i < L; i += 64) out[i] = in[i];
-    return;
-  }
-  if (J.mode == 3) {      // stored block of a linked frame: every byte a resolved word (k_snappy_emit writes the bytes)
-    if (L != out_len) { if (lane == 0) atomicOr(status, 1u); return; }
+  JobBody V;
+  if (!unpack_job_begin(J, src_base, dst_base, status, V)) return;
+  const uint8_t* const in = V.in;
+  const int64_t L = V.in_len, out_len = V.out_len;
+  if (J.mode == UNPACK_LINKED_STORED) {      // every byte a resolved word (k_snappy_emit writes the bytes)
+    if (L != out_len) { if (lane == 0) atomicOr(status, UNPACKF_MALFORMED); return; }
     uint32_t* S = resolve + J.s_off;
     for (int64_t i = lane; i < L; i += 64) S[i] = PJ_DONE | (uint32_t)in[i];
     return;
   }
-  if (J.mode == 2) { if (lane == 0) mark[J.c_off] = 1; return; }      // an LZ4 block starts with its first sequence
+  if (J.mode == UNPACK_LZ4_BLOCK) { if (lane == 0) mark[J.c_off] = 1; return; }      // an LZ4 block starts with its first sequence
   if (lane == 0) {
-    uint64_t ulen = 0; int sh = 0; int64_t ip = 0; bool bad = false;
-    for (;;) { if (ip >= L || sh > 35) { bad = true; break; } const uint32_t c = in[ip++]; ulen |= (uint64_t)(c & 0x7F) << sh; if (!(c & 0x80)) break; sh += 7; }
-    if (bad || (int64_t)ulen != out_len || out_len >= (int64_t)PJ_DONE) atomicOr(status, 1u);
-    else mark[J.c_off + ip] = 1;      // (an empty page: ip == L, the terminal slot)
+    const lz::SnHead H = lz::sn_preamble([&](int64_t a) { return in[a]; }, L);
+    if (!H.ok || H.ulen != out_len || out_len >= (int64_t)PJ_DONE) atomicOr(status, UNPACKF_MALFORMED);
+    else mark[J.c_off + H.start] = 1;      // (an empty page: start == L, the terminal slot)
   }
 }
 // every position: where the element that would start here ends, and how many bytes it would produce
@@ -602,18 +565,19 @@ __global__ __launch_bounds__(256) void k_sn_next(const uint8_t* __restrict__ src
   const uint2 m = cmap[blockIdx.x];
   const UnpackJob J = jobs[m.x];
   const uint8_t* in = src_base + J.src + J.raw_prefix;
-  const int64_t L = J.src_len - J.raw_prefix;
+  const int64_t L = J.src_len - J.raw_prefix, out_len = J.dst_len - J.raw_prefix;
+  const auto rd = [&](int64_t a) { return in[a]; };
   for (int k = 0; k < PJ_BLOCK_BYTES / 256; ++k) {
     const int64_t p = (int64_t)m.y + k * 256 + threadIdx.x;
     if (p > L) continue;
     uint32_t nx = (uint32_t)L, ol = 0;
     if (p < L) {
-      if (J.mode == 2) {
-        const Lz4Elem e = lz4_element(in, p, L);
-        if (!e.ok || p + e.size > L || e.lit_len + e.match_len >= (int64_t)PJ_DONE) ol = SN_BAD; else { nx = (uint32_t)(p + e.size); ol = (uint32_t)(e.lit_len + e.match_len); }
+      if (J.mode == UNPACK_LZ4_BLOCK) {
+        const lz::Lz4Seq e = lz::lz4_sequence(rd, p, L, L, out_len);      // (literals are bytes of the block, a match bytes of its output)
+        if (!e.ok || e.lit_len + e.match_len >= (int64_t)PJ_DONE) ol = SN_BAD; else { nx = (uint32_t)(p + e.size); ol = (uint32_t)(e.lit_len + e.match_len); }
       } else {
-        const SnElem e = sn_element(in, p, L);
-        if (p + e.size > L) ol = SN_BAD; else { nx = (uint32_t)(p + e.size); ol = e.olen; }
+        const lz::SnElem e = lz::sn_element(rd, p, L);
+        if (!e.ok) ol = SN_BAD; else { nx = (uint32_t)(p + e.size); ol = e.olen; }
       }
     }
     jump[J.c_off + p] = nx; olen[J.c_off + p] = ol;
@@ -647,8 +611,8 @@ __global__ __launch_bounds__(256) void k_sn_lens(const uint2* __restrict__ cmap,
     const int64_t p = (int64_t)m.y + k * 256 + threadIdx.x;
     if (p > L) continue;
     uint32_t v = 0;
-    if (mark[J.c_off + p] && p < L) { v = olen[J.c_off + p]; if (v == SN_BAD || v >= PJ_DONE) { v = 0; atomicOr(status, 1u); } }      // an element that runs past the end of the page
-    if (p == L && !mark[J.c_off + p]) atomicOr(status, 1u);                                                                             // the path must end exactly at the end
+    if (mark[J.c_off + p] && p < L) { v = olen[J.c_off + p]; if (v == SN_BAD || v >= PJ_DONE) { v = 0; atomicOr(status, UNPACKF_MALFORMED); } }      // an element that runs past the end of the page
+    if (p == L && !mark[J.c_off + p]) atomicOr(status, UNPACKF_MALFORMED);                                                                             // the path must end exactly at the end
     pos[J.c_off + p] = (int32_t)v;
   }
 }
@@ -661,29 +625,30 @@ __global__ __launch_bounds__(256) void k_sn_fill(const uint8_t* __restrict__ src
   const int64_t L = J.src_len - J.raw_prefix, out_len = J.dst_len - J.raw_prefix;
   uint32_t* S = resolve + J.s_off;
   const int64_t base = pos[J.c_off];
+  const auto rd = [&](int64_t a) { return in[a]; };
   for (int k = 0; k < PJ_BLOCK_BYTES / 256; ++k) {
     const int64_t p = (int64_t)m.y + k * 256 + threadIdx.x;
     if (p > L || !mark[J.c_off + p]) continue;
     const int64_t o = (int64_t)pos[J.c_off + p] - base;
-    if (p == L) { if (o != out_len) atomicOr(status, 1u); continue; }      // the elements must produce exactly the announced length
-    if (J.mode == 2) {
-      const Lz4Elem e = lz4_element(in, p, L);
-      if (!e.ok || p + e.size > L || o < 0 || o + e.lit_len + e.match_len > out_len) { atomicOr(status, 1u); continue; }
+    if (p == L) { if (o != out_len) atomicOr(status, UNPACKF_MALFORMED); continue; }      // the elements must produce exactly the announced length
+    if (J.mode == UNPACK_LZ4_BLOCK) {
+      const lz::Lz4Seq e = lz::lz4_sequence(rd, p, L, L, out_len);
+      if (!e.ok || o < 0 || o + e.lit_len + e.match_len > out_len) { atomicOr(status, UNPACKF_MALFORMED); continue; }
       for (int64_t i = 0; i < e.lit_len; ++i) S[o + i] = PJ_DONE | (uint32_t)in[e.lit + i];
       if (e.match_len) {
         const int64_t at = J.p_base + o + e.lit_len;      // position in the FRAME's output: a match may reach back into earlier blocks
-        if (e.off == 0 || (int64_t)e.off > at) { atomicOr(status, 1u); continue; }
+        if (e.off == 0 || (int64_t)e.off > at) { atomicOr(status, UNPACKF_MALFORMED); continue; }
         const uint32_t from = (uint32_t)(at - e.off);
         uint32_t* M = S + o + e.lit_len;
         for (int64_t i = 0; i < e.match_len; ++i) M[i] = from + (uint32_t)((int64_t)e.off >= e.match_len ? i : i % (int64_t)e.off);
       }
       continue;
     }
-    const SnElem e = sn_element(in, p, L);
-    if (p + e.size > L || o < 0 || o + (int64_t)e.olen > out_len) { atomicOr(status, 1u); continue; }      // (o < 0: a corrupted stream whose announced lengths wrapped the 32-bit scan)
-    if (e.kind == 0) { for (uint32_t i = 0; i < e.olen; ++i) S[o + i] = PJ_DONE | (uint32_t)in[e.lit + i]; }
+    const lz::SnElem e = lz::sn_element(rd, p, L);
+    if (!e.ok || o < 0 || o + (int64_t)e.olen > out_len) { atomicOr(status, UNPACKF_MALFORMED); continue; }      // (o < 0: a corrupted stream whose announced lengths wrapped the 32-bit scan)
+    if (!e.copy) { for (uint32_t i = 0; i < e.olen; ++i) S[o + i] = PJ_DONE | (uint32_t)in[e.lit + i]; }
     else {
-      if (e.off == 0 || (int64_t)e.off > o) { atomicOr(status, 1u); continue; }
+      if (e.off == 0 || (int64_t)e.off > o) { atomicOr(status, UNPACKF_MALFORMED); continue; }
       const uint32_t from = (uint32_t)(o - e.off);
       for (uint32_t i = 0; i < e.olen; ++i) S[o + i] = from + (e.off >= e.olen ? i : i % e.off);
     }
@@ -732,30 +697,31 @@ __global__ __launch_bounds__(256) void k_snappy_emit(const uint32_t* __restrict_
       *(uint32_t*)(out + p) = (v.x & 0xFF) | ((v.y & 0xFF) << 8) | ((v.z & 0xFF) << 16) | ((v.w & 0xFF) << 24);
     } else for (int64_t q = p; q < p + 4 && q < len; ++q) { const uint32_t v = S[q]; bad = bad || !(v & PJ_DONE); out[q] = (uint8_t)v; }
   }
-  if (bad) atomicOr(status, 1u);
+  if (bad) atomicOr(status, UNPACKF_MALFORMED);
 }
-void launch_unpack_pages_pj(hipStream_t s, const uint8_t* src, uint8_t* dst, const UnpackJob* jobs, int n_jobs, const SnappyPjBuffers& B, uint32_t* status) {
-  if (n_jobs <= 0) return;
-  // front: which positions of the compressed streams are elements, and where their output goes
-  hipLaunchKernelGGL(k_sn_head, dim3((unsigned)n_jobs), dim3(64), 0, s, src, dst, jobs, n_jobs, B.mark, B.resolve, status);
-  if (B.n_blocks <= 0) return;
-  if (B.n_cblocks > 0) {      // (none: a linked LZ4 frame of stored blocks only -- k_sn_head has written every word, k_snappy_emit still has to write the bytes)
-    hipLaunchKernelGGL(k_sn_next, dim3((unsigned)B.n_cblocks), dim3(256), 0, s, src, B.cmap, jobs, B.jump_a, B.olen);
-    uint32_t* ja = B.jump_a; uint32_t* jb = B.jump_b;
-    for (int r = 0; r < B.mark_rounds; ++r) {
-      hipLaunchKernelGGL(k_sn_mark, dim3((unsigned)B.n_cblocks), dim3(256), 0, s, B.cmap, jobs, (const uint32_t*)ja, jb, B.mark, B.counts + (size_t)r * n_jobs, B.counts + (size_t)(r + 1) * n_jobs, r == 0 ? 1 : 0);
-      std::swap(ja, jb);
-    }
-    int32_t* pos = (int32_t*)B.jump_b;      // (both jump arrays are free now)
-    hipLaunchKernelGGL(k_sn_lens, dim3((unsigned)B.n_cblocks), dim3(256), 0, s, B.cmap, jobs, (const uint8_t*)B.mark, (const uint32_t*)B.olen, pos, status);
-    launch_exclusive_scan_i32(s, pos, B.c_slots, B.scan_ws, B.scan_ws_bytes);
-    hipLaunchKernelGGL(k_sn_fill, dim3((unsigned)B.n_cblocks), dim3(256), 0, s, src, B.cmap, jobs, (const uint8_t*)B.mark, (const int32_t*)pos, B.resolve, status);
-  }
-  // back: copies resolved by pointer jumping, then the bytes
-  uint32_t* c2 = B.counts + (size_t)(B.mark_rounds + 1) * n_jobs;
-  for (int r = 0; r < B.rounds; ++r)
-    hipLaunchKernelGGL(k_snappy_round, dim3((unsigned)B.n_blocks), dim3(256), 0, s, B.resolve, B.blkmap, jobs, c2 + (size_t)r * n_jobs, c2 + (size_t)(r + 1) * n_jobs, r == 0 ? 1 : 0);
-  hipLaunchKernelGGL(k_snappy_emit, dim3((unsigned)B.n_blocks), dim3(256), 0, s, (const uint32_t*)B.resolve, B.blkmap, jobs, dst, status);
+// one launch each; unpack_launch.cpp holds their order and their scratch
+void launch_sn_head(hipStream_t s, const uint8_t* src, uint8_t* dst, const UnpackJob* jobs, int n_jobs, uint8_t* mark, uint32_t* resolve, uint32_t* status) {
+  hipLaunchKernelGGL(k_sn_head, dim3((unsigned)n_jobs), dim3(64), 0, s, src, dst, jobs, n_jobs, mark, resolve, status);
+}
+void launch_sn_next(hipStream_t s, const uint8_t* src, const uint2* cmap, int n_cblocks, const UnpackJob* jobs, uint32_t* jump, uint32_t* olen) {
+  hipLaunchKernelGGL(k_sn_next, dim3((unsigned)n_cblocks), dim3(256), 0, s, src, cmap, jobs, jump, olen);
+}
+void launch_sn_mark(hipStream_t s, const uint2* cmap, int n_cblocks, const UnpackJob* jobs, const uint32_t* jump_in, uint32_t* jump_out, uint8_t* mark, const uint32_t* cnt_prev,
+                    uint32_t* cnt_cur, bool first) {
+  hipLaunchKernelGGL(k_sn_mark, dim3((unsigned)n_cblocks), dim3(256), 0, s, cmap, jobs, jump_in, jump_out, mark, cnt_prev, cnt_cur, first ? 1 : 0);
+}
+void launch_sn_lens(hipStream_t s, const uint2* cmap, int n_cblocks, const UnpackJob* jobs, const uint8_t* mark, const uint32_t* olen, int32_t* pos, uint32_t* status) {
+  hipLaunchKernelGGL(k_sn_lens, dim3((unsigned)n_cblocks), dim3(256), 0, s, cmap, jobs, mark, olen, pos, status);
+}
+void launch_sn_fill(hipStream_t s, const uint8_t* src, const uint2* cmap, int n_cblocks, const UnpackJob* jobs, const uint8_t* mark, const int32_t* pos, uint32_t* resolve,
+                    uint32_t* status) {
+  hipLaunchKernelGGL(k_sn_fill, dim3((unsigned)n_cblocks), dim3(256), 0, s, src, cmap, jobs, mark, pos, resolve, status);
+}
+void launch_snappy_round(hipStream_t s, uint32_t* resolve, const uint2* blkmap, int n_blocks, const UnpackJob* jobs, const uint32_t* cnt_prev, uint32_t* cnt_cur, bool first) {
+  hipLaunchKernelGGL(k_snappy_round, dim3((unsigned)n_blocks), dim3(256), 0, s, resolve, blkmap, jobs, cnt_prev, cnt_cur, first ? 1 : 0);
+}
+void launch_snappy_emit(hipStream_t s, const uint32_t* resolve, const uint2* blkmap, int n_blocks, const UnpackJob* jobs, uint8_t* dst, uint32_t* status) {
+  hipLaunchKernelGGL(k_snappy_emit, dim3((unsigned)n_blocks), dim3(256), 0, s, resolve, blkmap, jobs, dst, status);
 }
 
 void launch_unpack_pages(hipStream_t s, const uint8_t* src, uint8_t* dst, const UnpackJob* jobs, int n_jobs, uint32_t* status) {

@@ -431,8 +431,8 @@ int gpuq_parquet_decode_groups(gpuq_ctx* ctx, void* stream, const uint8_t* file,
         if (K.num_values == 0) continue;
         if (K.num_values < 0 || K.total_compressed <= 0 || K.data_page_offset < 0) throw std::runtime_error("parquet: negative size / offset in a column chunk's metadata");
         if (K.codec != 0 && K.codec != 1 && K.codec != 6 && K.codec != 7) throw Unsupported("parquet: compressed column chunk (codec " + std::to_string(K.codec) + ") in '" + L.name + "': UNCOMPRESSED, SNAPPY, ZSTD and LZ4_RAW pages are decoded on the device");
-        const int cmode = K.codec == 1 ? 1 : (K.codec == 7 ? 2 : (K.codec == 6 ? 4 : 0));      // UnpackJob::mode: 1 Snappy, 2 one raw LZ4 block per page (LZ4_RAW), 4 ZSTD frames
-        if (cmode == 2) any_lz4 = true;
+        const int cmode = K.codec == 1 ? UNPACK_SNAPPY : (K.codec == 7 ? UNPACK_LZ4_BLOCK : (K.codec == 6 ? UNPACK_ZSTD : UNPACK_STORED));      // (LZ4_RAW: one block per page)
+        if (cmode == UNPACK_LZ4_BLOCK) any_lz4 = true;
         int64_t pos = K.dict_page_offset >= 0 && K.dict_page_offset < K.data_page_offset ? K.dict_page_offset : K.data_page_offset;
         const int64_t chunk_end = pos + K.total_compressed;
         if (pos < 4 || chunk_end > n_bytes - 8) throw std::runtime_error("parquet: column chunk outside the file");
@@ -451,7 +451,7 @@ int gpuq_parquet_decode_groups(gpuq_ctx* ctx, void* stream, const uint8_t* file,
           } else if (H.type == 0 || H.type == 3) {
             // a v2 page stores its levels uncompressed in front of the (optionally) compressed values
             const int prefix = H.type == 3 ? H.def_v2 + H.rep_v2 : 0;
-            const int pmode = (H.type == 3 && !H.v2_compressed) ? 0 : cmode;
+            const int pmode = (H.type == 3 && !H.v2_compressed) ? UNPACK_STORED : cmode;
             PqPage G2{}; G2.src = place(payload + base, H.compressed, H.uncompressed, prefix, pmode); G2.bytes = any_compressed ? H.uncompressed : H.compressed;
             G2.n_values = H.num_values; G2.row0 = row + seen; G2.dict = dict_id;
             if (H.encoding == 0) G2.enc = PQE_PLAIN; else if (H.encoding == 2 || H.encoding == 8) G2.enc = PQE_DICT; else if (H.encoding == 3 && L.type == 0) G2.enc = PQE_RLE;
@@ -478,66 +478,38 @@ int gpuq_parquet_decode_groups(gpuq_ctx* ctx, void* stream, const uint8_t* file,
     DevBuf dfile; dfile.ensure((size_t)up_bytes + 64);
     g_uploader.copy_segments(ctx->device, s, dfile.p, segs);
     DevBuf flags; flags.ensure(16); HIPCHECK(hipMemsetAsync(flags.p, 0, 16, s));
-    DevBuf dpagebuf, djobs, dresolve, dblk, dcblk, dcnt, dja, djb, dolen, dmark, dscan;
+    DevBuf dpagebuf, djobs;
     const uint8_t* pages_base = (const uint8_t*)dfile.p; int64_t pages_bytes = up_bytes;
     if (any_compressed) {
       dpagebuf.ensure((size_t)page_bytes + 64); djobs.ensure(jobs.size() * sizeof(UnpackJob) + 64);
       HIPCHECK(hipMemcpyAsync(djobs.p, jobs.data(), jobs.size() * sizeof(UnpackJob), hipMemcpyHostToDevice, s));
-      // Snappy pages are decoded without a serial element walk (kernels_lz4.hip: positions -> path by doubling -> scan -> resolve words ->
-      // pointer jumping), in batches of consecutive pages whose scratch -- a 32-bit word per uncompressed byte, 13 bytes per compressed
-      // byte -- stays within ~5 GB (2^30 words); GPUQ_SNAPPY_PJ=0 (or a single page beyond that) keeps the serial decoder
+      // Snappy and LZ4_RAW pages are decoded without a serial element walk (unpack_pages_parallel), in batches of consecutive pages whose
+      // scratch -- a 32-bit word per uncompressed byte, 13 bytes per compressed byte -- stays within ~5 GB (2^30 words); GPUQ_SNAPPY_PJ=0 (or
+      // a single page beyond that) keeps the serial decoder
       static const bool pj_on = []() { const char* e = std::getenv("GPUQ_SNAPPY_PJ"); return !(e && e[0] == '0'); }();
       const int64_t max_words = (int64_t)1 << 30;
       bool any_snappy = false, fits = true;
-      for (auto& j : jobs) if (j.mode == 1 || j.mode == 2) { any_snappy = true; if (j.dst_len > max_words || j.src_len > max_words) fits = false; }
+      for (auto& j : jobs) if (unpack_job_is_compressed(j)) { any_snappy = true; if (j.dst_len > max_words || j.src_len > max_words) fits = false; }
       if (any_lz4 && !(pj_on && fits)) throw Unsupported("parquet: LZ4_RAW pages are decoded by the parallel path only (GPUQ_SNAPPY_PJ=0, or a page beyond 2^30 bytes)");
       if (pj_on && any_snappy && fits) {
-        HIPCHECK(hipMemsetAsync(dmark.ensure(64), 0, 64, s));
-        size_t first = 0;
-        while (first < jobs.size()) {
-          int64_t words = 0, max_len = 0, slots = 0, max_in = 0;
-          size_t last = first;
-          std::vector<uint2> blk, cblk;
-          for (; last < jobs.size(); ++last) {
+        UnpackScratch X;
+        for (size_t first = 0, last; first < jobs.size(); first = last) {
+          int64_t words = 0, slots = 0;
+          for (last = first; last < jobs.size(); ++last) {
             UnpackJob& j = jobs[last];
-            const bool sn = (j.mode == 1 || j.mode == 2) && j.raw_prefix <= j.src_len && j.raw_prefix <= j.dst_len;
+            const bool sn = unpack_job_is_compressed(j) && j.raw_prefix <= j.src_len && j.raw_prefix <= j.dst_len;      // (anything else takes no scratch)
             const int64_t len = sn ? j.dst_len - j.raw_prefix : 0, cl = sn ? j.src_len - j.raw_prefix : 0;
             if (last > first && sn && (words + len > max_words || slots + cl + 1 > max_words)) break;
             j.s_off = words; j.c_off = slots; j.f_off = words; j.p_base = 0;
-            if (!sn) continue;
-            const uint32_t k = (uint32_t)(last - first);
-            for (int64_t bb = 0; bb < len; bb += 4096) blk.push_back(make_uint2(k, (uint32_t)bb));
-            for (int64_t bb = 0; bb <= cl; bb += 4096) cblk.push_back(make_uint2(k, (uint32_t)bb));
-            words += (len + 3) & ~(int64_t)3; slots += cl + 1;
-            if (len > max_len) max_len = len; if (cl > max_in) max_in = cl;
+            if (sn) { words += (len + 3) & ~(int64_t)3; slots += cl + 1; }
           }
-          const size_t nj = last - first;
-          int rounds = 1; while (((int64_t)1 << rounds) < max_len) ++rounds;
-          rounds += 1;
-          int mrounds = 1; while (((int64_t)1 << mrounds) < max_in + 1) ++mrounds;
-          mrounds += 1;
-          dresolve.ensure((size_t)words * 4 + 64); dblk.ensure(blk.size() * sizeof(uint2) + 64); dcblk.ensure(cblk.size() * sizeof(uint2) + 64);
-          dcnt.ensure((size_t)(rounds + mrounds + 3) * nj * 4 + 64);
-          dja.ensure((size_t)(slots + 1) * 4 + 64); djb.ensure((size_t)(slots + 1) * 4 + 64); dolen.ensure((size_t)(slots + 1) * 4 + 64); dmark.ensure((size_t)slots + 64);
-          const size_t swb = exclusive_scan_ws_bytes(slots + 1); dscan.ensure(swb);
-          HIPCHECK(hipMemcpyAsync((UnpackJob*)djobs.p + first, jobs.data() + first, nj * sizeof(UnpackJob), hipMemcpyHostToDevice, s));      // (again: with the s_off / c_off fields)
-          if (!blk.empty()) HIPCHECK(hipMemcpyAsync(dblk.p, blk.data(), blk.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
-          if (!cblk.empty()) HIPCHECK(hipMemcpyAsync(dcblk.p, cblk.data(), cblk.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
-          HIPCHECK(hipMemsetAsync(dcnt.p, 0, (size_t)(rounds + mrounds + 3) * nj * 4, s));
-          HIPCHECK(hipMemsetAsync(dmark.p, 0, (size_t)slots + 64, s));
-          SnappyPjBuffers B{};
-          B.resolve = (uint32_t*)dresolve.p; B.blkmap = (const uint2*)dblk.p; B.n_blocks = (int)blk.size(); B.rounds = rounds;
-          B.jump_a = (uint32_t*)dja.p; B.jump_b = (uint32_t*)djb.p; B.olen = (uint32_t*)dolen.p; B.mark = (uint8_t*)dmark.p; B.cmap = (const uint2*)dcblk.p; B.n_cblocks = (int)cblk.size();
-          B.mark_rounds = mrounds; B.c_slots = slots; B.scan_ws = dscan.p; B.scan_ws_bytes = swb; B.counts = (uint32_t*)dcnt.p;
-          launch_unpack_pages_pj(s, (const uint8_t*)dfile.p, (uint8_t*)dpagebuf.p, (const UnpackJob*)djobs.p + first, (int)nj, B, (uint32_t*)flags.p + 1);
-          HIPCHECK(hipStreamSynchronize(s));      // the block maps (pageable host memory) and the scratch are reused by the next batch
-          first = last;
+          unpack_pages_parallel(s, (const uint8_t*)dfile.p, (uint8_t*)dpagebuf.p, jobs.data() + first, (int)(last - first), X, (uint32_t*)flags.p + 1);
         }
       } else
       launch_unpack_pages(s, (const uint8_t*)dfile.p, (uint8_t*)dpagebuf.p, (const UnpackJob*)djobs.p, (int)jobs.size(), (uint32_t*)flags.p + 1);
       // ZSTD pages (the reference's `tpch convert` default): one wave per page, in launches of at most 4096 pages
       std::vector<int32_t> zjobs;
-      for (size_t j = 0; j < jobs.size(); ++j) if (jobs[j].mode == 4) zjobs.push_back((int32_t)j);
+      for (size_t j = 0; j < jobs.size(); ++j) if (jobs[j].mode == UNPACK_ZSTD) zjobs.push_back((int32_t)j);
       DevBuf dzwhich, dzscratch;
       if (!zjobs.empty()) {
         const int zbatch = 4096;

@@ -20,6 +20,7 @@
 #include "../../include/gpuq.h"
 #include "devbuf.h"
 #include "gpuq_kernels.h"
+#include "lz_elements.h"
 
 using namespace gpuq;
 
@@ -509,9 +510,9 @@ int gpuq_ipc_decode_stream(gpuq_ctx* ctx, void* stream, const uint8_t* bytes, in
     std::vector<Lz4Unit> units, units_seq;      // fast path (independent blocks assumed full) and the always-valid per-frame walk
     bool split_any = false;
     // linked frames of two blocks or more (what Arrow C++ writes: every block may copy from the 64 KB before it) are decoded WITHOUT the
-    // serial walk (kernels_lz4.hip, launch_unpack_pages_pj: the machinery of the Snappy pages with LZ4's sequences as elements and the
-    // frame as the space copies point into) -- one job per block; the per-frame walk stays as the fallback (units_seq)
-    std::vector<UnpackJob> ljobs; int64_t lwords = 0, lslots = 0, lmax_frame = 0, lmax_in = 0;
+    // serial walk (unpack_pages_parallel: the machinery of the Snappy pages with LZ4's sequences as elements and the frame as the space
+    // copies point into) -- one job per block; the per-frame walk stays as the fallback (units_seq)
+    std::vector<UnpackJob> ljobs; int64_t lwords = 0, lslots = 0;      // (where the next frame's resolve words and position slots go)
     static const bool lz4_pj_on = []() { const char* e = std::getenv("GPUQ_LZ4_PJ"); return !(e && e[0] == '0'); }();
     // uncompressed length of buffer j of message g (host only)
     struct CopyFix { uint8_t* dst; const uint8_t* src; int64_t n; };       // device-to-device copies, in issue order
@@ -553,43 +554,33 @@ int gpuq_ipc_decode_stream(gpuq_ctx* ctx, void* stream, const uint8_t* bytes, in
       if (hp + 4 > flen) throw std::runtime_error("truncated LZ4 frame");
       Lz4Unit whole{off + 8 + hp, (int64_t)(uintptr_t)dst, flen - hp, ulen, LZ4_UNIT_FRAME_BLOCKS, bchk ? LZ4_UNIT_BLOCK_CHECKSUM : 0};
       units_seq.push_back(whole);
+      // the block index, on the host (lz4_frame_blocks): every block but the last decodes to the frame's block size (verified on the device)
+      const auto rd = [&](int64_t a) { return f[a]; };
       if (!indep) {
-        // the block index, on the host (as for independent blocks below): every block but the last decodes to the frame's block size
-        std::vector<UnpackJob> fj; int64_t ip = hp, op = 0; bool okw = lz4_pj_on && ulen > bmax && ulen < ((int64_t)1 << 30);
-        int64_t words0 = (lwords + 3) & ~(int64_t)3, slots = lslots, max_in = 0;
-        while (okw) {
-          if (ip + 4 > flen) { okw = false; break; }
-          uint32_t h; std::memcpy(&h, f + ip, 4); ip += 4;
-          if (h == 0) break;
-          const int64_t bs = h & 0x7FFFFFFFu;
-          if (bs > flen - ip || op >= ulen || bs == 0) { okw = false; break; }
-          const int64_t dl = std::min(bmax, ulen - op);
-          const bool stored = (h & 0x80000000u) != 0;
-          UnpackJob j{off + 8 + ip, (int64_t)(uintptr_t)dst + op, bs, dl, 0, stored ? 3 : 2, 0, words0 + op, slots, words0, op};
-          fj.push_back(j);
-          if (!stored) { slots += bs + 1; if (bs > max_in) max_in = bs; }
-          ip += bs + (bchk ? 4 : 0); op += dl;
-        }
-        if (okw && op == ulen && fj.size() >= 2 && words0 + ulen < ((int64_t)1 << 30) && slots < ((int64_t)1 << 30)) {
-          for (auto& j : fj) ljobs.push_back(j);
-          lwords = words0 + ulen; lslots = slots; lmax_frame = std::max(lmax_frame, ulen); lmax_in = std::max(lmax_in, max_in);
+        // one job per block of a frame of two blocks or more that stays within the resolve array's 2^30 words
+        std::vector<UnpackJob> fj;
+        const int64_t words0 = (lwords + 3) & ~(int64_t)3; int64_t slots = lslots;
+        const bool okw = lz4_pj_on && ulen > bmax && ulen < ((int64_t)1 << 30) && lz::lz4_frame_blocks(rd, hp, flen, bchk, bmax, ulen, [&](int64_t at, int64_t bs, bool stored, int64_t op, int64_t dl) -> int64_t {
+          if (dl <= 0 || bs == 0) return -1;
+          fj.push_back({off + 8 + at, (int64_t)(uintptr_t)dst + op, bs, dl, 0, stored ? UNPACK_LINKED_STORED : UNPACK_LZ4_BLOCK, 0, words0 + op, slots, words0, op});
+          if (!stored) slots += bs + 1;
+          return op + dl;
+        });
+        if (okw && fj.size() >= 2 && words0 + ulen < ((int64_t)1 << 30) && slots < ((int64_t)1 << 30)) {
+          ljobs.insert(ljobs.end(), fj.begin(), fj.end());
+          lwords = words0 + ulen; lslots = slots;
           return;
         }
         units.push_back(whole); return;
       }
-      // independent blocks: walk the block index on the host, one unit per block (all but the last assumed full; verified on the device)
-      int64_t ip = hp, op = 0; const size_t first_unit = units.size(); bool okw = true;
-      while (true) {
-        if (ip + 4 > flen) { okw = false; break; }
-        uint32_t h; std::memcpy(&h, f + ip, 4); ip += 4;
-        if (h == 0) break;
-        const int64_t bs = h & 0x7FFFFFFFu;
-        if (bs > flen - ip || op >= ulen) { okw = false; break; }
-        const int64_t dl = std::min(bmax, ulen - op);
-        units.push_back({off + 8 + ip, (int64_t)(uintptr_t)dst + op, bs, dl, (h & 0x80000000u) ? LZ4_UNIT_STORED : LZ4_UNIT_BLOCK, 0});
-        ip += bs + (bchk ? 4 : 0); op += dl;
-      }
-      if (!okw || op != ulen) { units.resize(first_unit); units.push_back(whole); }
+      // independent blocks: one unit per block
+      const size_t first_unit = units.size();
+      const bool okw = lz::lz4_frame_blocks(rd, hp, flen, bchk, bmax, ulen, [&](int64_t at, int64_t bs, bool stored, int64_t op, int64_t dl) -> int64_t {
+        if (dl <= 0) return -1;
+        units.push_back({off + 8 + at, (int64_t)(uintptr_t)dst + op, bs, dl, stored ? LZ4_UNIT_STORED : LZ4_UNIT_BLOCK, 0});
+        return op + dl;
+      });
+      if (!okw) { units.resize(first_unit); units.push_back(whole); }
       else if (units.size() - first_unit > 1) split_any = true;
     };
     struct BitFix { uint8_t* dst; int64_t bit0; const uint8_t* src; int64_t n; };          // after the decode: dst bits [bit0, +n) |= src (NULL: ones)
@@ -684,7 +675,7 @@ int gpuq_ipc_decode_stream(gpuq_ctx* ctx, void* stream, const uint8_t* bytes, in
       B->cols.push_back(std::move(col));
     }
     DevBuf dunits, dstatus, dpieces; dstatus.ensure(16);
-    DevBuf pj_resolve, pj_blk, pj_cblk, pj_jobs, pj_cnt, pj_ja, pj_jb, pj_olen, pj_mark, pj_scan;
+    UnpackScratch pj_scratch;
     // Utf8 piece descriptors of all columns in one upload
     size_t n_pieces = checks.size(); for (auto& u : utf8_cols) { n_pieces += u.pieces.size(); max_check_rows = std::max(max_check_rows, u.max_rows); }
     std::vector<size_t> piece0;
@@ -707,33 +698,7 @@ int gpuq_ipc_decode_stream(gpuq_ctx* ctx, void* stream, const uint8_t* bytes, in
         HIPCHECK(hipMemcpyAsync(dunits.p, up, sizeof(Lz4Unit) * us.size(), hipMemcpyHostToDevice, s));
         launch_lz4_decode(s, db, pos, nullptr, (const Lz4Unit*)dunits.p, (int)us.size(), dstatus.as<uint32_t>());
       }
-      if (&us == &units && !ljobs.empty()) {      // (the fallback list holds those frames as whole units)
-        std::vector<uint2> blk, cblk;
-        for (size_t k = 0; k < ljobs.size(); ++k) {
-          for (int64_t bb = 0; bb < ljobs[k].dst_len; bb += 4096) blk.push_back(make_uint2((uint32_t)k, (uint32_t)bb));
-          if (ljobs[k].mode == 2) for (int64_t bb = 0; bb <= ljobs[k].src_len; bb += 4096) cblk.push_back(make_uint2((uint32_t)k, (uint32_t)bb));
-        }
-        int rounds = 1; while (((int64_t)1 << rounds) < lmax_frame) ++rounds;
-        rounds += 1;
-        int mrounds = 1; while (((int64_t)1 << mrounds) < lmax_in + 1) ++mrounds;
-        mrounds += 1;
-        const size_t nj = ljobs.size();
-        pj_resolve.ensure((size_t)lwords * 4 + 64); pj_blk.ensure(blk.size() * sizeof(uint2) + 64); pj_cblk.ensure(cblk.size() * sizeof(uint2) + 64); pj_jobs.ensure(nj * sizeof(UnpackJob) + 64);
-        pj_cnt.ensure((size_t)(rounds + mrounds + 3) * nj * 4 + 64);
-        pj_ja.ensure((size_t)(lslots + 1) * 4 + 64); pj_jb.ensure((size_t)(lslots + 1) * 4 + 64); pj_olen.ensure((size_t)(lslots + 1) * 4 + 64); pj_mark.ensure((size_t)lslots + 64);
-        const size_t swb = exclusive_scan_ws_bytes(lslots + 1); pj_scan.ensure(swb);
-        HIPCHECK(hipMemcpyAsync(pj_jobs.p, ljobs.data(), nj * sizeof(UnpackJob), hipMemcpyHostToDevice, s));
-        HIPCHECK(hipMemcpyAsync(pj_blk.p, blk.data(), blk.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
-        if (!cblk.empty()) HIPCHECK(hipMemcpyAsync(pj_cblk.p, cblk.data(), cblk.size() * sizeof(uint2), hipMemcpyHostToDevice, s));
-        HIPCHECK(hipMemsetAsync(pj_cnt.p, 0, (size_t)(rounds + mrounds + 3) * nj * 4, s));
-        HIPCHECK(hipMemsetAsync(pj_mark.p, 0, (size_t)lslots + 64, s));
-        SnappyPjBuffers PB{};
-        PB.resolve = (uint32_t*)pj_resolve.p; PB.blkmap = (const uint2*)pj_blk.p; PB.n_blocks = (int)blk.size(); PB.rounds = rounds;
-        PB.jump_a = (uint32_t*)pj_ja.p; PB.jump_b = (uint32_t*)pj_jb.p; PB.olen = (uint32_t*)pj_olen.p; PB.mark = (uint8_t*)pj_mark.p; PB.cmap = (const uint2*)pj_cblk.p; PB.n_cblocks = (int)cblk.size();
-        PB.mark_rounds = mrounds; PB.c_slots = lslots; PB.scan_ws = pj_scan.p; PB.scan_ws_bytes = swb; PB.counts = (uint32_t*)pj_cnt.p;
-        launch_unpack_pages_pj(s, db, nullptr, (const UnpackJob*)pj_jobs.p, (int)nj, PB, dstatus.as<uint32_t>());
-        HIPCHECK(hipStreamSynchronize(s));      // the block maps are pageable host memory
-      }
+      if (&us == &units) unpack_pages_parallel(s, db, nullptr, ljobs.data(), (int)ljobs.size(), pj_scratch, dstatus.as<uint32_t>());      // (the fallback list holds those frames as whole units)
       for (auto& x : copyfix) HIPCHECK(hipMemcpyAsync(x.dst, x.src, (size_t)x.n, hipMemcpyDeviceToDevice, s));
       for (auto& x : bitfix) launch_concat_bitmap(s, (u64*)x.dst, x.bit0, x.src, 0, x.n);
       // untrusted offsets: monotone, from >= 0, ending inside their data buffer -- before anything is derived from them

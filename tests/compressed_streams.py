@@ -654,7 +654,7 @@ def _frames_fixed():
     B = 65536
     rng = np.random.default_rng(7)
     add("linked_stored_x2", Lz4Frame().stored(R(1, B)).stored(R(2, 1000)),
-        "linked frame of two stored blocks, the last partial: no compressed block, so launch_unpack_pages_pj has an empty cmap (ADVICE: output left unwritten, status 0)")
+        "linked frame of two stored blocks, the last partial: no compressed block, so unpack_pages_parallel has an empty cmap (ADVICE: output left unwritten, status 0)")
     add("linked_stored_x3", Lz4Frame().stored(R(3, B)).stored(R(4, B)).stored(R(5, 4)), "three stored blocks, a 4-byte last one")
     f = Lz4Frame().stored(R(6, B))
     f.add(f.new_block().seq(b"", 65535, 400).seq(R(7, 5), 65535, 4).seq(b"", 1, 70).end())
@@ -764,7 +764,7 @@ def _edit(data, at, new):
 
 def _malformed():
     """One targeted edit of a valid stream each.  The reason names the line that refuses it (parallel path, the default;
-    K = csrc/kernels_lz4.hip, H = csrc/shuffle_codec.cpp); both CPU judges reject every one of them.
+    K = csrc/kernels_lz4.hip, H = csrc/shuffle_codec.cpp, P = csrc/lz_elements.h, the format parsers both of them call); both CPU judges reject every one of them.
 
     Taken out because the judges disagree (reference decoder / library):
       lz4_raw offset 0 and lz4_frame offset 0 (one block, and in the second linked block): Malformed / liblz4 1.10 decodes
@@ -784,15 +784,15 @@ def _malformed():
         C.append(Case("snappy/bad_" + name, plain, stream, "snappy", "malformed", reason))
     sn("offset0", _edit(good, cp + 1, b"\x00\x00"), "K k_sn_fill: `e.off == 0`")
     sn("offset_position_plus1", _edit(good, cp + 1, b"\x09\x00"), "K k_sn_fill: `(int64_t)e.off > o` (9 bytes back from output position 8)")
-    sn("preamble_plus1", _edit(good, 0, bytes([len(plain) + 1])), "K k_sn_head: `(int64_t)ulen != out_len` (the page header announces the true length)")
-    sn("preamble_minus1", _edit(good, 0, bytes([len(plain) - 1])), "K k_sn_head: `(int64_t)ulen != out_len`")
-    sn("last_literal_truncated", good[:-1], "K k_sn_next: `p + e.size > L` marks the element SN_BAD, k_sn_lens flags it on the path")
+    sn("preamble_plus1", _edit(good, 0, bytes([len(plain) + 1])), "K k_sn_head: `H.ulen != out_len` (the page header announces the true length)")
+    sn("preamble_minus1", _edit(good, 0, bytes([len(plain) - 1])), "K k_sn_head: `H.ulen != out_len`")
+    sn("last_literal_truncated", good[:-1], "P sn_element: `len > L - q`, so K k_sn_next marks the element SN_BAD and k_sn_lens flags it on the path")
     s2 = Snappy().lit(R(3, 8)).copy2(4, 8)
-    C.append(Case("snappy/bad_last_copy_truncated", s2.plain(), s2.stream()[:-1], "snappy", "malformed", "K k_sn_next: `p + e.size > L` (a copy-2 with one offset byte), flagged by k_sn_lens"))
+    C.append(Case("snappy/bad_last_copy_truncated", s2.plain(), s2.stream()[:-1], "snappy", "malformed", "P sn_element: `q + 2 > L` (a copy-2 with one offset byte): SN_BAD in K k_sn_next, flagged by k_sn_lens"))
     s4 = Snappy().lit(R(3, 8)).copy4(4, 8)
-    C.append(Case("snappy/bad_last_copy4_truncated", s4.plain(), s4.stream()[:-1], "snappy", "malformed", "K k_sn_next: `p + e.size > L` (a copy-4 with three offset bytes), flagged by k_sn_lens"))
-    sn("literal_past_page", _edit(good, 1 + s.elems[2][0], bytes([(30 - 1) << 2])), "K k_sn_next: `p + e.size > L` (a 30-byte literal with 4 bytes left), flagged by k_sn_lens")
-    sn("literal_w4_past_page", good[:1 + s.elems[2][0]] + bytes([63 << 2]) + b"\xff\xff\xff\x7f" + R(2, 4), "K k_sn_next: `p + e.size > L` with a 2^31-byte length field")
+    C.append(Case("snappy/bad_last_copy4_truncated", s4.plain(), s4.stream()[:-1], "snappy", "malformed", "P sn_element: `q + 4 > L` (a copy-4 with three offset bytes): SN_BAD in K k_sn_next, flagged by k_sn_lens"))
+    sn("literal_past_page", _edit(good, 1 + s.elems[2][0], bytes([(30 - 1) << 2])), "P sn_element: `len > L - q` (a 30-byte literal with 4 bytes left): SN_BAD in K k_sn_next, flagged by k_sn_lens")
+    sn("literal_w4_past_page", good[:1 + s.elems[2][0]] + bytes([63 << 2]) + b"\xff\xff\xff\x7f" + R(2, 4), "P sn_element: `len > L - q` with a 2^31-byte length field (the length is 64-bit)")
     sn("copy4_offset_2_31", good[:cp] + bytes([3 | (7 << 2)]) + b"\x00\x00\x00\x80" + good[cp + 3:], "K k_sn_fill: `(int64_t)e.off > o` with offset 2^31 (unsigned compare)")
     sn("output_one_short", good[:1 + s.elems[2][0]] + bytes([(3 - 1) << 2]) + R(2, 3), "K k_sn_fill: `o != out_len` at the terminal position")
     # -- LZ4_RAW pages: seq(lit 8, off 4, ml 8) | final literals 12
@@ -803,12 +803,12 @@ def _malformed():
     def lz(name, stream, reason, plain=plainb):
         C.append(Case("lz4_raw/bad_" + name, plain, stream, "lz4_raw", "malformed", reason))
     lz("offset_position_plus1", _edit(goodb, op, b"\x09\x00"), "K k_sn_fill: `(int64_t)e.off > at`")
-    lz("last_literals_truncated", goodb[:-1], "K lz4_element: `lit > L - q`, so k_sn_next marks SN_BAD and k_sn_lens flags it")
-    lz("literal_length_past_page", _edit(goodb, b.seqs[1][0], b"\xf0\x40"), "K lz4_element: `lit > L - q` (79 literals announced, 12 present)")
+    lz("last_literals_truncated", goodb[:-1], "P lz4_sequence: `lit > L - q`, so K k_sn_next marks SN_BAD and k_sn_lens flags it")
+    lz("literal_length_past_page", _edit(goodb, b.seqs[1][0], b"\xf0\x40"), "P lz4_sequence: `lit > L - q` (79 literals announced, 12 present)")
     b2 = Lz4Block().seq(R(5, 8), 4, 300)
-    lz("match_run_cut_by_block_end", b2.block()[:-1], "K lz4_element: `if (q >= L) return e` inside the match length run", b2.plain())
+    lz("match_run_cut_by_block_end", b2.block()[:-1], "P lz4_length_run: `q >= L` inside the match length run", b2.plain())
     b3 = Lz4Block().seq(R(5, 8), 4, 8)
-    lz("offset_cut_by_block_end", b3.block()[:-1], "K lz4_element: `q + 2 > L`", b3.plain())
+    lz("offset_cut_by_block_end", b3.block()[:-1], "P lz4_sequence: `q + 2 > L`", b3.plain())
     # -- LZ4 frames
     f = Lz4Frame()
     f.add(f.new_block().seq(R(7, 8), 4, 300).end())
@@ -818,12 +818,12 @@ def _malformed():
     def fr(name, stream, reason, plain=plainf, expect="malformed"):
         C.append(Case("lz4_frame/bad_" + name, plain, stream, "lz4_frame", expect, reason))
     fr("match_before_frame_start", _edit(goodf, blk0 + 9, b"\x09\x00"), "K lz4_decode_block: `offset > op - out_lo`")
-    fr("block_size_past_frame", _edit(goodf, f.marks[0], struct.pack("<I", len(goodf))), "K k_lz4_decode: `bs > iend - ip` (H emit: a one-block frame is a whole-frame unit)")
+    fr("block_size_past_frame", _edit(goodf, f.marks[0], struct.pack("<I", len(goodf))), "P lz4_frame_blocks: `bs > iend - ip` on the host (H emit: the frame becomes a whole-frame unit), then K k_lz4_decode: `bs > iend - ip`")
     g2 = Lz4Frame()
     g2.add(g2.new_block().seq(R(8, 8), 4, 300))
     fr("match_run_cut_by_block_end", _edit(g2.frame(), g2.marks[0], struct.pack("<I", len(g2.blocks[0][1]) - 1))[:g2.marks[0] + 4 + len(g2.blocks[0][1]) - 1] + b"\x00\x00\x00\x00",
        "K lz4_decode_block: `ip >= iend` inside the match length run", g2.plain())
-    fr("missing_endmark", goodf[:-4], "K k_lz4_decode: `ip + 4 > iend` where a block header or the EndMark is expected")
+    fr("missing_endmark", goodf[:-4], "P lz4_frame_blocks: `ip + 4 > iend` where a block header or the EndMark is expected (H emit), then K k_lz4_decode: `ip + 4 > iend`")
     g3 = Lz4Frame()
     first = g3.new_block().seq(R(9, 8), 4, 300)
     g3x = first.seqs[0][1]
@@ -833,7 +833,7 @@ def _malformed():
     g4 = Lz4Frame()
     g4.stored(R(10, 65536)).stored(R(11, 1000))
     fr("linked_stored_block_size_past_frame", _edit(g4.frame(), g4.marks[1], struct.pack("<I", 0x80000000 | 5000)),
-       "H emit: `bs > flen - ip` keeps the frame off the parallel path, then K k_lz4_decode: `bs > iend - ip`", g4.plain())
+       "P lz4_frame_blocks: `bs > iend - ip` in H emit keeps the frame off the parallel path, then K k_lz4_decode: `bs > iend - ip`", g4.plain())
     g5 = Lz4Frame(dict_id=0x11223344)
     g5.add(g5.new_block().seq(R(7, 8), 4, 300).end())
     fr("dictionary_id", g5.frame(), "H emit: `if (has_dict) throw Unsupported`", g5.plain(), expect="unsupported")

@@ -1,8 +1,12 @@
 """The hand-assembled Snappy / LZ4 corpus of compressed_streams.py is right before any kernel sees it: the plaintext by
 construction, the small reference decoders and liblz4 / libsnappy (through pyarrow) agree on every case; the Parquet and IPC
 containers read back through Arrow C++ and the project's own host-side footer walk; and the corpus still holds the elements no
-encoder emits.  No GPU."""
+encoder emits; and the format parsers the kernels share (csrc/lz_elements.h), as a stand-alone program under AddressSanitizer and UBSan,
+decode every valid Snappy and LZ4_RAW case byte for byte and refuse every malformed one within bounds.  No GPU."""
 import io
+import os
+import struct
+import subprocess
 
 import numpy as np
 import pyarrow as pa
@@ -13,6 +17,7 @@ import arrow_ballista_amd as g
 import compressed_streams as cs
 
 LIB = {"snappy": "snappy", "lz4_raw": "lz4_raw", "lz4_frame": "lz4"}
+CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "arrow-ballista_amd", "csrc")
 
 
 def py_decode(c):
@@ -164,3 +169,89 @@ def test_the_corpus_still_covers_what_no_encoder_emits():
     assert stored_only >= 2, "no linked frame with zero compressed blocks"
     assert nonfull_inner >= 2, "no linked frame with a non-full inner block"
     assert stored_in_linked >= 2 and with_bchk >= 3 and with_csize >= 3 and with_cchk >= 3 and bsids == {4, 5, 6, 7}
+
+
+# ---- the shared parsers themselves: a plain-pointer reader, a serial expansion loop, stand-alone, under the sanitizers
+HOST_PROGRAM = r"""
+#include "lz_elements.h"
+#include <cstdio>
+#include <cstring>
+#include <string>
+using namespace gpuq::lz;
+// the checks that depend on where the output stands are the caller's, as in the kernels
+static bool snappy(const unsigned char* in, int64_t L, unsigned char* out, int64_t n) {
+  const auto rd = [&](int64_t a) { return in[a]; };
+  const SnHead H = sn_preamble(rd, L);
+  if (!H.ok || H.ulen != n) return false;
+  int64_t ip = H.start, op = 0;
+  while (ip < L) {
+    const SnElem e = sn_element(rd, ip, L);
+    if (!e.ok || (int64_t)e.olen > n - op) return false;
+    if (e.copy) {
+      if (e.off == 0 || (int64_t)e.off > op) return false;
+      for (uint32_t i = 0; i < e.olen; ++i) out[op + i] = out[op + i - e.off];
+    } else std::memcpy(out + op, in + e.lit, e.olen);
+    ip += e.size; op += e.olen;
+  }
+  return op == n;
+}
+static bool lz4_block(const unsigned char* in, int64_t L, unsigned char* out, int64_t n) {
+  const auto rd = [&](int64_t a) { return in[a]; };
+  int64_t ip = 0, op = 0;
+  while (ip < L) {
+    const Lz4Seq e = lz4_sequence(rd, ip, L, L - ip, n - op);
+    if (!e.ok) return false;
+    std::memcpy(out + op, in + e.lit, (size_t)e.lit_len); op += e.lit_len; ip += e.size;
+    if (e.last) break;
+    if (e.off == 0 || (int64_t)e.off > op || e.match_len > n - op) return false;
+    for (int64_t i = 0; i < e.match_len; ++i) out[op + i] = out[op + i - e.off];
+    op += e.match_len;
+  }
+  return op == n;
+}
+// corpus file: per case  u32 name length, name, u8 kind (0 snappy, 1 lz4_raw), u64 stream length, stream, u64 plaintext length, plaintext
+// prints per case: name <tab> E exact, R refused, W accepted with other bytes
+int main(int argc, char** argv) {
+  if (argc < 2) return 2;
+  FILE* f = std::fopen(argv[1], "rb");
+  if (!f) return 2;
+  for (;;) {
+    uint32_t nl; if (std::fread(&nl, 4, 1, f) != 1) break;
+    std::string name(nl, ' '); uint8_t kind; uint64_t sl, pl;
+    if (std::fread(&name[0], 1, nl, f) != nl || std::fread(&kind, 1, 1, f) != 1 || std::fread(&sl, 8, 1, f) != 1) return 2;
+    unsigned char* in = new unsigned char[sl];      // exact-size heap buffers: an overrun is ASan's
+    if (std::fread(in, 1, sl, f) != sl || std::fread(&pl, 8, 1, f) != 1) return 2;
+    unsigned char* want = new unsigned char[pl];
+    if (std::fread(want, 1, pl, f) != pl) return 2;
+    unsigned char* out = new unsigned char[pl]; std::memset(out, 0xA5, pl);
+    const bool ok = kind == 0 ? snappy(in, (int64_t)sl, out, (int64_t)pl) : lz4_block(in, (int64_t)sl, out, (int64_t)pl);
+    std::printf("%s\t%c\n", name.c_str(), !ok ? 'R' : (std::memcmp(out, want, pl) == 0 ? 'E' : 'W'));
+    delete[] in; delete[] want; delete[] out;
+  }
+  std::fclose(f);
+  return 0;
+}
+"""
+
+
+def test_host_build_of_the_parsers_under_sanitizers(tmp_path):
+    """Every snappy and lz4_raw case of the corpus through csrc/lz_elements.h: valid ones byte exact, malformed ones refused, and a clean
+    exit -- no read outside the exact-size buffers, no undefined behaviour.  (lz4_frame cases: their container checks are emit()'s.)"""
+    todo = [c for c in cs.corpus() if c.kind in ("snappy", "lz4_raw")]
+    assert len(todo) == len(cs.cases("snappy")) + len(cs.cases("lz4_raw")) and {c.expect for c in todo} == {"valid", "malformed"}
+    src, exe, path = str(tmp_path / "lz_host.cpp"), str(tmp_path / "lz_host"), str(tmp_path / "corpus.bin")
+    with open(src, "w") as f:
+        f.write(HOST_PROGRAM)
+    # the sanitizers' runtimes linked statically: the program starts in any environment, whatever that environment preloads
+    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan",
+                        "-I", CSRC, src, "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    with open(path, "wb") as f:
+        for c in todo:
+            n = c.name.encode()
+            f.write(struct.pack("<I", len(n)) + n + bytes([c.kind == "lz4_raw"]) + struct.pack("<Q", len(c.stream)) + c.stream + struct.pack("<Q", len(c.plaintext)) + c.plaintext)
+    r = subprocess.run([exe, path], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, "the sanitised host build stopped:\n" + r.stdout[-1500:] + r.stderr[-6000:]
+    got = dict(line.split("\t") for line in r.stdout.splitlines())
+    assert list(got) == [c.name for c in todo]
+    assert [c.name + ": " + got[c.name] for c in todo if got[c.name] != {"valid": "E", "malformed": "R"}[c.expect]] == []
