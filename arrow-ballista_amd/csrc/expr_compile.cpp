@@ -579,7 +579,131 @@ NodeP ExprCompiler::from_json(const Json& e) {
       if (len < 0 || (args.size() == 3 && len > 15)) throw Unsupported("substr: a length outside 0..15");
       return raw(OP_SUBSTR, mk(T_UTF8), x->nullable, 127, {x}, (uint32_t)(start - 1) | ((uint32_t)len << 8));
     }
-    throw Unsupported("scalar function '" + nm + "' is not built on the device (date_part, substr are)");
+    // The conditional, rounding and sign functions.  Three opcodes of their own (OP_FFLOOR / OP_FCEIL / OP_FTRUNC); the rest is composed
+    // from OP_SELECT, OP_ISNOTNULL, the compares, OP_BAND / OP_BOR over a float's re-typed pattern (OP_MOV aliases the register) and OP_FSQRT.
+    auto argn = [&](size_t lo, size_t hi, const char* sig) {
+      if (args.size() < lo || args.size() > hi) throw std::runtime_error(nm + " takes " + sig);
+    };
+    auto refuse = [&](const NodeP& x, const char* takes) { throw Unsupported(nm + " over " + x->type.to_string() + " (" + takes + ")"); };
+    // a float operand as it is, an integer one cast to Float64 (datafusion's coercion of the math functions [UPSTREAM-KNOWLEDGE]); a decimal
+    // arrives under the plan's own cast to Float64 and is refused by name without it
+    auto float_arg = [&](NodeP x) -> NodeP {
+      if (x->type.is_float()) return x;
+      if (x->type.is_int()) return cast(x, mk(T_FLOAT64));
+      refuse(x, x->type.is_decimal() ? "Float32 / Float64 and the integers: cast the decimal to Float64" : "Float32 / Float64 and the integers");
+      return x;
+    };
+    const u64 ABS_MASK = 0x7FFFFFFFFFFFFFFFull, INF_BITS = 0x7FF0000000000000ull;
+    // |x|'s pattern as an Int64 in 0 .. 2^63 - 1 (a Float32 lives in a register as the double of its value: the same bit)
+    auto magnitude = [&](NodeP x) { return raw(OP_BAND, mk(T_INT64), x->nullable, 64, {raw(OP_MOV, mk(T_INT64), x->nullable, 64, {x}), lit_int(mk(T_INT64), (i128)ABS_MASK)}); };
+    // integer compares of that pattern: OP_FNE / OP_FEQ are total-order compares, under which NaN equals itself
+    auto isnan_of = [&](NodeP x) { return raw(OP_GT, mk(T_BOOL), x->nullable, 2, {magnitude(x), lit_int(mk(T_INT64), (i128)INF_BITS)}); };
+    // round half away from zero, the sign of zero kept (Rust's f64::round): with a = |x| and t = trunc(a), a - t is exact, the magnitude is
+    // t + (a - t >= 0.5 ? 1.0 : 0.0) -- the compare on the difference's pattern, which orders as the non-negative doubles do -- and x's
+    // sign bit is put back with an OR, so that round(-0.3) is -0.0.  inf: a - t is NaN, either outcome of the compare leaves inf.
+    auto round_of = [&](NodeP x) -> NodeP {
+      const DType i64t = mk(T_INT64), f64t = mk(T_FLOAT64);
+      const bool nb = x->nullable;
+      NodeP sign = raw(OP_BAND, i64t, nb, 64, {raw(OP_MOV, i64t, nb, 64, {x}), lit_int(i64t, (i128)(ABS_MASK + 1))});
+      NodeP a = raw(OP_MOV, f64t, nb, 127, {magnitude(x)});
+      NodeP t = raw(OP_FTRUNC, f64t, nb, 127, {a});
+      NodeP d = raw(OP_FSUB, f64t, nb, 127, {a, t});
+      NodeP up = raw(OP_GE, mk(T_BOOL), nb, 2, {raw(OP_MOV, i64t, nb, 64, {d}), lit_int(i64t, (i128)0x3FE0000000000000ull)});
+      NodeP r = raw(OP_FADD, f64t, nb, 127, {t, raw(OP_SELECT, f64t, false, 127, {up, lit_f64(1.0), lit_f64(0.0)})});
+      return raw(OP_MOV, x->type, nb, 127, {raw(OP_BOR, i64t, nb, 64, {raw(OP_MOV, i64t, nb, 64, {r}), sign})});
+    };
+    if (nm == "coalesce") {
+      if (args.empty()) throw std::runtime_error("coalesce takes (x1, ..., xn), n >= 1");
+      std::vector<NodeP> xs;
+      for (const Json& a : args) xs.push_back(from_json(a));
+      DType t = mk(T_NULL);
+      for (auto& x : xs) if (x->type.id != T_NULL) { t = x->type; break; }
+      for (auto& x : xs) {
+        if (x->type.id == T_NULL) x = lit_null(t);
+        if (x->type != t) throw Unsupported("coalesce over mixed types " + t.to_string() + ", " + x->type.to_string() + " (the plan carries the coercion casts)");
+      }
+      // the first argument that cannot be NULL ends the list; the result is nullable iff every argument is
+      size_t n = xs.size();
+      for (size_t i = 0; i < xs.size(); ++i) if (!xs[i]->nullable) { n = i + 1; break; }
+      NodeP acc = xs[n - 1];
+      for (size_t i = n - 1; i-- > 0;) acc = raw(OP_SELECT, t, acc->nullable, std::max(xs[i]->bits, acc->bits), {is_null(xs[i], true), xs[i], acc});
+      return acc;
+    }
+    if (nm == "nullif") {
+      argn(2, 2, "(a, b)");
+      NodeP a = from_json(args[0]), b = from_json(args[1]);
+      if (b->type.id == T_NULL) b = lit_null(a->type);
+      if (a->type.id == T_NULL || a->type != b->type) throw Unsupported("nullif over " + a->type.to_string() + ", " + b->type.to_string() + " (two arguments of one type)");
+      // the engine's own '=' (floats: total order); a NULL comparison is not true and leaves a
+      return raw(OP_SELECT, a->type, true, a->bits, {binary("=", a, b), lit_null(a->type), a});
+    }
+    if (nm == "isnan" || nm == "iszero") {
+      argn(1, 1, "(x)");
+      NodeP x = from_json(args[0]);
+      if (!x->type.is_float()) refuse(x, "Float32 and Float64");
+      if (nm == "isnan") return isnan_of(x);
+      return raw(OP_EQ, mk(T_BOOL), x->nullable, 2, {magnitude(x), lit_int(mk(T_INT64), 0)});      // +0 and -0
+    }
+    if (nm == "nanvl") {
+      argn(2, 2, "(x, y)");
+      NodeP x = from_json(args[0]), y = from_json(args[1]);
+      if (!x->type.is_float()) refuse(x, "Float32 and Float64");
+      if (y->type.id == T_NULL) y = lit_null(x->type);
+      if (y->type != x->type) throw Unsupported("nanvl over " + x->type.to_string() + ", " + y->type.to_string() + " (two floats of one type)");
+      // NULL if either side is (datafusion's binary math kernels [UPSTREAM-KNOWLEDGE]); a NULL x fails isnan(x) and is taken as it is
+      NodeP z = raw(OP_SELECT, x->type, x->nullable || y->nullable, 127, {isnan_of(x), y, x});
+      if (y->nullable) z = raw(OP_SELECT, x->type, true, 127, {is_null(y, false), lit_null(x->type), z});
+      return z;
+    }
+    if (nm == "abs") {
+      argn(1, 1, "(x)");
+      NodeP x = from_json(args[0]);
+      if (x->type.is_float()) return raw(OP_MOV, x->type, x->nullable, 127, {magnitude(x)});      // the sign bit cleared: NaN and -0.0 included
+      if (x->type.is_unsigned()) return x;
+      // -x wraps at the type's minimum like the engine's integer arithmetic (abs(-128) = -128 for an Int8); a decimal's does not leave its precision
+      if (x->type.is_int() || x->type.is_decimal())
+        return raw(OP_SELECT, x->type, x->nullable, x->bits, {raw(OP_LT, mk(T_BOOL), x->nullable, 2, {x, lit_int(x->type, 0)}), negative(x), x});
+      refuse(x, "the integers, Float32 / Float64 and Decimal128");
+    }
+    if (nm == "signum") {
+      argn(1, 1, "(x)");
+      NodeP x = float_arg(from_json(args[0]));
+      // total order: x > +0.0 holds for the positive values (and +NaN), x < -0.0 for the negative ones (and -NaN); NaN is taken out first
+      auto f = [&](double v) { return x->type.id == T_FLOAT32 ? lit_f32((float)v) : lit_f64(v); };
+      NodeP neg = raw(OP_SELECT, x->type, x->nullable, 127, {raw(OP_FLT, mk(T_BOOL), x->nullable, 2, {x, f(-0.0)}), f(-1.0), f(0.0)});
+      NodeP pos = raw(OP_SELECT, x->type, x->nullable, 127, {raw(OP_FGT, mk(T_BOOL), x->nullable, 2, {x, f(0.0)}), f(1.0), neg});
+      NodeP z = raw(OP_SELECT, x->type, x->nullable, 127, {isnan_of(x), x, pos});
+      // a NULL x fails all three tests and would come out as 0.0: the outer select puts the NULL back
+      return x->nullable ? raw(OP_SELECT, x->type, true, 127, {is_null(x, true), z, x}) : z;
+    }
+    if (nm == "ceil" || nm == "floor" || nm == "trunc" || nm == "round" || nm == "sqrt") {
+      const bool is_round = nm == "round";
+      argn(1, is_round ? 2 : 1, is_round ? "(x [, n])" : "(x)");
+      NodeP x = float_arg(from_json(args[0]));
+      const bool f32 = x->type.id == T_FLOAT32;
+      auto r32 = [&](NodeP z) { return f32 ? raw(OP_F32R, x->type, z->nullable, 127, {z}) : z; };
+      if (nm == "sqrt") return r32(raw(OP_FSQRT, mk(T_FLOAT64), x->nullable, 127, {x}));      // Float32: the double's root rounded once more is the float's root
+      // integral results are exact in either width: no OP_F32R
+      if (!is_round) return raw(nm == "ceil" ? OP_FCEIL : nm == "floor" ? OP_FFLOOR : OP_FTRUNC, x->type, x->nullable, 127, {x});
+      if (args.size() == 1) return round_of(x);
+      // round(x, n) = round(x * 10^n) / 10^n with 10^n an exact double for n <= 22.  Float32: the factor is the float nearest 10^n and each of
+      // the multiply and the divide is rounded to float (a product of two floats is exact in a double, a quotient rounds innocuously)
+      const Json& a1 = args[1];
+      const bool int_lit = a1.is_obj() && a1.o.size() == 1 && a1.o[0].first == "literal" && dtype_from_json(a1.o[0].second.at("type")).is_int();
+      if (!int_lit) throw Unsupported("round(x, n): n must be a non-NULL integer literal");
+      const i128 nd = parse_i128(lit_arg(a1, "n").s);
+      if (nd < 0 || nd > 22) throw Unsupported("round(x, n): n outside 0..22 (10^n must be an exact double)");
+      if (nd == 0) return round_of(x);
+      double p10 = 1.0;
+      for (int k = 0; k < (int)nd; ++k) p10 *= 10.0;      // exact at every step up to 10^22
+      NodeP f = f32 ? cast(lit_f32((float)p10), mk(T_FLOAT64)) : lit_f64(p10);
+      NodeP xd = cast(x, mk(T_FLOAT64));
+      NodeP m = r32(raw(OP_FMUL, mk(T_FLOAT64), x->nullable, 127, {xd, f}));
+      NodeP q = raw(OP_FDIV, mk(T_FLOAT64), x->nullable, 127, {round_of(cast(m, mk(T_FLOAT64))), f});
+      return f32 ? r32(q) : q;
+    }
+    throw Unsupported("scalar function '" + nm + "' is not built on the device (date_part, substr, coalesce, nullif, nanvl, isnan, iszero, abs, signum, "
+                      "ceil, floor, trunc, round, sqrt are)");
   }
   if (kind == "case_") {
     NodeP base = v.has("expr") ? from_json(v.at("expr")) : nullptr;
@@ -875,10 +999,17 @@ std::string ExprCompiler::jit_source(const CompiledProgram& C, const std::vector
   }
   // ---- expressions
   int vid = 0;
-  auto V = [&](const NodeP& x) { return name.at(rep(x.get())); };
+  // (an OP_MOV that re-types a float's pattern as an integer or back -- abs, isnan, iszero -- aliases a variable of the other C type: the
+  // operand is read through a bit cast there)
+  auto V = [&](const NodeP& x) {
+    Node* r = rep(x.get());
+    if (is_f(x.get()) && !is_f(r) && !is_str(r)) return "__longlong_as_double((i64)" + name.at(r) + ")";
+    if (!is_f(x.get()) && is_f(r) && !is_str(x.get())) return "__double_as_longlong(" + name.at(r) + ")";
+    return name.at(r);
+  };
   auto N = [&](const NodeP& x) { return nul.at(rep(x.get())); };
   auto orn = [&](std::initializer_list<std::string> xs) { std::string r; for (auto& x : xs) if (x != "false") r += (r.empty() ? "" : " || ") + x; return r.empty() ? std::string("false") : r; };
-  auto as128 = [&](const NodeP& x) { Node* r = rep(x.get()); return is_str(r) ? "mk128(" + name.at(r) + "_lo, " + name.at(r) + "_hi)" : "(i128)" + name.at(r); };
+  auto as128 = [&](const NodeP& x) { Node* r = rep(x.get()); return is_str(r) ? "mk128(" + name.at(r) + "_lo, " + name.at(r) + "_hi)" : "(i128)" + V(x); };
   Node* predn = pred_ ? rep(pred_.get()) : nullptr;
   bool pred_done = false;
   auto emit_pred = [&]() { if (predn && !pred_done && name.count(predn)) { L("if (" + (nul.at(predn) == "false" ? std::string("") : "(" + nul.at(predn) + ") || ") + "!" + name.at(predn) + ") return false;"); pred_done = true; } };
@@ -978,6 +1109,9 @@ std::string ExprCompiler::jit_source(const CompiledProgram& C, const std::vector
       case OP_BOR: e = "(" + as128(a) + " | " + as128(b) + ")"; break;
       case OP_BAND: e = "(" + as128(a) + " & " + as128(b) + ")"; break;
       case OP_BXOR: e = "(" + as128(a) + " ^ " + as128(b) + ")"; break;
+      case OP_FFLOOR: e = "floor(" + V(a) + ")"; ne = N(a); break;
+      case OP_FCEIL: e = "ceil(" + V(a) + ")"; ne = N(a); break;
+      case OP_FTRUNC: e = "trunc(" + V(a) + ")"; ne = N(a); break;
       case OP_WRAP: e = "wrap_int((i128)" + V(a) + ", " + std::to_string(n->imm) + "u)"; ne = N(a); break;
       case OP_ADDC: case OP_SUBC: case OP_MULC: {
         L("bool " + t + "_o; const i128 " + t + "_v = checked_arith(" + std::to_string(n->op) + ", " + as128(a) + ", " + as128(b) + ", " + ((n->imm & 1u) ? "true" : "false") + ", " + t + "_o);");

@@ -13,6 +13,11 @@
 //   integer + - *, NEGATIVE and integer casts wrap at the node's type width at every node (OP_WRAP); x/0 -> NULL,
 //   INT_MIN / -1 -> INT_MIN, INT_MIN % -1 -> 0
 //   & | ^ take two integers of one type and give that type (OP_BAND / OP_BOR / OP_BXOR over both register halves: no wrap needed)
+//   scalar functions (names without regard to case; from_json, scalar_function):
+//     coalesce(x1..xn): one type, nullable iff every argument is      nullif(a, b): a's type, always nullable, NULL where a = b (floats: total order)
+//     nanvl(x, y), isnan(x), iszero(x): Float32 / Float64 (NULL if an argument is)      abs(x): integers (wraps at the minimum), floats, Decimal128
+//     signum, ceil, floor, trunc, round(x [, literal n in 0..22]), sqrt: Float32 -> Float32, Float64 -> Float64, an integer is cast to Float64 first;
+//     round is half away from zero and keeps the sign of zero; round(x, n) = round(x * 10^n) / 10^n, in Float32 arithmetic for a Float32
 //   a decimal result beyond the 38 digits its type is capped at, or an operand whose rescale by 10^k leaves 127 bits,
 //   is an error at run time (OP_ADDC / OP_SUBC / OP_MULC raise FLAG_DEC_OVERFLOW; arrow-arith raises there)
 #pragma once

@@ -89,6 +89,11 @@ enum Op : uint8_t {
   // Both halves are combined, so two correctly sign- / zero-extended values give a correctly extended result.  NULL if either side is.
   OP_BAND,    // dst <- a & b
   OP_BXOR,    // dst <- a ^ b
+  // The scalar functions' own opcodes (everything else they need is composed from the ones above; expr_compile.cpp, scalar_function).
+  // Rounding to an integral double: f64 in lo, NULL iff the operand is.  Exact, so a Float32 operand needs no OP_F32R behind them.
+  // (There is no OP_FROUND: a round() case here cost two interpreter kernels an occupancy step -- DESIGN.md, the interpreter's resource
+  // table -- so round-half-away is composed from OP_FTRUNC and the integer opcodes over the float's pattern, expr_compile.cpp.)
+  OP_FFLOOR, OP_FCEIL, OP_FTRUNC,
 };
 
 struct DevInsn { uint8_t op, dst, a, b; uint32_t imm; };
@@ -489,6 +494,9 @@ __device__ __forceinline__ void run_program(const DevProgram& P, GPUQ_REGS_PARAM
       case OP_NULLIF0: zlo = alo; zhi = ahi; zn = an || bn || (blo == 0 && bhi == 0); break;
       case OP_COALESCE0: zlo = an ? 0 : alo; zhi = an ? 0 : ahi; zn = false; break;
       case OP_WRAP: { const i128 z = wrap_int(mk128(alo, ahi), imm); zlo = (u64)z; zhi = (u64)((u128)z >> 64); zn = an; break; }
+      case OP_FFLOOR: zlo = (u64)__double_as_longlong(floor(__longlong_as_double((i64)alo))); zn = an; break;
+      case OP_FCEIL: zlo = (u64)__double_as_longlong(ceil(__longlong_as_double((i64)alo))); zn = an; break;
+      case OP_FTRUNC: zlo = (u64)__double_as_longlong(trunc(__longlong_as_double((i64)alo))); zn = an; break;
       case OP_ADDC: case OP_SUBC: case OP_MULC: {
         bool over; const i128 z = checked_arith(op, mk128(alo, ahi), mk128(blo, bhi), (imm & 1u) != 0, over);
         zlo = (u64)z; zhi = (u64)((u128)z >> 64);

@@ -109,9 +109,60 @@ def like(e, pattern, negated=False, case_insensitive=False):
 
 
 def scalar_function(name, args):
-    """PhysicalScalarFunctionNode (datafusion.proto): built on the device are date_part('YEAR' | 'MONTH' | 'DAY', Date32) -> Float64 and
-    substr(Utf8, start [, length]) with literal bounds (ASCII)."""
+    """PhysicalScalarFunctionNode (datafusion.proto): built on the device are date_part('YEAR' | 'MONTH' | 'DAY', Date32) -> Float64,
+    substr(Utf8, start [, length]) with literal bounds (ASCII), and the conditional, rounding and sign functions below."""
     return {"scalar_function": {"name": name, "args": list(args)}}
+
+
+def coalesce(*es):
+    """The first non-NULL argument; every argument has one type (the plan carries the coercion casts)."""
+    return scalar_function("coalesce", es)
+
+
+def nullif(a, b):
+    """NULL where a = b (the engine's own '=': total order for floats), otherwise a."""
+    return scalar_function("nullif", [a, b])
+
+
+def nanvl(x, y):
+    return scalar_function("nanvl", [x, y])
+
+
+def isnan(x):
+    return scalar_function("isnan", [x])
+
+
+def iszero(x):
+    return scalar_function("iszero", [x])
+
+
+def abs_(x):
+    return scalar_function("abs", [x])
+
+
+def signum(x):
+    return scalar_function("signum", [x])
+
+
+def ceil(x):
+    return scalar_function("ceil", [x])
+
+
+def floor(x):
+    return scalar_function("floor", [x])
+
+
+def trunc(x):
+    return scalar_function("trunc", [x])
+
+
+def round_(x, n=None):
+    """round(x): half away from zero; round(x, n) with a literal n in 0..22: round(x * 10^n) / 10^n."""
+    return scalar_function("round", [x] + ([lit(int(n), "Int64")] if n is not None else []))
+
+
+def sqrt(x):
+    return scalar_function("sqrt", [x])
 
 
 def date_part(part, e):

@@ -12,6 +12,7 @@ use ballista_core::execution_plans::{CoalesceTasksExec, ShuffleReaderExec, Shuff
 use datafusion::arrow::datatypes::{DataType, SchemaRef};
 use datafusion::common::{DataFusionError, Result, ScalarValue};
 use datafusion::logical_expr::Operator;
+use datafusion::physical_expr::ScalarFunctionExpr;
 use datafusion::physical_plan::aggregates::{AggregateExec, AggregateMode};
 use datafusion::physical_plan::coalesce_batches::CoalesceBatchesExec;
 use datafusion::physical_plan::coalesce_partitions::CoalescePartitionsExec;
@@ -164,6 +165,18 @@ pub fn expr(e: &Arc<dyn PhysicalExpr>) -> Result<Value> {
     }
     if let Some(x) = a.downcast_ref::<LikeExpr>() {
         return Ok(json!({"like_expr": {"negated": x.negated(), "case_insensitive": x.case_insensitive(), "expr": expr(x.expr())?, "pattern": expr(x.pattern())?}}));
+    }
+    if let Some(x) = a.downcast_ref::<ScalarFunctionExpr>() {
+        // PhysicalScalarFunctionNode: the names the device's expression compiler builds (csrc/expr_compile.cpp, which checks the argument
+        // types and refuses by message); every other function keeps its subtree on the host
+        const BUILT: [&str; 16] = ["date_part", "datepart", "substr", "substring", "coalesce", "nullif", "nanvl", "isnan", "iszero", "abs", "signum", "ceil", "floor",
+                                   "trunc", "round", "sqrt"];
+        let name = x.name().to_ascii_lowercase();
+        if !BUILT.contains(&name.as_str()) {
+            return unsupported(format!("scalar function {name}"));
+        }
+        let args: Result<Vec<Value>> = x.args().iter().map(expr).collect();
+        return Ok(json!({"scalar_function": {"name": name, "args": args?}}));
     }
     unsupported(format!("physical expression {e:?}"))
 }

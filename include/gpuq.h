@@ -235,7 +235,8 @@ const char* gpuq_scan_last_error(void);
 /* ---- compiled operators ------------------------------------------------------------------ */
 /* Descriptor JSON (see INTEGRATION.md for the grammar).  Expression nodes mirror PhysicalExprNode
    (datafusion.proto:1142-1180): column, literal, binary_expr (+ - * / %, the comparisons, AND / OR, and & | ^ over two integers
-   of one type), cast, try_cast, not_expr, is_null_expr,
+   of one type), scalar_function (date_part, substr, coalesce, nullif, nanvl, isnan, iszero, abs, signum, ceil, floor, trunc, round, sqrt:
+   INTEGRATION.md has the argument types), cast, try_cast, not_expr, is_null_expr,
    is_not_null_expr, negative, in_list, case_ (like_expr is evaluated by gpuq_like_utf8 and lowered to a Boolean column by the plan
    executor).  "op" is one of
      "filter"      FilterExec        {input, predicate}
