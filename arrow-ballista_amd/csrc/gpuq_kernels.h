@@ -481,7 +481,7 @@ struct CsvSpec {
   uint8_t delim, quote; uint8_t pad[2];
 };
 struct CsvOut { void* data[CSV_MAX_FIELDS]; u64* valid[CSV_MAX_FIELDS]; uint32_t* str_start[CSV_MAX_FIELDS]; int32_t* str_len[CSV_MAX_FIELDS]; };
-constexpr uint32_t CSVF_BAD_NUMBER = 1u, CSVF_FIELD_COUNT = 2u, CSVF_QUOTE = 4u, CSVF_NULL_IN_REQUIRED = 8u, CSVF_FLOAT_PRECISION = 16u;
+constexpr uint32_t CSVF_BAD_NUMBER = 1u, CSVF_FIELD_COUNT = 2u, CSVF_QUOTE = 4u, CSVF_NULL_IN_REQUIRED = 8u, CSVF_FLOAT_PRECISION = 16u, CSVF_BLANK_LINE = 32u, CSVF_BARE_CR = 64u;
 void launch_csv_count_lines(hipStream_t s, const uint8_t* text, i64 n, i64 chunk, int nblocks, uint32_t* counts);
 void launch_csv_line_starts(hipStream_t s, const uint8_t* text, i64 n, i64 chunk, int nblocks, const uint32_t* block_offsets, i64* starts);
 void launch_csv_parse(hipStream_t s, const uint8_t* text, i64 n_bytes, const i64* starts, i64 row0, i64 n_rows, const CsvSpec& S, const CsvOut& O, uint32_t* flags);

@@ -82,6 +82,25 @@ struct CsvText {
   const uint8_t* g; const uint8_t* l; i64 base; bool staged;
   __device__ __forceinline__ uint8_t operator[](i64 i) const { return staged ? l[i - base] : g[i]; }
 };
+// The field grammar, per column type (anything else raises a flag that fails the call; an empty field is NULL or, in a required
+// column other than Utf8, refused):
+//   Int32 / Int64   [+-]? digit+                                    within the type's range
+//   Date32          dddd-dd-dd                                      year 0001..9999, month 01..12, day 01..the month's last
+//   Decimal128      [+-]? (digit+ [. digit*] | . digit+)            at most `scale` fraction digits, |value| < 10^precision
+//   Float64         the same mantissa, then ([eE] [+-]? digit+)?    Clinger's exact fast path only (below)
+//   Boolean         true True TRUE false False FALSE
+//   Utf8            any bytes
+// A quote or a carriage return (other than the one before the line's '\n') anywhere in a line, and a line without a byte, are refused.
+__device__ __forceinline__ bool csv_digit(uint8_t c) { return (unsigned)c - (unsigned)'0' <= 9u; }
+// [p, q) spells `lower` (n bytes) in lower case, capitalised or in upper case
+__device__ __forceinline__ bool csv_word(const CsvText& text, i64 p, i64 q, const char* lower, int n) {
+  if (q - p != n) return false;
+  const uint8_t c0 = text[p]; const bool up0 = c0 == (uint8_t)(lower[0] - 32);
+  if (c0 != (uint8_t)lower[0] && !up0) return false;
+  bool lo = true, up = true;
+  for (int k = 1; k < n; ++k) { const uint8_t c = text[p + k]; lo &= c == (uint8_t)lower[k]; up &= c == (uint8_t)(lower[k] - 32); }
+  return lo || (up && up0);
+}
 __global__ void __launch_bounds__(FBLOCK) k_csv_parse(const uint8_t* __restrict__ gtext, const i64 n_bytes, const i64* __restrict__ starts, const i64 row0, const i64 n_rows,
                                                       const CsvSpec S, const CsvOut O, uint32_t* __restrict__ flags) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[CSV_LDS_BYTES];
@@ -97,16 +116,21 @@ __global__ void __launch_bounds__(FBLOCK) k_csv_parse(const uint8_t* __restrict_
       __syncthreads();
     }
     i64 p = 0, end = 0;
+    uint32_t myflags = 0;
     if (live) {
       p = starts[row0 + r]; end = starts[row0 + r + 1] - 1;            // end = position of the '\n' (or of the end of the text)
       if (end > p && text[end - 1] == '\r') --end;
+      if (end == p) myflags |= CSVF_BLANK_LINE;      // a reader skips it; a row of NULLs (or of "") is what neither reader returns
     }
-    uint32_t myflags = 0;
     for (int f = 0; f < S.n_fields; ++f) {
       // field = [p, q)
       i64 q = p;
       if (live) {
-        while (q < end && text[q] != S.delim) { if (text[q] == S.quote) myflags |= CSVF_QUOTE; ++q; }
+        for (; q < end; ++q) {
+          const uint8_t c = text[q]; if (c == S.delim) break;
+          if (c == S.quote) myflags |= CSVF_QUOTE;
+          if (c == '\r') myflags |= CSVF_BARE_CR;      // the readers end a record there; the line splitter does not
+        }
       }
       const int kind = S.kind[f];
       if (kind != CSV_SKIP) {
@@ -139,54 +163,68 @@ __global__ void __launch_bounds__(FBLOCK) k_csv_parse(const uint8_t* __restrict_
               if (!empty) {
                 if (q - p != 10 || text[p + 4] != '-' || text[p + 7] != '-') myflags |= CSVF_BAD_NUMBER;
                 else {
+                  bool ok = true;
+                  for (int z = 0; z < 10; ++z) if (z != 4 && z != 7) ok &= csv_digit(text[p + z]);
                   const int y = (text[p] - '0') * 1000 + (text[p + 1] - '0') * 100 + (text[p + 2] - '0') * 10 + (text[p + 3] - '0');
                   const int m = (text[p + 5] - '0') * 10 + (text[p + 6] - '0'), d = (text[p + 8] - '0') * 10 + (text[p + 9] - '0');
-                  days = days_from_civil(y, m, d);
+                  const bool leap = (y % 4 == 0 && y % 100 != 0) || y % 400 == 0;
+                  const int last = m == 2 ? (leap ? 29 : 28) : 30 + ((m + (m >> 3)) & 1);      // 31 for 1 3 5 7 8 10 12
+                  if (!ok || y < 1 || m < 1 || m > 12 || d < 1 || d > last) myflags |= CSVF_BAD_NUMBER;
+                  else days = days_from_civil(y, m, d);
                 }
               }
               ((int32_t*)O.data[oc])[r] = days;
               break;
             }
-            case CSV_DEC128: {      // [-]digits[.digits] -> unscaled integer at the column's scale (extra fraction digits are an error, missing ones are zeros)
-              i128 v = 0; bool neg = false; i64 k = p; int frac = -1;
+            case CSV_DEC128: {      // [+-]digits[.digits] -> unscaled integer at the column's scale (extra fraction digits are an error, missing ones are zeros)
+              // unsigned: a field of more than 38 digits wraps (and is refused by its digit count below), which is defined only for unsigned
+              u128 v = 0; bool neg = false; i64 k = p; int frac = -1, any = 0, nd = 0;      // nd: digits from the first non-zero one on
               if (k < q && (text[k] == '-' || text[k] == '+')) { neg = text[k] == '-'; ++k; }
               for (; k < q; ++k) {
                 if (text[k] == '.') { if (frac >= 0) myflags |= CSVF_BAD_NUMBER; frac = 0; continue; }
                 const int dg = (int)text[k] - '0'; if (dg < 0 || dg > 9) { myflags |= CSVF_BAD_NUMBER; break; }
-                v = v * 10 + dg; if (frac >= 0) ++frac;
+                v = v * 10 + (u128)dg; any = 1; nd += (nd | dg) != 0; if (frac >= 0) ++frac;
               }
+              if (!any && !empty) myflags |= CSVF_BAD_NUMBER;      // a sign or a dot alone is no number
               if (frac < 0) frac = 0;
               if (frac > S.scale[f]) myflags |= CSVF_BAD_NUMBER;
+              // with the zeros the scale appends the value has nd + scale - frac digits: beyond 38 it cannot lie below 10^precision, and
+              // 10^38 < 2^127 is the most the accumulator holds without wrapping -- so count, whatever v came to
+              if (nd != 0 && nd + (S.scale[f] > frac ? S.scale[f] - frac : 0) > 38) myflags |= CSVF_BAD_NUMBER;
               for (int z = frac; z < S.scale[f]; ++z) v *= 10;
-              // more digits than the column's precision (or than 38: the accumulator would have wrapped) is an error
-              { i128 lim10 = 1; for (int z = 0; z < S.prec[f]; ++z) lim10 *= 10; if (q - p > 40 || v >= lim10) myflags |= CSVF_BAD_NUMBER; }
-              if (neg) v = -v;
-              ((u64*)O.data[oc])[2 * r] = (u64)v; ((u64*)O.data[oc])[2 * r + 1] = (u64)((u128)v >> 64);
+              { u128 lim10 = 1; for (int z = 0; z < S.prec[f]; ++z) lim10 *= 10; if (v >= lim10) myflags |= CSVF_BAD_NUMBER; }
+              if (neg) v = (u128)0 - v;
+              ((u64*)O.data[oc])[2 * r] = (u64)v; ((u64*)O.data[oc])[2 * r + 1] = (u64)(v >> 64);
               break;
             }
             case CSV_F64: {
-              // Clinger's exact fast path only: <= 15 significant digits and |decimal exponent| <= 22 give the correctly rounded
-              // double with one multiplication or division; anything longer raises CSVF_FLOAT_PRECISION (refused loudly)
-              u64 w = 0; int digits = 0, e10 = 0; bool neg = false, seen_dot = false; i64 k = p;
+              // Clinger's exact fast path only: the written digits as an integer below 2^53 (15 digits always are) and a decimal exponent
+              // of -22..22 left after the fraction digits give the correctly rounded double with one multiplication or division;
+              // anything else raises CSVF_FLOAT_PRECISION (refused loudly).  A mantissa of zeros is 0.0 whatever its exponent.
+              u64 w = 0; int digits = 0, nman = 0; i64 e10 = 0; bool neg = false, seen_dot = false; i64 k = p;      // (e10 moves by one per byte of the field: 64 bits)
               if (k < q && (text[k] == '-' || text[k] == '+')) { neg = text[k] == '-'; ++k; }
               for (; k < q; ++k) {
                 const uint8_t ch = text[k];
                 if (ch == '.') { if (seen_dot) myflags |= CSVF_BAD_NUMBER; seen_dot = true; continue; }
                 if (ch == 'e' || ch == 'E') break;
                 const int dg = (int)ch - '0'; if (dg < 0 || dg > 9) { myflags |= CSVF_BAD_NUMBER; break; }
+                ++nman;
                 if (w != 0 || dg != 0) { if (digits < 19) { w = w * 10 + (u64)dg; ++digits; } else if (!seen_dot) ++e10, myflags |= CSVF_FLOAT_PRECISION; else myflags |= (dg ? CSVF_FLOAT_PRECISION : 0u); }
                 if (seen_dot) --e10;
               }
+              if (nman == 0 && !empty) myflags |= CSVF_BAD_NUMBER;      // a sign, a dot or an exponent without a mantissa digit
               if (k < q && (text[k] == 'e' || text[k] == 'E')) {
-                ++k; bool eneg = false; int ev = 0;
+                ++k; bool eneg = false; int ev = 0, nexp = 0;
                 if (k < q && (text[k] == '-' || text[k] == '+')) { eneg = text[k] == '-'; ++k; }
-                for (; k < q; ++k) { const int dg = (int)text[k] - '0'; if (dg < 0 || dg > 9) { myflags |= CSVF_BAD_NUMBER; break; } ev = ev * 10 + dg; }
+                // the exponent saturates far outside the fast path instead of wrapping back into it
+                for (; k < q; ++k) { const int dg = (int)text[k] - '0'; if (dg < 0 || dg > 9) { myflags |= CSVF_BAD_NUMBER; break; } ++nexp; if (ev < 100000) ev = ev * 10 + dg; }
+                if (nexp == 0) myflags |= CSVF_BAD_NUMBER;
                 e10 += eneg ? -ev : ev;
               }
               double v = (double)w;
               if (w >= (1ull << 53) || e10 > 22 || e10 < -22) { if (w != 0) myflags |= CSVF_FLOAT_PRECISION; }
               else {
-                double p10 = 1.0; for (int z = 0; z < (e10 < 0 ? -e10 : e10); ++z) p10 *= 10.0;      // exact: 10^k for k <= 22
+                double p10 = 1.0; for (int z = 0; z < (int)(e10 < 0 ? -e10 : e10); ++z) p10 *= 10.0;      // exact: 10^k for k <= 22
                 v = e10 < 0 ? v / p10 : v * p10;
               }
               if (neg) v = -v;
@@ -198,8 +236,8 @@ __global__ void __launch_bounds__(FBLOCK) k_csv_parse(const uint8_t* __restrict_
           }
         }
         if (kind == CSV_BOOL) {
-          const bool t = live && (q - p == 4) && (text[p] == 't' || text[p] == 'T');
-          if (live && !empty && !t && !((q - p == 5) && (text[p] == 'f' || text[p] == 'F'))) myflags |= CSVF_BAD_NUMBER;
+          const bool t = live && csv_word(text, p, q, "true", 4);
+          if (live && !empty && !t && !csv_word(text, p, q, "false", 5)) myflags |= CSVF_BAD_NUMBER;
           const u64 m = __ballot(t);
           if (flane() == 0 && live) ((u64*)O.data[oc])[r >> 6] = m;
         }

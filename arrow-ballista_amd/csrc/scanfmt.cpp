@@ -174,6 +174,8 @@ int gpuq_csv_decode(gpuq_ctx* ctx, void* stream, const uint8_t* text, int64_t n_
     HIPCHECK(hipGetLastError());
     const uint32_t fl = d2h_value(s, (const uint32_t*)flags.p);
     if (fl & CSVF_QUOTE) throw Unsupported("csv: quoted fields are not parsed on the device");
+    if (fl & CSVF_BARE_CR) throw Unsupported("csv: a carriage return that is not followed by a line feed (lines end at \\n or \\r\\n on the device)");
+    if (fl & CSVF_BLANK_LINE) throw Unsupported("csv: a blank line (a reader skips it; the device makes a row of every line, so it refuses the text)");
     if (fl & CSVF_FIELD_COUNT) throw std::runtime_error("csv: a line does not have the schema's number of fields");
     if (fl & CSVF_BAD_NUMBER) throw std::runtime_error("csv: a field does not parse as its column's type");
     if (fl & CSVF_NULL_IN_REQUIRED) throw std::runtime_error("csv: an empty field in a non-nullable column");

@@ -210,7 +210,9 @@ const char* gpuq_ingest_last_error(void);
    of a nullable non-Utf8 column is NULL, as arrow-csv reads it); `projection` (or NULL = all) picks output columns by file index.
    A trailing delimiter before the newline (TPC-H .tbl) is accepted.  Types: Int32 Int64 Date32 (yyyy-mm-dd) Decimal128 Float64
    Boolean Utf8.  Refused loudly rather than decoded differently: quoted fields, a Float64 field outside the exactly-rounded fast
-   path (> 15 significant digits or |exponent| > 22), lines whose field count differs from the schema (blank lines included), > 4 GiB per call.
+   path (written digits of 2^53 or more, or an exponent beyond -22..22 after the fraction), lines whose field count differs from the schema,
+   blank lines, a carriage return that is not followed by a line feed, > 4 GiB per call.  A field outside its type's grammar or range
+   (scan-side decode) is an error, never a clamped or wrapped value.
    gpuq_parquet_decode: flat schemas; physical BOOLEAN INT32 INT64 DOUBLE BYTE_ARRAY FIXED_LEN_BYTE_ARRAY(decimal); DATE and
    DECIMAL annotations; required / optional columns; PLAIN, PLAIN_DICTIONARY / RLE_DICTIONARY and RLE-boolean pages (v1 and v2); UNCOMPRESSED
    SNAPPY, LZ4_RAW and ZSTD column chunks (Snappy / LZ4 pages are decompressed without a serial walk: element positions by doubling, copies by
