@@ -77,6 +77,8 @@ def lib():
         "gpuq_memory_limit": (i32, [i64]),
         "gpuq_memory_stats": (i32, [C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), i32]),
         "gpuq_utf8_compare": (i32, [vp, vp, C.POINTER(gpuq_column), vp, C.POINTER(gpuq_column), vp, C.c_char_p, i64, i64, i32, vp, vp]),
+        "gpuq_segment_heads": (i32, [vp, vp, C.POINTER(gpuq_column), i32, i64, vp, vp, i64, vp]),
+        "gpuq_segment_median": (i32, [vp, vp, C.POINTER(gpuq_column), vp, i64, vp, vp]),
         "gpuq_ingest_create": (i32, [vp, vp, i64, i64, i32, C.POINTER(vp)]),
         "gpuq_ingest_push": (i32, [vp, vp]),
         "gpuq_ingest_rows_landed": (i32, [vp, C.POINTER(i64)]),
@@ -224,6 +226,28 @@ def compile_check(descriptor):
     if rc != 0:
         raise GpuqError(rc, L.gpuq_last_error(None).decode())
     return json.loads(buf.value.decode())
+
+
+def plan_schema(plan):
+    """Host only: the output fields [{"name", "type", "nullable"}] the native executor announces for a plan (the JSON of
+    gpuq_plan_create), typed without a device -- a plan created without a context validates and types, it cannot execute."""
+    from .table import type_json
+    L = lib()
+    h = C.c_void_p()
+    rc = L.gpuq_plan_create(None, json.dumps(plan).encode(), C.byref(h))
+    if rc != 0:
+        raise GpuqError(rc, (L.gpuq_plan_last_error() or b"").decode())
+    try:
+        n = C.c_int(0)
+        rc = L.gpuq_plan_schema(h, None, 0, C.byref(n))
+        f = (gpuq_field_info * max(1, n.value))()
+        if rc == 0:
+            rc = L.gpuq_plan_schema(h, f, n.value, C.byref(n))
+        if rc != 0:
+            raise GpuqError(rc, (L.gpuq_plan_last_error() or b"").decode())
+        return [{"name": f[i].name.decode(), "type": type_json(f[i].type, f[i].precision, f[i].scale), "nullable": bool(f[i].nullable)} for i in range(n.value)]
+    finally:
+        L.gpuq_plan_free(h)
 
 
 def compile_jit_source(descriptor, kernel_id):

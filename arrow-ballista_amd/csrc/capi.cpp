@@ -1729,6 +1729,49 @@ int gpuq_utf8_compare(gpuq_ctx* ctx, void* stream, const gpuq_column* a, const u
     HIPCHECK(hipGetLastError());
   });
 }
+// ---------------------------------------------------------------- segments of a key-sorted table, and their medians (MEDIAN)
+int gpuq_segment_heads(gpuq_ctx* ctx, void* stream, const gpuq_column* key_cols, int n_keys, int64_t n, int32_t* seg_id_out, int32_t* starts_out, int64_t starts_cap,
+                       uint64_t* n_groups_dev) {
+  return guarded(ctx, [&]() {
+    check_ctx(ctx);
+    if (n < 0 || n_keys < 0 || (n_keys > 0 && !key_cols) || !starts_out || starts_cap < 0 || !n_groups_dev) throw std::runtime_error("gpuq_segment_heads: bad arguments");
+    if (n_keys > SEG_MAX_KEYS) throw Unsupported("gpuq_segment_heads: more than " + std::to_string(SEG_MAX_KEYS) + " key columns");
+    if (n >= (1ll << 31)) throw Unsupported("gpuq_segment_heads (MEDIAN): >= 2^31 rows in one call (segment ids are 32-bit)");
+    SegKeys K{}; K.n_keys = n_keys;
+    for (int k = 0; k < n_keys; ++k) {
+      const gpuq_column& c = key_cols[k];
+      if (c.type == T_UTF8 && c.repr != GPUQ_REPR_PACKED15) throw Unsupported("gpuq_segment_heads: a Utf8 key column must be in the fixed-width PACKED15 form");
+      if (n > 0 && (!c.data || c.length < n)) throw std::runtime_error("gpuq_segment_heads: key column " + std::to_string(k) + " is shorter than n");
+      DType dt; dt.id = c.type; dt.p = c.precision; dt.s = c.scale;
+      K.width[k] = c.type == T_BOOL ? 0 : type_width(dt); K.data[k] = c.data; K.valid[k] = c.validity;
+    }
+    hipStream_t s = use_stream(stream);
+    DevBuf scan, ws;      // released to the pool behind the launches on this stream
+    if (n > 0) { scan.ensure((size_t)(n + 1) * 4); ws.ensure(exclusive_scan_ws_bytes(n)); }
+    launch_segment_heads(s, K, n, (int32_t*)scan.p, ws.p, ws.cap, seg_id_out, starts_out, starts_cap, (u64*)n_groups_dev);
+    HIPCHECK(hipGetLastError());
+  });
+}
+int gpuq_segment_median(gpuq_ctx* ctx, void* stream, const gpuq_column* value_col, const int32_t* starts, int64_t n_groups, void* out_data, uint8_t* out_validity) {
+  return guarded(ctx, [&]() {
+    check_ctx(ctx);
+    if (!value_col || n_groups < 0 || (n_groups > 0 && (!starts || !out_data || !out_validity))) throw std::runtime_error("gpuq_segment_median: bad arguments");
+    if (((uintptr_t)out_validity & 7) != 0) throw std::runtime_error("gpuq_segment_median: out_validity must be 8-byte aligned");
+    if (n_groups >= (1ll << 31)) throw Unsupported("gpuq_segment_median (MEDIAN): >= 2^31 segments in one call");
+    DType dt; dt.id = value_col->type; dt.p = value_col->precision; dt.s = value_col->scale;
+    int kind = SEG_SINT;
+    switch (dt.id) {
+      case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_DECIMAL128: kind = SEG_SINT; break;
+      case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: kind = SEG_UINT; break;
+      case T_FLOAT32: kind = SEG_F32; break;
+      case T_FLOAT64: kind = SEG_F64; break;
+      default: throw Unsupported("MEDIAN over " + dt.to_string() + " is not supported (Int8..Int64, UInt8..UInt64, Float32, Float64, Decimal128)");
+    }
+    launch_segment_median(use_stream(stream), value_col->data, value_col->validity, type_width(dt), kind, starts, n_groups, out_data, (u64*)out_validity);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
 int gpuq_like_utf8(gpuq_ctx* ctx, void* stream, const gpuq_column* col, const uint32_t* idx, int64_t n, const char* pattern, int negated, int case_insensitive,
                    uint8_t* bits_out, uint8_t* validity_out) {
   return guarded(ctx, [&]() {

@@ -471,6 +471,13 @@ void launch_utf8_max_len(hipStream_t s, const int32_t* offsets, const uint8_t* v
 void launch_utf8_intern(hipStream_t s, const uint8_t* ddata, const int32_t* doffs, const uint8_t* data, const int32_t* offsets, const uint8_t* validity, const uint32_t* idx, i64 n,
                         u64* table, u64 mask, int insert, i64* codes, u64* valid_out, uint32_t* flags);
 void launch_popcount_bits(hipStream_t s, const uint8_t* bits, int64_t n_bits, unsigned long long* out);
+// ----- segments of a key-sorted table and their medians (kernels_segment.hip)
+constexpr int SEG_MAX_KEYS = 16;
+struct SegKeys { int32_t n_keys; int32_t width[SEG_MAX_KEYS]; const void* data[SEG_MAX_KEYS]; const uint8_t* valid[SEG_MAX_KEYS]; };      // width: bytes per value, 0 = a bitmap (Boolean)
+enum SegKind : int32_t { SEG_SINT = 0, SEG_UINT = 1, SEG_F32 = 2, SEG_F64 = 3 };      // how two middles are combined (width 16 is always a signed integer)
+// scan: n + 1 words of scratch (the flags, then their exclusive scan); seg_id (n, or nullptr), starts (starts_cap + 1), n_groups as gpuq_segment_heads
+void launch_segment_heads(hipStream_t s, const SegKeys& K, i64 n, int32_t* scan, void* scan_ws, size_t scan_ws_bytes, int32_t* seg_id, int32_t* starts, i64 starts_cap, u64* n_groups);
+void launch_segment_median(hipStream_t s, const void* data, const uint8_t* valid, int width, int kind, const int32_t* starts, i64 n_groups, void* out, u64* out_valid);
 
 // ----- scan-side decode (kernels_scanfmt.hip): delimited text and Parquet pages
 enum CsvKind : int32_t { CSV_SKIP = 0, CSV_I32 = 1, CSV_I64 = 2, CSV_DATE32 = 3, CSV_DEC128 = 4, CSV_F64 = 5, CSV_BOOL = 6, CSV_UTF8 = 7 };

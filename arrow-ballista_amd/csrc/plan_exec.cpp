@@ -1001,9 +1001,211 @@ Json bound_aggr_exprs(const Json& aggr_expr, const ColMap* cm, const std::vector
   }
   return ae;
 }
+// ---- MEDIAN (include/gpuq.h, gpuq_segment_median, has the rules).  Its state is the group's values, so it is no accumulator of the
+// aggregate operator: a node that holds one is lowered here, in the plan, as COUNT(DISTINCT) is (build_node) -- see AggregateExec::run_median.
+bool is_median(const Json& a) {
+  std::string f = a.get_str("fn", "");
+  for (char& c : f) c = (char)std::toupper((unsigned char)c);
+  return f == "MEDIAN";
+}
+void median_check_arg(const DType& t) {
+  switch (t.id) {
+    case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: case T_FLOAT32: case T_FLOAT64: case T_DECIMAL128: return;
+    default: throw Unsupported("MEDIAN over " + t.to_string() + " is not supported (Int8..Int64, UInt8..UInt64, Float32, Float64, Decimal128)");
+  }
+}
+void median_check_key(const DType& t, const std::string& name) {
+  if (t.is_float()) throw Unsupported("MEDIAN: the " + t.to_string() + " group key '" + name + "' is refused on a node with a MEDIAN (bytewise segment heads and the hash "
+                                      "aggregate need not agree on -0.0 / NaN)");
+}
+// the argument of MEDIAN `a` over the node's input: with FILTER (WHERE p), a row where p is not true counts as a NULL argument
+Json median_arg(const Json& a, const ColMap* cm) {
+  if (!a.has("expr")) throw std::runtime_error("MEDIAN needs an argument (\"expr\")");
+  const Json e = inline_projection(a.at("expr"), cm);
+  if (!a.has("filter")) return e;
+  return jobj({{"case_", jobj({{"when_then_expr", jarr({jobj({{"when_expr", inline_projection(a.at("filter"), cm)}, {"then_expr", e}})})}})}});
+}
+// a projection of any number of expressions (the project operator writes MAX_OUTS columns at most): tags [tag, tag + 20)
+PTable project_wide(Exec& x, const PTable& t, const std::vector<Json>& exprs, const std::vector<std::string>& names, const void* site, int tag) {
+  if (exprs.size() <= 12) return project(x, t, exprs, names, site, tag);
+  PTable out; out.n = t.n;
+  for (size_t a = 0; a < exprs.size(); a += 12) {
+    const size_t hi = std::min(a + 12, exprs.size());
+    PTable part = project(x, t, std::vector<Json>(exprs.begin() + (long)a, exprs.begin() + (long)hi), std::vector<std::string>(names.begin() + (long)a, names.begin() + (long)hi), site, tag + (int)(a / 12));
+    out.cols.insert(out.cols.end(), part.cols.begin(), part.cols.end()); out.sides.insert(out.sides.end(), part.cols.size(), 0); out.own(part);
+  }
+  return out;
+}
+
 struct AggregateExec : PNode {
   PNodeP input; std::string mode, strategy = "auto"; Json group_expr, aggr_expr; int64_t expected_groups = 0, output_capacity = 0;
   std::vector<PNode*> children() override { return {input.get()}; }
+  bool has_median() const { for (auto& a : aggr_expr.a) if (is_median(a)) return true; return false; }
+  Json plain_aggr_exprs() const { Json p = jarr(); for (auto& a : aggr_expr.a) if (!is_median(a)) p.a.push_back(a); return p; }
+  // A node with MEDIANs is typed without asking the aggregate operator to compile MEDIAN: keys and arguments by the projection that
+  // run_median makes of them, the other aggregates by the operator over the node without its MEDIANs.
+  PSchema median_schema() {
+    const PSchema in = input->schema(); const auto nm = schema_names(in);
+    const size_t nk = group_expr.a.size();
+    std::vector<Json> ex; std::vector<std::string> names;
+    for (auto& g : group_expr.a) { ex.push_back(g.at("expr")); names.push_back(g.at("name").str()); }
+    for (auto& a : aggr_expr.a) if (is_median(a)) { ex.push_back(median_arg(a, nullptr)); names.push_back(a.at("name").str()); }
+    const PSchema typed = compiled_outputs(project_desc(input_of(in), ex, names, &nm));
+    for (size_t k = 0; k < nk; ++k) median_check_key(dtype_from_json(typed[k].type), typed[k].name);
+    for (size_t k = nk; k < typed.size(); ++k) median_check_arg(dtype_from_json(typed[k].type));
+    PSchema plain;
+    const Json pa = plain_aggr_exprs();
+    if (!pa.a.empty()) {
+      Json ge = jarr();
+      for (auto& g : group_expr.a) ge.a.push_back(jobj({{"expr", rebind(g.at("expr"), nm)}, {"name", g.at("name")}}));
+      plain = compiled_outputs(jobj({{"op", jstr("aggregate")}, {"mode", jstr(mode)}, {"input", input_of(in)}, {"strategy", jstr("hash")},
+                                     {"group_expr", ge}, {"aggr_expr", bound_aggr_exprs(pa, nullptr, nm)}}));
+    }
+    PSchema out(typed.begin(), typed.begin() + (long)nk);
+    size_t mi = nk, pi = nk;
+    for (auto& a : aggr_expr.a) {
+      PField f = is_median(a) ? typed[mi++] : plain.at(pi++);
+      f.nullable = true;      // (the declared form: see schema())
+      out.push_back(f);
+    }
+    return out;
+  }
+  // The lowering of a node with MEDIANs (mode Single).  The input is projected to [keys, one column per distinct MEDIAN argument, the
+  // columns the other aggregates read] and sorted by (keys..., argument) -- once per distinct argument; keys lead and the rows are the
+  // same, so every sort has the same segments.  The segments are taken from the first sort (gpuq_segment_heads); the other aggregates
+  // run on the existing operator grouped by the segment id alone, so group identity is decided once and both halves are aligned by
+  // construction; one lane per segment picks the middles (gpuq_segment_median).  The node runs synchronously in every execution.
+  PTable run_median(Exec& x, PTable t, const Fused& f) {
+    const ColMap* cm = f.has_map ? &f.map : nullptr;
+    settle(x, &t);      // what is pending is settled and t's count made exact; nothing below is offered a deferred run
+    struct SyncOnly { Exec& x; bool was; explicit SyncOnly(Exec& x_) : x(x_), was(x_.deferred) { x.deferred = false; } ~SyncOnly() { x.deferred = was; } } sync_only(x);
+    if (f.has_pred) t = filter_table(x, t, f.pred, this, 20);
+    const size_t nk = group_expr.a.size();
+    auto key_name = [](size_t k) { return "__mk" + std::to_string(k); };
+    auto arg_name = [](size_t j) { return "__ma" + std::to_string(j); };
+    // ---- 1. the projection
+    std::vector<Json> ex; std::vector<std::string> nm;
+    for (size_t k = 0; k < nk; ++k) {
+      const Json e = inline_projection(group_expr.a[k].at("expr"), cm);
+      const int ci = long_key_column(t, e);
+      if (ci >= 0) {      // a string key leaves the projection as 16 packed bytes: that is what makes the keys fixed-width
+        int32_t maxlen = 0;
+        check(x, gpuq_utf8_max_len(x.ctx, x.stream, &t.cols[(size_t)ci].c, via_of(t, (size_t)ci), t.n, &maxlen));
+        if (maxlen > 15) throw Unsupported("MEDIAN: the group key '" + group_expr.a[k].at("name").str() + "' holds strings longer than 15 bytes (" + std::to_string(maxlen) + ")");
+      }
+      ex.push_back(e); nm.push_back(key_name(k));
+    }
+    std::vector<std::string> arg_text; std::vector<int> arg_of(aggr_expr.a.size(), -1);
+    for (size_t i = 0; i < aggr_expr.a.size(); ++i) {
+      if (!is_median(aggr_expr.a[i])) continue;
+      const Json e = median_arg(aggr_expr.a[i], cm);
+      const std::string text = e.dump();
+      size_t j = 0; while (j < arg_text.size() && arg_text[j] != text) ++j;
+      if (j == arg_text.size()) { arg_text.push_back(text); ex.push_back(e); nm.push_back(arg_name(j)); }
+      arg_of[i] = (int)j;
+    }
+    const size_t na = arg_text.size();
+    const Json plain = plain_aggr_exprs();
+    Names plain_cols;
+    for (auto& a : plain.a) for_each_agg_arg(a, [&](const char*, const Json& e) { collect_columns(inline_projection(e, cm), plain_cols); });
+    for (auto& c : plain_cols) { ex.push_back(jcolname(c)); nm.push_back(c); }
+    const PTable proj = project_wide(x, t, ex, nm, this, 21);
+    const int64_t n = proj.n;
+    if (n >= (1ll << 31)) throw Unsupported("MEDIAN over >= 2^31 rows in one partition (segment ids are 32-bit)");
+    for (size_t k = 0; k < nk; ++k) median_check_key(dtype_of(proj.cols[k].c), group_expr.a[k].at("name").str());
+    for (size_t j = 0; j < na; ++j) median_check_arg(dtype_of(proj.cols[nk + j].c));
+    // ---- 2. one sort per distinct argument, materialised (keep: the columns read afterwards)
+    auto sorted_by = [&](size_t j, const Names& keep) {
+      if (n == 0) return proj;
+      Json se = jarr();
+      for (size_t k = 0; k < nk; ++k) se.a.push_back(jobj({{"expr", jcolname(key_name(k))}, {"asc", jbool(true)}, {"nulls_first", jbool(false)}}));
+      se.a.push_back(jobj({{"expr", jcolname(arg_name(j))}, {"asc", jbool(true)}, {"nulls_first", jbool(false)}}));
+      PTable v;
+      if (se.a.size() <= 4) v = sort_table(x, proj, se, -1, this, 200 + (int)j);
+      else {      // more keys than one sort takes: stable passes, least significant first -- four keys a pass, or one when four do not fit 128 bits
+        PermOut po;
+        try { po = sort_perm_long(x, proj, se, this, 200 + (int)j); }
+        catch (const Unsupported& e) { if (!is_wide_sort_key(e)) throw; po = sort_perm_long(x, proj, se, this, 300 + (int)j, 1); }
+        v = select_view(x, proj, po.p, n, nullptr);
+        for (auto& b : po.keep) v.keep.push_back(b);
+      }
+      prune_columns(v, keep);
+      return materialize(x, v);
+    };
+    Names keep0 = plain_cols; keep0.insert(arg_name(0));
+    for (size_t k = 0; k < nk; ++k) keep0.insert(key_name(k));
+    const PTable sorted0 = sorted_by(0, keep0);
+    // ---- 3. segments
+    int64_t G = 1;
+    BufP starts = dev_alloc((size_t)(n + 2) * 4), seg_id;
+    if (nk) {
+      std::vector<gpuq_column> kc;
+      for (size_t k = 0; k < nk; ++k) kc.push_back(sorted0.cols[(size_t)find_column(sorted0, key_name(k))].c);
+      if (!plain.a.empty()) seg_id = alloc_rows(n);
+      BufP cnt = dev_alloc(16);
+      check(x, gpuq_segment_heads(x.ctx, x.stream, kc.data(), (int)nk, n, seg_id ? (int32_t*)seg_id->p : nullptr, (int32_t*)starts->p, n, (uint64_t*)cnt->p));
+      G = (int64_t)read_u64(x, cnt->p);
+      if (G < 0 || G > n) throw std::runtime_error("MEDIAN: " + std::to_string(G) + " segments over " + std::to_string(n) + " rows");
+    } else {      // ungrouped: one segment, also over no rows (one row holding NULL)
+      const int32_t whole[2] = {0, (int32_t)n};
+      upload(x, starts, whole, sizeof(whole));
+    }
+    // ---- 4. the other aggregates, grouped by the segment id, brought into segment order
+    PTable pres;
+    if (!plain.a.empty()) {
+      PTable src = nk ? sorted0 : proj;
+      if (nk) append_column(src, "__seg", T_INT32, seg_id->p, seg_id, nullptr, n, false);
+      gpuq_op* op = cached_op(x, this, 19, table_sig(src), [&]() {
+        const auto names = names_of(src);
+        Json ge = jarr();
+        if (nk) ge.a.push_back(jobj({{"expr", rebind(jcolname("__seg"), names)}, {"name", jstr("__seg")}}));
+        return jobj({{"op", jstr("aggregate")}, {"mode", jstr("Single")}, {"input", input_of(src)}, {"strategy", jstr("auto")}, {"group_expr", ge},
+                     {"aggr_expr", bound_aggr_exprs(plain, cm, names)}});
+      });
+      use_sync(x, op);
+      InputC ic; make_input(src, ic);
+      std::vector<gpuq_column> carr;
+      pres = alloc_outputs(op, std::max<int64_t>(G, 1), carr);
+      int64_t ng = 0;
+      const int rc = gpuq_aggregate_run(op, x.stream, &ic.in, carr.data(), (int)carr.size(), std::max<int64_t>(G, 1), &ng);
+      ++x.host_syncs;
+      if (rc == GPUQ_OK && ng != G) throw std::runtime_error("MEDIAN: the aggregate operator returned " + std::to_string(ng) + " groups for " + std::to_string(G) + " segments");
+      check(x, rc);
+      pres.n = G; for (auto& c : pres.cols) c.c.length = G;
+      if (nk && G > 1) pres = materialize(x, sort_table(x, pres, jarr({jobj({{"expr", jcolname("__seg")}, {"asc", jbool(true)}, {"nulls_first", jbool(false)}})}), -1, this, 18));
+    }
+    // ---- 5. the medians
+    PTable r; r.n = G;
+    std::vector<PCol> med(na);
+    for (size_t j = 0; j < na; ++j) {
+      const PTable sj = j == 0 ? sorted0 : sorted_by(j, Names{arg_name(j)});
+      const PCol& ac = sj.cols[(size_t)find_column(sj, arg_name(j))];
+      BufP data = dev_alloc((size_t)std::max<int64_t>(G, 1) * width_of(ac.c) + 16), valid = dev_alloc(bitmap_bytes(G) + 8);
+      check(x, gpuq_segment_median(x.ctx, x.stream, &ac.c, (const int32_t*)starts->p, G, data->p, (uint8_t*)valid->p));
+      med[j] = ac; med[j].nullable = true; med[j].c.data = data->p; med[j].c.validity = (const uint8_t*)valid->p; med[j].c.length = G;
+      r.keep.push_back(data); r.keep.push_back(valid); r.own(sj);
+    }
+    // ---- 6. the result in declared order: the keys of every segment's first row, then the aggregates
+    if (nk) {
+      PTable keys = sorted0;
+      Names kn; for (size_t k = 0; k < nk; ++k) kn.insert(key_name(k));
+      prune_columns(keys, kn);
+      PTable kv = select_view(x, keys, (const uint32_t*)starts->p, G, starts);
+      kv.dense = true;      // (every position is a row)
+      const PTable km = materialize(x, kv);
+      for (size_t k = 0; k < nk; ++k) { PCol c = km.cols[(size_t)find_column(km, key_name(k))]; c.name = group_expr.a[k].at("name").str(); c.c.length = G; r.cols.push_back(c); }
+      r.own(km);
+    }
+    size_t pi = nk ? 1 : 0;
+    for (size_t i = 0; i < aggr_expr.a.size(); ++i) {
+      PCol c = arg_of[i] >= 0 ? med[(size_t)arg_of[i]] : pres.cols.at(pi++);
+      c.name = aggr_expr.a[i].at("name").str(); c.c.length = G;
+      r.cols.push_back(c);
+    }
+    r.own(pres); r.keep.push_back(starts);
+    r.sides.assign(r.cols.size(), 0);
+    return r;
+  }
   void require(const Names*) override {
     if (mode == "Final" || mode == "FinalPartitioned") { input->require(nullptr); return; }      // reads its input's state columns by position
     Names n;
@@ -1012,6 +1214,7 @@ struct AggregateExec : PNode {
     input->require(&n);
   }
   PSchema schema() override {
+    if (has_median()) return median_schema();
     const PSchema in = input->schema(); const auto nm = schema_names(in);
     Json ge = jarr();
     for (auto& g : group_expr.a) ge.a.push_back(jobj({{"expr", rebind(g.at("expr"), nm)}, {"name", g.at("name")}}));
@@ -1033,6 +1236,7 @@ struct AggregateExec : PNode {
     // -- never from a table some node in between has handed on
     if (final_ || !f.src->is_hash_join()) t.by_build = nullptr;
     auto t0 = std::chrono::steady_clock::now();
+    if (has_median()) { t.by_build = nullptr; return timed(x, t0, run_median(x, t, f)); }
     // (more group columns than the table holds keys, some of them strings: codes from the start -- a 128-bit packed string takes a key
     // slot of its own, a 32-bit code is packed with its neighbours, see compile_aggregate)
     bool many_string_keys = false;
@@ -2215,6 +2419,13 @@ PNodeP build_node(const Json& j) {
     // node is DISTINCT over the same argument the node becomes two -- GROUP BY (keys, x) throws the duplicates away, GROUP BY keys
     // aggregates what is left -- which is the rewrite DataFusion's SingleDistinctToGroupBy rule makes [UPSTREAM-KNOWLEDGE]; both levels
     // run on the existing hash aggregate.  Mixed DISTINCT / plain aggregates stay refused (gpuq_op_create says so).
+    // MEDIAN is lowered in the plan as well (AggregateExec::run_median), in mode Single only: the state a Partial would emit is the
+    // group's values, a list column, which the engine has no type for
+    if (n->has_median()) {
+      if (n->mode != "Single") throw Unsupported("MEDIAN in an AggregateExec of mode " + n->mode + " is not supported (its state would be a list column): mode Single only");
+      for (auto& a : n->aggr_expr.a)
+        if (a.get_bool("distinct", false)) throw Unsupported(std::string(is_median(a) ? "MEDIAN(DISTINCT ...)" : "a DISTINCT aggregate on a node with a MEDIAN") + " is not supported");
+    }
     bool any_distinct = false, all_distinct = !n->aggr_expr.a.empty();
     for (auto& a : n->aggr_expr.a) { const bool d = a.get_bool("distinct", false); any_distinct = any_distinct || d; all_distinct = all_distinct && d; }
     if (any_distinct && all_distinct && n->mode == "Single") {

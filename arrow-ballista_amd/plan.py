@@ -614,7 +614,9 @@ class AggregateExec(ExecutionPlan):
     """AggregateExec(mode, group_expr, aggr_expr, input) -- datafusion.proto:1405-1450.
     group_expr: [(expr, name)];  aggr_expr: [{"fn": f, "expr": e[, "expr2": e2], "name": n}]; the function names (those of
     datafusion.proto:631-669 and their aliases) and each function's state columns are listed with the operator descriptors in
-    include/gpuq.h.  Modes: Partial (emits state columns), Final / FinalPartitioned (merge states), Single."""
+    include/gpuq.h.  Modes: Partial (emits state columns), Final / FinalPartitioned (merge states), Single.
+    MEDIAN (mode Single; `"filter"` allowed) is not one of the operator's functions: the native executor lowers a node that holds one
+    (include/gpuq.h, gpuq_segment_median); the Python restatement of the executor (GPUQ_PLAN_LAYER=mirror) does not have it."""
 
     def __init__(self, mode, group_expr, aggr_expr, input, strategy="auto", expected_groups=0):
         super().__init__()
@@ -636,6 +638,14 @@ class AggregateExec(ExecutionPlan):
         return d
 
     def schema(self):
+        if any(str(a.get("fn", "")).upper() == "MEDIAN" for a in self.aggr_expr):
+            # MEDIAN is no accumulator of the operator (compile_check refuses it): the native executor lowers the node in the plan
+            # (csrc/plan_exec.cpp run_median) and types it there, without a device -- ask it, over the input's schema as a leaf
+            leaf = {"MemoryExec": {"schema": [{"name": f["name"], "type": f["type"], "nullable": bool(f.get("nullable", True))} for f in self.input.schema()],
+                                   "partitions": [0]}}
+            return B.plan_schema({"AggregateExec": {"input": leaf, "mode": self.mode, "strategy": self.strategy,
+                                                    "group_expr": [{"expr": e, "name": n} for e, n in self.group_expr],
+                                                    "aggr_expr": [{k: v for k, v in a.items() if v is not None} for a in self.aggr_expr]}})
         d = B.compile_check(self._descriptor(self.input.schema(), None, None))
         return [_field_from_desc(o) for o in d["outputs"]]
 

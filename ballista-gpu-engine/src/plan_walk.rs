@@ -17,7 +17,7 @@ use datafusion::physical_plan::aggregates::{AggregateExec, AggregateMode};
 use datafusion::physical_plan::coalesce_batches::CoalesceBatchesExec;
 use datafusion::physical_plan::coalesce_partitions::CoalescePartitionsExec;
 use datafusion::physical_plan::expressions::{
-    Avg, BinaryExpr, BitAnd, BitOr, BitXor, BoolAnd, BoolOr, CaseExpr, CastExpr, Column, Count, InListExpr, IsNotNullExpr, IsNullExpr, LikeExpr, Literal, Max, Min, NegativeExpr, NotExpr,
+    Avg, BinaryExpr, BitAnd, BitOr, BitXor, BoolAnd, BoolOr, CaseExpr, CastExpr, Column, Count, InListExpr, IsNotNullExpr, IsNullExpr, LikeExpr, Literal, Max, Median, Min, NegativeExpr, NotExpr,
     PhysicalSortExpr, Sum, TryCastExpr,
 };
 use datafusion::physical_plan::filter::FilterExec;
@@ -191,6 +191,7 @@ fn aggregate_fn(a: &Arc<dyn AggregateExpr>) -> Result<&'static str> {
     Ok(if x.is::<Sum>() { "SUM" } else if x.is::<Avg>() { "AVG" } else if x.is::<Count>() { "COUNT" } else if x.is::<Min>() { "MIN" } else if x.is::<Max>() { "MAX" }
        else if x.is::<BitAnd>() { "BIT_AND" } else if x.is::<BitOr>() { "BIT_OR" } else if x.is::<BitXor>() { "BIT_XOR" }
        else if x.is::<BoolAnd>() { "BOOL_AND" } else if x.is::<BoolOr>() { "BOOL_OR" }
+       else if x.is::<Median>() { "MEDIAN" }      // mode Single only: the native executor lowers it in the plan (include/gpuq.h) and refuses the other modes
        else { return unsupported(format!("aggregate {}", a.name())) })
 }
 

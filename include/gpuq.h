@@ -466,6 +466,37 @@ int gpuq_like_utf8(gpuq_ctx* ctx, void* stream, const gpuq_column* col, const ui
 int gpuq_utf8_compare(gpuq_ctx* ctx, void* stream, const gpuq_column* a, const uint32_t* idx_a, const gpuq_column* b, const uint32_t* idx_b, const char* literal,
                       int64_t literal_len, int64_t n, int op, uint8_t* bits_out, uint8_t* validity_out);
 
+/* MEDIAN (AggregateFunction MEDIAN = 18 in datafusion.proto; DataFusion 34's MedianAccumulator [UPSTREAM-KNOWLEDGE: the crate source is
+   not in the reference tree]).  Its state is the group's values, not a cell, so it is not a row of the operator's accumulator table: the
+   "aggregate" descriptor of gpuq_op_create / gpuq_compile_check refuses it, and the native plan executor lowers an AggregateExec in mode
+   Single that holds MEDIANs (next to any other aggregates) to one sort by (keys..., argument) per distinct argument plus the two entry
+   points below.  The rules:
+     argument   Int8..Int64, UInt8..UInt64, Float32, Float64, Decimal128(p, s); anything else is refused ("MEDIAN over <type>").
+                The result has the argument's type (a decimal keeps p and s) and is always nullable.
+     values     NULL arguments are ignored; with FILTER (WHERE p) -- the "filter" member of the aggregate entry -- a row where p is not
+                true counts as a NULL argument.  The v non-NULL values of a group are ordered as SortExec orders them (floats by
+                IEEE-754 totalOrder: -0.0 before 0.0, a positive NaN last).
+     result     v = 0: NULL.  v odd: the value at rank v / 2.  v even: lo = rank v / 2 - 1 and hi = rank v / 2 combined on the
+                column's own type -- integers and decimals: lo + hi wrapping at the declared width (8 / 16 / 32 / 64 / 128 bits), then
+                divided by 2 truncating toward zero (Int8 100, 120 -> -18; -3, 0 -> -1); floats: (lo + hi) / 2 in the column's
+                precision.
+     no rows    ungrouped: one row holding NULL; grouped: no rows.
+   Refused, with MEDIAN in the message: modes Partial / Final / FinalPartitioned (the state would be a list column), `distinct`, a
+   Float32 / Float64 group key on a node with a MEDIAN (bytewise segment heads and the hash aggregate need not agree on -0.0 / NaN),
+   group keys holding strings beyond 15 bytes.  APPROX_MEDIAN / APPROX_PERCENTILE_CONT are t-digest answers and stay refused.
+
+   gpuq_segment_heads: the segments of a table whose rows are sorted by `key_cols` (n_keys fixed-width columns of n rows as they lie:
+   Arrow layout, Utf8 as PACKED15; n_keys = 0: one segment).  Row i starts a segment when i = 0 or any key column differs from row
+   i - 1: validity first (NULL equals NULL), then the value's bytes.  seg_id_out (int32[n], or NULL): every row's segment, dense from 0;
+   starts_out (int32[starts_cap + 1]): the first row of segment g for g < min(G, starts_cap) and starts_out[G] = n when G <= starts_cap
+   (starts_cap = n always suffices); *n_groups_dev (device u64) = G.  n >= 2^31 is GPUQ_ERR_UNSUPPORTED (the scan is 32-bit).
+   gpuq_segment_median: one median per segment [starts[g], starts[g + 1]) of `value_col`, whose values are ascending inside every
+   segment with the NULLs last.  out_data: n_groups values of the column's width; out_validity: (n_groups + 63) / 64 * 8 bytes, 8-byte
+   aligned, written as whole words.  Both asynchronous. */
+int gpuq_segment_heads(gpuq_ctx* ctx, void* stream, const gpuq_column* key_cols, int n_keys, int64_t n, int32_t* seg_id_out, int32_t* starts_out, int64_t starts_cap,
+                       uint64_t* n_groups_dev);
+int gpuq_segment_median(gpuq_ctx* ctx, void* stream, const gpuq_column* value_col, const int32_t* starts, int64_t n_groups, void* out_data, uint8_t* out_validity);
+
 /* dst[i] = src[i] + delta for n Utf8 offsets: joining the offset arrays of partitions that are concatenated (fan-in). */
 int gpuq_offsets_rebase(gpuq_ctx* ctx, void* stream, const int32_t* src, int64_t n, int32_t delta, int32_t* dst);
 
@@ -494,6 +525,7 @@ int gpuq_copy_bits(gpuq_ctx* ctx, void* stream, uint8_t* dst, int64_t dst_bit_of
      {"ProjectionExec": {"input": node, "expr": [expr], "expr_name": [str]}}         (:1399-1403)
      {"AggregateExec": {"input", "mode", "group_expr": [{"expr","name"}], "aggr_expr": [{"fn","expr","expr2"?,"name"}],
                         "strategy"?, "expected_groups"?, "output_capacity"?}}        (:1405-1450)
+         fn: the operator's functions, and -- mode Single, this executor only -- MEDIAN ("expr", "filter"?; see gpuq_segment_median)
      {"HashJoinExec": {"left", "right", "on": [{"left": expr, "right": expr}], "join_type", "partition_mode",
                        "null_equals_null", "filter"?}}                               (:1346-1360)
      {"SortExec" | "SortPreservingMergeExec": {"input", "expr": [{"expr","asc","nulls_first"}], "fetch"?}}   (:1465-1478)
