@@ -539,4 +539,8 @@ __device__ __host__ __forceinline__ u64 hash_combine(u64 h, u64 lo, u64 hi, bool
   return mix64(h * 31 + v + 0x9E3779B97F4A7C15ull);
 }
 
+// ---------------------------------------------------------------- wave idioms
+// rank of this lane among the set bits of a wave ballot (blocks are one-dimensional multiples of 64 threads)
+__device__ __forceinline__ uint32_t lane_rank(const u64 ballot) { return (uint32_t)__popcll(ballot & ((1ull << (threadIdx.x & 63)) - 1)); }
+
 }  // namespace gpuq

@@ -80,6 +80,11 @@ struct HashTable {
   // Only for unique build keys (duplicates need the chain heads initialised).  nullptr = the array alone (NIL = no key).
   uint32_t* dense_bits;
 };
+// Membership in the direct-addressed table, in three steps that stay separate because callers with several rows in flight issue every
+// load before they test any: the index of a key (false: outside the table), the presence word of an index, the index's bit in that word.
+__device__ __forceinline__ bool dense_index(const HashTable& T, const u64 key, u64& idx) { idx = key - (u64)T.dense_min; return idx < T.dense_range; }
+__device__ __forceinline__ uint32_t dense_presence_word(const uint32_t* __restrict__ dense_bits, const u64 idx) { return dense_bits[idx >> 5]; }
+__device__ __forceinline__ bool dense_present(const uint32_t word, const u64 idx) { return (word >> (idx & 31)) & 1u; }
 // chain fusion: the build kernel first looks its rows up in ANOTHER join's table (kernels_hash.hip k_join_build_body)
 struct SemiProbe { HashTable T; KeySpec K; int32_t null_eq; int32_t on; uint32_t* hit_out; u64* rows_out; };
 enum JoinType : int32_t { JT_INNER = 0, JT_LEFT = 1, JT_RIGHT = 2, JT_FULL = 3, JT_LEFT_SEMI = 4, JT_LEFT_ANTI = 5, JT_RIGHT_SEMI = 6, JT_RIGHT_ANTI = 7 };

@@ -49,19 +49,22 @@ __device__ __forceinline__ bool make_key(const KeySpec& K, GPUQ_REGS_CPARAM, u64
   }
   // kw[] is indexed statically only (it must stay in VGPRs); the source register is the dynamic part
 #pragma unroll
+  // every word is written, and written ONCE: callers pass kw[] uninitialised, and a zero store followed by a conditional second
+  // store costs some kernels 30 VGPRs when nothing initialised the array before
   for (int q = 0; q < MAX_KW; ++q) {
-    kw[q] = 0;
+    u64 word = 0;
     if (q < K.key_words) {
       const int half = __builtin_amdgcn_readfirstlane(K.word_half[q]);
-      if (half == 2) kw[q] = knull;
+      if (half == 2) word = knull;
       else {
         const int r = __builtin_amdgcn_readfirstlane(K.word_reg[q]);
         const bool isn = (rnulls >> r) & 1;
         const u64 vl = rlo[r], vh = rhi[r];   // read both: a select of element pointers would demote the file to scratch
         const u64 v = (vl & ((u64)half - 1)) | (vh & (0 - (u64)half));
-        kw[q] = isn ? 0 : v;
+        word = isn ? 0 : v;
       }
     }
+    kw[q] = word;
   }
   hash = h;
   return knull != 0;
@@ -189,33 +192,73 @@ __global__ void __launch_bounds__(HBLOCK) k_ht_init(const HashTable T, const Agg
 }
 #endif
 
-// ------------------------------------------------------------------ hash aggregate
-// Rows-in-flight driver for the one-row-per-lane kernels (hash aggregate, key range, build, generic unique probe): a wave takes ROWS_U of its 64-row words per step.  With
-// the generated evaluator its three stages are used so that every column load of all ROWS_U words is issued before any loaded
-// value is looked at (one memory round trip per step instead of one per word: vmcnt is in order, and the one-shot evaluator waits
-// for its record before the next word's loads can be issued); with the interpreter the words are simply taken one after the other.
-// body(w, pos, active, regs...) runs wave-uniformly once per word (active = row exists and passes the fused predicate).
+// ------------------------------------------------------------------ the staged row front
+#ifdef GPUQ_JIT
+// Every kernel of this file that keeps several rows per lane in flight starts a step here: the U 64-row words w0, w0 + w_stride, ...
+// The generated evaluator is used in its three stages (expr_compile.cpp: pre / load / compute) so that EVERY column load of all U
+// words is issued before any loaded value is looked at: one memory round trip per step instead of one per word (vmcnt is in order,
+// and the one-shot evaluator waits for its record before the next word's loads can be issued).  Rows past the end (w >= w_end or
+// pos >= n: ex[u] false) are clamped to the last row and masked by the caller afterwards, so there are no exec-masked load regions.
+// Stages one and two: what comes back is what gpuq_jit_compute(P, posc[u], jw[u], regs) needs, word by word.
+template <int U>
+__device__ __forceinline__ void load_rows_staged(const DevProgram& P, const i64 n, const i64 w0, const i64 w_stride, const i64 w_end,
+                                                 i64 (&posc)[U], bool (&ex)[U], JitRaw (&jw)[U]) {
+  JitPre jq[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const i64 w = w0 + (i64)u * w_stride;
+    const i64 pos = (w << 6) + hlane();
+    ex[u] = w < w_end && pos < n;
+    posc[u] = ex[u] ? pos : (n > 0 ? n - 1 : 0);
+    gpuq_jit_pre(P, posc[u], jq[u]);
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) gpuq_jit_load(P, posc[u], jq[u], jw[u]);
+}
+// The whole front for the specialised kernels (one narrow key in a register known at compile time): stage three too, each word
+// handed to row(u, w, pos, active, regs...) with active = the row exists and passes the fused predicate.  row() runs for all U words,
+// wave-uniformly, also for words at or past w_end (all rows inactive): what a caller keeps per row is indexed by u, a constant in
+// each copy of the unrolled loop.
+template <int U, class Row>
+__device__ __forceinline__ void eval_rows_staged(const DevProgram& P, const i64 n, const i64 w0, const i64 w_stride, const i64 w_end, Row row) {
+  JitRaw jw[U]; i64 posc[U]; bool ex[U];
+  load_rows_staged<U>(P, n, w0, w_stride, w_end, posc, ex, jw);
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const i64 w = w0 + (i64)u * w_stride;
+    GPUQ_REGS_DECL;
+    const bool pass = gpuq_jit_compute(P, posc[u], jw[u], GPUQ_REGS);
+    row(u, w, (w << 6) + hlane(), ex[u] && pass, GPUQ_REGS);
+  }
+}
+// ONE narrow (<= 64-bit) key of a staged row, register R: its value and whether it is NULL, both cleared for a row that is not active
+template <int R>
+__device__ __forceinline__ u64 narrow_key(const bool active, GPUQ_REGS_CPARAM, bool& is_null) {
+  is_null = active && ((rnulls >> R) & 1);
+  return (active && !is_null) ? rlo[R] : 0;
+}
+#endif
+
+// Rows-in-flight driver for the one-row-per-lane kernels (hash aggregate, key range, build, generic unique probe): a wave takes its
+// words [w_first, w_end) (w_end < 0: to the last word) in steps of w_stride; body(w, pos, active, regs...) runs wave-uniformly once
+// per word (active = row exists and passes the fused predicate).  With the generated evaluator, the loads of GPUQ_ROWS_U words per
+// step are staged; the interpreter takes the words one after the other.
+// These bodies index the register file with run-time (wave-uniform) register numbers, which makes it a vector in VGPRs, and that
+// vector must be declared in the function that holds the loop and handed straight to the body: evaluated inside eval_rows_staged
+// instead, the interpreter instantiations of the build and of the unique probe take 30 more VGPRs and lose a wave of occupancy, and
+// the generated build re-initialises the 64 registers for every word (measured: 5 % on a 2^24-key build).  So stage three stays here.
 #ifndef GPUQ_ROWS_U
 #define GPUQ_ROWS_U 2
 #endif
 template <int MAXC, class Body>
 __device__ __forceinline__ void for_rows_in_flight(const DevProgram& P, const i64 n, const i64 w_first, const i64 w_stride, Body body, const i64 w_end = -1) {
   const i64 nw_all = (n + 63) >> 6;
-  const i64 nwords = (w_end >= 0 && w_end < nw_all) ? w_end : nw_all;      // words [w_first, nwords) in steps of w_stride
+  const i64 nwords = (w_end >= 0 && w_end < nw_all) ? w_end : nw_all;
 #ifdef GPUQ_JIT
   constexpr int U = GPUQ_ROWS_U;
   for (i64 w0 = w_first; w0 < nwords; w0 += w_stride * U) {
-    JitPre jq[U]; JitRaw jw[U]; i64 posc[U]; bool ex[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const i64 w = w0 + (i64)u * w_stride;
-      const i64 pos = (w << 6) + hlane();
-      ex[u] = w < nwords && pos < n;
-      posc[u] = ex[u] ? pos : n - 1;      // clamped, masked afterwards: no exec-masked load regions (n > 0 here: nwords > 0)
-      gpuq_jit_pre(P, posc[u], jq[u]);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) gpuq_jit_load(P, posc[u], jq[u], jw[u]);
+    JitRaw jw[U]; i64 posc[U]; bool ex[U];
+    load_rows_staged<U>(P, n, w0, w_stride, nwords, posc, ex, jw);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const i64 w = w0 + (i64)u * w_stride;
@@ -235,6 +278,47 @@ __device__ __forceinline__ void for_rows_in_flight(const DevProgram& P, const i6
   }
 #endif
 }
+
+// ------------------------------------------------------------------ per-wave queue in LDS
+// A FIFO of entries of N uint32_t fields, private to one wave: rows that need a further chain of dependent memory operations (a hit's
+// build row, a survivor's insert) are queued as they turn up, a few lanes per step, and worked off 64 at a time with every lane busy.
+// The kernel declares the storage (one uint32_t[N][CAP] per wave) and bounds what waits: at most CAP entries between head and tail.
+// head and tail are wave-uniform and count up; slots are taken modulo CAP.  Protocol: push() any number of times, publish() once, then
+// pop() while enough entries wait.  The lanes of a wave exchange data through LDS here, so the order of the LDS accesses is part of
+// the contract: publish() makes the pushed entries visible to every lane, and pop() ends with the wave barrier that keeps the next
+// push from overtaking its reads.
+template <int N, int CAP>
+struct WaveQueue {
+  uint32_t (&slots)[N][CAP];
+  uint32_t head = 0, tail = 0;
+  __device__ __forceinline__ explicit WaveQueue(uint32_t (&storage)[N][CAP]) : slots(storage) {}
+  __device__ __forceinline__ uint32_t size() const { return tail - head; }
+  // every lane calls; the lanes with `flag` append their entry, in lane order
+  __device__ __forceinline__ void push(const bool flag, const uint32_t (&fields)[N]) {
+    const u64 m = __ballot(flag);
+    if (flag) {
+      const uint32_t s = (tail + lane_rank(m)) % (uint32_t)CAP;
+#pragma unroll
+      for (int k = 0; k < N; ++k) slots[k][s] = fields[k];
+    }
+    tail += (uint32_t)__popcll(m);
+  }
+  __device__ __forceinline__ void publish() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+  // the cnt (<= 64, <= size()) oldest entries, entry i to lane i; true for the lanes that got one
+  __device__ __forceinline__ bool pop(const uint32_t cnt, uint32_t (&fields)[N]) {
+    const bool on = (uint32_t)hlane() < cnt;
+    const uint32_t s = (head + (on ? (uint32_t)hlane() : 0u)) % (uint32_t)CAP;
+#pragma unroll
+    for (int k = 0; k < N; ++k) fields[k] = slots[k][s];
+    head += cnt;
+    __builtin_amdgcn_wave_barrier();
+    return on;
+  }
+};
+
+// ------------------------------------------------------------------ hash aggregate
 
 template <int MAXC>
 __device__ __forceinline__ void k_agg_hash_body(const DevProgram P, const i64 n_arg, const KeySpec K, const AggSpec A, const HashTable T) {
@@ -323,7 +407,6 @@ __global__ void __launch_bounds__(HBLOCK) k_agg_hash_extract(const KeySpec K, co
   const u64 chunk_slots = 64ull * XSUB;
   const u64 nchunks = (T.n_slots + chunk_slots - 1) / chunk_slots;
   const u64 wave0 = (u64)blockIdx.x * HWAVES + hwave(), nwaves = (u64)gridDim.x * HWAVES;
-  const u64 ltmask = (1ull << hlane()) - 1;
   for (u64 c = wave0; c < nchunks; c += nwaves) {
     u64 masks[XSUB]; uint32_t total = 0;
 #pragma unroll
@@ -344,7 +427,7 @@ __global__ void __launch_bounds__(HBLOCK) k_agg_hash_extract(const KeySpec K, co
       if ((m >> hlane()) & 1) {
         const u64 s = c * chunk_slots + (u64)j * 64 + hlane();
         const u64* slot = T.slots + s * (u64)T.slot_words;
-        const uint32_t g = base + (uint32_t)__popcll(m & ltmask);
+        const uint32_t g = base + lane_rank(m);
         if (g < (uint32_t)out.cap) { if (K.state_key) emit_state_group(slot, K, A, soa, g); else emit_group(slot, cell0, K, A, out, g); }
       }
       base += (uint32_t)__popcll(m);
@@ -372,8 +455,6 @@ __device__ __forceinline__ void k_agg_bucket_id_body(const DevProgram P, const i
     GPUQ_REGS_DECL;
     const bool pass = GPUQ_EVAL(MAXC, P, pos);
     u64 kw[MAX_KW]; u64 h = 0;
-#pragma unroll
-    for (int q = 0; q < MAX_KW; ++q) kw[q] = 0;
     if (pass) make_key(K, GPUQ_REGS, kw, h);
     if (!ids) bid[pos] = ((h & bucket_mask) << 32) | (u64)(pass ? (uint32_t)pos : NIL);      // one 8-byte (bucket, row) record
     else { bid[pos] = h & bucket_mask; ids[pos] = pass ? (uint32_t)pos : NIL; }
@@ -417,8 +498,6 @@ __global__ void __launch_bounds__(HBLOCK) k_key_sample(const DevProgram P, const
     if (m && hlane() == 0) atomicAdd(&block_passed, (unsigned int)__popcll(m));
     if (!active) continue;
     u64 kw[MAX_KW]; u64 h = 0;
-#pragma unroll
-    for (int q = 0; q < MAX_KW; ++q) kw[q] = 0;
     make_key(K, GPUQ_REGS, kw, h);
     const u64 bit = mix64(h) & bit_mask;
     // few groups = a million samples on a handful of words: look before the atomic (q1's 4 groups: 5.9 ms of same-address
@@ -460,8 +539,6 @@ __device__ __forceinline__ void k_agg_lds_body(const DevProgram P, const i64 n_a
     if (active) active = GPUQ_EVAL(MAXC, P, pos);
     if (!active) continue;
     u64 kw[MAX_KW]; u64 h = 0;
-#pragma unroll
-    for (int q = 0; q < MAX_KW; ++q) kw[q] = 0;
     make_key(K, GPUQ_REGS, kw, h);
     uint32_t ls = NIL;
     if (!__hip_atomic_load(&lfull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
@@ -569,8 +646,6 @@ __device__ __forceinline__ void k_agg_bucket_body(const DevProgram P, const KeyS
       if (active) active = GPUQ_EVAL(MAXC, P, (i64)row);
       if (!active) continue;
       u64 kw[MAX_KW]; u64 h;
-#pragma unroll
-      for (int q = 0; q < MAX_KW; ++q) kw[q] = 0;
       make_key(K, GPUQ_REGS, kw, h);
       const uint32_t s = lds_find_or_insert<false>(bslots, cap, slot_words, key_words, kw, h, (uint32_t)(h >> 20), cap);      // bits the bucket id did not use
       if (s == NIL) { atomicOr(P.flags, FLAG_TABLE_FULL); continue; }
@@ -595,7 +670,7 @@ __device__ __forceinline__ void k_agg_bucket_body(const DevProgram P, const KeyS
         if (hlane() == 0 && m) wbase = atomicAdd(&cnt[pass], (uint32_t)__popcll(m));
         wbase = __shfl(wbase, 0);
         if (pass == 1 && live) {
-          const uint32_t g = gbase + wbase + (uint32_t)__popcll(m & ((1ull << hlane()) - 1));
+          const uint32_t g = gbase + wbase + lane_rank(m);
           if (g >= (uint32_t)out.cap) atomicOr(P.flags, FLAG_GROUP_OVERFLOW);
           else emit_group(slot, cell0, K, A, out, g);
         }
@@ -658,13 +733,21 @@ extern "C" __global__ void __launch_bounds__(HBLOCK) gpuq_jit_entry(const DevPro
 // key lookup shared by the probes: chain head row of the key, or NIL
 __device__ __forceinline__ uint32_t join_lookup(const HashTable& T, const u64 (&kw)[MAX_KW], const u64 h) {
   if (T.dense) {
-    const u64 idx = kw[0] - (u64)T.dense_min;
-    if (idx >= T.dense_range) return NIL;
-    if (T.dense_bits && !((T.dense_bits[idx >> 5] >> (idx & 31)) & 1u)) return NIL;
+    u64 idx;
+    if (!dense_index(T, kw[0], idx)) return NIL;
+    if (T.dense_bits && !dense_present(dense_presence_word(T.dense_bits, idx), idx)) return NIL;
     return T.dense[idx];
   }
   uint32_t payload;
   return ht_find(T, kw, h, payload) ? payload : NIL;
+}
+
+// The build's bookkeeping after a row found its place: the first row of a key ends its chain; a later one raises the duplicate flag
+// (the host then uses the chained probe) and links the row it displaced (`old`, NIL when the table keeps no head to displace).
+__device__ __forceinline__ void note_duplicate_and_link(const DevProgram& P, uint32_t* __restrict__ next, const uint32_t row, const bool inserted, const uint32_t old) {
+  // test first: one word must not be hammered
+  if (!inserted && !(__hip_atomic_load(P.flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & FLAG_DUP_BUILD_KEY)) atomicOr(P.flags, FLAG_DUP_BUILD_KEY);
+  if (next) next[row] = inserted ? NIL : old;
 }
 
 // Chain fusion (A |x| B) |x| C with A's keys unique: the build side of the second join is "the rows of B that find their key in A's
@@ -687,12 +770,17 @@ __device__ __forceinline__ void build_insert_dense(const DevProgram& P, const Ha
     old = __hip_atomic_exchange(T.dense + idx, row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     inserted = old == NIL;
   }
-  if (inserted) {
-    if (next) next[row] = NIL;
-  } else {
-    // duplicate key: remember it (the host then uses the chained probe) -- test first, one word must not be hammered
-    if (!(__hip_atomic_load(P.flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & FLAG_DUP_BUILD_KEY)) atomicOr(P.flags, FLAG_DUP_BUILD_KEY);
-    if (next) next[row] = old;
+  note_duplicate_and_link(P, next, row, inserted, old);
+}
+// Survivor queue of the chain-fused builds, entry = (position, index in the table being built, the other table's answer): the cnt oldest
+// entries go into the table, one per lane.  late_row: the other table's answer is an index into its row array, read only here.
+template <int CAP>
+__device__ __forceinline__ void insert_queued(WaveQueue<3, CAP>& q, const uint32_t cnt, const DevProgram& P, const HashTable& T, uint32_t* __restrict__ next,
+                                              const SemiProbe& S, const bool late_row) {
+  uint32_t e[3];
+  if (q.pop(cnt, e)) {
+    if (S.hit_out) S.hit_out[e[0]] = late_row ? S.T.dense[e[2]] : e[2];
+    build_insert_dense(P, T, next, (u64)e[1], e[0]);
   }
 }
 constexpr int BUILD_QCAP = 128;      // survivor queue per wave: < 64 waiting + <= 64 from one more word
@@ -708,33 +796,23 @@ __device__ __forceinline__ void k_join_build_body(const DevProgram P, const i64 
   // table's row for the hit vector).  Run per 64-row word, that chain is paid 2.3 M times with six lanes busy (measured: 2.27 ms for
   // the orders side, worse than the two-step form).  So the survivors of a wave are QUEUED in LDS -- (position, table index, the other
   // table's index) -- and inserted 64 at a time with every lane busy: the chain is paid once per 64 survivors.
-  __shared__ uint32_t q_pos[SEMI ? HWAVES : 1][SEMI ? BUILD_QCAP : 1], q_idx[SEMI ? HWAVES : 1][SEMI ? BUILD_QCAP : 1], q_aux[SEMI ? HWAVES : 1][SEMI ? BUILD_QCAP : 1];
+  constexpr int QC = SEMI ? BUILD_QCAP : 1;
+  __shared__ uint32_t q_lds[SEMI ? HWAVES : 1][3][QC];
+  WaveQueue<3, QC> q(q_lds[SEMI ? hwave() : 0]);
   const bool queued = SEMI && S.on && T.dense != nullptr;
   const bool s_bits = S.T.dense != nullptr && S.T.dense_bits != nullptr;      // the other table answers "is it there" from its bitmap alone
-  uint32_t qn = 0, survivors = 0;
-  const int wv = SEMI ? hwave() : 0;
-  auto flush = [&](const uint32_t from, const uint32_t cnt) {      // entries [from, from + cnt) of the queue, cnt <= 64
-    const bool on = (uint32_t)hlane() < cnt;
-    const uint32_t j = from + (on ? (uint32_t)hlane() : 0u);
-    const uint32_t pos = q_pos[wv][j], idx = q_idx[wv][j], aux = q_aux[wv][j];
-    if (on) {
-      if (S.hit_out) S.hit_out[pos] = s_bits ? S.T.dense[aux] : aux;
-      build_insert_dense(P, T, next, (u64)idx, pos);
-    }
-  };
+  uint32_t survivors = 0;
   for_rows_in_flight<MAXC>(P, n, (i64)blockIdx.x * HWAVES + hwave(), (i64)gridDim.x * HWAVES, [&](const i64 w, const i64 pos, bool active, GPUQ_REGS_PARAM) {
     uint32_t aux = NIL;
     if (SEMI && S.on) {
       bool found = false;
       if (active) {
         u64 kw1[MAX_KW]; u64 h1;
-#pragma unroll
-        for (int q = 0; q < MAX_KW; ++q) kw1[q] = 0;
         const bool null1 = make_key(S.K, GPUQ_REGS, kw1, h1);
         if (!(null1 && !S.null_eq)) {
           if (s_bits && queued) {
-            const u64 i1 = kw1[0] - (u64)S.T.dense_min;
-            if (i1 < S.T.dense_range && ((S.T.dense_bits[i1 >> 5] >> (i1 & 31)) & 1u)) { found = true; aux = (uint32_t)i1; }      // the row itself is read at the flush
+            u64 i1;
+            if (dense_index(S.T, kw1[0], i1) && dense_present(dense_presence_word(S.T.dense_bits, i1), i1)) { found = true; aux = (uint32_t)i1; }      // the row itself is read when the queue is worked off
           } else { aux = join_lookup(S.T, kw1, h1); found = aux != NIL; }
         }
       }
@@ -750,35 +828,26 @@ __device__ __forceinline__ void k_join_build_body(const DevProgram P, const i64 
       u64 idx = 0; bool ins = false;
       if (active) {
         u64 kw[MAX_KW]; u64 h;
-#pragma unroll
-        for (int q = 0; q < MAX_KW; ++q) kw[q] = 0;
         const bool any_null = make_key(K, GPUQ_REGS, kw, h);
-        idx = kw[0] - (u64)T.dense_min;
+        const bool in_range = dense_index(T, kw[0], idx);
         ins = !(any_null && !null_eq);
-        if (ins && idx >= T.dense_range) { atomicOr(P.flags, FLAG_TABLE_FULL); ins = false; }
+        if (ins && !in_range) { atomicOr(P.flags, FLAG_TABLE_FULL); ins = false; }
         if (!ins && S.hit_out) S.hit_out[pos] = s_bits ? S.T.dense[aux] : aux;      // a surviving row without a usable key is still a row of the build side
       }
-      const u64 m = __ballot(ins);
-      if (ins) {
-        const uint32_t j = qn + (uint32_t)__popcll(m & ((1ull << hlane()) - 1));
-        q_pos[wv][j] = (uint32_t)pos; q_idx[wv][j] = (uint32_t)idx; q_aux[wv][j] = aux;
-      }
-      qn += (uint32_t)__popcll(m);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      if (qn >= 64) { qn -= 64; flush(qn, 64); __builtin_amdgcn_wave_barrier(); }
+      q.push(ins, {(uint32_t)pos, (uint32_t)idx, aux});
+      q.publish();
+      while (q.size() >= 64) insert_queued(q, 64, P, T, next, S, s_bits);
       return;
     }
     if (!active) return;
     u64 kw[MAX_KW]; u64 h;
-#pragma unroll
-    for (int q = 0; q < MAX_KW; ++q) kw[q] = 0;
     const bool any_null = make_key(K, GPUQ_REGS, kw, h);
     uint32_t row = (uint32_t)pos;
     if (payload_via > 0) { row = P.via[payload_via - 1][pos]; if (present) atomicOr(&present[row >> 5], 1u << (row & 31)); }
     if (any_null && !null_eq) return;   // a NULL key never matches (SQL equi-join)
     if (T.dense) {
-      const u64 idx = kw[0] - (u64)T.dense_min;
-      if (idx >= T.dense_range) { atomicOr(P.flags, FLAG_TABLE_FULL); return; }      // cannot happen: the range was measured on these rows
+      u64 idx;
+      if (!dense_index(T, kw[0], idx)) { atomicOr(P.flags, FLAG_TABLE_FULL); return; }      // cannot happen: the range was measured on these rows
       build_insert_dense(P, T, next, idx, row);
       return;
     }
@@ -789,14 +858,9 @@ __device__ __forceinline__ void k_join_build_body(const DevProgram P, const i64 
       uint32_t* head = (uint32_t*)(T.slots + s * (u64)T.slot_words) + 1;   // high half of word 0
       old = __hip_atomic_exchange(head, row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (inserted) {
-      if (next) next[row] = NIL;
-    } else {
-      if (!(__hip_atomic_load(P.flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & FLAG_DUP_BUILD_KEY)) atomicOr(P.flags, FLAG_DUP_BUILD_KEY);
-      if (next) next[row] = old;
-    }
+    note_duplicate_and_link(P, next, row, inserted, old);
   });
-  if (queued && qn > 0) flush(0, qn);
+  if (queued && q.size() > 0) insert_queued(q, q.size(), P, T, next, S, s_bits);
   if (SEMI && S.on && S.rows_out) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) survivors += __shfl_xor(survivors, o);
@@ -806,7 +870,7 @@ __device__ __forceinline__ void k_join_build_body(const DevProgram P, const i64 
 #if defined(GPUQ_JIT) && defined(GPUQ_JIT_SEMI) && GPUQ_JIT_SEMI == 2
 // Chain fusion, specialised (run-time compiled) for the PK/FK shape: ONE narrow key on each side (registers JIT_KEY_REG0 = the key
 // the rows are looked up with in the other join's table, JIT_KEY2_REG = this build's key), a direct-addressed table to build, no
-// `present` bitmap.  The front is the unique probe's (k_join_probe_unique_body): U words of rows per step, every column load of all
+// `present` bitmap.  The front is the unique probe's (eval_rows_staged): U words of rows per step, every column load of all
 // U issued before any value is looked at, then the U lookups in the other table back to back; survivors go to the wave's LDS queue
 // and are inserted 64 at a time (see k_join_build_body).  The per-word form above waits for one lookup per word: 1.9 ms for the
 // orders side of SF100 q3 against 0.84 ms for the unique probe over the same rows.
@@ -816,68 +880,44 @@ __device__ __forceinline__ void k_join_build_semi1_body(const DevProgram P, cons
 #define GPUQ_SEMI_ROWS 4
 #endif
   constexpr int U = GPUQ_SEMI_ROWS;
-  constexpr int QC = 64 * (U + 1);
-  __shared__ uint32_t q_pos[HWAVES][QC], q_idx[HWAVES][QC], q_aux[HWAVES][QC];
+  constexpr int QC = 64 * (U + 1);      // < 64 waiting + <= 64 U from one more step
+  __shared__ uint32_t q_lds[HWAVES][3][QC];
+  WaveQueue<3, QC> q(q_lds[hwave()]);
   const i64 n = rows_of(P, n_arg);
   const i64 nwords = (n + 63) >> 6;
-  const int wv = hwave();
   const bool s_dense = S.T.dense != nullptr;
   const uint32_t* __restrict__ sbits = S.T.dense_bits;
-  const bool late_row = s_dense && sbits != nullptr;      // the other table's row is only read for the survivors, at the flush
-  uint32_t qn = 0, survivors = 0;
-  auto flush = [&](const uint32_t from, const uint32_t cnt) {
-    const bool on = (uint32_t)hlane() < cnt;
-    const uint32_t j = from + (on ? (uint32_t)hlane() : 0u);
-    const uint32_t pos = q_pos[wv][j], idx = q_idx[wv][j], aux = q_aux[wv][j];
-    if (on) {
-      if (S.hit_out) S.hit_out[pos] = late_row ? S.T.dense[aux] : aux;
-      build_insert_dense(P, T, next, (u64)idx, pos);
-    }
-  };
+  const bool late_row = s_dense && sbits != nullptr;      // the other table's row is only read for the survivors, when the queue is worked off
+  uint32_t survivors = 0;
   const i64 wave0 = ((i64)blockIdx.x * HWAVES + hwave()) * U, wstride = (i64)gridDim.x * HWAVES * U;
   for (i64 wb = wave0; wb < nwords; wb += wstride) {
-    bool act[U]; u64 key1[U], key2[U]; bool n1[U], n2[U]; i64 posc[U];
-    {
-      JitPre jq[U]; JitRaw jw[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const i64 pos = ((wb + u) << 6) + hlane();
-        act[u] = (wb + u) < nwords && pos < n;
-        posc[u] = act[u] ? pos : n - 1;      // clamped, masked afterwards (n > 0 here)
-        gpuq_jit_pre(P, posc[u], jq[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) gpuq_jit_load(P, posc[u], jq[u], jw[u]);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        GPUQ_REGS_DECL;
-        const bool pass = gpuq_jit_compute(P, posc[u], jw[u], GPUQ_REGS);
-        act[u] = act[u] && pass;
-        n1[u] = (rnulls >> JIT_KEY_REG0) & 1; n2[u] = (rnulls >> JIT_KEY2_REG) & 1;
-        key1[u] = rlo[JIT_KEY_REG0]; key2[u] = rlo[JIT_KEY2_REG];
-      }
-    }
+    bool act[U]; u64 key1[U], key2[U]; bool n1[U], n2[U]; uint32_t row[U];
+    eval_rows_staged<U>(P, n, wb, 1, nwords, [&](const int u, const i64, const i64 pos, const bool active, GPUQ_REGS_PARAM) __attribute__((always_inline)) {
+      act[u] = active; row[u] = (uint32_t)pos;
+      key1[u] = narrow_key<JIT_KEY_REG0>(active, GPUQ_REGS, n1[u]);
+      key2[u] = narrow_key<JIT_KEY2_REG>(active, GPUQ_REGS, n2[u]);
+    });
     // the other table: all U lookups in flight
     uint32_t aux[U]; bool found[U];
     if (s_dense) {
       uint32_t bw[U]; u64 i1[U]; bool in[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        i1[u] = key1[u] - (u64)S.T.dense_min;
-        in[u] = act[u] && !n1[u] && i1[u] < S.T.dense_range;
+        const bool in_range = dense_index(S.T, key1[u], i1[u]);
+        in[u] = act[u] && !n1[u] && in_range;
         bw[u] = 0;
-        if (in[u]) bw[u] = sbits ? sbits[i1[u] >> 5] : S.T.dense[i1[u]];
+        if (in[u]) bw[u] = sbits ? dense_presence_word(sbits, i1[u]) : S.T.dense[i1[u]];
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        if (sbits) { found[u] = in[u] && ((bw[u] >> (i1[u] & 31)) & 1u); aux[u] = (uint32_t)i1[u]; }
+        if (sbits) { found[u] = in[u] && dense_present(bw[u], i1[u]); aux[u] = (uint32_t)i1[u]; }
         else { found[u] = in[u] && bw[u] != NIL; aux[u] = bw[u]; }
       }
     } else {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         aux[u] = NIL;
-        if (act[u] && !n1[u]) { u64 kw1[MAX_KW]; for (int q = 0; q < MAX_KW; ++q) kw1[q] = 0; kw1[0] = key1[u]; aux[u] = join_lookup(S.T, kw1, hash_combine(0x243F6A8885A308D3ull, key1[u], 0, false)); }
+        if (act[u] && !n1[u]) { const u64 kw1[MAX_KW] = {key1[u]}; aux[u] = join_lookup(S.T, kw1, hash_combine(0x243F6A8885A308D3ull, key1[u], 0, false)); }
         found[u] = aux[u] != NIL;
       }
     }
@@ -885,22 +925,17 @@ __device__ __forceinline__ void k_join_build_semi1_body(const DevProgram P, cons
     for (int u = 0; u < U; ++u) {
       const bool surv = act[u] && found[u];
       survivors += surv ? 1u : 0u;
-      const u64 idx = key2[u] - (u64)T.dense_min;
+      u64 idx;
+      const bool in_range = dense_index(T, key2[u], idx);
       bool ins = surv && !n2[u];
-      if (ins && idx >= T.dense_range) { atomicOr(P.flags, FLAG_TABLE_FULL); ins = false; }
-      if (surv && !ins && S.hit_out) S.hit_out[posc[u]] = late_row ? S.T.dense[aux[u]] : aux[u];
-      const u64 m = __ballot(ins);
-      if (ins) {
-        const uint32_t j = qn + (uint32_t)__popcll(m & ((1ull << hlane()) - 1));
-        q_pos[wv][j] = (uint32_t)posc[u]; q_idx[wv][j] = (uint32_t)idx; q_aux[wv][j] = aux[u];
-      }
-      qn += (uint32_t)__popcll(m);
+      if (ins && !in_range) { atomicOr(P.flags, FLAG_TABLE_FULL); ins = false; }
+      if (surv && !ins && S.hit_out) S.hit_out[row[u]] = late_row ? S.T.dense[aux[u]] : aux[u];
+      q.push(ins, {row[u], (uint32_t)idx, aux[u]});
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    while (qn >= 64) { qn -= 64; flush(qn, 64); }
-    __builtin_amdgcn_wave_barrier();
+    q.publish();
+    while (q.size() >= 64) insert_queued(q, 64, P, T, next, S, late_row);
   }
-  if (qn > 0) flush(0, qn);
+  if (q.size() > 0) insert_queued(q, q.size(), P, T, next, S, late_row);
   if (S.rows_out) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) survivors += __shfl_xor(survivors, o);
@@ -929,6 +964,15 @@ extern "C" __global__ void __launch_bounds__(HBLOCK) gpuq_jit_entry(const DevPro
 #endif
 
 // ------------------------------------------------------------------ join probe
+// Does a probe row emit (once: unique build keys, or the semi / anti types)?  RightSemi on a hit, RightAnti on a miss; the types that
+// produce pairs on a hit, and those of them that keep every probe row (Right, Full) on a miss too, with no build row.
+__device__ __forceinline__ bool probe_row_emits(const int join_type, const bool active, const bool hit) {
+  if (join_type == JT_RIGHT_SEMI) return active && hit;
+  if (join_type == JT_RIGHT_ANTI) return active && !hit;
+  const bool want_pairs = (join_type == JT_INNER || join_type == JT_LEFT || join_type == JT_RIGHT || join_type == JT_FULL);
+  const bool probe_outer = (join_type == JT_RIGHT || join_type == JT_FULL);
+  return want_pairs && active && (hit || probe_outer);
+}
 // Emits (build_row, probe_row) pairs with wave-ballot compaction: one global atomic per wave per
 // chain step.  Pair order is not input order (DataFusion's is batch-local and unspecified across
 // partitions); the SET of pairs is deterministic.
@@ -942,6 +986,19 @@ __device__ __forceinline__ void k_join_probe_body(const DevProgram P, const i64 
   const bool emit_pairs = (join_type == JT_INNER || join_type == JT_LEFT || join_type == JT_RIGHT || join_type == JT_FULL);
   const bool probe_outer = (join_type == JT_RIGHT || join_type == JT_FULL);
   const bool mark = (visited != nullptr);
+  // the wave's rows with `emit` appended to the output: one atomic per wave for the base, the lane's rank among them for its place
+  auto append = [&](const bool emit, const uint32_t brow, const uint32_t prow) __attribute__((always_inline)) {
+    const u64 m = __ballot(emit);
+    if (m == 0) return;
+    u64 base = 0;
+    if (hlane() == 0) base = a_add(out_count, (u64)__popcll(m));
+    base = __shfl(base, 0);
+    if (emit) {
+      const u64 idx = base + lane_rank(m);
+      if (idx < out_cap) { if (out_build) out_build[idx] = brow; out_probe[idx] = prow; }
+      else atomicOr(P.flags, FLAG_OUT_OVERFLOW);
+    }
+  };
   for (i64 w = (i64)blockIdx.x * HWAVES + hwave(); w < nwords; w += (i64)gridDim.x * HWAVES) {
     const i64 pos = (w << 6) + hlane();
     bool active = pos < n;
@@ -952,41 +1009,17 @@ __device__ __forceinline__ void k_join_probe_body(const DevProgram P, const i64 
     if (active) {
       if (payload_via > 0) prow = P.via[payload_via - 1][pos];
       u64 kw[MAX_KW]; u64 h;
-#pragma unroll
-      for (int q = 0; q < MAX_KW; ++q) kw[q] = 0;
       const bool any_null = make_key(K, GPUQ_REGS, kw, h);
       if (!(any_null && !null_eq)) cur = join_lookup(T, kw, h);
     }
     if (join_type == JT_RIGHT_SEMI || join_type == JT_RIGHT_ANTI) {
-      const bool emit = active && ((join_type == JT_RIGHT_SEMI) == (cur != NIL));
-      const u64 m = __ballot(emit);
-      if (m) {
-        u64 base = 0;
-        if (hlane() == 0) base = a_add(out_count, (u64)__popcll(m));
-        base = __shfl(base, 0);
-        if (emit) {
-          const u64 idx = base + (u64)__popcll(m & ((1ull << hlane()) - 1));
-          if (idx < out_cap) { if (out_build) out_build[idx] = NULL_ROW; out_probe[idx] = prow; }
-          else atomicOr(P.flags, FLAG_OUT_OVERFLOW);
-        }
-      }
+      append(probe_row_emits(join_type, active, cur != NIL), NULL_ROW, prow);
       continue;
     }
     bool first = true;
     for (;;) {
       const bool has = (cur != NIL);
-      const bool emit = emit_pairs && active && (has || (first && probe_outer));
-      const u64 m = __ballot(emit);
-      if (m) {
-        u64 base = 0;
-        if (hlane() == 0) base = a_add(out_count, (u64)__popcll(m));
-        base = __shfl(base, 0);
-        if (emit) {
-          const u64 idx = base + (u64)__popcll(m & ((1ull << hlane()) - 1));
-          if (idx < out_cap) { out_build[idx] = has ? cur : NULL_ROW; out_probe[idx] = prow; }
-          else atomicOr(P.flags, FLAG_OUT_OVERFLOW);
-        }
-      }
+      append(emit_pairs && active && (has || (first && probe_outer)), has ? cur : NULL_ROW, prow);
       if (has) {
         if (mark) atomicOr(&visited[cur >> 5], 1u << (cur & 31));
         cur = next ? next[cur] : NIL;
@@ -1021,7 +1054,7 @@ __device__ __forceinline__ uint32_t emit_pairs(const bool emit, const uint32_t h
                                                uint32_t* __restrict__ seg_build, uint32_t* __restrict__ seg_probe) {
   const u64 m = __ballot(emit);
   if (emit) {
-    const u64 j = seg_base + cnt + (u64)__popcll(m & ((1ull << hlane()) - 1));
+    const u64 j = seg_base + cnt + lane_rank(m);
     if (seg_build) seg_build[j] = hit;
     seg_probe[j] = prow;
   }
@@ -1045,125 +1078,66 @@ __device__ __forceinline__ void k_join_probe_unique_body(const DevProgram P, con
   constexpr int U = GPUQ_PROBE_ROWS;
   // Hit queue (sparse domain, Inner / RightSemi): a probe that finds its key's bit set still has to fetch the build row from the row
   // array and write the pair -- a third dependent memory round trip per step that one row in a hundred needs (SF100 q3: 3.0 M hits in
-  // 323 M probes, measured; the 14.6 M quoted elsewhere are the first join's pairs).  Hits go to a FIFO in LDS (table index, probe row: first in, first out keeps probe order) and are resolved 64 at a
-  // time with every lane busy and full-wave coalesced pair stores; the per-step chain is columns -> bitmap.
-  constexpr int QC = 64 * (U + 1);
-  __shared__ uint32_t hq_idx[HWAVES][QC], hq_row[HWAVES][QC];
+  // 323 M probes, measured; the 14.6 M quoted elsewhere are the first join's pairs).  Hits go to the wave's queue in LDS (table index,
+  // probe row: first in, first out keeps probe order) and are resolved 64 at a time with every lane busy and full-wave coalesced pair
+  // stores; the per-step chain is columns -> bitmap.
+  constexpr int QC = 64 * (U + 1);      // < 64 waiting + <= 64 U from one more step
+  __shared__ uint32_t hq_lds[HWAVES][2][QC];
+  WaveQueue<2, QC> hq(hq_lds[hwave()]);
   const i64 seg = (i64)blockIdx.x * HWAVES + hwave();
   if (seg >= nsegs) return;
   const i64 nwords = (n + 63) >> 6;
   const i64 w0 = seg * wpw;
   i64 w1 = w0 + wpw; if (w1 > nwords) w1 = nwords;
   const u64 seg_base = (u64)w0 << 6;
-  const bool probe_outer = (join_type == JT_RIGHT || join_type == JT_FULL);
-  const bool want_pairs = (join_type == JT_INNER || join_type == JT_LEFT || join_type == JT_RIGHT || join_type == JT_FULL);
   const u64 mask = T.n_slots - 1;
   const ulonglong2* __restrict__ slots = (const ulonglong2*)T.slots;
   const uint32_t* __restrict__ dense = T.dense;
   uint32_t cnt = 0;
   const bool hit_queue = dense != nullptr && T.dense_bits != nullptr && visited == nullptr && (join_type == JT_INNER || join_type == JT_RIGHT_SEMI);
-  uint32_t qhead = 0, qtail = 0;      // wave-uniform; positions count up, slots are taken modulo QC
-  const int wvq = hwave();
-  auto drain = [&](const uint32_t n_out) {      // the n_out (<= 64) oldest hits -> pairs at seg_base + cnt
-    const bool on = (uint32_t)hlane() < n_out;
-    const uint32_t slot = (qhead + (on ? (uint32_t)hlane() : 0u)) % (uint32_t)QC;
-    const uint32_t idx = hq_idx[wvq][slot], pr = hq_row[wvq][slot];
-    if (on) {
+  auto resolve_hits = [&](const uint32_t n_out) __attribute__((always_inline)) {      // the n_out (<= 64) oldest hits -> pairs at seg_base + cnt
+    uint32_t e[2];
+    if (hq.pop(n_out, e)) {
       const u64 pos = seg_base + cnt + (u64)hlane();
-      if (seg_build) seg_build[pos] = dense[idx];
-      seg_probe[pos] = pr;
+      if (seg_build) seg_build[pos] = dense[e[0]];
+      seg_probe[pos] = e[1];
     }
-    cnt += n_out; qhead += n_out;
+    cnt += n_out;
   };
   for (i64 wb = w0; wb < w1; wb += U) {
     bool act[U]; u64 key[U]; u64 hs[U]; bool isn[U]; uint32_t prow[U];
-    // stage 1: evaluate U rows.  The generated evaluator is used in its three stages (expr_compile.cpp: pre / load / compute) so that
-    // EVERY column load of all U rows is issued before any loaded value is looked at: calling the one-shot evaluator per row puts
-    // each row's loads behind the previous row's predicate (vmcnt is in order), i.e. 2 U dependent memory round trips per step
-    // instead of 2.  Rows beyond the end are clamped to the last row and masked afterwards (no exec-masked load regions).
-#ifndef GPUQ_PROBE_STAGED
-#define GPUQ_PROBE_STAGED 1
-#endif
-#if GPUQ_PROBE_STAGED
-    {
-      JitPre jq[U]; JitRaw jw[U]; i64 posc[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const i64 pos = ((wb + u) << 6) + hlane();
-        act[u] = (wb + u) < w1 && pos < n;
-        posc[u] = act[u] ? pos : (n > 0 ? n - 1 : 0);
-        prow[u] = (uint32_t)pos;
-        gpuq_jit_pre(P, posc[u], jq[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) gpuq_jit_load(P, posc[u], jq[u], jw[u]);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        GPUQ_REGS_DECL;
-        const bool pass = gpuq_jit_compute(P, posc[u], jw[u], GPUQ_REGS);
-        act[u] = act[u] && pass;
-        isn[u] = pass && ((rnulls >> JIT_KEY_REG0) & 1);
-        key[u] = (pass && !isn[u]) ? rlo[JIT_KEY_REG0] : 0;
-        hs[u] = 0;
-        if (act[u] && payload_via > 0) prow[u] = P.via[payload_via - 1][posc[u]];
-      }
-    }
-#else
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const i64 pos = ((wb + u) << 6) + hlane();
-      act[u] = (wb + u) < w1 && pos < n;
-      key[u] = 0; hs[u] = 0; isn[u] = false; prow[u] = (uint32_t)pos;
-      if (act[u]) {
-        GPUQ_REGS_DECL;
-        act[u] = GPUQ_EVAL(MAXC, P, pos);
-        isn[u] = (rnulls >> JIT_KEY_REG0) & 1;
-        key[u] = isn[u] ? 0 : rlo[JIT_KEY_REG0];
-        if (payload_via > 0) prow[u] = P.via[payload_via - 1][pos];
-      }
-    }
-#endif
+    // stage 1: evaluate U rows, every column load of all of them in flight (eval_rows_staged)
+    eval_rows_staged<U>(P, n, wb, 1, w1, [&](const int u, const i64, const i64 pos, const bool active, GPUQ_REGS_PARAM) __attribute__((always_inline)) {
+      act[u] = active;
+      key[u] = narrow_key<JIT_KEY_REG0>(active, GPUQ_REGS, isn[u]);
+      hs[u] = 0;
+      prow[u] = (uint32_t)pos;
+      if (active && payload_via > 0) prow[u] = P.via[payload_via - 1][pos];
+    });
     uint32_t hit[U];
     if (dense) {
       // direct addressing: one load per row, all U in flight; neighbouring lanes with equal or adjacent keys share cache lines
       const uint32_t* __restrict__ dbits = T.dense_bits;
+      u64 idx[U]; bool in[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) { const bool in_range = dense_index(T, key[u], idx[u]); in[u] = act[u] && !isn[u] && in_range; }
       if (dbits) {
         // sparse domain: presence bits first (all U loads in flight), the row array only for the hits
-        uint32_t bw[U]; bool in[U];
+        uint32_t bw[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const u64 idx = key[u] - (u64)T.dense_min;
-          in[u] = act[u] && !isn[u] && idx < T.dense_range;
-          bw[u] = 0;
-          if (in[u]) bw[u] = dbits[idx >> 5];
-        }
+        for (int u = 0; u < U; ++u) { bw[u] = 0; if (in[u]) bw[u] = dense_presence_word(dbits, idx[u]); }
         if (hit_queue) {
 #pragma unroll
-          for (int u = 0; u < U; ++u) {
-            const u64 idx = key[u] - (u64)T.dense_min;
-            const bool h = in[u] && ((bw[u] >> (idx & 31)) & 1u);
-            const u64 m = __ballot(h);
-            if (h) { const uint32_t slot = (qtail + (uint32_t)__popcll(m & ((1ull << hlane()) - 1))) % (uint32_t)QC; hq_idx[wvq][slot] = (uint32_t)idx; hq_row[wvq][slot] = prow[u]; }
-            qtail += (uint32_t)__popcll(m);
-          }
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-          while (qtail - qhead >= 64u) drain(64u);
-          __builtin_amdgcn_wave_barrier();
+          for (int u = 0; u < U; ++u) hq.push(in[u] && dense_present(bw[u], idx[u]), {(uint32_t)idx[u], prow[u]});
+          hq.publish();
+          while (hq.size() >= 64u) resolve_hits(64u);
           continue;
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const u64 idx = key[u] - (u64)T.dense_min;
-          hit[u] = NIL;
-          if (in[u] && ((bw[u] >> (idx & 31)) & 1u)) hit[u] = dense[idx];
-        }
+        for (int u = 0; u < U; ++u) { hit[u] = NIL; if (in[u] && dense_present(bw[u], idx[u])) hit[u] = dense[idx[u]]; }
       } else {
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const u64 idx = key[u] - (u64)T.dense_min;
-          hit[u] = NIL;
-          if (act[u] && !isn[u] && idx < T.dense_range) hit[u] = dense[idx];
-        }
+        for (int u = 0; u < U; ++u) { hit[u] = NIL; if (in[u]) hit[u] = dense[idx[u]]; }
       }
     } else {
       // Neighbouring lanes with the same key (clustered foreign keys: the lines of one order) look the key up once: only the
@@ -1207,14 +1181,10 @@ __device__ __forceinline__ void k_join_probe_unique_body(const DevProgram P, con
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       if (visited && hit[u] != NIL) atomicOr(&visited[hit[u] >> 5], 1u << (hit[u] & 31));
-      bool emit;
-      if (join_type == JT_RIGHT_SEMI) emit = act[u] && hit[u] != NIL;
-      else if (join_type == JT_RIGHT_ANTI) emit = act[u] && hit[u] == NIL;
-      else emit = want_pairs && act[u] && (hit[u] != NIL || probe_outer);
-      cnt += emit_pairs(emit, hit[u], prow[u], seg_base, cnt, seg_build, seg_probe);
+      cnt += emit_pairs(probe_row_emits(join_type, act[u], hit[u] != NIL), hit[u], prow[u], seg_base, cnt, seg_build, seg_probe);
     }
   }
-  if (hit_queue && qtail != qhead) drain(qtail - qhead);
+  if (hit_queue && hq.size() > 0) resolve_hits(hq.size());
   if (hlane() == 0) seg_counts[seg] = cnt;
 }
 #else
@@ -1231,8 +1201,6 @@ __device__ __forceinline__ void k_join_probe_unique_body(const DevProgram P, con
   const i64 w0 = seg * wpw;
   i64 w1 = w0 + wpw; if (w1 > nwords) w1 = nwords;
   const u64 seg_base = (u64)w0 << 6;
-  const bool probe_outer = (join_type == JT_RIGHT || join_type == JT_FULL);
-  const bool want_pairs = (join_type == JT_INNER || join_type == JT_LEFT || join_type == JT_RIGHT || join_type == JT_FULL);
   uint32_t cnt = 0;
   // the segment's words in order (pair positions depend on it), two of them with all column loads in flight per step
   for_rows_in_flight<MAXC>(P, n, w0, 1, [&](const i64, const i64 pos, bool active, GPUQ_REGS_PARAM) {
@@ -1240,17 +1208,11 @@ __device__ __forceinline__ void k_join_probe_unique_body(const DevProgram P, con
     if (active) {
       if (payload_via > 0) prow = P.via[payload_via - 1][pos];
       u64 kw[MAX_KW]; u64 h;
-#pragma unroll
-      for (int q = 0; q < MAX_KW; ++q) kw[q] = 0;
       const bool any_null = make_key(K, GPUQ_REGS, kw, h);
       if (!(any_null && !null_eq)) hit = join_lookup(T, kw, h);
       if (visited && hit != NIL) atomicOr(&visited[hit >> 5], 1u << (hit & 31));
     }
-    bool emit;
-    if (join_type == JT_RIGHT_SEMI) emit = active && hit != NIL;
-    else if (join_type == JT_RIGHT_ANTI) emit = active && hit == NIL;
-    else emit = want_pairs && active && (hit != NIL || probe_outer);
-    cnt += emit_pairs(emit, hit, prow, seg_base, cnt, seg_build, seg_probe);
+    cnt += emit_pairs(probe_row_emits(join_type, active, hit != NIL), hit, prow, seg_base, cnt, seg_build, seg_probe);
   }, w1);
   if (hlane() == 0) seg_counts[seg] = cnt;
 }
@@ -1328,8 +1290,8 @@ __device__ __forceinline__ void k_rj_pack_body(const DevProgram P, const i64 n_a
     if (active) active = GPUQ_EVAL(MAXC, P, pos);
     u64 r = RJ_DROPPED; uint32_t d = G.nparts;
     if (active && !((rnulls >> kr) & 1)) {
-      const u64 idx = rlo[kr] - (u64)T.dense_min;
-      if (idx < T.dense_range) {
+      u64 idx;
+      if (dense_index(T, rlo[kr], idx)) {
         uint32_t prow = (uint32_t)pos;
         if (payload_via > 0) prow = P.via[payload_via - 1][pos];
         r = (idx << 32) | prow; d = (uint32_t)(idx >> G.shift);
@@ -1430,9 +1392,9 @@ __global__ void __launch_bounds__(HBLOCK) k_rj_probe(const u64* __restrict__ rec
     for (int u = 0; u < U; ++u) { const i64 pos = ((wb + u) << 6) + hlane(); act[u] = (wb + u) < g1 && pos < n; r[u] = act[u] ? rec[pos] : 0; }
     if (dbits) {
 #pragma unroll
-      for (int u = 0; u < U; ++u) { const u64 idx = r[u] >> 32; bw[u] = act[u] ? dbits[idx >> 5] : 0u; }
+      for (int u = 0; u < U; ++u) { bw[u] = act[u] ? dense_presence_word(dbits, r[u] >> 32) : 0u; }
 #pragma unroll
-      for (int u = 0; u < U; ++u) { const u64 idx = r[u] >> 32; hit[u] = NIL; if (act[u] && ((bw[u] >> (idx & 31)) & 1u)) hit[u] = dense[idx]; }
+      for (int u = 0; u < U; ++u) { const u64 idx = r[u] >> 32; hit[u] = NIL; if (act[u] && dense_present(bw[u], idx)) hit[u] = dense[idx]; }
     } else {
 #pragma unroll
       for (int u = 0; u < U; ++u) { hit[u] = NIL; if (act[u]) hit[u] = dense[r[u] >> 32]; }

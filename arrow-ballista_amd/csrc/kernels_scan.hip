@@ -120,7 +120,7 @@ __global__ void __launch_bounds__(BLOCK) k_compact(const u64* __restrict__ bitma
     const u64 m = bitmap[w];
     const int l = lane_id();
     if ((m >> l) & 1) {
-      const uint32_t rank = (uint32_t)__popcll(m & ((1ull << l) - 1));
+      const uint32_t rank = lane_rank(m);
       const i64 pos = (w << 6) + l;
       sel_out[out + rank] = sel_in ? sel_in[pos] : (uint32_t)pos;
     }

@@ -353,7 +353,7 @@ __global__ void __launch_bounds__(64) k_pq_decode(const uint8_t* __restrict__ fi
       const int i = i0 + flane();
       const uint32_t lv = i < n ? vidx[i] : 0u;
       const u64 m = __ballot(lv != 0);
-      const uint32_t mine = run + (uint32_t)__popcll(m & ((1ull << flane()) - 1));
+      const uint32_t mine = run + lane_rank(m);
       if (i < n) vidx[i] = lv ? mine : NULL_ROW;
       if (C.valid && m) {
         const i64 bit0 = P.row0 + i0; const int sh = (int)(bit0 & 63);

@@ -90,6 +90,13 @@ def test_chain_fused_build_jit(jit, mirror_layer):
         assert M.norm(M.arrow_rows(p.execute(0).to_arrow())) == M.norm(exp), run
 
 
+def test_chain_fused_build_queue_boundaries_jit(jit, mirror_layer):
+    """The one-narrow-key specialisation of the chain-fused build (GPUQ_JIT_SEMI 2) takes four words per step: with eight words per
+    wave its survivor queue is worked off in mid-loop (test_gpu_join_chain.build_queue_case)."""
+    import test_gpu_join_chain as M
+    M.build_queue_boundaries(jit)
+
+
 @pytest.mark.parametrize("jt", ["Inner", "Left", "Right", "Full", "RightSemi", "RightAnti"])
 def test_clustered_probe_keys_jit(jit, jt):
     """Foreign keys arrive clustered (the lines of one order are neighbours): the specialised unique-key probe looks a run

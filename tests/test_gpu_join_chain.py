@@ -4,6 +4,7 @@ rows must be those of the two-step form -- checked against a plain dictionary jo
 (plan.py executes the two joins one after the other) -- for every outer join type the fused form takes, with filters fused into each
 side, NULL keys, A's columns used above the join, duplicate keys in A (falls back), and again when executed deferred."""
 import collections
+import functools
 
 import numpy as np
 import pyarrow as pa
@@ -128,6 +129,68 @@ def test_chain_inner_metrics_and_large(tc):
     assert p.exec_stats() == {"deferred": True, "settles": 1, "host_syncs": 0, "retries": 0}
     m = [x for x in p.metrics() if x["node"] == "HashJoinExec"]
     assert sorted(x["output_rows"] for x in m) == sorted([3 * int(b_live.sum()), 3 * int(live.sum())])
+
+
+# survivors per 64-row word of B in build_queue_case, repeated.  13 words: a wave's words are a power of two apart, so its eight
+# words fall on different places of the cycle
+SURVIVORS_PER_WORD = [64, 64, 63, 1, 0, 64, 33, 0, 30, 1, 63, 64, 0]
+
+
+@functools.lru_cache(maxsize=1)
+def build_queue_case(n_cu):
+    """(A, B, C, rows of A |x| B, expected rows of (A |x| B) |x| C as columns ordered by cv).  B has 8 words of 64 rows for every wave
+    the build launches (4 waves x 8 blocks per CU), so every wave works its survivor queue off in mid-loop, not only at the end.  A:
+    4,096 unique keys 8 j (a sparse domain: its table is the presence bitmap).  B: row i has the unique key 4 i + 1 and looks up a
+    key of A in SURVIVORS_PER_WORD[w % 13] lanes of word w (a run of lanes that starts at a random lane and wraps), elsewhere in turn
+    an absent key inside A's range and a key above it; no NULLs.  C: 2^16 rows with keys of random rows of B, survivors or not."""
+    r = np.random.default_rng(41)
+    na, nb, nc = 4096, 8 * 64 * 4 * 8 * n_cu, 1 << 16
+    ak = 8 * r.permutation(na).astype(np.int64)
+    av = r.integers(0, 100, na).astype(np.int64)
+    av_of = np.empty(na, dtype=np.int64); av_of[ak // 8] = av
+    nw = nb // 64
+    want = np.array(SURVIVORS_PER_WORD)[np.arange(nw) % len(SURVIVORS_PER_WORD)]
+    survive = ((np.arange(64)[None, :] - r.integers(0, 64, nw)[:, None]) % 64 < want[:, None]).reshape(nb)
+    assert np.array_equal(survive.reshape(nw, 64).sum(axis=1), want)
+    j = r.integers(0, na, nb).astype(np.int64)
+    bka = np.where(survive, 8 * j, np.where(np.arange(nb) % 2 == 0, 8 * j + 3, 8 * na + j))
+    bkc = 4 * np.arange(nb, dtype=np.int64) + 1
+    ci = r.integers(0, nb, nc)
+    ck, cv = bkc[ci], np.arange(nc, dtype=np.int64)
+    A = pa.table({"ak": pa.array(ak), "av": pa.array(av)})
+    B = pa.table({"bka": pa.array(bka), "bkc": pa.array(bkc)})
+    C = pa.table({"ck": pa.array(ck), "cv": pa.array(cv)})
+    m = survive[ci]
+    exp = [bka[ci][m], av_of[bka[ci][m] // 8], bka[ci][m], bkc[ci][m], ck[m], cv[m]]
+    return A, B, C, int(survive.sum()), exp
+
+
+def build_queue_boundaries(tc):
+    import torch
+    A, B, C, ab_rows, exp = build_queue_case(torch.cuda.get_device_properties(tc.device).multi_processor_count)
+    p = g.NativePlan(_plan(A, B, C, "Inner"), tc)
+    runs = 3                      # synchronous, then deferred twice
+    for run in range(runs):
+        t = p.execute(0).to_arrow()
+        got = [t.column(k).to_numpy() for k in range(6)]
+        order = np.argsort(got[5], kind="stable")
+        for k in range(6):
+            assert np.array_equal(got[k][order], exp[k]), (run, k)
+    assert p.exec_stats()["deferred"]
+    m = [x for x in p.metrics() if x["node"] == "HashJoinExec"]
+    assert sorted(x["output_rows"] for x in m) == sorted([runs * ab_rows, runs * len(exp[5])])          # the metrics add up over the runs
+
+
+def test_build_queue_boundaries(tc):
+    """The chain-fused build queues the rows of B that survive the lookup in A's table per wave and inserts them 64 at a time.  The
+    cases above give every wave one or two words, so their queues are only ever emptied at the end; here every wave takes eight
+    words whose survivor counts fill the queue exactly, leave 63, 1 and 0 waiting, and add nothing (build_queue_case).  Interpreter
+    kernels (the generic body); test_gpu_jit.py runs the same case through the one-narrow-key specialisation."""
+    tc.ctx.set_jit("off")
+    try:
+        build_queue_boundaries(tc)
+    finally:
+        tc.ctx.set_jit("auto")
 
 
 def test_chain_without_the_inner_build_sides_columns(tc):

@@ -153,6 +153,84 @@ def test_segments_keep_probe_order_and_cover_ragged_tails(tc, layout, jitmode, j
     assert int(opb[k:].max().item() if k < n else -2) == -2                           # nothing written past the count
 
 
+# hits per 64-row probe word of test_hit_queue_boundaries.  The specialised probe takes 4 words per step and resolves queued hits 64
+# at a time, segments are 16 words: step 0 queues 256 hits, the first segment 448 in all (the 320-entry ring wraps); what waits after
+# a step's drain is 0, 0, 63, 0 in the first segment, 0 (a step of misses only), 1, 0, 63 in the second, 5 in the ragged third
+HITS_PER_WORD = [64, 64, 64, 64, 63, 1, 0, 64, 33, 0, 30, 0, 1, 0, 0, 0,
+                 0, 0, 0, 0, 64, 1, 0, 0, 63, 64, 64, 64, 64, 64, 64, 63,
+                 64, 5]
+
+
+def hit_queue_case():
+    """(build keys, probe keys, probe NULL mask, expected build row per probe row or -1): 1,024 unique build keys 8 i in shuffled row
+    order, 2,048 + 77 probe rows with HITS_PER_WORD[w] matching rows in word w at shuffled lanes; the other rows miss in turn with
+    an absent key inside the range (8 i + 3), a key below the minimum, a key above the maximum, and NULL (over a key that would match)."""
+    r = np.random.default_rng(31)
+    nb, n = 1024, 2048 + 77
+    bkeys = 8 * r.permutation(nb).astype(np.int64)
+    where = np.empty(nb, dtype=np.int64); where[bkeys // 8] = np.arange(nb)
+    pk = np.empty(n, dtype=np.int64); null = np.zeros(n, dtype=bool); exp = np.full(n, -1, dtype=np.int64)
+    assert len(HITS_PER_WORD) == (n + 63) // 64
+    miss = 0
+    for w, c in enumerate(HITS_PER_WORD):
+        rows = np.arange(64 * w, min(64 * w + 64, n))
+        hits = set(r.permutation(rows)[:c].tolist())
+        assert len(hits) == c
+        for p in rows:
+            i = int(r.integers(0, nb))
+            if p in hits:
+                pk[p], exp[p] = 8 * i, where[i]
+                continue
+            kind, miss = miss % 4, miss + 1
+            pk[p] = (8 * i + 3, -1 - 8 * i, 8 * nb + i, 8 * i)[kind]
+            null[p] = kind == 3
+    return bkeys, pk, null, exp
+
+
+@pytest.mark.parametrize("jt", ["Inner", "RightSemi", "Right", "RightAnti"])
+def test_hit_queue_boundaries(tc, jitmode, jt):
+    """The specialised unique probe over a sparse key domain (presence bitmap, chosen from the data: the key range is 8 x the key
+    count) queues its hits per wave and resolves them 64 at a time: hit counts per word that fill, wrap and exactly empty the
+    queue, leave 0, 1 and 63 waiting across steps, a step without a hit, a ragged last segment (HITS_PER_WORD).  Inner and
+    RightSemi take the queue, Right and RightAnti the same front without it; with run-time compilation off the interpreter probe
+    runs over the same rows.  Pair list == the host's probe-ordered list, element by element."""
+    import torch
+    bkeys, pk, null, hit = hit_queue_case()
+    nb, n = len(bkeys), len(pk)
+    dev = tc.device
+    bt = g.DeviceTable.from_arrow(pa.table({"k": pa.array(bkeys)}), dev)
+    pt = g.DeviceTable.from_arrow(pa.table({"k": pa.array(pk, mask=null)}), dev)
+    bs, ps = bt.schema(), pt.schema()
+    bop = tc.op({"op": "join_build", "input": {"fields": bs}, "on": [col("k", bs)]})
+    pop = tc.op({"op": "join_probe", "input": {"fields": ps}, "on": [col("k", ps)], "join_type": jt})
+    binp, _k1 = bt.input_struct()
+    pinp, _k2 = pt.input_struct()
+    h = C.c_void_p()
+    tc.ctx.check(tc.ctx.L.gpuq_join_build_run(bop.h, tc.stream_ptr(), C.byref(binp), 0, nb, C.byref(h)))
+    ob = torch.full((n,), -2, dtype=torch.int32, device=dev)
+    opb = torch.full((n,), -2, dtype=torch.int32, device=dev)
+    cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+    tc.ctx.check(tc.ctx.L.gpuq_join_probe_run(pop.h, tc.stream_ptr(), h, C.byref(pinp), 0, ob.data_ptr(), opb.data_ptr(), n, cnt.data_ptr()))
+    tc.sync()
+    pop.check(tc.stream_ptr())
+    k = int(cnt[0].item())
+    tc.ctx.L.gpuq_join_table_free(h)
+    rows = np.arange(n)
+    if jt == "Inner":
+        exp_b, exp_p = hit[hit >= 0], rows[hit >= 0]
+    elif jt == "Right":
+        exp_b, exp_p = hit, rows
+    elif jt == "RightSemi":
+        exp_b, exp_p = None, rows[hit >= 0]
+    else:
+        exp_b, exp_p = None, rows[hit < 0]
+    assert k == len(exp_p)
+    assert np.array_equal(opb[:k].cpu().numpy().astype(np.int64), exp_p)
+    if exp_b is not None:
+        assert np.array_equal(ob[:k].cpu().numpy().astype(np.int64), exp_b)          # -1 == NULL_ROW (0xFFFFFFFF) for unmatched outer rows
+    assert int(opb[k:].max().item() if k < n else -2) == -2                           # nothing written past the count
+
+
 def test_capacity_overflow_is_reported(tc, layout):
     """out_cap smaller than the pair count: the count is still exact, the check reports GPUQ_ERR_CAPACITY, nothing is written past out_cap."""
     import torch
