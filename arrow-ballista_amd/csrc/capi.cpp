@@ -67,6 +67,7 @@ struct gpuq_op {
   struct PostChunk { CompiledProgram prog; DevBuf code; int first_out = 0; };
   std::deque<PostChunk> posts; Schema post_schema;
   i64 expected_groups = 0;
+  int agg_path = 0;                 // the way this operator's last run took (Learned::ag::path numbering; 0: it has not run)
   // join
   int join_type = JT_INNER; int null_eq = 0; bool build_side_rows = true;
   bool has_semi = false; KeySpec semi_keys{};      // chain fusion: the keys this build's rows are looked up with in another join's table
@@ -84,17 +85,18 @@ struct gpuq_op {
   struct Learned {
     struct { bool valid = false, dense = false, sparse_bits = false, has_dups = false; i64 kmin = 0; u64 krange = 0; } jb;
     // groups / path: what this operator's previous run produced and the way it took (1 LDS dictionary, 2 global hash table, 3 radix-
-    // partitioned); they outlive `valid` (only paths 1 and 2 can be replayed) and steer the next synchronous run
+    // partitioned, 4 runs of key-clustered input); they outlive `valid` (paths 1, 2 and 4 can be replayed) and steer the next synchronous run
     struct { bool valid = false; int path = 0, gmax = 0; u64 est = 0; bool use_lds = false; i64 groups = -1; } ag;
     struct { bool valid = false; SortPack K{}; int total = 0; } so;
     bool join_guess_failed = false, sort_guess_failed = false;      // a guessed key range / key layout did not hold once: measure from now on
+    bool agg_runs_failed = false;      // the aggregate's input was not clustered on its key once (FLAG_AGG_RUNS): the table from now on
     uint32_t expect_flags = 0;      // status bits a deferred run is allowed to raise (a build side known to hold duplicate keys)
     void forget() { jb.valid = ag.valid = so.valid = false; }
   } learned;
   // scratch, by operator kind (an operator has one): kept across calls, grown when a call needs more
   struct { DevBuf bitmap, counts, total; } w_filter;
   // raw result (keys, key_nulls, cells), partials of the LDS dictionary, hash table, result columns, cardinality sample, parked float sums
-  struct { DevBuf keys, key_nulls, cells, tiny, table, soa, sample, fstage; } w_agg;
+  struct { DevBuf keys, key_nulls, cells, tiny, table, soa, sample, fstage, runs; } w_agg;      // runs: the per-segment words of the runs path
   struct { DevBuf key_range; } w_build;
   struct { DevBuf seg_build, seg_probe, counts, rec, rec2, hist, scan, locality; } w_probe;      // rec .. scan: the partitioned probe
   // blocks: the min/max blocks of the key plan, then the split points of a merge round (the plan has been read back by then)
@@ -194,12 +196,13 @@ void raise_flags(uint32_t f) {
   if (f & FLAG_TABLE_FULL) throw std::runtime_error("hash table full");
   if (f & FLAG_GROUP_OVERFLOW) throw Capacity("group capacity exceeded");
   if (f & FLAG_SORT_LAYOUT) throw std::runtime_error("a row does not fit the remembered sort key layout");
+  if (f & FLAG_AGG_RUNS) throw std::runtime_error("the aggregate's input is not clustered on its key");
 }
 // What follows a status read: a bit outside `tolerated` is an error -- the word is cleared for the next run and the bit raised.  The
 // tolerated bits are handed back and are still set on the device: the site says whether it clears them or its next launch does.
 // Only the tolerated bits are kept from raise_flags.  One aggregate site used to hand it the whole word; that is the same, because
 // raise_flags tests FLAG_GROUP_OVERFLOW (what an aggregate tolerates) behind every other bit an aggregate's kernels raise: only
-// FLAG_SORT_LAYOUT follows it.
+// FLAG_SORT_LAYOUT and FLAG_AGG_RUNS follow it.
 uint32_t raise_unless(gpuq_op* op, hipStream_t s, uint32_t f, uint32_t tolerated = 0) {
   if (f & ~tolerated) { reset_flags(op, s); raise_flags(f & ~tolerated); }
   return f & tolerated;
@@ -606,7 +609,7 @@ int gpuq_ops_settle(gpuq_ctx* ctx, void* stream, gpuq_op* const* ops, int n_ops,
       static const bool trace = getenv("GPUQ_TRACE_DEFER") != nullptr;
       const uint32_t expected = ops[i]->learned.expect_flags;
       if (trace && (f & ~expected)) fprintf(stderr, "[gpuq] settle: operator %d of %d (kind %d) raised status 0x%x (expected 0x%x)\n", i, n_ops, (int)ops[i]->kind, f, expected);
-      if (f & ~expected) { retry = true; ops[i]->learned.forget(); }
+      if (f & ~expected) { retry = true; ops[i]->learned.forget(); if (f & FLAG_AGG_RUNS) ops[i]->learned.agg_runs_failed = true; }
     }
     if (retry) throw Retry("an assumption of a deferred run did not hold");
   });
@@ -621,6 +624,10 @@ int gpuq_op_profile(gpuq_op* op, int enable, float* kernel_ms_out, int* launches
     op->last_total_ms = op->total_ms;
     op->kernel_ms = 0; op->total_ms = 0; op->launches = 0; if (enable >= 0) op->profile = enable != 0;
   });
+}
+const char* gpuq_op_agg_path(gpuq_op* op) {
+  static const char* const names[] = {"", "tiny", "table", "radix", "runs"};
+  return (op && op->kind == K_AGG && op->agg_path >= 0 && op->agg_path <= 4) ? names[op->agg_path] : "";
 }
 int gpuq_op_profile_total(gpuq_op* op, float* total_ms_out) {      // of the interval the last gpuq_op_profile call closed
   if (!op || !total_ms_out) return GPUQ_ERR_INVALID;
@@ -774,6 +781,37 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
       if (direct) { layout_soa((uint32_t)raw.cap, true); soa_filled = true; }
       launch_agg_hash_extract(s, Krun, op->agg, T, raw, op->flags_dev.as<uint32_t>(), direct ? &soa : nullptr);
     };
+    // runs of key-clustered input (path 4): no table.  Eligible: the key packs into the state word and every accumulator's finished cell
+    // is its own result whatever the order of the folds (integer SUM, the counts, the bitwise kinds).  Two halves, because the
+    // synchronous form sizes the result from the count: count = heads per segment, scanned into the group count word, and the order test
+    // (FLAG_AGG_RUNS: the input is not clustered after all); write = one row per run into columns of `rcap` rows whose accumulator cells
+    // start as the identities (the pieces of a run that crosses a word boundary fold into them)
+    bool runs_ok = nk > 0 && op->keys.state_key;
+    for (int a = 0; a < na; ++a) {
+      const int kd = op->agg.acc_kind[a];
+      runs_ok = runs_ok && (kd == ACC_SUM || kd == ACC_COUNT || kd == ACC_COUNT_STAR || kd == ACC_BAND || kd == ACC_BOR || kd == ACC_BXOR);
+    }
+    RunsGeom G{};
+    auto launch_runs_count = [&](const bool reset) {
+      Krun = op->keys;
+      G = agg_runs_geometry(n);
+      const size_t segs = (size_t)std::max<int32_t>(G.nsegs, 1);
+      G.seg_last = (u64*)op->w_agg.runs.ensure(segs * 20 + 16); G.seg_first = G.seg_last + segs; G.counts = (uint32_t*)(G.seg_first + segs);
+      raw.n_groups = n_groups_dev(op);
+      if (reset) reset_flags(op, s);
+      if (G.nsegs <= 0) { HIPCHECK(hipMemsetAsync(raw.n_groups, 0, 8, s)); return; }
+      { SinkJit jit(op, op->prog, GPUQ_SINK_AGG_RUNS_COUNT, n); launch_agg_runs_count(s, jit.fn, P, n, Krun, G); }
+      launch_scan_block_counts(s, G.counts, G.nsegs, (u64*)raw.n_groups);      // (the count and its pad: OpStatus)
+      launch_agg_runs_order(s, G, op->flags_dev.as<uint32_t>());
+    };
+    auto launch_runs_write = [&](const i64 rcap) {
+      raw.cap = (int32_t)rcap;
+      layout_soa((uint32_t)rcap, true); soa_filled = true;
+      if (na > 0) HIPCHECK(hipMemsetAsync(soa.acc_col[0], 0, (size_t)na * (size_t)rcap * 16, s));      // (the accumulator columns follow each other)
+      for (int a = 0; a < na; ++a) if (op->agg.acc_kind[a] == ACC_BAND) launch_fill_cells(s, soa.acc_col[a], rcap, ~0ull, 0);
+      SinkJit jit(op, op->prog, GPUQ_SINK_AGG_RUNS_WRITE, n); ProfScope ps(op, s);
+      launch_agg_runs_write(s, jit.fn, P, n, Krun, op->agg, G, soa, (uint32_t)rcap);
+    };
     // radix-partitioned (path 3).  High cardinality: partition the rows by key hash into buckets whose groups fit an LDS table, aggregate
     // every bucket inside one block (kernels_hash.hip).  false: on to the global table -- a bucket overflowed (skew, or more groups than
     // the hint promised)
@@ -824,7 +862,7 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
     // bound: on to the synchronous form
     if (ndev_out && op->deferred && L.ag.valid) {
       if (L.ag.path == 1) {
-        if (cap >= 64) { launch_tiny(L.ag.gmax, false); finish_on_device(); return; }
+        if (cap >= 64) { launch_tiny(L.ag.gmax, false); op->agg_path = 1; finish_on_device(); return; }
       } else if (L.ag.path == 2) {
         // the table follows the group count of the last run (+ 1/4), not the size that run happened to use (its first run sizes from a sample)
         const u64 est = std::min<u64>(std::max<u64>(L.ag.est, 64), (u64)(L.ag.groups + L.ag.groups / 4 + 64));
@@ -833,6 +871,17 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
           launch_table(est, agg_slot_pct(true), L.ag.use_lds, false);
           alloc_raw(rcap);
           extract();
+          op->agg_path = 2;
+          finish_on_device();
+          return;
+        }
+      } else if (L.ag.path == 4) {
+        // a set FLAG_AGG_RUNS (the input is no longer clustered) or FLAG_GROUP_OVERFLOW is found at the settle, like a full table
+        const i64 rcap = std::min<i64>(L.ag.groups + L.ag.groups / 4 + 1024, cap);
+        if (rcap >= 1 && rcap <= 0x7FFFFFFFll) {
+          launch_runs_count(false);
+          launch_runs_write(rcap);
+          op->agg_path = 4;
           finish_on_device();
           return;
         }
@@ -900,9 +949,25 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
     // (a count that is merely REMEMBERED says nothing about how the keys lie: the run that produced it went through the global table --
     // e.g. because its keys are clustered, which the table's wave-level run combining turns into one touch per run -- so the same
     // path is taken again; the partitioned form is for a caller's hint or a sample that saw every group several times)
-    const bool remembered_hash = op->expected_groups <= 0 && L.ag.path == 2;
+    const bool remembered_hash = op->expected_groups <= 0 && (L.ag.path == 2 || L.ag.path == 4);
     if (!done && (strat == "radix" || (strat == "auto" && !remembered_hash && ((n >= (1ll << 22) && op->expected_groups >= (1ll << 20)) ||
                                                             (n >= (1ll << 20) && known_groups >= 4096))))) { done = run_radix(strat, known_groups); if (done) path_done = 3; }
+    // where the global table would be next: runs, when asked for ("runs") or when a large input may well be clustered on its key (auto:
+    // eligible, 2^20 rows or more, and this operator's input has not failed the order test before).  A failed try falls to the table in
+    // the same call: the write pass has not run, the count pass is what it cost
+    if (!done && runs_ok && (strat == "runs" || (strat == "auto" && n >= (1ll << 20) && !L.agg_runs_failed))) {
+      launch_runs_count(true);
+      HIPCHECK(hipGetLastError());
+      const OpStatus st = read_status(op, s);
+      if (raise_unless(op, s, st.flags, FLAG_AGG_RUNS)) { L.agg_runs_failed = true; reset_flags(op, s); }
+      else {
+        ng = st.n_groups;
+        launch_runs_write(std::max<i64>(ng, 1));
+        HIPCHECK(hipGetLastError());
+        raise_unless(op, s, read_flags(op, s));
+        done = true; path_done = 4;
+      }
+    }
     if (!done) {
       // global hash table; grow on FLAG_TABLE_FULL
       // the group count this operator produced last time (another partition of the same stage, the same query again) stands in
@@ -965,7 +1030,8 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
         }
       }
     }
-    L.ag = {path_done == 1 || path_done == 2, path_done, gmax_done, est_done, lds_done, (i64)ng};
+    L.ag = {path_done == 1 || path_done == 2 || path_done == 4, path_done, gmax_done, est_done, lds_done, (i64)ng};
+    op->agg_path = path_done;
     if (L.ag.valid) L.expect_flags = 0;
     if (n_groups_out) *n_groups_out = ng;
     if ((i64)ng > cap) throw Capacity("aggregate produced " + std::to_string(ng) + " groups, output capacity is " + std::to_string(cap));

@@ -139,6 +139,7 @@ constexpr uint32_t FLAG_OUT_OVERFLOW = 16u;
 constexpr uint32_t FLAG_WIDE_MINMAX = 32u;  // MIN/MAX over a value outside the int64 range
 constexpr uint32_t FLAG_DEC_OVERFLOW = 128u;  // a decimal result (or an operand rescaled by a power of ten) left 127 bits / its 38 digits: arrow-arith raises there
 constexpr uint32_t FLAG_SORT_LAYOUT = 64u;  // a row does not fit the composite sort key layout remembered from the previous run (deferred execution)
+constexpr uint32_t FLAG_AGG_RUNS = 256u;    // the aggregate's input is not clustered on its key in increasing order (the "runs" path does not apply)
 
 // Per-lane register file.  lo/hi MUST be separate plain u64 arrays local to the kernel: hipcc then
 // keeps them in VGPRs and lowers wave-uniform dynamic indexing to s_set_gpr_idx_on.  Wrapped in a

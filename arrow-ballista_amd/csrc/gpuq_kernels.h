@@ -185,6 +185,37 @@ __device__ __forceinline__ u64 acc_result_hi(const int kind, const u64 lo, const
   return (kind == ACC_MIN || kind == ACC_MAX) ? (u64)((i64)lo >> 63) : hi;
 }
 
+// ----- aggregate over key-clustered input ("runs", kernels_hash.hip k_agg_runs_count / k_agg_runs_write): the head / output-row arithmetic,
+// plain functions so that a host program can call them too.  Rows are looked at 64 at a time (one wave-word); a key is the packed
+// state-word key (< 2^62) and travels as key + 1 where 0 has to mean "no row".
+//   active      the row exists and passes the fused predicate
+//   below       row pos - 1 is active (lane 0: the last row of the word before)
+//   prev_p1     key + 1 of the nearest active row before this one, as far back as the wave's segment reaches (0: none there)
+// A row starts a run (is a head) when it is active and does not continue the run of the row directly below it.
+__host__ __device__ inline bool runs_head(const bool active, const bool below, const u64 prev_p1, const u64 key) { return active && !(below && prev_p1 == key + 1); }
+// A head must exceed every key before it; rows before it are non-decreasing unless an earlier head already failed this test, so the
+// nearest active row stands for all of them.  (Equal keys around an inactive row are two runs of one key: out of order, by this rule.)
+__host__ __device__ inline bool runs_out_of_order(const bool head, const u64 prev_p1, const u64 key) { return head && prev_p1 != 0 && key + 1 <= prev_p1; }
+// the lanes 0..lane of a 64-bit lane mask
+__host__ __device__ inline u64 runs_lanes_le(const u64 mask, const int lane) { return mask & (~0ull >> (63 - lane)); }
+// Output row of the active row in `lane`: (heads up to and including the row) - 1 = heads of the earlier segments (base) + of this
+// segment's earlier words + of this word's lanes 0..lane, - 1.  A row that continues a run from before the word gets that run's row.
+__host__ __device__ inline uint32_t runs_out_row(const uint32_t base, const uint32_t heads_before_word, const u64 head_mask, const int lane) {
+  return base + heads_before_word + (uint32_t)__builtin_popcountll(runs_lanes_le(head_mask, lane)) - 1u;
+}
+// A piece is a run's share of one word; it ends in `tail_lane` and starts in the nearest lane at or below it that does not continue
+// the lane below (start_mask: those lanes; lane 0 always is one).  It is the whole run -- interior, its cells are stored plainly --
+// when it starts with a head and ends before lane 63 (what follows is then another run, an inactive row or the end of the input).
+// Any other piece may share its run with a neighbouring word and folds into the run's cells atomically.
+__host__ __device__ inline bool runs_piece_interior(const u64 head_mask, const u64 start_mask, const int tail_lane) {
+  const int start = 63 - __builtin_clzll(runs_lanes_le(start_mask, tail_lane) | 1ull);
+  return tail_lane < 63 && ((head_mask >> start) & 1ull);
+}
+// How the rows are dealt out: wave-segment s (one wave of a block, segments of a block are neighbours) owns the 64-row words
+// [s * wps, (s + 1) * wps); per segment the count kernel leaves its number of heads (scanned into the segment's first output row),
+// key + 1 of its last active row and of the one head it could not test (nothing active before it inside the segment): 0 = none.
+struct RunsGeom { i64 wps; int32_t nsegs; int32_t pad; uint32_t* counts; u64* seg_last; u64* seg_first; };
+
 // LDS open-addressing table of one block: slot = [state (0 empty, 1 being written, else tag), hash if STORE_HASH, key words, cells].
 // Finds the key's slot or claims one, starting at slot `start & (cap - 1)` and giving up (NIL) after max_probes occupied slots.
 template <bool STORE_HASH>
@@ -293,6 +324,8 @@ struct GatherWords { int32_t n; int32_t pad; const u64* src[64]; };
 #define GPUQ_SINK_AGG_LDS 13
 #define GPUQ_SINK_JOIN_KEYRANGE 14
 #define GPUQ_SINK_RJ_PACK 15
+#define GPUQ_SINK_AGG_RUNS_COUNT 16
+#define GPUQ_SINK_AGG_RUNS_WRITE 17
 
 #ifndef GPUQ_JIT
 // ---- host launch interface (AOT build only)
@@ -313,6 +346,8 @@ constexpr SinkInfo GPUQ_SINKS[] = {
     {GPUQ_SINK_AGG_LDS, "kernels_hash.hip", "gpuq_jit_agg_lds"},
     {GPUQ_SINK_JOIN_KEYRANGE, "kernels_hash.hip", "gpuq_jit_join_keyrange"},
     {GPUQ_SINK_RJ_PACK, "kernels_hash.hip", "gpuq_jit_rj_pack"},
+    {GPUQ_SINK_AGG_RUNS_COUNT, "kernels_hash.hip", "gpuq_jit_agg_runs_count"},
+    {GPUQ_SINK_AGG_RUNS_WRITE, "kernels_hash.hip", "gpuq_jit_agg_runs_write"},
 };
 // The launchers of the sinks take `jit_fn`: the specialised function to run (capi.cpp's SinkJit resolves it), or nullptr for the AOT kernel.
 void launch_gather_words(hipStream_t s, const GatherWords& g, u64* out);
@@ -339,6 +374,14 @@ void launch_agg_bucket(hipStream_t s, void* jit_fn, const DevProgram& P, const K
                        uint32_t cap, int slot_words, const AggOut& out);
 // soa: state-word keys only (K.state_key): the groups are written as result columns directly (out gives the capacity and the count word)
 void launch_agg_hash_extract(hipStream_t s, const KeySpec& K, const AggSpec& A, const HashTable& T, const AggOut& out, uint32_t* flags, const AggSoA* soa = nullptr);
+// aggregate over key-clustered input (state-word keys): the segments of `n` rows (arrays not set), then the launches in their order --
+// heads per segment; launch_scan_block_counts(counts, nsegs, the group count word) in between; the order test across segments
+// (FLAG_AGG_RUNS); one result row per run, written into columns whose accumulator cells hold their identities (cap rows)
+RunsGeom agg_runs_geometry(i64 n);
+void launch_agg_runs_count(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const RunsGeom& G);
+void launch_agg_runs_order(hipStream_t s, const RunsGeom& G, uint32_t* flags);
+void launch_agg_runs_write(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const AggSpec& A, const RunsGeom& G, const AggSoA& soa, uint32_t cap);
+void launch_fill_cells(hipStream_t s, ulonglong2* cells, i64 n, u64 lo, u64 hi);
 // false: no interpreter kernel for this shape (chain fusion over more than 8 input columns)
 bool launch_join_build(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const HashTable& T, uint32_t* next, uint32_t* present,
                        int payload_via, int null_equals_null, const SemiProbe* semi = nullptr);

@@ -134,10 +134,8 @@ __device__ __forceinline__ u64 ht_state_find_or_insert(const HashTable& T, const
   }
   return ~0ull;
 }
-#ifndef GPUQ_JIT
-// a finished slot of such a table written as row g of the result COLUMNS (validity words start as all ones: a NULL key clears its bit)
-__device__ __forceinline__ void emit_state_group(const u64* slot, const KeySpec& K, const AggSpec& A, const AggSoA& soa, const uint32_t g) {
-  const u64 st = slot[0] >> 2;
+// a packed key written as the key columns of row g of the result COLUMNS (validity words start as all ones: a NULL key clears its bit)
+__device__ __forceinline__ void emit_state_key(const u64 st, const KeySpec& K, const AggSoA& soa, const uint32_t g) {
   int shift = 0;
   for (int k = 0; k < K.n_keys; ++k) {
     const int b = K.sk_bits[k];
@@ -148,6 +146,11 @@ __device__ __forceinline__ void emit_state_group(const u64* slot, const KeySpec&
     soa.key_col[k][g] = make_ulonglong2(lo, (u64)((i64)lo >> 63));
     if (isn) atomicAnd((unsigned long long*)(soa.key_valid[k] + (g >> 6)), ~(1ull << (g & 63)));
   }
+}
+#ifndef GPUQ_JIT
+// a finished slot of such a table written as row g of the result columns
+__device__ __forceinline__ void emit_state_group(const u64* slot, const KeySpec& K, const AggSpec& A, const AggSoA& soa, const uint32_t g) {
+  emit_state_key(slot[0] >> 2, K, soa, g);
   for (int a = 0; a < A.n_accs; ++a) {
     const u64 lo = slot[1 + 2 * a];
     soa.acc_col[a][g] = make_ulonglong2(lo, acc_result_hi(A.acc_kind[a], lo, slot[2 + 2 * a]));
@@ -320,6 +323,22 @@ struct WaveQueue {
 
 // ------------------------------------------------------------------ hash aggregate
 
+// Inclusive segmented scan of one accumulator over the lanes of a wave: `f` marks the lanes that start a segment (lane 0 counts as one);
+// afterwards every lane holds its segment's partial up to and including itself, and whether any of those rows contributed.  All 64
+// lanes execute it.
+__device__ __forceinline__ void acc_wave_segscan(const int kind, const int lane, bool f, u64& vlo, u64& vhi, bool& any) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const u64 ulo = __shfl_up(vlo, off), uhi = __shfl_up(vhi, off);
+    const bool uf = __shfl_up((int)f, off) != 0, uany = __shfl_up((int)any, off) != 0;
+    if (lane >= off && !f) {
+      acc_combine(kind, vlo, vhi, ulo, uhi);
+      any = any || uany;
+      f = uf;
+    }
+  }
+}
+
 template <int MAXC>
 __device__ __forceinline__ void k_agg_hash_body(const DevProgram P, const i64 n_arg, const KeySpec K, const AggSpec A, const HashTable T) {
   const i64 n = rows_of(P, n_arg);      // deferred execution: the row count is a device word, n_arg its host-side bound
@@ -372,19 +391,7 @@ __device__ __forceinline__ void k_agg_hash_body(const DevProgram P, const i64 n_
       const bool wide = any && acc_wide_minmax(kind, vlo, vhi);
       if (__ballot(wide)) { if (wide) atomicOr(P.flags, FLAG_WIDE_MINMAX); continue; }
       if (!any) { vlo = acc_identity(kind, 0); vhi = acc_identity(kind, 1); }      // rows that do not contribute hold the identity
-      if (combine) {
-        bool f = head;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          const u64 ulo = __shfl_up(vlo, off), uhi = __shfl_up(vhi, off);
-          const bool uf = __shfl_up((int)f, off) != 0, uany = __shfl_up((int)any, off) != 0;
-          if (lane >= off && !f) {
-            acc_combine(kind, vlo, vhi, ulo, uhi);
-            any = any || uany;
-            f = uf;
-          }
-        }
-      }
+      if (combine) acc_wave_segscan(kind, lane, head, vlo, vhi, any);
       // (FMIN / FMAX are never combined: every row is its own run)
       if (upd && any) acc_fold<__HIP_MEMORY_SCOPE_AGENT>(cells + 2 * a, kind, vlo, vhi);
     }
@@ -433,6 +440,160 @@ __global__ void __launch_bounds__(HBLOCK) k_agg_hash_extract(const KeySpec K, co
       base += (uint32_t)__popcll(m);
     }
   }
+}
+#endif
+
+// ------------------------------------------------------------------ aggregate over key-clustered input ("runs")
+// Input whose packed state-word key arrives in runs of equal values with strictly increasing heads (a unique-key probe's pair list over
+// a fact table clustered on the key, a scan of a key-ordered file) needs no table: every group is one run, the result is one row per
+// run in input order.  Three passes, no workgroup waits for or reads what another one of the same launch writes:
+//   k_agg_runs_count   per wave-segment (RunsGeom): the number of heads, and the order test inside the segment (FLAG_AGG_RUNS)
+//   (launch_scan_block_counts: the segments' first output rows and the group count)
+//   k_agg_runs_order   the order test across segments
+//   k_agg_runs_write   one result row per run: a run that lies inside one word is stored plainly, the pieces of a run that crosses a
+//                      word boundary fold into cells the host has set to the accumulators' identities
+// The head rule is local (a row continues the run of the ACTIVE row directly below it with an equal key), so both kernels find the
+// same heads whatever the order turns out to be; a wrong guess about order costs nothing but the flag.
+// One word of a segment's walk.  In: the row's activity and packed key, and the walk's state -- `below63`: the last row of the word
+// before is active, `last_p1`: key + 1 of the nearest active row before this word inside the walk (0: none).  Out: the lane's view
+// (head, prev_p1) and the state moved on.  Executed by all 64 lanes.
+struct RunsLane { bool head; u64 prev_p1; u64 active_mask; };
+__device__ __forceinline__ RunsLane runs_word(const bool active, const u64 key, bool& below63, u64& last_p1) {
+  const int lane = hlane();
+  RunsLane r;
+  r.active_mask = __ballot(active);
+  const u64 under = lane ? runs_lanes_le(r.active_mask, lane - 1) : 0ull;      // the active lanes below this one
+  const u64 near_key = __shfl(key, under ? 63 - __builtin_clzll(under) : 0);
+  r.prev_p1 = under ? near_key + 1 : last_p1;
+  const bool below = lane ? ((r.active_mask >> (lane - 1)) & 1ull) != 0 : below63;
+  r.head = runs_head(active, below, r.prev_p1, key);
+  const u64 top_key = __shfl(key, r.active_mask ? 63 - __builtin_clzll(r.active_mask) : 0);
+  if (r.active_mask) last_p1 = top_key + 1;
+  below63 = (r.active_mask >> 63) != 0;
+  return r;
+}
+// A segment's walk: the word before the segment is evaluated for its last row alone (what lane 0 of the first word continues, or
+// not), then body(key, active, lane view, regs...) runs for the segment's own words.  Returns key + 1 of the last active row the
+// walk saw (0: none) -- the segment's own, or the row's before it when the segment has none: a row before the next segment either way.
+template <int MAXC, class Body>
+__device__ __forceinline__ u64 runs_walk(const DevProgram& P, const i64 n, const KeySpec& K, const i64 ws, const i64 wps, Body body) {
+  bool below63 = false; u64 last_p1 = 0;
+  for_rows_in_flight<MAXC>(P, n, ws > 0 ? ws - 1 : 0, 1, [&](const i64 w, const i64, const bool active, GPUQ_REGS_PARAM) {
+    const u64 key = active ? pack_state_key(K, GPUQ_REGS) : 0;
+    if (w < ws) {
+      const int a63 = __shfl((int)active, 63); const u64 k63 = __shfl(key, 63);
+      below63 = a63 != 0; last_p1 = a63 ? k63 + 1 : 0;
+      return;
+    }
+    const RunsLane r = runs_word(active, key, below63, last_p1);
+    body(key, active, r, GPUQ_REGS);
+  }, ws + wps);
+  return last_p1;
+}
+
+template <int MAXC>
+__device__ __forceinline__ void k_agg_runs_count_body(const DevProgram P, const i64 n_arg, const KeySpec K, const RunsGeom G) {
+  const i64 n = rows_of(P, n_arg);      // deferred execution: the row count is a device word, n_arg its host-side bound
+  const i64 s = (i64)blockIdx.x * HWAVES + hwave();
+  if (s >= G.nsegs) return;
+  uint32_t heads = 0; u64 first_p1 = 0; bool bad = false;
+  const u64 last_p1 = runs_walk<MAXC>(P, n, K, s * G.wps, G.wps, [&](const u64 key, const bool, const RunsLane& r, GPUQ_REGS_CPARAM) {
+    heads += (uint32_t)__popcll(__ballot(r.head));
+    bad = bad || runs_out_of_order(r.head, r.prev_p1, key);
+    // the one head of a segment with no active row before it inside the walk: k_agg_runs_order tests it against the segments before
+    const u64 open = __ballot(r.head && r.prev_p1 == 0);
+    const u64 open_key = __shfl(key, open ? __builtin_ctzll(open) : 0);
+    if (open) first_p1 = open_key + 1;
+  });
+  if (__ballot(bad) && hlane() == 0) atomicOr(P.flags, FLAG_AGG_RUNS);
+  if (hlane() == 0) { G.counts[s] = heads; G.seg_last[s] = last_p1; G.seg_first[s] = first_p1; }
+}
+#ifndef GPUQ_JIT
+template <int MAXC>
+__global__ void __launch_bounds__(HBLOCK) k_agg_runs_count(const DevProgram P, const i64 n, const KeySpec K, const RunsGeom G) { k_agg_runs_count_body<MAXC>(P, n, K, G); }
+#elif GPUQ_JIT_KERNEL == GPUQ_SINK_AGG_RUNS_COUNT
+extern "C" __global__ void __launch_bounds__(HBLOCK) gpuq_jit_entry(const DevProgram P, const i64 n, const KeySpec K, const RunsGeom G) { k_agg_runs_count_body<0>(P, n, K, G); }
+#endif
+
+#ifndef GPUQ_JIT
+// Heads must exceed every key of the segments before them.  Inside a segment the count kernel has tested that; left is each segment's
+// open head (seg_first) against the last keys of all segments before it (seg_last: a running maximum, which is the nearest one while
+// nothing is out of order).  One block; every wave owns a contiguous sixteenth of the segments and walks it 64 at a time.
+__global__ void __launch_bounds__(1024) k_agg_runs_order(const RunsGeom G, uint32_t* __restrict__ flags) {
+  __shared__ u64 wmax[16];
+  const int t = threadIdx.x, w = t >> 6, l = t & 63, n = G.nsegs;
+  const int per = ((n + 15) / 16 + 63) & ~63;
+  const int a = w * per, b = a + per < n ? a + per : n;
+  u64 m = 0;
+  for (int i = a + l; i < b; i += 64) { const u64 v = G.seg_last[i]; m = v > m ? v : m; }
+  for (int off = 32; off > 0; off >>= 1) { const u64 o = __shfl_xor(m, off); m = o > m ? o : m; }
+  if (l == 0) wmax[w] = m;
+  __syncthreads();
+  if (t == 0) { u64 run = 0; for (int k = 0; k < 16; ++k) { const u64 v = wmax[k]; wmax[k] = run; run = v > run ? v : run; } }
+  __syncthreads();
+  u64 carry = wmax[w]; bool bad = false;
+  for (int i0 = a; i0 < b; i0 += 64) {
+    const int i = i0 + l;
+    u64 x = i < b ? G.seg_last[i] : 0;
+    for (int off = 1; off < 64; off <<= 1) { const u64 y = __shfl_up(x, off); if (l >= off && y > x) x = y; }
+    u64 before = __shfl_up(x, 1); if (l == 0) before = 0;
+    if (carry > before) before = carry;
+    const u64 f = i < b ? G.seg_first[i] : 0;
+    bad = bad || (f != 0 && f <= before);
+    const u64 top = __shfl(x, 63); if (top > carry) carry = top;
+  }
+  if (bad) atomicOr(flags, FLAG_AGG_RUNS);
+}
+// the accumulator cells of one result column set to (lo, hi): an identity that is not all zero bits (BIT_AND)
+__global__ void __launch_bounds__(HBLOCK) k_fill_cells(ulonglong2* __restrict__ cells, const i64 n, const u64 lo, const u64 hi) {
+  for (i64 i = (i64)blockIdx.x * HBLOCK + threadIdx.x; i < n; i += (i64)gridDim.x * HBLOCK) cells[i] = make_ulonglong2(lo, hi);
+}
+#endif
+
+template <int MAXC>
+__device__ __forceinline__ void k_agg_runs_write_body(const DevProgram P, const i64 n_arg, const KeySpec K, const AggSpec A, const RunsGeom G, const AggSoA soa, const uint32_t cap) {
+  if (__hip_atomic_load(P.flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & FLAG_AGG_RUNS) return;      // (raised by the launches before this one: the result is void)
+  const i64 n = rows_of(P, n_arg);      // deferred execution: the row count is a device word, n_arg its host-side bound
+  const i64 s = (i64)blockIdx.x * HWAVES + hwave();
+  if (s >= G.nsegs) return;
+  const int lane = hlane();
+  const uint32_t base = G.counts[s];      // (scanned: the heads of the segments before this one)
+  uint32_t heads = 0;
+  runs_walk<MAXC>(P, n, K, s * G.wps, G.wps, [&](const u64 key, const bool active, const RunsLane& r, GPUQ_REGS_CPARAM) {
+    if (r.active_mask == 0) return;
+    const u64 head_mask = __ballot(r.head);
+    // a lane starts a piece when it does not continue the lane below: heads, inactive rows, and lane 0 (whose run may come from the word before)
+    const bool start = r.head | !active | (lane == 0);
+    const u64 start_mask = __ballot(start);
+    const bool tail = active && (lane == 63 || ((start_mask >> (lane + 1)) & 1ull));
+    const uint32_t g = runs_out_row(base, heads, head_mask, lane);
+    const bool fits = active && g < cap;
+    if (r.head && g >= cap) atomicOr(P.flags, FLAG_GROUP_OVERFLOW);
+    if (r.head && fits) emit_state_key(key, K, soa, g);
+    const bool interior = runs_piece_interior(head_mask, start_mask, lane);
+    for (int a = 0; a < A.n_accs; ++a) {
+      const int kind = A.acc_kind[a];
+      u64 vlo, vhi;
+      bool any = acc_operand(A, a, GPUQ_REGS, vlo, vhi) && active;
+      if (!any) { vlo = acc_identity(kind, 0); vhi = acc_identity(kind, 1); }      // rows that do not contribute hold the identity
+      acc_wave_segscan(kind, lane, start, vlo, vhi, any);
+      if (tail && fits) {
+        u64* cell = (u64*)(soa.acc_col[a] + g);
+        if (interior) { cell[0] = vlo; cell[1] = vhi; }      // the whole run: nobody else writes this row
+        else if (any) acc_fold<__HIP_MEMORY_SCOPE_AGENT>(cell, kind, vlo, vhi);
+      }
+    }
+    heads += (uint32_t)__popcll(head_mask);
+  });
+}
+#ifndef GPUQ_JIT
+template <int MAXC>
+__global__ void __launch_bounds__(HBLOCK) k_agg_runs_write(const DevProgram P, const i64 n, const KeySpec K, const AggSpec A, const RunsGeom G, const AggSoA soa, const uint32_t cap) {
+  k_agg_runs_write_body<MAXC>(P, n, K, A, G, soa, cap);
+}
+#elif GPUQ_JIT_KERNEL == GPUQ_SINK_AGG_RUNS_WRITE
+extern "C" __global__ void __launch_bounds__(HBLOCK) gpuq_jit_entry(const DevProgram P, const i64 n, const KeySpec K, const AggSpec A, const RunsGeom G, const AggSoA soa, const uint32_t cap) {
+  k_agg_runs_write_body<0>(P, n, K, A, G, soa, cap);
 }
 #endif
 
@@ -1483,6 +1644,32 @@ void launch_agg_hash_extract(hipStream_t s, const KeySpec& K, const AggSpec& A, 
   const u64 cap = (u64)num_cus() * 16;
   const int grid = (int)(need < cap ? (need ? need : 1) : cap);
   hipLaunchKernelGGL(k_agg_hash_extract, dim3(grid), dim3(HBLOCK), 0, s, K, A, T, out, flags, soa ? *soa : none);
+}
+// one wave per segment; enough segments to fill the chip eight blocks deep, at least two words each (the word before a segment is
+// evaluated once more for its last row: 1 / wps of extra loads)
+RunsGeom agg_runs_geometry(i64 n) {
+  RunsGeom G{};
+  const i64 nwords = (n + 63) >> 6, max_segs = (i64)num_cus() * 8 * HWAVES;
+  G.wps = std::max<i64>((nwords + max_segs - 1) / max_segs, 2);
+  G.nsegs = (int32_t)((nwords + G.wps - 1) / G.wps);
+  return G;
+}
+void launch_agg_runs_count(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const RunsGeom& G) {
+  if (G.nsegs <= 0) return;
+  launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_agg_runs_count), dim3((G.nsegs + HWAVES - 1) / HWAVES), dim3(HBLOCK), 0, s, P, n, K, G);
+}
+void launch_agg_runs_order(hipStream_t s, const RunsGeom& G, uint32_t* flags) {
+  if (G.nsegs <= 0) return;
+  hipLaunchKernelGGL(k_agg_runs_order, dim3(1), dim3(1024), 0, s, G, flags);
+}
+void launch_agg_runs_write(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const AggSpec& A, const RunsGeom& G, const AggSoA& soa, uint32_t cap) {
+  if (G.nsegs <= 0) return;
+  launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_agg_runs_write), dim3((G.nsegs + HWAVES - 1) / HWAVES), dim3(HBLOCK), 0, s, P, n, K, A, G, soa, cap);
+}
+void launch_fill_cells(hipStream_t s, ulonglong2* cells, i64 n, u64 lo, u64 hi) {
+  if (n <= 0) return;
+  const i64 need = (n + HBLOCK - 1) / HBLOCK, cap = (i64)num_cus() * 16;
+  hipLaunchKernelGGL(k_fill_cells, dim3((unsigned)(need < cap ? need : cap)), dim3(HBLOCK), 0, s, cells, n, lo, hi);
 }
 void launch_agg_bucket_id(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, u64 bucket_mask, u64* bid, uint32_t* ids) {
   if (n <= 0) return;

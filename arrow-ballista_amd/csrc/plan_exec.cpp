@@ -2720,7 +2720,9 @@ int gpuq_plan_profile_all(gpuq_plan* p, char* json_out, size_t cap) {
     Json num; num.kind = Json::NUM; { char b[64]; std::snprintf(b, sizeof(b), "%.6f", (double)ms); num.s = b; }
     float tot = 0; (void)gpuq_op_profile_total(kv.second, &tot);
     Json tnum; tnum.kind = Json::NUM; { char b[64]; std::snprintf(b, sizeof(b), "%.6f", (double)tot); tnum.s = b; }
-    arr.a.push_back(jobj({{"op", jstr(kind)}, {"kernel_ms", num}, {"op_ms", tnum}, {"launches", jnum(n)}, {"desc", jstr(kv.first)}}));
+    std::vector<std::pair<std::string, Json>> e = {{"op", jstr(kind)}, {"kernel_ms", num}, {"op_ms", tnum}, {"launches", jnum(n)}, {"desc", jstr(kv.first)}};
+    if (kind == "aggregate") e.push_back({"agg_path", jstr(gpuq_op_agg_path(kv.second))});      // the way its last run took
+    arr.a.push_back(jobj(e));
   }
   const std::string s = arr.dump();
   if (s.size() + 1 > cap) return GPUQ_ERR_CAPACITY;

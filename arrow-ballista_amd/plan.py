@@ -615,6 +615,7 @@ class AggregateExec(ExecutionPlan):
     group_expr: [(expr, name)];  aggr_expr: [{"fn": f, "expr": e[, "expr2": e2], "name": n}]; the function names (those of
     datafusion.proto:631-669 and their aliases) and each function's state columns are listed with the operator descriptors in
     include/gpuq.h.  Modes: Partial (emits state columns), Final / FinalPartitioned (merge states), Single.
+    strategy: "auto" (by cardinality and input order), or one kernel family: "tiny", "lds", "hash", "radix", "runs" (include/gpuq.h).
     MEDIAN (mode Single; `"filter"` allowed) is not one of the operator's functions: the native executor lowers a node that holds one
     (include/gpuq.h, gpuq_segment_median); the Python restatement of the executor (GPUQ_PLAN_LAYER=mirror) does not have it."""
 

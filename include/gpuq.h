@@ -244,7 +244,7 @@ const char* gpuq_scan_last_error(void);
      "filter"      FilterExec        {input, predicate}
      "project"     ProjectionExec    {input, exprs:[{expr,name}]}
      "aggregate"   AggregateExec     {input, mode:Partial|Final|FinalPartitioned|Single, group_expr:[{expr,name}],
-                                      aggr_expr:[{fn, expr, expr2?, name, filter?}], predicate?, strategy?:auto|tiny|hash|lds|radix, expected_groups?}
+                                      aggr_expr:[{fn, expr, expr2?, name, filter?}], predicate?, strategy?:auto|tiny|hash|lds|radix|runs, expected_groups?}
                    fn (any letter case; one row of AGG_FNS in csrc/agg_compile.cpp each) and the state columns "<name>[..]" its Partial emits
                    and its Final reads, by position, after the group columns:
                      COUNT (expr optional: COUNT(*))                   [count]
@@ -306,7 +306,10 @@ int gpuq_project_run(gpuq_op* op, void* stream, const gpuq_input* in, gpuq_colum
 
 /* AggregateExec.  Strategy "auto" picks the kernel by cardinality: <= 64 groups an LDS dictionary with per-lane accumulators;
    a few hundred to a few thousand, block-local LDS tables flushed to a global one ("lds"); >= 4096 known groups on >= 2^20
-   rows, radix partitioning + one LDS table per bucket ("radix"); otherwise / unknown a global hash table ("hash").  The
+   rows, radix partitioning + one LDS table per bucket ("radix"); otherwise / unknown a global hash table ("hash").  Where the
+   table would be next, input of >= 2^20 rows whose key packs into one 62-bit word and whose accumulators are integer sums, counts
+   or bitwise is first tried as runs of equal keys with increasing heads ("runs": one result row per run, in input order, no
+   table); input that is not so clustered falls to the table in the same call and is not tried again.  The
    group count is taken from expected_groups, else from this operator's previous run -- keep operators alive across the
    partitions of a stage.  outs: caller-allocated columns of capacity `cap` rows in output-schema order.
    Synchronous (the group count decides the strategy and the result length); *n_groups_out (host)
@@ -589,6 +592,7 @@ const char* gpuq_plan_last_error(void);
    dominant kernel and report the operator with the most accumulated kernel time (its descriptor text in op_desc_out). */
 int gpuq_plan_profile(gpuq_plan* plan, int enable, float* kernel_ms_out, int* launches_out, char* op_desc_out, size_t cap);
 /* Every operator the plan has compiled, as a JSON array [{"op": kind, "kernel_ms": accumulated ms, "launches": n, "desc": descriptor}]
+   (an aggregate also "agg_path": gpuq_op_agg_path)
    (reads and resets the accumulators; profiling stays as it was set by gpuq_plan_profile).  GPUQ_ERR_CAPACITY when cap is too small. */
 int gpuq_plan_profile_all(gpuq_plan* plan, char* json_out, size_t cap);
 int64_t gpuq_result_num_rows(const gpuq_result* r);
@@ -717,6 +721,9 @@ int gpuq_op_profile(gpuq_op* op, int enable, float* kernel_ms_out, int* launches
 /* ... and of EVERYTHING the op's run calls queued in the interval the last gpuq_op_profile call closed (the dominant kernel plus table
    initialisation, scans, compactions, the result projection): the operator's share of a step. */
 int gpuq_op_profile_total(gpuq_op* op, float* total_ms_out);
+/* The way an aggregate operator's last run took: "tiny", "table", "radix" or "runs"; "" before its first run and for other operators.
+   gpuq_plan_profile_all reports it as "agg_path" next to the descriptor. */
+const char* gpuq_op_agg_path(gpuq_op* op);
 
 #ifdef __cplusplus
 }
