@@ -79,6 +79,7 @@ def lib():
         "gpuq_utf8_compare": (i32, [vp, vp, C.POINTER(gpuq_column), vp, C.POINTER(gpuq_column), vp, C.c_char_p, i64, i64, i32, vp, vp]),
         "gpuq_segment_heads": (i32, [vp, vp, C.POINTER(gpuq_column), i32, i64, vp, vp, i64, vp]),
         "gpuq_segment_median": (i32, [vp, vp, C.POINTER(gpuq_column), vp, i64, vp, vp]),
+        "gpuq_segment_approx_distinct": (i32, [vp, vp, C.POINTER(gpuq_column), vp, i64, i64, i64, vp]),
         "gpuq_ingest_create": (i32, [vp, vp, i64, i64, i32, C.POINTER(vp)]),
         "gpuq_ingest_push": (i32, [vp, vp]),
         "gpuq_ingest_rows_landed": (i32, [vp, C.POINTER(i64)]),

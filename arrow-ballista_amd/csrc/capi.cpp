@@ -1837,6 +1837,40 @@ int gpuq_segment_median(gpuq_ctx* ctx, void* stream, const gpuq_column* value_co
     HIPCHECK(hipGetLastError());
   });
 }
+// ---------------------------------------------------------------- one HyperLogLog estimate per segment (APPROX_DISTINCT)
+int gpuq_segment_approx_distinct(gpuq_ctx* ctx, void* stream, const gpuq_column* value_col, const int32_t* starts, int64_t n_groups, int64_t n_rows, int64_t tile_rows,
+                                 uint64_t* out) {
+  return guarded(ctx, [&]() {
+    check_ctx(ctx);
+    if (!value_col || n_groups < 0 || n_rows < 0 || (n_groups > 0 && (!starts || !out))) throw std::runtime_error("gpuq_segment_approx_distinct: bad arguments");
+    if (tile_rows != 0 && (tile_rows < 256 || tile_rows % 256 != 0)) throw std::runtime_error("gpuq_segment_approx_distinct: tile_rows must be 0 or a multiple of 256");
+    if (n_rows >= (1ll << 31)) throw Unsupported("gpuq_segment_approx_distinct (APPROX_DISTINCT): >= 2^31 rows in one call (segment starts are 32-bit)");
+    if (n_groups >= (1ll << 31)) throw Unsupported("gpuq_segment_approx_distinct (APPROX_DISTINCT): >= 2^31 segments in one call");
+    DType dt; dt.id = value_col->type; dt.p = value_col->precision; dt.s = value_col->scale;
+    HllCol col{value_col->data, value_col->validity, 0, HLL_SINT};
+    switch (dt.id) {
+      case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_DATE32: case T_DATE64: case T_TIMESTAMP: case T_DECIMAL128: col.kind = HLL_SINT; break;
+      case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: col.kind = HLL_UINT; break;
+      case T_FLOAT32: col.kind = HLL_F32; break;
+      case T_FLOAT64: col.kind = HLL_F64; break;
+      case T_UTF8:
+        if (value_col->repr != GPUQ_REPR_PACKED15) throw Unsupported("gpuq_segment_approx_distinct (APPROX_DISTINCT): a Utf8 column must be in the fixed-width PACKED15 form");
+        col.kind = HLL_UINT; break;
+      default: throw Unsupported("APPROX_DISTINCT over " + dt.to_string() + " is not supported (integers, dates, timestamps, Decimal128, Float32, Float64, Utf8 up to 15 bytes)");
+    }
+    col.width = dt.id == T_UTF8 ? 16 : type_width(dt);
+    if (n_groups == 0) return;
+    if (n_rows > 0 && (!value_col->data || value_col->length < n_rows)) throw std::runtime_error("gpuq_segment_approx_distinct: the column is shorter than n_rows");
+    hipStream_t s = use_stream(stream);
+    HIPCHECK(hipMemsetAsync(out, 0, (size_t)n_groups * 8, s));      // an empty segment is met by no tile
+    if (n_rows == 0) return;
+    if (tile_rows == 0) tile_rows = hll_tile_rows(n_rows);
+    DevBuf partial;      // released to the pool behind the launches on this stream
+    partial.ensure(hll_partial_bytes(n_rows, tile_rows));
+    launch_hll_approx_distinct(s, col, starts, n_groups, n_rows, tile_rows, partial.p, (u64*)out);
+    HIPCHECK(hipGetLastError());
+  });
+}
 
 int gpuq_like_utf8(gpuq_ctx* ctx, void* stream, const gpuq_column* col, const uint32_t* idx, int64_t n, const char* pattern, int negated, int case_insensitive,
                    uint8_t* bits_out, uint8_t* validity_out) {

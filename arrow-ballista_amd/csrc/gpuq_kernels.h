@@ -526,6 +526,13 @@ enum SegKind : int32_t { SEG_SINT = 0, SEG_UINT = 1, SEG_F32 = 2, SEG_F64 = 3 };
 // scan: n + 1 words of scratch (the flags, then their exclusive scan); seg_id (n, or nullptr), starts (starts_cap + 1), n_groups as gpuq_segment_heads
 void launch_segment_heads(hipStream_t s, const SegKeys& K, i64 n, int32_t* scan, void* scan_ws, size_t scan_ws_bytes, int32_t* seg_id, int32_t* starts, i64 starts_cap, u64* n_groups);
 void launch_segment_median(hipStream_t s, const void* data, const uint8_t* valid, int width, int kind, const int32_t* starts, i64 n_groups, void* out, u64* out_valid);
+// ----- one HyperLogLog estimate per segment of a column (kernels_hll.hip; hll_estimate.h has the hash and the estimator)
+enum HllKind : int32_t { HLL_SINT = 0, HLL_UINT = 1, HLL_F32 = 2, HLL_F64 = 3 };      // how a value of 8 bytes or fewer is widened to 64 bits (width 16: both words as they lie)
+struct HllCol { const void* data; const uint8_t* valid; int32_t width; int32_t kind; };
+i64 hll_tile_rows(i64 n_rows);                              // the library's choice of tile_rows: a multiple of 256
+size_t hll_partial_bytes(i64 n_rows, i64 tile_rows);        // two 16 KB sketches per tile
+// out[g] for every non-empty segment g (the caller zeroes `out`: an empty segment is met by no tile); rows [0, n_rows) of `col` are read
+void launch_hll_approx_distinct(hipStream_t s, const HllCol& col, const int32_t* starts, i64 n_groups, i64 n_rows, i64 tile_rows, void* partial, u64* out);
 
 // ----- scan-side decode (kernels_scanfmt.hip): delimited text and Parquet pages
 enum CsvKind : int32_t { CSV_SKIP = 0, CSV_I32 = 1, CSV_I64 = 2, CSV_DATE32 = 3, CSV_DEC128 = 4, CSV_F64 = 5, CSV_BOOL = 6, CSV_UTF8 = 7 };

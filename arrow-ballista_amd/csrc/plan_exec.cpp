@@ -883,6 +883,7 @@ Json type_json_from_string(const std::string& t) {      // DType::to_string(): "
     if (t.find(',') != std::string::npos && t.find(", ") == std::string::npos) std::sscanf(t.c_str(), "Decimal128(%lld,%lld)", &p, &sc);
     return jobj({{"Decimal128", jarr({jnum(p), jnum(sc)})}});
   }
+  if (t.rfind("Timestamp(", 0) == 0 && t.back() == ')') return jobj({{"Timestamp", jarr({jstr(t.substr(10, t.size() - 11)), Json()})}});      // "Timestamp(Nanosecond)"
   return jstr(t);
 }
 PSchema compiled_outputs(const Json& desc) {
@@ -1001,12 +1002,23 @@ Json bound_aggr_exprs(const Json& aggr_expr, const ColMap* cm, const std::vector
   }
   return ae;
 }
-// ---- MEDIAN (include/gpuq.h, gpuq_segment_median, has the rules).  Its state is the group's values, so it is no accumulator of the
-// aggregate operator: a node that holds one is lowered here, in the plan, as COUNT(DISTINCT) is (build_node) -- see AggregateExec::run_median.
-bool is_median(const Json& a) {
+// ---- The segment aggregates: MEDIAN and APPROX_DISTINCT (include/gpuq.h, gpuq_segment_median and gpuq_segment_approx_distinct, have the
+// rules).  Their state is the group's values / a 16 KB sketch, so they are no accumulators of the aggregate operator: a node that holds
+// one is lowered here, in the plan, as COUNT(DISTINCT) is (build_node) -- see AggregateExec::run_segment_aggs.
+bool is_agg_fn(const Json& a, const char* name) {
   std::string f = a.get_str("fn", "");
   for (char& c : f) c = (char)std::toupper((unsigned char)c);
-  return f == "MEDIAN";
+  return f == name;
+}
+bool is_median(const Json& a) { return is_agg_fn(a, "MEDIAN"); }
+bool is_approx_distinct(const Json& a) { return is_agg_fn(a, "APPROX_DISTINCT"); }
+bool is_segment_agg(const Json& a) { return is_median(a) || is_approx_distinct(a); }
+void approx_distinct_check_arg(const DType& t) {
+  switch (t.id) {
+    case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: case T_DATE32: case T_DATE64: case T_TIMESTAMP:
+    case T_FLOAT32: case T_FLOAT64: case T_DECIMAL128: case T_UTF8: return;
+    default: throw Unsupported("APPROX_DISTINCT over " + t.to_string() + " is not supported (integers, dates, timestamps, Decimal128, Float32, Float64, Utf8 up to 15 bytes)");
+  }
 }
 void median_check_arg(const DType& t) {
   switch (t.id) {
@@ -1014,13 +1026,14 @@ void median_check_arg(const DType& t) {
     default: throw Unsupported("MEDIAN over " + t.to_string() + " is not supported (Int8..Int64, UInt8..UInt64, Float32, Float64, Decimal128)");
   }
 }
-void median_check_key(const DType& t, const std::string& name) {
-  if (t.is_float()) throw Unsupported("MEDIAN: the " + t.to_string() + " group key '" + name + "' is refused on a node with a MEDIAN (bytewise segment heads and the hash "
-                                      "aggregate need not agree on -0.0 / NaN)");
+// (who: the function the node is lowered for -- "MEDIAN" when it holds one, else "APPROX_DISTINCT")
+void median_check_key(const DType& t, const std::string& name, const std::string& who = "MEDIAN") {
+  if (t.is_float()) throw Unsupported(who + ": the " + t.to_string() + " group key '" + name + "' is refused on a node with a" + (who[0] == 'A' ? "n " : " ") + who +
+                                      " (bytewise segment heads and the hash aggregate need not agree on -0.0 / NaN)");
 }
-// the argument of MEDIAN `a` over the node's input: with FILTER (WHERE p), a row where p is not true counts as a NULL argument
+// the argument of the segment aggregate `a` over the node's input: with FILTER (WHERE p), a row where p is not true counts as a NULL argument
 Json median_arg(const Json& a, const ColMap* cm) {
-  if (!a.has("expr")) throw std::runtime_error("MEDIAN needs an argument (\"expr\")");
+  if (!a.has("expr")) throw std::runtime_error(std::string(is_median(a) ? "MEDIAN" : "APPROX_DISTINCT") + " needs an argument (\"expr\")");
   const Json e = inline_projection(a.at("expr"), cm);
   if (!a.has("filter")) return e;
   return jobj({{"case_", jobj({{"when_then_expr", jarr({jobj({{"when_expr", inline_projection(a.at("filter"), cm)}, {"then_expr", e}})})}})}});
@@ -1041,18 +1054,26 @@ struct AggregateExec : PNode {
   PNodeP input; std::string mode, strategy = "auto"; Json group_expr, aggr_expr; int64_t expected_groups = 0, output_capacity = 0;
   std::vector<PNode*> children() override { return {input.get()}; }
   bool has_median() const { for (auto& a : aggr_expr.a) if (is_median(a)) return true; return false; }
-  Json plain_aggr_exprs() const { Json p = jarr(); for (auto& a : aggr_expr.a) if (!is_median(a)) p.a.push_back(a); return p; }
-  // A node with MEDIANs is typed without asking the aggregate operator to compile MEDIAN: keys and arguments by the projection that
-  // run_median makes of them, the other aggregates by the operator over the node without its MEDIANs.
-  PSchema median_schema() {
+  bool has_segment_agg() const { for (auto& a : aggr_expr.a) if (is_segment_agg(a)) return true; return false; }
+  std::string segment_fn() const { return has_median() ? "MEDIAN" : "APPROX_DISTINCT"; }      // the function the node's refusals name
+  Json plain_aggr_exprs() const { Json p = jarr(); for (auto& a : aggr_expr.a) if (!is_segment_agg(a)) p.a.push_back(a); return p; }
+  // A node with segment aggregates is typed without asking the aggregate operator to compile them: keys and arguments by the projection
+  // that run_segment_aggs makes of them, the other aggregates by the operator over the node without its segment aggregates.
+  PSchema segment_schema() {
     const PSchema in = input->schema(); const auto nm = schema_names(in);
     const size_t nk = group_expr.a.size();
     std::vector<Json> ex; std::vector<std::string> names;
     for (auto& g : group_expr.a) { ex.push_back(g.at("expr")); names.push_back(g.at("name").str()); }
-    for (auto& a : aggr_expr.a) if (is_median(a)) { ex.push_back(median_arg(a, nullptr)); names.push_back(a.at("name").str()); }
-    const PSchema typed = compiled_outputs(project_desc(input_of(in), ex, names, &nm));
-    for (size_t k = 0; k < nk; ++k) median_check_key(dtype_from_json(typed[k].type), typed[k].name);
-    for (size_t k = nk; k < typed.size(); ++k) median_check_arg(dtype_from_json(typed[k].type));
+    for (auto& a : aggr_expr.a) if (is_segment_agg(a)) { ex.push_back(median_arg(a, nullptr)); names.push_back(a.at("name").str()); }
+    PSchema typed = compiled_outputs(project_desc(input_of(in), ex, names, &nm));
+    for (size_t k = 0; k < nk; ++k) median_check_key(dtype_from_json(typed[k].type), typed[k].name, segment_fn());
+    size_t si = nk;
+    for (auto& a : aggr_expr.a) {
+      if (!is_segment_agg(a)) continue;
+      if (is_median(a)) median_check_arg(dtype_from_json(typed[si].type));
+      else { approx_distinct_check_arg(dtype_from_json(typed[si].type)); typed[si].type = jstr("UInt64"); }
+      ++si;
+    }
     PSchema plain;
     const Json pa = plain_aggr_exprs();
     if (!pa.a.empty()) {
@@ -1064,19 +1085,23 @@ struct AggregateExec : PNode {
     PSchema out(typed.begin(), typed.begin() + (long)nk);
     size_t mi = nk, pi = nk;
     for (auto& a : aggr_expr.a) {
-      PField f = is_median(a) ? typed[mi++] : plain.at(pi++);
-      f.nullable = true;      // (the declared form: see schema())
+      PField f = is_segment_agg(a) ? typed[mi++] : plain.at(pi++);
+      f.nullable = !is_approx_distinct(a);      // (the declared form: see schema(); an APPROX_DISTINCT is a count, 0 over nothing)
       out.push_back(f);
     }
     return out;
   }
-  // The lowering of a node with MEDIANs (mode Single).  The input is projected to [keys, one column per distinct MEDIAN argument, the
-  // columns the other aggregates read] and sorted by (keys..., argument) -- once per distinct argument; keys lead and the rows are the
-  // same, so every sort has the same segments.  The segments are taken from the first sort (gpuq_segment_heads); the other aggregates
-  // run on the existing operator grouped by the segment id alone, so group identity is decided once and both halves are aligned by
-  // construction; one lane per segment picks the middles (gpuq_segment_median).  The node runs synchronously in every execution.
-  PTable run_median(Exec& x, PTable t, const Fused& f) {
+  // The lowering of a node with segment aggregates, MEDIAN and APPROX_DISTINCT (mode Single).  The input is projected to [keys, one
+  // column per distinct argument of a segment aggregate, the columns the other aggregates read] and sorted by (keys..., argument) --
+  // once per distinct MEDIAN argument; keys lead and the rows are the same, so every sort has the same segments.  A node without MEDIAN
+  // is sorted by its keys alone, and not at all when it has none: a sketch does not care for the order inside a segment.  The segments
+  // are taken from the first sort (gpuq_segment_heads); the other aggregates run on the existing operator grouped by the segment id
+  // alone, so group identity is decided once and both halves are aligned by construction; one lane per segment picks the middles
+  // (gpuq_segment_median), one pass over the first sort's argument column sketches it (gpuq_segment_approx_distinct).  The node runs
+  // synchronously in every execution.
+  PTable run_segment_aggs(Exec& x, PTable t, const Fused& f) {
     const ColMap* cm = f.has_map ? &f.map : nullptr;
+    const std::string who = segment_fn();
     settle(x, &t);      // what is pending is settled and t's count made exact; nothing below is offered a deferred run
     struct SyncOnly { Exec& x; bool was; explicit SyncOnly(Exec& x_) : x(x_), was(x_.deferred) { x.deferred = false; } ~SyncOnly() { x.deferred = was; } } sync_only(x);
     if (f.has_pred) t = filter_table(x, t, f.pred, this, 20);
@@ -1091,50 +1116,70 @@ struct AggregateExec : PNode {
       if (ci >= 0) {      // a string key leaves the projection as 16 packed bytes: that is what makes the keys fixed-width
         int32_t maxlen = 0;
         check(x, gpuq_utf8_max_len(x.ctx, x.stream, &t.cols[(size_t)ci].c, via_of(t, (size_t)ci), t.n, &maxlen));
-        if (maxlen > 15) throw Unsupported("MEDIAN: the group key '" + group_expr.a[k].at("name").str() + "' holds strings longer than 15 bytes (" + std::to_string(maxlen) + ")");
+        if (maxlen > 15) throw Unsupported(who + ": the group key '" + group_expr.a[k].at("name").str() + "' holds strings longer than 15 bytes (" + std::to_string(maxlen) + ")");
       }
       ex.push_back(e); nm.push_back(key_name(k));
     }
-    std::vector<std::string> arg_text; std::vector<int> arg_of(aggr_expr.a.size(), -1);
+    // (med / apx: a MEDIAN / an APPROX_DISTINCT reads the argument)
+    std::vector<std::string> arg_text; std::vector<int> arg_of(aggr_expr.a.size(), -1); std::vector<char> med, apx;
     for (size_t i = 0; i < aggr_expr.a.size(); ++i) {
-      if (!is_median(aggr_expr.a[i])) continue;
+      if (!is_segment_agg(aggr_expr.a[i])) continue;
       const Json e = median_arg(aggr_expr.a[i], cm);
       const std::string text = e.dump();
       size_t j = 0; while (j < arg_text.size() && arg_text[j] != text) ++j;
-      if (j == arg_text.size()) { arg_text.push_back(text); ex.push_back(e); nm.push_back(arg_name(j)); }
+      if (j == arg_text.size()) { arg_text.push_back(text); ex.push_back(e); nm.push_back(arg_name(j)); med.push_back(0); apx.push_back(0); }
       arg_of[i] = (int)j;
+      if (is_median(aggr_expr.a[i])) med[j] = 1;
+      else if (!apx[j]) {      // a string argument leaves the projection as 16 packed bytes, as a string key does
+        apx[j] = 1;
+        Names cols; collect_columns(e, cols);
+        for (auto& c : cols) {
+          const int ci = long_key_column(t, jcolname(c));
+          if (ci < 0) continue;
+          int32_t maxlen = 0;
+          check(x, gpuq_utf8_max_len(x.ctx, x.stream, &t.cols[(size_t)ci].c, via_of(t, (size_t)ci), t.n, &maxlen));
+          if (maxlen > 15) throw Unsupported("APPROX_DISTINCT: the argument '" + aggr_expr.a[i].at("name").str() + "' reads strings longer than 15 bytes (" + std::to_string(maxlen) +
+                                             ") in column '" + c + "'");
+        }
+      }
     }
     const size_t na = arg_text.size();
+    int first_med = -1;
+    for (size_t j = 0; j < na && first_med < 0; ++j) if (med[j]) first_med = (int)j;
     const Json plain = plain_aggr_exprs();
     Names plain_cols;
     for (auto& a : plain.a) for_each_agg_arg(a, [&](const char*, const Json& e) { collect_columns(inline_projection(e, cm), plain_cols); });
     for (auto& c : plain_cols) { ex.push_back(jcolname(c)); nm.push_back(c); }
     const PTable proj = project_wide(x, t, ex, nm, this, 21);
     const int64_t n = proj.n;
-    if (n >= (1ll << 31)) throw Unsupported("MEDIAN over >= 2^31 rows in one partition (segment ids are 32-bit)");
-    for (size_t k = 0; k < nk; ++k) median_check_key(dtype_of(proj.cols[k].c), group_expr.a[k].at("name").str());
-    for (size_t j = 0; j < na; ++j) median_check_arg(dtype_of(proj.cols[nk + j].c));
-    // ---- 2. one sort per distinct argument, materialised (keep: the columns read afterwards)
-    auto sorted_by = [&](size_t j, const Names& keep) {
-      if (n == 0) return proj;
+    if (n >= (1ll << 31)) throw Unsupported(who + " over >= 2^31 rows in one partition (segment ids are 32-bit)");
+    for (size_t k = 0; k < nk; ++k) median_check_key(dtype_of(proj.cols[k].c), group_expr.a[k].at("name").str(), who);
+    for (size_t j = 0; j < na; ++j) {
+      if (med[j]) median_check_arg(dtype_of(proj.cols[nk + j].c));
+      if (apx[j]) approx_distinct_check_arg(dtype_of(proj.cols[nk + j].c));
+    }
+    // ---- 2. one sort per distinct MEDIAN argument (j < 0: by the keys alone), materialised (keep: the columns read afterwards)
+    auto sorted_by = [&](int j, const Names& keep) {
+      if (n == 0 || (j < 0 && nk == 0)) return proj;
       Json se = jarr();
       for (size_t k = 0; k < nk; ++k) se.a.push_back(jobj({{"expr", jcolname(key_name(k))}, {"asc", jbool(true)}, {"nulls_first", jbool(false)}}));
-      se.a.push_back(jobj({{"expr", jcolname(arg_name(j))}, {"asc", jbool(true)}, {"nulls_first", jbool(false)}}));
+      if (j >= 0) se.a.push_back(jobj({{"expr", jcolname(arg_name((size_t)j))}, {"asc", jbool(true)}, {"nulls_first", jbool(false)}}));
       PTable v;
-      if (se.a.size() <= 4) v = sort_table(x, proj, se, -1, this, 200 + (int)j);
+      if (se.a.size() <= 4) v = sort_table(x, proj, se, -1, this, 200 + j);
       else {      // more keys than one sort takes: stable passes, least significant first -- four keys a pass, or one when four do not fit 128 bits
         PermOut po;
-        try { po = sort_perm_long(x, proj, se, this, 200 + (int)j); }
-        catch (const Unsupported& e) { if (!is_wide_sort_key(e)) throw; po = sort_perm_long(x, proj, se, this, 300 + (int)j, 1); }
+        try { po = sort_perm_long(x, proj, se, this, 200 + j); }
+        catch (const Unsupported& e) { if (!is_wide_sort_key(e)) throw; po = sort_perm_long(x, proj, se, this, 300 + j, 1); }
         v = select_view(x, proj, po.p, n, nullptr);
         for (auto& b : po.keep) v.keep.push_back(b);
       }
       prune_columns(v, keep);
       return materialize(x, v);
     };
-    Names keep0 = plain_cols; keep0.insert(arg_name(0));
+    Names keep0 = plain_cols;      // the first sort also carries what the sketches read: they take the rows of a segment in any order
+    for (size_t j = 0; j < na; ++j) if ((int)j == first_med || apx[j]) keep0.insert(arg_name(j));
     for (size_t k = 0; k < nk; ++k) keep0.insert(key_name(k));
-    const PTable sorted0 = sorted_by(0, keep0);
+    const PTable sorted0 = sorted_by(first_med, keep0);
     // ---- 3. segments
     int64_t G = 1;
     BufP starts = dev_alloc((size_t)(n + 2) * 4), seg_id;
@@ -1145,8 +1190,8 @@ struct AggregateExec : PNode {
       BufP cnt = dev_alloc(16);
       check(x, gpuq_segment_heads(x.ctx, x.stream, kc.data(), (int)nk, n, seg_id ? (int32_t*)seg_id->p : nullptr, (int32_t*)starts->p, n, (uint64_t*)cnt->p));
       G = (int64_t)read_u64(x, cnt->p);
-      if (G < 0 || G > n) throw std::runtime_error("MEDIAN: " + std::to_string(G) + " segments over " + std::to_string(n) + " rows");
-    } else {      // ungrouped: one segment, also over no rows (one row holding NULL)
+      if (G < 0 || G > n) throw std::runtime_error(who + ": " + std::to_string(G) + " segments over " + std::to_string(n) + " rows");
+    } else {      // ungrouped: one segment, also over no rows (one row holding NULL; an APPROX_DISTINCT holds 0)
       const int32_t whole[2] = {0, (int32_t)n};
       upload(x, starts, whole, sizeof(whole));
     }
@@ -1169,21 +1214,31 @@ struct AggregateExec : PNode {
       int64_t ng = 0;
       const int rc = gpuq_aggregate_run(op, x.stream, &ic.in, carr.data(), (int)carr.size(), std::max<int64_t>(G, 1), &ng);
       ++x.host_syncs;
-      if (rc == GPUQ_OK && ng != G) throw std::runtime_error("MEDIAN: the aggregate operator returned " + std::to_string(ng) + " groups for " + std::to_string(G) + " segments");
+      if (rc == GPUQ_OK && ng != G) throw std::runtime_error(who + ": the aggregate operator returned " + std::to_string(ng) + " groups for " + std::to_string(G) + " segments");
       check(x, rc);
       pres.n = G; for (auto& c : pres.cols) c.c.length = G;
       if (nk && G > 1) pres = materialize(x, sort_table(x, pres, jarr({jobj({{"expr", jcolname("__seg")}, {"asc", jbool(true)}, {"nulls_first", jbool(false)}})}), -1, this, 18));
     }
-    // ---- 5. the medians
+    // ---- 5. the segment aggregates, per function: the medians of every sort, the sketches over the first
     PTable r; r.n = G;
-    std::vector<PCol> med(na);
+    std::vector<PCol> medians(na), sketches(na);
     for (size_t j = 0; j < na; ++j) {
-      const PTable sj = j == 0 ? sorted0 : sorted_by(j, Names{arg_name(j)});
-      const PCol& ac = sj.cols[(size_t)find_column(sj, arg_name(j))];
-      BufP data = dev_alloc((size_t)std::max<int64_t>(G, 1) * width_of(ac.c) + 16), valid = dev_alloc(bitmap_bytes(G) + 8);
-      check(x, gpuq_segment_median(x.ctx, x.stream, &ac.c, (const int32_t*)starts->p, G, data->p, (uint8_t*)valid->p));
-      med[j] = ac; med[j].nullable = true; med[j].c.data = data->p; med[j].c.validity = (const uint8_t*)valid->p; med[j].c.length = G;
-      r.keep.push_back(data); r.keep.push_back(valid); r.own(sj);
+      if (med[j]) {
+        const PTable sj = (int)j == first_med ? sorted0 : sorted_by((int)j, Names{arg_name(j)});
+        const PCol& ac = sj.cols[(size_t)find_column(sj, arg_name(j))];
+        BufP data = dev_alloc((size_t)std::max<int64_t>(G, 1) * width_of(ac.c) + 16), valid = dev_alloc(bitmap_bytes(G) + 8);
+        check(x, gpuq_segment_median(x.ctx, x.stream, &ac.c, (const int32_t*)starts->p, G, data->p, (uint8_t*)valid->p));
+        medians[j] = ac; medians[j].nullable = true; medians[j].c.data = data->p; medians[j].c.validity = (const uint8_t*)valid->p; medians[j].c.length = G;
+        r.keep.push_back(data); r.keep.push_back(valid); r.own(sj);
+      }
+      if (apx[j]) {
+        const PCol& ac = sorted0.cols[(size_t)find_column(sorted0, arg_name(j))];
+        BufP est = dev_alloc((size_t)std::max<int64_t>(G, 1) * 8 + 16);
+        check(x, gpuq_segment_approx_distinct(x.ctx, x.stream, &ac.c, (const int32_t*)starts->p, G, n, 0, (uint64_t*)est->p));
+        PTable one; append_column(one, arg_name(j), T_UINT64, est->p, est, nullptr, G, false);
+        sketches[j] = one.cols[0];
+        r.own(one); r.own(sorted0);
+      }
     }
     // ---- 6. the result in declared order: the keys of every segment's first row, then the aggregates
     if (nk) {
@@ -1198,7 +1253,7 @@ struct AggregateExec : PNode {
     }
     size_t pi = nk ? 1 : 0;
     for (size_t i = 0; i < aggr_expr.a.size(); ++i) {
-      PCol c = arg_of[i] >= 0 ? med[(size_t)arg_of[i]] : pres.cols.at(pi++);
+      PCol c = arg_of[i] < 0 ? pres.cols.at(pi++) : is_median(aggr_expr.a[i]) ? medians[(size_t)arg_of[i]] : sketches[(size_t)arg_of[i]];
       c.name = aggr_expr.a[i].at("name").str(); c.c.length = G;
       r.cols.push_back(c);
     }
@@ -1214,7 +1269,7 @@ struct AggregateExec : PNode {
     input->require(&n);
   }
   PSchema schema() override {
-    if (has_median()) return median_schema();
+    if (has_segment_agg()) return segment_schema();
     const PSchema in = input->schema(); const auto nm = schema_names(in);
     Json ge = jarr();
     for (auto& g : group_expr.a) ge.a.push_back(jobj({{"expr", rebind(g.at("expr"), nm)}, {"name", g.at("name")}}));
@@ -1236,7 +1291,7 @@ struct AggregateExec : PNode {
     // -- never from a table some node in between has handed on
     if (final_ || !f.src->is_hash_join()) t.by_build = nullptr;
     auto t0 = std::chrono::steady_clock::now();
-    if (has_median()) { t.by_build = nullptr; return timed(x, t0, run_median(x, t, f)); }
+    if (has_segment_agg()) { t.by_build = nullptr; return timed(x, t0, run_segment_aggs(x, t, f)); }
     // (more group columns than the table holds keys, some of them strings: codes from the start -- a 128-bit packed string takes a key
     // slot of its own, a 32-bit code is packed with its neighbours, see compile_aggregate)
     bool many_string_keys = false;
@@ -2419,12 +2474,16 @@ PNodeP build_node(const Json& j) {
     // node is DISTINCT over the same argument the node becomes two -- GROUP BY (keys, x) throws the duplicates away, GROUP BY keys
     // aggregates what is left -- which is the rewrite DataFusion's SingleDistinctToGroupBy rule makes [UPSTREAM-KNOWLEDGE]; both levels
     // run on the existing hash aggregate.  Mixed DISTINCT / plain aggregates stay refused (gpuq_op_create says so).
-    // MEDIAN is lowered in the plan as well (AggregateExec::run_median), in mode Single only: the state a Partial would emit is the
-    // group's values, a list column, which the engine has no type for
-    if (n->has_median()) {
-      if (n->mode != "Single") throw Unsupported("MEDIAN in an AggregateExec of mode " + n->mode + " is not supported (its state would be a list column): mode Single only");
+    // MEDIAN and APPROX_DISTINCT are lowered in the plan as well (AggregateExec::run_segment_aggs), in mode Single only: the state a
+    // Partial would emit is the group's values, a list column, or the group's sketch, a 16 KB binary one, which the engine has no types for
+    if (n->has_segment_agg()) {
+      if (n->mode != "Single" && n->has_median()) throw Unsupported("MEDIAN in an AggregateExec of mode " + n->mode + " is not supported (its state would be a list column): mode Single only");
+      if (n->mode != "Single") throw Unsupported("APPROX_DISTINCT in an AggregateExec of mode " + n->mode + " is not supported (its state would be a 16 KB binary column per group, and "
+                                                 "there is no Binary type yet): mode Single only");
       for (auto& a : n->aggr_expr.a)
-        if (a.get_bool("distinct", false)) throw Unsupported(std::string(is_median(a) ? "MEDIAN(DISTINCT ...)" : "a DISTINCT aggregate on a node with a MEDIAN") + " is not supported");
+        if (a.get_bool("distinct", false))
+          throw Unsupported((is_median(a) ? "MEDIAN(DISTINCT ...)" : is_approx_distinct(a) ? "APPROX_DISTINCT(DISTINCT ...)" :
+                             n->has_median() ? "a DISTINCT aggregate on a node with a MEDIAN" : "a DISTINCT aggregate on a node with an APPROX_DISTINCT") + std::string(" is not supported"));
     }
     bool any_distinct = false, all_distinct = !n->aggr_expr.a.empty();
     for (auto& a : n->aggr_expr.a) { const bool d = a.get_bool("distinct", false); any_distinct = any_distinct || d; all_distinct = all_distinct && d; }

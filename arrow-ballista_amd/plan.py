@@ -616,8 +616,9 @@ class AggregateExec(ExecutionPlan):
     datafusion.proto:631-669 and their aliases) and each function's state columns are listed with the operator descriptors in
     include/gpuq.h.  Modes: Partial (emits state columns), Final / FinalPartitioned (merge states), Single.
     strategy: "auto" (by cardinality and input order), or one kernel family: "tiny", "lds", "hash", "radix", "runs" (include/gpuq.h).
-    MEDIAN (mode Single; `"filter"` allowed) is not one of the operator's functions: the native executor lowers a node that holds one
-    (include/gpuq.h, gpuq_segment_median); the Python restatement of the executor (GPUQ_PLAN_LAYER=mirror) does not have it."""
+    MEDIAN and APPROX_DISTINCT (mode Single; `"filter"` allowed) are not among the operator's functions: the native executor lowers a
+    node that holds one (include/gpuq.h, gpuq_segment_median and gpuq_segment_approx_distinct; APPROX_DISTINCT is a HyperLogLog estimate,
+    UInt64 and never NULL); the Python restatement of the executor (GPUQ_PLAN_LAYER=mirror) has neither."""
 
     def __init__(self, mode, group_expr, aggr_expr, input, strategy="auto", expected_groups=0):
         super().__init__()
@@ -639,9 +640,10 @@ class AggregateExec(ExecutionPlan):
         return d
 
     def schema(self):
-        if any(str(a.get("fn", "")).upper() == "MEDIAN" for a in self.aggr_expr):
-            # MEDIAN is no accumulator of the operator (compile_check refuses it): the native executor lowers the node in the plan
-            # (csrc/plan_exec.cpp run_median) and types it there, without a device -- ask it, over the input's schema as a leaf
+        if any(str(a.get("fn", "")).upper() in ("MEDIAN", "APPROX_DISTINCT") for a in self.aggr_expr):
+            # MEDIAN and APPROX_DISTINCT are no accumulators of the operator (compile_check refuses them): the native executor lowers the
+            # node in the plan (csrc/plan_exec.cpp run_segment_aggs) and types it there, without a device -- ask it, over the input's
+            # schema as a leaf
             leaf = {"MemoryExec": {"schema": [{"name": f["name"], "type": f["type"], "nullable": bool(f.get("nullable", True))} for f in self.input.schema()],
                                    "partitions": [0]}}
             return B.plan_schema({"AggregateExec": {"input": leaf, "mode": self.mode, "strategy": self.strategy,

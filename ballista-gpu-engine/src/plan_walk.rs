@@ -17,7 +17,7 @@ use datafusion::physical_plan::aggregates::{AggregateExec, AggregateMode};
 use datafusion::physical_plan::coalesce_batches::CoalesceBatchesExec;
 use datafusion::physical_plan::coalesce_partitions::CoalescePartitionsExec;
 use datafusion::physical_plan::expressions::{
-    Avg, BinaryExpr, BitAnd, BitOr, BitXor, BoolAnd, BoolOr, CaseExpr, CastExpr, Column, Count, InListExpr, IsNotNullExpr, IsNullExpr, LikeExpr, Literal, Max, Median, Min, NegativeExpr, NotExpr,
+    ApproxDistinct, Avg, BinaryExpr, BitAnd, BitOr, BitXor, BoolAnd, BoolOr, CaseExpr, CastExpr, Column, Count, InListExpr, IsNotNullExpr, IsNullExpr, LikeExpr, Literal, Max, Median, Min, NegativeExpr, NotExpr,
     PhysicalSortExpr, Sum, TryCastExpr,
 };
 use datafusion::physical_plan::filter::FilterExec;
@@ -192,6 +192,7 @@ fn aggregate_fn(a: &Arc<dyn AggregateExpr>) -> Result<&'static str> {
        else if x.is::<BitAnd>() { "BIT_AND" } else if x.is::<BitOr>() { "BIT_OR" } else if x.is::<BitXor>() { "BIT_XOR" }
        else if x.is::<BoolAnd>() { "BOOL_AND" } else if x.is::<BoolOr>() { "BOOL_OR" }
        else if x.is::<Median>() { "MEDIAN" }      // mode Single only: the native executor lowers it in the plan (include/gpuq.h) and refuses the other modes
+       else if x.is::<ApproxDistinct>() { "APPROX_DISTINCT" }      // mode Single only, as MEDIAN: lowered in the plan (a HyperLogLog sketch per segment); its two-phase state is refused
        else { return unsupported(format!("aggregate {}", a.name())) })
 }
 

@@ -413,6 +413,69 @@ def h2o(tc, T, g, n=10_000_000, k=100, reps=3):
     return out
 
 
+def approx_distinct(tc, T, g, log2n=28, n_grouped=10_000_000, k=100, reps=3):
+    """APPROX_DISTINCT next to COUNT(DISTINCT) and to a plain streaming read of the same column (an ungrouped SUM), through the native
+    plan executor, inputs resident in HBM, best of `reps` after one warm-up: (a) ungrouped over 2^log2n Int64 rows holding 2^24 different
+    values -- one segment, every tile stores a partial sketch and one block merges them; (b) grouped in h2o's `id4, id5` shape
+    (k x k groups) over n_grouped rows.  COUNT(DISTINCT) of the same run gives the exact counts the estimates are held against.
+    Per-kernel times (the sketch pass and the merge apart) come from a kernel trace of this run, not from here."""
+    import sys
+    import numpy as np
+    import pyarrow as pa
+    from arrow_ballista_amd.expr import col
+
+    def timed(plan):
+        plan.execute(0); best = None
+        for _ in range(reps):
+            _sync(tc); t0 = time.perf_counter(); res = plan.execute(0); _sync(tc); dt = time.perf_counter() - t0
+            best = dt if best is None or dt < best else best
+        return best * 1e3, res.to_arrow()
+
+    def three(src, keys, c, exact_rows):
+        s = src.schema()
+        ke = [(col(x, s), x) for x in keys]
+        A = lambda fn, name, **kw: dict({"fn": fn, "expr": col(c, s), "name": name}, **kw)
+        e = {}
+        e["sum_ms"], _ = timed(g.NativePlan(g.AggregateExec("Single", ke, [A("SUM", "s")], src), tc))
+        print("approx_distinct bench: SUM by %s done" % (keys or "nothing"), file=sys.stderr, flush=True)
+        e["approx_distinct_ms"], apx = timed(g.NativePlan(g.AggregateExec("Single", ke, [A("APPROX_DISTINCT", "d")], src), tc))
+        print("approx_distinct bench: APPROX_DISTINCT done", file=sys.stderr, flush=True)
+        e["count_distinct_ms"], cd = timed(g.NativePlan(g.AggregateExec("Single", ke, [A("COUNT", "d", distinct=True)], src), tc))
+        print("approx_distinct bench: COUNT(DISTINCT) done", file=sys.stderr, flush=True)
+        e["count_distinct_over_approx"] = e["count_distinct_ms"] / e["approx_distinct_ms"]
+        e["approx_over_sum"] = e["approx_distinct_ms"] / e["sum_ms"]
+        by = [(x, "ascending") for x in keys]
+        a, b = (apx.sort_by(by), cd.sort_by(by)) if keys else (apx, cd)
+        est, exact = a.column("d").to_numpy().astype(np.float64), b.column("d").to_numpy().astype(np.float64)
+        e["groups"] = int(len(exact))
+        e["same_groups"] = bool(all(a.column(x).equals(b.column(x)) for x in keys)) and len(est) == len(exact)
+        e["exact_is_known_count"] = None if exact_rows is None else bool(len(exact) == 1 and int(exact[0]) == exact_rows)
+        e["worst_relative_error"] = float(np.max(np.abs(est - exact) / np.maximum(exact, 1.0)))
+        e["mean_relative_error"] = float(np.mean(np.abs(est - exact) / np.maximum(exact, 1.0)))
+        return e
+    out = {}
+    n = 1 << log2n
+    # uniform draws, not an arithmetic sequence: the hash aggregate behind COUNT(DISTINCT) sizes itself from every (n / 2^20)-th row, and a
+    # sequence i * c mod 2^24 shows such a power-of-two stride only 2^24 / stride of its values
+    v = np.random.default_rng(5).integers(0, 1 << 24, n)
+    known = int(np.count_nonzero(np.bincount(v, minlength=1 << 24)))
+    t = pa.table({"v": pa.array(v)})
+    t = t.cast(pa.schema([pa.field("v", pa.int64(), nullable=False)]))
+    src = g.MemoryExec([g.DeviceTable.from_arrow(t, tc.device)])
+    del v, t
+    out["ungrouped"] = dict({"rows": n, "bytes": n * 8}, **three(src, [], "v", known))
+    out["ungrouped"]["approx_distinct_GBps"] = n * 8 / out["ungrouped"]["approx_distinct_ms"] / 1e6
+    out["ungrouped"]["sum_GBps"] = n * 8 / out["ungrouped"]["sum_ms"] / 1e6
+    del src
+    r = np.random.default_rng(11)
+    m = n_grouped
+    x = pa.table({"id4": pa.array(r.integers(1, k + 1, m).astype(np.int32)), "id5": pa.array(r.integers(1, k + 1, m).astype(np.int32)),
+                  "id3": pa.array(r.integers(1, m // k + 1, m), pa.int64())})
+    x = x.cast(pa.schema([pa.field(f.name, f.type, nullable=False) for f in x.schema]))
+    out["by_id4_id5"] = dict({"rows": m}, **three(g.MemoryExec([g.DeviceTable.from_arrow(x, tc.device)]), ["id4", "id5"], "id3", None))
+    return out
+
+
 def like_micro(tc, T, g, n=1 << 23, reps=5):
     """LikeExpr throughput (q13's `o_comment NOT LIKE '%special%requests%'` shape): n comment-like strings of 19-78 bytes built
     from a word list, Arrow layout in HBM; one gpuq_like_utf8 launch per pattern.  Bytes = offsets + string bytes read."""
@@ -760,6 +823,11 @@ if __name__ == "__main__":
         sys.exit(0)
     if "--like" in sys.argv:
         print(json.dumps(like_micro(tc, T, g), indent=1))
+        sys.exit(0)
+    if "--approx-distinct" in sys.argv:      # [--log2n 28] [--rows 10000000]
+        bits = int(sys.argv[sys.argv.index("--log2n") + 1]) if "--log2n" in sys.argv else 28
+        rows = int(sys.argv[sys.argv.index("--rows") + 1]) if "--rows" in sys.argv else 10_000_000
+        print(json.dumps(approx_distinct(tc, T, g, bits, rows), indent=1))
         sys.exit(0)
     if "--h2o" in sys.argv:
         rows = int(sys.argv[sys.argv.index("--rows") + 1]) if "--rows" in sys.argv else 10_000_000

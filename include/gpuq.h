@@ -500,6 +500,44 @@ int gpuq_segment_heads(gpuq_ctx* ctx, void* stream, const gpuq_column* key_cols,
                        uint64_t* n_groups_dev);
 int gpuq_segment_median(gpuq_ctx* ctx, void* stream, const gpuq_column* value_col, const int32_t* starts, int64_t n_groups, void* out_data, uint8_t* out_validity);
 
+/* APPROX_DISTINCT (AggregateFunction APPROX_DISTINCT in datafusion.proto:637-648; DataFusion 34's HyperLogLog [UPSTREAM-KNOWLEDGE:
+   physical-expr aggregate/approx_distinct.rs, hyperloglog.rs; the crate source is not in the reference tree]; the known answer
+   approx_distinct(id) = 8 of ballista/client/src/context.rs:817-829).  Its state is a 16 KB sketch per group, so like MEDIAN it is no row
+   of the operator's accumulator table: the "aggregate" descriptor of gpuq_op_create / gpuq_compile_check refuses it, and the native plan
+   executor lowers an AggregateExec in mode Single that holds one (next to MEDIANs and any other aggregates) to a sort by the keys -- none
+   when the node is ungrouped; MEDIAN's sorts when it holds MEDIANs too -- gpuq_segment_heads and the entry point below.  The rules:
+     spelling   {"fn": "APPROX_DISTINCT", "expr": e, "name": n, "filter"?: p}; the name is matched without regard to case.
+     argument   Int8..Int64, UInt8..UInt64, Date32, Date64, Timestamp, Decimal128, Float32, Float64; Utf8 while every value fits the
+                packed 15 bytes (refused by name beyond that); Boolean and anything else is refused ("APPROX_DISTINCT over <type>").
+     result     UInt64, never NULL: 0 for a group with no non-NULL argument.
+     values     NULL arguments are ignored; with FILTER (WHERE p) a row where p is not true counts as a NULL argument.  Floats count by
+                value: -0.0 and 0.0 are one value, every NaN is one value.
+     no rows    ungrouped: one row holding 0; grouped: no rows.
+     sketch     precision p = 14: m = 16384 one-byte registers, q = 50.  DataFusion's ahash is CPU-feature dependent, so the hash is this
+                library's: h = mix64(lo ^ mix64(hi + 0x632BE59BD9B4E019)), the value half of the partition hash.  Types of 8 bytes or
+                fewer: lo = the value widened to 64 bits (integers sign- or zero-extended by their type; floats their canonical bit
+                pattern, zero-extended, Float32 its own 32 bits), hi = 0.  Decimal128 and packed Utf8: lo, hi = the two words as they
+                lie.  idx = h & 16383; rho = ctz((h >> 14) | (1 << 50)) + 1 in 1..51; reg[idx] = max(reg[idx], rho).
+     estimator  Ertl's improved estimator over the histogram C[0..51] of the register values, in Float64 without contraction
+                (csrc/hll_estimate.h): z = m tau((m - C[51]) / m); for k = 50 .. 1: z = 0.5 (z + C[k]); z += m sigma(C[0] / m);
+                E = floor(0.5 / ln 2 * m^2 / z + 0.5), and 0 when z is infinite (every register 0).
+                sigma(x): x = 1: +inf; else y = 1, z = x; repeat x *= x, z += x y, y += y until z stops changing.
+                tau(x): x = 0 or 1: 0; else y = 1, z = 1 - x; repeat x = sqrt(x), y *= 0.5, z -= (1 - x)^2 y until z stops changing; z / 3.
+                The estimate is exact for a handful of values and within about 1.04 / sqrt(m) = 0.8 % (one standard error) beyond; it
+                does not depend on the order of the rows, so it is reproducible bit for bit.
+   Refused, with APPROX_DISTINCT in the message: modes Partial / Final / FinalPartitioned (the state would be a 16 KB binary column per
+   group, and there is no Binary type yet), `distinct`, a DISTINCT aggregate on the same node, a Float32 / Float64 group key (bytewise
+   segment heads and the hash aggregate need not agree on -0.0 / NaN), group keys holding strings beyond 15 bytes, 2^31 rows or more in
+   a partition.
+
+   gpuq_segment_approx_distinct: out[g] (n_groups device words) = the estimate over segment [starts[g], starts[g + 1]) of the first n_rows
+   rows of `value_col` (Arrow layout as it lies; Utf8 as PACKED15); starts: n_groups + 1 ascending device int32.  Rows are in any order
+   inside a segment; an empty segment gives 0; n_groups = 0 writes nothing.  tile_rows: the rows one block walks -- 0 for the library's
+   choice, else a multiple of 256 (the result does not depend on it).  Scratch (two 16 KB sketches per tile) comes from the context's pool
+   and counts against gpuq_memory_limit.  Asynchronous on `stream`. */
+int gpuq_segment_approx_distinct(gpuq_ctx* ctx, void* stream, const gpuq_column* value_col, const int32_t* starts, int64_t n_groups, int64_t n_rows, int64_t tile_rows,
+                                 uint64_t* out);
+
 /* dst[i] = src[i] + delta for n Utf8 offsets: joining the offset arrays of partitions that are concatenated (fan-in). */
 int gpuq_offsets_rebase(gpuq_ctx* ctx, void* stream, const int32_t* src, int64_t n, int32_t delta, int32_t* dst);
 
@@ -529,6 +567,7 @@ int gpuq_copy_bits(gpuq_ctx* ctx, void* stream, uint8_t* dst, int64_t dst_bit_of
      {"AggregateExec": {"input", "mode", "group_expr": [{"expr","name"}], "aggr_expr": [{"fn","expr","expr2"?,"name"}],
                         "strategy"?, "expected_groups"?, "output_capacity"?}}        (:1405-1450)
          fn: the operator's functions, and -- mode Single, this executor only -- MEDIAN ("expr", "filter"?; see gpuq_segment_median)
+             and APPROX_DISTINCT ("expr", "filter"?; see gpuq_segment_approx_distinct)
      {"HashJoinExec": {"left", "right", "on": [{"left": expr, "right": expr}], "join_type", "partition_mode",
                        "null_equals_null", "filter"?}}                               (:1346-1360)
      {"SortExec" | "SortPreservingMergeExec": {"input", "expr": [{"expr","asc","nulls_first"}], "fetch"?}}   (:1465-1478)
