@@ -541,7 +541,94 @@ __device__ __host__ __forceinline__ u64 hash_combine(u64 h, u64 lo, u64 hi, bool
 }
 
 // ---------------------------------------------------------------- wave idioms
-// rank of this lane among the set bits of a wave ballot (blocks are one-dimensional multiples of 64 threads)
-__device__ __forceinline__ uint32_t lane_rank(const u64 ballot) { return (uint32_t)__popcll(ballot & ((1ull << (threadIdx.x & 63)) - 1)); }
+// Blocks are one-dimensional multiples of 64 threads, and every helper below is executed by all 64 lanes of its wave (the block
+// helpers: by all threads of the block): a lane parked on a branch around them reads as garbage in its neighbours' shuffles.
+__device__ __forceinline__ int lane() { return (int)(threadIdx.x & 63); }
+__device__ __forceinline__ int wave() { return (int)(threadIdx.x >> 6); }
+// rank of this lane among the set bits of a wave ballot
+__device__ __forceinline__ uint32_t lane_rank(const u64 ballot) { return (uint32_t)__popcll(ballot & ((1ull << lane()) - 1)); }
+
+struct SumOp { template <class T> __device__ __forceinline__ T operator()(const T a, const T b) const { return a + b; } };
+struct MaxOp { template <class T> __device__ __forceinline__ T operator()(const T a, const T b) const { return b > a ? b : a; } };
+struct MinOp { template <class T> __device__ __forceinline__ T operator()(const T a, const T b) const { return b < a ? b : a; } };
+
+// Butterfly reduction: every lane ends with the combination of all 64 values, combined in the same fixed order (a float sum is
+// bitwise reproducible run to run).
+template <class F, class T> __device__ __forceinline__ T wave_reduce(T v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = F()(v, __shfl_xor(v, off));
+  return v;
+}
+template <class T> __device__ __forceinline__ T wave_sum(const T v) { return wave_reduce<SumOp>(v); }
+template <class T> __device__ __forceinline__ T wave_max(const T v) { return wave_reduce<MaxOp>(v); }
+template <class T> __device__ __forceinline__ T wave_min(const T v) { return wave_reduce<MinOp>(v); }
+
+// Inclusive scan over the lanes: lane l ends with the combination of lanes 0..l.
+template <class F = SumOp, class T> __device__ __forceinline__ T wave_incl_scan(T v) {
+  const int l = lane();
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) { const T y = __shfl_up(v, off); if (l >= off) v = F()(y, v); }
+  return v;
+}
+
+// ---------------------------------------------------------------- block idioms
+// Exclusive prefix sum of one value per thread across a block of WAVES waves; *total (when asked for) is the block's sum, in every
+// thread.  wsum is the caller's __shared__ T[WAVES].  Contains ONE barrier, between the waves' stores to wsum and the reads of it;
+// the caller owes a barrier of its own before wsum is written again (another call, or any other use of the array).
+template <int WAVES, class T> __device__ __forceinline__ T block_excl_scan(const T v, T* wsum, T* total = nullptr) {
+  const int w = wave();
+  const T incl = wave_incl_scan(v);
+  if (lane() == 63) wsum[w] = incl;
+  __syncthreads();
+  T pre = 0, all = 0;
+#pragma unroll
+  for (int q = 0; q < WAVES; ++q) { const T s = wsum[q]; if (q < w) pre += s; all += s; }
+  if (total) *total = all;
+  return pre + incl - v;
+}
+// The block's sum of one value per thread, valid in thread 0 ONLY (the shape "thread 0 writes the total").  Same barrier contract as
+// block_excl_scan: one barrier inside, one owed by the caller before wsum is written again.
+template <int WAVES, class T> __device__ __forceinline__ T block_sum(const T v, T* wsum) {
+  const T s = wave_sum(v);
+  if (lane() == 0) wsum[wave()] = s;
+  __syncthreads();
+  T all = 0;
+  if (threadIdx.x == 0) for (int q = 0; q < WAVES; ++q) all += wsum[q];
+  return all;
+}
+// One block of 1024 threads scans a whole array: store(i, p) is called once for every i < n with p = the combination of
+// load(0..i-1) (`identity` for i = 0), *total (when asked for) receives the combination of everything.  Every wave owns a contiguous
+// sixteenth of the array, rounded up to a multiple of 64 (so the tail waves of a short array own nothing), and walks it 64 items at
+// a time: coalesced loads and stores.  (A thread-per-range layout made every load of a wave touch 64 different cache lines: 57 us
+// for 32 Ki counts, most of it latency.)  load(i) is called twice per item; store may write where load reads, item by item.
+// Two barriers inside, in its own 16 words of LDS; every thread of the block must arrive.
+template <class F, class T, class I, class Load, class Store>
+__device__ __forceinline__ void block_walk_scan(const I n, const T identity, Load load, Store store, T* total) {
+  __shared__ T wtot[16];
+  const int w = wave(), l = lane();
+  const I per = (I)(((n + 15) / 16 + 63) & ~(I)63);      // items per wave, a multiple of 64
+  const I a = (I)w * per, b = a + per < n ? a + per : n;
+  // pass 1: the wave's total
+  T tot = identity;
+  for (I i = a + l; i < b; i += 64) tot = F()(tot, load(i));
+  tot = wave_reduce<F>(tot);
+  if (l == 0) wtot[w] = tot;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    T run = identity;
+    for (int k = 0; k < 16; ++k) { const T v = wtot[k]; wtot[k] = run; run = F()(run, v); }
+    if (total) *total = run;
+  }
+  __syncthreads();
+  // pass 2: the prefix inside the wave's range, carried from one 64-item step to the next
+  T carry = wtot[w];
+  for (I i0 = a; i0 < b; i0 += 64) {
+    const I i = i0 + l;
+    const T x = wave_incl_scan<F>(i < b ? load(i) : identity);
+    T before = __shfl_up(x, 1); if (l == 0) before = identity;
+    if (i < b) store(i, F()(carry, before));
+    carry = F()(carry, __shfl(x, 63));
+  }
+}
 
 }  // namespace gpuq

@@ -353,6 +353,8 @@ constexpr SinkInfo GPUQ_SINKS[] = {
 void launch_gather_words(hipStream_t s, const GatherWords& g, u64* out);
 void set_num_cus(int n);
 int num_cus();
+// blocks for n rows at one 64-row word per wave, at least one, capped at blocks_per_cu per compute unit
+int grid_for_words(i64 n, int waves_per_block, int blocks_per_cu);
 void launch_filter_bitmap(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, u64* bitmap, uint32_t* block_counts, int nblocks, i64 words_per_block);
 void launch_scan_block_counts(hipStream_t s, uint32_t* block_counts, int nblocks, u64* total_out);
 void launch_compact(hipStream_t s, const u64* bitmap, const uint32_t* block_offsets, int nblocks, i64 words_per_block, i64 n,

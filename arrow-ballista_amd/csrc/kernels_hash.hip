@@ -22,8 +22,6 @@ namespace gpuq {
 constexpr int HBLOCK = 256;
 constexpr int HWAVES = HBLOCK / 64;
 
-__device__ __forceinline__ int hlane() { return threadIdx.x & 63; }
-__device__ __forceinline__ int hwave() { return threadIdx.x >> 6; }
 
 __device__ __forceinline__ u64 a_load(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void a_store(u64* p, u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -210,7 +208,7 @@ __device__ __forceinline__ void load_rows_staged(const DevProgram& P, const i64 
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const i64 w = w0 + (i64)u * w_stride;
-    const i64 pos = (w << 6) + hlane();
+    const i64 pos = (w << 6) + lane();
     ex[u] = w < w_end && pos < n;
     posc[u] = ex[u] ? pos : (n > 0 ? n - 1 : 0);
     gpuq_jit_pre(P, posc[u], jq[u]);
@@ -231,7 +229,7 @@ __device__ __forceinline__ void eval_rows_staged(const DevProgram& P, const i64 
     const i64 w = w0 + (i64)u * w_stride;
     GPUQ_REGS_DECL;
     const bool pass = gpuq_jit_compute(P, posc[u], jw[u], GPUQ_REGS);
-    row(u, w, (w << 6) + hlane(), ex[u] && pass, GPUQ_REGS);
+    row(u, w, (w << 6) + lane(), ex[u] && pass, GPUQ_REGS);
   }
 }
 // ONE narrow (<= 64-bit) key of a staged row, register R: its value and whether it is NULL, both cleared for a row that is not active
@@ -268,12 +266,12 @@ __device__ __forceinline__ void for_rows_in_flight(const DevProgram& P, const i6
       if (w >= nwords) break;             // wave-uniform
       GPUQ_REGS_DECL;
       const bool pass = gpuq_jit_compute(P, posc[u], jw[u], GPUQ_REGS);
-      body(w, (w << 6) + hlane(), ex[u] && pass, GPUQ_REGS);
+      body(w, (w << 6) + lane(), ex[u] && pass, GPUQ_REGS);
     }
   }
 #else
   for (i64 w = w_first; w < nwords; w += w_stride) {
-    const i64 pos = (w << 6) + hlane();
+    const i64 pos = (w << 6) + lane();
     bool active = pos < n;
     GPUQ_REGS_DECL;
     if (active) active = GPUQ_EVAL(MAXC, P, pos);
@@ -311,8 +309,8 @@ struct WaveQueue {
   }
   // the cnt (<= 64, <= size()) oldest entries, entry i to lane i; true for the lanes that got one
   __device__ __forceinline__ bool pop(const uint32_t cnt, uint32_t (&fields)[N]) {
-    const bool on = (uint32_t)hlane() < cnt;
-    const uint32_t s = (head + (on ? (uint32_t)hlane() : 0u)) % (uint32_t)CAP;
+    const bool on = (uint32_t)lane() < cnt;
+    const uint32_t s = (head + (on ? (uint32_t)lane() : 0u)) % (uint32_t)CAP;
 #pragma unroll
     for (int k = 0; k < N; ++k) fields[k] = slots[k][s];
     head += cnt;
@@ -351,8 +349,8 @@ __device__ __forceinline__ void k_agg_hash_body(const DevProgram P, const i64 n_
   // table access is a device-scope transaction (~10 G/s on this part), so a run of r rows costs 1/r of the traffic.
   bool combine = true;
   for (int a = 0; a < A.n_accs; ++a) combine = combine && A.acc_kind[a] != ACC_FMIN && A.acc_kind[a] != ACC_FMAX;
-  const int lane = hlane();
-  for_rows_in_flight<MAXC>(P, n, (i64)blockIdx.x * HWAVES + hwave(), (i64)gridDim.x * HWAVES, [&](const i64, const i64, const bool active, GPUQ_REGS_PARAM) {
+  const int lane = gpuq::lane();
+  for_rows_in_flight<MAXC>(P, n, (i64)blockIdx.x * HWAVES + wave(), (i64)gridDim.x * HWAVES, [&](const i64, const i64, const bool active, GPUQ_REGS_PARAM) {
     if (__ballot(active) == 0) return;
     u64 kw[MAX_KW]; u64 h = 0;
 #pragma unroll
@@ -413,26 +411,26 @@ __global__ void __launch_bounds__(HBLOCK) k_agg_hash_extract(const KeySpec K, co
   const int cell0 = 1 + T.key_words;
   const u64 chunk_slots = 64ull * XSUB;
   const u64 nchunks = (T.n_slots + chunk_slots - 1) / chunk_slots;
-  const u64 wave0 = (u64)blockIdx.x * HWAVES + hwave(), nwaves = (u64)gridDim.x * HWAVES;
+  const u64 wave0 = (u64)blockIdx.x * HWAVES + wave(), nwaves = (u64)gridDim.x * HWAVES;
   for (u64 c = wave0; c < nchunks; c += nwaves) {
     u64 masks[XSUB]; uint32_t total = 0;
 #pragma unroll
     for (int j = 0; j < XSUB; ++j) {
-      const u64 s = c * chunk_slots + (u64)j * 64 + hlane();
+      const u64 s = c * chunk_slots + (u64)j * 64 + lane();
       const bool live = s < T.n_slots && ((uint32_t)T.slots[s * (u64)T.slot_words]) >= 2u;
       masks[j] = __ballot(live); total += (uint32_t)__popcll(masks[j]);
     }
     if (total == 0) continue;
     uint32_t base = 0;
-    if (hlane() == 0) base = atomicAdd(out.n_groups, total);
+    if (lane() == 0) base = atomicAdd(out.n_groups, total);
     base = __shfl(base, 0);
     if (out.cap == 0) continue;           // counting pass (the caller sizes the result from n_groups): nothing to write, nothing to flag
-    if (base + total > (uint32_t)out.cap && hlane() == 0) atomicOr(flags, FLAG_GROUP_OVERFLOW);      // once per wave, not once per row
+    if (base + total > (uint32_t)out.cap && lane() == 0) atomicOr(flags, FLAG_GROUP_OVERFLOW);      // once per wave, not once per row
 #pragma unroll
     for (int j = 0; j < XSUB; ++j) {
       const u64 m = masks[j];
-      if ((m >> hlane()) & 1) {
-        const u64 s = c * chunk_slots + (u64)j * 64 + hlane();
+      if ((m >> lane()) & 1) {
+        const u64 s = c * chunk_slots + (u64)j * 64 + lane();
         const u64* slot = T.slots + s * (u64)T.slot_words;
         const uint32_t g = base + lane_rank(m);
         if (g < (uint32_t)out.cap) { if (K.state_key) emit_state_group(slot, K, A, soa, g); else emit_group(slot, cell0, K, A, out, g); }
@@ -459,7 +457,7 @@ __global__ void __launch_bounds__(HBLOCK) k_agg_hash_extract(const KeySpec K, co
 // (head, prev_p1) and the state moved on.  Executed by all 64 lanes.
 struct RunsLane { bool head; u64 prev_p1; u64 active_mask; };
 __device__ __forceinline__ RunsLane runs_word(const bool active, const u64 key, bool& below63, u64& last_p1) {
-  const int lane = hlane();
+  const int lane = gpuq::lane();
   RunsLane r;
   r.active_mask = __ballot(active);
   const u64 under = lane ? runs_lanes_le(r.active_mask, lane - 1) : 0ull;      // the active lanes below this one
@@ -494,7 +492,7 @@ __device__ __forceinline__ u64 runs_walk(const DevProgram& P, const i64 n, const
 template <int MAXC>
 __device__ __forceinline__ void k_agg_runs_count_body(const DevProgram P, const i64 n_arg, const KeySpec K, const RunsGeom G) {
   const i64 n = rows_of(P, n_arg);      // deferred execution: the row count is a device word, n_arg its host-side bound
-  const i64 s = (i64)blockIdx.x * HWAVES + hwave();
+  const i64 s = (i64)blockIdx.x * HWAVES + wave();
   if (s >= G.nsegs) return;
   uint32_t heads = 0; u64 first_p1 = 0; bool bad = false;
   const u64 last_p1 = runs_walk<MAXC>(P, n, K, s * G.wps, G.wps, [&](const u64 key, const bool, const RunsLane& r, GPUQ_REGS_CPARAM) {
@@ -505,8 +503,8 @@ __device__ __forceinline__ void k_agg_runs_count_body(const DevProgram P, const 
     const u64 open_key = __shfl(key, open ? __builtin_ctzll(open) : 0);
     if (open) first_p1 = open_key + 1;
   });
-  if (__ballot(bad) && hlane() == 0) atomicOr(P.flags, FLAG_AGG_RUNS);
-  if (hlane() == 0) { G.counts[s] = heads; G.seg_last[s] = last_p1; G.seg_first[s] = first_p1; }
+  if (__ballot(bad) && lane() == 0) atomicOr(P.flags, FLAG_AGG_RUNS);
+  if (lane() == 0) { G.counts[s] = heads; G.seg_last[s] = last_p1; G.seg_first[s] = first_p1; }
 }
 #ifndef GPUQ_JIT
 template <int MAXC>
@@ -520,28 +518,9 @@ extern "C" __global__ void __launch_bounds__(HBLOCK) gpuq_jit_entry(const DevPro
 // open head (seg_first) against the last keys of all segments before it (seg_last: a running maximum, which is the nearest one while
 // nothing is out of order).  One block; every wave owns a contiguous sixteenth of the segments and walks it 64 at a time.
 __global__ void __launch_bounds__(1024) k_agg_runs_order(const RunsGeom G, uint32_t* __restrict__ flags) {
-  __shared__ u64 wmax[16];
-  const int t = threadIdx.x, w = t >> 6, l = t & 63, n = G.nsegs;
-  const int per = ((n + 15) / 16 + 63) & ~63;
-  const int a = w * per, b = a + per < n ? a + per : n;
-  u64 m = 0;
-  for (int i = a + l; i < b; i += 64) { const u64 v = G.seg_last[i]; m = v > m ? v : m; }
-  for (int off = 32; off > 0; off >>= 1) { const u64 o = __shfl_xor(m, off); m = o > m ? o : m; }
-  if (l == 0) wmax[w] = m;
-  __syncthreads();
-  if (t == 0) { u64 run = 0; for (int k = 0; k < 16; ++k) { const u64 v = wmax[k]; wmax[k] = run; run = v > run ? v : run; } }
-  __syncthreads();
-  u64 carry = wmax[w]; bool bad = false;
-  for (int i0 = a; i0 < b; i0 += 64) {
-    const int i = i0 + l;
-    u64 x = i < b ? G.seg_last[i] : 0;
-    for (int off = 1; off < 64; off <<= 1) { const u64 y = __shfl_up(x, off); if (l >= off && y > x) x = y; }
-    u64 before = __shfl_up(x, 1); if (l == 0) before = 0;
-    if (carry > before) before = carry;
-    const u64 f = i < b ? G.seg_first[i] : 0;
-    bad = bad || (f != 0 && f <= before);
-    const u64 top = __shfl(x, 63); if (top > carry) carry = top;
-  }
+  bool bad = false;
+  block_walk_scan<MaxOp>((int)G.nsegs, (u64)0, [&](const int i) { return G.seg_last[i]; },
+                         [&](const int i, const u64 before) { const u64 f = G.seg_first[i]; bad = bad || (f != 0 && f <= before); }, (u64*)nullptr);
   if (bad) atomicOr(flags, FLAG_AGG_RUNS);
 }
 // the accumulator cells of one result column set to (lo, hi): an identity that is not all zero bits (BIT_AND)
@@ -554,9 +533,9 @@ template <int MAXC>
 __device__ __forceinline__ void k_agg_runs_write_body(const DevProgram P, const i64 n_arg, const KeySpec K, const AggSpec A, const RunsGeom G, const AggSoA soa, const uint32_t cap) {
   if (__hip_atomic_load(P.flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & FLAG_AGG_RUNS) return;      // (raised by the launches before this one: the result is void)
   const i64 n = rows_of(P, n_arg);      // deferred execution: the row count is a device word, n_arg its host-side bound
-  const i64 s = (i64)blockIdx.x * HWAVES + hwave();
+  const i64 s = (i64)blockIdx.x * HWAVES + wave();
   if (s >= G.nsegs) return;
-  const int lane = hlane();
+  const int lane = gpuq::lane();
   const uint32_t base = G.counts[s];      // (scanned: the heads of the segments before this one)
   uint32_t heads = 0;
   runs_walk<MAXC>(P, n, K, s * G.wps, G.wps, [&](const u64 key, const bool active, const RunsLane& r, GPUQ_REGS_CPARAM) {
@@ -610,8 +589,8 @@ __device__ __forceinline__ void k_agg_bucket_id_body(const DevProgram P, const i
                                                          u64* __restrict__ bid, uint32_t* __restrict__ ids) {
   const i64 n = rows_of(P, n_arg);      // deferred execution: the row count is a device word, n_arg its host-side bound
   const i64 nwords = (n + 63) >> 6;
-  for (i64 w = (i64)blockIdx.x * HWAVES + hwave(); w < nwords; w += (i64)gridDim.x * HWAVES) {
-    const i64 pos = (w << 6) + hlane();
+  for (i64 w = (i64)blockIdx.x * HWAVES + wave(); w < nwords; w += (i64)gridDim.x * HWAVES) {
+    const i64 pos = (w << 6) + lane();
     if (pos >= n) continue;
     GPUQ_REGS_DECL;
     const bool pass = GPUQ_EVAL(MAXC, P, pos);
@@ -649,14 +628,14 @@ __global__ void __launch_bounds__(HBLOCK) k_key_sample(const DevProgram P, const
   if (threadIdx.x == 0) block_passed = 0;
   __syncthreads();
   const i64 nwords = (nsample + 63) >> 6;
-  for (i64 w = (i64)blockIdx.x * HWAVES + hwave(); w < nwords; w += (i64)gridDim.x * HWAVES) {
-    const i64 i = (w << 6) + hlane();
+  for (i64 w = (i64)blockIdx.x * HWAVES + wave(); w < nwords; w += (i64)gridDim.x * HWAVES) {
+    const i64 i = (w << 6) + lane();
     i64 pos = i * stride; if (pos >= n) pos = n - 1;
     bool active = i < nsample;
     GPUQ_REGS_DECL;
     if (active) active = GPUQ_EVAL(MAXC, P, pos);
     const u64 m = __ballot(active);
-    if (m && hlane() == 0) atomicAdd(&block_passed, (unsigned int)__popcll(m));
+    if (m && lane() == 0) atomicAdd(&block_passed, (unsigned int)__popcll(m));
     if (!active) continue;
     u64 kw[MAX_KW]; u64 h = 0;
     make_key(K, GPUQ_REGS, kw, h);
@@ -693,8 +672,8 @@ __device__ __forceinline__ void k_agg_lds_body(const DevProgram P, const i64 n_a
   if (threadIdx.x == 0) lfull = 0;
   __syncthreads();
   const i64 nwords = (n + 63) >> 6;
-  for (i64 w = (i64)blockIdx.x * HWAVES + hwave(); w < nwords; w += (i64)gridDim.x * HWAVES) {
-    const i64 pos = (w << 6) + hlane();
+  for (i64 w = (i64)blockIdx.x * HWAVES + wave(); w < nwords; w += (i64)gridDim.x * HWAVES) {
+    const i64 pos = (w << 6) + lane();
     bool active = pos < n;
     GPUQ_REGS_DECL;
     if (active) active = GPUQ_EVAL(MAXC, P, pos);
@@ -752,20 +731,18 @@ __device__ __forceinline__ void k_agg_lds_body(const DevProgram P, const i64 n_a
 __global__ void __launch_bounds__(HBLOCK) k_fsum_stage_reduce(const HashTable T, const AggSpec A, const u64* __restrict__ fstage, const int n_fsum, const uint32_t nblk) {
   const int gcell0 = 1 + T.key_words;
   const u64 items = T.n_slots * (u64)n_fsum;
-  for (u64 it = (u64)blockIdx.x * HWAVES + hwave(); it < items; it += (u64)gridDim.x * HWAVES) {
+  for (u64 it = (u64)blockIdx.x * HWAVES + wave(); it < items; it += (u64)gridDim.x * HWAVES) {
     const u64 gs = it / (u64)n_fsum; const int kf = (int)(it % (u64)n_fsum);
     if ((uint32_t)T.slots[gs * (u64)T.slot_words] < 2u) continue;
     const u64* src = fstage + it * nblk;
     double acc = 0.0;
     for (uint32_t b0 = 0; b0 < nblk; b0 += 64) {
-      const uint32_t b = b0 + hlane();
+      const uint32_t b = b0 + lane();
       double v = b < nblk ? __longlong_as_double((i64)src[b]) : 0.0;
       // fixed tree inside the 64 blocks, then in order across groups of 64
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-      acc += v;
+      acc += wave_sum(v);
     }
-    if (hlane() == 0) {
+    if (lane() == 0) {
       int k = 0, a = 0;
       for (; a < A.n_accs; ++a) if (A.acc_kind[a] == ACC_FSUM) { if (k == kf) break; ++k; }
       double* cell = (double*)(T.slots + gs * (u64)T.slot_words + gcell0 + 2 * a);
@@ -828,7 +805,7 @@ __device__ __forceinline__ void k_agg_bucket_body(const DevProgram P, const KeyS
         const bool live = s < cap && (uint32_t)slot[0] >= 2u;
         const u64 m = __ballot(live);
         uint32_t wbase = 0;
-        if (hlane() == 0 && m) wbase = atomicAdd(&cnt[pass], (uint32_t)__popcll(m));
+        if (lane() == 0 && m) wbase = atomicAdd(&cnt[pass], (uint32_t)__popcll(m));
         wbase = __shfl(wbase, 0);
         if (pass == 1 && live) {
           const uint32_t g = gbase + wbase + lane_rank(m);
@@ -865,19 +842,15 @@ __device__ __forceinline__ void k_join_keyrange_body(const DevProgram P, const i
   i64 mn = 0x7FFFFFFFFFFFFFFFll, mx = (i64)0x8000000000000000ull; u64 cn = 0;
   const int kr = __builtin_amdgcn_readfirstlane(K.key_reg[0]);
   // wstep > 1: every wstep-th 64-row word only (a sample: the host widens what comes out and the build checks every row against it)
-  for_rows_in_flight<MAXC>(P, n, ((i64)blockIdx.x * HWAVES + hwave()) * wstep, (i64)gridDim.x * HWAVES * wstep, [&](const i64, const i64, const bool active, GPUQ_REGS_PARAM) {
+  for_rows_in_flight<MAXC>(P, n, ((i64)blockIdx.x * HWAVES + wave()) * wstep, (i64)gridDim.x * HWAVES * wstep, [&](const i64, const i64, const bool active, GPUQ_REGS_PARAM) {
     if (active && !((rnulls >> kr) & 1)) {
       const i64 v = (i64)rlo[kr];
       mn = v < mn ? v : mn; mx = v > mx ? v : mx; ++cn;
     }
   });
   (void)null_eq;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const i64 a = __shfl_xor(mn, o), b = __shfl_xor(mx, o); const u64 c = __shfl_xor(cn, o);
-    mn = a < mn ? a : mn; mx = b > mx ? b : mx; cn += c;
-  }
-  if (hlane() == 0) { smn[hwave()] = mn; smx[hwave()] = mx; scn[hwave()] = cn; }
+  mn = wave_min(mn); mx = wave_max(mx); cn = wave_sum(cn);
+  if (lane() == 0) { smn[wave()] = mn; smx[wave()] = mx; scn[wave()] = cn; }
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int k = 1; k < HWAVES; ++k) { mn = smn[k] < mn ? smn[k] : mn; mx = smx[k] > mx ? smx[k] : mx; cn += scn[k]; }
@@ -959,11 +932,11 @@ __device__ __forceinline__ void k_join_build_body(const DevProgram P, const i64 
   // table's index) -- and inserted 64 at a time with every lane busy: the chain is paid once per 64 survivors.
   constexpr int QC = SEMI ? BUILD_QCAP : 1;
   __shared__ uint32_t q_lds[SEMI ? HWAVES : 1][3][QC];
-  WaveQueue<3, QC> q(q_lds[SEMI ? hwave() : 0]);
+  WaveQueue<3, QC> q(q_lds[SEMI ? wave() : 0]);
   const bool queued = SEMI && S.on && T.dense != nullptr;
   const bool s_bits = S.T.dense != nullptr && S.T.dense_bits != nullptr;      // the other table answers "is it there" from its bitmap alone
   uint32_t survivors = 0;
-  for_rows_in_flight<MAXC>(P, n, (i64)blockIdx.x * HWAVES + hwave(), (i64)gridDim.x * HWAVES, [&](const i64 w, const i64 pos, bool active, GPUQ_REGS_PARAM) {
+  for_rows_in_flight<MAXC>(P, n, (i64)blockIdx.x * HWAVES + wave(), (i64)gridDim.x * HWAVES, [&](const i64 w, const i64 pos, bool active, GPUQ_REGS_PARAM) {
     uint32_t aux = NIL;
     if (SEMI && S.on) {
       bool found = false;
@@ -984,7 +957,7 @@ __device__ __forceinline__ void k_join_build_body(const DevProgram P, const i64 
     // `present` = every build-side row that passes the side's predicate, NULL keys included (outer joins emit them).  When rows
     // are positions, the 64 rows of this step ARE word w of the bitmap: one plain 8-byte store (64 lanes OR-ing into two words
     // serialise in the L2's atomic unit -- it was most of the build's time: 1.4 ms for 14.6 M rows)
-    if (present && payload_via == 0) { const u64 am = __ballot(active); if (hlane() == 0) ((u64*)present)[w] = am; }
+    if (present && payload_via == 0) { const u64 am = __ballot(active); if (lane() == 0) ((u64*)present)[w] = am; }
     if (queued) {
       u64 idx = 0; bool ins = false;
       if (active) {
@@ -1023,9 +996,8 @@ __device__ __forceinline__ void k_join_build_body(const DevProgram P, const i64 
   });
   if (queued && q.size() > 0) insert_queued(q, q.size(), P, T, next, S, s_bits);
   if (SEMI && S.on && S.rows_out) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) survivors += __shfl_xor(survivors, o);
-    if (hlane() == 0 && survivors) atomicAdd((unsigned long long*)S.rows_out, (unsigned long long)survivors);
+    survivors = wave_sum(survivors);
+    if (lane() == 0 && survivors) atomicAdd((unsigned long long*)S.rows_out, (unsigned long long)survivors);
   }
 }
 #if defined(GPUQ_JIT) && defined(GPUQ_JIT_SEMI) && GPUQ_JIT_SEMI == 2
@@ -1043,14 +1015,14 @@ __device__ __forceinline__ void k_join_build_semi1_body(const DevProgram P, cons
   constexpr int U = GPUQ_SEMI_ROWS;
   constexpr int QC = 64 * (U + 1);      // < 64 waiting + <= 64 U from one more step
   __shared__ uint32_t q_lds[HWAVES][3][QC];
-  WaveQueue<3, QC> q(q_lds[hwave()]);
+  WaveQueue<3, QC> q(q_lds[wave()]);
   const i64 n = rows_of(P, n_arg);
   const i64 nwords = (n + 63) >> 6;
   const bool s_dense = S.T.dense != nullptr;
   const uint32_t* __restrict__ sbits = S.T.dense_bits;
   const bool late_row = s_dense && sbits != nullptr;      // the other table's row is only read for the survivors, when the queue is worked off
   uint32_t survivors = 0;
-  const i64 wave0 = ((i64)blockIdx.x * HWAVES + hwave()) * U, wstride = (i64)gridDim.x * HWAVES * U;
+  const i64 wave0 = ((i64)blockIdx.x * HWAVES + wave()) * U, wstride = (i64)gridDim.x * HWAVES * U;
   for (i64 wb = wave0; wb < nwords; wb += wstride) {
     bool act[U]; u64 key1[U], key2[U]; bool n1[U], n2[U]; uint32_t row[U];
     eval_rows_staged<U>(P, n, wb, 1, nwords, [&](const int u, const i64, const i64 pos, const bool active, GPUQ_REGS_PARAM) __attribute__((always_inline)) {
@@ -1098,9 +1070,8 @@ __device__ __forceinline__ void k_join_build_semi1_body(const DevProgram P, cons
   }
   if (q.size() > 0) insert_queued(q, q.size(), P, T, next, S, late_row);
   if (S.rows_out) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) survivors += __shfl_xor(survivors, o);
-    if (hlane() == 0 && survivors) atomicAdd((unsigned long long*)S.rows_out, (unsigned long long)survivors);
+    survivors = wave_sum(survivors);
+    if (lane() == 0 && survivors) atomicAdd((unsigned long long*)S.rows_out, (unsigned long long)survivors);
   }
 }
 #endif
@@ -1152,7 +1123,7 @@ __device__ __forceinline__ void k_join_probe_body(const DevProgram P, const i64 
     const u64 m = __ballot(emit);
     if (m == 0) return;
     u64 base = 0;
-    if (hlane() == 0) base = a_add(out_count, (u64)__popcll(m));
+    if (lane() == 0) base = a_add(out_count, (u64)__popcll(m));
     base = __shfl(base, 0);
     if (emit) {
       const u64 idx = base + lane_rank(m);
@@ -1160,8 +1131,8 @@ __device__ __forceinline__ void k_join_probe_body(const DevProgram P, const i64 
       else atomicOr(P.flags, FLAG_OUT_OVERFLOW);
     }
   };
-  for (i64 w = (i64)blockIdx.x * HWAVES + hwave(); w < nwords; w += (i64)gridDim.x * HWAVES) {
-    const i64 pos = (w << 6) + hlane();
+  for (i64 w = (i64)blockIdx.x * HWAVES + wave(); w < nwords; w += (i64)gridDim.x * HWAVES) {
+    const i64 pos = (w << 6) + lane();
     bool active = pos < n;
     GPUQ_REGS_DECL;
     if (active) active = GPUQ_EVAL(MAXC, P, pos);
@@ -1244,8 +1215,8 @@ __device__ __forceinline__ void k_join_probe_unique_body(const DevProgram P, con
   // stores; the per-step chain is columns -> bitmap.
   constexpr int QC = 64 * (U + 1);      // < 64 waiting + <= 64 U from one more step
   __shared__ uint32_t hq_lds[HWAVES][2][QC];
-  WaveQueue<2, QC> hq(hq_lds[hwave()]);
-  const i64 seg = (i64)blockIdx.x * HWAVES + hwave();
+  WaveQueue<2, QC> hq(hq_lds[wave()]);
+  const i64 seg = (i64)blockIdx.x * HWAVES + wave();
   if (seg >= nsegs) return;
   const i64 nwords = (n + 63) >> 6;
   const i64 w0 = seg * wpw;
@@ -1259,7 +1230,7 @@ __device__ __forceinline__ void k_join_probe_unique_body(const DevProgram P, con
   auto resolve_hits = [&](const uint32_t n_out) __attribute__((always_inline)) {      // the n_out (<= 64) oldest hits -> pairs at seg_base + cnt
     uint32_t e[2];
     if (hq.pop(n_out, e)) {
-      const u64 pos = seg_base + cnt + (u64)hlane();
+      const u64 pos = seg_base + cnt + (u64)lane();
       if (seg_build) seg_build[pos] = dense[e[0]];
       seg_probe[pos] = e[1];
     }
@@ -1312,10 +1283,10 @@ __device__ __forceinline__ void k_join_probe_unique_body(const DevProgram P, con
         const int pp = __shfl_up((int)probe, 1);
         const u64 pk = __shfl_up(key[u], 1);
         const int pn = __shfl_up((int)isn[u], 1);
-        const bool same = (hlane() > 0) & (pp != 0) & (pk == key[u]) & ((pn != 0) == isn[u]);
+        const bool same = (lane() > 0) & (pp != 0) & (pk == key[u]) & ((pn != 0) == isn[u]);
         head[u] = probe & !same;
-        const u64 hm = __ballot(head[u]) & ((2ull << hlane()) - 1);          // heads at or below this lane
-        src[u] = (probe && hm) ? (63 - __clzll((long long)hm)) : hlane();
+        const u64 hm = __ballot(head[u]) & ((2ull << lane()) - 1);          // heads at or below this lane
+        src[u] = (probe && hm) ? (63 - __clzll((long long)hm)) : lane();
       }
       // stage 2: first slot of every run
       ulonglong2 sv[U]; u64 si[U];
@@ -1346,7 +1317,7 @@ __device__ __forceinline__ void k_join_probe_unique_body(const DevProgram P, con
     }
   }
   if (hit_queue && hq.size() > 0) resolve_hits(hq.size());
-  if (hlane() == 0) seg_counts[seg] = cnt;
+  if (lane() == 0) seg_counts[seg] = cnt;
 }
 #else
 template <int MAXC>
@@ -1356,7 +1327,7 @@ __device__ __forceinline__ void k_join_probe_unique_body(const DevProgram P, con
                                                               uint32_t* __restrict__ seg_counts, const int nsegs, const i64 wpw,
                                                               uint32_t* __restrict__ visited) {
   const i64 n = rows_of(P, n_arg);      // deferred execution: the row count is a device word, n_arg its host-side bound
-  const i64 seg = (i64)blockIdx.x * HWAVES + hwave();
+  const i64 seg = (i64)blockIdx.x * HWAVES + wave();
   if (seg >= nsegs) return;
   const i64 nwords = (n + 63) >> 6;
   const i64 w0 = seg * wpw;
@@ -1375,7 +1346,7 @@ __device__ __forceinline__ void k_join_probe_unique_body(const DevProgram P, con
     }
     cnt += emit_pairs(probe_row_emits(join_type, active, hit != NIL), hit, prow, seg_base, cnt, seg_build, seg_probe);
   }, w1);
-  if (hlane() == 0) seg_counts[seg] = cnt;
+  if (lane() == 0) seg_counts[seg] = cnt;
 }
 #endif  // GPUQ_JIT_PROBE1
 #ifndef GPUQ_JIT
@@ -1400,11 +1371,11 @@ __global__ void __launch_bounds__(HBLOCK) k_copy_segments(const uint32_t* __rest
                                                           uint32_t* __restrict__ out_build, uint32_t* __restrict__ out_probe, const u64 out_cap,
                                                           uint32_t* __restrict__ flags) {
   const u64 tot = *total;
-  for (i64 seg = (i64)blockIdx.x * HWAVES + hwave(); seg < nsegs; seg += (i64)gridDim.x * HWAVES) {
+  for (i64 seg = (i64)blockIdx.x * HWAVES + wave(); seg < nsegs; seg += (i64)gridDim.x * HWAVES) {
     const u64 off = seg_offsets[seg];
     const u64 end = (seg + 1 < nsegs) ? (u64)seg_offsets[seg + 1] : tot;
     const u64 src = (u64)(seg * wpw) << 6;
-    for (u64 i = hlane(); off + i < end; i += 64) {
+    for (u64 i = lane(); off + i < end; i += 64) {
       if (off + i < out_cap) {
         if (out_build) out_build[off + i] = seg_build[src + i];
         out_probe[off + i] = seg_probe[src + i];
@@ -1444,8 +1415,8 @@ __device__ __forceinline__ void k_rj_pack_body(const DevProgram P, const i64 n_a
   const int kr = __builtin_amdgcn_readfirstlane(K.key_reg[0]);
   const i64 a = (i64)blockIdx.x * G.tile;
   i64 b = a + G.tile; if (b > n) b = n;
-  for (i64 p0 = a + (i64)hwave() * 64; p0 < b; p0 += HBLOCK) {
-    const i64 pos = p0 + hlane();
+  for (i64 p0 = a + (i64)wave() * 64; p0 < b; p0 += HBLOCK) {
+    const i64 pos = p0 + lane();
     bool active = pos < b;
     GPUQ_REGS_DECL;
     if (active) active = GPUQ_EVAL(MAXC, P, pos);
@@ -1480,8 +1451,8 @@ __global__ void __launch_bounds__(HBLOCK) k_rj_scatter(const u64* __restrict__ r
   __shared__ uint32_t lcnt[RJ_MAX_PARTS + 1];     // records of the digit in this step, then the digit's first slot in sk
   __shared__ uint32_t gbase[RJ_MAX_PARTS + 1];    // global position of the digit's next record
   __shared__ uint32_t wsum[HWAVES];
-  const int t = threadIdx.x, l = hlane(), w = hwave();
-  const uint32_t D = G.nparts;                    // digits 0..D-1 are written; digit D (dropped) is counted and skipped
+  const int t = threadIdx.x;
+  const uint32_t D = G.nparts;                   // digits 0..D-1 are written; digit D (dropped) is counted and skipped
   for (uint32_t d = t; d <= D; d += HBLOCK) gbase[d] = (uint32_t)offsets[(size_t)d * G.nblocks + blockIdx.x];
   const uint32_t per = (D + 1 + HBLOCK - 1) / HBLOCK;       // digits per thread in the scan (<= 5)
   const i64 a = (i64)blockIdx.x * G.tile;
@@ -1499,15 +1470,7 @@ __global__ void __launch_bounds__(HBLOCK) k_rj_scatter(const u64* __restrict__ r
     uint32_t c[5]; uint32_t tot = 0;
 #pragma unroll
     for (uint32_t k = 0; k < 5; ++k) { const uint32_t d = t * per + k; c[k] = (k < per && d <= D) ? lcnt[d] : 0; tot += c[k]; }
-    uint32_t x = tot;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const uint32_t y = __shfl_up(x, off); if (l >= off) x += y; }
-    if (l == 63) wsum[w] = x;
-    __syncthreads();
-    uint32_t pre = 0;
-#pragma unroll
-    for (int q = 0; q < HWAVES; ++q) if (q < w) pre += wsum[q];
-    uint32_t run = pre + x - tot;
+    uint32_t run = block_excl_scan<HWAVES>(tot, wsum);
 #pragma unroll
     for (uint32_t k = 0; k < 5; ++k) { const uint32_t d = t * per + k; if (k < per && d <= D) { lcnt[d] = run; run += c[k]; } }
     __syncthreads();
@@ -1537,20 +1500,20 @@ __global__ void __launch_bounds__(HBLOCK) k_rj_probe(const u64* __restrict__ rec
                                                      uint32_t* __restrict__ seg_build, uint32_t* __restrict__ seg_probe, uint32_t* __restrict__ seg_counts,
                                                      const int nsegs, const i64 wpw) {
   constexpr int U = 4;
-  const i64 seg = (i64)blockIdx.x * HWAVES + hwave();
+  const i64 seg = (i64)blockIdx.x * HWAVES + wave();
   if (seg >= nsegs) return;
   const i64 n = (i64)*n_live_p;
   const i64 nwords = (n + 63) >> 6;
   const i64 x = blockIdx.x % 8, nbx = ((i64)gridDim.x - x + 7) / 8;          // blocks of this group
   const i64 g0 = nwords * x / 8, g1 = nwords * (x + 1) / 8;                   // the group's words
-  const i64 nwx = nbx * HWAVES, wl = (i64)(blockIdx.x / 8) * HWAVES + hwave();  // waves of the group, this wave's index among them
+  const i64 nwx = nbx * HWAVES, wl = (i64)(blockIdx.x / 8) * HWAVES + wave();  // waves of the group, this wave's index among them
   const u64 seg_base = (u64)(seg * wpw) << 6;
   const uint32_t* __restrict__ dense = T.dense; const uint32_t* __restrict__ dbits = T.dense_bits;
   uint32_t cnt = 0;
   for (i64 wb = g0 + wl * U; wb < g1; wb += nwx * U) {
     u64 r[U]; bool act[U]; uint32_t hit[U]; uint32_t bw[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) { const i64 pos = ((wb + u) << 6) + hlane(); act[u] = (wb + u) < g1 && pos < n; r[u] = act[u] ? rec[pos] : 0; }
+    for (int u = 0; u < U; ++u) { const i64 pos = ((wb + u) << 6) + lane(); act[u] = (wb + u) < g1 && pos < n; r[u] = act[u] ? rec[pos] : 0; }
     if (dbits) {
 #pragma unroll
       for (int u = 0; u < U; ++u) { bw[u] = act[u] ? dense_presence_word(dbits, r[u] >> 32) : 0u; }
@@ -1563,7 +1526,7 @@ __global__ void __launch_bounds__(HBLOCK) k_rj_probe(const u64* __restrict__ rec
 #pragma unroll
     for (int u = 0; u < U; ++u) cnt += emit_pairs(act[u] && hit[u] != NIL, hit[u], (uint32_t)r[u], seg_base, cnt, join_type == JT_RIGHT_SEMI ? nullptr : seg_build, seg_probe);
   }
-  if (hlane() == 0) seg_counts[seg] = cnt;
+  if (lane() == 0) seg_counts[seg] = cnt;
 }
 #endif
 
@@ -1574,8 +1537,8 @@ __global__ void __launch_bounds__(HBLOCK) k_join_locality(const DevProgram P, co
                                                           u64* __restrict__ out) {
   const int kr = __builtin_amdgcn_readfirstlane(K.key_reg[0]);
   u64 pairs = 0, near = 0;
-  for (i64 sidx = (i64)blockIdx.x * HWAVES + hwave(); sidx < nsample; sidx += (i64)gridDim.x * HWAVES) {
-    const i64 pos = ((sidx * stride) << 6) + hlane();
+  for (i64 sidx = (i64)blockIdx.x * HWAVES + wave(); sidx < nsample; sidx += (i64)gridDim.x * HWAVES) {
+    const i64 pos = ((sidx * stride) << 6) + lane();
     bool active = pos < n;
     GPUQ_REGS_DECL;
     if (active) active = GPUQ_EVAL(MAXC, P, pos);
@@ -1584,24 +1547,18 @@ __global__ void __launch_bounds__(HBLOCK) k_join_locality(const DevProgram P, co
     active = active && idx < T.dense_range;
     const u64 nidx = __shfl_down(idx, 1);
     const int nact = __shfl_down((int)active, 1);
-    const bool pair = active && nact && hlane() < 63;
+    const bool pair = active && nact && lane() < 63;
     const u64 d = nidx > idx ? nidx - idx : idx - nidx;
     pairs += (u64)__popcll(__ballot(pair));
     near += (u64)__popcll(__ballot(pair && d < (1ull << 14)));
   }
-  if (hlane() == 0 && pairs) { atomicAdd((unsigned long long*)out, (unsigned long long)pairs); atomicAdd((unsigned long long*)out + 1, (unsigned long long)near); }
+  if (lane() == 0 && pairs) { atomicAdd((unsigned long long*)out, (unsigned long long)pairs); atomicAdd((unsigned long long*)out + 1, (unsigned long long)near); }
 }
 #endif
 
 #ifndef GPUQ_JIT
 // ------------------------------------------------------------------ launchers
-static int hgrid(i64 n, int blocks_per_cu) {
-  const i64 nwords = (n + 63) >> 6;
-  i64 need = (nwords + HWAVES - 1) / HWAVES;
-  if (need < 1) need = 1;
-  const i64 cap = (i64)num_cus() * blocks_per_cu;
-  return (int)(need < cap ? need : cap);
-}
+static int hgrid(i64 n, int blocks_per_cu) { return grid_for_words(n, HWAVES, blocks_per_cu); }
 
 void launch_ht_init(hipStream_t s, const HashTable& T, const AggSpec* A) {
   AggSpec dummy{};
@@ -1713,10 +1670,8 @@ __global__ void __launch_bounds__(HBLOCK) k_bitmap_select(const u64* __restrict_
     if (w == nwords - 1 && (n & 63)) m &= (1ull << (n & 63)) - 1;
     bitmap[w] = m; cnt += (uint32_t)__popcll(m);
   }
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-  if (hlane() == 0) wc[hwave()] = cnt;
-  __syncthreads();
-  if (threadIdx.x == 0) { uint32_t t = 0; for (int k = 0; k < HWAVES; ++k) t += wc[k]; block_counts[blockIdx.x] = t; }
+  const uint32_t t = block_sum<HWAVES>(cnt, wc);
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = t;
 }
 #endif
 void launch_bitmap_select(hipStream_t s, const u64* present, const u64* visited, int matched, i64 nwords, i64 n, u64* bitmap,

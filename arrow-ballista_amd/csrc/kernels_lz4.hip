@@ -22,12 +22,11 @@ constexpr int LZ4_MFLIMIT = 12;        // a match must start at least 12 bytes b
 constexpr int LZ4_LASTLITERALS = 5;    // the last 5 bytes of a block are literals
 
 __device__ __forceinline__ uint32_t ld32u(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 __device__ __forceinline__ int rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // n bytes, all lanes of the wave; src and dst do not overlap
 __device__ __forceinline__ void wave_copy(uint8_t* dst, const uint8_t* src, int n) {
-  const int lane = lane_id();
+  const int lane = gpuq::lane();
   if (n >= 512) {           // long runs: 4 bytes per lane through unaligned dword loads, stores aligned after a byte head
     const int head = (int)((4 - ((uintptr_t)dst & 3)) & 3);
     if (lane < head) dst[lane] = src[lane];
@@ -43,7 +42,7 @@ __device__ __forceinline__ void wave_copy(uint8_t* dst, const uint8_t* src, int 
 // ---------------------------------------------------------------- compress
 // length field continuation: v >= 15 -> bytes of 255 then the remainder
 __device__ __forceinline__ int put_len_ext(uint8_t* out, int o, int v /* value - 15, >= 0 */) {
-  const int nb = v / 255 + 1, lane = lane_id();
+  const int nb = v / 255 + 1, lane = gpuq::lane();
   for (int i = lane; i < nb; i += 64) out[o + i] = (uint8_t)((i < nb - 1) ? 255 : (v % 255));
   return o + nb;
 }
@@ -53,7 +52,7 @@ __global__ __launch_bounds__(64) void k_lz4_compress(const uint8_t* __restrict__
   __shared__ uint16_t ht[1 << LZ4_HASH_BITS];
   const int b = (int)blockIdx.x;
   if (b >= n_blocks) return;
-  const int lane = lane_id();
+  const int lane = gpuq::lane();
   const uint8_t* src = src_base + blocks[b].src;
   uint8_t* out = dst_base + blocks[b].slot;
   const int len = blocks[b].len;
@@ -160,17 +159,13 @@ __global__ void __launch_bounds__(256) k_lz4_layout_sizes(const Lz4Block* __rest
     const int k = k0 + t;
     int64_t v = 0, r = 0;
     if (k < l) { r = blocks[k].len; v = 4 + (csize[k] < blocks[k].len ? csize[k] : blocks[k].len); }
-    int64_t x = v, rr = r;                                      // inclusive scan inside the wave, raw sum alongside
-    for (int o = 1; o < 64; o <<= 1) { const int64_t y = __shfl_up(x, o); if ((t & 63) >= o) x += y; }
-    for (int o = 32; o > 0; o >>= 1) rr += __shfl_xor(rr, o);
-    if ((t & 63) == 63) wsum[t >> 6] = x;
+    const int64_t rr = wave_sum(r);                             // raw sum alongside
+    int64_t step;
+    const int64_t before = block_excl_scan<4>(v, wsum, &step);
+    if (k < l) blk_dst[k] = carry + before;
     __syncthreads();
-    int64_t before = carry;
-    for (int w = 0; w < (t >> 6); ++w) before += wsum[w];
-    if (k < l) blk_dst[k] = before + x - v;                     // exclusive
-    __syncthreads();
-    if (t == 0) carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    if ((t & 63) == 0) atomicAdd((unsigned long long*)&rawc, (unsigned long long)rr);
+    if (t == 0) carry += step;
+    if (lane() == 0) atomicAdd((unsigned long long*)&rawc, (unsigned long long)rr);
     __syncthreads();
   }
   if (t == 0) {
@@ -242,7 +237,7 @@ struct InWin {      // 256-byte window of the compressed stream held in register
 };
 __device__ __forceinline__ void win_load(InWin& W, int64_t dw) {
   W.w0 = dw;
-  const int64_t i = dw + lane_id();
+  const int64_t i = dw + lane();
   W.w = (i < W.wend) ? W.base[i] : 0u;
 }
 __device__ __forceinline__ int win_byte(InWin& W, int64_t a /* byte address relative to W.base */) {
@@ -255,7 +250,7 @@ __device__ __forceinline__ int win_byte(InWin& W, int64_t a /* byte address rela
 // one LZ4 block: in [ip, iend) -> out at op; returns the new op or -1 on a malformed stream
 // (the sequence format is stated here a second time, beside lz::lz4_sequence: see the head of lz_elements.h for what the shared form cost this loop)
 __device__ __forceinline__ int64_t lz4_decode_block(InWin& W, const uint8_t* in8, int64_t ip, int64_t iend, uint8_t* out, int64_t op, int64_t out_lo, int64_t out_hi) {
-  const int lane = lane_id();
+  const int lane = gpuq::lane();
   while (ip < iend) {
     const int token = win_byte(W, ip); ip += 1;
     int64_t lit = token >> 4;      // 64-bit, and bounded while it grows: a long run of 0xFF length bytes must not wrap past the checks below
@@ -318,7 +313,7 @@ __global__ __launch_bounds__(64) void k_lz4_decode(const uint8_t* __restrict__ s
     }
     if (!bad && op != U.dst_len) bad = true;
   }
-  if (bad && lane_id() == 0) atomicOr(status, UNPACKF_MALFORMED);
+  if (bad && lane() == 0) atomicOr(status, UNPACKF_MALFORMED);
 }
 
 __global__ void k_popcount_bits(const u64* __restrict__ bits, int64_t n_bits, unsigned long long* __restrict__ out) {
@@ -329,8 +324,8 @@ __global__ void k_popcount_bits(const u64* __restrict__ bits, int64_t n_bits, un
     if (w == words - 1 && (n_bits & 63)) x &= (1ull << (n_bits & 63)) - 1ull;
     c += (unsigned long long)__popcll(x);
   }
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-  if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
+  c = wave_sum(c);
+  if (lane() == 0 && c) atomicAdd(out, c);
 }
 
 // ---------------------------------------------------------------- Utf8 columns of a multi-batch stream
@@ -381,7 +376,7 @@ __global__ __launch_bounds__(256) void k_utf8_piece_compact(const Utf8Piece* __r
 // left to k_zstd_pages, a stored one is copied.  -> true: `V` is a compressed stream (or a linked frame's stored block) for the caller
 struct JobBody { const uint8_t* in; uint8_t* out; int64_t in_len, out_len; };
 __device__ __forceinline__ bool unpack_job_begin(const UnpackJob& J, const uint8_t* __restrict__ src_base, uint8_t* __restrict__ dst_base, uint32_t* __restrict__ status, JobBody& V) {
-  const int lane = lane_id();
+  const int lane = gpuq::lane();
   const uint8_t* in = src_base + J.src; uint8_t* out = dst_base + J.dst;
   if (J.raw_prefix > J.src_len || J.raw_prefix > J.dst_len) { if (lane == 0) atomicOr(status, UNPACKF_MALFORMED); return false; }
   for (int64_t i = lane; i < J.raw_prefix; i += 64) out[i] = in[i];
@@ -411,7 +406,7 @@ __global__ __launch_bounds__(64) void k_unpack_pages(const uint8_t* __restrict__
   const int u = (int)blockIdx.x;
   if (u >= n_jobs) return;
   const UnpackJob J = jobs[u];
-  const int lane = lane_id();
+  const int lane = gpuq::lane();
   JobBody V;
   if (!unpack_job_begin(J, src_base, dst_base, status, V)) return;
   if (J.mode != UNPACK_SNAPPY) { if (lane == 0) atomicOr(status, UNPACKF_MALFORMED); return; }      // (LZ4 jobs are the parallel decoder's: the host never sends one here)
@@ -542,7 +537,7 @@ __global__ __launch_bounds__(64) void k_sn_head(const uint8_t* __restrict__ src_
   const int u = (int)blockIdx.x;
   if (u >= n_jobs) return;
   const UnpackJob J = jobs[u];
-  const int lane = lane_id();
+  const int lane = gpuq::lane();
   JobBody V;
   if (!unpack_job_begin(J, src_base, dst_base, status, V)) return;
   const uint8_t* const in = V.in;
@@ -598,8 +593,8 @@ __global__ __launch_bounds__(256) void k_sn_mark(const uint2* __restrict__ cmap,
     if (mark[J.c_off + p] && !mark[J.c_off + j]) { mark[J.c_off + j] = 1; ++fresh; }
     jout[J.c_off + p] = jin[J.c_off + j];
   }
-  for (int o = 32; o > 0; o >>= 1) fresh += __shfl_xor(fresh, o);
-  if ((threadIdx.x & 63) == 0 && fresh) atomicAdd(&cnt_cur[m.x], fresh);
+  fresh = wave_sum(fresh);
+  if (lane() == 0 && fresh) atomicAdd(&cnt_cur[m.x], fresh);
 }
 // scan input: the output length of every real element
 __global__ __launch_bounds__(256) void k_sn_lens(const uint2* __restrict__ cmap, const UnpackJob* __restrict__ jobs, const uint8_t* __restrict__ mark, const uint32_t* __restrict__ olen,
@@ -676,8 +671,8 @@ __global__ __launch_bounds__(256) void k_snappy_round(uint32_t* __restrict__ res
       }
     }
   }
-  for (int o = 32; o > 0; o >>= 1) left += __shfl_xor(left, o);
-  if ((threadIdx.x & 63) == 0 && left) atomicAdd(&cnt_cur[m.x], left);
+  left = wave_sum(left);
+  if (lane() == 0 && left) atomicAdd(&cnt_cur[m.x], left);
 }
 // the bytes: four resolved words -> one 32-bit store (the pages start 64-byte aligned)
 __global__ __launch_bounds__(256) void k_snappy_emit(const uint32_t* __restrict__ resolve, const uint2* __restrict__ blkmap, const UnpackJob* __restrict__ jobs, uint8_t* __restrict__ dst_base,

@@ -15,8 +15,6 @@ namespace gpuq {
 constexpr int BLOCK = 256;
 constexpr int WAVES = BLOCK / 64;
 
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
-__device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 __device__ __forceinline__ u64 uniform_u64(u64 v) {   // value known to be equal in all lanes -> SGPR pair
   return (u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) | ((u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32);
 }
@@ -33,18 +31,18 @@ __device__ __forceinline__ void k_filter_bitmap_body(const DevProgram P, const i
   const i64 w0 = (i64)blockIdx.x * wpb;
   i64 w1 = w0 + wpb; if (w1 > nwords) w1 = nwords;
   uint32_t cnt = 0;
-  for (i64 w = w0 + wave_id(); w < w1; w += WAVES) {
-    const i64 pos = (w << 6) + lane_id();
+  for (i64 w = w0 + wave(); w < w1; w += WAVES) {
+    const i64 pos = (w << 6) + lane();
     bool pass = false;
     if (pos < n) {
       GPUQ_REGS_DECL;
       pass = GPUQ_EVAL(MAXC, P, pos);
     }
     const u64 m = __ballot(pass);
-    if (lane_id() == 0) bitmap[w] = m;
+    if (lane() == 0) bitmap[w] = m;
     cnt += (uint32_t)__popcll(m);
   }
-  if (lane_id() == 0) wave_cnt[wave_id()] = cnt;
+  if (lane() == 0) wave_cnt[wave()] = cnt;
   __syncthreads();
   if (threadIdx.x == 0) {
     uint32_t t = 0;
@@ -64,34 +62,7 @@ extern "C" __global__ void __launch_bounds__(BLOCK) gpuq_jit_entry(const DevProg
 // Exclusive scan of <= 1024*ITEMS block counts in place; single block of 1024 threads.
 #ifndef GPUQ_JIT
 __global__ void __launch_bounds__(1024) k_scan_counts(uint32_t* __restrict__ counts, const int n, u64* __restrict__ total_out) {
-  // every wave owns a contiguous 1/16 of the counts and walks it 64 at a time (coalesced loads and stores; a thread-per-range
-  // layout made every load of a wave touch 64 different cache lines: 57 us for 32 Ki counts, most of it latency)
-  __shared__ u64 wsum[16];
-  const int t = threadIdx.x, w = t >> 6, l = t & 63;
-  const int per = ((n + 15) / 16 + 63) & ~63;            // counts per wave, a multiple of 64
-  const int a = w * per, b = a + per < n ? a + per : n;
-  // pass 1: the wave's total
-  u64 tot = 0;
-  for (int i = a + l; i < b; i += 64) tot += counts[i];
-  for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
-  if (l == 0) wsum[w] = tot;
-  __syncthreads();
-  if (t == 0) {
-    u64 run = 0;
-    for (int k = 0; k < 16; ++k) { u64 v = wsum[k]; wsum[k] = run; run += v; }
-    if (total_out) *total_out = run;
-  }
-  __syncthreads();
-  // pass 2: exclusive prefix inside the wave's range
-  u64 carry = wsum[w];
-  for (int i0 = a; i0 < b; i0 += 64) {
-    const int i = i0 + l;
-    const uint32_t c = i < b ? counts[i] : 0u;
-    u64 x = c;
-    for (int off = 1; off < 64; off <<= 1) { const u64 y = __shfl_up(x, off); if (l >= off) x += y; }
-    if (i < b) counts[i] = (uint32_t)(carry + x - c);
-    carry += __shfl(x, 63);
-  }
+  block_walk_scan<SumOp>(n, (u64)0, [&](const int i) { return (u64)counts[i]; }, [&](const int i, const u64 before) { counts[i] = (uint32_t)before; }, total_out);
 }
 #endif
 
@@ -107,18 +78,18 @@ __global__ void __launch_bounds__(BLOCK) k_compact(const u64* __restrict__ bitma
   i64 w1 = w0 + wpb; if (w1 > nwords) w1 = nwords;
   const i64 span = w1 > w0 ? (w1 - w0) : 0;
   const i64 per = (span + WAVES - 1) / WAVES;
-  const i64 a = w0 + per * wave_id();
+  const i64 a = w0 + per * wave();
   i64 b = a + per; if (b > w1) b = w1;
   uint32_t cnt = 0;
-  for (i64 w = a + lane_id(); w < b; w += 64) cnt += (uint32_t)__popcll(bitmap[w]);
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-  if (lane_id() == 0) wave_cnt[wave_id()] = cnt;
+  for (i64 w = a + lane(); w < b; w += 64) cnt += (uint32_t)__popcll(bitmap[w]);
+  cnt = wave_sum(cnt);
+  if (lane() == 0) wave_cnt[wave()] = cnt;
   __syncthreads();
   u64 out = block_offsets[blockIdx.x];
-  for (int k = 0; k < wave_id(); ++k) out += wave_cnt[k];
+  for (int k = 0; k < wave(); ++k) out += wave_cnt[k];
   for (i64 w = a; w < b; ++w) {
     const u64 m = bitmap[w];
-    const int l = lane_id();
+    const int l = lane();
     if ((m >> l) & 1) {
       const uint32_t rank = lane_rank(m);
       const i64 pos = (w << 6) + l;
@@ -134,8 +105,8 @@ template <int MAXC>
 __device__ __forceinline__ void k_project_body(const DevProgram P, const i64 n_arg, const OutSpec O) {
   const i64 n = rows_of(P, n_arg);
   const i64 nwords = (n + 63) >> 6;
-  for (i64 w = (i64)blockIdx.x * WAVES + wave_id(); w < nwords; w += (i64)gridDim.x * WAVES) {
-    const i64 pos = (w << 6) + lane_id();
+  for (i64 w = (i64)blockIdx.x * WAVES + wave(); w < nwords; w += (i64)gridDim.x * WAVES) {
+    const i64 pos = (w << 6) + lane();
     const bool active = pos < n;
     GPUQ_REGS_DECL;
     if (active) (void)GPUQ_EVAL(MAXC, P, pos);
@@ -148,7 +119,7 @@ __device__ __forceinline__ void k_project_body(const DevProgram P, const i64 n_a
         if (active) { lo = rlo[r]; hi = rhi[r]; isnull = (rnulls >> r) & 1; }
         if (oc.validity) {
           const u64 vm = __ballot(active && !isnull);
-          if (lane_id() == 0) oc.validity[w] = vm;
+          if (lane() == 0) oc.validity[w] = vm;
         }
         if (isnull) { lo = 0; hi = 0; }
         switch (oc.cls) {
@@ -158,7 +129,7 @@ __device__ __forceinline__ void k_project_body(const DevProgram P, const i64 n_a
           case CC_I16: case CC_U16: if (active) ((uint16_t*)oc.data)[pos] = (uint16_t)lo; break;
           case CC_F32: if (active) ((float*)oc.data)[pos] = (float)__longlong_as_double((i64)lo); break;
           case CC_I128: case CC_STR: if (active) ((ulonglong2*)oc.data)[pos] = make_ulonglong2(lo, hi); break;
-          case CC_BIT: { const u64 bm = __ballot(active && lo != 0); if (lane_id() == 0) ((u64*)oc.data)[w] = bm; break; }
+          case CC_BIT: { const u64 bm = __ballot(active && lo != 0); if (lane() == 0) ((u64*)oc.data)[w] = bm; break; }
           default: break;
         }
       }
@@ -364,7 +335,7 @@ __device__ __forceinline__ void k_agg_tiny_body(const DevProgram P, const i64 n_
       const u64 need = __ballot(active && gid < 0);
       if (need == 0) break;
       const int leader = __ffsll((long long)need) - 1;
-      if (lane_id() == leader) {
+      if (lane() == leader) {
         while (atomicCAS(L.lock, 0u, 1u) != 0u) {}
         LDS_ACQUIRE();
         const uint32_t n2 = lds_ld(L.dict_n) & 0x7FFFFFFFu;
@@ -475,11 +446,11 @@ __device__ __forceinline__ void k_agg_tiny_body(const DevProgram P, const i64 n_
   constexpr int PU = GPUQ_PIPE_ROWS;
   const i64 nsteps = (nwords + PU - 1) / PU;
   const i64 tstride = (i64)gridDim.x * WAVES;
-  i64 t = (i64)blockIdx.x * WAVES + wave_id();
+  i64 t = (i64)blockIdx.x * WAVES + wave();
   // Rows past the end are clamped to the last row (loaded, evaluated, never accumulated): unconditional loads keep the
   // stages free of exec-masked regions, which lets the compiler leave them in flight.
   const i64 last = n - 1;
-  auto row_of = [&](i64 step, int u) { return ((step * PU + u) << 6) + lane_id(); };
+  auto row_of = [&](i64 step, int u) { return ((step * PU + u) << 6) + lane(); };
   JitRaw raws[2][PU]; JitPre pres[2][PU];
 #pragma unroll
   for (int u = 0; u < PU; ++u) {
@@ -523,8 +494,8 @@ __device__ __forceinline__ void k_agg_tiny_body(const DevProgram P, const i64 n_
   }
 pipeline_done:
 #else
-  for (i64 w = (i64)blockIdx.x * WAVES + wave_id(); w < nwords; w += (i64)gridDim.x * WAVES) {
-    const i64 pos = (w << 6) + lane_id();
+  for (i64 w = (i64)blockIdx.x * WAVES + wave(); w < nwords; w += (i64)gridDim.x * WAVES) {
+    const i64 pos = (w << 6) + lane();
     bool active = pos < n;
     GPUQ_REGS_DECL;
     if (active) active = GPUQ_EVAL(MAXC, P, pos);
@@ -554,7 +525,7 @@ pipeline_done:
       const u64 olo = __shfl_xor(lo, off), ohi = __shfl_xor(hi, off);
       acc_combine(kind, lo, hi, olo, ohi);      // lanes combine in a fixed butterfly order -> float sums are bitwise reproducible run to run
     }
-    if (lane_id() == 0) { red[wave_id() * 2] = lo; red[wave_id() * 2 + 1] = hi; }
+    if (lane() == 0) { red[wave() * 2] = lo; red[wave() * 2 + 1] = hi; }
     __syncthreads();
     if (tid == 0) {
       u64 rlo = red[0], rhi = red[1];
@@ -710,13 +681,13 @@ __global__ void __launch_bounds__(BLOCK) k_agg_emit(const AggOut raw, const int 
   if (ng_dev) { const uint32_t nd = *ng_dev; if (nd < ng) ng = nd; }
   const int kstride = n_keys > 0 ? n_keys : 1;
   const uint32_t nwords = (ng + 63) >> 6;
-  for (uint32_t w = blockIdx.x * WAVES + wave_id(); w < nwords; w += gridDim.x * WAVES) {
-    const uint32_t g = (w << 6) + lane_id();
+  for (uint32_t w = blockIdx.x * WAVES + wave(); w < nwords; w += gridDim.x * WAVES) {
+    const uint32_t g = (w << 6) + lane();
     const bool active = g < ng;
     const uint32_t kn = active ? raw.key_nulls[g] : 0u;
     for (int k = 0; k < n_keys; ++k) {
       const bool valid = active && !((kn >> k) & 1);
-      if (soa.key_valid[k]) { const u64 m = __ballot(valid); if (lane_id() == 0) soa.key_valid[k][w] = m; }
+      if (soa.key_valid[k]) { const u64 m = __ballot(valid); if (lane() == 0) soa.key_valid[k][w] = m; }
       if (active) soa.key_col[k][g] = make_ulonglong2(raw.keys[((size_t)g * kstride + k) * 2], raw.keys[((size_t)g * kstride + k) * 2 + 1]);
     }
     for (int a = 0; a < n_accs; ++a)
@@ -754,8 +725,8 @@ __global__ void __launch_bounds__(BLOCK) k_unpack_bytes(const ulonglong2* __rest
 __global__ void __launch_bounds__(BLOCK) k_take_utf8_lengths(const int32_t* __restrict__ offsets, const uint8_t* __restrict__ validity, const uint32_t* __restrict__ idx,
                                                              const i64 n, int32_t* __restrict__ lens, u64* __restrict__ valid_out) {
   const i64 nwords = (n + 63) >> 6;
-  for (i64 w = (i64)blockIdx.x * WAVES + wave_id(); w < nwords; w += (i64)gridDim.x * WAVES) {
-    const i64 j = (w << 6) + lane_id();
+  for (i64 w = (i64)blockIdx.x * WAVES + wave(); w < nwords; w += (i64)gridDim.x * WAVES) {
+    const i64 j = (w << 6) + lane();
     bool ok = false; int32_t len = 0;
     if (j < n) {
       const uint32_t r = idx ? idx[j] : (uint32_t)j;
@@ -764,18 +735,18 @@ __global__ void __launch_bounds__(BLOCK) k_take_utf8_lengths(const int32_t* __re
       lens[j] = len;
     }
     const u64 m = __ballot(ok);
-    if (valid_out && lane_id() == 0) valid_out[w] = m;
+    if (valid_out && lane() == 0) valid_out[w] = m;
   }
 }
 // one wave per output string: lanes copy 64 bytes per step (long strings stay coalesced, short ones cost one step)
 __global__ void __launch_bounds__(BLOCK) k_take_utf8_bytes(const uint8_t* __restrict__ data, const int32_t* __restrict__ offsets, const uint32_t* __restrict__ idx,
                                                            const i64 n, const int32_t* __restrict__ out_offsets, uint8_t* __restrict__ out) {
-  for (i64 j = (i64)blockIdx.x * WAVES + wave_id(); j < n; j += (i64)gridDim.x * WAVES) {
+  for (i64 j = (i64)blockIdx.x * WAVES + wave(); j < n; j += (i64)gridDim.x * WAVES) {
     const int32_t o0 = out_offsets[j], len = out_offsets[j + 1] - o0;
     if (len <= 0) continue;
     const uint32_t r = idx ? idx[j] : (uint32_t)j;
     const uint8_t* src = data + offsets[r];
-    for (int32_t k = lane_id(); k < len; k += 64) out[o0 + k] = src[k];
+    for (int32_t k = lane(); k < len; k += 64) out[o0 + k] = src[k];
   }
 }
 // short strings (names, flags: a few bytes each): one lane per string -- a whole wave per 8-byte string leaves 56 lanes idle
@@ -800,25 +771,13 @@ __global__ void __launch_bounds__(BLOCK) k_scan_tile_sums(const int32_t* __restr
   const i64 base = (i64)blockIdx.x * SCAN_TILE;
   u64 s = 0;
   for (int k = threadIdx.x; k < SCAN_TILE; k += BLOCK) if (base + k < n) s += (u64)(uint32_t)d[base + k];
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-  if (lane_id() == 0) ws[wave_id()] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) { u64 t = 0; for (int k = 0; k < WAVES; ++k) t += ws[k]; tile_sums[blockIdx.x] = t; }
+  const u64 t = block_sum<WAVES>(s, ws);
+  if (threadIdx.x == 0) tile_sums[blockIdx.x] = t;
 }
 #endif
 #ifndef GPUQ_JIT
 __global__ void __launch_bounds__(1024) k_scan_tiles_serial(u64* __restrict__ tile_sums, const i64 ntiles) {
-  // one block; thread-strided sequential chunks then a serial fix-up over <=1024 partials
-  __shared__ u64 part[1024];
-  const int t = threadIdx.x;
-  const i64 per = (ntiles + 1023) / 1024;
-  const i64 a = (i64)t * per; i64 b = a + per; if (b > ntiles) b = ntiles;
-  u64 s = 0; for (i64 i = a; i < b; ++i) s += tile_sums[i];
-  part[t] = s; __syncthreads();
-  if (t == 0) { const int lim = (int)((ntiles + per - 1) / per); u64 run = 0; for (int k = 0; k < lim; ++k) { const u64 v = part[k]; part[k] = run; run += v; } }   // chunks past lim are empty
-  __syncthreads();
-  u64 run = part[t];
-  for (i64 i = a; i < b; ++i) { const u64 v = tile_sums[i]; tile_sums[i] = run; run += v; }
+  block_walk_scan<SumOp>(ntiles, (u64)0, [&](const i64 i) { return tile_sums[i]; }, [&](const i64 i, const u64 before) { tile_sums[i] = before; }, (u64*)nullptr);
 }
 #endif
 #ifndef GPUQ_JIT
@@ -829,12 +788,7 @@ __global__ void __launch_bounds__(BLOCK) k_scan_downsweep(int32_t* __restrict__ 
   int32_t v[PER]; u64 local = 0;
 #pragma unroll
   for (int k = 0; k < PER; ++k) { const i64 i = base + (i64)threadIdx.x * PER + k; v[k] = (i < n) ? d[i] : 0; local += (u64)(uint32_t)v[k]; }
-  u64 x = local;
-  for (int off = 1; off < 64; off <<= 1) { const u64 y = __shfl_up(x, off); if (lane_id() >= off) x += y; }
-  if (lane_id() == 63) ws[wave_id()] = x;
-  __syncthreads();
-  u64 wbase = 0; for (int k = 0; k < wave_id(); ++k) wbase += ws[k];
-  u64 run = tile_offsets[blockIdx.x] + wbase + x - local;
+  u64 run = tile_offsets[blockIdx.x] + block_excl_scan<WAVES>(local, ws);
 #pragma unroll
   for (int k = 0; k < PER; ++k) { const i64 i = base + (i64)threadIdx.x * PER + k; if (i <= n) { if (i < n) d[i] = (int32_t)run; else d[i] = (int32_t)run; } run += (u64)(uint32_t)v[k]; }
 }
@@ -845,14 +799,14 @@ __global__ void __launch_bounds__(BLOCK) k_scan_downsweep(int32_t* __restrict__ 
 static int g_num_cus = 256;
 void set_num_cus(int n) { if (n > 0) g_num_cus = n; }
 int num_cus() { return g_num_cus; }
-
-static int grid_for(i64 n, int blocks_per_cu) {
+int grid_for_words(i64 n, int waves_per_block, int blocks_per_cu) {
   const i64 nwords = (n + 63) >> 6;
-  i64 need = (nwords + WAVES - 1) / WAVES;
-  i64 cap = (i64)g_num_cus * blocks_per_cu;
+  i64 need = (nwords + waves_per_block - 1) / waves_per_block;
+  const i64 cap = (i64)g_num_cus * blocks_per_cu;
   if (need < 1) need = 1;
   return (int)(need < cap ? need : cap);
 }
+static int grid_for(i64 n, int blocks_per_cu) { return grid_for_words(n, WAVES, blocks_per_cu); }
 
 void launch_filter_bitmap(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, u64* bitmap, uint32_t* block_counts, int nblocks, i64 wpb) {
   launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_filter_bitmap), dim3(nblocks), dim3(BLOCK), 0, s, P, n, bitmap, block_counts, wpb);
@@ -931,7 +885,7 @@ void launch_agg_emit(hipStream_t s, const AggOut& raw, int n_keys, int n_accs, u
   uint32_t grid = (nwords + WAVES - 1) / WAVES; if (grid > (uint32_t)g_num_cus * 8) grid = g_num_cus * 8;
   hipLaunchKernelGGL(k_agg_emit, dim3(grid), dim3(BLOCK), 0, s, raw, n_keys, n_accs, n_groups, soa, n_groups_dev);
 }
-static int lin_grid(i64 n) { i64 need = (n + BLOCK - 1) / BLOCK; if (need < 1) need = 1; const i64 cap = (i64)g_num_cus * 16; return (int)(need < cap ? need : cap); }
+static int lin_grid(i64 n) { return grid_for(n, 16); }      // one row per thread: ceil(ceil(n / 64) / WAVES) == ceil(n / BLOCK)
 void launch_unpack_utf8_lengths(hipStream_t s, const ulonglong2* packed, i64 n, int32_t* lens_out, uint32_t* too_long) {
   if (n > 0) hipLaunchKernelGGL(k_unpack_lengths, dim3(lin_grid(n)), dim3(BLOCK), 0, s, packed, n, lens_out, too_long);
 }
@@ -1077,8 +1031,8 @@ __global__ void __launch_bounds__(BLOCK) k_like_utf8(const uint8_t* __restrict__
   for (int i = (int)threadIdx.x; i < pat.n; i += BLOCK) tok[i] = pat.tok[i];
   __syncthreads();
   const i64 words = (n + 63) >> 6;
-  for (i64 w = (i64)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); w < words; w += (i64)gridDim.x * (BLOCK / 64)) {
-    const i64 i = w * 64 + (threadIdx.x & 63);
+  for (i64 w = (i64)blockIdx.x * (BLOCK / 64) + wave(); w < words; w += (i64)gridDim.x * (BLOCK / 64)) {
+    const i64 i = w * 64 + lane();
     bool valid = false, m = false;
     if (i < n) {
       const uint32_t r = idx ? idx[i] : (uint32_t)i;
@@ -1104,7 +1058,7 @@ __global__ void __launch_bounds__(BLOCK) k_like_utf8(const uint8_t* __restrict__
       }
     }
     const u64 mb = __ballot(valid && m), vb = __ballot(valid);
-    if ((threadIdx.x & 63) == 0) { bits_out[w] = mb; if (valid_out) valid_out[w] = vb; }
+    if (lane() == 0) { bits_out[w] = mb; if (valid_out) valid_out[w] = vb; }
   }
 }
 void launch_like_utf8(hipStream_t s, const uint8_t* data, const int32_t* offsets, const uint8_t* validity, const uint32_t* idx, i64 n, const LikePattern& pat, int negated,
@@ -1118,8 +1072,8 @@ void launch_like_utf8(hipStream_t s, const uint8_t* data, const int32_t* offsets
 struct Utf8Side { const uint8_t* data; const int32_t* offsets; const uint8_t* validity; const uint32_t* idx; };
 __global__ void __launch_bounds__(BLOCK) k_utf8_compare(const Utf8Side A, const Utf8Side B, const int32_t blen, const i64 n, const int op, u64* __restrict__ bits_out, u64* __restrict__ valid_out) {
   const i64 words = (n + 63) >> 6;
-  for (i64 w = (i64)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); w < words; w += (i64)gridDim.x * (BLOCK / 64)) {
-    const i64 i = w * 64 + (threadIdx.x & 63);
+  for (i64 w = (i64)blockIdx.x * (BLOCK / 64) + wave(); w < words; w += (i64)gridDim.x * (BLOCK / 64)) {
+    const i64 i = w * 64 + lane();
     bool valid = false, m = false;
     if (i < n) {
       const uint32_t ra = A.idx ? A.idx[i] : (uint32_t)i;
@@ -1144,7 +1098,7 @@ __global__ void __launch_bounds__(BLOCK) k_utf8_compare(const Utf8Side A, const 
       }
     }
     const u64 mb = __ballot(valid && m), vb = __ballot(valid);
-    if ((threadIdx.x & 63) == 0) { bits_out[w] = mb; if (valid_out) valid_out[w] = vb; }
+    if (lane() == 0) { bits_out[w] = mb; if (valid_out) valid_out[w] = vb; }
   }
 }
 void launch_utf8_compare(hipStream_t s, const uint8_t* adata, const int32_t* aoffs, const uint8_t* avalid, const uint32_t* aidx, const uint8_t* bdata, const int32_t* boffs,
@@ -1176,8 +1130,8 @@ __global__ void __launch_bounds__(BLOCK) k_utf8_max_len(const int32_t* __restric
     const int32_t len = offsets[r + 1] - offsets[r];
     m = len > m ? len : m;
   }
-  for (int o = 32; o > 0; o >>= 1) { const int32_t y = __shfl_xor(m, o); m = y > m ? y : m; }
-  if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(out, m);
+  m = wave_max(m);
+  if (lane() == 0 && m > 0) atomicMax(out, m);
 }
 // codes[i] = dictionary code of row i (through idx), valid bit i = the row has a code (not NULL; for lookups: the string is in the dictionary)
 __global__ void __launch_bounds__(BLOCK) k_utf8_intern(const uint8_t* __restrict__ ddata, const int32_t* __restrict__ doffs,
@@ -1185,7 +1139,7 @@ __global__ void __launch_bounds__(BLOCK) k_utf8_intern(const uint8_t* __restrict
                                                        const uint32_t* __restrict__ idx, const i64 n, u64* __restrict__ table, const u64 mask, const int insert,
                                                        i64* __restrict__ codes, u64* __restrict__ valid_out, uint32_t* __restrict__ flags) {
   for (i64 i0 = (i64)blockIdx.x * BLOCK + (threadIdx.x & ~63); i0 < n; i0 += (i64)gridDim.x * BLOCK) {
-    const i64 i = i0 + (threadIdx.x & 63);
+    const i64 i = i0 + lane();
     bool has = false; i64 code = 0;
     if (i < n) {
       const uint32_t r = idx ? idx[i] : (uint32_t)i;
@@ -1217,7 +1171,7 @@ __global__ void __launch_bounds__(BLOCK) k_utf8_intern(const uint8_t* __restrict
       codes[i] = code;
     }
     const u64 m = __ballot(has);
-    if ((threadIdx.x & 63) == 0 && valid_out) valid_out[i0 >> 6] = m;
+    if (lane() == 0 && valid_out) valid_out[i0 >> 6] = m;
   }
 }
 // codes (Int64 + validity) -> row ids for a take: NULL -> 0xFFFFFFFF
@@ -1235,7 +1189,7 @@ void launch_utf8_code_rows(hipStream_t s, const void* codes, int width, const ui
 __global__ void __launch_bounds__(BLOCK) k_utf8_sort_piece(const uint8_t* __restrict__ data, const int32_t* __restrict__ offsets, const uint8_t* __restrict__ validity,
                                                            const uint32_t* __restrict__ idx, const i64 n, const int piece, ulonglong2* __restrict__ out, u64* __restrict__ valid_out) {
   for (i64 i0 = (i64)blockIdx.x * BLOCK + (threadIdx.x & ~63); i0 < n; i0 += (i64)gridDim.x * BLOCK) {
-    const i64 i = i0 + (threadIdx.x & 63);
+    const i64 i = i0 + lane();
     bool has = false; u64 lo = 0, hi = 0;
     if (i < n) {
       const uint32_t r = idx ? idx[i] : (uint32_t)i;
@@ -1253,7 +1207,7 @@ __global__ void __launch_bounds__(BLOCK) k_utf8_sort_piece(const uint8_t* __rest
       }
     }
     const u64 vm = __ballot(has);
-    if (valid_out && (threadIdx.x & 63) == 0) valid_out[i0 >> 6] = vm;
+    if (valid_out && lane() == 0) valid_out[i0 >> 6] = vm;
     if (i < n) out[i] = make_ulonglong2(lo, hi);
   }
 }

@@ -11,8 +11,6 @@ namespace gpuq {
 
 constexpr int FBLOCK = 256;
 constexpr int FWAVES = FBLOCK / 64;
-__device__ __forceinline__ int flane() { return threadIdx.x & 63; }
-__device__ __forceinline__ int fwave() { return threadIdx.x >> 6; }
 
 // ------------------------------------------------------------------ delimited text
 // 1. line ends: every block counts the '\n' bytes of its chunk; after a scan of the counts k_csv_line_starts writes the start
@@ -40,10 +38,8 @@ __global__ void __launch_bounds__(FBLOCK) k_csv_count_lines(const uint8_t* __res
   const i64 a = (i64)blockIdx.x * chunk; i64 b = a + chunk; if (b > n) b = n;
   uint32_t c = 0;
   for (i64 i = a + (i64)threadIdx.x * 16; i < b; i += FBLOCK * 16) c += (uint32_t)__popc(nl_bits16(text, i, a, b));
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-  if (flane() == 0) wc[fwave()] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) { uint32_t t = 0; for (int k = 0; k < FWAVES; ++k) t += wc[k]; counts[blockIdx.x] = t; }
+  const uint32_t t = block_sum<FWAVES>(c, wc);
+  if (threadIdx.x == 0) counts[blockIdx.x] = t;
 }
 // starts[r + 1] = offset of the byte after the r-th '\n' (starts[0] = 0 is set by the host): one wave walks the block's chunk,
 // 16 bytes per lane and step; the lanes' newline counts are prefix-summed across the wave to place each line start in order
@@ -52,11 +48,10 @@ __global__ void __launch_bounds__(64) k_csv_line_starts(const uint8_t* __restric
   const i64 a = (i64)blockIdx.x * chunk; i64 b = a + chunk; if (b > n) b = n;
   u64 out = (u64)block_offsets[blockIdx.x] + 1;
   for (i64 i0 = a; i0 < b; i0 += 64 * 16) {
-    const i64 i = i0 + (i64)flane() * 16;
+    const i64 i = i0 + (i64)lane() * 16;
     uint32_t bits = i < b ? nl_bits16(text, i, a, b) : 0u;
     const uint32_t cnt = (uint32_t)__popc(bits);
-    uint32_t incl = cnt;
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(incl, o); if (flane() >= o) incl += y; }
+    const uint32_t incl = wave_incl_scan(cnt);
     u64 at = out + (u64)(incl - cnt);
     while (bits) { const int k = __ffs((int)bits) - 1; bits &= bits - 1; starts[at++] = i + k + 1; }
     out += (u64)__shfl(incl, 63);
@@ -239,9 +234,9 @@ __global__ void __launch_bounds__(FBLOCK) k_csv_parse(const uint8_t* __restrict_
           const bool t = live && csv_word(text, p, q, "true", 4);
           if (live && !empty && !t && !csv_word(text, p, q, "false", 5)) myflags |= CSVF_BAD_NUMBER;
           const u64 m = __ballot(t);
-          if (flane() == 0 && live) ((u64*)O.data[oc])[r >> 6] = m;
+          if (lane() == 0 && live) ((u64*)O.data[oc])[r >> 6] = m;
         }
-        if (O.valid[oc]) { const u64 m = __ballot(valid); if (flane() == 0 && live) O.valid[oc][r >> 6] = m; }
+        if (O.valid[oc]) { const u64 m = __ballot(valid); if (lane() == 0 && live) O.valid[oc][r >> 6] = m; }
       }
       if (live) {
         if (q < end) p = q + 1;
@@ -296,7 +291,7 @@ __device__ __forceinline__ bool pq_hybrid(const uint8_t* p, const uint8_t* end, 
       const int take = cnt < (i64)(n - done) ? (int)cnt : n - done;
       // the values read must be there; the zero padding of a last group beyond them may be cut (old parquet-mr writers did, Arrow C++ reads it)
       if (((i64)take * bw + 7) / 8 > b.end - b.p) return false;
-      for (int i = flane(); i < take; i += 64) sink(done + i, pq_unpack(b.p, b.end, bw, (uint32_t)i));
+      for (int i = lane(); i < take; i += 64) sink(done + i, pq_unpack(b.p, b.end, bw, (uint32_t)i));
       const i64 adv = (cnt * bw + 7) / 8;
       b.p = adv < b.end - b.p ? b.p + adv : b.end; done += take;
     } else {          // run of one value, (bw + 7) / 8 bytes little-endian
@@ -308,7 +303,7 @@ __device__ __forceinline__ bool pq_hybrid(const uint8_t* p, const uint8_t* end, 
       if (v > vmax) return false;
       b.p += nb;
       const int take = cnt < (i64)(n - done) ? (int)cnt : n - done;
-      for (int i = flane(); i < take; i += 64) sink(done + i, v);
+      for (int i = lane(); i < take; i += 64) sink(done + i, v);
       done += take;
     }
   }
@@ -329,7 +324,7 @@ __global__ void __launch_bounds__(64) k_pq_decode(const uint8_t* __restrict__ fi
   const int pg = blockIdx.x;
   if (pg >= n_pages) return;
   const PqPage P = pages[pg];
-  if (P.src < 0 || P.src + P.bytes > file_bytes) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
+  if (P.src < 0 || P.src + P.bytes > file_bytes) { if (lane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
   const uint8_t* p = file + P.src; const uint8_t* end = p + P.bytes;
   uint32_t* vidx = scratch + (size_t)pg * (size_t)scratch_stride;      // row -> index among the page's non-null values
   const int n = P.n_values;
@@ -339,25 +334,25 @@ __global__ void __launch_bounds__(64) k_pq_decode(const uint8_t* __restrict__ fi
     const uint8_t* dp = p; const uint8_t* dend;
     if (P.def_v2 > 0) { dend = p + P.def_v2; p = dend; }
     else {
-      if (end - p < 4) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
+      if (end - p < 4) { if (lane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
       const uint32_t len = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
       dp = p + 4; dend = dp + len; p = dend;
     }
-    if (dend > end) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
+    if (dend > end) { if (lane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
     const bool ok = pq_hybrid(dp, dend, 1, n, 1u /* max definition level of a flat optional column */, [&](int i, uint32_t v) { vidx[i] = v; });
-    if (!ok) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
+    if (!ok) { if (lane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
     // exclusive prefix of the levels = value index; validity bits by ballot (rows of a page start at any bit: atomicOr)
     uint32_t run = 0;
     for (int i0 = 0; i0 < n; i0 += 64) {
-      const int i = i0 + flane();
+      const int i = i0 + lane();
       const uint32_t lv = i < n ? vidx[i] : 0u;
       const u64 m = __ballot(lv != 0);
       const uint32_t mine = run + lane_rank(m);
       if (i < n) vidx[i] = lv ? mine : NULL_ROW;
       if (C.valid && m) {
         const i64 bit0 = P.row0 + i0; const int sh = (int)(bit0 & 63);
-        if (flane() == 0) { atomicOr((unsigned long long*)&C.valid[bit0 >> 6], (unsigned long long)(m << sh)); if (sh) atomicOr((unsigned long long*)&C.valid[(bit0 >> 6) + 1], (unsigned long long)(m >> (64 - sh))); }
+        if (lane() == 0) { atomicOr((unsigned long long*)&C.valid[bit0 >> 6], (unsigned long long)(m << sh)); if (sh) atomicOr((unsigned long long*)&C.valid[(bit0 >> 6) + 1], (unsigned long long)(m >> (64 - sh))); }
       }
       run += (uint32_t)__popcll(m);
     }
@@ -367,14 +362,14 @@ __global__ void __launch_bounds__(64) k_pq_decode(const uint8_t* __restrict__ fi
   // ---- values
   const i64 voff = p - file;      // payload position of the values
   if (P.enc == PQE_RLE) {      // v2 pages write BOOLEAN values as a length-prefixed hybrid stream of 1-bit values
-    if (C.phys != PQ_BOOL || end - p < 4) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
+    if (C.phys != PQ_BOOL || end - p < 4) { if (lane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
     const uint32_t len = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
     p += 4;
-    if ((i64)len > end - p) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
+    if ((i64)len > end - p) { if (lane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
     uint32_t* bits = vidx + n;
-    if (!pq_hybrid(p, p + len, 1, n_present, 0xFFFFFFFFu, [&](int i, uint32_t v) { bits[i] = v; })) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
+    if (!pq_hybrid(p, p + len, 1, n_present, 0xFFFFFFFFu, [&](int i, uint32_t v) { bits[i] = v; })) { if (lane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
-    for (int i = flane(); i < n; i += 64) {
+    for (int i = lane(); i < n; i += 64) {
       const uint32_t vi = C.optional ? vidx[i] : (uint32_t)i;
       if (vi == NULL_ROW) continue;
       const i64 r = P.row0 + i;
@@ -384,17 +379,17 @@ __global__ void __launch_bounds__(64) k_pq_decode(const uint8_t* __restrict__ fi
   }
   if (P.enc == PQE_DICT) {
     // a page without a present value needs no index stream, not even the width byte (an all-NULL v2 page may end with its levels)
-    if (P.dict < 0 || (p >= end && n_present > 0)) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
+    if (P.dict < 0 || (p >= end && n_present > 0)) { if (lane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
     const PqDict D = dicts[P.dict];
     const int bw = p < end ? (int)*p++ : 0;
-    if (bw > 32) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
+    if (bw > 32) { if (lane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
     // indices of the present values, decoded into the tail of the scratch row (n_present <= n).  Width 0 (parquet-rs writes it for a
     // one-entry dictionary) is a stream like any other: runs whose values take no bytes; its headers must still announce n_present values
     uint32_t* ix = vidx + n;
     const bool ok = pq_hybrid(p, end, bw, n_present, 0xFFFFFFFFu, [&](int i, uint32_t v) { ix[i] = v; });
-    if (!ok) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
+    if (!ok) { if (lane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
-    for (int i = flane(); i < n; i += 64) {
+    for (int i = lane(); i < n; i += 64) {
       const uint32_t vi = C.optional ? vidx[i] : (uint32_t)i;
       const i64 r = P.row0 + i;
       if (vi == NULL_ROW) { if (C.phys == PQ_BYTE_ARRAY) { C.str_len[r] = 0; C.str_src[r] = -1; } continue; }
@@ -414,7 +409,7 @@ __global__ void __launch_bounds__(64) k_pq_decode(const uint8_t* __restrict__ fi
     // length-prefixed values: a serial walk (lane 0) over the page's present values records where each one starts
     i64* starts = (i64*)(vidx + n + (n & 1));      // 8-byte aligned tail of the scratch row: n_present positions
     int walk_bad = 0;
-    if (flane() == 0) {
+    if (lane() == 0) {
       const uint8_t* q = p;
       for (int i = 0; i < n_present; ++i) {
         if (end - q < 4) { walk_bad = 1; break; }
@@ -426,7 +421,7 @@ __global__ void __launch_bounds__(64) k_pq_decode(const uint8_t* __restrict__ fi
     }
     if (__shfl(walk_bad, 0)) return;      // the positions beyond the break are not written: nobody may follow them
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
-    for (int i = flane(); i < n; i += 64) {
+    for (int i = lane(); i < n; i += 64) {
       const uint32_t vi = C.optional ? vidx[i] : (uint32_t)i;
       const i64 r = P.row0 + i;
       if (vi == NULL_ROW) { C.str_len[r] = 0; C.str_src[r] = -1; continue; }
@@ -440,9 +435,9 @@ __global__ void __launch_bounds__(64) k_pq_decode(const uint8_t* __restrict__ fi
   {      // the page must hold every value its header and levels announce: nothing below reads past `end`
     const i64 have = end - p;
     const i64 need = C.phys == PQ_BOOL ? ((i64)n_present + 7) / 8 : (i64)n_present * ((C.phys == PQ_I32 || C.phys == PQ_F32) ? 4 : (C.phys == PQ_FLBA ? C.flba_len : (C.phys == PQ_I96 ? 12 : 8)));
-    if (need > have) { if (flane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
+    if (need > have) { if (lane() == 0) atomicOr(flags, PQF_MALFORMED); return; }
   }
-  for (int i = flane(); i < n; i += 64) {
+  for (int i = lane(); i < n; i += 64) {
     const uint32_t vi = C.optional ? vidx[i] : (uint32_t)i;
     if (vi == NULL_ROW) continue;
     const i64 r = P.row0 + i;

@@ -120,7 +120,7 @@ __global__ void __launch_bounds__(SEG_BLOCK) k_segment_median(const void* __rest
   }
   // 64 consecutive segments are one wave: their validity bits are one word, written whole by one lane
   const u64 word = __ballot(has);
-  if ((threadIdx.x & 63) == 0 && s < n_groups) out_valid[s >> 6] = word;
+  if (lane() == 0 && s < n_groups) out_valid[s >> 6] = word;
 }
 }  // namespace
 

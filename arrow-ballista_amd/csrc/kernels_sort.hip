@@ -19,9 +19,6 @@ constexpr int SBLOCK = 256;
 constexpr int SWAVES = SBLOCK / 64;
 constexpr int RADIX = 256;
 
-__device__ __forceinline__ int slane() { return threadIdx.x & 63; }
-__device__ __forceinline__ int swave() { return threadIdx.x >> 6; }
-
 // ordered 128-bit view of a key register: signed integers as is; f64 through the total-order map;
 // packed strings with the top bit flipped so that signed compare == bytewise compare
 __device__ __forceinline__ i128 sort_view(u64 lo, u64 hi, int kind) {
@@ -57,7 +54,7 @@ __device__ __forceinline__ void mm_reduce_store(MinMax& m, int k, u64 (*red)[MAX
     if (omx > mk128(m.mx_lo, m.mx_hi)) { m.mx_lo = (u64)omx; m.mx_hi = (u64)((u128)omx >> 64); }
     { const uint32_t of = __shfl_xor(m.fl, off); const uint32_t ml = (of & 0xFF00u) > (m.fl & 0xFF00u) ? (of & 0xFF00u) : (m.fl & 0xFF00u); m.fl = ((m.fl | of) & 0xFFu) | ml; }
   }
-  if (slane() == 0) { red[swave()][k][0] = m.mn_lo; red[swave()][k][1] = m.mn_hi; red[swave()][k][2] = m.mx_lo; red[swave()][k][3] = m.mx_hi; red[swave()][k][4] = m.fl; }
+  if (lane() == 0) { red[wave()][k][0] = m.mn_lo; red[wave()][k][1] = m.mn_hi; red[wave()][k][2] = m.mx_lo; red[wave()][k][3] = m.mx_hi; red[wave()][k][4] = m.fl; }
 }
 template <int MAXC>
 __device__ __forceinline__ void k_sort_minmax_body(const DevProgram P, const i64 n_arg, const SortSpec S, u64* __restrict__ out, const i64 wstep) {
@@ -67,9 +64,9 @@ __device__ __forceinline__ void k_sort_minmax_body(const DevProgram P, const i64
   mm_init(m0); mm_init(m1); mm_init(m2); mm_init(m3);
   const i64 nw_all = (n + 63) >> 6;
   const i64 nwords = wstep > 1 ? (nw_all + wstep - 1) / wstep + 1 : nw_all;      // wstep > 1: a strided sample of 64-row words + the last word
-  for (i64 w = (i64)blockIdx.x * SWAVES + swave(); w < nwords; w += (i64)gridDim.x * SWAVES) {
+  for (i64 w = (i64)blockIdx.x * SWAVES + wave(); w < nwords; w += (i64)gridDim.x * SWAVES) {
     const i64 wi = w * wstep < nw_all ? w * wstep : nw_all - 1;
-    const i64 pos = (wi << 6) + slane();
+    const i64 pos = (wi << 6) + lane();
     if (pos >= n) continue;
     GPUQ_REGS_DECL;
     (void)GPUQ_EVAL(MAXC, P, pos);
@@ -116,8 +113,8 @@ __device__ __forceinline__ void k_sort_pack_body(const DevProgram P, const i64 n
   // (taking two or four 64-row words per wave and step with all their column loads issued first, as the join and aggregate kernels
   // do, was measured here and changes nothing: 2.74 / 2.80 / 2.77 ms per sort of 2^27 rows with 1 / 2 / 4 words)
   const i64 nwords = (n + 63) >> 6;
-  for (i64 w = (i64)blockIdx.x * SWAVES + swave(); w < nwords; w += (i64)gridDim.x * SWAVES) {
-    const i64 pos = (w << 6) + slane();
+  for (i64 w = (i64)blockIdx.x * SWAVES + wave(); w < nwords; w += (i64)gridDim.x * SWAVES) {
+    const i64 pos = (w << 6) + lane();
     if (pos >= n) continue;
     const bool real = pos < n_real;
     GPUQ_REGS_DECL;
@@ -150,7 +147,7 @@ __device__ __forceinline__ void k_sort_pack_body(const DevProgram P, const i64 n
       for (int p = 0; p < hist_passes; ++p) {
         const uint32_t d = (uint32_t)(comp >> (8 * p)) & 0xFFu;
         const uint32_t d0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)d);
-        if (__ballot(d == d0) == live) { if (slane() == (int)__builtin_ctzll(live)) atomicAdd(&h0[p][d0], (uint32_t)__popcll(live)); }
+        if (__ballot(d == d0) == live) { if (lane() == (int)__builtin_ctzll(live)) atomicAdd(&h0[p][d0], (uint32_t)__popcll(live)); }
         else atomicAdd(&h0[p][d], 1u);
       }
     }
@@ -259,8 +256,8 @@ __device__ __forceinline__ void k_part_pid_body(const DevProgram P, const i64 n_
                                                      u64* __restrict__ pid_out, uint32_t* __restrict__ ids) {
   const i64 n = rows_of(P, n_arg);      // deferred execution: the row count is a device word, n_arg its host-side bound
   const i64 nwords = (n + 63) >> 6;
-  for (i64 w = (i64)blockIdx.x * SWAVES + swave(); w < nwords; w += (i64)gridDim.x * SWAVES) {
-    const i64 pos = (w << 6) + slane();
+  for (i64 w = (i64)blockIdx.x * SWAVES + wave(); w < nwords; w += (i64)gridDim.x * SWAVES) {
+    const i64 pos = (w << 6) + lane();
     if (pos >= n) continue;
     GPUQ_REGS_DECL;
     (void)GPUQ_EVAL(MAXC, P, pos);
@@ -304,16 +301,7 @@ __global__ void __launch_bounds__(SBLOCK) k_pid_count(const u64* __restrict__ pi
 #endif
 #ifndef GPUQ_JIT
 __global__ void __launch_bounds__(1024) k_part_scan(const uint32_t* __restrict__ counts, const uint32_t np, u64* __restrict__ offsets) {
-  __shared__ u64 part[1024];
-  const int t = threadIdx.x;
-  const uint32_t per = (np + 1023) / 1024;
-  const uint32_t a = t * per; uint32_t b = a + per; if (b > np) b = np;
-  u64 s = 0; for (uint32_t i = a; i < b; ++i) s += counts[i];
-  part[t] = s; __syncthreads();
-  if (t == 0) { u64 run = 0; for (int k = 0; k < 1024; ++k) { const u64 v = part[k]; part[k] = run; run += v; } offsets[np] = run; }
-  __syncthreads();
-  u64 run = part[t];
-  for (uint32_t i = a; i < b; ++i) { offsets[i] = run; run += counts[i]; }
+  block_walk_scan<SumOp>(np, (u64)0, [&](const uint32_t i) { return (u64)counts[i]; }, [&](const uint32_t i, const u64 before) { offsets[i] = before; }, offsets + np);
 }
 #endif
 
@@ -354,13 +342,7 @@ __global__ void __launch_bounds__(SBLOCK) k_radix_ghist(const u64* __restrict__ 
 __global__ void __launch_bounds__(RADIX) k_radix_ghist_scan(u64* __restrict__ ghist) {
   __shared__ u64 ws[RADIX / 64];
   u64* h = ghist + (size_t)blockIdx.x * RADIX;
-  const int t = threadIdx.x, l = t & 63;
-  const u64 c = h[t]; u64 x = c;
-  for (int off = 1; off < 64; off <<= 1) { const u64 y = __shfl_up(x, off); if (l >= off) x += y; }
-  if (l == 63) ws[t >> 6] = x;
-  __syncthreads();
-  u64 pre = 0; for (int q = 0; q < (t >> 6); ++q) pre += ws[q];
-  h[t] = pre + x - c;
+  h[threadIdx.x] = block_excl_scan<RADIX / 64>(h[threadIdx.x], ws);
 }
 // OROUNDS keys per thread: the tile is SBLOCK * OROUNDS records.  Longer tiles mean longer runs per digit in the write-out and fewer
 // barriers / look-back words per key (measured on 2^27 packed records: 2048-record tiles 1.2 ms per pass, 4096: 0.75, 8192: 0.63); the
@@ -376,7 +358,7 @@ __global__ void __launch_bounds__(SBLOCK) k_onesweep(const u64* __restrict__ key
   __shared__ u64 gbase[RADIX];
   __shared__ uint32_t wsum[SWAVES];
   __shared__ uint32_t s_tile;
-  const int t = threadIdx.x, w = swave(), l = slane();
+  const int t = threadIdx.x, w = wave(), l = lane();
   const u64 lt = (1ull << l) - 1;
   if (t == 0) s_tile = atomicAdd(ticket, 1u);
   for (int i = t; i < SWAVES * RADIX; i += SBLOCK) (&wcnt[0][0])[i] = 0;
@@ -427,15 +409,7 @@ __global__ void __launch_bounds__(SBLOCK) k_onesweep(const u64* __restrict__ key
 #pragma unroll
     for (int q = 0; q < SWAVES; ++q) { c[q] = wcnt[q][t]; tot += c[q]; }
     __hip_atomic_store(&look[(size_t)T * RADIX + t], (T == 0 ? LB_PREFIX : LB_AGG) | (u64)tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint32_t x = tot;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const uint32_t y = __shfl_up(x, off); if (l >= off) x += y; }
-    if (l == 63) wsum[w] = x;
-    __syncthreads();
-    uint32_t pre = 0;
-#pragma unroll
-    for (int q = 0; q < SWAVES; ++q) if (q < w) pre += wsum[q];
-    const uint32_t ds = pre + x - tot;
+    const uint32_t ds = block_excl_scan<SWAVES>(tot, wsum);
     dstart[t] = ds;
     uint32_t run = ds;
 #pragma unroll
@@ -585,12 +559,7 @@ __global__ void __launch_bounds__(SBLOCK) k_merge_pairs(const u64* __restrict__ 
 #endif
 
 // ------------------------------------------------------------------ launchers
-static int sgrid(i64 n, int blocks_per_cu) {
-  const i64 nwords = (n + 63) >> 6;
-  i64 need = (nwords + SWAVES - 1) / SWAVES; if (need < 1) need = 1;
-  const i64 cap = (i64)num_cus() * blocks_per_cu;
-  return (int)(need < cap ? need : cap);
-}
+static int sgrid(i64 n, int blocks_per_cu) { return grid_for_words(n, SWAVES, blocks_per_cu); }
 int sort_minmax_blocks(i64 n) { return sgrid(n, 4); }
 void launch_sort_minmax(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const SortSpec& S, u64* out, int nblocks, i64 wstep) {
   if (wstep < 1) wstep = 1;
@@ -685,8 +654,8 @@ __global__ void __launch_bounds__(SBLOCK) k_sort_decode(const u64* __restrict__ 
   const i64 nwords = (n + 63) >> 6;
   const i128 base = mk128(K.base_lo[0], K.base_hi[0]);
   const u64 vmask = K.vbits[0] >= 64 ? ~0ull : ((1ull << K.vbits[0]) - 1);
-  for (i64 w = (i64)blockIdx.x * SWAVES + swave(); w < nwords; w += (i64)gridDim.x * SWAVES) {
-    const i64 i = (w << 6) + slane();
+  for (i64 w = (i64)blockIdx.x * SWAVES + wave(); w < nwords; w += (i64)gridDim.x * SWAVES) {
+    const i64 i = (w << 6) + lane();
     bool valid = false;
     if (i < n) {
       const u64 comp = recs[i] >> rec_shift;
@@ -703,7 +672,7 @@ __global__ void __launch_bounds__(SBLOCK) k_sort_decode(const u64* __restrict__ 
         default: ((ulonglong2*)out)[i] = make_ulonglong2((u64)v, (u64)((u128)v >> 64)); break;
       }
     }
-    if (valid_out) { const u64 vb = __ballot(valid); if (slane() == 0) valid_out[w] = vb; }
+    if (valid_out) { const u64 vb = __ballot(valid); if (lane() == 0) valid_out[w] = vb; }
   }
 }
 void launch_sort_decode(hipStream_t s, const u64* recs, int rec_shift, i64 n, const SortPack& K, int desc, int nulls_first, int width, void* out, u64* valid_out) {

@@ -137,6 +137,46 @@ def test_keys_out_of_order_fall_back_in_the_same_call(tc, name, key_type):
         assert p.exec_stats()["retries"] == 0 and agg_path(p) == "table"
 
 
+# The order test across segments (k_agg_runs_order) is a one-block running maximum over the segments (csrc/gpuq_dev.h block_walk_scan):
+# every wave owns ((segments + 15) / 16 rounded up to 64) of them and walks them 64 at a time.  A segment is one wave's two 64-row words
+# (csrc/kernels_hash.hip agg_runs_geometry, while the input has at most 2 * 32 words per compute unit), so `segs` segments are
+# 128 * segs rows less a ragged tail.  Only a segment's FIRST head is left to that kernel (the count kernel has tested the others inside
+# the segment), so the out-of-order key goes to the first row of a segment.
+def seg_keys(tc, segs, bad_seg=None):
+    import torch
+    n = 128 * segs - 5
+    assert (n + 63) // 64 <= torch.cuda.get_device_properties(tc.device).multi_processor_count * 32 * 2
+    keys = np.arange(n) * 3 + 1
+    if bad_seg is not None:
+        keys[128 * bad_seg] = keys[128 * bad_seg - 2] + 1      # a key of its own, below the last key of the segment before
+    return keys
+
+
+def wave_range_start(segs):
+    """the first segment of a wave's range, the middle one of the ranges that start inside (0, segs); None when wave 0 owns them all"""
+    per = ((segs + 15) // 16 + 63) & ~63
+    starts = list(range(per, segs, per))
+    return starts[len(starts) // 2] if starts else None
+
+
+@pytest.mark.parametrize("segs", [64, 65, 1024, 1025])
+def test_segment_counts_at_the_order_scan_edges_in_order(tc, segs):
+    p, exp = check(tc, table(seg_keys(tc, segs), seed=segs), "runs")
+    assert len(exp) == 128 * segs - 5 and agg_path(p) == "runs"
+
+
+@pytest.mark.parametrize("where", ["first_of_a_wave_range", "last_segment"])
+@pytest.mark.parametrize("segs", [64, 65, 1024, 1025])
+def test_one_head_out_of_order_at_the_order_scan_edges(tc, segs, where):
+    """the flag is raised and the table takes over inside the same call (check: the result equals the oracle's, no retry booked).
+    64 segments are wave 0's alone: no other wave range starts there, so that case puts the head into the last segment of the
+    one 64-item step both times."""
+    bad = wave_range_start(segs) if where == "first_of_a_wave_range" else segs - 1
+    assert (bad is None) == (segs == 64 and where == "first_of_a_wave_range")
+    p, exp = check(tc, table(seg_keys(tc, segs, segs - 1 if bad is None else bad), seed=segs), "runs")
+    assert len(exp) == 128 * segs - 5 and agg_path(p) == "table"
+
+
 def test_null_arguments_and_a_null_key_run(tc):
     """NULL arguments inside runs (SUM and COUNT(v) skip them; a run of only NULLs sums to NULL); a nullable key with one NULL run -- its
     packed form lies above every value, so as the last run it keeps the order and in the middle it breaks it: right either way."""

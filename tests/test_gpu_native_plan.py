@@ -253,6 +253,26 @@ def test_long_strings_travel_as_payload(tc):
     assert native_rows(tc, fan)[0] == want
 
 
+@pytest.mark.parametrize("n", [1, 2047, 2048, 2049, 2048 * 1024 + 5])
+def test_taken_utf8_offsets_are_the_prefix_sums_of_the_lengths(tc, mirror_layer, n):
+    """gpuq_take_utf8 scans the taken rows' lengths into offsets over tiles of 2048 entries, n + 1 of them (csrc/kernels_scan.hip
+    launch_exclusive_scan_i32): one tile, a tile that the end offset alone spills from, and more than 1024 tiles, which the one-block
+    scan of the tile sums walks in two steps per wave.  Strings of 0..3 bytes; offsets against numpy's cumsum, exactly."""
+    r = np.random.default_rng(n)
+    lens = r.integers(0, 4, n + 1).astype(np.int32)      # (one row more than is taken: a filter that keeps every row hands on no view)
+    all_offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    offs = all_offs[:n + 1]
+    data = np.frombuffer(b"abcdefghijklmnopqrstuvwxyz" * (int(all_offs[-1]) // 26 + 1), dtype=np.uint8)[:int(all_offs[-1])]
+    s_col = pa.StringArray.from_buffers(n + 1, pa.py_buffer(all_offs.tobytes()), pa.py_buffer(data.tobytes()))
+    t = pa.table({"s": s_col, "v": pa.array(np.arange(n + 1, dtype=np.int64))})
+    src = g.MemoryExec([t])
+    view = g.FilterExec(binary(col("v", src.schema()), Op.Lt, lit(n)), src).execute(0, tc)      # the first n rows, through an index vector
+    assert view.is_view() and view.num_rows == n
+    out = g.plan.materialize(tc, view).column("s")
+    assert np.array_equal(out.offsets[:n + 1].cpu().numpy(), offs)
+    assert bytes(out.data[:int(offs[-1])].cpu().numpy()) == data[:int(offs[-1])].tobytes()
+
+
 def test_native_stage_driver_writes_and_reads_shuffle_files(tc, tmp_path):
     """The stage driver in the native executor: ShuffleWriterExec root (hash repartition + device LZ4 + IPC files in the
     reference's path layout, result batch = partition / path / num_rows / num_batches / num_bytes as shuffle_writer.rs:470-520)

@@ -98,6 +98,65 @@ def test_filter_exec(tc, n, nulls):
         close_rows(got, exp)        # order preserved: FilterExec keeps input order
 
 
+def device_cus(tc):
+    import torch
+    return torch.cuda.get_device_properties(tc.device).multi_processor_count
+
+
+def half_with_edges(seed, n, edges):
+    """0/1 per row, about half of them 1; of an input of more than two blocks the first and the last 1024 rows (one block of the
+    selection, one segment of the unique-key probe) all 0 / all 1 as `edges` says"""
+    x = np.random.default_rng(seed).integers(0, 2, n)
+    if n > 2048:
+        x[:1024], x[-1024:] = edges
+    return x
+
+
+# Sizes at which the one-block scan of the per-block counts (csrc/gpuq_dev.h block_walk_scan under k_scan_counts) can go wrong: every
+# wave owns ((counts + 15) / 16 rounded up to 64) of them, so 1..64 counts are one 64-item step of wave 0, 65 reaches wave 1, 1023 / 1024 fill
+# the sixteen waves' single steps and 1025 makes each wave's range two steps (the carry) with empty tail waves.
+SCAN_COUNTS = [1, 63, 64, 65, 1023, 1024, 1025]
+
+
+@pytest.mark.parametrize("edges", [(0, 1), (1, 0)], ids=["none_first_all_last", "all_first_none_last"])
+@pytest.mark.parametrize("counts", SCAN_COUNTS)
+def test_filter_selection_at_block_count_edges(tc, mirror_layer, counts, edges):
+    """FilterExec's selection vector (the index vector of the view that the Python layer hands on) against the oracle's, exactly.  The selection runs over blocks of 16 bitmap words = 1024 rows
+    (csrc/capi.cpp selection_geometry) while the input has at most 8 * 16 words per compute unit, so `counts` blocks are
+    1024 * counts rows less a ragged tail."""
+    n = 1024 * counts - 37
+    assert (n + 63) // 64 <= device_cus(tc) * 8 * 16
+    t = pa.table({"x": pa.array(half_with_edges(counts, n, edges).astype(np.int32))})
+    src = g.MemoryExec([t])
+    pred = binary(col("x", src.schema()), Op.Eq, lit(1, "Int32"))
+    view = g.FilterExec(pred, src).execute(0, tc)
+    exp = np.asarray(O.filter_rows(O.Table.from_arrow(t), pred), dtype=np.int64)
+    assert 0 < len(exp) < n and view.num_rows == len(exp) and len(view.via) == 1
+    got = view.via[0][:view.num_rows].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+    assert np.array_equal(got, exp)
+
+
+@pytest.mark.parametrize("counts", SCAN_COUNTS)
+def test_unique_key_join_pairs_at_segment_count_edges(tc, counts):
+    """The unique-key probe counts its pairs per segment of 16 words = 1024 probe rows (csrc/capi.cpp, while the probe side has at most
+    128 * 16 words per compute unit) and scans the counts with the same kernel: the pairs in probe order against the oracle's."""
+    n, nb = 1024 * counts - 37, 1000
+    assert (n + 63) // 64 <= device_cus(tc) * 128 * 16
+    r = np.random.default_rng(counts)
+    pk = np.where(half_with_edges(counts, n, (0, 1)) == 1, r.integers(0, nb, n), r.integers(nb, 2 * nb, n))
+    bt = pa.table({"bk": pa.array(r.permutation(nb).astype(np.int64))})
+    pt = pa.table({"pk": pa.array(pk.astype(np.int64)), "pid": pa.array(np.arange(n, dtype=np.int64))})
+    L, R = g.MemoryExec([bt]), g.MemoryExec([pt])
+    on = [(col("bk", L.schema()), col("pk", R.schema()))]
+    j = g.HashJoinExec(L, R, on, None, "Inner", "CollectLeft", False)
+    js = j.schema()
+    out = g.plan.materialize(tc, g.ProjectionExec([(col("bk", js), "bk"), (col("pid", js), "pid")], j).execute(0, tc)).to_arrow(tc.ctx)
+    pairs = sorted(O.hash_join(O.Table.from_arrow(bt), O.Table.from_arrow(pt), on, "Inner"), key=lambda ij: ij[1])      # one pair per probe row
+    bk = bt["bk"].to_numpy()
+    assert np.array_equal(out["pid"].to_numpy(), np.array([k for _, k in pairs], dtype=np.int64))      # probe order kept
+    assert np.array_equal(out["bk"].to_numpy(), bk[np.array([i for i, _ in pairs], dtype=np.int64)])
+
+
 def test_filter_of_filter_and_projection(tc):
     t = rand_table(5, 5000, 0.1)
     ot = O.Table.from_arrow(t)
@@ -599,6 +658,25 @@ def test_hash_partition(tc, nparts):
             got = dev_rows(tc, v)
             exp = [tuple(c[i] for c in ot.cols) for i in range(ot.n) if pid[i] == p]    # input order kept inside a partition
             close_rows(got, exp)
+
+
+@pytest.mark.parametrize("nparts", [63, 64, 65, 1023, 1024, 1025, 5000])
+def test_hash_partition_at_offset_scan_edges(tc, nparts):
+    """Partition counts at which the one-block scan of the partition sizes into offsets (k_part_scan over block_walk_scan) changes
+    shape: one 64-item step of one wave, a second wave, all sixteen waves, two steps per wave with a carry and empty tail waves.
+    Sizes and the row order inside every partition (input order) against the oracle: the views' index vectors one after the other
+    are the stable sort of the rows by partition."""
+    t = rand_table(55, 20_000, 0.1)
+    ot = O.Table.from_arrow(t)
+    src = g.MemoryExec([t])
+    keys = [col("k64", src.schema())]
+    views = g.RepartitionExec(src, keys, nparts).execute_all(0, tc)
+    pid = np.asarray(O.hash_partition(ot, keys, nparts), dtype=np.int64)
+    assert len(views) == nparts and all(len(v.via) == 1 for v in views)
+    assert np.array_equal(np.array([v.num_rows for v in views], dtype=np.int64), np.bincount(pid, minlength=nparts))
+    import torch
+    order = torch.cat([v.via[0][:v.num_rows] for v in views]).cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+    assert np.array_equal(order, np.argsort(pid, kind="stable"))
 
 
 def test_shuffle_writer_round_trip(tc, tmp_path):

@@ -99,6 +99,16 @@ def test_independent_block_frames_and_block_index_walk(tc):
     same(pa.ipc.open_stream(raw).read_all(), t)
 
 
+def test_buffer_of_more_blocks_than_one_layout_step(tc):
+    """The frame layout scans a buffer's block sizes 256 blocks at a time (csrc/kernels_lz4.hip k_lz4_layout_sizes): 258 blocks of
+    64 KiB cross that step, so the second step starts from the first one's carry."""
+    n = 257 * 8192 + 1
+    t = pa.table({"k": pa.array(np.arange(n, dtype=np.int64) % 1000)})
+    buf = io.BytesIO()
+    S.write_ipc_stream(tc, buf, g.DeviceTable.from_arrow(t, tc.device), codec=0)
+    same(pa.ipc.open_stream(buf.getvalue()).read_all(), t)
+
+
 def test_frame_by_frame_fallback_keeps_raw_stored_bitmaps(tc):
     """A frame whose independent blocks are smaller than its declared maximum (legal: BD only bounds them) defeats the host-side
     block index, and the decoder falls back to walking frames one by one after clearing the OR-merged bitmaps.  Buffers stored raw
