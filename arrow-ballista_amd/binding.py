@@ -7,13 +7,22 @@ T_NULL, T_BOOL, T_INT32, T_INT64, T_DATE32, T_FLOAT64, T_DECIMAL128, T_UTF8, T_U
 T_INT8, T_INT16, T_UINT8, T_UINT16, T_FLOAT32, T_TIMESTAMP, T_DATE64 = range(10, 17)
 REPR_ARROW, REPR_PACKED15 = 0, 1
 _STATUS = {6: "CANCELLED", 1: "INVALID", 2: "HIP", 3: "UNSUPPORTED", 4: "CAPACITY", 5: "INTERNAL"}
+REFUSAL_NONE, REFUSAL_LONG_STRING, REFUSAL_WIDE_SORT_KEY, REFUSAL_NODE_NOT_NATIVE = range(4)      # gpuq_refusal
 
 
 class GpuqError(RuntimeError):
-    def __init__(self, status, message):
+    """status: the gpuq_status; refusal: which UNSUPPORTED it was (gpuq_refusal) -- what callers branch on, never the message."""
+
+    def __init__(self, status, message, refusal=REFUSAL_NONE):
         super().__init__("gpuq %s: %s" % (_STATUS.get(status, status), message))
         self.status = status
         self.message = message
+        self.refusal = refusal
+
+
+def failed(L, rc, message):
+    """The GpuqError of a library call that returned `rc` (with the calling thread's gpuq_last_refusal when it was UNSUPPORTED)."""
+    return GpuqError(rc, message, L.gpuq_last_refusal() if rc == 3 else REFUSAL_NONE)
 
 
 class gpuq_column(C.Structure):
@@ -66,6 +75,7 @@ def lib():
         "gpuq_ctx_create": (vp, [i32, C.c_char_p]),
         "gpuq_ctx_free": (None, [vp]),
         "gpuq_last_error": (C.c_char_p, [vp]),
+        "gpuq_last_refusal": (i32, []),
         "gpuq_ctx_device_info": (i32, [vp, C.c_char_p, C.c_size_t]),
         "gpuq_buffer_alloc": (i32, [vp, C.c_size_t, C.POINTER(vp)]),
         "gpuq_buffer_free": (i32, [vp, vp]),
@@ -225,7 +235,7 @@ def compile_check(descriptor):
     buf = C.create_string_buffer(1 << 18)
     rc = L.gpuq_compile_check(json.dumps(descriptor).encode(), buf, len(buf))
     if rc != 0:
-        raise GpuqError(rc, L.gpuq_last_error(None).decode())
+        raise failed(L, rc, L.gpuq_last_error(None).decode())
     return json.loads(buf.value.decode())
 
 
@@ -237,7 +247,7 @@ def plan_schema(plan):
     h = C.c_void_p()
     rc = L.gpuq_plan_create(None, json.dumps(plan).encode(), C.byref(h))
     if rc != 0:
-        raise GpuqError(rc, (L.gpuq_plan_last_error() or b"").decode())
+        raise failed(L, rc, (L.gpuq_plan_last_error() or b"").decode())
     try:
         n = C.c_int(0)
         rc = L.gpuq_plan_schema(h, None, 0, C.byref(n))
@@ -245,7 +255,7 @@ def plan_schema(plan):
         if rc == 0:
             rc = L.gpuq_plan_schema(h, f, n.value, C.byref(n))
         if rc != 0:
-            raise GpuqError(rc, (L.gpuq_plan_last_error() or b"").decode())
+            raise failed(L, rc, (L.gpuq_plan_last_error() or b"").decode())
         return [{"name": f[i].name.decode(), "type": type_json(f[i].type, f[i].precision, f[i].scale), "nullable": bool(f[i].nullable)} for i in range(n.value)]
     finally:
         L.gpuq_plan_free(h)
@@ -257,7 +267,7 @@ def compile_jit_source(descriptor, kernel_id):
     buf = C.create_string_buffer(1 << 20)
     rc = L.gpuq_compile_jit_source(json.dumps(descriptor).encode(), int(kernel_id), buf, len(buf))
     if rc != 0:
-        raise GpuqError(rc, L.gpuq_last_error(None).decode())
+        raise failed(L, rc, L.gpuq_last_error(None).decode())
     return buf.value.decode()
 
 
@@ -273,7 +283,7 @@ class Context:
 
     def check(self, rc):
         if rc != 0:
-            raise GpuqError(rc, self.L.gpuq_last_error(self.h).decode())
+            raise failed(self.L, rc, self.L.gpuq_last_error(self.h).decode())
 
     def set_jit(self, mode, min_rows=-1):
         self.check(self.L.gpuq_ctx_set_jit(self.h, mode.encode(), int(min_rows)))

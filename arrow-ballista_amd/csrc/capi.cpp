@@ -188,7 +188,7 @@ OpStatus read_status(gpuq_op* op, hipStream_t s, int words = 4) {
 }
 uint32_t read_flags(gpuq_op* op, hipStream_t s) { return read_status(op, s, 1).flags; }
 void raise_flags(uint32_t f) {
-  if (f & FLAG_STR_TRUNC) throw Unsupported("a Utf8 value longer than 15 bytes reached a device string comparison/key (PACKED15 limit)");
+  if (f & FLAG_STR_TRUNC) throw LongString("a Utf8 value longer than 15 bytes reached a device string comparison/key (PACKED15 limit)");
   if (f & FLAG_DEC_OVERFLOW) throw std::runtime_error("decimal arithmetic overflow: a result or a rescaled operand does not fit Decimal128 (38 digits / 127 bits)");
   if (f & FLAG_WIDE_MINMAX) throw Unsupported("MIN/MAX over a value outside the int64 range is not supported on device");
   if (f & FLAG_DUP_BUILD_KEY) throw Unsupported("duplicate build keys without a chain buffer");
@@ -369,6 +369,7 @@ gpuq_ctx* gpuq_ctx_create(int device_ordinal, const char* json_opts) {
 }
 void gpuq_ctx_free(gpuq_ctx* ctx) { delete ctx; }
 const char* gpuq_last_error(gpuq_ctx*) { return g_last_error.c_str(); }
+int gpuq_last_refusal(void) { return tls_refusal(); }
 int gpuq_ctx_device_info(gpuq_ctx* ctx, char* buf, size_t cap) {
   return guarded(ctx, [&]() {
     check_ctx(ctx);
@@ -1395,7 +1396,7 @@ static SortPack sort_key_plan(gpuq_op* op, hipStream_t s, const DevProgram& P, i
       if (cost_class(t) != cls) t = layout(-1, true, G);
       K = G; total = t; K.check = 1;
     }
-    if (total > 128) throw Unsupported("composite sort key needs " + std::to_string(total) + " bits (max 128)");
+    if (total > 128) throw WideSortKey("composite sort key needs " + std::to_string(total) + " bits (max 128)");
     *total_out = total;
     return K;
 }

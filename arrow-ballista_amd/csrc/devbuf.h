@@ -1,37 +1,13 @@
-// Device buffers recycled through a process-wide pool, and the exception types that map to the C ABI's status codes.
+// Device buffers recycled through a process-wide pool (the exception types that map to the C ABI's status codes: status.h).
 // Shared by every translation unit behind the C ABI (capi.cpp, plan_exec.cpp, exchange.cpp, shuffle_codec.cpp, ingest.cpp, scanfmt.cpp).
 #pragma once
-#include "../../include/gpuq.h"
+#include "status.h"
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <mutex>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
 namespace gpuq {
-
-struct HipError : std::runtime_error { using std::runtime_error::runtime_error; };
-struct Unsupported : std::runtime_error { using std::runtime_error::runtime_error; };
-struct Capacity : std::runtime_error { using std::runtime_error::runtime_error; };
-struct Retry : std::runtime_error { using std::runtime_error::runtime_error; };      // deferred execution: an assumption did not hold (GPUQ_ERR_RETRY)
-
-// The one mapping from what the library throws to the C ABI's status codes.  Call it inside a catch block: it rethrows the exception
-// in flight, returns its status and leaves its message in `err` (each boundary names its own thread-local string: the one behind its
-// gpuq_*_last_error).  A unit with exception types of its own catches those first and hands everything else over.
-inline int status_of_exception(std::string& err) {
-  try { throw; }
-  catch (const HipError& e) { err = e.what(); return GPUQ_ERR_HIP; }
-  catch (const Unsupported& e) { err = e.what(); return GPUQ_ERR_UNSUPPORTED; }
-  catch (const Capacity& e) { err = e.what(); return GPUQ_ERR_CAPACITY; }
-  catch (const Retry& e) { err = e.what(); return GPUQ_ERR_RETRY; }
-  catch (const std::bad_alloc&) { err = "out of host memory"; return GPUQ_ERR_INTERNAL; }
-  catch (const std::exception& e) { err = e.what(); return GPUQ_ERR_INVALID; }
-}
-template <class F> int guarded_into(std::string& err, F&& f) {
-  try { f(); return GPUQ_OK; }
-  catch (...) { return status_of_exception(err); }
-}
 
 // a bitmap over n rows (validity, selection, presence): its 64-row words, and its size as every such buffer is allocated (a spare word behind them)
 inline size_t words_of(int64_t n) { return (size_t)((n + 63) / 64); }

@@ -73,7 +73,7 @@ void nccl_check(int rc, const char* what) {
 struct PeerFailed : std::runtime_error { using std::runtime_error::runtime_error; };      // a rank of the node failed: GPUQ_ERR_PEER on all of them
 template <class F> int guarded_x(F&& f) {
   try { f(); return GPUQ_OK; }
-  catch (const PeerFailed& e) { g_xerr = e.what(); return GPUQ_ERR_PEER; }
+  catch (const PeerFailed& e) { g_xerr = e.what(); tls_refusal() = GPUQ_REFUSAL_NONE; return GPUQ_ERR_PEER; }
   catch (...) { return status_of_exception(g_xerr); }
 }
 

@@ -246,7 +246,7 @@ void check(Exec& x, int rc) {
   if (rc == GPUQ_OK) return;
   const char* m = gpuq_last_error(x.ctx);
   const std::string msg = m ? m : "gpuq error";
-  if (rc == GPUQ_ERR_UNSUPPORTED) throw Unsupported(msg);
+  if (rc == GPUQ_ERR_UNSUPPORTED) throw_unsupported(gpuq_last_refusal(), msg);      // the refusals the executor answers come back as their types
   if (rc == GPUQ_ERR_CAPACITY) throw Capacity(msg);
   if (rc == GPUQ_ERR_HIP) throw HipError(msg);
   throw std::runtime_error(msg);
@@ -260,10 +260,11 @@ gpuq_op* get_op(Exec& x, const Json& desc) {
   (*x.ops)[key] = op;
   return op;
 }
-// Operator for a call site and an input layout.  Building and serialising a descriptor costs tens of microseconds; a plan
-// that runs repeatedly (or over many partitions) sees the same layouts again, so the descriptor is only built on a miss.
-template <class MakeDesc> gpuq_op* cached_op(Exec& x, const void* site, int tag, const std::string& sig, MakeDesc&& mk) {
-  std::string key = std::to_string((uintptr_t)site); key += '#'; key += std::to_string(tag); key += '#'; key += sig;
+enum Rung { RUNG_PLAIN = 0, RUNG_LONG_CMP, RUNG_LONG_KEYS, RUNG_WIDE };      // the form an operator runs in: as planned, or as a recovery from a loud refusal (long_string_ladder, sort_table)
+// Operator for a call site (a node and the literal tag of the call there), the rung it runs at, the pass of a multi-pass sort, and an input layout.  Building and
+// serialising a descriptor costs tens of microseconds; a plan that runs repeatedly (or over many partitions) sees the same layouts again, so it is only built on a miss.
+template <class MakeDesc> gpuq_op* cached_op(Exec& x, const void* site, int tag, const std::string& sig, MakeDesc&& mk, Rung rung = RUNG_PLAIN, int pass = 0) {
+  std::string key = std::to_string((uintptr_t)site); for (const int k : {tag, (int)rung, pass}) { key += '#'; key += std::to_string(k); } key += '#'; key += sig;
   auto it = x.memo->find(key);
   if (it != x.memo->end()) return it->second;
   gpuq_op* op = get_op(x, mk());
@@ -478,7 +479,6 @@ PTable lower_strcmp(Exec& x, const PTable& t, std::vector<Json>& exprs) {
 // value reached a key, the executor runs the operator again over exact dictionary codes (gpuq_utf8_intern): a group / join key
 // that is a plain Utf8 column in Arrow layout is replaced by an Int64 code column appended to (a copy of) the table; strings come
 // back with a take through the codes.  Nothing is paid on the common path: the rewrite only happens after the loud failure.
-bool is_long_string_failure(const std::exception& e) { return std::string(e.what()).find("longer than 15 bytes reached") != std::string::npos; }
 struct Utf8DictGuard { gpuq_utf8_dict* d = nullptr; ~Utf8DictGuard() { if (d) gpuq_utf8_dict_free(d); } };
 struct JoinTableGuard { gpuq_join_table* t = nullptr; ~JoinTableGuard() { if (t) gpuq_join_table_free(t); } };
 // appends the code column of t.cols[ci] (insert: fills `dict` from it; else looks it up in `dict`) under `name`
@@ -494,13 +494,19 @@ void strip_code_columns(PTable& t) {
     if (t.cols[i].name.rfind("__code_", 0) == 0) { t.cols.erase(t.cols.begin() + (long)i); t.sides.erase(t.sides.begin() + (long)i); t.record_cap = 0; }
 }
 
-// run(tag, long_cmp); when a string comparison met a value beyond 15 bytes (the loud failure above), once more with the comparisons
-// lowered to helper columns (lower_strcmp), as an operator of its own in the cache (tag + 64)
-template <class F> auto retry_long_cmp(const int tag, F&& run) -> decltype(run(tag, false)) {
-  try { return run(tag, false); }
-  catch (const Unsupported& e) { if (!is_long_string_failure(e)) throw; }
-  return run(tag + 64, true);
+// The one place a LongString refusal is answered, for projection, filter, aggregate and join: run(RUNG_PLAIN) (skip_plain: the caller knows it cannot serve); when a
+// value beyond 15 bytes reached a packed comparison or key, before_second() and run(second) -- RUNG_LONG_CMP: the comparisons lowered to helper columns (lower_strcmp);
+// RUNG_LONG_KEYS: the keys as dictionary codes -- an operator of its own in the cache; when that is refused too, lift() applies the filters that were fused into the
+// operator on their own (filter_table lowers their comparisons; false: there were none, the refusal stands) and run(second) runs again.
+template <class Run, class Before, class Lift>
+auto long_string_ladder(const Rung second, const bool skip_plain, Run&& run, Before&& before_second, Lift&& lift) -> decltype(run(RUNG_PLAIN)) {
+  if (!skip_plain) try { return run(RUNG_PLAIN); } catch (const LongString&) {}
+  before_second();
+  try { return run(second); }
+  catch (const LongString&) { if (!lift()) throw; }
+  return run(second);
 }
+template <class Run> auto retry_long_cmp(Run&& run) -> decltype(run(RUNG_PLAIN)) { return long_string_ladder(RUNG_LONG_CMP, false, run, []() {}, []() { return false; }); }
 // ---------------------------------------------------------------- operator descriptors: one builder per kind, called on a cached_op miss (or from a static schema())
 // in_names: the input's column names the expressions are bound to by name; nullptr: they are by-position references already
 Json project_desc(const Json& input, const std::vector<Json>& exprs, const std::vector<std::string>& names, const std::vector<std::string>* in_names) {
@@ -521,13 +527,14 @@ Json sort_desc(const PTable& t, const Json& sort_exprs) {
   return jobj({{"op", jstr("sort")}, {"input", input_of(t)}, {"expr", ex}});
 }
 
-static PTable project_impl(Exec& x, const PTable& t_in, const std::vector<Json>& exprs_in, const std::vector<std::string>& names, const void* site, int tag, const bool long_cmp) {
+static PTable project_impl(Exec& x, const PTable& t_in, const std::vector<Json>& exprs_in, const std::vector<std::string>& names, const void* site, int tag, const Rung rung) {
+  const bool long_cmp = rung == RUNG_LONG_CMP;
   std::vector<Json> exprs = exprs_in;
   bool any_like = false; for (auto& e : exprs) any_like = any_like || has_like(e);
   PTable t_res = t_in; if (any_like || long_cmp) resolve(x, t_res);      // the LIKE / compare kernels take an exact row count
   PTable t = lower_like(x, t_res, exprs);
   if (long_cmp) t = lower_strcmp(x, t, exprs);
-  gpuq_op* op = cached_op(x, site, tag, table_sig(t), [&]() { const auto nm = names_of(t); return project_desc(input_of(t), exprs, names, &nm); });
+  gpuq_op* op = cached_op(x, site, tag, table_sig(t), [&]() { const auto nm = names_of(t); return project_desc(input_of(t), exprs, names, &nm); }, rung);
   const bool deferred = prep(x, op, t);
   std::vector<gpuq_column> carr;
   PTable out = alloc_outputs(op, t.n, carr);
@@ -545,7 +552,7 @@ static PTable project_impl(Exec& x, const PTable& t_in, const std::vector<Json>&
   return out;
 }
 PTable project(Exec& x, const PTable& t_in, const std::vector<Json>& exprs_in, const std::vector<std::string>& names, const void* site, int tag) {
-  return retry_long_cmp(tag, [&](int tg, bool long_cmp) { return project_impl(x, t_in, exprs_in, names, site, tg, long_cmp); });
+  return retry_long_cmp([&](Rung rung) { return project_impl(x, t_in, exprs_in, names, site, tag, rung); });
 }
 
 // new[j] = vec[idx[j]] with NULL_ROW propagated
@@ -658,14 +665,15 @@ PTable materialize(Exec& x, const PTable& t_in, bool force) {
 // `source` (in order) and the device word `cnt` their number.  exact: the caller reads the count back -- source's own count is made
 // exact first and the operator is not offered a deferred run; otherwise it may run deferred (`deferred`), over `n` rows at most.
 struct FilterRun { gpuq_op* op = nullptr; BufP sel, cnt; int64_t n = 0; bool deferred = false; PTable t; };      // t: what the operator read (helper columns live as long as this)
-static FilterRun run_filter(Exec& x, PTable& source, const Json& predicate_in, const void* site, int tag, const bool long_cmp, const bool exact) {
+static FilterRun run_filter(Exec& x, PTable& source, const Json& predicate_in, const void* site, int tag, const Rung rung, const bool exact) {
+  const bool long_cmp = rung == RUNG_LONG_CMP;
   std::vector<Json> pe{predicate_in};
   if (exact || has_like(predicate_in) || long_cmp) resolve(x, source);      // the LIKE / compare kernels take an exact row count
   FilterRun r; PTable& t = r.t;
   t = lower_like(x, source, pe);
   if (long_cmp) t = lower_strcmp(x, t, pe);
   const Json& predicate = pe[0];
-  r.op = cached_op(x, site, tag, table_sig(t), [&]() { return filter_desc(t, predicate); });
+  r.op = cached_op(x, site, tag, table_sig(t), [&]() { return filter_desc(t, predicate); }, rung);
   r.deferred = !exact && prep(x, r.op, t);
   if (!t.n_dev && source.n_dev) { source.n = t.n; source.count_from(t); }
   r.sel = alloc_rows(t.n); r.cnt = dev_alloc(16); r.n = t.n;
@@ -674,21 +682,21 @@ static FilterRun run_filter(Exec& x, PTable& source, const Json& predicate_in, c
   return r;
 }
 // the passing driving positions of `source` (in order) and their number
-static int64_t filter_sel_impl(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag, BufP& sel_out, const bool long_cmp) {
+static int64_t filter_sel_impl(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag, BufP& sel_out, const Rung rung) {
   PTable source = source_in;
-  const FilterRun r = run_filter(x, source, predicate_in, site, tag, long_cmp, true);      // (the callers of this form need the exact count back)
+  const FilterRun r = run_filter(x, source, predicate_in, site, tag, rung, true);      // (the callers of this form need the exact count back)
   sel_out = r.sel;
   const int64_t k = (int64_t)read_u64(x, r.cnt->p);
   check(x, gpuq_op_check(r.op, x.stream));
   return k;
 }
 int64_t filter_sel(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag, BufP& sel_out) {
-  return retry_long_cmp(tag, [&](int tg, bool long_cmp) { return filter_sel_impl(x, source_in, predicate_in, site, tg, sel_out, long_cmp); });
+  return retry_long_cmp([&](Rung rung) { return filter_sel_impl(x, source_in, predicate_in, site, tag, sel_out, rung); });
 }
 
-static PTable filter_table_impl(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag, const bool long_cmp) {
+static PTable filter_table_impl(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag, const Rung rung) {
   PTable source = source_in;
-  const FilterRun r = run_filter(x, source, predicate_in, site, tag, long_cmp, false);
+  const FilterRun r = run_filter(x, source, predicate_in, site, tag, rung, false);
   if (r.deferred && r.n > 0) {      // the survivors' count stays on the device: the view is as long as its input at most
     PTable c; c.n_dev = (const uint64_t*)r.cnt->p; c.n_keep = r.cnt;
     return select_view(x, source, (const uint32_t*)r.sel->p, r.n, r.sel, &c);
@@ -698,15 +706,15 @@ static PTable filter_table_impl(Exec& x, const PTable& source_in, const Json& pr
   return select_view(x, source, (const uint32_t*)r.sel->p, k, r.sel);
 }
 PTable filter_table(Exec& x, const PTable& source_in, const Json& predicate_in, const void* site, int tag) {
-  return retry_long_cmp(tag, [&](int tg, bool long_cmp) { return filter_table_impl(x, source_in, predicate_in, site, tg, long_cmp); });
+  return retry_long_cmp([&](Rung rung) { return filter_table_impl(x, source_in, predicate_in, site, tag, rung); });
 }
 
 // the stable permutation that puts `t` in `sort_exprs` order (one gpuq_sort_run: <= 4 keys whose composite fits 128 bits)
 // ORDER BY one plain column of an integer-like type: the operator can hand that column back IN ORDER (rebuilt from its sorted records,
 // gpuq_sort_run_keys) -- the view over the sorted table then reads it directly instead of through the permutation.
 struct SortedKey { int col = -1; BufP data, valid; bool decoded = false; };
-static BufP sort_perm(Exec& x, PTable& t, const Json& sort_exprs, const void* site, int tag, SortedKey* sk = nullptr) {      // (t's count is made exact when the operator cannot run deferred)
-  gpuq_op* op = cached_op(x, site, tag, table_sig(t), [&]() { return sort_desc(t, sort_exprs); });
+static BufP sort_perm(Exec& x, PTable& t, const Json& sort_exprs, const void* site, int tag, SortedKey* sk = nullptr, Rung rung = RUNG_PLAIN, int pass = 0) {      // (t's count is made exact when the operator cannot run deferred)
+  gpuq_op* op = cached_op(x, site, tag, table_sig(t), [&]() { return sort_desc(t, sort_exprs); }, rung, pass);
   prep(x, op, t);
   BufP perm = alloc_rows(t.n);
   InputC ic; make_input(t, ic);
@@ -731,7 +739,8 @@ static BufP sort_perm(Exec& x, PTable& t, const Json& sort_exprs, const void* si
 // long strings go through in groups of up to four, as one composite key per pass.  Every pass sorts the rows in the order the
 // later keys left them, so ties keep that order.  Nothing is paid on the common path: this runs only after the loud failure.
 struct PermOut { const uint32_t* p = nullptr; std::vector<BufP> keep; };
-static PermOut sort_perm_long(Exec& x, const PTable& t, const Json& sort_exprs, const void* site, int tag, size_t max_group = 4) {
+static PermOut sort_perm_long(Exec& x, const PTable& t, const Json& sort_exprs, const void* site, int tag, const Rung rung = RUNG_LONG_KEYS) {
+  const size_t max_group = rung == RUNG_WIDE ? 1 : 4;      // RUNG_WIDE: a group of four did not fit 128 bits -- one key a pass
   PTable w = t;
   std::vector<Json> groups; Json cur = jarr();
   auto flush = [&]() { if (!cur.a.empty()) { groups.push_back(cur); cur = jarr(); } };
@@ -753,9 +762,9 @@ static PermOut sort_perm_long(Exec& x, const PTable& t, const Json& sort_exprs, 
   flush();
   PermOut out;
   for (size_t gi = groups.size(); gi-- > 0;) {
-    if (!out.p) { BufP p = sort_perm(x, w, groups[gi], site, tag * 64 + 8 + (int)gi); out.p = (const uint32_t*)p->p; out.keep.push_back(p); continue; }      // (w is exact: see sort_table)
+    if (!out.p) { BufP p = sort_perm(x, w, groups[gi], site, tag, nullptr, rung, (int)gi); out.p = (const uint32_t*)p->p; out.keep.push_back(p); continue; }      // (w is exact: see sort_table)
     PTable view = select_view(x, w, out.p, w.n, nullptr);
-    BufP p2 = sort_perm(x, view, groups[gi], site, tag * 64 + 8 + (int)gi);
+    BufP p2 = sort_perm(x, view, groups[gi], site, tag, nullptr, rung, (int)gi);
     out.keep.push_back(p2);
     for (auto& b : view.keep) out.keep.push_back(b);
     out.p = take_u32(x, out.p, w.n, (const uint32_t*)p2->p, w.n, out.keep);      // rows in the new order = old order read through the pass's permutation
@@ -764,9 +773,8 @@ static PermOut sort_perm_long(Exec& x, const PTable& t, const Json& sort_exprs, 
   return out;
 }
 
-static bool is_wide_sort_key(const std::exception& e) { return std::string(e.what()).find("composite sort key needs") != std::string::npos; }
 PTable sort_table(Exec& x, const PTable& t_in, const Json& sort_exprs, int64_t fetch, const void* site, int tag) {
-  PTable t = t_in; bool wide = false;
+  PTable t = t_in; Rung rung = RUNG_LONG_KEYS;
   try {
     // one key that is a plain fixed-width column of a materialised table with enough rows for the radix passes: ask for it in order
     SortedKey sk;
@@ -792,12 +800,12 @@ PTable sort_table(Exec& x, const PTable& t_in, const Json& sort_exprs, int64_t f
       out.record_cap = 0;
     }
     return out;
-  } catch (const Unsupported& e) { if (!is_long_string_failure(e) && !is_wide_sort_key(e)) throw; wide = is_wide_sort_key(e); }
+  } catch (const LongString&) {} catch (const WideSortKey&) { rung = RUNG_WIDE; }
   resolve(x, t);
   const int64_t k = (fetch < 0 || fetch > t.n) ? t.n : fetch;
   // strings beyond 15 bytes: stable passes over 14-byte pieces; a composite key beyond 128 bits (two packed strings and a Float64 whose bit
   // patterns span 2^40: q7's ORDER BY supp_nation, cust_nation, l_year): one stable pass per key, least significant first
-  PermOut po = sort_perm_long(x, t, sort_exprs, site, tag, wide ? 1 : 4);
+  PermOut po = sort_perm_long(x, t, sort_exprs, site, tag, rung);
   PTable out = select_view(x, t, po.p, k, nullptr);
   for (auto& b : po.keep) out.keep.push_back(b);
   return out;
@@ -1169,7 +1177,7 @@ struct AggregateExec : PNode {
       else {      // more keys than one sort takes: stable passes, least significant first -- four keys a pass, or one when four do not fit 128 bits
         PermOut po;
         try { po = sort_perm_long(x, proj, se, this, 200 + j); }
-        catch (const Unsupported& e) { if (!is_wide_sort_key(e)) throw; po = sort_perm_long(x, proj, se, this, 300 + j, 1); }
+        catch (const WideSortKey&) { po = sort_perm_long(x, proj, se, this, 200 + j, RUNG_WIDE); }
         v = select_view(x, proj, po.p, n, nullptr);
         for (auto& b : po.keep) v.keep.push_back(b);
       }
@@ -1299,17 +1307,11 @@ struct AggregateExec : PNode {
       const ColMap* cm0 = f.has_map ? &f.map : nullptr;
       for (auto& g : group_expr.a) if (long_key_column(t, inline_projection(g.at("expr"), cm0)) >= 0) many_string_keys = true;
     }
-    if (!many_string_keys) {
-      try { return timed(x, t0, run(x, t, f, false)); }
-      catch (const Unsupported& e) { if (!is_long_string_failure(e)) throw; }
-    }
-    resolve(x, t);
-    try { return timed(x, t0, run(x, t, f, true)); }      // a group key holds strings of more than 15 bytes: again, over dictionary codes
-    catch (const Unsupported& e) { if (!is_long_string_failure(e) || !f.has_pred) throw; }
-    // it was the fused FILTER that compared long strings: apply it on its own (filter_table lowers such comparisons), then aggregate
-    Fused f2 = f; f2.has_pred = false;
-    PTable t2 = filter_table(x, t, f.pred, this, 9);
-    return timed(x, t0, run(x, t2, f2, true));
+    // a group key holds strings of more than 15 bytes: again, over dictionary codes; it was the fused FILTER that compared them: the filter on its own, then the aggregate
+    return long_string_ladder(RUNG_LONG_KEYS, many_string_keys,
+      [&](Rung rung) { return timed(x, t0, run(x, t, f, rung)); },
+      [&]() { resolve(x, t); },
+      [&]() { if (!f.has_pred) return false; t = filter_table(x, t, f.pred, this, 9); f.has_pred = false; return true; });
   }
   // Grouping by the build row (BuildRows).  The input is the pair list of an Inner join over unique build keys, and every group expression
   // is a join-key column (of either side: they are equal on every joined row) or an expression over build-side columns, with all join
@@ -1367,7 +1369,8 @@ struct AggregateExec : PNode {
     for (size_t i = 1; i < out.cols.size(); ++i) { PCol c = out.cols[i]; c.c.length = keys.n; r.cols.push_back(c); r.sides.push_back(0); }
     return r;
   }
-  PTable run(Exec& x, PTable t, const Fused& f, const bool long_keys) {
+  PTable run(Exec& x, PTable t, const Fused& f, const Rung rung) {
+    const bool long_keys = rung == RUNG_LONG_KEYS;
     const ColMap* cm0 = f.has_map ? &f.map : nullptr;
     std::vector<Json> over_build;
     const BuildRows* br = long_keys ? nullptr : build_row_grouping(t, cm0, over_build);
@@ -1392,7 +1395,7 @@ struct AggregateExec : PNode {
       } else ci = -1;
       gexprs.push_back(e); coded.push_back(ci);
     }
-    gpuq_op* op = cached_op(x, this, long_keys ? 6 : (br ? 10 : 0), table_sig(t), [&]() {
+    gpuq_op* op = cached_op(x, this, br ? 10 : 0, table_sig(t), [&]() {
     const auto nm = names_of(t);
     const ColMap* cm = f.has_map ? &f.map : nullptr;
     Json ge = jarr();
@@ -1403,7 +1406,7 @@ struct AggregateExec : PNode {
     if (expected_groups) d.push_back({"expected_groups", jnum(expected_groups)});
     if (br) d.push_back({"group_by", jstr("build_row")});      // (read by nobody but whoever looks at the plan's profile)
     return jobj(d);
-    });
+    }, rung);
     const bool deferred = !long_keys && prep(x, op, t);
     if (!deferred) resolve(x, t);
     int64_t cap = output_capacity > 0 ? output_capacity : (group_expr.a.empty() ? 4096 : std::max<int64_t>(4096, std::min<int64_t>(t.n, 1ll << 22)));
@@ -1578,30 +1581,25 @@ struct HashJoinExec : PNode {
       if (chain_build(x, inner, Li, Ri, ch)) {
         JoinTableGuard guard{ch.table};
         Side Lv; Lv.t = ch.view;
-        return timed(x, t0, join_sides(x, Lv, R, false, &ch));
+        return timed(x, t0, join_sides(x, Lv, R, RUNG_PLAIN, &ch));
       }
       // the inner build side holds duplicate keys (or a layout the fused form does not take): the two-step form, over the same inputs
       auto t1 = std::chrono::steady_clock::now();
-      L.t = inner->timed(x, t1, inner->join_sides(x, Li, Ri, false));
+      L.t = inner->timed(x, t1, inner->join_sides(x, Li, Ri, RUNG_PLAIN));
     } else sides(part, x, L, R);
     auto t0 = std::chrono::steady_clock::now();
-    try { return timed(x, t0, join_sides(x, L, R, false)); }
-    catch (const Unsupported& e) { if (!is_long_string_failure(e)) throw; }
     // a join key holds strings of more than 15 bytes: again, with those key columns replaced by exact dictionary codes (the
-    // build side fills the dictionary, the probe side is looked up in it; a probe string that is not in it gets no code = no match)
-    resolve(x, L.t); resolve(x, R.t);
-    PTable out;
-    try { out = join_sides(x, L, R, true); }
-    catch (const Unsupported& e) {
-      if (!is_long_string_failure(e) || !(L.has_pred || R.has_pred)) throw;
-      // it was a filter fused into a side that compared long strings: apply the filters on their own (filter_table lowers such comparisons)
-      if (L.has_pred) { L.t = filter_table(x, L.t, L.pred, this, 41); L.has_pred = false; }
-      if (R.has_pred) { R.t = filter_table(x, R.t, R.pred, this, 42); R.has_pred = false; }
-      strip_code_columns(L.t); strip_code_columns(R.t);
-      out = join_sides(x, L, R, true);
-    }
-    strip_code_columns(out);
-    return timed(x, t0, out);
+    // build side fills the dictionary, the probe side is looked up in it; a probe string that is not in it gets no code = no match);
+    // it was a filter fused into a side that compared long strings: the filters on their own, then the join over codes
+    return long_string_ladder(RUNG_LONG_KEYS, false,
+      [&](Rung rung) { PTable out = join_sides(x, L, R, rung); if (rung == RUNG_LONG_KEYS) strip_code_columns(out); return timed(x, t0, out); },
+      [&]() { resolve(x, L.t); resolve(x, R.t); },
+      [&]() {
+        if (!(L.has_pred || R.has_pred)) return false;
+        if (L.has_pred) { L.t = filter_table(x, L.t, L.pred, this, 41); L.has_pred = false; }
+        if (R.has_pred) { R.t = filter_table(x, R.t, R.pred, this, 42); R.has_pred = false; }
+        strip_code_columns(L.t); strip_code_columns(R.t); return true;
+      });
   }
   void sides(int part, Exec& x, Side& L, Side& R) {
     const int lpart = partition_mode == "Partitioned" ? part : 0;
@@ -1712,7 +1710,8 @@ struct HashJoinExec : PNode {
     ch.view = v;
     return true;
   }
-  PTable join_sides(Exec& x, Side L, Side R, const bool long_keys, Chain* chain = nullptr) {
+  PTable join_sides(Exec& x, Side L, Side R, const Rung rung, Chain* chain = nullptr) {
+    const bool long_keys = rung == RUNG_LONG_KEYS;
     // columns nobody above this join reads are dropped before anything is gathered through the pair vectors (q5: the region / nation /
     // customer columns that only served the joins below; SF100: the materialisation of the orders-side view took 0.7 ms with them)
     if (!out_need_all) {
@@ -1746,12 +1745,12 @@ struct HashJoinExec : PNode {
         on_eff.a[k] = jobj({{"left", jcolname(nm + "l")}, {"right", jcolname(nm + "r")}});
       }
     }
-    gpuq_op* bop = chain ? nullptr : cached_op(x, this, long_keys ? 7 : 0, table_sig(L.t), [&]() {
+    gpuq_op* bop = chain ? nullptr : cached_op(x, this, 0, table_sig(L.t), [&]() {
       // only Left / Full / LeftSemi / LeftAnti ask the table for its build side's rows afterwards
       const bool side_rows = jt == "Left" || jt == "Full" || jt == "LeftSemi" || jt == "LeftAnti";
       return join_build_desc(L, on_eff, nullptr, null_equals_null, side_rows, label("build"));
-    });
-    gpuq_op* pop = cached_op(x, this, long_keys ? 8 : 1, table_sig(R.t), [&]() { return join_probe_desc(R, on_eff, jt, null_equals_null, label("probe")); });
+    }, rung);
+    gpuq_op* pop = cached_op(x, this, 1, table_sig(R.t), [&]() { return join_probe_desc(R, on_eff, jt, null_equals_null, label("probe")); }, rung);
     // Deferred (a plan's second run on): the build keeps the table layout it remembers, the probe's pair count stays on the device and
     // sizes nothing on the host -- the pair vectors are as long as the count this call site produced last time allows (+ 1/8), an
     // overflow raises the probe's status word.  Only the join types whose output is the pair list itself run this way.
@@ -2551,7 +2550,7 @@ PNodeP build_node(const Json& j) {
     for (auto& f : v.at("schema").a) n->schema_.push_back({f.at("name").str(), f.at("type"), f.get_bool("nullable", true)});
     for (auto& p : v.at("partition").a) { n->locations.emplace_back(); for (auto& l : p.a) n->locations.back().push_back(l.is_obj() ? l.at("path").str() : l.str()); }
     out = std::move(n);
-  } else throw Unsupported("plan: node type '" + kind + "' is not executed natively");
+  } else throw NotNative("plan: node type '" + kind + "' is not executed natively");
   out->kind = kind;
   return out;
 }
@@ -2575,8 +2574,8 @@ struct gpuq_result { PTable t; std::vector<gpuq_field_info> fields; };
 namespace {
 template <class F> int plan_guarded(F&& f) {
   try { f(); return GPUQ_OK; }
-  catch (const Cancelled& e) { g_plan_error = e.what(); return GPUQ_ERR_CANCELLED; }
-  catch (const AgreedFailure& e) { g_plan_error = e.what(); return e.rc; }
+  catch (const Cancelled& e) { g_plan_error = e.what(); tls_refusal() = GPUQ_REFUSAL_NONE; return GPUQ_ERR_CANCELLED; }
+  catch (const AgreedFailure& e) { g_plan_error = e.what(); tls_refusal() = GPUQ_REFUSAL_NONE; return e.rc; }
   catch (...) { return status_of_exception(g_plan_error); }
 }
 }  // namespace
@@ -2675,7 +2674,7 @@ struct gpuq_task {
   gpuq_plan* plan = nullptr; void* stream = nullptr; int partition = 0;
   std::vector<gpuq_input> inputs; std::vector<std::vector<gpuq_column>> cols;      // private copies: the caller's arrays may go away
   std::thread th; std::atomic<int> cancel{0}, done{0};
-  int rc = GPUQ_OK; std::string err; gpuq_result* res = nullptr;
+  int rc = GPUQ_OK, refusal = GPUQ_REFUSAL_NONE; std::string err; gpuq_result* res = nullptr;
 };
 
 int gpuq_plan_execute_async(gpuq_plan* p, void* stream, int partition, const gpuq_input* inputs, int n_inputs, gpuq_task** out) {
@@ -2694,7 +2693,7 @@ int gpuq_plan_execute_async(gpuq_plan* p, void* stream, int partition, const gpu
     t->th = std::thread([raw, dev]() {
       (void)hipSetDevice(dev);
       raw->rc = plan_execute_impl(raw->plan, raw->stream, raw->partition, raw->inputs.data(), (int)raw->inputs.size(), &raw->cancel, &raw->res);
-      if (raw->rc != GPUQ_OK) raw->err = g_plan_error;      // the error text is per thread: carry it to whoever waits
+      if (raw->rc != GPUQ_OK) { raw->err = g_plan_error; raw->refusal = tls_refusal(); }      // the error text and the refusal are per thread: carry them to whoever waits
       raw->done.store(1, std::memory_order_release);
     });
     *out = t.release();
@@ -2706,7 +2705,7 @@ int gpuq_task_wait(gpuq_task* t, gpuq_result** out) {
   if (!t) return GPUQ_ERR_INVALID;
   if (t->th.joinable()) t->th.join();
   if (out) { *out = t->res; t->res = nullptr; }
-  if (t->rc != GPUQ_OK) g_plan_error = t->err;
+  if (t->rc != GPUQ_OK) { g_plan_error = t->err; tls_refusal() = t->refusal; }
   return t->rc;
 }
 void gpuq_task_free(gpuq_task* t) {

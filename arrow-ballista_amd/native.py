@@ -29,7 +29,7 @@ ArrowArray._fields_ = [("length", C.c_int64), ("null_count", C.c_int64), ("offse
 
 def _check(L, rc):
     if rc != 0:
-        raise B.GpuqError(rc, (L.gpuq_plan_last_error() or b"").decode())
+        raise B.failed(L, rc, (L.gpuq_plan_last_error() or b"").decode())
 
 
 def plan_to_json(node, tc, inputs):
@@ -108,7 +108,7 @@ def plan_to_json(node, tc, inputs):
     if isinstance(node, P.ShuffleReaderExec):
         return {"ShuffleReaderExec": {"schema": [{"name": f["name"], "type": f["type"], "nullable": bool(f.get("nullable", True))} for f in node.schema()],
                                       "partition": [[{"path": (l["path"] if isinstance(l, dict) else l)} for l in p] for p in node.partition]}}
-    raise B.GpuqError(3, "plan node %s is not executed natively" % t)
+    raise B.GpuqError(3, "plan node %s is not executed natively" % t, B.REFUSAL_NODE_NOT_NATIVE)
 
 
 class NativeResult:

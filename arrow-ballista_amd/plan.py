@@ -400,7 +400,7 @@ def _native_execute(node, partition, context, mirror):
         try:
             np_ = N.NativePlan(node, context)
         except B.GpuqError as e:
-            if "not executed natively" in str(e):      # a node only the mirror implements
+            if e.refusal == B.REFUSAL_NODE_NOT_NATIVE:      # a node only the mirror implements
                 cache[id(context)] = False
                 return mirror(node, partition, context)
             raise

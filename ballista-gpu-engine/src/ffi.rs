@@ -5,6 +5,11 @@ use std::os::raw::{c_char, c_int, c_void};
 pub const GPUQ_OK: c_int = 0;
 pub const GPUQ_ERR_UNSUPPORTED: c_int = 3;
 pub const GPUQ_ERR_CANCELLED: c_int = 6;
+// gpuq_refusal: which GPUQ_ERR_UNSUPPORTED it was (gpuq_last_refusal, per calling thread)
+pub const GPUQ_REFUSAL_NONE: c_int = 0;
+pub const GPUQ_REFUSAL_LONG_STRING: c_int = 1;
+pub const GPUQ_REFUSAL_WIDE_SORT_KEY: c_int = 2;
+pub const GPUQ_REFUSAL_NODE_NOT_NATIVE: c_int = 3;
 
 #[repr(C)]
 pub struct gpuq_ctx { _p: [u8; 0] }
@@ -60,6 +65,7 @@ extern "C" {
     pub fn gpuq_memory_limit(bytes: i64) -> c_int;
     pub fn gpuq_memory_stats(in_use: *mut i64, peak: *mut i64, cached: *mut i64, limit: *mut i64, reset_peak: c_int) -> c_int;
     pub fn gpuq_last_error(ctx: *mut gpuq_ctx) -> *const c_char;
+    pub fn gpuq_last_refusal() -> c_int;
 
     pub fn gpuq_plan_create(ctx: *mut gpuq_ctx, plan_json: *const c_char, out: *mut *mut gpuq_plan) -> c_int;
     pub fn gpuq_plan_free(plan: *mut gpuq_plan);

@@ -49,6 +49,16 @@ typedef enum gpuq_status {
   GPUQ_ERR_PEER = 8          /* exchange: a rank of the node announced a failure (or cannot hold what it would receive); no payload moved */
 } gpuq_status;
 
+/* Which refusal a GPUQ_ERR_UNSUPPORTED was, where a caller answers it by doing the work in another form (the native plan executor
+   does, for the first two; a driver hands a plan with a node of the third kind to another executor).  The message is for people;
+   this is what code branches on.  See gpuq_last_refusal. */
+typedef enum gpuq_refusal {
+  GPUQ_REFUSAL_NONE = 0,             /* any other reason: final */
+  GPUQ_REFUSAL_LONG_STRING = 1,      /* a Utf8 value longer than 15 bytes reached a packed key or comparison */
+  GPUQ_REFUSAL_WIDE_SORT_KEY = 2,    /* the composite sort key needs more than 128 bits */
+  GPUQ_REFUSAL_NODE_NOT_NATIVE = 3   /* gpuq_plan_create: a node type the native executor does not run */
+} gpuq_refusal;
+
 /* Logical types (subset of ballista/core/proto/datafusion.proto:1004-1040 ArrowType). */
 typedef enum gpuq_type {
   GPUQ_NULL = 0, GPUQ_BOOL = 1, GPUQ_INT32 = 2, GPUQ_INT64 = 3, GPUQ_DATE32 = 4, GPUQ_FLOAT64 = 5,
@@ -98,6 +108,10 @@ int gpuq_abi_version(void);
 gpuq_ctx* gpuq_ctx_create(int device_ordinal, const char* json_opts);
 void gpuq_ctx_free(gpuq_ctx* ctx);
 const char* gpuq_last_error(gpuq_ctx* ctx);
+/* The gpuq_refusal of the calling thread's last failing call, whichever gpuq_*_last_error its message went to.  Per calling thread,
+   like the messages; meaningful right after a call on this thread returned GPUQ_ERR_UNSUPPORTED (a call that fails with any other
+   status leaves GPUQ_REFUSAL_NONE, a call that succeeds leaves it alone).  gpuq_task_wait restores the worker thread's. */
+int gpuq_last_refusal(void);
 int gpuq_ctx_device_info(gpuq_ctx* ctx, char* buf, size_t cap); /* JSON: name, arch, cus, hbm_bytes */
 /* Tuning switches (strings): "join_dense" = "0" | "1" (default 1; env GPUQ_JOIN_DENSE at ctx creation): join tables over ONE
    Int32 / Int64 / Date32 key whose build values span a bounded range are direct-addressed arrays instead of hash tables;

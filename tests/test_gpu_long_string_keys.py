@@ -243,3 +243,56 @@ def test_long_string_comparison_in_a_filter_fused_into_an_aggregate_and_a_join(t
     j = g.HashJoinExec(g.MemoryExec([small]), f, [(col("jk", g.MemoryExec([small]).schema()), col("k", s))], None, "Inner", "CollectLeft", False)
     got, _ = native_rows(tc, j)
     assert sorted(r_[4] for r_ in got) == [i for i, x in enumerate(A) if _py_cmp("<", x, "Customer#000001017")]
+
+
+def test_both_join_sides_carry_a_fused_long_string_comparison(tc):
+    """The third rung with a predicate on EACH side: the join refuses plain, refuses over codes (the fused filters still compare long
+    strings), then both filters run on their own and the join runs over what they pass.  Checker: a dictionary join."""
+    lt, rt = _cmp_table(300, 41), _cmp_table(310, 42).rename_columns(["ra", "rb", "rk", "rid"])
+    L, R = g.MemoryExec([lt]), g.MemoryExec([rt])
+    ls, rs = L.schema(), R.schema()
+    lo, hi = "Customer#000001017", "Customer#000000015"
+    fl = g.FilterExec(binary(col("a", ls), Op.Lt, lit(lo)), L)
+    fr = g.FilterExec(binary(col("rb", rs), Op.GtEq, lit(hi)), R)
+    got, _ = native_rows(tc, g.HashJoinExec(fl, fr, [(col("k", ls), col("rk", rs))], None, "Inner", "CollectLeft", False))
+    by_k = collections.defaultdict(list)
+    for x, k, i in zip(lt["a"].to_pylist(), lt["k"].to_pylist(), lt["id"].to_pylist()):
+        if _py_cmp("<", x, lo):
+            by_k[k].append(i)
+    exp = [(i, j) for y, k, j in zip(rt["rb"].to_pylist(), rt["rk"].to_pylist(), rt["rid"].to_pylist()) if _py_cmp(">=", y, hi) for i in by_k[k]]
+    assert sorted((r_[3], r_[7]) for r_ in got) == sorted(exp) and len(exp) > 1000
+    assert all(r_[2] == r_[6] and _py_cmp("<", r_[0], lo) and _py_cmp(">=", r_[5], hi) for r_ in got)
+
+
+# ------------------------------------------------------------------ which refusal it was (gpuq_last_refusal / GpuqError.refusal)
+def test_operators_say_which_refusal_it_was(tc, mirror_layer):
+    """Operator calls through the binding, 600 rows: the two refusals the native executor answers carry their kind; refusals that only
+    read alike -- MIN / MAX beyond int64, a too-long value met while unpacking -- carry none."""
+    import decimal
+    from arrow_ballista_amd import binding as B
+    from test_gpu_expr_extremes import PACKED15, WIDE_MINMAX
+    n = 600
+    r = np.random.default_rng(600)
+    strs = ["k%03d" % (i % 50) for i in range(n)]
+    strs[417] = "exactly15bytes!!"      # 16 bytes
+    assert len(strs[417].encode()) == 16 and max(len(x) for x in strs[:417] + strs[418:]) <= 15
+    wide = [decimal.Decimal(int(v)) for v in r.integers(-100, 100, n)]
+    wide[5] = decimal.Decimal(2**64 + 1)
+    t = pa.table({"s": pa.array(strs), "a": r.integers(-2**62, 2**62, n), "b": r.integers(-2**62, 2**62, n), "c": r.integers(-2**62, 2**62, n),
+                  "w": pa.array(wide, pa.decimal128(20, 0)), "grp": pa.array(np.arange(n) % 7, pa.int64())})
+    src = g.MemoryExec([t]); s = src.schema()
+    with pytest.raises(g.GpuqError, match=PACKED15) as ei:
+        g.FilterExec(binary(col("s", s), Op.Lt, lit("k025")), src).execute(0, tc)
+    assert (ei.value.status, ei.value.refusal) == (3, B.REFUSAL_LONG_STRING)
+    order = [{"expr": col(c, s), "asc": True, "nulls_first": False} for c in ("a", "b", "c")]
+    with pytest.raises(g.GpuqError, match="composite sort key needs") as ei:
+        g.SortExec(order, src).execute(0, tc)
+    assert (ei.value.status, ei.value.refusal) == (3, B.REFUSAL_WIDE_SORT_KEY)
+    with pytest.raises(g.GpuqError, match=WIDE_MINMAX) as ei:
+        g.NativePlan(g.AggregateExec("Single", [(col("grp", s), "grp")], [{"fn": "MAX", "expr": col("w", s), "name": "m"}], src), tc).execute(0).to_arrow()
+    assert (ei.value.status, ei.value.refusal) == (3, B.REFUSAL_NONE)
+    packed = g.plan._project(tc, src.execute(0, tc), [col("s", s)], ["s"])      # a bare column comes out packed; its bytes are asked for below
+    assert packed.columns[0].repr == B.REPR_PACKED15
+    with pytest.raises(g.GpuqError, match="longer than 15 bytes went through") as ei:
+        packed.to_arrow(tc.ctx)
+    assert (ei.value.status, ei.value.refusal) == (3, B.REFUSAL_NONE)

@@ -114,3 +114,59 @@ def test_merge_of_sorted_runs_is_the_stable_sort_of_their_concatenation(tc, size
         assert np.array_equal(got, want)
         native = g.NativePlan(plan, tc).execute(0).to_arrow()
         assert np.array_equal(np.asarray(native.column("rid")), want)
+
+
+# ------------------------------------------------------------------ a composite key beyond 128 bits: one stable pass per key
+def wide_keys(r, n, pool):
+    """n values out of `pool` distinct ones from +-2^62 (63 key bits, with ties)."""
+    return r.integers(-2**62, 2**62, pool)[r.integers(0, pool, n)]
+
+
+@pytest.mark.parametrize("n", [513, 2000])
+def test_three_full_range_keys_are_sorted_by_one_pass_per_key(tc, n):
+    """Three Int64 keys from +-2^62 make a 189-bit composite (above the one-block sort's 512 rows the operator builds one and refuses):
+    SortExec then sorts by one stable pass per key, least significant first.  Ascending and descending mixed, ties in the first two keys,
+    then one nullable key with NULLs first and last; every plan twice (the second execution finds its operators by their rung and pass)."""
+    r = np.random.default_rng(n)
+    a, b, c = wide_keys(r, n, n // 8), wide_keys(r, n, n // 2), wide_keys(r, n, n)
+    mask = r.random(n) < 0.2
+    t = pa.table({"rid": np.arange(n, dtype=np.int64), "a": a, "b": b, "c": c, "bn": pa.array(b, mask=mask)})
+    t = t.cast(pa.schema([pa.field(f.name, f.type, nullable=f.name == "bn") for f in t.schema]))
+    src = g.MemoryExec([t]); s = src.schema()
+
+    def check(spec, want):
+        p = g.NativePlan(g.SortExec([{"expr": col(k, s), "asc": asc, "nulls_first": nf} for k, asc, nf in spec], src), tc)
+        for _ in range(2):
+            assert np.array_equal(np.asarray(p.execute(0).to_arrow().column("rid")), want), spec
+    check([("a", True, False), ("b", False, False), ("c", True, False)], np.lexsort((c, -b, a)))      # |b| < 2^62: no overflow
+    check([("a", False, True), ("b", True, True), ("c", False, True)], np.lexsort((-c, b, -a)))
+    for nulls_first in (True, False):
+        rank = np.where(mask, 0 if nulls_first else 2, 1)
+        check([("a", True, False), ("bn", False, nulls_first), ("c", True, False)], np.lexsort((c, np.where(mask, 0, -b), rank, a)))
+
+
+def test_median_grouped_by_five_full_range_keys(tc):
+    """MEDIAN(v) GROUP BY k1..k5 sorts by six keys: stable passes of four keys each, and the four Int64 keys from +-2^62 of the first
+    group do not fit 128 bits -- the segment aggregate goes on with one key a pass.  600 rows in 150 groups against a dictionary."""
+    n, groups = 600, 150
+    r = np.random.default_rng(150)
+    keys = r.integers(-2**62, 2**62, (groups, 5))
+    gid = r.permutation(np.concatenate([np.arange(groups), r.integers(0, groups, n - groups)]))
+    v = r.integers(-10**9, 10**9, n)
+    sizes = np.bincount(gid, minlength=groups)
+    assert len({tuple(k) for k in keys.tolist()}) == groups and sizes.min() >= 1 and (sizes % 2 == 0).sum() > 20 and (sizes % 2 == 1).sum() > 20
+    names = ["k%d" % i for i in range(1, 6)]
+    t = pa.table(dict({nm: keys[gid, i] for i, nm in enumerate(names)}, v=v))
+    src = g.MemoryExec([t]); s = src.schema()
+    plan = g.AggregateExec("Single", [(col(nm, s), nm) for nm in names], [{"fn": "MEDIAN", "expr": col("v", s), "name": "m"}], src)
+    want = {}
+    for k in range(groups):
+        x = sorted(v[gid == k].tolist())
+        h = len(x) // 2
+        two = x[h - 1] + x[h]
+        want[tuple(keys[k].tolist())] = x[h] if len(x) % 2 else (two // 2 if two >= 0 else -((-two) // 2))      # the mean of two middles: toward zero
+    p = g.NativePlan(plan, tc)
+    for _ in range(2):
+        out = p.execute(0).to_arrow()
+        got = {tuple(row[nm] for nm in names): row["m"] for row in out.to_pylist()}
+        assert out.num_rows == groups and got == want
