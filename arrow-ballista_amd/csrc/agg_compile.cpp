@@ -133,7 +133,17 @@ struct Scan {
   bool ungrouped = false;
   std::string fn;               // the function being compiled as the descriptor names it, upper-cased: error texts quote it
   const Json* desc = nullptr;   // ... and its aggr_expr entry
-  explicit Scan(const Schema& in) : ec(in) {}
+  // The moment aggregates sum over x - K.  K is run-time parameter k of the scan program and of the result projection
+  // (ExprCompiler::param_f64); it is picked, on the device, from the values `origin_of[k]` takes on the rows that take part: a
+  // second small program (`pick`, the same predicate) has them as its outputs.  One K per distinct argument.
+  ExprCompiler pick;
+  std::vector<NodeP> origin_of;
+  explicit Scan(const Schema& in) : ec(in), pick(in) {}
+  int origin(const NodeP& candidate) {
+    for (size_t k = 0; k < origin_of.size(); ++k) if (origin_of[k]->key == candidate->key) return (int)k;
+    if ((int)origin_of.size() >= MAX_ORIGINS) throw Unsupported("aggregate needs more than " + std::to_string(MAX_ORIGINS) + " moment arguments");
+    origin_of.push_back(candidate); pick.add_output(candidate); return (int)origin_of.size() - 1;
+  }
 
   int acc(int kind, NodeP arg, const DType& type) {
     for (size_t i = 0; i < accs.size(); ++i)
@@ -186,7 +196,8 @@ struct AggPlan {
   bool arg_nullable = false;    // the value goes through NULLIF0 on cnt (Scan::may_be_null of the argument)
   int arg_precision = 0;        // AVG over decimals: the argument's precision
   int cnt = -1, sum = -1, mm = -1;      // count / sum / min-max accumulators
-  int sx = -1, sy = -1, sxx = -1, syy = -1, sxy = -1;      // variance family: f64 power sums
+  int sx = -1, sy = -1, sxx = -1, syy = -1, sxy = -1;      // variance family: f64 power sums about the origins
+  int kx = -1, ky = -1;         // ... and which origins (Scan::origin)
 };
 
 // The result side: a post program over the SoA result [key_0.., acc_0..] and the names of its outputs
@@ -201,23 +212,31 @@ struct Post {
 
 // VARIANCE / STDDEV / COVARIANCE / CORRELATION (datafusion.proto:639-645).  The reference keeps Welford-style
 // running (count, mean, m2[, algo_const]) states [UPSTREAM-KNOWLEDGE]; a data-parallel device cannot follow a
-// row order, so the accumulators are the order-free power sums n, Sx, Sy, Sxx, Syy, Sxy in f64 and the
-// reference's state columns are derived from them (mean = Sx/n, m2 = Sxx - Sx^2/n, algo = Sxy - Sx*Sy/n).
-// Results agree with the reference to f64 rounding (tolerance stated in tests/test_gpu_operators.py).
+// row order, so the accumulators are order-free power sums in f64 -- of d = x - Kx and e = y - Ky, not of x and y:
+// n, Sx = sum d, Sy = sum e, Sxx = sum d*d, Syy = sum e*e, Sxy = sum d*e, and the reference's state columns are derived
+// from them (mean = Kx + Sx/n, m2 = Sxx - Sx^2/n, algo = Sxy - Sx*Sy/n).  The origin K is one value per argument and
+// run, picked on the device from the rows that take part (Scan::origin; a Final picks it from the state means), so it
+// lies inside the data's range R = max - min and |d| <= R: the subtraction in m2 then cancels like (R/sigma)^2
+// whatever the data's offset from zero, where sums of x itself cancel like (mean/sigma)^2 -- STDDEV over a second of
+// microsecond timestamps was noise.  |error(m2)| <= (3n + 8) * 2^-53 * (M2 + n R^2); tests/float_agg_exact.py states
+// the bound, DESIGN.md ("Accuracy of the moment aggregates") what it leaves open: R spans every group of the operator.
 // Both directions of the conversion, over a group's count n:
 struct Moments {
   ExprCompiler& c; NodeP n, nf, zero;
   Moments(ExprCompiler& c_, NodeP count) : c(c_), n(count), nf(c_.cast(count, F64)), zero(c_.lit_f64(0.0)) {}
-  // states -> power sums, to be added up (a Final's scan program): Sa = n * mean_a, Sab = central_ab + n * mean_a * mean_b
-  NodeP sum(NodeP mean) { return c.binary("*", nf, mean); }
-  NodeP product_sum(NodeP central, NodeP mean_a, NodeP mean_b) { return c.binary("+", central, c.binary("*", nf, c.binary("*", mean_a, mean_b))); }
+  // states -> power sums about (Ka, Kb), to be added up (a Final's scan program): Sa = n * (mean_a - Ka),
+  // Sab = central_ab + n * (mean_a - Ka) * (mean_b - Kb)
+  NodeP sum(NodeP off_a) { return c.binary("*", nf, off_a); }
+  NodeP product_sum(NodeP central, NodeP off_a, NodeP off_b) { return c.binary("+", central, c.binary("*", nf, c.binary("*", off_a, off_b))); }
   // power sums -> states and statistics (the result projection)
   NodeP F(int op, NodeP l, NodeP r) { return c.raw(op, F64, false, 127, {l, r}); }
   NodeP sqrt(NodeP v) { return c.raw(OP_FSQRT, F64, false, 127, {v}); }
   NodeP n_is0() { return c.binary("=", n, c.lit_int(I64, 0)); }
   NodeP when0(NodeP v) { return c.select(n_is0(), zero, v); }                    // state columns of an empty group are 0
   NodeP nonneg(NodeP v) { return c.select(c.raw(OP_FLT, BOOL, false, 1, {v, zero}), zero, v); }   // rounding can leave -eps
-  NodeP mean(NodeP sa) { return when0(F(OP_FDIV, sa, nf)); }
+  // the mean state of an empty group is 0, like every state column: NULL where n is 0, then NULL as 0 -- both in place, no register
+  // for the test or the zero (tests/test_cpu_agg_compile.py, nine_aggregates: that Partial's states fit one post program only so)
+  NodeP mean(NodeP sa, NodeP k) { return c.coalesce0(c.nullif0(F(OP_FADD, k, F(OP_FDIV, sa, nf)), n)); }
   NodeP central(NodeP sab, NodeP sa, NodeP sb) { return when0(F(OP_FSUB, sab, F(OP_FDIV, F(OP_FMUL, sa, sb), nf))); }
   NodeP m2(NodeP saa, NodeP sa) { return nonneg(central(saa, sa, sa)); }
   // sample statistics divide by n - 1 and need n >= 2, population by n and n >= 1; NULL otherwise
@@ -332,6 +351,12 @@ struct BoolAgg {
   static void states(Post& p, const AggPlan& pl) { p.out(truth(p, pl), pl.name + pl.fn->state); }
   static void value(Post& p, const AggPlan& pl) { p.out(truth(p, pl), pl.name); }
 };
+// an argument (or a state mean) about its origin: x - K, NULL where x is
+NodeP about(ExprCompiler& ec, const NodeP& x, int k) { return ec.binary("-", x, ec.param_f64(k)); }
+// what a Final picks an origin from: the mean of a state row that stands for at least one input row (an empty group's mean is 0, not data)
+NodeP mean_of_rows(ExprCompiler& ec, const NodeP& count, const NodeP& mean) {
+  return ec.select(ec.binary(">", ec.cast(count, I64), ec.lit_int(I64, 0)), mean, ec.lit_null(F64));
+}
 // the two-argument functions skip a row where either argument is NULL, for every sum
 void pair_up(ExprCompiler& ec, NodeP& x, NodeP& y) {
   NodeP both = ec.binary("AND", ec.is_null(x, true), ec.is_null(y, true));
@@ -340,18 +365,22 @@ void pair_up(ExprCompiler& ec, NodeP& x, NodeP& y) {
 struct Variance {      // and its square root
   static void from_args(Scan& s, AggPlan& pl, NodeP arg) {
     NodeP x = s.f64_arg(arg);
-    pl.cnt = s.count(x); pl.sx = s.fsum(x); pl.sxx = s.fsum(s.ec.binary("*", x, x));
+    pl.kx = s.origin(x);
+    NodeP d = about(s.ec, x, pl.kx);
+    pl.cnt = s.count(x); pl.sx = s.fsum(d); pl.sxx = s.fsum(s.ec.binary("*", d, d));
   }
   static void from_states(Scan& s, AggPlan& pl, States& st) {
     NodeP c = st.take(); Moments M(s.ec, c);
     pl.cnt = s.state_count(c);
     NodeP mean = st.take_f64(), m2 = st.take_f64();
-    pl.sx = s.state_sum(M.sum(mean)); pl.sxx = s.state_sum(M.product_sum(m2, mean, mean));
+    pl.kx = s.origin(mean_of_rows(s.ec, c, mean));
+    NodeP d = about(s.ec, mean, pl.kx);
+    pl.sx = s.state_sum(M.sum(d)); pl.sxx = s.state_sum(M.product_sum(m2, d, d));
   }
   static void states(Post& p, const AggPlan& pl) {
     Moments M(p.pc, p.acc(pl.cnt));
     p.out(p.pc.cast(M.n, U64), pl.name + "[count]");
-    p.out(M.mean(p.acc(pl.sx)), pl.name + "[mean]");
+    p.out(M.mean(p.acc(pl.sx), p.pc.param_f64(pl.kx)), pl.name + "[mean]");
     p.out(M.m2(p.acc(pl.sxx), p.acc(pl.sx)), pl.name + "[m2]");
   }
   static void value(Post& p, const AggPlan& pl) {
@@ -365,19 +394,23 @@ struct Covariance {
   static void from_args(Scan& s, AggPlan& pl, NodeP arg) {
     NodeP x = s.f64_arg(arg), y = s.second_f64_arg();
     pair_up(s.ec, x, y);
-    pl.cnt = s.count(x); pl.sx = s.fsum(x); pl.sy = s.fsum(y); pl.sxy = s.fsum(s.ec.binary("*", x, y));
+    pl.kx = s.origin(x); pl.ky = s.origin(y);
+    NodeP d = about(s.ec, x, pl.kx), e = about(s.ec, y, pl.ky);
+    pl.cnt = s.count(x); pl.sx = s.fsum(d); pl.sy = s.fsum(e); pl.sxy = s.fsum(s.ec.binary("*", d, e));
   }
   static void from_states(Scan& s, AggPlan& pl, States& st) {
     NodeP c = st.take(); Moments M(s.ec, c);
     pl.cnt = s.state_count(c);
     NodeP mean1 = st.take_f64(), mean2 = st.take_f64(), algo = st.take_f64();
-    pl.sx = s.state_sum(M.sum(mean1)); pl.sy = s.state_sum(M.sum(mean2)); pl.sxy = s.state_sum(M.product_sum(algo, mean1, mean2));
+    pl.kx = s.origin(mean_of_rows(s.ec, c, mean1)); pl.ky = s.origin(mean_of_rows(s.ec, c, mean2));
+    NodeP d = about(s.ec, mean1, pl.kx), e = about(s.ec, mean2, pl.ky);
+    pl.sx = s.state_sum(M.sum(d)); pl.sy = s.state_sum(M.sum(e)); pl.sxy = s.state_sum(M.product_sum(algo, d, e));
   }
   static void states(Post& p, const AggPlan& pl) {
     Moments M(p.pc, p.acc(pl.cnt));
     p.out(p.pc.cast(M.n, U64), pl.name + "[count]");
-    p.out(M.mean(p.acc(pl.sx)), pl.name + "[mean1]");
-    p.out(M.mean(p.acc(pl.sy)), pl.name + "[mean2]");
+    p.out(M.mean(p.acc(pl.sx), p.pc.param_f64(pl.kx)), pl.name + "[mean1]");
+    p.out(M.mean(p.acc(pl.sy), p.pc.param_f64(pl.ky)), pl.name + "[mean2]");
     p.out(M.central(p.acc(pl.sxy), p.acc(pl.sx), p.acc(pl.sy)), pl.name + "[algoConst]");
   }
   static void value(Post& p, const AggPlan& pl) {
@@ -389,23 +422,27 @@ struct Correlation {
   static void from_args(Scan& s, AggPlan& pl, NodeP arg) {
     NodeP x = s.f64_arg(arg), y = s.second_f64_arg();
     pair_up(s.ec, x, y);
-    pl.cnt = s.count(x); pl.sx = s.fsum(x); pl.sxx = s.fsum(s.ec.binary("*", x, x));
-    pl.sy = s.fsum(y); pl.sxy = s.fsum(s.ec.binary("*", x, y)); pl.syy = s.fsum(s.ec.binary("*", y, y));
+    pl.kx = s.origin(x); pl.ky = s.origin(y);
+    NodeP d = about(s.ec, x, pl.kx), e = about(s.ec, y, pl.ky);
+    pl.cnt = s.count(x); pl.sx = s.fsum(d); pl.sxx = s.fsum(s.ec.binary("*", d, d));
+    pl.sy = s.fsum(e); pl.sxy = s.fsum(s.ec.binary("*", d, e)); pl.syy = s.fsum(s.ec.binary("*", e, e));
   }
   static void from_states(Scan& s, AggPlan& pl, States& st) {
     NodeP c = st.take(); Moments M(s.ec, c);
     pl.cnt = s.state_count(c);
     NodeP mean1 = st.take_f64(), m2_1 = st.take_f64(), mean2 = st.take_f64(), m2_2 = st.take_f64(), algo = st.take_f64();
-    pl.sx = s.state_sum(M.sum(mean1)); pl.sxx = s.state_sum(M.product_sum(m2_1, mean1, mean1));
-    pl.sy = s.state_sum(M.sum(mean2)); pl.syy = s.state_sum(M.product_sum(m2_2, mean2, mean2));
-    pl.sxy = s.state_sum(M.product_sum(algo, mean1, mean2));
+    pl.kx = s.origin(mean_of_rows(s.ec, c, mean1)); pl.ky = s.origin(mean_of_rows(s.ec, c, mean2));
+    NodeP d = about(s.ec, mean1, pl.kx), e = about(s.ec, mean2, pl.ky);
+    pl.sx = s.state_sum(M.sum(d)); pl.sxx = s.state_sum(M.product_sum(m2_1, d, d));
+    pl.sy = s.state_sum(M.sum(e)); pl.syy = s.state_sum(M.product_sum(m2_2, e, e));
+    pl.sxy = s.state_sum(M.product_sum(algo, d, e));
   }
   static void states(Post& p, const AggPlan& pl) {
     Moments M(p.pc, p.acc(pl.cnt));
     p.out(p.pc.cast(M.n, U64), pl.name + "[count]");
-    p.out(M.mean(p.acc(pl.sx)), pl.name + "[mean1]");
+    p.out(M.mean(p.acc(pl.sx), p.pc.param_f64(pl.kx)), pl.name + "[mean1]");
     p.out(M.m2(p.acc(pl.sxx), p.acc(pl.sx)), pl.name + "[m2_1]");
-    p.out(M.mean(p.acc(pl.sy)), pl.name + "[mean2]");
+    p.out(M.mean(p.acc(pl.sy), p.pc.param_f64(pl.ky)), pl.name + "[mean2]");
     p.out(M.m2(p.acc(pl.syy), p.acc(pl.sy)), pl.name + "[m2_2]");
     p.out(M.central(p.acc(pl.sxy), p.acc(pl.sx), p.acc(pl.sy)), pl.name + "[algoConst]");
   }
@@ -501,6 +538,11 @@ AggCompiled compile_aggregate(const Schema& in, const Json& d) {
   for (auto& k : keys.nodes) key_slots.push_back(ec.add_output(k));
   for (size_t i = 0; i < accs.size(); ++i) if (accs[i].arg) acc_slots[i] = ec.add_output(accs[i].arg);
   R.prog = ec.finish();
+  if (!s.origin_of.empty()) {      // (the predicate is a node of `ec`: a program is assembled from the DAG alone, whichever compiler built it)
+    if (d.has("predicate")) s.pick.add_predicate(ec.from_json(d.at("predicate")));
+    R.pick = s.pick.finish();
+    R.n_origins = (int)s.origin_of.size();
+  }
   const int nk = (int)keys.nodes.size();
   R.agg.n_keys = nk; R.agg.n_accs = (int)accs.size();
   std::vector<int> kregs; bool any_null_key = false;

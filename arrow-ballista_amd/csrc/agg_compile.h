@@ -18,6 +18,10 @@ struct AggCompiled {
   std::string mode = "Single", strategy = "auto";
   i64 expected_groups = 0;
   CompiledProgram prog;             // the scan program: outputs are the keys, then the accumulator arguments
+  // The moment aggregates (VARIANCE .. CORRELATION) sum about origins picked at run time: run-time parameter k (param_imm of `prog`
+  // and of every post program that reads it) is output k of `pick`, a program over the same input with the same predicate, taken
+  // from the first row that passes and is not NULL there.  n_origins == 0: no moment aggregate, `pick` is empty.
+  CompiledProgram pick; int n_origins = 0;
   AggSpec agg{}; KeySpec keys{};
   std::vector<DType> key_types, acc_types;
   std::vector<int> acc_bits;        // |argument| < 2^bits per accumulator (type-derived)

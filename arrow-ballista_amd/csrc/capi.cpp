@@ -66,6 +66,8 @@ struct gpuq_op {
   std::map<std::tuple<const void*, int, size_t>, const JitFn*> jit_fns;      // (program, sink kernel, specialisation) -> compiled function
   struct PostChunk { CompiledProgram prog; DevBuf code; int first_out = 0; };
   std::deque<PostChunk> posts; Schema post_schema;
+  // the moment aggregates' origins (agg_compile.h): the program they are picked with and, in device memory, where they go
+  CompiledProgram pick; DevBuf pick_code, origins_dev, origin_rows; int n_origins = 0;
   i64 expected_groups = 0;
   int agg_path = 0;                 // the way this operator's last run took (Learned::ag::path numbering; 0: it has not run)
   // join
@@ -405,6 +407,22 @@ static void compile_op(gpuq_op* op, const Json& d) {
         op->posts.emplace_back(); gpuq_op::PostChunk& pc = op->posts.back();
         pc.prog = std::move(p.prog); pc.first_out = p.first_out; upload_code(pc.prog, pc.code);
       }
+      op->n_origins = c.n_origins;
+      if (op->n_origins > 0) {
+        op->pick = std::move(c.pick); upload_code(op->pick, op->pick_code);
+        // every immediate slot an origin is read from: the scan program's and the post programs'
+        OriginPick O{}; O.n_origins = op->n_origins;
+        for (int k = 0; k < op->n_origins; ++k) O.reg[k] = op->pick.out_reg[k];
+        auto dsts_of = [&](const CompiledProgram& cp, DevBuf& code) {
+          for (const auto& [k, slot] : cp.param_imm) {
+            if (O.n_dsts >= MAX_ORIGIN_DSTS) throw Unsupported("aggregate reads its origins in more than " + std::to_string(MAX_ORIGIN_DSTS) + " places");
+            O.dst_origin[O.n_dsts] = k; O.dst[O.n_dsts] = g_upload ? &code.as<DevCode>()->imm_lo[slot] : nullptr; ++O.n_dsts;
+          }
+        };
+        dsts_of(op->prog, op->code_dev);
+        for (auto& pc : op->posts) dsts_of(pc.prog, pc.code);
+        if (g_upload) { op->origins_dev.ensure(sizeof(OriginPick)); HIPCHECK(hipMemcpy(op->origins_dev.p, &O, sizeof(OriginPick), hipMemcpyHostToDevice)); }
+      }
     } else if (kind == "join_build" || kind == "join_probe") {
       op->kind = kind == "join_build" ? K_JOIN_BUILD : K_JOIN_PROBE;
       ExprCompiler ec(op->in_schema);
@@ -523,6 +541,11 @@ int gpuq_compile_check(const char* json, char* buf, size_t cap) {
       r += "],\"acc_kinds\":[";
       for (int a = 0; a < op->agg.n_accs; ++a) { if (a) r += ","; r += std::to_string(op->agg.acc_kind[a]); }
       r += std::string("],\"state_key\":") + (op->keys.state_key ? "true" : "false");      // the key fits the slot's state word (hash strategy)
+      if (op->n_origins > 0) {      // moment aggregates only: the program their origins are picked with, and which immediate slot of the scan program reads each
+        r += ",\"pick\":" + describe_program(op->pick, op->in_schema) + ",\"origin_imm\":[";
+        for (size_t i = 0; i < op->prog.param_imm.size(); ++i) { if (i) r += ","; r += "[" + std::to_string(op->prog.param_imm[i].first) + "," + std::to_string(op->prog.param_imm[i].second) + "]"; }
+        r += "]";
+      }
     }
     r += ",\"outputs\":[";
     for (size_t i = 0; i < op->out_fields.size(); ++i) {
@@ -688,6 +711,14 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
     DevProgram P = bind_input(op, in);
     const i64 n = in->n_rows;
     const int nk = op->agg.n_keys, na = op->agg.n_accs, kstride = nk > 0 ? nk : 1;
+    // the origins of the moment aggregates, before anything reads them: three small stream-ordered steps, whichever strategy follows.
+    // The pick program shares the operator's status word and runs before any reset of it (the deferred form resets nothing): a
+    // string or checked-decimal instruction of an argument can raise its bit here as well.  That changes nothing: the scan program
+    // holds the same instructions over the same rows and raises the same bits after the reset, and bits are only ever OR-ed.
+    if (op->n_origins > 0) {
+      unsigned int* first_row = (unsigned int*)op->origin_rows.ensure(MAX_ORIGINS * sizeof(unsigned int));
+      launch_agg_origin_pick(s, bind_program(op->pick, op->in_schema, op->pick_code.as<DevCode>(), op->flags_dev.as<uint32_t>(), in), n, op->origins_dev.as<OriginPick>(), first_row);
+    }
     uint32_t ng = 0;
     AggOut raw{};
     // the keys as the table of THIS run holds them: state_key only when the plain global-table kernel fills it (launch_table)

@@ -191,6 +191,11 @@ NodeP ExprCompiler::lit_f64(double v) {
   u64 b; std::memcpy(&b, &v, 8); n->lit_lo = b; n->key = "lf:" + std::to_string(b);
   return intern(n);
 }
+NodeP ExprCompiler::param_f64(int k) {
+  auto n = std::make_shared<Node>();
+  n->kind = Node::LIT; n->type.id = T_FLOAT64; n->nullable = false; n->param = k; n->key = "pf:" + std::to_string(k);
+  return intern(n);
+}
 NodeP ExprCompiler::lit_f32(float v) {      // registers hold a Float32 as the double of the same value
   auto n = std::make_shared<Node>();
   n->kind = Node::LIT; n->type.id = T_FLOAT32; n->nullable = false;
@@ -800,11 +805,16 @@ CompiledProgram ExprCompiler::finish() {
   for (size_t i = 0; i < C.col_field.size(); ++i) busy[i] = true;
   auto alloc = [&]() { for (int r = 0; r < NREG; ++r) if (!busy[r]) { busy[r] = true; return r; } throw std::runtime_error("expression needs more than " + std::to_string(NREG) + " live registers"); return -1; };
   std::vector<std::pair<u64, u64>> imms;
-  auto imm_index = [&](u64 lo, u64 hi) {
-    for (size_t i = 0; i < imms.size(); ++i) if (imms[i].first == lo && imms[i].second == hi) return (int)i;
+  std::vector<bool> imm_is_param;      // a run-time parameter's slot is written on the device: no literal may share it
+  auto imm_new = [&](u64 lo, u64 hi, bool is_param) {
     if ((int)imms.size() >= MAX_IMMS) throw std::runtime_error("expression needs more than " + std::to_string(MAX_IMMS) + " immediates");
-    imms.push_back({lo, hi}); return (int)imms.size() - 1;
+    imms.push_back({lo, hi}); imm_is_param.push_back(is_param); return (int)imms.size() - 1;
   };
+  auto imm_index = [&](u64 lo, u64 hi) {
+    for (size_t i = 0; i < imms.size(); ++i) if (!imm_is_param[i] && imms[i].first == lo && imms[i].second == hi) return (int)i;
+    return imm_new(lo, hi, false);
+  };
+  param_slot_.clear();
   auto emit = [&](int op, int d, int a, int b, uint32_t imm) {
     if (C.n_insns >= MAX_INSNS) throw std::runtime_error("expression program longer than " + std::to_string(MAX_INSNS) + " instructions");
     DevInsn& in = C.code.insns[C.n_insns++];
@@ -816,6 +826,7 @@ CompiledProgram ExprCompiler::finish() {
     if (n->kind == Node::COL) continue;
     if (n->kind == Node::LIT) {
       const int d = alloc(); reg[n] = d;
+      if (n->param >= 0) { const int slot = imm_new(0, 0, true); param_slot_[n] = slot; C.param_imm.push_back({n->param, slot}); emit(OP_IMM, d, 0, 0, (uint32_t)slot); continue; }
       if (n->lit_null) { emit(OP_IMM, d, 0, 0, (uint32_t)imm_index(0, 0)); emit(OP_NULLIF0, d, d, d, 0); }
       else emit(OP_IMM, d, 0, 0, (uint32_t)imm_index(n->lit_lo, n->lit_hi));
       continue;
@@ -1020,6 +1031,16 @@ std::string ExprCompiler::jit_source(const CompiledProgram& C, const std::vector
     if (n->kind == Node::LIT) {
       if (n->lit_null) { nul[n] = "true"; if (is_str(n)) { L("const u64 " + t + "_lo = 0, " + t + "_hi = 0;"); } else L("const " + ctype(n) + " " + t + " = 0;"); name[n] = t; continue; }
       nul[n] = "false";
+      if (n->param >= 0) {
+        // the slot of the program block, through the constant address space like the interpreter's OP_IMM: a scalar load.  It is issued in
+        // the load stage, next to the column loads, so that the compute stage does not wait for it on its own (the field is not
+        // "touched": it stays in scalar registers)
+        const std::string f = "p" + std::to_string(n->param);
+        FR += "  u64 " + f + ";\n";
+        LL("w." + f + " = *(const unsigned long long __attribute__((address_space(4)))*)(unsigned long long)(const void*)&P.code->imm_lo[" + std::to_string(param_slot_.at(n)) + "];");
+        L("const double " + t + " = __longlong_as_double((i64)w." + f + ");");
+        name[n] = t; continue;
+      }
       if (is_str(n)) L("const u64 " + t + "_lo = " + std::to_string(n->lit_lo) + "ull, " + t + "_hi = " + std::to_string(n->lit_hi) + "ull;");
       else if (is_f(n)) L("const double " + t + " = __longlong_as_double((i64)" + std::to_string(n->lit_lo) + "ull);");
       else if (is_b(n)) L("const bool " + t + " = " + (n->lit_lo ? "true" : "false") + ";");

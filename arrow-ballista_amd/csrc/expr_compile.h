@@ -86,6 +86,7 @@ struct Node {
   int col = -1;              // COL: schema field index
   u64 lit_lo = 0, lit_hi = 0; bool lit_null = false;   // LIT
   bool lit_long = false;     // LIT: a Utf8 literal beyond 15 bytes -- lit_lo / lit_hi pack its first 15; only a comparison may consume it (binary())
+  int param = -1;            // LIT: >= 0 -- a Float64 the device supplies before the program runs (ExprCompiler::param_f64); the value fields are unused
   std::string key;           // canonical text, CSE key
 };
 
@@ -101,6 +102,7 @@ struct CompiledProgram {
   std::vector<std::string> out_key;
   std::vector<int> out_bits;    // |value| < 2^bits for every output (from the declared types; 127 = unknown)
   bool checks_overflow = false; // holds a checked decimal instruction (OP_ADDC / OP_SUBC / OP_MULC): a run may raise FLAG_DEC_OVERFLOW
+  std::vector<std::pair<int, int>> param_imm;   // (run-time parameter, the immediate slot it is read from): ExprCompiler::param_f64
   std::string jit_src;          // C++ source of gpuq_jit_eval() for this program (typed, straight-line)
 };
 
@@ -113,6 +115,10 @@ class ExprCompiler {
   NodeP lit_int(DType t, i128 v);
   NodeP lit_f64(double v);
   NodeP lit_f32(float v);
+  // Run-time parameter k: a Float64 that is not known when the program is compiled.  It is read from an immediate slot of the
+  // uploaded DevCode that no literal shares (CompiledProgram::param_imm says which); whoever launches the program has a kernel
+  // write the slot, in stream order, before.  The interpreter and the generated code both read the slot, neither holds the value.
+  NodeP param_f64(int k);
   NodeP floor_div(NodeP e, i64 d, DType rt);
   NodeP rescale_time(NodeP e, i64 from_per_s, i64 to_per_s, DType rt);
   NodeP lit_null(DType t);
@@ -139,6 +145,7 @@ class ExprCompiler {
   NodeP pred_;
   std::vector<NodeP> outs_;
   std::map<std::string, NodeP> interned_;
+  std::map<const Node*, int> param_slot_;      // finish(): parameter node -> immediate slot, for jit_source
   NodeP intern(NodeP n);
   std::string jit_source(const CompiledProgram& C, const std::vector<Node*>& order, const std::map<Node*, int>& reg);
 };

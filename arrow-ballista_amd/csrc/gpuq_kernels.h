@@ -30,6 +30,19 @@ struct AggSpec {
   int32_t acc_reg[MAX_ACCS];
 };
 
+// The origins of the moment aggregates (agg_compile.cpp, Moments): origin k is register reg[k] of the pick program on the lowest
+// row that passes its predicate and is not NULL there -- 0.0 when there is no such row or the value is not finite.  It is stored
+// to every dst[i] with dst_origin[i] == k: the immediate slots of the uploaded programs that read it.  Built once per operator
+// and kept in device memory.
+constexpr int MAX_ORIGINS = 8;
+constexpr int MAX_ORIGIN_DSTS = 40;
+struct OriginPick {
+  int32_t n_origins, n_dsts;
+  int32_t reg[MAX_ORIGINS];
+  int32_t dst_origin[MAX_ORIGIN_DSTS];
+  u64* dst[MAX_ORIGIN_DSTS];
+};
+
 // Result layout shared by the tiny and hash aggregates (device memory, caller allocated):
 //   keys  [cap][n_keys] as (lo,hi) u64 pairs      key_nulls[cap] bitmask over keys
 //   cells [cap][n_accs] as (lo,hi) u64 pairs      n_groups (device u32)
@@ -367,6 +380,8 @@ void launch_agg_tiny_merge(hipStream_t s, const DevProgram& P, i64 n, const AggS
 void launch_ht_init(hipStream_t s, const HashTable& T, const AggSpec* A);
 void launch_agg_hash(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const AggSpec& A, const HashTable& T);
 void launch_key_sample(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, i64 stride, i64 nsample, uint32_t* bitmap, u64 nbits, unsigned long long* passed);
+// origins_dev: device memory; first_row: MAX_ORIGINS device words of scratch (the lowest row that takes part, per origin)
+void launch_agg_origin_pick(hipStream_t s, const DevProgram& pick, i64 n, const OriginPick* origins_dev, unsigned int* first_row);
 uint32_t agg_lds_slots(const HashTable& T);
 int agg_lds_grid(i64 n);
 void launch_agg_lds(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const AggSpec& A, const HashTable& T, u64* fstage, int n_fsum);

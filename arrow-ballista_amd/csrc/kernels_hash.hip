@@ -648,6 +648,65 @@ __global__ void __launch_bounds__(HBLOCK) k_key_sample(const DevProgram P, const
   __syncthreads();
   if (threadIdx.x == 0 && block_passed) atomicAdd(passed, (unsigned long long)block_passed);
 }
+
+// ------------------------------------------------------------------ origins of the moment aggregates
+// Origin k is the argument's value on the LOWEST row that takes part (the predicate holds, the argument is not NULL), so a run over
+// the same input picks the same one.  Two launches.  k_agg_origin_find: a grid of blocks takes the input in steps of HBLOCK rows, block
+// b the steps b, b + grid, ..., and folds the rows that take part into first_row[k] (device words the host sets to NULL_ROW) with
+// atomicMin.  A block stops at the first step that cannot lower any of them -- every first_row[k] is at or below the step's first row,
+// or the input has ended -- so ordinary data costs every block one step or none, and input whose leading rows take no part (a
+// predicate that keeps the tail of a sorted table) is searched by the whole grid, not by one block.  The words only ever fall and
+// only to rows that take part, so a stale read delays a block's stop and never makes it early.  k_agg_origin_store: one block
+// evaluates the rows found and stores each origin where the programs read it (none of them is the pick program: it holds no parameter).
+// Whether a block goes on is decided by one thread and handed over in LDS between two barriers: the loop and its barriers are
+// block-uniform.
+constexpr int ORIGIN_FIND_BLOCKS = 512;
+template <int MAXC>
+__global__ void __launch_bounds__(HBLOCK) k_agg_origin_find(const DevProgram P, const i64 n, const OriginPick* __restrict__ Op, unsigned int* __restrict__ first_row) {
+  const OriginPick& O = *Op;      // (device memory: a by-value struct indexed by a loop counter would be copied to scratch)
+  __shared__ int go_on;
+  const i64 rows = rows_of(P, n);
+  const int n_origins = O.n_origins;
+  for (i64 step = blockIdx.x; ; step += gridDim.x) {
+    const i64 base = step * HBLOCK;
+    if (threadIdx.x == 0) {
+      int need = 0;
+      if (base < rows) for (int k = 0; k < n_origins; ++k) need |= (i64)__hip_atomic_load(first_row + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > base;
+      go_on = need;
+    }
+    __syncthreads();
+    const int go = go_on;
+    __syncthreads();      // (every thread has read go_on before thread 0 writes the next step's)
+    if (!go) break;
+    const i64 pos = base + threadIdx.x;
+    bool active = pos < rows;
+    GPUQ_REGS_DECL;
+    if (active) active = GPUQ_EVAL(MAXC, P, pos);
+    for (int k = 0; k < n_origins; ++k) {
+      const int r = __builtin_amdgcn_readfirstlane(O.reg[k]);
+      const u64 m = __ballot(active && !((rnulls >> r) & 1u));
+      if (m && lane() == (int)__builtin_ctzll(m)) atomicMin(first_row + k, (unsigned int)pos);      // (the wave's lowest such row)
+    }
+  }
+}
+template <int MAXC>
+__global__ void __launch_bounds__(64) k_agg_origin_store(const DevProgram P, const OriginPick* __restrict__ Op, const unsigned int* __restrict__ first_row) {
+  const OriginPick& O = *Op;
+  __shared__ u64 value[MAX_ORIGINS];
+  for (int k = 0; k < O.n_origins; ++k) {      // one wave; every lane evaluates the same row
+    const unsigned int row = first_row[k];
+    u64 v = 0;      // no row takes part: 0.0
+    if (row != NULL_ROW) {
+      GPUQ_REGS_DECL;
+      (void)GPUQ_EVAL(MAXC, P, (i64)row);
+      v = rlo[__builtin_amdgcn_readfirstlane(O.reg[k])];
+      if (((v >> 52) & 0x7FFull) == 0x7FFull) v = 0;      // infinity or NaN: the sums are not finite either way, the origin must be
+    }
+    if (threadIdx.x == 0) value[k] = v;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < O.n_dsts; i += 64) *O.dst[i] = value[O.dst_origin[i]];
+}
 #endif
 
 // ------------------------------------------------------------------ block-local pre-aggregation (medium cardinality)
@@ -1575,6 +1634,12 @@ void launch_agg_hash(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, co
 void launch_key_sample(hipStream_t s, const DevProgram& P, i64 n, const KeySpec& K, i64 stride, i64 nsample, uint32_t* bitmap, u64 nbits, unsigned long long* passed) {
   if (n <= 0 || nsample <= 0) return;
   launch_sink(nullptr, P.n_cols, GPUQ_PICK(k_key_sample), dim3(hgrid(nsample, 8)), dim3(HBLOCK), 0, s, P, n, K, stride, nsample, bitmap, nbits - 1, passed);
+}
+void launch_agg_origin_pick(hipStream_t s, const DevProgram& pick, i64 n, const OriginPick* origins_dev, unsigned int* first_row) {
+  HIPCHECK(hipMemsetAsync(first_row, 0xFF, MAX_ORIGINS * sizeof(unsigned int), s));      // NULL_ROW: no row found
+  const i64 steps = (n + HBLOCK - 1) / HBLOCK;
+  if (steps > 0) launch_sink(nullptr, pick.n_cols, GPUQ_PICK(k_agg_origin_find), dim3((unsigned)std::min<i64>(steps, ORIGIN_FIND_BLOCKS)), dim3(HBLOCK), 0, s, pick, n, origins_dev, first_row);
+  launch_sink(nullptr, pick.n_cols, GPUQ_PICK(k_agg_origin_store), dim3(1), dim3(64), 0, s, pick, origins_dev, (const unsigned int*)first_row);
 }
 uint32_t agg_lds_slots(const HashTable& T) {      // LDS table size (slots) of the pre-aggregating kernel, 0 = a slot is too wide for it
   const size_t bytes = (size_t)(T.slot_words + 1) * 8;
