@@ -17,7 +17,7 @@ from .plan import (  # noqa: F401
     MemoryExec, FilterExec, ProjectionExec, AggregateExec, HashJoinExec, CrossJoinExec, SortExec, CoalesceBatchesExec,
     RepartitionExec, ShuffleWriterExec, ShuffleReaderExec, DefaultExecutionEngine, TaskContext,
     CoalesceTasksExec, CoalescePartitionsExec, SortPreservingMergeExec, UnionExec, LocalLimitExec, GlobalLimitExec,
-    RepartitionExchangeExec, BroadcastExec, RangeRepartitionExec,
+    RepartitionExchangeExec, BroadcastExec, RangeRepartitionExec, ParquetExec, CsvExec,
 )
 
 __all__ = [
@@ -26,4 +26,5 @@ __all__ = [
     "HashJoinExec", "CrossJoinExec", "SortExec", "CoalesceBatchesExec", "RepartitionExec", "ShuffleWriterExec", "ShuffleReaderExec",
     "DefaultExecutionEngine", "TaskContext", "CoalesceTasksExec", "CoalescePartitionsExec", "SortPreservingMergeExec",
     "UnionExec", "LocalLimitExec", "GlobalLimitExec", "RepartitionExchangeExec", "BroadcastExec", "RangeRepartitionExec",
+    "ParquetExec", "CsvExec",
 ]

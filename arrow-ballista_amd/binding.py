@@ -103,6 +103,7 @@ def lib():
         "gpuq_parquet_decode_groups": (i32, [vp, vp, vp, i64, C.POINTER(C.c_char_p), i32, C.POINTER(C.c_int32), i32, C.POINTER(vp)]),
         "gpuq_parquet_row_groups": (i32, [vp, i64, C.POINTER(i64), i32, C.POINTER(i32)]),
         "gpuq_parquet_schema": (i32, [vp, i64, C.POINTER(gpuq_field_info), i32, C.POINTER(i32), C.POINTER(i64)]),
+        "gpuq_parquet_prune": (i32, [vp, i64, C.c_char_p, C.POINTER(gpuq_field_info), i32, i64, i64, C.POINTER(C.c_int32), i32, C.POINTER(i32), C.POINTER(i32)]),
         "gpuq_scan_last_error": (C.c_char_p, []),
         "gpuq_table_num_rows": (i64, [vp]),
         "gpuq_table_num_columns": (i32, [vp]),

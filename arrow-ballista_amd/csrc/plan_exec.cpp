@@ -18,6 +18,12 @@
 #include "devbuf.h"
 #include "expr_compile.h"
 #include "json.h"
+#include "parquet_meta.h"
+#include "parquet_prune.h"
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <unistd.h>
+#include <cstdlib>
 #include <algorithm>
 #include <atomic>
 #include <thread>
@@ -2237,6 +2243,203 @@ struct ShuffleReaderExec : PNode {
   }
 };
 
+// ---------------------------------------------------------------- file scans: ParquetExec / CsvExec (FileScanExecConf, datafusion.proto)
+// The leaves of the reference's TPC-H plans over registered files.  Output partition p = the files of file group p, in the order
+// given, concatenated as ShuffleReaderExec concatenates its locations; the output schema is the projected fields of the FILE schema
+// in projection order.  Files are mapped read-only, so only what the decoders upload is read from disk; they are read again on every
+// execution and nothing decoded is kept from one execution to the next (ShuffleReaderExec's rules: the leaf runs synchronously, what is
+// above it may run deferred).  `limit`: the first rows of the partition in file order, after pruning; no further row group or file
+// is decoded once it is reached.
+struct MappedFile {
+  const uint8_t* p = nullptr; int64_t n = 0;
+  MappedFile(const std::string& path, const char* who) {
+    const int fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
+    if (fd < 0) throw std::runtime_error(std::string(who) + ": file " + path + " cannot be opened: " + std::strerror(errno));
+    struct stat st;
+    if (::fstat(fd, &st) != 0) { const int e = errno; ::close(fd); throw std::runtime_error(std::string(who) + ": file " + path + " cannot be opened: " + std::strerror(e)); }
+    n = (int64_t)st.st_size;
+    if (n > 0) {
+      void* m = ::mmap(nullptr, (size_t)n, PROT_READ, MAP_PRIVATE, fd, 0);
+      if (m == MAP_FAILED) { const int e = errno; ::close(fd); throw std::runtime_error(std::string(who) + ": file " + path + " cannot be mapped: " + std::strerror(e)); }
+      p = (const uint8_t*)m;
+    }
+    ::close(fd);
+  }
+  ~MappedFile() { if (p) (void)::munmap((void*)p, (size_t)n); }
+  MappedFile(const MappedFile&) = delete; MappedFile& operator=(const MappedFile&) = delete;
+};
+void scan_check(int rc) {      // a decoder's refusal travels up with its own status and message
+  if (rc == GPUQ_OK) return;
+  const std::string msg = gpuq_scan_last_error();
+  if (rc == GPUQ_ERR_UNSUPPORTED) throw Unsupported(msg);
+  if (rc == GPUQ_ERR_CAPACITY) throw Capacity(msg);
+  if (rc == GPUQ_ERR_HIP) throw HipError(msg);
+  throw std::runtime_error(msg);
+}
+struct ScanFile { std::string path; bool has_range = false; int64_t start = 0, end = 0; };
+struct FileScanExec : PNode {
+  PSchema file_schema; std::vector<int> projection; int64_t limit = -1; std::vector<std::vector<ScanFile>> groups;
+  int64_t row_groups = 0, row_groups_pruned = 0, bytes_scanned = 0, files = 0;      // gpuq_plan_metrics
+  PSchema schema() override { PSchema s; for (int i : projection) s.push_back(file_schema[(size_t)i]); return s; }
+  int partitions() override { return (int)groups.size(); }
+  std::vector<gpuq_field_info> file_fields() const { std::vector<gpuq_field_info> v; for (auto& f : file_schema) v.push_back(field_info_of(column_of(f))); return v; }
+  // a decoded table as a plan table of the projected schema; the library's buffers live as long as the table
+  PTable wrap(gpuq_table* tb) {
+    PTable t; t.n = gpuq_table_num_rows(tb);
+    t.keep.push_back(BufP(new DevBuf(), [tb](DevBuf* d) { delete d; gpuq_table_free(tb); }));
+    if (gpuq_table_num_columns(tb) != (int)projection.size()) throw std::runtime_error(kind + ": the decoder returned " + std::to_string(gpuq_table_num_columns(tb)) + " columns for " + std::to_string(projection.size()));
+    for (size_t i = 0; i < projection.size(); ++i) {
+      const PField& f = file_schema[(size_t)projection[i]];
+      PCol c; c.name = f.name; c.type = f.type; gpuq_field_info fi;
+      gpuq_table_column(tb, (int)i, &c.c, &fi);
+      c.nullable = f.nullable || c.c.validity != nullptr;
+      t.cols.push_back(c); t.sides.push_back(0);
+    }
+    return t;
+  }
+  PTable empty_table(Exec& x) {
+    std::vector<gpuq_field_info> fields; for (auto& f : schema()) fields.push_back(field_info_of(column_of(f)));
+    static const uint8_t eos[8] = {0xFF, 0xFF, 0xFF, 0xFF, 0, 0, 0, 0};
+    gpuq_ipc_batch* b = nullptr;
+    ipc_check(gpuq_ipc_decode_stream(x.ctx, x.stream, eos, 8, fields.data(), (int)fields.size(), &b));
+    PTable t; t.n = gpuq_ipc_batch_num_rows(b);
+    t.keep.push_back(BufP(new DevBuf(), [b](DevBuf* d) { delete d; gpuq_ipc_batch_free(b); }));
+    const PSchema s = schema();
+    for (size_t i = 0; i < s.size(); ++i) { PCol c; c.name = s[i].name; c.type = s[i].type; c.nullable = s[i].nullable; gpuq_ipc_batch_column(b, (int)i, &c.c); t.cols.push_back(c); t.sides.push_back(0); }
+    return t;
+  }
+  static void head(PTable& t, int64_t k) { if (k < t.n) { t.n = k; for (auto& c : t.cols) c.c.length = k; } }      // (decoded tables are plain: a prefix needs no copy)
+  // the files of the partition, one after another, until `limit` rows are there
+  virtual void scan_file(Exec& x, const ScanFile& f, int64_t left, std::vector<PTable>& out) = 0;
+  PTable execute(int part, Exec& x) override {
+    auto t0 = std::chrono::steady_clock::now();
+    if (part < 0 || part >= (int)groups.size()) throw std::runtime_error(kind + ": partition out of range");
+    std::vector<PTable> parts; int64_t left = limit;
+    for (auto& f : groups[(size_t)part]) {
+      if (limit >= 0 && left <= 0) break;
+      check_cancel(x);
+      const size_t before = parts.size();
+      scan_file(x, f, left, parts); ++files;
+      for (size_t k = before; k < parts.size(); ++k) if (limit >= 0) { head(parts[k], std::max<int64_t>(left, 0)); left -= parts[k].n; }
+    }
+    if (parts.empty()) parts.push_back(empty_table(x));
+    return timed(x, t0, parts.size() == 1 ? parts[0] : concat_tables(x, std::move(parts)));
+  }
+};
+
+struct ParquetExec : FileScanExec {
+  bool has_predicate = false, pruning = true; Json predicate;
+  void scan_file(Exec& x, const ScanFile& f, int64_t left, std::vector<PTable>& out) override {
+    MappedFile mf(f.path, "ParquetExec");
+    PqFileMeta M;
+    try { M = read_footer(mf.p, mf.n); } catch (const std::exception& e) { throw std::runtime_error(std::string(e.what()) + " (" + f.path + ")"); }
+    const std::vector<gpuq_field_info> ff = file_fields();
+    int in_range = 0;
+    std::vector<int32_t> keep = pq_prune(M, has_predicate && pruning ? &predicate : nullptr, ff.data(), (int)ff.size(), f.has_range ? f.start : 0, f.has_range ? f.end : -1, &in_range);
+    row_groups += in_range; row_groups_pruned += in_range - (int64_t)keep.size();
+    if (left >= 0) {      // the row groups that hold the first `left` rows
+      size_t k = 0; int64_t rows = 0;
+      while (k < keep.size() && rows < left) rows += M.groups[(size_t)keep[k++]].num_rows;
+      keep.resize(k);
+    }
+    // what the file holds against what the plan declares, before anything is uploaded; the chunk bytes the decode will move
+    std::vector<const char*> names;
+    for (int pi : projection) {
+      const PField& d = file_schema[(size_t)pi]; names.push_back(d.name.c_str());
+      int leaf = -1; for (size_t k = 1; k < M.schema.size(); ++k) if (M.schema[k].name == d.name) leaf = (int)k - 1;
+      if (leaf < 0) continue;      // (the decoder names the missing column)
+      int gt = -1, gp = 0, gs = 0, w = 0, dp = 0, ds = 0;
+      if (!pq_leaf_type(M.schema[(size_t)leaf + 1], gt, gp, gs, w)) continue;      // (the decoder says why it does not read it)
+      const int dt = type_id_of(d.type, dp, ds);
+      const bool same = dt == gt && ((dt != T_DECIMAL128 && dt != T_TIMESTAMP) || dp == gp) && (dt != T_DECIMAL128 || ds == gs);
+      if (!same) throw std::runtime_error("ParquetExec: column '" + d.name + "' is declared " + d.type.dump() + ", the file " + f.path + " holds " + type_json_of(gt, gp, gs).dump());
+      for (int32_t g : keep) if ((size_t)leaf < M.groups[(size_t)g].cols.size()) bytes_scanned += std::max<int64_t>(M.groups[(size_t)g].cols[(size_t)leaf].total_compressed, 0);
+    }
+    const int32_t none = 0;
+    gpuq_table* tb = nullptr;
+    scan_check(gpuq_parquet_decode_groups(x.ctx, x.stream, mf.p, mf.n, names.data(), (int)names.size(), keep.empty() ? &none : keep.data(), (int)keep.size(), &tb));
+    out.push_back(wrap(tb));
+  }
+};
+
+struct CsvExec : FileScanExec {
+  bool has_header = false; uint8_t delimiter = ',', quote = '"';
+  void scan_file(Exec& x, const ScanFile& f, int64_t left, std::vector<PTable>& out) override {
+    MappedFile mf(f.path, "CsvExec");
+    // a line belongs to the range in which its first byte lies; a line starts at offset 0 and after every '\n'
+    auto line_start_at_or_after = [&](int64_t at) -> int64_t {
+      if (at <= 0) return 0;
+      if (at >= mf.n) return mf.n;
+      const void* nl = std::memchr(mf.p + at - 1, '\n', (size_t)(mf.n - (at - 1)));
+      return nl ? (const uint8_t*)nl - mf.p + 1 : mf.n;
+    };
+    int64_t b = 0, e = mf.n;
+    if (f.has_range) { b = line_start_at_or_after(f.start); e = std::max(b, line_start_at_or_after(f.end)); }
+    if (has_header && b == 0 && e > 0) b = std::min(e, line_start_at_or_after(1));      // the header line goes with the range that holds offset 0
+    const std::vector<gpuq_field_info> ff = file_fields();
+    std::vector<int32_t> proj(projection.begin(), projection.end());
+    gpuq_csv_options opt{}; opt.delimiter = (char)delimiter; opt.quote = (char)quote; opt.has_header = 0;
+    // one call decodes less than 4 GiB: longer slices are cut behind the last line feed that fits (no value is looked at)
+    int64_t call_bytes = (1ll << 32) - (1ll << 20);
+    if (const char* env = std::getenv("GPUQ_CSV_CALL_BYTES")) { const long long v = std::atoll(env); if (v > 0 && v < call_bytes) call_bytes = v; }
+    while (b < e && (left < 0 || left > 0)) {
+      int64_t cut = e;
+      if (e - b > call_bytes) {
+        cut = b + call_bytes;
+        while (cut > b && mf.p[cut - 1] != '\n') --cut;
+        if (cut == b) throw std::runtime_error("csv: a line of " + f.path + " is longer than one call decodes (" + std::to_string(call_bytes) + " bytes)");
+      }
+      gpuq_table* tb = nullptr;
+      scan_check(gpuq_csv_decode(x.ctx, x.stream, mf.p + b, cut - b, ff.data(), (int)ff.size(), proj.data(), (int)proj.size(), &opt, &tb));
+      bytes_scanned += cut - b;
+      out.push_back(wrap(tb));
+      if (left >= 0) left -= std::min(left, out.back().n);
+      b = cut;
+    }
+  }
+};
+
+void read_file_scan(const std::string& kind, const Json& v, FileScanExec& n, const std::set<std::string>& members) {
+  for (const char* k : {"table_partition_cols", "output_ordering", "escape"})
+    if (v.has(k) && !(v.at(k).is_arr() && v.at(k).a.empty())) throw NotNative("plan: " + kind + " with '" + k + "' is not executed natively");
+  for (auto& kv : v.o) if (!members.count(kv.first)) throw std::runtime_error(kind + ": unknown member '" + kv.first + "'");
+  for (auto& f : v.at("schema").a) n.file_schema.push_back({f.at("name").str(), f.at("type"), f.get_bool("nullable", true)});
+  for (auto& f : n.file_schema) { int p, s; (void)type_id_of(f.type, p, s); }      // (a type the engine has no name for is refused here)
+  if (v.has("projection")) {
+    for (auto& i : v.at("projection").a) {
+      const long long k = i.i64();
+      if (k < 0 || k >= (long long)n.file_schema.size()) throw std::runtime_error(kind + ": projection index " + std::to_string(k) + " is out of range (the file schema has " + std::to_string(n.file_schema.size()) + " fields)");
+      n.projection.push_back((int)k);
+    }
+  } else for (size_t i = 0; i < n.file_schema.size(); ++i) n.projection.push_back((int)i);
+  n.limit = v.get_i64("limit", -1);
+  if (v.has("limit") && n.limit < 0) throw std::runtime_error(kind + ": limit " + std::to_string(n.limit) + " is negative");
+  for (auto& g : v.at("file_groups").a) {
+    n.groups.emplace_back();
+    for (auto& f : g.a) {
+      ScanFile sf;
+      if (f.is_str()) sf.path = f.str();
+      else {
+        for (auto& kv : f.o) if (kv.first != "path" && kv.first != "range") throw std::runtime_error(kind + ": unknown member '" + kv.first + "' of a file");
+        sf.path = f.at("path").str();
+        if (f.has("range")) {
+          const Json& r = f.at("range");
+          if (!r.is_arr() || r.a.size() != 2) throw std::runtime_error(kind + ": range of " + sf.path + " is not [start, end]");
+          sf.has_range = true; sf.start = r.a[0].i64(); sf.end = r.a[1].i64();
+          if (sf.start < 0 || sf.end < sf.start) throw std::runtime_error(kind + ": range [" + std::to_string(sf.start) + ", " + std::to_string(sf.end) + ") of " + sf.path + " is not a byte range");
+        }
+      }
+      n.groups.back().push_back(sf);
+    }
+  }
+}
+uint8_t one_byte(const std::string& kind, const Json& v, const char* key, uint8_t dflt) {
+  if (!v.has(key)) return dflt;
+  const std::string s = v.at(key).str();
+  if (s.size() != 1) throw std::runtime_error(kind + ": " + key + " must be one byte, got '" + s + "' (" + std::to_string(s.size()) + " bytes)");
+  return (uint8_t)s[0];
+}
+
 // ---------------------------------------------------------------- exchange between the GPUs of a node (exchange.cpp)
 // The intra-node stand-ins for a stage boundary of the reference (ShuffleWriterExec -> files -> ShuffleReaderExec):
 //   RepartitionExec {input, hash_expr, partition_count == ranks}: this rank's rows are hash-partitioned by destination rank
@@ -2550,6 +2753,18 @@ PNodeP build_node(const Json& j) {
     for (auto& f : v.at("schema").a) n->schema_.push_back({f.at("name").str(), f.at("type"), f.get_bool("nullable", true)});
     for (auto& p : v.at("partition").a) { n->locations.emplace_back(); for (auto& l : p.a) n->locations.back().push_back(l.is_obj() ? l.at("path").str() : l.str()); }
     out = std::move(n);
+  } else if (kind == "ParquetExec") {
+    auto n = std::make_unique<ParquetExec>();
+    read_file_scan(kind, v, *n, {"file_groups", "schema", "projection", "limit", "predicate", "pruning", "table_partition_cols", "output_ordering"});
+    if (v.has("predicate")) { n->has_predicate = true; n->predicate = v.at("predicate"); }
+    n->pruning = v.get_bool("pruning", true);
+    out = std::move(n);
+  } else if (kind == "CsvExec") {
+    auto n = std::make_unique<CsvExec>();
+    read_file_scan(kind, v, *n, {"file_groups", "schema", "projection", "limit", "has_header", "delimiter", "quote", "table_partition_cols", "output_ordering", "escape"});
+    n->has_header = v.at("has_header").boolean(); n->delimiter = one_byte(kind, v, "delimiter", 0); n->quote = one_byte(kind, v, "quote", '"');
+    if (!v.has("delimiter")) throw std::runtime_error("CsvExec: missing key 'delimiter'");
+    out = std::move(n);
   } else throw NotNative("plan: node type '" + kind + "' is not executed natively");
   out->kind = kind;
   return out;
@@ -2801,6 +3016,9 @@ int gpuq_plan_metrics(gpuq_plan* p, char* buf, size_t cap) {
       for (size_t k = 0; k < w->stage_partitions.size(); ++k) s += (k ? "," : "") + std::to_string(w->stage_partitions[k]);
       s += "]";
     }
+    if (auto* f = dynamic_cast<FileScanExec*>(nodes[i]))
+      s += ",\"row_groups\":" + std::to_string(f->row_groups) + ",\"row_groups_pruned\":" + std::to_string(f->row_groups_pruned) + ",\"bytes_scanned\":" + std::to_string(f->bytes_scanned) +
+           ",\"files\":" + std::to_string(f->files);
     s += "}";
   }
   s += "]";

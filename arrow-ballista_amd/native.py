@@ -108,6 +108,19 @@ def plan_to_json(node, tc, inputs):
     if isinstance(node, P.ShuffleReaderExec):
         return {"ShuffleReaderExec": {"schema": [{"name": f["name"], "type": f["type"], "nullable": bool(f.get("nullable", True))} for f in node.schema()],
                                       "partition": [[{"path": (l["path"] if isinstance(l, dict) else l)} for l in p] for p in node.partition]}}
+    if isinstance(node, (P.ParquetExec, P.CsvExec)):
+        what = node._not_native()
+        if what:      # the reference's FileScanExecConf members the native leaf does not implement: the node stays a host leaf
+            raise B.GpuqError(3, "plan node %s with %s is not executed natively" % (t, what), B.REFUSAL_NODE_NOT_NATIVE)
+        d = node._conf_json()
+        if isinstance(node, P.ParquetExec):
+            if node.predicate is not None:
+                d["predicate"] = node.predicate
+            if not node.pruning:
+                d["pruning"] = False
+        else:
+            d.update({"has_header": node.has_header, "delimiter": node.delimiter, "quote": node.quote})
+        return {t: d}
     raise B.GpuqError(3, "plan node %s is not executed natively" % t, B.REFUSAL_NODE_NOT_NATIVE)
 
 

@@ -1248,6 +1248,132 @@ class ShuffleReaderExec(ExecutionPlan):
         return out
 
 
+class _FileScanExec(ExecutionPlan):
+    """What ParquetExec and CsvExec share (FileScanExecConf, datafusion.proto): `file_groups` = one list of files per output
+    partition, a file being a path or {"path", "range": [start, end]}; `schema` = the FILE schema (field dicts); `projection` =
+    indices into it (None: all); `limit` = at most that many rows per partition, the first in file order.  Plans with
+    table_partition_cols, an output_ordering or a CSV escape character are not executed natively (REFUSAL_NODE_NOT_NATIVE)."""
+
+    def __init__(self, file_groups, schema, projection=None, limit=None, table_partition_cols=None, output_ordering=None):
+        super().__init__()
+        self.file_groups = [[dict(f) if isinstance(f, dict) else {"path": f} for f in g] for g in file_groups]
+        self.file_schema = [{"name": f["name"], "type": f["type"], "nullable": bool(f.get("nullable", True))} for f in schema]
+        self.projection = None if projection is None else [int(i) for i in projection]
+        self.limit = None if limit is None else int(limit)
+        self.table_partition_cols, self.output_ordering = table_partition_cols or [], output_ordering or []
+
+    def schema(self):
+        idx = range(len(self.file_schema)) if self.projection is None else self.projection
+        return [self.file_schema[i] for i in idx]
+
+    def output_partition_count(self):
+        return len(self.file_groups)
+
+    def _not_native(self):
+        for what in ("table_partition_cols", "output_ordering", "escape"):
+            if getattr(self, what, None):
+                return what
+        return None
+
+    def _conf_json(self):
+        d = {"file_groups": [[{k: (list(v) if k == "range" else v) for k, v in f.items()} for f in g] for g in self.file_groups], "schema": self.file_schema}
+        if self.projection is not None:
+            d["projection"] = self.projection
+        if self.limit is not None:
+            d["limit"] = self.limit
+        return d
+
+    def _scan_partition(self, partition, context, scan_file):
+        """The mirror's loop: the files of the partition in order, cut at `limit`, concatenated."""
+        from . import shuffle as S
+        t0 = time.perf_counter()
+        left, tables = self.limit, []
+        for f in self.file_groups[partition]:
+            if left is not None and left <= 0:
+                break
+            if not os.path.exists(f["path"]):
+                raise B.GpuqError(1, "%s: file %s cannot be opened: No such file or directory" % (type(self).__name__, f["path"]))
+            for t in scan_file(f, left):
+                if left is not None:
+                    t = slice_table(context, t, 0, left)
+                    left -= t.num_rows
+                tables.append(t)
+        if not tables:
+            out = S.empty_table(context, self.schema())
+        else:
+            out = tables[0] if len(tables) == 1 else concat_tables(context, tables)
+        return self._timed(t0, out)
+
+
+class ParquetExec(_FileScanExec):
+    """ParquetScanExecNode (datafusion.proto): row groups are pruned on the host from the byte range of each file and the footer's
+    statistics (scan.parquet_prune; `pruning=False` applies the range only), the survivors are decoded on the device.  The
+    predicate is over the file schema and is NOT applied to rows: the FilterExec above the leaf does that."""
+
+    def __init__(self, file_groups, schema, projection=None, limit=None, predicate=None, pruning=True, table_partition_cols=None, output_ordering=None):
+        super().__init__(file_groups, schema, projection, limit, table_partition_cols, output_ordering)
+        self.predicate, self.pruning = predicate, bool(pruning)
+        self.row_groups = self.row_groups_pruned = 0
+
+    def execute(self, partition, context):
+        from . import scan
+        from .table import type_id
+        L = context.ctx.L
+        out_schema = self.schema()
+
+        def scan_file(f, left):
+            keep, in_range = scan.parquet_prune(L, f["path"], self.predicate if self.pruning else None, self.file_schema, f.get("range"))
+            self.row_groups += in_range
+            self.row_groups_pruned += in_range - len(keep)
+            if left is not None:
+                rows, k, seen = scan.parquet_row_groups(L, f["path"]), 0, 0
+                while k < len(keep) and seen < left:
+                    seen += rows[keep[k]]
+                    k += 1
+                keep = keep[:k]
+            t = scan.read_parquet(context, f["path"], [c["name"] for c in out_schema], row_groups=keep)
+            for c, d in zip(t.columns, out_schema):
+                if type_id(c.type) != type_id(d["type"]):
+                    raise B.GpuqError(1, "ParquetExec: column '%s' is declared %s, the file %s holds %s" % (d["name"], json.dumps(d["type"]), f["path"], json.dumps(c.type)))
+            return [t]
+        return self._scan_partition(partition, context, scan_file)
+
+
+class CsvExec(_FileScanExec):
+    """CsvScanExecNode (datafusion.proto): delimited text decoded on the device.  With byte ranges a line belongs to the range in
+    which its first byte lies, and the header line goes with the range that holds offset 0."""
+
+    def __init__(self, file_groups, schema, projection=None, limit=None, has_header=False, delimiter=",", quote='"', escape=None, table_partition_cols=None,
+                 output_ordering=None):
+        super().__init__(file_groups, schema, projection, limit, table_partition_cols, output_ordering)
+        self.has_header, self.delimiter, self.quote, self.escape = bool(has_header), delimiter, quote, escape
+
+    def execute(self, partition, context):
+        from . import scan
+        file_schema = [(f["name"], f["type"], f["nullable"]) for f in self.file_schema]
+
+        def scan_file(f, left):
+            data = open(f["path"], "rb").read()
+
+            def line_start(at):
+                if at <= 0:
+                    return 0
+                if at >= len(data):
+                    return len(data)
+                nl = data.find(b"\n", at - 1)
+                return len(data) if nl < 0 else nl + 1
+            b, e = 0, len(data)
+            if f.get("range") is not None:
+                b = line_start(f["range"][0])
+                e = max(b, line_start(f["range"][1]))
+            if self.has_header and b == 0 and e > 0:
+                b = min(e, line_start(1))
+            if b >= e:
+                return []
+            return [scan.read_csv(context, data[b:e], file_schema, self.projection, self.delimiter, False, self.quote)]
+        return self._scan_partition(partition, context, scan_file)
+
+
 class DefaultQueryStageExec:
     """QueryStageExecutor (execution_engine.rs:49-60, :97-133)."""
 

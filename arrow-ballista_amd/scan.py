@@ -73,11 +73,7 @@ def read_csv(tc, src, schema, projection=None, delimiter=",", has_header=False, 
     {"Decimal128": [15, 2]}, "Utf8" ...).  projection: file column indices or names.  Returns a DeviceTable."""
     L = tc.ctx.L
     keep, addr, n = _host_bytes(src)
-    fields = (B.gpuq_field_info * len(schema))()
-    for i, (name, ty, nullable) in enumerate(schema):
-        tid, p, s = type_id(ty)
-        fields[i].name = name.encode()[:255]
-        fields[i].type, fields[i].precision, fields[i].scale, fields[i].nullable = tid, p, s, 1 if nullable else 0
+    fields = _field_array(schema)
     proj = None
     if projection is not None:
         names = [s[0] for s in schema]
@@ -132,6 +128,34 @@ def parquet_row_groups(L, src):
     _check(L, L.gpuq_parquet_row_groups(C.c_void_p(addr), n, rows, k.value, C.byref(k)))
     del keep
     return [int(rows[i]) for i in range(k.value)]
+
+
+def _field_array(schema):
+    """[(name, type, nullable)] or field dicts -> gpuq_field_info array."""
+    fields = (B.gpuq_field_info * max(1, len(schema)))()
+    for i, f in enumerate(schema):
+        name, ty, nullable = (f["name"], f["type"], f.get("nullable", True)) if isinstance(f, dict) else f
+        tid, p, s = type_id(ty)
+        fields[i].name = name.encode()[:255]
+        fields[i].type, fields[i].precision, fields[i].scale, fields[i].nullable = tid, p, s, 1 if nullable else 0
+    return fields
+
+
+def parquet_prune(L, src, predicate, schema, byte_range=None):
+    """Row-group pruning on the host (gpuq_parquet_prune; the rules are in include/gpuq.h): the row groups of the file that lie in
+    `byte_range` = (start, end) -- None: the whole file -- and in which `predicate` (expression JSON over `schema`, the FILE schema, by
+    name; or None) may be true.  Returns (indices ascending, number the range alone selected)."""
+    import json
+    keep, addr, n = _host_bytes(src)
+    fields = _field_array(schema)
+    pj = None if predicate is None else json.dumps(predicate).encode()
+    lo, hi = (0, -1) if byte_range is None else (int(byte_range[0]), int(byte_range[1]))
+    k, r = C.c_int(0), C.c_int(0)
+    _check(L, L.gpuq_parquet_prune(C.c_void_p(addr), n, pj, fields, len(schema), lo, hi, None, 0, C.byref(k), C.byref(r)))
+    out = (C.c_int32 * max(1, k.value))()
+    _check(L, L.gpuq_parquet_prune(C.c_void_p(addr), n, pj, fields, len(schema), lo, hi, out, k.value, C.byref(k), C.byref(r)))
+    del keep
+    return [int(out[i]) for i in range(k.value)], int(r.value)
 
 
 def read_parquet(tc, src, columns=None, row_groups=None):

@@ -3,14 +3,23 @@
 //!
 //! Nodes are recognised the way the reference does it itself: `as_any().downcast_ref::<T>()`
 //! (ballista/core/src/physical_optimizer/task_group.rs:143-167, ballista/core/src/utils.rs:274-311).  A subtree the
-//! device path does not execute (a scan, a window, an expression outside the supported subset) is NOT an error: it
-//! becomes a *host leaf* -- the shim runs that subtree with DataFusion as the stock executor would and hands its batches
-//! to the device through the Arrow C Data Interface (`gpuq_table_import_arrow`), as input slot k of a `MemoryExec` node.
+//! device path does not execute (a window, an expression outside the supported subset, a scan the native leaves do not
+//! cover) is NOT an error: it becomes a *host leaf* -- the shim runs that subtree with DataFusion as the stock executor
+//! would and hands its batches to the device through the Arrow C Data Interface (`gpuq_table_import_arrow`), as input
+//! slot k of a `MemoryExec` node.
+//!
+//! Scans: `ParquetExec` / `CsvExec` over the local file system map to the native leaves of the same names (file groups
+//! with their byte ranges, projection, limit, the pruning predicate through the expression walker): the file bytes cross
+//! PCIe once and are decoded on the device.  A scan over another object store, with table_partition_cols, an
+//! output_ordering or a CSV escape character stays a host leaf.  (This mapping was written without a Rust toolchain at
+//! hand, like the rest of this crate: it has not been compiled.)
 use std::sync::Arc;
 
 use ballista_core::execution_plans::{CoalesceTasksExec, ShuffleReaderExec, ShuffleWriterExec};
 use datafusion::arrow::datatypes::{DataType, SchemaRef};
 use datafusion::common::{DataFusionError, Result, ScalarValue};
+use datafusion::datasource::physical_plan::{CsvExec, FileScanConfig, ParquetExec};
+use datafusion::execution::object_store::ObjectStoreUrl;
 use datafusion::logical_expr::Operator;
 use datafusion::physical_expr::ScalarFunctionExpr;
 use datafusion::physical_plan::aggregates::{AggregateExec, AggregateMode};
@@ -294,7 +303,53 @@ fn walk_node(p: &Arc<dyn ExecutionPlan>, leaves: &mut Vec<(Arc<dyn ExecutionPlan
         }
         return Ok(json!({"ShuffleReaderExec": {"schema": schema_json(&n.schema())?, "partition": parts}}));
     }
+    if let Some(n) = a.downcast_ref::<ParquetExec>() {
+        let mut j = file_scan(n.base_config())?;
+        // the pruning predicate is over the FILE schema, by name; the FilterExec above the leaf applies it to rows.  A predicate the
+        // expression walker does not carry is dropped, not the scan: pruning is an optimisation, the filter is what decides
+        if let Some(pred) = n.predicate() {
+            if let Ok(e) = expr(pred) { j["predicate"] = e; }
+        }
+        return Ok(json!({"ParquetExec": j}));
+    }
+    if let Some(n) = a.downcast_ref::<CsvExec>() {
+        if n.escape().is_some() { return unsupported("CsvExec with an escape character"); }
+        let mut j = file_scan(n.base_config())?;
+        j["has_header"] = json!(n.has_header());
+        j["delimiter"] = json!(one_byte(n.delimiter())?);
+        j["quote"] = json!(one_byte(n.quote())?);
+        return Ok(json!({"CsvExec": j}));
+    }
     unsupported(format!("plan node {}", p.name()))
+}
+
+fn one_byte(b: u8) -> Result<String> {
+    // the grammar carries the byte as a one-byte JSON string: ASCII only
+    if b.is_ascii() { Ok((b as char).to_string()) } else { unsupported("a CSV delimiter / quote outside ASCII") }
+}
+
+/// FileScanExecConf (datafusion.proto) of a scan over local files -> the members ParquetExec / CsvExec share in the grammar.
+/// Anything else -- another object store, partition columns, a declared output ordering -- keeps the scan a host leaf.
+fn file_scan(c: &FileScanConfig) -> Result<Value> {
+    if c.object_store_url != ObjectStoreUrl::local_filesystem() { return unsupported("a scan over an object store other than the local file system"); }
+    if !c.table_partition_cols.is_empty() { return unsupported("a scan with table_partition_cols"); }
+    if !c.output_ordering.is_empty() { return unsupported("a scan with an output_ordering"); }
+    let mut groups = vec![];
+    for g in &c.file_groups {
+        let mut files = vec![];
+        for f in g {
+            if !f.partition_values.is_empty() { return unsupported("a partitioned file with partition values"); }
+            // object_store paths of the local file system are absolute paths without their leading '/'
+            let mut o = json!({"path": format!("/{}", f.object_meta.location.as_ref())});
+            if let Some(r) = &f.range { o["range"] = json!([r.start, r.end]); }
+            files.push(o);
+        }
+        groups.push(Value::Array(files));
+    }
+    let mut j = json!({"file_groups": groups, "schema": schema_json(&c.file_schema)?});
+    if let Some(p) = &c.projection { j["projection"] = json!(p); }
+    if let Some(l) = c.limit { j["limit"] = json!(l); }
+    Ok(j)
 }
 
 pub fn walk(p: &Arc<dyn ExecutionPlan>, leaves: &mut Vec<(Arc<dyn ExecutionPlan>, usize)>) -> Result<Value> {

@@ -772,6 +772,86 @@ def scan_decode(tc, T, g, sf=1):
     return out
 
 
+def scan_plan(tc, T, g, sf=10, reps=5):
+    """q1 and q6 from Parquet FILES through ONE plan (ParquetExec leaf: footer, row-group pruning, upload of the projected chunks,
+    page decode, then the query), PCIe included, next to today's two steps in the same process: scan.read_parquet of the same
+    columns, then the plan over a MemoryExec.  lineitem at `sf` is written to a temporary directory as the reference's `tpch convert`
+    would (ZSTD), as Snappy, and once more sorted by l_shipdate -- labelled as such: generated lineitem is not clustered by date and
+    prunes little, the sorted file shows what pruning buys when it can.  Every time is a list over `reps` repetitions after one
+    warm-up; "spread" is max - min of that list."""
+    import json
+    import shutil
+    import sys
+    import tempfile
+    import pyarrow as pa
+    import pyarrow.parquet as pq
+    from arrow_ballista_amd import scan
+    n = T.LINEITEM_ROWS.get(sf, int(6_000_000 * sf))
+    cols = ("l_quantity", "l_extendedprice", "l_discount", "l_tax", "l_returnflag", "l_linestatus", "l_shipdate")
+    if hasattr(T, "gen_lineitem_host"):
+        li = T.lineitem_host_to_arrow(T.gen_lineitem_host(n), n)
+    else:
+        li = T.gen_lineitem_device(tc, n, columns=cols).to_arrow(tc.ctx)
+    li = li.cast(pa.schema([pa.field(f.name, f.type, nullable=False) for f in li.schema]))
+    tj = {"int64": "Int64", "int32": "Int32", "string": "Utf8", "date32[day]": "Date32"}
+    schema = [{"name": f.name, "type": tj.get(str(f.type), {"Decimal128": [15, 2]}), "nullable": False} for f in li.schema]
+    names = [f["name"] for f in schema]
+    d = tempfile.mkdtemp(prefix="gpuq_scan_plan_")
+    out = {"rows": n, "reps": reps, "legs": []}
+    try:
+        files = []
+        for label, table, codec in (("zstd", li, "ZSTD"), ("snappy", li, "SNAPPY"), ("zstd, file sorted by l_shipdate", li.sort_by("l_shipdate"), "ZSTD")):
+            path = os.path.join(d, "lineitem_%d.parquet" % len(files))
+            pq.write_table(table, path, compression=codec, use_dictionary=True, data_page_size=1 << 20, row_group_size=1 << 20)
+            files.append((label, path))
+            print("scan-plan: wrote %s (%s, %d bytes)" % (path, label, os.path.getsize(path)), file=sys.stderr, flush=True)
+        del li
+        queries = (("q1", T.q1_plan, cols), ("q6", T.q6_plan, ("l_quantity", "l_extendedprice", "l_discount", "l_shipdate")))
+
+        def timed(fn):
+            _sync(tc); t0 = time.perf_counter(); r = fn(); _sync(tc)
+            return (time.perf_counter() - t0) * 1e3, r
+
+        def pred_of(plan):
+            while not isinstance(plan, g.FilterExec):
+                plan = plan.children()[0]
+            return plan.predicate
+        for label, path in files:
+            for q, make, need in queries:
+                proj = [names.index(c) for c in need]
+                leaf = g.ParquetExec([[path]], schema, projection=proj)
+                leaf.predicate = pred_of(make(leaf))
+                one = g.NativePlan(make(leaf), tc)
+                _, r = timed(lambda: one.execute(0))      # warm-up: operators compiled, staging lanes and allocator warm
+                m = [x for x in one.metrics() if x["node"] == "ParquetExec"][0]
+                rows_one = T.table_to_rows(tc, g.plan.materialize(tc, r.to_device_table(tc.device)))
+                dev = scan.read_parquet(tc, path, list(need))
+                two = g.NativePlan(make(g.MemoryExec([dev])), tc)
+                rows_two = T.table_to_rows(tc, g.plan.materialize(tc, two.execute(0).to_device_table(tc.device)))
+                del dev, r
+
+                def two_step():
+                    t = scan.read_parquet(tc, path, list(need))
+                    two.set_input(0, t)
+                    return two.execute(0), t
+                t_one, t_two = [], []
+                for _ in range(reps):      # interleaved: both forms see the same machine state
+                    t_two.append(timed(two_step)[0])
+                    t_one.append(timed(lambda: one.execute(0))[0])
+                spread = lambda v: max(v) - min(v)
+                out["legs"].append({"file": label, "query": q, "file_bytes": os.path.getsize(path), "one_plan_ms": [round(x, 2) for x in t_one],
+                                    "two_step_ms": [round(x, 2) for x in t_two], "one_plan_best_ms": round(min(t_one), 2), "two_step_best_ms": round(min(t_two), 2),
+                                    "one_plan_spread_ms": round(spread(t_one), 2), "two_step_spread_ms": round(spread(t_two), 2),
+                                    "one_plan_within_spread_of_two_step": min(t_one) <= min(t_two) + max(spread(t_one), spread(t_two)),
+                                    "row_groups": m["row_groups"], "row_groups_pruned": m["row_groups_pruned"], "bytes_scanned": m["bytes_scanned"],
+                                    "rows_equal": rows_one == rows_two and len(rows_one) > 0})
+                one.close(); two.close()
+                print("scan-plan: %s" % json.dumps(out["legs"][-1]), file=sys.stderr, flush=True)
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+    return out
+
+
 if __name__ == "__main__":
     import json
     import os
@@ -816,6 +896,9 @@ if __name__ == "__main__":
         i = sys.argv.index("--merge")
         bits = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 and sys.argv[i + 1].isdigit() else 27
         print(json.dumps(merge_micro(tc, T, g, bits), indent=1))
+        sys.exit(0)
+    if "--scan-plan" in sys.argv:      # [--sf1]: SF10 unless told otherwise
+        print(json.dumps(scan_plan(tc, T, g, 1 if "--sf1" in sys.argv else 10)))
         sys.exit(0)
     if "--scan" in sys.argv:
         sf = 10 if "--sf10" in sys.argv else 1

@@ -246,6 +246,36 @@ int gpuq_parquet_decode_groups(gpuq_ctx* ctx, void* stream, const uint8_t* file,
 int gpuq_parquet_row_groups(const uint8_t* file, int64_t n_bytes, int64_t* rows_out, int cap, int* n_out);
 /* host only: leaf columns (type = -1 where the device has no decoder) and row count from the footer */
 int gpuq_parquet_schema(const uint8_t* file, int64_t n_bytes, gpuq_field_info* fields_out, int cap, int* n_out, int64_t* rows_out);
+/* Host only: row-group pruning as the reference's ParquetExec does it, from the byte range of a PartitionedFile and the footer's
+   chunk Statistics (csrc/parquet_prune.h).
+   row groups of `file` that lie in [range_start, range_end) (range_end < 0: the whole file) and that the predicate
+   (expression JSON over `file_fields`, or NULL) may be true in: indices ascending into row_groups_out (cap entries),
+   their number into *n_out, the number the range alone selected into *n_in_range_out.  row_groups_out NULL with cap 0 only counts.
+   A group is dropped only when its statistics PROVE that no row makes the predicate true; whatever is not understood keeps it:
+   - understood: `column op literal` / `literal op column` with op in = < <= > >= and a literal of EXACTLY the column's type (a decimal:
+     same precision and scale; nothing under a cast); `column IN (literals)`, not negated (any element in [min, max]); IS NULL (unless
+     null_count is present and 0); IS NOT NULL (unless null_count is present and equals the chunk's num_values); AND (both sides), OR
+     (either side); NOT over such a comparison (the operator is negated; any other NOT keeps).  `!=` never prunes.  A NULL literal in a
+     comparison drops every group; so does any comparison over a group whose null_count equals num_values (null_count absent: not
+     known to be all NULL).
+   - columns are named, against `file_fields`; a column that is not in the file, or is declared with another type than the file
+     holds, keeps the group.
+   - min / max are bounds, never attained values (string bounds may be truncated): `>` against a max equal to the literal prunes,
+     `>=` keeps.
+   - min_value / max_value are used for every supported type; the deprecated min / max only for INT32 / INT64 physical columns that
+     are signed integers, dates, timestamps or decimals (never BYTE_ARRAY, FIXED_LEN_BYTE_ARRAY, unsigned integers).
+   - bytes: signed integers, Date32, Timestamp and INT32 / INT64 decimals little-endian signed; UInt8..UInt64 unsigned; decimals on
+     FIXED_LEN_BYTE_ARRAY / BYTE_ARRAY big-endian two's complement of 1..16 bytes; Utf8 bytewise unsigned, a proper prefix first
+     (gpuq_utf8_compare's order); Boolean one byte; INT96 none.
+   - Float32 / Float64 columns are never pruned on (writers leave NaN out of min / max; what a NaN row compares to is the comparison
+     kernel's business and nothing here depends on it).
+   - a value whose length does not fit its physical type, or min > max in the column's order: the group is kept, the call succeeds.
+   - a row group belongs to the range that holds the file offset of its first column chunk's first page (dictionary page if there is
+     one); ranges that tile [0, file size) select every row group exactly once. */
+int gpuq_parquet_prune(const uint8_t* file, int64_t n_bytes, const char* predicate_json,
+                       const gpuq_field_info* file_fields, int n_file_fields,
+                       int64_t range_start, int64_t range_end,
+                       int32_t* row_groups_out, int cap, int* n_out, int* n_in_range_out);
 const char* gpuq_scan_last_error(void);
 
 /* ---- compiled operators ------------------------------------------------------------------ */
@@ -602,6 +632,26 @@ int gpuq_copy_bits(gpuq_ctx* ctx, void* stream, uint8_t* dst, int64_t dst_bit_of
          CollectLeft build side read by every reduce task
      {"ShuffleReaderExec": {"schema": [{"name","type","nullable"}], "partition": [[{"path"} | path, ...], ...]}}   (shuffle_reader.rs:149-177;
          local files; a file that cannot be opened is reported as "FetchFailed: ...")
+     {"ParquetExec": {"file_groups": [[{"path": str, "range"?: [start, end]} | path, ...], ...], "schema": [field],   -- the FILE schema
+                      "projection"?: [index into schema], "limit"?: n, "predicate"?: expr over schema, "pruning"?: bool = true}}
+     {"CsvExec":     {"file_groups": ..., "schema": [field], "projection"?: ..., "limit"?: n,
+                      "has_header": bool, "delimiter": one byte, "quote"?: one byte}}
+         (ParquetScanExecNode / CsvScanExecNode over FileScanExecConf, datafusion.proto.)  The leaves of plans over registered files.
+         Output partition p = the files of file group p in the order given, concatenated as ShuffleReaderExec concatenates its
+         locations; an empty group is an empty table.  The output schema is the projected fields, in projection order.  Files are
+         mapped read-only (only what a decoder uploads is read from disk) and read again on every execution; a file that cannot be
+         opened or mapped is an error naming the path and strerror.  "limit": at most n rows per partition -- the first in file order,
+         after pruning -- and no further row group or file is decoded once they are there.
+         ParquetExec: per file the row groups of its byte range that the predicate may be true in (gpuq_parquet_prune; "pruning": false
+         applies the range only) are decoded by gpuq_parquet_decode_groups, projected by name; a projected column whose type in the file
+         differs from the declared one is refused, both types named.  The predicate is NOT applied to rows: the FilterExec above does that.
+         CsvExec: gpuq_csv_decode over the file's bytes, or over the lines of the range: a line belongs to the range in which its first
+         byte lies, the header line is skipped only by the range that holds offset 0, so ranges that tile the file yield every line
+         once.  More than one call's 4 GiB is cut at line boundaries.  What the decoder refuses stays refused, status and message.
+         "table_partition_cols", "output_ordering" (non-empty) and a CSV "escape" are GPUQ_REFUSAL_NODE_NOT_NATIVE: such a scan stays
+         a host leaf.  Any other unknown member is GPUQ_ERR_INVALID and named.
+         gpuq_plan_metrics adds to a scan leaf: "row_groups" (in range), "row_groups_pruned", "bytes_scanned" (chunk / text bytes
+         uploaded), "files".
    Expressions are the PhysicalExprNode mirror of gpuq_op_create; columns are resolved by NAME against each operator's input.
    gpuq_plan_execute runs one output partition: inputs[k] is the table MemoryExec leaves refer to as slot k (caller-owned device
    memory, must stay valid until the call returns); *out is a materialised result owned by the library (gpuq_result_free).
