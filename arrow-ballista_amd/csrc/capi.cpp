@@ -1903,6 +1903,105 @@ int gpuq_segment_approx_distinct(gpuq_ctx* ctx, void* stream, const gpuq_column*
     HIPCHECK(hipGetLastError());
   });
 }
+// ---------------------------------------------------------------- window functions over an ordered table (BoundedWindowAggExec)
+// the ABI's numbers are the kernels': gpuq_window_frame hands mode and out_kind over as they come
+static_assert(GPUQ_FRAME_ROWS == WFRAME_ROWS && GPUQ_FRAME_RANGE == WFRAME_RANGE && GPUQ_FRAME_SLIDING == WFRAME_SLIDING, "gpuq.h frame modes differ from WinFrameMode");
+static_assert(GPUQ_WINDOW_OUT_CELL == WOUT_CELL && GPUQ_WINDOW_OUT_AVG_INT == WOUT_AVG_INT && GPUQ_WINDOW_OUT_AVG_FLOAT == WOUT_AVG_F64 && GPUQ_WINDOW_OUT_AVG_DECIMAL == WOUT_AVG_DEC,
+              "gpuq.h window result kinds differ from WinOutKind");
+static void window_rows_check(const char* who, int64_t n) {
+  if (n < 0) throw std::runtime_error(std::string(who) + ": bad arguments");
+  if (n >= (1ll << 31)) throw Unsupported(std::string(who) + " (BoundedWindowAggExec): >= 2^31 rows in one partition of the plan (segment ids and starts are 32-bit)");
+}
+int gpuq_window_scan(gpuq_ctx* ctx, void* stream, const gpuq_column* value_col, const int32_t* seg_id, int64_t n, int fn, void* out_cells, int cell_width, int64_t* out_count,
+                     uint8_t* out_validity, uint32_t* status_dev) {
+  return guarded(ctx, [&]() {
+    check_ctx(ctx);
+    window_rows_check("gpuq_window_scan", n);
+    if (!value_col || (n > 0 && !out_cells) || (cell_width != 8 && cell_width != 16) || fn < GPUQ_WINDOW_SUM || fn > GPUQ_WINDOW_MAX) throw std::runtime_error("gpuq_window_scan: bad arguments");
+    if (((uintptr_t)out_validity & 7) != 0) throw std::runtime_error("gpuq_window_scan: out_validity must be 8-byte aligned");
+    static const char* names[] = {"SUM", "COUNT", "MIN", "MAX"};
+    DType dt; dt.id = value_col->type; dt.p = value_col->precision; dt.s = value_col->scale;
+    WinCol c{value_col->data, value_col->validity, 0, SEG_SINT};
+    switch (dt.id) {
+      case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_DATE32: case T_DATE64: case T_TIMESTAMP: case T_DECIMAL128: c.kind = SEG_SINT; break;
+      case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: c.kind = SEG_UINT; break;
+      case T_FLOAT32: c.kind = SEG_F32; break;
+      case T_FLOAT64: c.kind = SEG_F64; break;
+      default: throw Unsupported(std::string(names[fn]) + " over " + dt.to_string() + " is not supported as a window function");
+    }
+    c.width = type_width(dt);
+    const bool flt = dt.is_float();
+    if (fn == GPUQ_WINDOW_SUM && dt.is_temporal()) throw Unsupported("SUM over " + dt.to_string() + " is not supported as a window function");
+    int kind = ACC_COUNT;
+    if (fn == GPUQ_WINDOW_SUM) kind = flt ? ACC_FSUM : ACC_SUM;
+    else if (fn == GPUQ_WINDOW_MIN) kind = flt ? ACC_FMIN : ACC_MIN;
+    else if (fn == GPUQ_WINDOW_MAX) kind = flt ? ACC_FMAX : ACC_MAX;
+    if (cell_width == 16 && kind != ACC_SUM) throw std::runtime_error("gpuq_window_scan: only an integer or decimal SUM has 16-byte cells");
+    if (n == 0) return;
+    if (!value_col->data || value_col->length < n) throw std::runtime_error("gpuq_window_scan: the column is shorter than n");
+    hipStream_t s = use_stream(stream);
+    DevBuf ws;      // released to the pool behind the launches on this stream
+    ws.ensure(window_scan_ws_bytes(n));
+    launch_window_scan(s, c, seg_id, n, kind, ws.p, out_cells, cell_width, (i64*)out_count, (u64*)out_validity, status_dev);
+    HIPCHECK(hipGetLastError());
+  });
+}
+int gpuq_window_rank(gpuq_ctx* ctx, void* stream, const int32_t* part_id, const int32_t* part_starts, const int32_t* peer_id, const int32_t* peer_starts, int64_t n,
+                     uint64_t* row_number_out, uint64_t* rank_out, uint64_t* dense_rank_out) {
+  return guarded(ctx, [&]() {
+    check_ctx(ctx);
+    window_rows_check("gpuq_window_rank", n);
+    if (n > 0 && (!part_id || !part_starts || !peer_id || !peer_starts)) throw std::runtime_error("gpuq_window_rank: bad arguments");
+    launch_window_rank(use_stream(stream), part_id, part_starts, peer_id, peer_starts, n, (u64*)row_number_out, (u64*)rank_out, (u64*)dense_rank_out);
+    HIPCHECK(hipGetLastError());
+  });
+}
+int gpuq_window_shift(gpuq_ctx* ctx, void* stream, const gpuq_column* value_col, const int32_t* part_id, const int32_t* part_starts, int64_t n, int64_t delta,
+                      const gpuq_column* default_col, void* out_data, uint8_t* out_validity) {
+  return guarded(ctx, [&]() {
+    check_ctx(ctx);
+    window_rows_check("gpuq_window_shift", n);
+    if (!value_col || (n > 0 && (!part_id || !part_starts || !out_data || !out_validity))) throw std::runtime_error("gpuq_window_shift: bad arguments");
+    if (((uintptr_t)out_validity & 7) != 0) throw std::runtime_error("gpuq_window_shift: out_validity must be 8-byte aligned");
+    DType dt; dt.id = value_col->type; dt.p = value_col->precision; dt.s = value_col->scale;
+    if (dt.id == T_UTF8 || dt.id == T_BOOL) throw Unsupported("LAG / LEAD over " + dt.to_string() + " is not supported (fixed-width types only)");
+    if (default_col && (default_col->type != value_col->type || default_col->precision != value_col->precision || default_col->scale != value_col->scale))
+      throw std::runtime_error("gpuq_window_shift: the default's type differs from the value's");
+    if (n == 0) return;
+    if (!value_col->data || value_col->length < n || (default_col && (!default_col->data || default_col->length < n))) throw std::runtime_error("gpuq_window_shift: a column is shorter than n");
+    // an offset beyond any partition: every row takes the default (and i + delta cannot wrap)
+    const int64_t lim = 1ll << 31;
+    delta = std::max<int64_t>(-lim, std::min<int64_t>(lim, delta));
+    launch_window_shift(use_stream(stream), value_col->data, value_col->validity, type_width(dt), part_id, part_starts, n, delta, default_col ? default_col->data : nullptr,
+                        default_col ? default_col->validity : nullptr, default_col ? 0 : 1, out_data, (u64*)out_validity);
+    HIPCHECK(hipGetLastError());
+  });
+}
+int gpuq_window_frame(gpuq_ctx* ctx, void* stream, const gpuq_window_frame_spec* f, int64_t n) {
+  return guarded(ctx, [&]() {
+    check_ctx(ctx);
+    window_rows_check("gpuq_window_frame", n);
+    if (!f || (n > 0 && (!f->cells || !f->part_id || !f->part_starts || !f->out)) || (f->cell_width != 8 && f->cell_width != 16) || f->mode < GPUQ_FRAME_ROWS || f->mode > GPUQ_FRAME_SLIDING ||
+        f->out_kind < GPUQ_WINDOW_OUT_CELL || f->out_kind > GPUQ_WINDOW_OUT_AVG_DECIMAL || (f->mode == GPUQ_FRAME_RANGE && n > 0 && (!f->peer_id || !f->peer_starts)) ||
+        (f->mode == GPUQ_FRAME_SLIDING && f->following < 0))
+      throw std::runtime_error("gpuq_window_frame: bad arguments");
+    if (f->out_kind == GPUQ_WINDOW_OUT_CELL && f->out_width != 1 && f->out_width != 2 && f->out_width != 4 && f->out_width != 8 && f->out_width != 16)
+      throw std::runtime_error("gpuq_window_frame: out_width must be 1, 2, 4, 8 or 16");
+    if ((f->out_kind == GPUQ_WINDOW_OUT_AVG_INT || f->out_kind == GPUQ_WINDOW_OUT_AVG_DECIMAL) && f->cell_width != 16) throw std::runtime_error("gpuq_window_frame: an exact AVG reads 16-byte cells");
+    if (f->out_kind != GPUQ_WINDOW_OUT_CELL && !f->counts) throw std::runtime_error("gpuq_window_frame: an AVG needs the counts");
+    if (f->avg_scale_digits < 0 || f->avg_scale_digits > 38) throw std::runtime_error("gpuq_window_frame: avg_scale_digits out of range");
+    if (((uintptr_t)f->out_validity & 7) != 0) throw std::runtime_error("gpuq_window_frame: out_validity must be 8-byte aligned");
+    if (n == 0) return;
+    u128 mul = 1; for (int k = 0; k < f->avg_scale_digits; ++k) mul *= 10;
+    WinFrame F{};
+    F.cells = f->cells; F.counts = (const i64*)f->counts; F.part_id = f->part_id; F.part_starts = f->part_starts; F.peer_id = f->peer_id; F.peer_starts = f->peer_starts;
+    F.preceding = f->preceding; F.following = f->following; F.mul_lo = (u64)mul; F.mul_hi = (u64)(mul >> 64);
+    F.cell_width = f->cell_width; F.mode = f->mode; F.out_kind = f->out_kind; F.out_width = f->out_width; F.out_f32 = f->out_f32 ? 1 : 0;
+    F.out = f->out; F.out_valid = (u64*)f->out_validity;
+    launch_window_frame(use_stream(stream), F, n);
+    HIPCHECK(hipGetLastError());
+  });
+}
 
 int gpuq_like_utf8(gpuq_ctx* ctx, void* stream, const gpuq_column* col, const uint32_t* idx, int64_t n, const char* pattern, int negated, int case_insensitive,
                    uint8_t* bits_out, uint8_t* validity_out) {

@@ -151,7 +151,7 @@ constexpr uint32_t FLAG_AGG_RUNS = 256u;    // the aggregate's input is not clus
 
 __device__ __forceinline__ i128 mk128(u64 lo, u64 hi) { return (i128)(((u128)hi << 64) | (u128)lo); }
 
-__device__ __forceinline__ i64 f64_total_key(u64 bits) {
+__host__ __device__ __forceinline__ i64 f64_total_key(u64 bits) {
   // IEEE-754 totalOrder as a signed integer compare [UPSTREAM-KNOWLEDGE: arrow-ord 49 cmp kernels]
   i64 s = (i64)bits;
   return s ^ (i64)((u64)(s >> 63) >> 1);

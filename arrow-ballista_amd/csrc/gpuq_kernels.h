@@ -112,8 +112,8 @@ enum JoinType : int32_t { JT_INNER = 0, JT_LEFT = 1, JT_RIGHT = 2, JT_FULL = 3, 
 constexpr uint32_t NIL = 0xFFFFFFFFu;      // no row / no slot
 __device__ __forceinline__ uint32_t tag_of(u64 h) { return (uint32_t)(h >> 32) | 2u; }
 
-// identity of a cell, word `half`
-__device__ __forceinline__ u64 acc_identity(const int kind, const int half) {
+// identity of a cell, word `half` (this and acc_combine are plain arithmetic: host code may call them too, tests/window_scan_host.cpp does)
+__host__ __device__ __forceinline__ u64 acc_identity(const int kind, const int half) {
   switch (kind) {
     case ACC_MIN: return half ? 0 : 0x7FFFFFFFFFFFFFFFull;
     case ACC_MAX: return half ? ~0ull : 0x8000000000000000ull;
@@ -147,12 +147,12 @@ __device__ __forceinline__ bool acc_wide_minmax(const int kind, const u64 vlo, c
   return (kind == ACC_MIN || kind == ACC_MAX) && (i64)vhi != ((i64)vlo >> 63);
 }
 // partial (olo, ohi) combined into partial (lo, hi), no atomics (registers, or memory one thread owns)
-__device__ __forceinline__ void acc_combine(const int kind, u64& lo, u64& hi, const u64 olo, const u64 ohi) {
+__host__ __device__ __forceinline__ void acc_combine(const int kind, u64& lo, u64& hi, const u64 olo, const u64 ohi) {
   switch (kind) {
     case ACC_SUM: case ACC_COUNT: case ACC_COUNT_STAR: { const u64 s = lo + olo; hi = hi + ohi + (s < lo ? 1 : 0); lo = s; break; }
     case ACC_MIN: if ((i64)olo < (i64)lo) lo = olo; break;
     case ACC_MAX: if ((i64)olo > (i64)lo) lo = olo; break;
-    case ACC_FSUM: lo = (u64)__double_as_longlong(__longlong_as_double((i64)lo) + __longlong_as_double((i64)olo)); break;
+    case ACC_FSUM: lo = __builtin_bit_cast(u64, __builtin_bit_cast(double, lo) + __builtin_bit_cast(double, olo)); break;
     case ACC_FMIN: if (f64_total_key(olo) < f64_total_key(lo)) lo = olo; break;
     case ACC_FMAX: if (f64_total_key(olo) > f64_total_key(lo)) lo = olo; break;
     case ACC_BAND: lo &= olo; break;
@@ -543,6 +543,34 @@ enum SegKind : int32_t { SEG_SINT = 0, SEG_UINT = 1, SEG_F32 = 2, SEG_F64 = 3 };
 // scan: n + 1 words of scratch (the flags, then their exclusive scan); seg_id (n, or nullptr), starts (starts_cap + 1), n_groups as gpuq_segment_heads
 void launch_segment_heads(hipStream_t s, const SegKeys& K, i64 n, int32_t* scan, void* scan_ws, size_t scan_ws_bytes, int32_t* seg_id, int32_t* starts, i64 starts_cap, u64* n_groups);
 void launch_segment_median(hipStream_t s, const void* data, const uint8_t* valid, int width, int kind, const int32_t* starts, i64 n_groups, void* out, u64* out_valid);
+// ----- window functions over a table ordered by (partition keys, order keys) (kernels_window.hip; window_scan_op.h has the scan's operator)
+struct WinCol { const void* data; const uint8_t* valid; int32_t width; int32_t kind; };      // kind: a SegKind, how a value of 8 bytes or fewer is widened
+constexpr uint32_t WINF_WIDE_MINMAX = 1u;      // the scan's status word: a MIN / MAX operand outside int64 (what FLAG_WIDE_MINMAX is to the aggregate operator)
+size_t window_scan_ws_bytes(i64 n);            // one scan element per tile of 2,048 rows
+// segmented inclusive scan of accumulator `kind` (an AccKind) over rows [0, n): seg_id (or nullptr: one partition) restarts it.  out_cells:
+// cell_width 8 (the low word) or 16 bytes a row; out_count (i64 a row: the non-NULL values so far) and out_valid (bit = count > 0, whole
+// 64-bit words) may be nullptr.
+void launch_window_scan(hipStream_t s, const WinCol& c, const int32_t* seg_id, i64 n, int kind, void* ws, void* out_cells, int cell_width, i64* out_count, u64* out_valid,
+                        uint32_t* flags);
+void launch_window_rank(hipStream_t s, const int32_t* part_id, const int32_t* part_starts, const int32_t* peer_id, const int32_t* peer_starts, i64 n, u64* row_number, u64* rank,
+                        u64* dense_rank);
+// out[i] = data[i + delta] inside row i's partition, else dflt[i] (dflt_is_null, or dflt == nullptr: NULL); width 1, 2, 4, 8 or 16 bytes
+void launch_window_shift(hipStream_t s, const void* data, const uint8_t* valid, int width, const int32_t* part_id, const int32_t* part_starts, i64 n, i64 delta, const void* dflt,
+                         const uint8_t* dflt_valid, int dflt_is_null, void* out, u64* out_valid);
+// Frames over the scan's running cells P (and counts C, or nullptr: never NULL): the value of row i is P[hi] - P[lo - 1] over
+//   WFRAME_ROWS     lo = part_start, hi = i            WFRAME_RANGE    lo = part_start, hi = peer_end(i) - 1
+//   WFRAME_SLIDING  lo = max(part_start, i - preceding) (preceding < 0: unbounded), hi = min(part_end - 1, i + following)
+// with P[part_start - 1] = 0, stored as out_kind says: the cell in out_width bytes (out_f32: a double stored as a float), or an AVG --
+// of an exact 128-bit integer sum in Float64, of a Float64 sum, of a decimal sum times mul, truncating.  out_valid: bit = count > 0.
+enum WinFrameMode : int32_t { WFRAME_ROWS = 0, WFRAME_RANGE = 1, WFRAME_SLIDING = 2 };
+enum WinOutKind : int32_t { WOUT_CELL = 0, WOUT_AVG_INT = 1, WOUT_AVG_F64 = 2, WOUT_AVG_DEC = 3 };
+struct WinFrame {
+  const void* cells; const i64* counts; const int32_t* part_id; const int32_t* part_starts; const int32_t* peer_id; const int32_t* peer_starts;
+  i64 preceding, following; u64 mul_lo, mul_hi;
+  int32_t cell_width, mode, out_kind, out_width, out_f32, pad;
+  void* out; u64* out_valid;
+};
+void launch_window_frame(hipStream_t s, const WinFrame& F, i64 n);
 // ----- one HyperLogLog estimate per segment of a column (kernels_hll.hip; hll_estimate.h has the hash and the estimator)
 enum HllKind : int32_t { HLL_SINT = 0, HLL_UINT = 1, HLL_F32 = 2, HLL_F64 = 3 };      // how a value of 8 bytes or fewer is widened to 64 bits (width 16: both words as they lie)
 struct HllCol { const void* data; const uint8_t* valid; int32_t width; int32_t kind; };

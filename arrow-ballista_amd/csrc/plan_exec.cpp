@@ -1479,6 +1479,277 @@ struct SortExec : PNode {
   }
 };
 
+// ---- BoundedWindowAggExec (include/gpuq.h has the grammar and the rules).  The node neither sorts nor checks: mode Sorted promises input
+// ordered by (partition_by, order_by), which the SortExec below it made.  The keys and the arguments are projected to fixed-width columns,
+// gpuq_segment_heads finds the partitions and the peer groups, gpuq_window_* do the rest; the result columns are appended to the input as
+// it came (a view stays a view).  Like the segment aggregates the node runs synchronously: it needs an exact row count.
+struct WinFn {
+  enum Kind { ROW_NUMBER, RANK, DENSE_RANK, LAG, LEAD, COUNT, SUM, MIN, MAX, AVG } kind = ROW_NUMBER;
+  std::string fn, name, frame_text = "RANGE UNBOUNDED PRECEDING .. CURRENT ROW";
+  bool has_arg = false; Json arg;
+  int64_t offset = 1; bool has_default = false; Json dflt;      // LAG / LEAD
+  int mode = GPUQ_FRAME_RANGE; int64_t preceding = -1, following = 0;
+  bool is_agg() const { return kind >= COUNT; }
+  bool is_shift() const { return kind == LAG || kind == LEAD; }
+};
+std::string upper_of(std::string s) { for (char& c : s) c = (char)std::toupper((unsigned char)c); return s; }
+// one bound of a frame: `unbounded` or `value` rows
+struct WinBound { std::string type; bool unbounded = false; int64_t value = 0; std::string text; };
+WinBound window_bound(const std::string& who, const Json& b, const char* which) {
+  WinBound r; r.type = upper_of(b.at("type").str());
+  if (r.type == "CURRENT ROW") r.type = "CURRENT_ROW";
+  if (r.type != "PRECEDING" && r.type != "FOLLOWING" && r.type != "CURRENT_ROW") throw std::runtime_error(who + ": window_frame " + which + " has the unknown type '" + b.at("type").str() + "'");
+  const Json* v = b.find("value");
+  if (r.type == "CURRENT_ROW") { r.text = "CURRENT ROW"; return r; }
+  if (!v || v->is_null()) { r.unbounded = true; r.text = "UNBOUNDED " + r.type; return r; }
+  const bool digits = (v->is_num() || v->is_str()) && !v->s.empty() && v->s.find_first_not_of("0123456789", v->s[0] == '-' ? 1 : 0) == std::string::npos && v->s != "-";
+  if (!digits) throw std::runtime_error(who + ": window_frame " + which + " value " + v->dump() + " is not a whole number of rows");
+  r.value = v->i64();
+  if (r.value < 0) throw std::runtime_error(who + ": window_frame " + which + " value " + v->dump() + " is negative");
+  r.text = std::to_string(r.value) + " " + r.type;
+  return r;
+}
+WinFn window_fn(const Json& w) {
+  WinFn f; f.fn = upper_of(w.at("fn").str()); f.name = w.at("name").str();
+  static const std::pair<const char*, WinFn::Kind> kinds[] = {{"ROW_NUMBER", WinFn::ROW_NUMBER}, {"RANK", WinFn::RANK}, {"DENSE_RANK", WinFn::DENSE_RANK}, {"LAG", WinFn::LAG},
+                                                              {"LEAD", WinFn::LEAD}, {"COUNT", WinFn::COUNT}, {"SUM", WinFn::SUM}, {"MIN", WinFn::MIN}, {"MAX", WinFn::MAX}, {"AVG", WinFn::AVG}};
+  bool known = false;
+  for (auto& k : kinds) if (f.fn == k.first) { f.kind = k.second; known = true; }
+  if (!known) throw Unsupported("BoundedWindowAggExec: the window function " + f.fn + " is not supported (ROW_NUMBER, RANK, DENSE_RANK, LAG, LEAD, COUNT, SUM, MIN, MAX, AVG)");
+  const Json none = jarr();
+  const Json& args = w.find("args") && !w.at("args").is_null() ? w.at("args") : none;
+  const std::string who = "BoundedWindowAggExec: " + f.fn;
+  if (f.kind <= WinFn::DENSE_RANK) { if (!args.a.empty()) throw std::runtime_error(who + " takes no arguments"); }
+  else if (f.is_shift()) {
+    if (args.a.empty() || args.a.size() > 3) throw std::runtime_error(who + " takes (x [, offset [, default]])");
+    auto literal = [&](const Json& e, const char* what) -> const Json& {
+      if (!(e.is_obj() && e.o.size() == 1 && e.o[0].first == "literal")) throw std::runtime_error(who + ": the " + what + " must be a literal");
+      return e.o[0].second;
+    };
+    if (args.a.size() >= 2) {
+      const Json* v = literal(args.a[1], "offset").find("value");
+      if (!v || v->is_null()) throw std::runtime_error(who + ": the offset must not be NULL");
+      f.offset = v->i64();
+      if (f.offset < 0) throw std::runtime_error(who + ": the offset " + std::to_string(f.offset) + " is negative");
+    }
+    if (args.a.size() == 3) { const Json* v = literal(args.a[2], "default").find("value"); if (v && !v->is_null()) { f.has_default = true; f.dflt = args.a[2]; } }
+  } else if (args.a.size() != 1) throw std::runtime_error(who + " takes one argument");
+  if (!args.a.empty()) { f.has_arg = true; f.arg = args.a[0]; }
+  // the frame: what the aggregate functions read.  The ranks and LAG / LEAD do not look at theirs: it is not parsed, whatever it holds
+  if (f.is_agg() && w.has("window_frame")) {
+    const Json& fr = w.at("window_frame");
+    const std::string units = upper_of(fr.at("units").str());
+    const WinBound s = window_bound(who, fr.at("start_bound"), "start_bound"), e = window_bound(who, fr.at("end_bound"), "end_bound");
+    f.frame_text = units + " " + s.text + " .. " + e.text;
+    {
+      const std::string what = who + " over the frame " + f.frame_text + ": ";
+      if (units != "ROWS" && units != "RANGE" && units != "GROUPS") throw std::runtime_error(who + ": window_frame units '" + fr.at("units").str() + "' are unknown");
+      if (units == "GROUPS") throw Unsupported(what + "GROUPS frames are not supported");
+      if (e.type == "FOLLOWING" && e.unbounded) throw Unsupported(what + "an end bound of UNBOUNDED FOLLOWING is the unbounded node's (WindowAggExec)");
+      if (s.type == "FOLLOWING") throw Unsupported(what + "a start bound of FOLLOWING is not supported");
+      if (e.type == "PRECEDING") throw Unsupported(what + "an end bound of PRECEDING is not supported");
+      if (units == "RANGE") {
+        if (!(s.type == "PRECEDING" && s.unbounded && e.type == "CURRENT_ROW")) throw Unsupported(what + "RANGE with a numeric offset or between peers only is not supported (RANGE UNBOUNDED PRECEDING .. CURRENT ROW is)");
+        f.mode = GPUQ_FRAME_RANGE;
+      } else {
+        f.preceding = s.type == "CURRENT_ROW" ? 0 : s.unbounded ? -1 : s.value;
+        f.following = e.type == "CURRENT_ROW" ? 0 : e.value;
+        f.mode = f.preceding < 0 && f.following == 0 ? GPUQ_FRAME_ROWS : GPUQ_FRAME_SLIDING;
+        if (f.mode == GPUQ_FRAME_SLIDING && (f.kind == WinFn::MIN || f.kind == WinFn::MAX))
+          throw Unsupported(what + "sliding frames are supported for SUM / COUNT / AVG only (a running MIN / MAX cannot be taken back)");
+      }
+    }
+  }
+  return f;
+}
+
+struct BoundedWindowAggExec : PNode {
+  PNodeP input; std::vector<WinFn> fns; Json partition_by = jarr(), order_by = jarr();
+  std::vector<PNode*> children() override { return {input.get()}; }
+  // typed once (the input's schema does not change): the output fields and every function's argument type
+  bool typed = false; PSchema out_schema; std::vector<DType> arg_types, result_types;
+  static PSchema typed_exprs(const PSchema& in, const std::vector<Json>& ex) {
+    const auto nm = schema_names(in);
+    PSchema out;
+    for (size_t a = 0; a < ex.size(); a += 12) {
+      const size_t hi = std::min(a + 12, ex.size());
+      std::vector<std::string> names; for (size_t i = a; i < hi; ++i) names.push_back("__w" + std::to_string(i));
+      const PSchema part = compiled_outputs(project_desc(input_of(in), std::vector<Json>(ex.begin() + (long)a, ex.begin() + (long)hi), names, &nm));
+      out.insert(out.end(), part.begin(), part.end());
+    }
+    return out;
+  }
+  void type_node() {
+    if (typed) return;
+    const PSchema in = input->schema(); const auto nm = schema_names(in);
+    std::vector<Json> ex;
+    for (auto& p : partition_by.a) ex.push_back(p);
+    for (auto& o : order_by.a) ex.push_back(o.at("expr"));
+    const size_t nkeys = ex.size();
+    for (auto& f : fns) if (f.has_arg) ex.push_back(f.arg);
+    const PSchema t = typed_exprs(in, ex);
+    for (size_t k = 0; k < partition_by.a.size(); ++k) {
+      const DType dt = dtype_from_json(t[k].type);
+      if (dt.is_float()) throw Unsupported("BoundedWindowAggExec: the " + dt.to_string() + " partition_by column " + partition_by.a[k].dump() + " is refused (bytewise segment heads: -0.0 / 0.0 and the NaNs "
+                                           "would be partitions of their own)");
+    }
+    PSchema out = in; size_t ai = nkeys;
+    arg_types.assign(fns.size(), DType{}); result_types.assign(fns.size(), DType{});
+    for (size_t i = 0; i < fns.size(); ++i) {
+      const WinFn& f = fns[i];
+      PField r; r.name = f.name; r.nullable = true;
+      if (f.has_arg) arg_types[i] = dtype_from_json(t[ai].type);
+      if (!f.has_arg) { r.type = jstr("UInt64"); r.nullable = false; }
+      else if (f.is_shift()) {
+        if (arg_types[i].id == T_UTF8 || arg_types[i].id == T_BOOL) throw Unsupported("BoundedWindowAggExec: " + f.fn + " over " + arg_types[i].to_string() + " is not supported (fixed-width types only)");
+        r.type = t[ai].type;
+      } else {
+        if (!(f.kind == WinFn::COUNT || arg_types[i].is_int() || arg_types[i].is_float() || arg_types[i].is_decimal() || arg_types[i].is_temporal()))
+          throw Unsupported("BoundedWindowAggExec: " + f.fn + " over " + arg_types[i].to_string() + " is not supported");
+        // the type the AGG_FNS row of the same name gives in mode Single; what it refuses is refused here, in its words
+        const PSchema a = compiled_outputs(jobj({{"op", jstr("aggregate")}, {"mode", jstr("Single")}, {"input", input_of(in)}, {"strategy", jstr("hash")}, {"group_expr", jarr()},
+                                                 {"aggr_expr", jarr({jobj({{"fn", jstr(f.fn)}, {"name", jstr(f.name)}, {"expr", rebind(f.arg, nm)}})})}}));
+        r.type = a.at(0).type;
+        if (f.kind == WinFn::COUNT) r.nullable = false;
+        if (f.mode == GPUQ_FRAME_SLIDING && arg_types[i].is_float())
+          throw Unsupported("BoundedWindowAggExec: " + f.fn + " over the frame " + f.frame_text + " of a " + arg_types[i].to_string() + " argument: sliding frames over floats are not supported (a difference of "
+                            "two running sums cancels)");
+      }
+      result_types[i] = dtype_from_json(r.type);
+      if (f.has_arg) ++ai;
+      out.push_back(r);
+    }
+    out_schema = out; typed = true;
+  }
+  PSchema schema() override { type_node(); return out_schema; }
+
+  PTable execute(int part, Exec& x) override {
+    type_node();
+    PTable t = input->execute(part, x);
+    auto t0 = std::chrono::steady_clock::now();
+    settle(x, &t);      // what is pending is settled and t's count made exact; nothing below is offered a deferred run
+    struct SyncOnly { Exec& x; bool was; explicit SyncOnly(Exec& x_) : x(x_), was(x_.deferred) { x.deferred = false; } ~SyncOnly() { x.deferred = was; } } sync_only(x);
+    const int64_t n = t.n;
+    if (n >= (1ll << 31)) throw Unsupported("BoundedWindowAggExec over >= 2^31 rows in one partition of the plan (segment ids are 32-bit)");
+    hipStream_t s = (hipStream_t)x.stream;
+    // ---- 1. keys and arguments as fixed-width columns
+    const size_t np = partition_by.a.size(), no = order_by.a.size();
+    std::vector<Json> ex; std::vector<std::string> nm;
+    auto add_key = [&](const Json& e, const char* what, const std::string& name) {
+      const int ci = long_key_column(t, e);
+      if (ci >= 0) {      // a string key leaves the projection as 16 packed bytes
+        int32_t maxlen = 0;
+        check(x, gpuq_utf8_max_len(x.ctx, x.stream, &t.cols[(size_t)ci].c, via_of(t, (size_t)ci), n, &maxlen));
+        if (maxlen > 15) throw Unsupported(std::string("BoundedWindowAggExec: the ") + what + " column '" + t.cols[(size_t)ci].name + "' holds strings longer than 15 bytes (" + std::to_string(maxlen) + ")");
+      }
+      ex.push_back(e); nm.push_back(name);
+    };
+    for (size_t k = 0; k < np; ++k) add_key(partition_by.a[k], "partition_by", "__wp" + std::to_string(k));
+    for (size_t k = 0; k < no; ++k) add_key(order_by.a[k].at("expr"), "order_by", "__wo" + std::to_string(k));
+    std::vector<std::string> arg_text; std::vector<int> arg_of(fns.size(), -1), dflt_of(fns.size(), -1);
+    for (size_t i = 0; i < fns.size(); ++i) {
+      if (!fns[i].has_arg) continue;
+      Json arg = fns[i].arg;      // COUNT reads the validity alone: of a Utf8 / Boolean argument (any length) as `CASE WHEN x IS NOT NULL THEN 1 END`
+      if (fns[i].kind == WinFn::COUNT && (arg_types[i].id == T_UTF8 || arg_types[i].id == T_BOOL))
+        arg = jobj({{"case_", jobj({{"when_then_expr", jarr({jobj({{"when_expr", jobj({{"is_not_null_expr", jobj({{"expr", arg}})}})},
+                                                                   {"then_expr", jobj({{"literal", jobj({{"type", jstr("Int64")}, {"value", jstr("1")}})}})}})})}})}});
+      const std::string text = arg.dump();
+      size_t j = 0; while (j < arg_text.size() && arg_text[j] != text) ++j;
+      if (j == arg_text.size()) { arg_text.push_back(text); ex.push_back(arg); nm.push_back("__wa" + std::to_string(j)); }
+      arg_of[i] = (int)(np + no + j);
+    }
+    for (size_t i = 0; i < fns.size(); ++i) {      // a default literal travels as a column of the argument's type: the expression compiler parses and casts it
+      if (!fns[i].has_default) continue;
+      dflt_of[i] = (int)ex.size();
+      ex.push_back(jobj({{"cast", jobj({{"expr", fns[i].dflt}, {"arrow_type", type_json_of(arg_types[i].id, arg_types[i].p, arg_types[i].s)}})}}));
+      nm.push_back("__wd" + std::to_string(i));
+    }
+    PTable proj;
+    if (!ex.empty()) proj = project_wide(x, t, ex, nm, this, 1);
+    // ---- 2. partitions and peer groups
+    BufP part_id = alloc_rows(n), part_starts = dev_alloc((size_t)(n + 2) * 4), peer_id = part_id, peer_starts = part_starts, cnt = dev_alloc(16);
+    std::vector<gpuq_column> kc;
+    for (size_t k = 0; k < np + no; ++k) kc.push_back(proj.cols[k].c);
+    check(x, gpuq_segment_heads(x.ctx, x.stream, kc.data(), (int)np, n, (int32_t*)part_id->p, (int32_t*)part_starts->p, n, (uint64_t*)cnt->p));
+    if (no) {
+      peer_id = alloc_rows(n); peer_starts = dev_alloc((size_t)(n + 2) * 4);
+      check(x, gpuq_segment_heads(x.ctx, x.stream, kc.data(), (int)(np + no), n, (int32_t*)peer_id->p, (int32_t*)peer_starts->p, n, (uint64_t*)cnt->p));
+    }
+    const int32_t* pid = (const int32_t*)part_id->p; const int32_t* pst = (const int32_t*)part_starts->p;
+    const int32_t* qid = (const int32_t*)peer_id->p; const int32_t* qst = (const int32_t*)peer_starts->p;
+    // ---- 3. one result column per function, appended to the input as it came
+    PTable out = t;
+    struct Scan { BufP cells, counts; };
+    std::map<std::string, Scan> scans;
+    std::vector<std::pair<BufP, std::string>> wide_checks;
+    auto scan = [&](const WinFn& f, const gpuq_column& ac, int gfn, int cw, bool counts, const BufP& cells_to, const BufP& valid_to) {
+      const std::string key = std::to_string(gfn) + "|" + std::to_string((uintptr_t)ac.data) + "|" + std::to_string(cw) + (counts ? "c" : "");
+      auto it = cells_to ? scans.end() : scans.find(key);
+      if (it != scans.end()) return it->second;
+      Scan sc; sc.cells = cells_to ? cells_to : dev_alloc((size_t)std::max<int64_t>(n, 1) * (size_t)cw + 16);
+      if (counts) sc.counts = dev_alloc((size_t)std::max<int64_t>(n, 1) * 8 + 16);
+      BufP status;
+      if ((gfn == GPUQ_WINDOW_MIN || gfn == GPUQ_WINDOW_MAX) && (ac.type == T_DECIMAL128 || ac.type == T_UINT64)) {
+        status = dev_alloc(16); HIPCHECK(hipMemsetAsync(status->p, 0, 16, s)); wide_checks.push_back({status, f.fn});
+      }
+      check(x, gpuq_window_scan(x.ctx, x.stream, &ac, np ? pid : nullptr, n, gfn, sc.cells->p, cw, counts ? (int64_t*)sc.counts->p : nullptr, valid_to ? (uint8_t*)valid_to->p : nullptr,
+                                status ? (uint32_t*)status->p : nullptr));
+      if (!cells_to) scans[key] = sc;
+      return sc;
+    };
+    BufP ranks[3]; bool ranked = false;
+    for (size_t i = 0; i < fns.size(); ++i) {
+      const WinFn& f = fns[i]; const DType rt = result_types[i];
+      const size_t ow = (size_t)type_width(rt);
+      if (!f.has_arg) {      // the three ranks of a node come out of one launch
+        if (!ranked) {
+          for (auto& g : fns) if (!g.has_arg && !ranks[g.kind]) ranks[g.kind] = dev_alloc((size_t)std::max<int64_t>(n, 1) * 8 + 16);
+          check(x, gpuq_window_rank(x.ctx, x.stream, pid, pst, qid, qst, n, ranks[0] ? (uint64_t*)ranks[0]->p : nullptr, ranks[1] ? (uint64_t*)ranks[1]->p : nullptr,
+                                    ranks[2] ? (uint64_t*)ranks[2]->p : nullptr));
+          ranked = true;
+        }
+        append_column(out, f.name, T_UINT64, ranks[f.kind]->p, ranks[f.kind], nullptr, n, false);
+        continue;
+      }
+      const gpuq_column& ac = proj.cols[(size_t)arg_of[i]].c;
+      const DType at = arg_types[i];
+      BufP data = dev_alloc((size_t)std::max<int64_t>(n, 1) * ow + 16), valid;
+      const bool nullable = f.kind != WinFn::COUNT;
+      if (nullable) valid = dev_alloc(bitmap_bytes(n));
+      if (f.is_shift()) {
+        const gpuq_column* dc = dflt_of[i] >= 0 ? &proj.cols[(size_t)dflt_of[i]].c : nullptr;
+        check(x, gpuq_window_shift(x.ctx, x.stream, &ac, pid, pst, n, f.kind == WinFn::LAG ? -f.offset : f.offset, dc, data->p, (uint8_t*)valid->p));
+      } else {
+        const bool flt = at.is_float(), avg = f.kind == WinFn::AVG;
+        const int gfn = f.kind == WinFn::COUNT ? GPUQ_WINDOW_COUNT : f.kind == WinFn::MIN ? GPUQ_WINDOW_MIN : f.kind == WinFn::MAX ? GPUQ_WINDOW_MAX : GPUQ_WINDOW_SUM;
+        const bool sum128 = gfn == GPUQ_WINDOW_SUM && !flt;
+        // the running value IS the result when the frame is ROWS UNBOUNDED PRECEDING .. CURRENT ROW and the cell has the result's width
+        const bool direct = f.mode == GPUQ_FRAME_ROWS && !avg && (gfn == GPUQ_WINDOW_SUM || gfn == GPUQ_WINDOW_COUNT || ow == 8);
+        if (direct) (void)scan(f, ac, gfn, (int)ow, false, data, valid);
+        else {
+          const Scan sc = scan(f, ac, gfn, sum128 ? 16 : 8, nullable, nullptr, nullptr);
+          gpuq_window_frame_spec fs{};
+          fs.cells = sc.cells->p; fs.counts = nullable ? (const int64_t*)sc.counts->p : nullptr; fs.cell_width = sum128 ? 16 : 8;
+          fs.mode = f.mode; fs.preceding = f.preceding; fs.following = f.following;
+          fs.part_id = pid; fs.part_starts = pst; fs.peer_id = qid; fs.peer_starts = qst;
+          fs.out_kind = !avg ? GPUQ_WINDOW_OUT_CELL : flt ? GPUQ_WINDOW_OUT_AVG_FLOAT : at.is_decimal() ? GPUQ_WINDOW_OUT_AVG_DECIMAL : GPUQ_WINDOW_OUT_AVG_INT;
+          fs.out_width = (int32_t)ow; fs.out_f32 = (!avg && rt.id == T_FLOAT32) ? 1 : 0;
+          fs.avg_scale_digits = avg && at.is_decimal() ? std::max(0, rt.s - at.s) : 0;
+          fs.out = data->p; fs.out_validity = valid ? (uint8_t*)valid->p : nullptr;
+          check(x, gpuq_window_frame(x.ctx, x.stream, &fs, n));
+          out.keep.push_back(sc.cells); if (sc.counts) out.keep.push_back(sc.counts);      // (read by a launch that may still be in flight)
+        }
+      }
+      append_column(out, f.name, rt.id, data->p, data, valid, n, nullable, rt.p, rt.s);
+    }
+    for (auto& w : wide_checks)
+      if (read_u64(x, w.first->p) & 1u) throw Unsupported("BoundedWindowAggExec: " + w.second + " met an operand outside int64, which MIN / MAX do not hold (as the aggregate operator refuses it)");
+    for (const BufP& b : {part_id, part_starts, peer_id, peer_starts, cnt}) out.keep.push_back(b);
+    out.own(proj);
+    return timed(x, t0, out);
+  }
+};
+
 struct HashJoinExec : PNode {
   PNodeP left, right; Json on; std::string join_type = "Inner", partition_mode = "CollectLeft"; bool null_equals_null = false; bool has_filter = false; Json filter;
   std::vector<PNode*> children() override { return {left.get(), right.get()}; }
@@ -2707,6 +2978,25 @@ PNodeP build_node(const Json& j) {
     out = std::move(n);
   } else if (kind == "SortExec" || kind == "SortPreservingMergeExec") {
     auto n = std::make_unique<SortExec>(); n->input = build_child(v, "input"); n->expr = v.at("expr"); n->fetch = v.get_i64("fetch", -1); n->merge_all = kind != "SortExec";
+    out = std::move(n);
+  } else if (kind == "BoundedWindowAggExec") {
+    // WindowAggExecNode with partition_search_mode set (datafusion.proto:1417-1427); the unbounded WindowAggExec stays not native (below)
+    auto n = std::make_unique<BoundedWindowAggExec>(); n->input = build_child(v, "input");
+    const std::string mode = v.at("partition_search_mode").str();
+    if (mode == "Linear" || mode == "PartiallySorted") throw Unsupported("BoundedWindowAggExec: partition_search_mode " + mode + " is not supported (Sorted: input ordered by partition_by, order_by)");
+    if (mode != "Sorted") throw std::runtime_error("BoundedWindowAggExec: partition_search_mode '" + mode + "' is unknown");
+    const Json& we = v.at("window_expr");
+    if (!we.is_arr() || we.a.empty()) throw std::runtime_error("BoundedWindowAggExec: window_expr must be a non-empty array");
+    auto list_of = [](const Json& w, const char* k) { const Json* j = w.find(k); return j && j->is_arr() ? *j : jarr(); };
+    n->partition_by = list_of(we.a[0], "partition_by");
+    for (auto& o : list_of(we.a[0], "order_by").a) n->order_by.a.push_back(sort_key(o, o.at("expr")));
+    for (auto& w : we.a) {
+      n->fns.push_back(window_fn(w));
+      Json ob = jarr(); for (auto& o : list_of(w, "order_by").a) ob.a.push_back(sort_key(o, o.at("expr")));
+      if (list_of(w, "partition_by").dump() != n->partition_by.dump() || ob.dump() != n->order_by.dump())
+        throw Unsupported("BoundedWindowAggExec: the window expression '" + n->fns.back().name + "' (" + n->fns.back().fn + ") differs from the node's first in partition_by or order_by; one node "
+                          "computes one (partition_by, order_by)");
+    }
     out = std::move(n);
   } else if (kind == "HashJoinExec") {
     auto n = std::make_unique<HashJoinExec>(); n->left = build_child(v, "left"); n->right = build_child(v, "right"); n->on = v.at("on");

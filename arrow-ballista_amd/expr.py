@@ -178,6 +178,42 @@ def case(when_then, else_expr=None, expr=None):
                       "else_expr": else_expr}}
 
 
+# ---------------------------------------------------------------- window expressions (PhysicalWindowExprNode, datafusion.proto:1198-1209)
+def sort_expr(e, asc=True, nulls_first=None):
+    """One ORDER BY entry (PhysicalSortExprNode): nulls_first defaults to NULLS LAST for ASC, NULLS FIRST for DESC."""
+    return {"expr": e, "asc": bool(asc), "nulls_first": (not asc) if nulls_first is None else bool(nulls_first)}
+
+
+def frame_bound(type, value=None):
+    """WindowFrameBound (datafusion.proto:791-799): type PRECEDING | CURRENT_ROW | FOLLOWING; value None = UNBOUNDED (or no value)."""
+    return {"type": type, "value": None if value is None else int(value)}
+
+
+def window_frame(units="RANGE", start=None, end=None):
+    """WindowFrame (datafusion.proto:780-789).  Defaults: UNBOUNDED PRECEDING .. CURRENT ROW."""
+    return {"units": units, "start_bound": start if start is not None else frame_bound("PRECEDING"), "end_bound": end if end is not None else frame_bound("CURRENT_ROW")}
+
+
+def rows_between(preceding=None, following=0):
+    """ROWS `preceding` PRECEDING (None: UNBOUNDED) .. `following` FOLLOWING (0: CURRENT ROW)."""
+    return window_frame("ROWS", frame_bound("PRECEDING", preceding), frame_bound("FOLLOWING", following) if following else frame_bound("CURRENT_ROW"))
+
+
+def window(fn, args, name, partition_by=(), order_by=(), frame=None):
+    """One window expression of a BoundedWindowAggExec: fn(args) OVER (PARTITION BY partition_by ORDER BY order_by [frame]).
+    order_by: sort_expr(...) entries; frame None: RANGE UNBOUNDED PRECEDING .. CURRENT ROW."""
+    return {"fn": fn, "args": list(args), "partition_by": list(partition_by), "order_by": list(order_by), "window_frame": frame, "name": name}
+
+
+def lag(x, name, offset=1, default=None, **over):
+    """LAG(x, offset, default): default a literal (lit(...)) or None for NULL."""
+    return window("LAG", [x, lit(int(offset), "Int64")] + ([default] if default is not None else []), name, **over)
+
+
+def lead(x, name, offset=1, default=None, **over):
+    return window("LEAD", [x, lit(int(offset), "Int64")] + ([default] if default is not None else []), name, **over)
+
+
 # ---------------------------------------------------------------- tree utilities (host-side planning)
 def columns_of(e, acc=None):
     """Set of column names referenced by an expression."""

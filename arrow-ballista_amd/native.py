@@ -74,6 +74,8 @@ def plan_to_json(node, tc, inputs):
         return {"HashJoinExec": d}
     if isinstance(node, P.CrossJoinExec):
         return {"CrossJoinExec": {"left": sub(node.left), "right": sub(node.right)}}
+    if isinstance(node, P.BoundedWindowAggExec):
+        return node._json(sub(node.input))
     if isinstance(node, P.SortPreservingMergeExec):
         return {"SortPreservingMergeExec": {"input": sub(node.input), "expr": node.expr, "fetch": -1 if node.fetch is None else int(node.fetch)}}
     if isinstance(node, P.SortExec):

@@ -984,6 +984,33 @@ class CrossJoinExec(ExecutionPlan):
         raise B.GpuqError(3, "CrossJoinExec runs in the native executor (NativePlan)")
 
 
+class BoundedWindowAggExec(ExecutionPlan):
+    """BoundedWindowAggExec(input, window_expr, partition_search_mode="Sorted") -- WindowAggExecNode with partition_search_mode set,
+    datafusion.proto:1417-1427: the node DataFusion plans when every window expression has a bounded frame.  window_expr: a list of
+    expr.window(...) dicts that agree on partition_by and order_by; the input must be ordered by (partition_by, order_by) -- the node
+    neither sorts nor checks, a SortExec below it does the sorting.  Output: the input's columns, then one per expression.  Functions,
+    frames and what is refused: include/gpuq.h, with the plan nodes.  Executed by the native executor (NativePlan); this class types it."""
+
+    def __init__(self, input, window_expr, partition_search_mode="Sorted"):
+        super().__init__()
+        self.input, self.window_expr, self.partition_search_mode = input, list(window_expr), partition_search_mode
+
+    def children(self):
+        return [self.input]
+
+    def _json(self, input_json):
+        return {"BoundedWindowAggExec": {"input": input_json, "window_expr": [{k: v for k, v in w.items() if v is not None} for w in self.window_expr],
+                                         "partition_search_mode": self.partition_search_mode}}
+
+    def schema(self):
+        leaf = {"MemoryExec": {"schema": [{"name": f["name"], "type": f["type"], "nullable": bool(f.get("nullable", True))} for f in self.input.schema()],
+                               "partitions": [0]}}
+        return B.plan_schema(self._json(leaf))
+
+    def execute(self, partition, context):
+        raise B.GpuqError(3, "BoundedWindowAggExec runs in the native executor (NativePlan)")
+
+
 class UnionExec(ExecutionPlan):
     """UnionExec(inputs) -- datafusion.proto:1319-1321: output partitions are the inputs' partitions, one after another
     (UNION ALL; UNION adds an AggregateExec over all columns, client/src/context.rs:691-733)."""

@@ -3,7 +3,7 @@
 //!
 //! Nodes are recognised the way the reference does it itself: `as_any().downcast_ref::<T>()`
 //! (ballista/core/src/physical_optimizer/task_group.rs:143-167, ballista/core/src/utils.rs:274-311).  A subtree the
-//! device path does not execute (a window, an expression outside the supported subset, a scan the native leaves do not
+//! device path does not execute (an unbounded window, an expression outside the supported subset, a scan the native leaves do not
 //! cover) is NOT an error: it becomes a *host leaf* -- the shim runs that subtree with DataFusion as the stock executor
 //! would and hands its batches to the device through the Arrow C Data Interface (`gpuq_table_import_arrow`), as input
 //! slot k of a `MemoryExec` node.
@@ -36,6 +36,9 @@ use datafusion::physical_plan::projection::ProjectionExec;
 use datafusion::physical_plan::sorts::sort::SortExec;
 use datafusion::physical_plan::sorts::sort_preserving_merge::SortPreservingMergeExec;
 use datafusion::physical_plan::union::UnionExec;
+use datafusion::logical_expr::{WindowFrameBound, WindowFrameUnits};
+use datafusion::physical_plan::windows::{BoundedWindowAggExec, BuiltInWindowExpr, PartitionSearchMode, PlainAggregateWindowExpr, SlidingAggregateWindowExpr};
+use datafusion::physical_expr::window::{Rank, RankType, RowNumber, WindowExpr, WindowShift};
 use datafusion::physical_plan::{AggregateExpr, ExecutionPlan, Partitioning, PhysicalExpr};
 use serde_json::{json, Value};
 
@@ -195,6 +198,62 @@ fn sort_exprs(v: &[PhysicalSortExpr]) -> Result<Value> {
     Ok(Value::Array(r?))
 }
 
+/// One bound of a window frame (WindowFrameBound, datafusion.proto:791-799): a NULL scalar is UNBOUNDED.
+fn frame_bound(b: &WindowFrameBound) -> Result<Value> {
+    let rows = |v: &ScalarValue| -> Result<Value> {
+        if v.is_null() { return Ok(Value::Null); }
+        match v {
+            ScalarValue::UInt64(Some(x)) => Ok(json!(x)),
+            ScalarValue::Int64(Some(x)) => Ok(json!(x)),
+            other => unsupported(format!("window frame offset {other:?}")),      // a RANGE offset in the order key's type
+        }
+    };
+    Ok(match b {
+        WindowFrameBound::Preceding(v) => json!({"type": "PRECEDING", "value": rows(v)?}),
+        WindowFrameBound::CurrentRow => json!({"type": "CURRENT_ROW", "value": Value::Null}),
+        WindowFrameBound::Following(v) => json!({"type": "FOLLOWING", "value": rows(v)?}),
+    })
+}
+
+/// PhysicalWindowExprNode mirror (datafusion.proto:1198-1209) for the functions the native BoundedWindowAggExec runs; anything else keeps
+/// the node on the host.  [UPSTREAM-KNOWLEDGE: datafusion 34 physical-expr window/{built_in, rank, row_number, lead_lag, aggregate,
+/// sliding_aggregate}.rs -- LAG holds a positive shift offset, LEAD a negative one.]
+fn window_expr(w: &Arc<dyn WindowExpr>) -> Result<Value> {
+    let x = w.as_any();
+    // (is_agg: only the aggregate functions read their frame; the ranks' and LAG / LEAD's is left out, whatever scalars its bounds hold)
+    let mut is_agg = false;
+    let (name, args): (&str, Vec<Value>) = if let Some(b) = x.downcast_ref::<BuiltInWindowExpr>() {
+        let f = b.get_built_in_func_expr();
+        let fa = f.as_any();
+        if fa.is::<RowNumber>() { ("ROW_NUMBER", vec![]) }
+        else if let Some(r) = fa.downcast_ref::<Rank>() {
+            match r.get_type() { RankType::Basic => ("RANK", vec![]), RankType::Dense => ("DENSE_RANK", vec![]), RankType::Percent => return unsupported("PERCENT_RANK") }
+        } else if let Some(s) = fa.downcast_ref::<WindowShift>() {
+            let off = s.get_shift_offset();
+            let mut a = vec![expr(&f.expressions()[0])?, json!({"literal": {"type": "Int64", "value": off.abs()}})];
+            if let Some(d) = s.get_default_value() { a.push(json!({"literal": literal(&d)?})); }
+            (if off >= 0 { "LAG" } else { "LEAD" }, a)
+        } else { return unsupported(format!("window function {}", f.name())) }
+    } else {
+        let agg = if let Some(p) = x.downcast_ref::<PlainAggregateWindowExpr>() { p.get_aggregate_expr() }
+                  else if let Some(p) = x.downcast_ref::<SlidingAggregateWindowExpr>() { p.get_aggregate_expr() }
+                  else { return unsupported(format!("window expression {}", w.name())) };
+        let name = aggregate_fn(agg)?;
+        if !["COUNT", "SUM", "MIN", "MAX", "AVG"].contains(&name) { return unsupported(format!("window aggregate {name}")); }
+        let a: Result<Vec<Value>> = agg.expressions().iter().map(expr).collect();
+        is_agg = true;
+        (name, a?)
+    };
+    let pb: Result<Vec<Value>> = w.partition_by().iter().map(expr).collect();
+    let fr = w.get_window_frame();
+    let units = match fr.units { WindowFrameUnits::Rows => "ROWS", WindowFrameUnits::Range => "RANGE", WindowFrameUnits::Groups => "GROUPS" };
+    let mut j = json!({"fn": name, "args": args, "partition_by": pb?, "order_by": sort_exprs(w.order_by())?, "name": w.name()});
+    if is_agg {
+        j["window_frame"] = json!({"units": units, "start_bound": frame_bound(&fr.start_bound)?, "end_bound": frame_bound(&fr.end_bound)?});
+    }
+    Ok(j)
+}
+
 fn aggregate_fn(a: &Arc<dyn AggregateExpr>) -> Result<&'static str> {
     let x = a.as_any();
     Ok(if x.is::<Sum>() { "SUM" } else if x.is::<Avg>() { "AVG" } else if x.is::<Count>() { "COUNT" } else if x.is::<Min>() { "MIN" } else if x.is::<Max>() { "MAX" }
@@ -259,6 +318,16 @@ fn walk_node(p: &Arc<dyn ExecutionPlan>, leaves: &mut Vec<(Arc<dyn ExecutionPlan
     if let Some(n) = a.downcast_ref::<CrossJoinExec>() {
         // (an uncorrelated scalar subquery arrives as a one-row left side; gpuq refuses more than 2^32 pairs)
         return Ok(json!({"CrossJoinExec": {"left": walk(n.left(), leaves)?, "right": walk(n.right(), leaves)?}}));
+    }
+    if let Some(n) = a.downcast_ref::<BoundedWindowAggExec>() {
+        // The bounded-frame window node, in mode Sorted only: the input is ordered by (partition_by, order_by), which is all the native node
+        // asks for.  Linear / PartiallySorted, the unbounded WindowAggExec and the functions window_expr does not name stay host leaves; a
+        // frame or an argument type the device refuses (include/gpuq.h lists them) is refused loudly by gpuq_plan_create, as any refusal is.
+        if !matches!(n.partition_search_mode, PartitionSearchMode::Sorted) {
+            return unsupported("BoundedWindowAggExec in a partition_search_mode other than Sorted");
+        }
+        let we: Result<Vec<Value>> = n.window_expr().iter().map(window_expr).collect();
+        return Ok(json!({"BoundedWindowAggExec": {"input": walk(n.input(), leaves)?, "window_expr": we?, "partition_search_mode": "Sorted"}}));
     }
     if let Some(n) = a.downcast_ref::<SortExec>() {
         if n.preserve_partitioning() && n.input().output_partitioning().partition_count() > 1 {

@@ -476,6 +476,69 @@ def approx_distinct(tc, T, g, log2n=28, n_grouped=10_000_000, k=100, reps=3):
     return out
 
 
+def window(tc, T, g, log2n=28, log2p=20, reps=3):
+    """BoundedWindowAggExec over 2^log2n Int64 rows that are already ordered by an Int32 partition key of about 2^log2p partitions (their
+    sizes geometric) and an Int64 order key: one plan computes ROW_NUMBER, a running SUM (ROWS UNBOUNDED PRECEDING .. CURRENT ROW) and
+    LAG(v, 1), through the native plan executor, inputs resident in HBM, best of `reps` after one warm-up.  Next to the step time: the
+    segmented scan alone (gpuq_window_scan, its three launches between two events) with its share of the 8 TB/s peak on the algorithmic
+    bytes 2 (8 + 4) + 8 + 1/8 per row -- value and segment id read twice, the cell and a validity bit written once -- and a plain
+    ungrouped SUM over the same column in the same process, which is the one-read floor."""
+    import ctypes as C
+    import numpy as np
+    import pyarrow as pa
+    import torch
+    from arrow_ballista_amd import binding as B
+    from arrow_ballista_amd import expr as E
+    from arrow_ballista_amd.expr import col
+    n = 1 << log2n
+    r = np.random.default_rng(9)
+    k = np.cumsum(r.integers(0, 1 << (log2n - log2p), n, dtype=np.uint16 if log2n - log2p <= 16 else np.uint32) == 0, dtype=np.int32)
+    t = pa.table({"k": pa.array(k), "o": pa.array(np.arange(n, dtype=np.int64)), "v": pa.array(r.integers(-1000, 1000, n))})
+    t = t.cast(pa.schema([pa.field("k", pa.int32(), nullable=False), pa.field("o", pa.int64(), nullable=False), pa.field("v", pa.int64(), nullable=False)]))
+    partitions = int(k[-1]) + 1
+    dev = g.DeviceTable.from_arrow(t, tc.device)
+    src = g.MemoryExec([dev])
+    del k, t
+
+    def timed(plan):
+        plan.execute(0); best = None
+        for _ in range(reps):
+            _sync(tc); t0 = time.perf_counter(); res = plan.execute(0); _sync(tc); dt = time.perf_counter() - t0
+            best = dt if best is None or dt < best else best
+        return best * 1e3, res
+    ov = dict(partition_by=[col("k")], order_by=[E.sort_expr(col("o"))])
+    node = g.BoundedWindowAggExec(src, [E.window("ROW_NUMBER", [], "rn", **ov), E.window("SUM", [col("v")], "s", frame=E.rows_between(None, 0), **ov), E.lag(col("v"), "l", **ov)])
+    out = {"rows": n, "partitions": partitions}
+    out["step_ms"], res = timed(g.NativePlan(node, tc))
+    tail = res.to_arrow().slice(n - 4, 4)
+    out["last_rows"] = {c: tail[c].to_pylist() for c in ("k", "rn", "s", "l")}
+    del res, tail
+    s = src.schema()
+    out["plain_sum_ms"], _ = timed(g.NativePlan(g.AggregateExec("Single", [], [{"fn": "SUM", "expr": col("v", s), "name": "s"}], src), tc))
+    # the scan alone, on the entry point the node calls
+    L, ctx, stream = B.lib(), tc.ctx.h, tc.stream_ptr()
+    kc, vc = dev.column("k").to_c(), dev.column("v").to_c()
+    seg = torch.empty(n, dtype=torch.int32, device=tc.device); starts = torch.empty(n + 2, dtype=torch.int32, device=tc.device)
+    cnt = torch.zeros(2, dtype=torch.int64, device=tc.device)
+    cells = torch.empty(n, dtype=torch.int64, device=tc.device); valid = torch.empty((n + 63) // 64 + 1, dtype=torch.int64, device=tc.device)
+    tc.ctx.check(L.gpuq_segment_heads(ctx, stream, C.byref(kc), 1, n, seg.data_ptr(), starts.data_ptr(), n, cnt.data_ptr()))
+    best = None
+    for _ in range(reps + 1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        tc.ctx.check(L.gpuq_window_scan(ctx, stream, C.byref(vc), seg.data_ptr(), n, 0, cells.data_ptr(), 8, None, valid.data_ptr(), None))
+        e1.record(); _sync(tc)
+        ms = e0.elapsed_time(e1)
+        best = ms if best is None or ms < best else best
+    out["scan_ms"] = best
+    out["scan_bytes_per_row"] = 2 * (8 + 4) + 8 + 0.125
+    out["scan_GBps"] = n * out["scan_bytes_per_row"] / best / 1e6
+    out["scan_share_of_8TBps"] = out["scan_GBps"] / 8000.0
+    out["plain_sum_GBps"] = n * 8 / out["plain_sum_ms"] / 1e6
+    out["scan_over_plain_sum"] = best / out["plain_sum_ms"]
+    return out
+
+
 def like_micro(tc, T, g, n=1 << 23, reps=5):
     """LikeExpr throughput (q13's `o_comment NOT LIKE '%special%requests%'` shape): n comment-like strings of 19-78 bytes built
     from a word list, Arrow layout in HBM; one gpuq_like_utf8 launch per pattern.  Bytes = offsets + string bytes read."""
@@ -911,6 +974,11 @@ if __name__ == "__main__":
         bits = int(sys.argv[sys.argv.index("--log2n") + 1]) if "--log2n" in sys.argv else 28
         rows = int(sys.argv[sys.argv.index("--rows") + 1]) if "--rows" in sys.argv else 10_000_000
         print(json.dumps(approx_distinct(tc, T, g, bits, rows), indent=1))
+        sys.exit(0)
+    if "--window" in sys.argv:      # [--log2n 28] [--log2p 20]
+        bits = int(sys.argv[sys.argv.index("--log2n") + 1]) if "--log2n" in sys.argv else 28
+        pbits = int(sys.argv[sys.argv.index("--log2p") + 1]) if "--log2p" in sys.argv else 20
+        print(json.dumps(window(tc, T, g, bits, pbits)))
         sys.exit(0)
     if "--h2o" in sys.argv:
         rows = int(sys.argv[sys.argv.index("--rows") + 1]) if "--rows" in sys.argv else 10_000_000

@@ -582,6 +582,51 @@ int gpuq_segment_median(gpuq_ctx* ctx, void* stream, const gpuq_column* value_co
 int gpuq_segment_approx_distinct(gpuq_ctx* ctx, void* stream, const gpuq_column* value_col, const int32_t* starts, int64_t n_groups, int64_t n_rows, int64_t tile_rows,
                                  uint64_t* out);
 
+/* Window functions over an ordered table (WindowAggExecNode with partition_search_mode set, datafusion.proto:1417-1427: DataFusion's
+   BoundedWindowAggExec; window expressions :1198-1209, frames :780-799).  The native plan executor's BoundedWindowAggExec node (grammar
+   and rules with the plan nodes below) runs on these four entry points over a table that is ordered by (partition_by, order_by):
+   gpuq_segment_heads gives the partitions (part_id / part_starts) and the peer groups (peer_id / peer_starts: the heads over
+   partition_by + order_by), each `starts` array one entry longer than its number of segments.  n >= 2^31 is GPUQ_ERR_UNSUPPORTED.
+   All asynchronous on `stream`; scratch comes from the context's pool and counts against gpuq_memory_limit.
+
+   gpuq_window_scan: the running SUM / COUNT / MIN / MAX (fn) of `value_col` (Arrow layout, any fixed-width numeric or temporal type)
+   inside every partition (seg_id = part_id, or NULL: one partition): a segmented inclusive scan of one accumulator cell of the
+   aggregate operator -- SUM of integers and decimals in 128 bits (cell_width 16; cell_width 8 keeps the low word: Int64 / UInt64
+   wrapping), SUM of floats in Float64 (Float32 widened), MIN / MAX of integers, temporals and decimals in 64 bits, of floats by total
+   order as a Float64 -- in three launches (tile totals, one block over them, a downsweep), in a fixed order of combination.
+   out_cells: n cells of cell_width bytes; out_count (n x int64, or NULL): the non-NULL values so far; out_validity ((n + 63) / 64 * 8
+   bytes, 8-byte aligned, or NULL): bit = count > 0, written as whole words.  status_dev (device u32, zeroed by the caller, or NULL): bit
+   0 is set when a MIN / MAX operand lies outside int64 (a Decimal128 or UInt64 beyond it: what the aggregate operator refuses too).
+   gpuq_window_rank: row_number = i - part_start + 1, rank = peer_start - part_start + 1, dense_rank = peer_id - peer_id(part_start) + 1,
+   each n x uint64 or NULL.
+   gpuq_window_shift (LAG: delta = -offset, LEAD: delta = +offset): out[i] = value[i + delta] with its validity when row i + delta lies in
+   row i's partition, else default_col[i] (a column of value_col's type; NULL: the default is NULL).  Utf8 and Boolean are refused.
+   gpuq_window_frame: the frames the scan does not give directly, and the results that are not a cell.  With P the running cells (and C
+   the counts, or NULL: the result is never NULL) the value of row i is P[hi] - P[lo - 1], P[part_start - 1] = 0, wrapping:
+     GPUQ_FRAME_ROWS     lo = part_start, hi = i                      GPUQ_FRAME_RANGE    lo = part_start, hi = peer_end(i) - 1
+     GPUQ_FRAME_SLIDING  lo = max(part_start, i - preceding) (preceding < 0: UNBOUNDED), hi = min(part_end - 1, i + following)
+   (a difference is only right for SUM / COUNT cells of integers and decimals).  out_kind: the cell in out_width bytes (truncated, an
+   8-byte cell sign-extended to 16; out_f32: the Float64 cell stored as a Float32) | AVG of a 16-byte integer sum: one conversion to
+   Float64, one division | AVG of a Float64 sum | AVG of a 16-byte decimal sum: sum * 10^avg_scale_digits / count, truncating.
+   out_validity: bit = count > 0, whole words. */
+enum { GPUQ_WINDOW_SUM = 0, GPUQ_WINDOW_COUNT = 1, GPUQ_WINDOW_MIN = 2, GPUQ_WINDOW_MAX = 3 };
+enum { GPUQ_FRAME_ROWS = 0, GPUQ_FRAME_RANGE = 1, GPUQ_FRAME_SLIDING = 2 };
+enum { GPUQ_WINDOW_OUT_CELL = 0, GPUQ_WINDOW_OUT_AVG_INT = 1, GPUQ_WINDOW_OUT_AVG_FLOAT = 2, GPUQ_WINDOW_OUT_AVG_DECIMAL = 3 };
+typedef struct gpuq_window_frame_spec {
+  const void* cells; const int64_t* counts; int32_t cell_width;
+  int32_t mode; int64_t preceding, following;
+  const int32_t *part_id, *part_starts, *peer_id, *peer_starts;
+  int32_t out_kind, out_width, out_f32, avg_scale_digits;
+  void* out; uint8_t* out_validity;
+} gpuq_window_frame_spec;
+int gpuq_window_scan(gpuq_ctx* ctx, void* stream, const gpuq_column* value_col, const int32_t* seg_id, int64_t n, int fn, void* out_cells, int cell_width, int64_t* out_count,
+                     uint8_t* out_validity, uint32_t* status_dev);
+int gpuq_window_rank(gpuq_ctx* ctx, void* stream, const int32_t* part_id, const int32_t* part_starts, const int32_t* peer_id, const int32_t* peer_starts, int64_t n,
+                     uint64_t* row_number_out, uint64_t* rank_out, uint64_t* dense_rank_out);
+int gpuq_window_shift(gpuq_ctx* ctx, void* stream, const gpuq_column* value_col, const int32_t* part_id, const int32_t* part_starts, int64_t n, int64_t delta,
+                      const gpuq_column* default_col, void* out_data, uint8_t* out_validity);
+int gpuq_window_frame(gpuq_ctx* ctx, void* stream, const gpuq_window_frame_spec* f, int64_t n);
+
 /* dst[i] = src[i] + delta for n Utf8 offsets: joining the offset arrays of partitions that are concatenated (fan-in). */
 int gpuq_offsets_rebase(gpuq_ctx* ctx, void* stream, const int32_t* src, int64_t n, int32_t delta, int32_t* dst);
 
@@ -615,6 +660,44 @@ int gpuq_copy_bits(gpuq_ctx* ctx, void* stream, uint8_t* dst, int64_t dst_bit_of
      {"HashJoinExec": {"left", "right", "on": [{"left": expr, "right": expr}], "join_type", "partition_mode",
                        "null_equals_null", "filter"?}}                               (:1346-1360)
      {"SortExec" | "SortPreservingMergeExec": {"input", "expr": [{"expr","asc","nulls_first"}], "fetch"?}}   (:1465-1478)
+     {"BoundedWindowAggExec": {"input": node,
+        "window_expr": [{"fn": name, "args": [expr], "partition_by": [expr], "order_by": [{"expr","asc","nulls_first"}],
+                         "window_frame"?: {"units": "ROWS" | "RANGE",
+                                           "start_bound": {"type": "PRECEDING" | "CURRENT_ROW" | "FOLLOWING", "value": null | int},
+                                           "end_bound":   {...}},
+                         "name": str}],
+        "partition_keys"?: [expr], "partition_search_mode": "Sorted"}}                (:1198-1209, :780-799, :1417-1427)
+         WindowAggExecNode with partition_search_mode set: the node DataFusion plans when every window expression has a bounded frame.
+         Output: the input's fields, then one per window expression; rows keep the input's order, partitions are the input's.
+         Ordering: as in DataFusion the node does not sort and does not check.  Mode Sorted promises input ordered by (partition_by,
+         order_by) -- EnforceSorting puts a SortExec below.  A partition is a maximal run of adjacent rows equal on every partition_by
+         column, a peer group a maximal run equal on partition_by + order_by; equality is gpuq_segment_heads's (validity first, NULL
+         equals NULL, then bytes).  No partition_by: one partition; no order_by: every row of a partition is a peer.
+         Functions (names without regard to case):
+           ROW_NUMBER, RANK, DENSE_RANK   no arguments; UInt64, not nullable
+           LAG, LEAD      x [, offset literal >= 0, default 1 [, default literal or NULL]]; x's type, nullable.  The value `offset` rows
+                          before / after in the same partition, NULLs included (a NULL x is a value); outside the partition the default.
+                          Every fixed-width type; Utf8 and Boolean are refused by name.
+           COUNT          x (any type); Int64, not nullable: the non-NULL x in the frame
+           SUM, MIN, MAX, AVG   x; the type the aggregate operator's function of the same name gives in mode Single, nullable: NULL while
+                          the frame holds no non-NULL x.  The accumulators are that operator's (integer SUM wraps at 64 bits, Decimal128 SUM
+                          at 128, Float32 sums in Float64, float MIN / MAX by total order; a MIN / MAX operand outside int64 is refused at
+                          run time, the function named), with one difference: AVG of an integer keeps the exact 128-bit sum and rounds
+                          twice (its conversion to Float64, the division), so that a frame can be a difference of two running sums.
+         Frames of COUNT / SUM / MIN / MAX / AVG (the other functions ignore theirs); none: RANGE UNBOUNDED PRECEDING .. CURRENT ROW:
+           ROWS  UNBOUNDED PRECEDING .. CURRENT ROW     the rows of the partition up to and including this one
+           RANGE UNBOUNDED PRECEDING .. CURRENT ROW     ... up to and including the row's last peer
+           ROWS  k PRECEDING .. CURRENT ROW | m FOLLOWING (k may be UNBOUNDED; k, m literals; clipped to the partition): SUM / COUNT / AVG
+                 over integer and Decimal128 arguments -- a difference of two running values, exact in wrapping arithmetic
+         GPUQ_ERR_UNSUPPORTED (GPUQ_REFUSAL_NONE; the message names the function and the frame, the mode or the column): an end bound of
+         UNBOUNDED FOLLOWING or PRECEDING, a start bound of FOLLOWING; RANGE with a numeric offset; GROUPS; sliding frames for MIN / MAX (a
+         running extreme cannot be taken back) and for any Float32 / Float64 argument (a difference of prefix sums cancels, and
+         DataFusion's retracting sum rounds differently again); partition_search_mode Linear / PartiallySorted; window expressions of one
+         node that differ in partition_by or order_by; Float32 / Float64 partition_by columns (bytewise heads: -0.0 and the NaNs);
+         partition_by / order_by strings beyond 15 bytes; FIRST_VALUE / LAST_VALUE / NTH_VALUE and every other function; 2^31 rows or
+         more in a partition of the plan.  A frame value that is not a whole number >= 0 or a negative offset is GPUQ_ERR_INVALID.
+         "WindowAggExec", the unbounded-frame node (PERCENT_RANK, CUME_DIST, NTILE, SUM() OVER (PARTITION BY k)), stays
+         GPUQ_REFUSAL_NODE_NOT_NATIVE.  The node runs synchronously (it needs an exact row count); see gpuq_window_scan for its kernels.
      {"CoalesceBatchesExec": {"input"}}  {"LocalLimitExec": {"input","fetch"}}       (:1487-1490, :1460-1463)
      {"GlobalLimitExec": {"input","skip","fetch"}}  {"UnionExec": {"inputs": [node]}}  {"CoalescePartitionsExec": {"input"}}   (:1453, :1319, :1492)
      {"CoalesceTasksExec": {"input","partitions": [p],"order_by"?: [sort expr]}}     (ballista coalesce_tasks.rs:46-70)
