@@ -538,6 +538,9 @@ AggCompiled compile_aggregate(const Schema& in, const Json& d) {
   for (auto& k : keys.nodes) key_slots.push_back(ec.add_output(k));
   for (size_t i = 0; i < accs.size(); ++i) if (accs[i].arg) acc_slots[i] = ec.add_output(accs[i].arg);
   R.prog = ec.finish();
+  // the key-and-predicate program: what the runs count pass needs of `prog` (a head is decided by the key and by whether the row is
+  // active; FILTER clauses and accumulator operands are outputs behind the keys and are no part of either)
+  R.heads = ec.prune(R.prog, (int)keys.nodes.size());
   if (!s.origin_of.empty()) {      // (the predicate is a node of `ec`: a program is assembled from the DAG alone, whichever compiler built it)
     if (d.has("predicate")) s.pick.add_predicate(ec.from_json(d.at("predicate")));
     R.pick = s.pick.finish();

@@ -18,6 +18,9 @@ struct AggCompiled {
   std::string mode = "Single", strategy = "auto";
   i64 expected_groups = 0;
   CompiledProgram prog;             // the scan program: outputs are the keys, then the accumulator arguments
+  // `prog` cut down to the keys and the predicate (ExprCompiler::prune): same registers, so `keys` addresses both; for every row the key
+  // registers and the predicate are bit for bit those of `prog`.  Empty (!heads.pruned()) when that removes nothing: `prog` serves then.
+  CompiledProgram heads;
   // The moment aggregates (VARIANCE .. CORRELATION) sum about origins picked at run time: run-time parameter k (param_imm of `prog`
   // and of every post program that reads it) is output k of `pick`, a program over the same input with the same predicate, taken
   // from the first row that passes and is not NULL there.  n_origins == 0: no moment aggregate, `pick` is empty.

@@ -68,6 +68,7 @@ struct gpuq_op {
   std::deque<PostChunk> posts; Schema post_schema;
   // the moment aggregates' origins (agg_compile.h): the program they are picked with and, in device memory, where they go
   CompiledProgram pick; DevBuf pick_code, origins_dev, origin_rows; int n_origins = 0;
+  CompiledProgram heads; DevBuf heads_code;      // the key-and-predicate program of the runs count pass (agg_compile.h); !heads.pruned(): `prog` serves
   i64 expected_groups = 0;
   int agg_path = 0;                 // the way this operator's last run took (Learned::ag::path numbering; 0: it has not run)
   // join
@@ -168,6 +169,15 @@ DevProgram bind_program(const CompiledProgram& cp, const Schema& schema, const D
 }
 
 DevProgram bind_input(gpuq_op* op, const gpuq_input* in) { return bind_program(op->prog, op->in_schema, op->code_dev.as<DevCode>(), op->flags_dev.as<uint32_t>(), in); }
+// The bound scan program of an aggregate -> its key-and-predicate program over the same binding: the shorter instruction list, and
+// the slots nothing reads any more emptied (class CC_NONE: the interpreter loads nothing for them and leaves their registers zero).
+// Slot and register numbers, index vectors, status word and device-side row count are those of P.
+DevProgram heads_program(const gpuq_op* op, const DevProgram& P) {
+  DevProgram H = P;
+  H.code = op->heads_code.as<DevCode>(); H.n_insns = op->heads.n_insns;
+  for (size_t c = 0; c < op->heads.col_dead.size(); ++c) if (op->heads.col_dead[c]) { H.cols[c] = DevCol{}; H.cols[c].cls = CC_NONE; }
+  return H;
+}
 void check_payload_via(int payload_via, const gpuq_input* in) { if (payload_via < 0 || payload_via > in->n_via) throw std::runtime_error("payload_via out of range"); }
 void check_row_limit(i64 n, const char* what) { if (n >= (1ll << 31)) throw Unsupported(std::string(what) + " of >= 2^31 rows in one call"); }
 // entry points that decide things on the host from the exact row count cannot take a device-side one
@@ -330,11 +340,9 @@ SelGeom selection_geometry(const gpuq_ctx* ctx, i64 n) {
 // caller has put the digit counts of the `npass` passes into pass.hist (from the ids, or from counts it has anyway).  The last pass
 // writes the row ids to `ids_out`: last_mode 1 = only those, 2 = the records as well.  Returns where the last pass left its records.
 u64* bucket_records(hipStream_t s, u64* rec, u64* rec2, i64 n, int npass, const PassBufs& pass, uint32_t* ids_out, int last_mode) {
-  for (int p = 0; p < npass; ++p) {
-    const bool last = p + 1 == npass;
-    launch_onesweep_pass(s, rec, nullptr, n, 32 + 8 * p, pass.hist.as<u64>() + (size_t)p * 256, pass.look.p, pass.look_bytes, rec2, last ? ids_out : nullptr, last ? last_mode : 0);
-    std::swap(rec, rec2);
-  }
+  launch_radix_ghist_scan(s, pass.hist.as<u64>(), npass);
+  uint32_t* none = nullptr; uint32_t* none2 = nullptr;      // packed records: no value arrays
+  launch_onesweep_passes(s, rec, none, rec2, none2, n, 32, npass, pass.hist.as<u64>(), pass.look.p, pass.look_bytes, ids_out, last_mode);
   return rec;
 }
 
@@ -400,6 +408,7 @@ static void compile_op(gpuq_op* op, const Json& d) {
       AggCompiled c = compile_aggregate(op->in_schema, d);
       op->mode = c.mode; op->strategy = c.strategy; op->expected_groups = c.expected_groups; op->refuse = c.refuse;
       op->prog = std::move(c.prog); upload_code(op->prog, op->code_dev);
+      op->heads = std::move(c.heads); if (op->heads.pruned()) upload_code(op->heads, op->heads_code);
       op->agg = c.agg; op->keys = c.keys;
       op->key_types = std::move(c.key_types); op->acc_types = std::move(c.acc_types); op->acc_bits = std::move(c.acc_bits);
       op->post_schema = std::move(c.post_schema); op->out_fields = std::move(c.out_fields);
@@ -572,6 +581,7 @@ int gpuq_compile_jit_source(const char* json, int kernel_id, char* buf, size_t c
     compile_op(op, d);
     g_upload = true;
     std::string eval = op->prog.jit_src;
+    if (kernel_id == GPUQ_SINK_AGG_RUNS_COUNT && op->kind == K_AGG && op->heads.pruned()) eval = op->heads.jit_src;      // what the run-time path compiles for that pass
     if (kernel_id == GPUQ_SINK_AGG_TINY && op->kind == K_AGG) eval += agg_tiny_spec(op, (int)d.get_i64("jit_gmax", 4));   // what the run-time path appends
     const std::string src = jit_full_source(eval, kernel_id);
     if (src.size() + 1 > cap) throw Capacity("source needs " + std::to_string(src.size() + 1) + " bytes");
@@ -832,9 +842,13 @@ static int aggregate_run_impl(gpuq_op* op, void* stream, const gpuq_input* in, g
       raw.n_groups = n_groups_dev(op);
       if (reset) reset_flags(op, s);
       if (G.nsegs <= 0) { HIPCHECK(hipMemsetAsync(raw.n_groups, 0, 8, s)); return; }
-      { SinkJit jit(op, op->prog, GPUQ_SINK_AGG_RUNS_COUNT, n); launch_agg_runs_count(s, jit.fn, P, n, Krun, G); }
-      launch_scan_block_counts(s, G.counts, G.nsegs, (u64*)raw.n_groups);      // (the count and its pad: OpStatus)
-      launch_agg_runs_order(s, G, op->flags_dev.as<uint32_t>());
+      // The count pass runs the key-and-predicate program where there is one: no load of an accumulator's operand.  INVARIANT: both
+      // passes must find the same heads -- a head is a function of the row's packed key and of `active` (the fused predicate) alone,
+      // and the pruned program yields both bit for bit as `prog` does (ExprCompiler::prune); FILTER clauses and operands are neither.
+      const bool pruned = op->heads.pruned();
+      const DevProgram Pc = pruned ? heads_program(op, P) : P;
+      { SinkJit jit(op, pruned ? op->heads : op->prog, GPUQ_SINK_AGG_RUNS_COUNT, n); launch_agg_runs_count(s, jit.fn, Pc, n, Krun, G); }
+      launch_agg_runs_scan_order(s, G, (u64*)raw.n_groups, op->flags_dev.as<uint32_t>());      // (the count and its pad: OpStatus)
     };
     auto launch_runs_write = [&](const i64 rcap) {
       raw.cap = (int32_t)rcap;
@@ -1528,17 +1542,15 @@ static void sort_with_plan(gpuq_op* op, hipStream_t s, const DevProgram& P, cons
       HIPCHECK(hipGetLastError());
       return;
     }
-    // single-read passes (kernels_sort.hip): one look-back kernel per 8 key bits, the last one writes the row ids straight into perm_out
+    // single-read passes (kernels_sort.hip): one look-back kernel per 8 key bits, the last one writes the row ids straight into perm_out.
+    // The counts of ALL passes (both words of a key beyond 64 bits) become bases in one launch.
     void* lws = W.pass.lookback(n); const size_t lwb = W.pass.look_bytes;
+    launch_radix_ghist_scan(s, ghist, np_all);
     auto run_passes = [&](int bits, int shift0, int pass0, bool last_word) {
       const int np = (bits + 7) / 8;
       if (np == 0) { if (last_word) HIPCHECK(hipMemcpyAsync(perm_out, ids, (size_t)n * 4, hipMemcpyDeviceToDevice, s)); return; }
-      for (int p = 0; p < np; ++p) {
-        const bool final_pass = last_word && p + 1 == np;
-        // (decode: the last pass keeps its records as well -- packed: records AND ids, otherwise keys and ids -- the key column is rebuilt from them)
-        launch_onesweep_pass(s, klo, ids, n, shift0 + 8 * p, ghist + (size_t)(pass0 + p) * 256, lws, lwb, klo2, final_pass ? perm_out : ids2, final_pass ? (decode ? (packed ? 2 : 0) : 1) : 0);
-        std::swap(klo, klo2); if (!final_pass) std::swap(ids, ids2);
-      }
+      // (decode: the last pass keeps its records as well -- packed: records AND ids, otherwise keys and ids -- the key column is rebuilt from them)
+      launch_onesweep_passes(s, klo, ids, klo2, ids2, n, shift0, np, ghist + (size_t)pass0 * 256, lws, lwb, last_word ? perm_out : nullptr, decode ? (packed ? 2 : 0) : 1);
     };
     if (packed) {
       run_passes(total, 32, 0, true);

@@ -822,13 +822,16 @@ CompiledProgram ExprCompiler::finish() {
   };
   std::map<Node*, int> remaining = uses;
   auto release = [&](Node* c0) { Node* c = rep(c0); if (--remaining[c] == 0) busy[reg[c]] = false; };
+  fin_insns_.clear();
   for (Node* n : order) {
     if (n->kind == Node::COL) continue;
+    const int first_insn = C.n_insns;
     if (n->kind == Node::LIT) {
       const int d = alloc(); reg[n] = d;
-      if (n->param >= 0) { const int slot = imm_new(0, 0, true); param_slot_[n] = slot; C.param_imm.push_back({n->param, slot}); emit(OP_IMM, d, 0, 0, (uint32_t)slot); continue; }
+      if (n->param >= 0) { const int slot = imm_new(0, 0, true); param_slot_[n] = slot; C.param_imm.push_back({n->param, slot}); emit(OP_IMM, d, 0, 0, (uint32_t)slot); fin_insns_[n] = {first_insn, 1}; continue; }
       if (n->lit_null) { emit(OP_IMM, d, 0, 0, (uint32_t)imm_index(0, 0)); emit(OP_NULLIF0, d, d, d, 0); }
       else emit(OP_IMM, d, 0, 0, (uint32_t)imm_index(n->lit_lo, n->lit_hi));
+      fin_insns_[n] = {first_insn, C.n_insns - first_insn};
       continue;
     }
     const int a = n->ch.size() > 0 ? reg.at(rep(n->ch[0].get())) : 0;
@@ -838,7 +841,9 @@ CompiledProgram ExprCompiler::finish() {
     for (auto& c : n->ch) release(c.get());     // operands are read before dst is written
     const int d = alloc(); reg[n] = d;
     emit(n->op, d, a, b, imm);
+    fin_insns_[n] = {first_insn, 1};
   }
+  fin_order_ = order; fin_reg_ = reg;
   for (size_t i = 0; i < imms.size(); ++i) { C.code.imm_lo[i] = imms[i].first; C.code.imm_hi[i] = imms[i].second; }
   C.pred_reg = pred_ ? reg.at(rep(pred_.get())) : -1;
   for (auto& o : outs_) {
@@ -847,6 +852,45 @@ CompiledProgram ExprCompiler::finish() {
   for (Node* n : order) if (n->kind == Node::OPN && (n->op == OP_ADDC || n->op == OP_SUBC || n->op == OP_MULC)) C.checks_overflow = true;
   C.jit_src = jit_source(C, order, reg);
   return C;
+}
+
+CompiledProgram ExprCompiler::prune(const CompiledProgram& C, int n_outs) {
+  auto rep = [](Node* n) { while (n->kind == Node::OPN && n->op == OP_MOV) n = n->ch[0].get(); return n; };
+  if (n_outs < 0 || n_outs > (int)outs_.size() || C.out_reg.size() != outs_.size()) throw std::runtime_error("prune: not the program finish() returned");
+  // live = what the predicate and the kept outputs read, directly or through other operations
+  std::set<Node*> live;
+  std::function<void(Node*)> mark = [&](Node* n0) {
+    Node* n = rep(n0);
+    if (!live.insert(n).second) return;
+    for (auto& c : n->ch) mark(c.get());
+  };
+  if (pred_) mark(pred_.get());
+  for (int k = 0; k < n_outs; ++k) mark(outs_[(size_t)k].get());
+  std::vector<Node*> order;
+  for (Node* n : fin_order_) if (live.count(n)) order.push_back(n);
+  if (order.size() == fin_order_.size()) return CompiledProgram();      // nothing to remove
+  for (Node* n : order) if (n->kind == Node::LIT && n->param >= 0) return CompiledProgram();
+  // The kept instructions in their order, untouched: a removed instruction wrote a register that held no live value at that point
+  // (finish() allocated it so), and every operand of a kept instruction is written by a kept one.
+  CompiledProgram R;
+  R.code = C.code; R.n_insns = 0;
+  for (Node* n : order) {
+    auto it = fin_insns_.find(n);
+    if (it == fin_insns_.end()) continue;      // (a column)
+    for (int i = 0; i < it->second.second; ++i) R.code.insns[R.n_insns++] = C.code.insns[it->second.first + i];
+  }
+  for (int i = R.n_insns; i < MAX_INSNS; ++i) R.code.insns[i] = DevInsn{};
+  R.col_field = C.col_field; R.col_loose = C.col_loose;
+  R.col_dead.assign(C.col_field.size(), true);
+  for (Node* n : order) if (n->kind == Node::COL) for (size_t c = 0; c < C.col_field.size(); ++c) if (C.col_field[c] == n->col) R.col_dead[c] = false;
+  R.pred_reg = C.pred_reg;
+  for (int k = 0; k < n_outs; ++k) {
+    R.out_reg.push_back(C.out_reg[(size_t)k]); R.out_type.push_back(C.out_type[(size_t)k]); R.out_nullable.push_back(C.out_nullable[(size_t)k]);
+    R.out_key.push_back(C.out_key[(size_t)k]); R.out_bits.push_back(C.out_bits[(size_t)k]);
+  }
+  for (Node* n : order) if (n->kind == Node::OPN && (n->op == OP_ADDC || n->op == OP_SUBC || n->op == OP_MULC)) R.checks_overflow = true;
+  R.jit_src = jit_source(R, order, fin_reg_);
+  return R;
 }
 
 // ------------------------------------------------------------------ JIT source
@@ -879,8 +923,10 @@ std::string ExprCompiler::jit_source(const CompiledProgram& C, const std::vector
     else if (ty != "bool") touch += "  asm volatile(\"\" :: \"v\"(w." + nm + "));\n";
   };
   // ---- rows
+  // (a pruned program keeps the slot numbers of the full one: a slot no operation of `order` reads is not loaded)
+  auto dead = [&](size_t c) { return c < C.col_dead.size() && C.col_dead[c]; };
   bool via_used[MAX_VIA + 1] = {false, false, false, false};
-  for (size_t c = 0; c < C.col_field.size(); ++c) via_used[schema_.fields[C.col_field[c]].side] = true;
+  for (size_t c = 0; c < C.col_field.size(); ++c) if (!dead(c)) via_used[schema_.fields[C.col_field[c]].side] = true;
   LP("const uint32_t row0 = (uint32_t)pos; (void)row0;");
   LL("const uint32_t row0 = (uint32_t)pos; (void)row0;");
   L("const uint32_t row0 = (uint32_t)pos; (void)row0;");
@@ -902,6 +948,7 @@ std::string ExprCompiler::jit_source(const CompiledProgram& C, const std::vector
   }
   // ---- loads
   for (size_t c = 0; c < C.col_field.size(); ++c) {
+    if (dead(c)) continue;
     const Field& f = schema_.fields[C.col_field[c]];
     const std::string cs = std::to_string(c), row = "row" + std::to_string(f.side);
     LL("const DevCol& col" + cs + " = P.cols[" + cs + "];");
@@ -955,7 +1002,7 @@ std::string ExprCompiler::jit_source(const CompiledProgram& C, const std::vector
   // ---- first byte of every string column
   for (size_t c = 0; c < C.col_field.size(); ++c) {
     const Field& f = schema_.fields[C.col_field[c]];
-    if (f.raw128 || f.type.id != T_UTF8) continue;
+    if (dead(c) || f.raw128 || f.type.id != T_UTF8) continue;
     const std::string cs = std::to_string(c);
     L("const int32_t len" + cs + " = o" + cs + "b - o" + cs + "a;");
     L("const uint8_t* sp" + cs + " = (const uint8_t*)col" + cs + ".data + o" + cs + "a;");
@@ -1161,7 +1208,7 @@ std::string ExprCompiler::jit_source(const CompiledProgram& C, const std::vector
   // ---- outputs into the registers the sink reads
   L("uint32_t nm = 0;");
   std::set<int> done;
-  for (size_t k = 0; k < outs_.size(); ++k) {
+  for (size_t k = 0; k < C.out_reg.size(); ++k) {      // (all of outs_, or the first ones a pruned program keeps)
     Node* o = rep(outs_[k].get());
     const int r = C.out_reg[k];
     if (done.count(r)) continue;

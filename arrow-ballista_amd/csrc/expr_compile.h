@@ -95,6 +95,8 @@ struct CompiledProgram {
   int n_insns = 0;
   std::vector<int> col_field;   // program column slot -> schema field index
   std::vector<bool> col_loose;  // Utf8 slot only compared for (in)equality with literals / tested for NULL: values beyond 15 bytes are fine (CC_STRQ)
+  std::vector<bool> col_dead;   // a pruned program (ExprCompiler::prune) only, one per slot: the slot keeps its number but nothing reads it -- it is not loaded
+  bool pruned() const { return !col_dead.empty(); }
   int pred_reg = -1;
   std::vector<int> out_reg;
   std::vector<DType> out_type;
@@ -138,6 +140,13 @@ class ExprCompiler {
   void add_predicate(NodeP e);                    // AND-ed with any previous predicate
   int add_output(NodeP e);                        // value must be live at program end; returns output slot
   CompiledProgram finish();
+  // After finish(): the program C it returned, cut down to what the predicate and the first n_outs outputs need -- by liveness over the
+  // operation list: an operation stays when one of those reads its result, directly or not; a column slot nothing reads any more is
+  // not loaded (col_dead).  Registers, column slots and immediates keep their numbers, so whatever addresses the kept outputs of C
+  // (a KeySpec) addresses them here, and for every row the predicate and those outputs are bit for bit what C computes.  Its own
+  // instruction list and its own generated source.  Returns an EMPTY program (pruned() is false, no source) when nothing would be
+  // removed, or when a kept operation reads a run-time parameter (its slot is written in the full program's block only).
+  CompiledProgram prune(const CompiledProgram& C, int n_outs);
   const Schema& schema() const { return schema_; }
 
  private:
@@ -146,6 +155,9 @@ class ExprCompiler {
   std::vector<NodeP> outs_;
   std::map<std::string, NodeP> interned_;
   std::map<const Node*, int> param_slot_;      // finish(): parameter node -> immediate slot, for jit_source
+  std::vector<Node*> fin_order_;               // finish(): the operation list (representatives, operands first), for prune
+  std::map<Node*, int> fin_reg_;
+  std::map<Node*, std::pair<int, int>> fin_insns_;      // node -> (first instruction, how many)
   NodeP intern(NodeP n);
   std::string jit_source(const CompiledProgram& C, const std::vector<Node*>& order, const std::map<Node*, int>& reg);
 };

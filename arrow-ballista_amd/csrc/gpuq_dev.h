@@ -48,6 +48,7 @@ enum ColClass : int32_t {
   CC_F32 = 11,  // Float32: 4 bytes in memory, the double of the same value in a register
   CC_STRQ = 6,  // Utf8 as CC_STR, for a column the program only compares for (in)equality with literals or tests for NULL: the length
                 // byte alone tells a value beyond 15 bytes from every literal a register can hold, so such a value is not an error
+  CC_NONE = 15, // a slot of a pruned program that nothing reads (ExprCompiler::prune): no load, the register stays zero and not NULL
 };
 
 struct DevCol {

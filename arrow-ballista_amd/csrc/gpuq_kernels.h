@@ -392,11 +392,11 @@ void launch_agg_bucket(hipStream_t s, void* jit_fn, const DevProgram& P, const K
 // soa: state-word keys only (K.state_key): the groups are written as result columns directly (out gives the capacity and the count word)
 void launch_agg_hash_extract(hipStream_t s, const KeySpec& K, const AggSpec& A, const HashTable& T, const AggOut& out, uint32_t* flags, const AggSoA* soa = nullptr);
 // aggregate over key-clustered input (state-word keys): the segments of `n` rows (arrays not set), then the launches in their order --
-// heads per segment; launch_scan_block_counts(counts, nsegs, the group count word) in between; the order test across segments
-// (FLAG_AGG_RUNS); one result row per run, written into columns whose accumulator cells hold their identities (cap rows)
+// heads per segment; one block that scans the counts (in place; n_groups_out: the group count word and its pad) and tests the order
+// across segments (FLAG_AGG_RUNS); one result row per run, written into columns whose accumulator cells hold their identities (cap rows)
 RunsGeom agg_runs_geometry(i64 n);
 void launch_agg_runs_count(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const RunsGeom& G);
-void launch_agg_runs_order(hipStream_t s, const RunsGeom& G, uint32_t* flags);
+void launch_agg_runs_scan_order(hipStream_t s, const RunsGeom& G, u64* n_groups_out, uint32_t* flags);
 void launch_agg_runs_write(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const AggSpec& A, const RunsGeom& G, const AggSoA& soa, uint32_t cap);
 void launch_fill_cells(hipStream_t s, ulonglong2* cells, i64 n, u64 lo, u64 hi);
 // false: no interpreter kernel for this shape (chain fusion over more than 8 input columns)
@@ -445,8 +445,10 @@ size_t merge_splits_entries(i64 max_len, int n_pairs);
 void launch_merge_pairs(hipStream_t s, const u64* klo, const u64* khi, const uint32_t* ids, const i64* pairs, int n_pairs, i64 max_len, i64* splits,
                         u64* klo_out, u64* khi_out, uint32_t* ids_out);
 void launch_radix_ghist(hipStream_t s, const u64* keys, i64 n, int shift0, int npasses, u64* ghist);
-void launch_onesweep_pass(hipStream_t s, const u64* keys, const uint32_t* vals, i64 n, int shift, u64* gexcl, void* ws, size_t ws_bytes,
-                          u64* keys_out, uint32_t* vals_out, int ids_only /* 0 records, 1 row ids only, 2 packed records + row ids */);
+void launch_radix_ghist_scan(hipStream_t s, u64* ghist, int npasses);      // counts -> bases, all passes in one launch
+// np stable 8-bit passes from bit shift0 (kernels_sort.hip); (keys, vals) <-> (keys2, vals2) change roles pass by pass
+void launch_onesweep_passes(hipStream_t s, u64*& keys, uint32_t*& vals, u64*& keys2, uint32_t*& vals2, i64 n, int shift0, int np, const u64* gexcl,
+                            void* ws, size_t ws_bytes, uint32_t* final_vals_out, int final_mode /* 0 records, 1 row ids only, 2 packed records + row ids */);
 void launch_agg_emit(hipStream_t s, const AggOut& raw, int n_keys, int n_accs, uint32_t n_groups, const AggSoA& soa, const uint32_t* n_groups_dev = nullptr);
 void launch_concat_bitmap(hipStream_t s, u64* dst, i64 dst_bit_offset, const uint8_t* src, i64 src_bit_offset, i64 n_bits);
 void launch_unpack_utf8_lengths(hipStream_t s, const ulonglong2* packed, i64 n, int32_t* lens_out, uint32_t* too_long);

@@ -446,8 +446,7 @@ __global__ void __launch_bounds__(HBLOCK) k_agg_hash_extract(const KeySpec K, co
 // a fact table clustered on the key, a scan of a key-ordered file) needs no table: every group is one run, the result is one row per
 // run in input order.  Three passes, no workgroup waits for or reads what another one of the same launch writes:
 //   k_agg_runs_count   per wave-segment (RunsGeom): the number of heads, and the order test inside the segment (FLAG_AGG_RUNS)
-//   (launch_scan_block_counts: the segments' first output rows and the group count)
-//   k_agg_runs_order   the order test across segments
+//   k_agg_runs_scan_order   one block: the segments' first output rows and the group count, and the order test across segments
 //   k_agg_runs_write   one result row per run: a run that lies inside one word is stored plainly, the pieces of a run that crosses a
 //                      word boundary fold into cells the host has set to the accumulators' identities
 // The head rule is local (a row continues the run of the ACTIVE row directly below it with an equal key), so both kernels find the
@@ -498,7 +497,7 @@ __device__ __forceinline__ void k_agg_runs_count_body(const DevProgram P, const 
   const u64 last_p1 = runs_walk<MAXC>(P, n, K, s * G.wps, G.wps, [&](const u64 key, const bool, const RunsLane& r, GPUQ_REGS_CPARAM) {
     heads += (uint32_t)__popcll(__ballot(r.head));
     bad = bad || runs_out_of_order(r.head, r.prev_p1, key);
-    // the one head of a segment with no active row before it inside the walk: k_agg_runs_order tests it against the segments before
+    // the one head of a segment with no active row before it inside the walk: k_agg_runs_scan_order tests it against the segments before
     const u64 open = __ballot(r.head && r.prev_p1 == 0);
     const u64 open_key = __shfl(key, open ? __builtin_ctzll(open) : 0);
     if (open) first_p1 = open_key + 1;
@@ -517,10 +516,47 @@ extern "C" __global__ void __launch_bounds__(HBLOCK) gpuq_jit_entry(const DevPro
 // Heads must exceed every key of the segments before them.  Inside a segment the count kernel has tested that; left is each segment's
 // open head (seg_first) against the last keys of all segments before it (seg_last: a running maximum, which is the nearest one while
 // nothing is out of order).  One block; every wave owns a contiguous sixteenth of the segments and walks it 64 at a time.
-__global__ void __launch_bounds__(1024) k_agg_runs_order(const RunsGeom G, uint32_t* __restrict__ flags) {
+// The same walk turns the segments' head counts into their first output rows (in place) and writes the group count: two scans over
+// the same nsegs items -- a sum of counts, a running maximum of seg_last -- whose loads travel together and whose steps share the
+// wave's serial chain; as two single-block launches (the plain count scan, then block_walk_scan<MaxOp>) each paid the walk's latency
+// on its own.  Layout and barriers are block_walk_scan's (gpuq_dev.h): two barriers, every thread of the block arrives; a step's loads
+// are issued one step ahead of its scans (a step stores counts[i] only, the loads ahead read index i + 64).
+__global__ void __launch_bounds__(1024) k_agg_runs_scan_order(const RunsGeom G, u64* __restrict__ n_groups_out, uint32_t* __restrict__ flags) {
+  __shared__ u64 wsum[16], wmax[16];
+  const int n = (int)G.nsegs, w = wave(), l = lane();
+  const int per = (((n + 15) / 16) + 63) & ~63;      // segments per wave, a multiple of 64
+  const int a = w * per, b = a + per < n ? a + per : n;
+  // pass 1: the wave's totals
+  u64 sum = 0, mx = 0;
+  for (int i = a + l; i < b; i += 64) { sum += (u64)G.counts[i]; mx = MaxOp()(mx, G.seg_last[i]); }
+  sum = wave_reduce<SumOp>(sum); mx = wave_reduce<MaxOp>(mx);
+  if (l == 0) { wsum[w] = sum; wmax[w] = mx; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u64 rs = 0, rm = 0;
+    for (int k = 0; k < 16; ++k) { const u64 vs = wsum[k], vm = wmax[k]; wsum[k] = rs; wmax[k] = rm; rs += vs; rm = MaxOp()(rm, vm); }
+    *n_groups_out = rs;
+  }
+  __syncthreads();
+  // pass 2: both prefixes inside the wave's range, carried from one 64-segment step to the next
+  u64 csum = wsum[w], cmax = wmax[w];
   bool bad = false;
-  block_walk_scan<MaxOp>((int)G.nsegs, (u64)0, [&](const int i) { return G.seg_last[i]; },
-                         [&](const int i, const u64 before) { const u64 f = G.seg_first[i]; bad = bad || (f != 0 && f <= before); }, (u64*)nullptr);
+  u64 c = 0, last = 0, first = 0;
+  if (a + l < b) { c = (u64)G.counts[a + l]; last = G.seg_last[a + l]; first = G.seg_first[a + l]; }
+  for (int i0 = a; i0 < b; i0 += 64) {
+    const int i = i0 + l, nx = i + 64;
+    u64 c2 = 0, last2 = 0, first2 = 0;
+    if (nx < b) { c2 = (u64)G.counts[nx]; last2 = G.seg_last[nx]; first2 = G.seg_first[nx]; }
+    const u64 xs = wave_incl_scan<SumOp>(c), xm = wave_incl_scan<MaxOp>(last);
+    u64 bs = __shfl_up(xs, 1), bm = __shfl_up(xm, 1);
+    if (l == 0) { bs = 0; bm = 0; }
+    if (i < b) {
+      G.counts[i] = (uint32_t)(csum + bs);
+      bad = bad || (first != 0 && first <= MaxOp()(cmax, bm));
+    }
+    csum += __shfl(xs, 63); cmax = MaxOp()(cmax, __shfl(xm, 63));
+    c = c2; last = last2; first = first2;
+  }
   if (bad) atomicOr(flags, FLAG_AGG_RUNS);
 }
 // the accumulator cells of one result column set to (lo, hi): an identity that is not all zero bits (BIT_AND)
@@ -1680,9 +1716,9 @@ void launch_agg_runs_count(hipStream_t s, void* jit_fn, const DevProgram& P, i64
   if (G.nsegs <= 0) return;
   launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_agg_runs_count), dim3((G.nsegs + HWAVES - 1) / HWAVES), dim3(HBLOCK), 0, s, P, n, K, G);
 }
-void launch_agg_runs_order(hipStream_t s, const RunsGeom& G, uint32_t* flags) {
+void launch_agg_runs_scan_order(hipStream_t s, const RunsGeom& G, u64* n_groups_out, uint32_t* flags) {
   if (G.nsegs <= 0) return;
-  hipLaunchKernelGGL(k_agg_runs_order, dim3(1), dim3(1024), 0, s, G, flags);
+  hipLaunchKernelGGL(k_agg_runs_scan_order, dim3(1), dim3(1024), 0, s, G, n_groups_out, flags);
 }
 void launch_agg_runs_write(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, const AggSpec& A, const RunsGeom& G, const AggSoA& soa, uint32_t cap) {
   if (G.nsegs <= 0) return;

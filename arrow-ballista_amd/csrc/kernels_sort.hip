@@ -12,6 +12,9 @@
 // over the declared Decimal128+Date32 widths.  Hash repartition is one such pass with
 // digit = partition id.  All passes stream HBM with coalesced reads; LDS holds the digit counters.
 #include "gpuq_kernels.h"
+#ifndef GPUQ_JIT
+#include <cstdlib>
+#endif
 
 namespace gpuq {
 
@@ -327,6 +330,7 @@ __global__ void __launch_bounds__(SBLOCK) k_gather_u64(const u64* __restrict__ s
 #ifndef GPUQ_JIT
 constexpr u64 LB_AGG = 1ull << 62, LB_PREFIX = 2ull << 62, LB_MASK = (1ull << 62) - 1;
 constexpr int GHIST_MAX_PASSES = 8;
+constexpr int LB_TICKET_STRIDE = 32;      // words between the two regions' tickets (a cache line of their own each)
 __global__ void __launch_bounds__(SBLOCK) k_radix_ghist(const u64* __restrict__ keys, const i64 n, const int shift0, const int npasses, u64* __restrict__ ghist) {
   __shared__ uint32_t cnt[GHIST_MAX_PASSES][RADIX];
   for (int i = threadIdx.x; i < GHIST_MAX_PASSES * RADIX; i += SBLOCK) (&cnt[0][0])[i] = 0;
@@ -349,8 +353,18 @@ __global__ void __launch_bounds__(RADIX) k_radix_ghist_scan(u64* __restrict__ gh
 // (key, value) form uses 6144 because its 12 bytes per record would leave one block per CU at 8192.
 template <bool HASVAL, int OROUNDS>
 __global__ void __launch_bounds__(SBLOCK) k_onesweep(const u64* __restrict__ keys, const uint32_t* __restrict__ vals, const i64 n, const int shift,
-                                                     const u64* __restrict__ gexcl, u64* __restrict__ look, uint32_t* __restrict__ ticket,
+                                                     const u64* __restrict__ gexcl, u64* __restrict__ looks, uint32_t* __restrict__ ticket,
                                                      u64* __restrict__ keys_out, uint32_t* __restrict__ vals_out, const int ids_only) {
+  // looks: the look-back words of TWO regions (gridDim.x x RADIX words each) and, behind them, their two tickets LB_TICKET_STRIDE words
+  // apart (launch_onesweep_passes); ticket: this pass's -- which of the two it is says which region is this pass's.  The other region
+  // is the next pass's: the pass before this one used it and is complete (stream order), nobody reads it during this launch, so every
+  // tile clears its own row there and tile 0 the ticket -- the passes of a sequence need no fill between them.
+  const size_t lwords = (size_t)gridDim.x * RADIX;
+  uint32_t* const tickets = (uint32_t*)(looks + 2 * lwords);
+  const int mine = ticket == tickets ? 0 : 1;
+  u64* const look = looks + (size_t)mine * lwords;
+  u64* const look_next = looks + (size_t)(1 - mine) * lwords;
+  uint32_t* const ticket_next = tickets + (1 - mine) * LB_TICKET_STRIDE;
   __shared__ u64 sk[(SBLOCK * OROUNDS)];
   __shared__ uint32_t sv[HASVAL ? (SBLOCK * OROUNDS) : 1];
   __shared__ uint32_t wcnt[SWAVES][RADIX];
@@ -364,6 +378,8 @@ __global__ void __launch_bounds__(SBLOCK) k_onesweep(const u64* __restrict__ key
   for (int i = t; i < SWAVES * RADIX; i += SBLOCK) (&wcnt[0][0])[i] = 0;
   __syncthreads();
   const i64 T = (i64)s_tile;
+  look_next[(size_t)T * RADIX + t] = 0;      // (T < gridDim.x: inside the region)
+  if (T == 0 && t == 0) *ticket_next = 0;
   const i64 s0 = T * (SBLOCK * OROUNDS);
   if (s0 >= n) return;                                 // (grid == number of tiles: not reached)
   const i64 b = s0 + (SBLOCK * OROUNDS) < n ? s0 + (SBLOCK * OROUNDS) : n;
@@ -566,11 +582,21 @@ void launch_sort_minmax(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n,
   launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_sort_minmax), dim3(nblocks), dim3(SBLOCK), 0, s, P, n, S, out, wstep);
 }
 int sort_max_passes() { return SORT_MAX_PASSES; }
+// rows per block below which the pack kernel's grid shrinks (measured: profiles/r17_tail.json); GPUQ_SORT_PACK_ROWS is the measurement switch
+constexpr i64 SORT_PACK_ROWS = 2048;
+static i64 sort_pack_rows() {
+  static const i64 r = []() { const char* e = getenv("GPUQ_SORT_PACK_ROWS"); const i64 v = e ? atoll(e) : 0; return v >= 64 ? v : SORT_PACK_ROWS; }();
+  return r;
+}
 void launch_sort_pack(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const SortSpec& S, const SortPack& K, u64* key_lo, u64* key_hi, uint32_t* ids, u64* hist, int hist_passes) {
   if (n <= 0) return;
-  if (hist) (void)hipMemsetAsync(hist, 0, (size_t)hist_passes * RADIX * 8, s);
-  if (hist && K.check == 1) (void)hipMemsetAsync(hist + (size_t)SORT_MAX_PASSES * RADIX, 0, 8, s);      // the "layout does not hold" word
-  launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_sort_pack), dim3(sgrid(n, 8)), dim3(SBLOCK), 0, s, P, n, S, K, key_lo, key_hi, ids, hist, hist_passes);
+  // one fill: the counters of the passes in use, or -- with the "layout does not hold" word behind all SORT_MAX_PASSES of them -- the whole block (32 KiB)
+  if (hist) (void)hipMemsetAsync(hist, 0, K.check == 1 ? ((size_t)SORT_MAX_PASSES * RADIX + 1) * 8 : (size_t)hist_passes * RADIX * 8, s);
+  // Every block ends with up to hist_passes x 256 device-scope atomics on the same counters: a block takes at least sort_pack_rows()
+  // rows, so that the flush is spread over them (the chip-filling grid of a large input is below n / rows anyway and stays as it is)
+  int grid = sgrid(n, 8);
+  if (hist) { const i64 by_rows = (n + sort_pack_rows() - 1) / sort_pack_rows(); if (by_rows < grid) grid = (int)by_rows; }
+  launch_sink(jit_fn, P.n_cols, GPUQ_PICK(k_sort_pack), dim3(grid), dim3(SBLOCK), 0, s, P, n, S, K, key_lo, key_hi, ids, hist, hist_passes);
 }
 void launch_part_pid(hipStream_t s, void* jit_fn, const DevProgram& P, i64 n, const KeySpec& K, uint32_t nparts, u64* pid_out, uint32_t* ids) {
   if (n <= 0) return;
@@ -637,9 +663,12 @@ void launch_sort_small(hipStream_t s, const u64* klo, const u64* khi, const uint
 }
 
 constexpr int OS_ROUNDS_PACKED = 32, OS_ROUNDS_KV = 24;      // 8192-record tiles for 8-byte records (6144: 3.4 ms instead of 3.15 on 2^27 rows), 6144 for (key, value) (4096: 6.55 ms instead of 5.9 over 5 passes; 8192 leaves one block per CU)
-size_t onesweep_ws_bytes(i64 n) { const i64 tiles = (n + SBLOCK * OS_ROUNDS_KV - 1) / (SBLOCK * OS_ROUNDS_KV); return (size_t)tiles * RADIX * 8 + 256; }      // look-back words + ticket (the smallest tile: an upper bound)
+// the look-back words of TWO regions of `tiles` tiles, used alternately by the passes of a sequence (launch_onesweep_passes) whatever
+// their number, and the two tickets behind them
+static size_t onesweep_used_bytes(i64 tiles) { return 2 * (size_t)tiles * RADIX * 8 + 2 * LB_TICKET_STRIDE * 4; }
+size_t onesweep_ws_bytes(i64 n) { const i64 tiles = (n + SBLOCK * OS_ROUNDS_KV - 1) / (SBLOCK * OS_ROUNDS_KV); return onesweep_used_bytes(tiles); }      // (the smallest tile: an upper bound)
 int onesweep_max_passes() { return GHIST_MAX_PASSES; }
-// ghist: npasses * 256 u64 digit counts (launch_onesweep_pass turns a pass's counts into bases)
+// ghist: npasses * 256 u64 digit counts (launch_radix_ghist_scan turns them into the passes' bases)
 void launch_radix_ghist(hipStream_t s, const u64* keys, i64 n, int shift0, int npasses, u64* ghist) {
   if (n <= 0 || npasses <= 0) return;
   (void)hipMemsetAsync(ghist, 0, (size_t)npasses * RADIX * 8, s);
@@ -681,18 +710,38 @@ void launch_sort_decode(hipStream_t s, const u64* recs, int rec_shift, i64 n, co
   hipLaunchKernelGGL(k_sort_decode, dim3((unsigned)(need < cap ? need : cap)), dim3(SBLOCK), 0, s, recs, rec_shift, n, K, desc, nulls_first, width, (uint8_t*)out, valid_out);
 }
 
-// one stable 8-bit pass; vals == NULL: packed (key << 32 | row) records; ids_only: only vals_out is written (the last pass)
-void launch_onesweep_pass(hipStream_t s, const u64* keys, const uint32_t* vals, i64 n, int shift, u64* gexcl, void* ws, size_t ws_bytes,
-                          u64* keys_out, uint32_t* vals_out, int ids_only) {
-  if (n <= 0) return;
+// digit counts -> exclusive bases for `npasses` consecutive passes of ghist, one launch (one block per pass): all the passes of a sort,
+// both words of a key beyond 64 bits included
+void launch_radix_ghist_scan(hipStream_t s, u64* ghist, int npasses) {
+  if (npasses > 0) hipLaunchKernelGGL(k_radix_ghist_scan, dim3((unsigned)npasses), dim3(RADIX), 0, s, ghist);
+}
+// `np` stable 8-bit passes over bits [shift0, shift0 + 8 np) of the keys; gexcl: the passes' bases (launch_radix_ghist_scan), 256 each.
+// vals == NULL: packed (key << 32 | row) records.  Pass p reads (keys, vals) and writes (keys2, vals2), then the pairs change roles:
+// on return (keys, vals) is what the last pass wrote.  final_vals_out (or NULL): the last pass writes its row ids there instead, in
+// final_mode (1 row ids only, 2 packed records and their row ids, 0 records and values); vals / vals2 keep their roles then.
+// The per-pass setup exists once, here: ONE fill clears both look-back regions; pass p uses region p & 1 and clears the other one for
+// pass p + 1 on the way (k_onesweep), so a sequence of any length has one fill and no state survives into the next sequence.
+void launch_onesweep_passes(hipStream_t s, u64*& keys, uint32_t*& vals, u64*& keys2, uint32_t*& vals2, i64 n, int shift0, int np, const u64* gexcl,
+                            void* ws, size_t ws_bytes, uint32_t* final_vals_out, int final_mode) {
+  if (n <= 0 || np <= 0) return;
   const int rounds = vals ? OS_ROUNDS_KV : OS_ROUNDS_PACKED;
   const i64 tile = (i64)SBLOCK * rounds;
   const i64 tiles = (n + tile - 1) / tile;
-  (void)hipMemsetAsync(ws, 0, ws_bytes, s);
-  u64* look = (u64*)ws; uint32_t* ticket = (uint32_t*)((char*)ws + (size_t)tiles * RADIX * 8);
-  hipLaunchKernelGGL(k_radix_ghist_scan, dim3(1), dim3(RADIX), 0, s, gexcl);      // this pass's counts (taken by the pack kernel) -> bases
-  if (vals) hipLaunchKernelGGL((k_onesweep<true, OS_ROUNDS_KV>), dim3((unsigned)tiles), dim3(SBLOCK), 0, s, keys, vals, n, shift, (const u64*)gexcl, look, ticket, keys_out, vals_out, ids_only);
-  else hipLaunchKernelGGL((k_onesweep<false, OS_ROUNDS_PACKED>), dim3((unsigned)tiles), dim3(SBLOCK), 0, s, keys, vals, n, shift, (const u64*)gexcl, look, ticket, keys_out, vals_out, ids_only);
+  const size_t used = onesweep_used_bytes(tiles);
+  if (used > ws_bytes) throw std::runtime_error("radix passes: look-back workspace too small");
+  (void)hipMemsetAsync(ws, 0, used, s);
+  u64* looks = (u64*)ws; uint32_t* tickets = (uint32_t*)(looks + 2 * (size_t)tiles * RADIX);
+  for (int p = 0; p < np; ++p) {
+    uint32_t* ticket = tickets + (p & 1) * LB_TICKET_STRIDE;      // (and with it the region: k_onesweep)
+    const bool final_pass = final_vals_out && p + 1 == np;
+    uint32_t* vout = final_pass ? final_vals_out : vals2;
+    const int mode = final_pass ? final_mode : 0;
+    const u64* base = gexcl + (size_t)p * RADIX;
+    const int shift = shift0 + 8 * p;
+    if (vals) hipLaunchKernelGGL((k_onesweep<true, OS_ROUNDS_KV>), dim3((unsigned)tiles), dim3(SBLOCK), 0, s, (const u64*)keys, (const uint32_t*)vals, n, shift, base, looks, ticket, keys2, vout, mode);
+    else hipLaunchKernelGGL((k_onesweep<false, OS_ROUNDS_PACKED>), dim3((unsigned)tiles), dim3(SBLOCK), 0, s, (const u64*)keys, (const uint32_t*)vals, n, shift, base, looks, ticket, keys2, vout, mode);
+    std::swap(keys, keys2); if (!final_pass) std::swap(vals, vals2);
+  }
 }
 
 // one round: n_pairs triples in `pairs` (device), the longest pair has max_len records
