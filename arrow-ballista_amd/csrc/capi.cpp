@@ -1915,6 +1915,55 @@ int gpuq_segment_approx_distinct(gpuq_ctx* ctx, void* stream, const gpuq_column*
     HIPCHECK(hipGetLastError());
   });
 }
+// ---------------------------------------------------------------- COUNT / SUM / BIT_XOR over every segment's distinct values (DISTINCT aggregates)
+int gpuq_segment_distinct(gpuq_ctx* ctx, void* stream, const gpuq_column* value_col, const int32_t* starts, int64_t n_groups, int64_t n_rows, int64_t* out_count, void* out_sum,
+                          int sum_width, void* out_xor, int xor_width, uint8_t* out_validity) {
+  return guarded(ctx, [&]() {
+    check_ctx(ctx);
+    if (!value_col || n_groups < 0 || n_rows < 0 || (n_groups > 0 && !starts)) throw std::runtime_error("gpuq_segment_distinct: bad arguments");
+    if (((uintptr_t)out_validity & 7) != 0) throw std::runtime_error("gpuq_segment_distinct: out_validity must be 8-byte aligned");
+    if (n_rows >= (1ll << 31)) throw Unsupported("gpuq_segment_distinct (DISTINCT aggregates): >= 2^31 rows in one call (segment starts are 32-bit)");
+    if (n_groups >= (1ll << 31)) throw Unsupported("gpuq_segment_distinct (DISTINCT aggregates): >= 2^31 segments in one call");
+    DType dt; dt.id = value_col->type; dt.p = value_col->precision; dt.s = value_col->scale;
+    WinCol c{value_col->data, value_col->validity, 0, SEG_SINT};
+    bool summable = true, bitwise = true;
+    switch (dt.id) {
+      case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_DECIMAL128: c.kind = SEG_SINT; break;
+      case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: c.kind = SEG_UINT; break;
+      case T_FLOAT32: c.kind = SEG_F32; bitwise = false; break;
+      case T_FLOAT64: c.kind = SEG_F64; bitwise = false; break;
+      case T_DATE32: case T_DATE64: case T_TIMESTAMP: c.kind = SEG_SINT; summable = bitwise = false; break;
+      case T_UTF8:
+        if (value_col->repr != GPUQ_REPR_PACKED15) throw Unsupported("gpuq_segment_distinct (COUNT(DISTINCT)): a Utf8 column must be in the fixed-width PACKED15 form");
+        c.kind = SEG_UINT; summable = bitwise = false; break;
+      default: throw Unsupported("COUNT(DISTINCT) over " + dt.to_string() + " is not supported (integers, dates, timestamps, Decimal128, Float32, Float64, Utf8 up to 15 bytes)");
+    }
+    c.width = dt.id == T_UTF8 ? 16 : type_width(dt);
+    if (out_sum && !summable) throw Unsupported("SUM(DISTINCT) over " + dt.to_string() + " is not supported (integers, Decimal128, Float32, Float64)");
+    if (out_xor && !bitwise) throw Unsupported("BIT_XOR(DISTINCT) over " + dt.to_string() + " is not supported (integers; Decimal128 by its low 64 bits)");
+    if (out_sum && sum_width != 8 && !(sum_width == 16 && !dt.is_float())) throw std::runtime_error("gpuq_segment_distinct: sum_width is 8, or 16 for an integer or decimal SUM");
+    if (out_xor && xor_width != 1 && xor_width != 2 && xor_width != 4 && xor_width != 8) throw std::runtime_error("gpuq_segment_distinct: xor_width is 1, 2, 4 or 8");
+    if (n_groups == 0) return;
+    if (n_rows > 0 && (!value_col->data || value_col->length < n_rows)) throw std::runtime_error("gpuq_segment_distinct: the column is shorter than n_rows");
+    hipStream_t s = use_stream(stream);
+    DevBuf ws, cnt;      // released to the pool behind the launches on this stream
+    if (!out_count && out_validity) { cnt.ensure((size_t)n_groups * 8); out_count = (int64_t*)cnt.p; }
+    // a segment without rows is met by no tile: 0 / NULL from here
+    if (out_count) HIPCHECK(hipMemsetAsync(out_count, 0, (size_t)n_groups * 8, s));
+    if (out_sum) HIPCHECK(hipMemsetAsync(out_sum, 0, (size_t)n_groups * (size_t)sum_width, s));
+    if (out_xor) HIPCHECK(hipMemsetAsync(out_xor, 0, (size_t)n_groups * (size_t)xor_width, s));
+    if (n_rows > 0) {
+      ws.ensure(window_scan_ws_bytes(n_rows));
+      // one scan per accumulator; each also counts the run heads
+      bool counted = false;
+      if (out_sum) { launch_segment_distinct(s, c, starts, n_groups, n_rows, dt.is_float() ? ACC_FSUM : ACC_SUM, ws.p, out_sum, sum_width, (i64*)out_count); counted = true; }
+      if (out_xor) { launch_segment_distinct(s, c, starts, n_groups, n_rows, ACC_BXOR, ws.p, out_xor, xor_width, counted ? nullptr : (i64*)out_count); counted = true; }
+      if (!counted && out_count) launch_segment_distinct(s, c, starts, n_groups, n_rows, ACC_COUNT, ws.p, nullptr, 8, (i64*)out_count);
+    }
+    if (out_validity) launch_segment_distinct_valid(s, (const i64*)out_count, n_groups, (u64*)out_validity);
+    HIPCHECK(hipGetLastError());
+  });
+}
 // ---------------------------------------------------------------- window functions over an ordered table (BoundedWindowAggExec)
 // the ABI's numbers are the kernels': gpuq_window_frame hands mode and out_kind over as they come
 static_assert(GPUQ_FRAME_ROWS == WFRAME_ROWS && GPUQ_FRAME_RANGE == WFRAME_RANGE && GPUQ_FRAME_SLIDING == WFRAME_SLIDING, "gpuq.h frame modes differ from WinFrameMode");

@@ -573,6 +573,12 @@ struct WinFrame {
   void* out; u64* out_valid;
 };
 void launch_window_frame(hipStream_t s, const WinFrame& F, i64 n);
+// ----- DISTINCT aggregates over a column sorted inside its segments (kernels_distinct.hip; distinct_scan_op.h has the row rule)
+// accumulator `kind` (ACC_COUNT, ACC_SUM, ACC_FSUM or ACC_BXOR) over the run heads of every segment of rows [0, n): out_cells[g] in cell_width
+// bytes (1, 2, 4, 8: the low bytes of the cell; 16: both words) and out_count[g], either may be nullptr.  ws: window_scan_ws_bytes(n).  A
+// segment without rows is met by no tile: the caller zeroes the outputs.
+void launch_segment_distinct(hipStream_t s, const WinCol& c, const int32_t* starts, i64 n_groups, i64 n, int kind, void* ws, void* out_cells, int cell_width, i64* out_count);
+void launch_segment_distinct_valid(hipStream_t s, const i64* count, i64 n_groups, u64* out_valid);      // bit g = count[g] > 0, whole 64-bit words
 // ----- one HyperLogLog estimate per segment of a column (kernels_hll.hip; hll_estimate.h has the hash and the estimator)
 enum HllKind : int32_t { HLL_SINT = 0, HLL_UINT = 1, HLL_F32 = 2, HLL_F64 = 3 };      // how a value of 8 bytes or fewer is widened to 64 bits (width 16: both words as they lie)
 struct HllCol { const void* data; const uint8_t* valid; int32_t width; int32_t kind; };

@@ -1016,17 +1016,43 @@ Json bound_aggr_exprs(const Json& aggr_expr, const ColMap* cm, const std::vector
   }
   return ae;
 }
-// ---- The segment aggregates: MEDIAN and APPROX_DISTINCT (include/gpuq.h, gpuq_segment_median and gpuq_segment_approx_distinct, have the
-// rules).  Their state is the group's values / a 16 KB sketch, so they are no accumulators of the aggregate operator: a node that holds
-// one is lowered here, in the plan, as COUNT(DISTINCT) is (build_node) -- see AggregateExec::run_segment_aggs.
-bool is_agg_fn(const Json& a, const char* name) {
-  std::string f = a.get_str("fn", "");
-  for (char& c : f) c = (char)std::toupper((unsigned char)c);
-  return f == name;
-}
+// ---- The segment aggregates: MEDIAN, APPROX_DISTINCT and COUNT / SUM / BIT_XOR(DISTINCT) (include/gpuq.h, gpuq_segment_median,
+// gpuq_segment_approx_distinct and gpuq_segment_distinct, have the rules).  Their state is the group's values / a 16 KB sketch / the
+// group's set of values, so they are no accumulators of the aggregate operator: a node that holds one is lowered here, in the plan, as
+// the all-DISTINCT node over one argument is (build_node) -- see AggregateExec::run_segment_aggs.
+std::string agg_fn_upper(const Json& a) { std::string f = a.get_str("fn", ""); for (char& c : f) c = (char)std::toupper((unsigned char)c); return f; }
+bool is_agg_fn(const Json& a, const char* name) { return agg_fn_upper(a) == name; }
 bool is_median(const Json& a) { return is_agg_fn(a, "MEDIAN"); }
 bool is_approx_distinct(const Json& a) { return is_agg_fn(a, "APPROX_DISTINCT"); }
-bool is_segment_agg(const Json& a) { return is_median(a) || is_approx_distinct(a); }
+// agg(DISTINCT x) by function: reduced over the run heads of a sort (COUNT, SUM, BIT_XOR), the plain aggregate (a set has the MIN, MAX,
+// AND and OR of its rows), or refused by name
+bool distinct_is_noop(const std::string& f) { return f == "MIN" || f == "MAX" || f == "BIT_AND" || f == "BIT_OR" || f == "BOOL_AND" || f == "BOOL_OR"; }
+bool is_distinct_agg(const Json& a) {
+  if (!a.get_bool("distinct", false)) return false;
+  const std::string f = agg_fn_upper(a);
+  return f == "COUNT" || f == "SUM" || f == "BIT_XOR";
+}
+bool is_segment_agg(const Json& a) { return is_median(a) || is_approx_distinct(a) || is_distinct_agg(a); }
+void distinct_check_arg(const std::string& fn, const DType& t) {
+  bool ok = false;
+  switch (t.id) {
+    case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: ok = true; break;
+    case T_DECIMAL128: case T_FLOAT32: case T_FLOAT64: ok = fn != "BIT_XOR"; break;
+    case T_DATE32: case T_DATE64: case T_TIMESTAMP: case T_UTF8: ok = fn == "COUNT"; break;
+    default: break;
+  }
+  if (!ok) throw Unsupported(fn + "(DISTINCT) over " + t.to_string() + " is not supported (COUNT: integers, dates, timestamps, Decimal128, Float32, Float64, Utf8 up to 15 bytes; "
+                             "SUM: integers, Decimal128, Float32, Float64; BIT_XOR: integers)");
+}
+// the result field of SUM / BIT_XOR(DISTINCT x): the operator's for the plain function over a column of x's type (mode Single)
+PField distinct_result_field(const std::string& fn, const Json& arg_type) {
+  const Json in = jobj({{"fields", jarr({jobj({{"name", jstr("x")}, {"type", arg_type}, {"nullable", jbool(true)}})})}});
+  const Json ae = jarr({jobj({{"fn", jstr(fn)}, {"expr", jcolname("x")}, {"name", jstr("r")}})});
+  PField f = compiled_outputs(jobj({{"op", jstr("aggregate")}, {"mode", jstr("Single")}, {"input", in}, {"strategy", jstr("hash")}, {"group_expr", jarr()},
+                                    {"aggr_expr", bound_aggr_exprs(ae, nullptr, std::vector<std::string>{"x"})}})).at(0);
+  f.nullable = true;
+  return f;
+}
 void approx_distinct_check_arg(const DType& t) {
   switch (t.id) {
     case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: case T_DATE32: case T_DATE64: case T_TIMESTAMP:
@@ -1040,14 +1066,14 @@ void median_check_arg(const DType& t) {
     default: throw Unsupported("MEDIAN over " + t.to_string() + " is not supported (Int8..Int64, UInt8..UInt64, Float32, Float64, Decimal128)");
   }
 }
-// (who: the function the node is lowered for -- "MEDIAN" when it holds one, else "APPROX_DISTINCT")
+// (who: the function the node is lowered for -- "MEDIAN" when it holds one, else "APPROX_DISTINCT", else the first "FN(DISTINCT)")
 void median_check_key(const DType& t, const std::string& name, const std::string& who = "MEDIAN") {
   if (t.is_float()) throw Unsupported(who + ": the " + t.to_string() + " group key '" + name + "' is refused on a node with a" + (who[0] == 'A' ? "n " : " ") + who +
                                       " (bytewise segment heads and the hash aggregate need not agree on -0.0 / NaN)");
 }
 // the argument of the segment aggregate `a` over the node's input: with FILTER (WHERE p), a row where p is not true counts as a NULL argument
 Json median_arg(const Json& a, const ColMap* cm) {
-  if (!a.has("expr")) throw std::runtime_error(std::string(is_median(a) ? "MEDIAN" : "APPROX_DISTINCT") + " needs an argument (\"expr\")");
+  if (!a.has("expr")) throw std::runtime_error((is_distinct_agg(a) ? agg_fn_upper(a) + "(DISTINCT)" : std::string(is_median(a) ? "MEDIAN" : "APPROX_DISTINCT")) + " needs an argument (\"expr\")");
   const Json e = inline_projection(a.at("expr"), cm);
   if (!a.has("filter")) return e;
   return jobj({{"case_", jobj({{"when_then_expr", jarr({jobj({{"when_expr", inline_projection(a.at("filter"), cm)}, {"then_expr", e}})})}})}});
@@ -1068,8 +1094,13 @@ struct AggregateExec : PNode {
   PNodeP input; std::string mode, strategy = "auto"; Json group_expr, aggr_expr; int64_t expected_groups = 0, output_capacity = 0;
   std::vector<PNode*> children() override { return {input.get()}; }
   bool has_median() const { for (auto& a : aggr_expr.a) if (is_median(a)) return true; return false; }
+  bool has_approx_distinct() const { for (auto& a : aggr_expr.a) if (is_approx_distinct(a)) return true; return false; }
   bool has_segment_agg() const { for (auto& a : aggr_expr.a) if (is_segment_agg(a)) return true; return false; }
-  std::string segment_fn() const { return has_median() ? "MEDIAN" : "APPROX_DISTINCT"; }      // the function the node's refusals name
+  std::string segment_fn() const {      // the function the node's refusals name
+    if (has_median()) return "MEDIAN";
+    for (auto& a : aggr_expr.a) if (is_distinct_agg(a)) return agg_fn_upper(a) + "(DISTINCT)";
+    return "APPROX_DISTINCT";
+  }
   Json plain_aggr_exprs() const { Json p = jarr(); for (auto& a : aggr_expr.a) if (!is_segment_agg(a)) p.a.push_back(a); return p; }
   // A node with segment aggregates is typed without asking the aggregate operator to compile them: keys and arguments by the projection
   // that run_segment_aggs makes of them, the other aggregates by the operator over the node without its segment aggregates.
@@ -1085,7 +1116,12 @@ struct AggregateExec : PNode {
     for (auto& a : aggr_expr.a) {
       if (!is_segment_agg(a)) continue;
       if (is_median(a)) median_check_arg(dtype_from_json(typed[si].type));
-      else { approx_distinct_check_arg(dtype_from_json(typed[si].type)); typed[si].type = jstr("UInt64"); }
+      else if (is_approx_distinct(a)) { approx_distinct_check_arg(dtype_from_json(typed[si].type)); typed[si].type = jstr("UInt64"); }
+      else {
+        const std::string fn = agg_fn_upper(a);
+        distinct_check_arg(fn, dtype_from_json(typed[si].type));
+        typed[si].type = fn == "COUNT" ? jstr("Int64") : distinct_result_field(fn, typed[si].type).type;
+      }
       ++si;
     }
     PSchema plain;
@@ -1100,18 +1136,19 @@ struct AggregateExec : PNode {
     size_t mi = nk, pi = nk;
     for (auto& a : aggr_expr.a) {
       PField f = is_segment_agg(a) ? typed[mi++] : plain.at(pi++);
-      f.nullable = !is_approx_distinct(a);      // (the declared form: see schema(); an APPROX_DISTINCT is a count, 0 over nothing)
+      f.nullable = !is_approx_distinct(a) && !(is_distinct_agg(a) && agg_fn_upper(a) == "COUNT");      // (the declared form: see schema(); an APPROX_DISTINCT / a COUNT(DISTINCT) is a count, 0 over nothing)
       out.push_back(f);
     }
     return out;
   }
-  // The lowering of a node with segment aggregates, MEDIAN and APPROX_DISTINCT (mode Single).  The input is projected to [keys, one
-  // column per distinct argument of a segment aggregate, the columns the other aggregates read] and sorted by (keys..., argument) --
-  // once per distinct MEDIAN argument; keys lead and the rows are the same, so every sort has the same segments.  A node without MEDIAN
-  // is sorted by its keys alone, and not at all when it has none: a sketch does not care for the order inside a segment.  The segments
-  // are taken from the first sort (gpuq_segment_heads); the other aggregates run on the existing operator grouped by the segment id
-  // alone, so group identity is decided once and both halves are aligned by construction; one lane per segment picks the middles
-  // (gpuq_segment_median), one pass over the first sort's argument column sketches it (gpuq_segment_approx_distinct).  The node runs
+  // The lowering of a node with segment aggregates, MEDIAN, APPROX_DISTINCT and COUNT / SUM / BIT_XOR(DISTINCT) (mode Single).  The input
+  // is projected to [keys, one column per distinct argument of a segment aggregate, the columns the other aggregates read] and sorted by
+  // (keys..., argument) -- once per distinct argument of a MEDIAN or a DISTINCT; keys lead and the rows are the same, so every sort has
+  // the same segments.  A node with sketches only is sorted by its keys alone, and not at all when it has none: a sketch does not care
+  // for the order inside a segment.  The segments are taken from the first sort (gpuq_segment_heads); the other aggregates run on the
+  // existing operator grouped by the segment id alone, so group identity is decided once and both halves are aligned by construction;
+  // one lane per segment picks the middles (gpuq_segment_median), one pass over the first sort's argument column sketches it
+  // (gpuq_segment_approx_distinct), one segmented scan reduces a sorted argument's run heads (gpuq_segment_distinct).  The node runs
   // synchronously in every execution.
   PTable run_segment_aggs(Exec& x, PTable t, const Fused& f) {
     const ColMap* cm = f.has_map ? &f.map : nullptr;
@@ -1134,32 +1171,36 @@ struct AggregateExec : PNode {
       }
       ex.push_back(e); nm.push_back(key_name(k));
     }
-    // (med / apx: a MEDIAN / an APPROX_DISTINCT reads the argument)
-    std::vector<std::string> arg_text; std::vector<int> arg_of(aggr_expr.a.size(), -1); std::vector<char> med, apx;
+    // (med / apx / dst: a MEDIAN / an APPROX_DISTINCT / a DISTINCT reads the argument; of a DISTINCT's argument, which results are asked for)
+    struct DistinctWant { bool sum = false, bxor = false; };
+    std::vector<std::string> arg_text; std::vector<int> arg_of(aggr_expr.a.size(), -1); std::vector<char> med, apx, dst, packed; std::vector<DistinctWant> want;
     for (size_t i = 0; i < aggr_expr.a.size(); ++i) {
       if (!is_segment_agg(aggr_expr.a[i])) continue;
       const Json e = median_arg(aggr_expr.a[i], cm);
       const std::string text = e.dump();
       size_t j = 0; while (j < arg_text.size() && arg_text[j] != text) ++j;
-      if (j == arg_text.size()) { arg_text.push_back(text); ex.push_back(e); nm.push_back(arg_name(j)); med.push_back(0); apx.push_back(0); }
+      if (j == arg_text.size()) { arg_text.push_back(text); ex.push_back(e); nm.push_back(arg_name(j)); med.push_back(0); apx.push_back(0); dst.push_back(0); packed.push_back(0); want.push_back({}); }
       arg_of[i] = (int)j;
+      const bool distinct = is_distinct_agg(aggr_expr.a[i]);
+      if (distinct) { dst[j] = 1; const std::string fn = agg_fn_upper(aggr_expr.a[i]); want[j].sum = want[j].sum || fn == "SUM"; want[j].bxor = want[j].bxor || fn == "BIT_XOR"; }
       if (is_median(aggr_expr.a[i])) med[j] = 1;
-      else if (!apx[j]) {      // a string argument leaves the projection as 16 packed bytes, as a string key does
-        apx[j] = 1;
+      else if (!distinct) apx[j] = 1;
+      if (!is_median(aggr_expr.a[i]) && !packed[j]) {      // a string argument leaves the projection as 16 packed bytes, as a string key does
+        packed[j] = 1;
         Names cols; collect_columns(e, cols);
         for (auto& c : cols) {
           const int ci = long_key_column(t, jcolname(c));
           if (ci < 0) continue;
           int32_t maxlen = 0;
           check(x, gpuq_utf8_max_len(x.ctx, x.stream, &t.cols[(size_t)ci].c, via_of(t, (size_t)ci), t.n, &maxlen));
-          if (maxlen > 15) throw Unsupported("APPROX_DISTINCT: the argument '" + aggr_expr.a[i].at("name").str() + "' reads strings longer than 15 bytes (" + std::to_string(maxlen) +
+          if (maxlen > 15) throw Unsupported((distinct ? agg_fn_upper(aggr_expr.a[i]) + "(DISTINCT)" : std::string("APPROX_DISTINCT")) + ": the argument '" + aggr_expr.a[i].at("name").str() + "' reads strings longer than 15 bytes (" + std::to_string(maxlen) +
                                              ") in column '" + c + "'");
         }
       }
     }
     const size_t na = arg_text.size();
-    int first_med = -1;
-    for (size_t j = 0; j < na && first_med < 0; ++j) if (med[j]) first_med = (int)j;
+    int first_med = -1;      // the first argument a sort is made for: a MEDIAN's or a DISTINCT's
+    for (size_t j = 0; j < na && first_med < 0; ++j) if (med[j] || dst[j]) first_med = (int)j;
     const Json plain = plain_aggr_exprs();
     Names plain_cols;
     for (auto& a : plain.a) for_each_agg_arg(a, [&](const char*, const Json& e) { collect_columns(inline_projection(e, cm), plain_cols); });
@@ -1172,7 +1213,9 @@ struct AggregateExec : PNode {
       if (med[j]) median_check_arg(dtype_of(proj.cols[nk + j].c));
       if (apx[j]) approx_distinct_check_arg(dtype_of(proj.cols[nk + j].c));
     }
-    // ---- 2. one sort per distinct MEDIAN argument (j < 0: by the keys alone), materialised (keep: the columns read afterwards)
+    for (size_t i = 0; i < aggr_expr.a.size(); ++i)
+      if (is_distinct_agg(aggr_expr.a[i])) distinct_check_arg(agg_fn_upper(aggr_expr.a[i]), dtype_of(proj.cols[nk + (size_t)arg_of[i]].c));
+    // ---- 2. one sort per distinct argument of a MEDIAN or a DISTINCT (j < 0: by the keys alone), materialised (keep: the columns read afterwards)
     auto sorted_by = [&](int j, const Names& keep) {
       if (n == 0 || (j < 0 && nk == 0)) return proj;
       Json se = jarr();
@@ -1233,9 +1276,9 @@ struct AggregateExec : PNode {
       pres.n = G; for (auto& c : pres.cols) c.c.length = G;
       if (nk && G > 1) pres = materialize(x, sort_table(x, pres, jarr({jobj({{"expr", jcolname("__seg")}, {"asc", jbool(true)}, {"nulls_first", jbool(false)}})}), -1, this, 18));
     }
-    // ---- 5. the segment aggregates, per function: the medians of every sort, the sketches over the first
+    // ---- 5. the segment aggregates, per function: the medians and the DISTINCT results of every sort, the sketches over the first
     PTable r; r.n = G;
-    std::vector<PCol> medians(na), sketches(na);
+    std::vector<PCol> medians(na), sketches(na), dcount(na), dsum(na), dxor(na);
     for (size_t j = 0; j < na; ++j) {
       if (med[j]) {
         const PTable sj = (int)j == first_med ? sorted0 : sorted_by((int)j, Names{arg_name(j)});
@@ -1244,6 +1287,21 @@ struct AggregateExec : PNode {
         check(x, gpuq_segment_median(x.ctx, x.stream, &ac.c, (const int32_t*)starts->p, G, data->p, (uint8_t*)valid->p));
         medians[j] = ac; medians[j].nullable = true; medians[j].c.data = data->p; medians[j].c.validity = (const uint8_t*)valid->p; medians[j].c.length = G;
         r.keep.push_back(data); r.keep.push_back(valid); r.own(sj);
+      }
+      if (dst[j]) {      // COUNT, and SUM / BIT_XOR where asked for, over the run heads of the argument's sort: one call
+        const PTable sj = (int)j == first_med ? sorted0 : sorted_by((int)j, Names{arg_name(j)});
+        const PCol& ac = sj.cols[(size_t)find_column(sj, arg_name(j))];
+        const size_t Gc = (size_t)std::max<int64_t>(G, 1);
+        BufP cnt = dev_alloc(Gc * 8 + 16), valid = dev_alloc(bitmap_bytes(G) + 8), sum, bx;
+        DType st; int sw = 8; const int xw = (int)width_of(ac.c);
+        if (want[j].sum) { st = dtype_from_json(distinct_result_field("SUM", ac.type).type); sw = type_width(st); sum = dev_alloc(Gc * (size_t)sw + 16); }
+        if (want[j].bxor) bx = dev_alloc(Gc * (size_t)xw + 16);
+        check(x, gpuq_segment_distinct(x.ctx, x.stream, &ac.c, (const int32_t*)starts->p, G, n, (int64_t*)cnt->p, sum ? sum->p : nullptr, sw, bx ? bx->p : nullptr, xw, (uint8_t*)valid->p));
+        PTable one;
+        append_column(one, arg_name(j), T_INT64, cnt->p, cnt, nullptr, G, false); dcount[j] = one.cols.back();
+        if (sum) { append_column(one, arg_name(j), st.id, sum->p, sum, valid, G, true, st.p, st.s); dsum[j] = one.cols.back(); }
+        if (bx) { append_column(one, arg_name(j), ac.c.type, bx->p, bx, valid, G, true); dxor[j] = one.cols.back(); }
+        r.own(one); r.own(sj);
       }
       if (apx[j]) {
         const PCol& ac = sorted0.cols[(size_t)find_column(sorted0, arg_name(j))];
@@ -1267,7 +1325,8 @@ struct AggregateExec : PNode {
     }
     size_t pi = nk ? 1 : 0;
     for (size_t i = 0; i < aggr_expr.a.size(); ++i) {
-      PCol c = arg_of[i] < 0 ? pres.cols.at(pi++) : is_median(aggr_expr.a[i]) ? medians[(size_t)arg_of[i]] : sketches[(size_t)arg_of[i]];
+      const Json& a = aggr_expr.a[i]; const size_t j = (size_t)std::max(arg_of[i], 0);
+      PCol c = arg_of[i] < 0 ? pres.cols.at(pi++) : is_median(a) ? medians[j] : is_approx_distinct(a) ? sketches[j] : agg_fn_upper(a) == "COUNT" ? dcount[j] : agg_fn_upper(a) == "SUM" ? dsum[j] : dxor[j];
       c.name = aggr_expr.a[i].at("name").str(); c.c.length = G;
       r.cols.push_back(c);
     }
@@ -2946,10 +3005,10 @@ PNodeP build_node(const Json& j) {
     // agg(DISTINCT x) (AggregateExprNode.distinct; benchmarks/queries/q16.sql:5 count(distinct ps_suppkey)): when every aggregate of the
     // node is DISTINCT over the same argument the node becomes two -- GROUP BY (keys, x) throws the duplicates away, GROUP BY keys
     // aggregates what is left -- which is the rewrite DataFusion's SingleDistinctToGroupBy rule makes [UPSTREAM-KNOWLEDGE]; both levels
-    // run on the existing hash aggregate.  Mixed DISTINCT / plain aggregates stay refused (gpuq_op_create says so).
+    // run on the existing hash aggregate.  Every other node with a DISTINCT entry is lowered with the segment aggregates (below).
     // MEDIAN and APPROX_DISTINCT are lowered in the plan as well (AggregateExec::run_segment_aggs), in mode Single only: the state a
     // Partial would emit is the group's values, a list column, or the group's sketch, a 16 KB binary one, which the engine has no types for
-    if (n->has_segment_agg()) {
+    if (n->has_median() || n->has_approx_distinct()) {
       if (n->mode != "Single" && n->has_median()) throw Unsupported("MEDIAN in an AggregateExec of mode " + n->mode + " is not supported (its state would be a list column): mode Single only");
       if (n->mode != "Single") throw Unsupported("APPROX_DISTINCT in an AggregateExec of mode " + n->mode + " is not supported (its state would be a 16 KB binary column per group, and "
                                                  "there is no Binary type yet): mode Single only");
@@ -2958,7 +3017,7 @@ PNodeP build_node(const Json& j) {
           throw Unsupported((is_median(a) ? "MEDIAN(DISTINCT ...)" : is_approx_distinct(a) ? "APPROX_DISTINCT(DISTINCT ...)" :
                              n->has_median() ? "a DISTINCT aggregate on a node with a MEDIAN" : "a DISTINCT aggregate on a node with an APPROX_DISTINCT") + std::string(" is not supported"));
     }
-    bool any_distinct = false, all_distinct = !n->aggr_expr.a.empty();
+    bool any_distinct = false, all_distinct = !n->aggr_expr.a.empty(), rewritten = false;
     for (auto& a : n->aggr_expr.a) { const bool d = a.get_bool("distinct", false); any_distinct = any_distinct || d; all_distinct = all_distinct && d; }
     if (any_distinct && all_distinct && n->mode == "Single") {
       const Json& arg = n->aggr_expr.a[0].at("expr");
@@ -2972,7 +3031,21 @@ PNodeP build_node(const Json& j) {
         Json outer_groups = jarr(), outer_aggs = jarr();
         for (auto& g : n->group_expr.a) outer_groups.a.push_back(jobj({{"expr", jcolname(g.at("name"))}, {"name", g.at("name")}}));
         for (auto& a : n->aggr_expr.a) outer_aggs.a.push_back(jobj({{"fn", a.at("fn")}, {"expr", jcolname("__distinct")}, {"name", a.at("name")}}));
-        n->input = std::move(inner); n->group_expr = outer_groups; n->aggr_expr = outer_aggs;
+        n->input = std::move(inner); n->group_expr = outer_groups; n->aggr_expr = outer_aggs; rewritten = true;
+      }
+    }
+    // Every other node with a DISTINCT entry -- beside plain aggregates, over several arguments, with a filter, with more keys -- is
+    // lowered with the segment aggregates (AggregateExec::run_segment_aggs; include/gpuq.h, gpuq_segment_distinct, has the rules): COUNT,
+    // SUM and BIT_XOR are reduced over the run heads of a sort by (keys..., argument); where DISTINCT changes nothing the flag is
+    // dropped and the plain aggregate runs; the rest is refused by name.  Mode Single only: a Partial's state would be a list column.
+    if (any_distinct && !rewritten) {
+      for (auto& a : n->aggr_expr.a) {
+        if (!a.get_bool("distinct", false)) continue;
+        const std::string f = agg_fn_upper(a);
+        if (n->mode != "Single") throw Unsupported(f + "(DISTINCT ...) in an AggregateExec of mode " + n->mode + " is not supported (its state would be a list column): mode Single only");
+        if (!is_distinct_agg(a) && !distinct_is_noop(f))
+          throw Unsupported(f + "(DISTINCT ...) is not supported beside other aggregates or arguments (DataFusion plans COUNT, SUM, BIT_XOR, MIN, MAX, BIT_AND, BIT_OR, BOOL_AND "
+                            "and BOOL_OR as DISTINCT); alone over one argument, without a filter and with at most three group keys, it runs");
       }
     }
     out = std::move(n);

@@ -618,7 +618,10 @@ class AggregateExec(ExecutionPlan):
     strategy: "auto" (by cardinality and input order), or one kernel family: "tiny", "lds", "hash", "radix", "runs" (include/gpuq.h).
     MEDIAN and APPROX_DISTINCT (mode Single; `"filter"` allowed) are not among the operator's functions: the native executor lowers a
     node that holds one (include/gpuq.h, gpuq_segment_median and gpuq_segment_approx_distinct; APPROX_DISTINCT is a HyperLogLog estimate,
-    UInt64 and never NULL); the Python restatement of the executor (GPUQ_PLAN_LAYER=mirror) has neither."""
+    UInt64 and never NULL); the Python restatement of the executor (GPUQ_PLAN_LAYER=mirror) has neither.
+    `"distinct": True` on an entry (mode Single; `"filter"` allowed): COUNT / SUM / BIT_XOR over the set of the group's non-NULL values,
+    beside plain aggregates and over several arguments; on MIN / MAX / BIT_AND / BIT_OR / BOOL_AND / BOOL_OR it changes nothing.  The
+    native executor lowers such a node too (include/gpuq.h, gpuq_segment_distinct, has the rules); the mirror layer gets nothing."""
 
     def __init__(self, mode, group_expr, aggr_expr, input, strategy="auto", expected_groups=0):
         super().__init__()
@@ -640,10 +643,10 @@ class AggregateExec(ExecutionPlan):
         return d
 
     def schema(self):
-        if any(str(a.get("fn", "")).upper() in ("MEDIAN", "APPROX_DISTINCT") for a in self.aggr_expr):
-            # MEDIAN and APPROX_DISTINCT are no accumulators of the operator (compile_check refuses them): the native executor lowers the
-            # node in the plan (csrc/plan_exec.cpp run_segment_aggs) and types it there, without a device -- ask it, over the input's
-            # schema as a leaf
+        if any(str(a.get("fn", "")).upper() in ("MEDIAN", "APPROX_DISTINCT") or a.get("distinct") for a in self.aggr_expr):
+            # MEDIAN, APPROX_DISTINCT and DISTINCT aggregates are no accumulators of the operator (compile_check refuses them): the native
+            # executor lowers the node in the plan (csrc/plan_exec.cpp build_node, run_segment_aggs) and types it there, without a device
+            # -- ask it, over the input's schema as a leaf
             leaf = {"MemoryExec": {"schema": [{"name": f["name"], "type": f["type"], "nullable": bool(f.get("nullable", True))} for f in self.input.schema()],
                                    "partitions": [0]}}
             return B.plan_schema({"AggregateExec": {"input": leaf, "mode": self.mode, "strategy": self.strategy,

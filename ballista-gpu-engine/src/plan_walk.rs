@@ -26,7 +26,7 @@ use datafusion::physical_plan::aggregates::{AggregateExec, AggregateMode};
 use datafusion::physical_plan::coalesce_batches::CoalesceBatchesExec;
 use datafusion::physical_plan::coalesce_partitions::CoalescePartitionsExec;
 use datafusion::physical_plan::expressions::{
-    ApproxDistinct, Avg, BinaryExpr, BitAnd, BitOr, BitXor, BoolAnd, BoolOr, CaseExpr, CastExpr, Column, Count, InListExpr, IsNotNullExpr, IsNullExpr, LikeExpr, Literal, Max, Median, Min, NegativeExpr, NotExpr,
+    ApproxDistinct, Avg, BinaryExpr, BitAnd, BitOr, BitXor, BoolAnd, BoolOr, CaseExpr, CastExpr, Column, Count, DistinctBitXor, DistinctCount, DistinctSum, InListExpr, IsNotNullExpr, IsNullExpr, LikeExpr, Literal, Max, Median, Min, NegativeExpr, NotExpr,
     PhysicalSortExpr, Sum, TryCastExpr,
 };
 use datafusion::physical_plan::filter::FilterExec;
@@ -264,6 +264,14 @@ fn aggregate_fn(a: &Arc<dyn AggregateExpr>) -> Result<&'static str> {
        else { return unsupported(format!("aggregate {}", a.name())) })
 }
 
+/// agg(DISTINCT x) as DataFusion 34 plans it beside other aggregates: an accumulator of its own that keeps the group's set of values.  The
+/// JSON carries the plain function's name plus `"distinct": true`; the native executor lowers the node (mode Single only; include/gpuq.h,
+/// gpuq_segment_distinct, has the rules) and refuses the other modes by name.
+fn distinct_aggregate_fn(a: &Arc<dyn AggregateExpr>) -> Option<&'static str> {
+    let x = a.as_any();
+    if x.is::<DistinctCount>() { Some("COUNT") } else if x.is::<DistinctSum>() { Some("SUM") } else if x.is::<DistinctBitXor>() { Some("BIT_XOR") } else { None }
+}
+
 /// One plan node.  On `NotImplemented` from anything below, the caller turns the WHOLE subtree rooted here into a host leaf.
 fn walk_node(p: &Arc<dyn ExecutionPlan>, leaves: &mut Vec<(Arc<dyn ExecutionPlan>, usize)>) -> Result<Value> {
     let a = p.as_any();
@@ -290,7 +298,10 @@ fn walk_node(p: &Arc<dyn ExecutionPlan>, leaves: &mut Vec<(Arc<dyn ExecutionPlan
         let ge: Result<Vec<Value>> = n.group_expr().expr().iter().map(|(e, name)| Ok(json!({"expr": expr(e)?, "name": name}))).collect();
         let mut ae = vec![];
         for agg in n.aggr_expr() {
-            let mut o = json!({"fn": aggregate_fn(agg)?, "name": agg.name()});
+            let mut o = match distinct_aggregate_fn(agg) {
+                Some(f) => json!({"fn": f, "name": agg.name(), "distinct": true}),
+                None => json!({"fn": aggregate_fn(agg)?, "name": agg.name()}),
+            };
             if !final_ {
                 // Final modes read the state columns of the Partial stage by position: no argument expressions
                 let args = agg.expressions();

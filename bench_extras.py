@@ -476,6 +476,117 @@ def approx_distinct(tc, T, g, log2n=28, n_grouped=10_000_000, k=100, reps=3):
     return out
 
 
+def distinct(tc, T, g, n=10_000_000, k=100, reps=3, log2big=27):
+    """DISTINCT beside plain aggregates: COUNT(DISTINCT v1), SUM(v3), COUNT(DISTINCT id6) as ONE plan over n rows of the db-benchmark
+    shape (v1 in 1..5, id6 in 1..n/k, v3 Float64), grouped by id4, id5 (k x k groups) and ungrouped, through the native plan executor,
+    inputs resident in HBM, best of `reps` after one warm-up.  Next to the step time: the plans a user needed before for the same answers
+    -- each COUNT(DISTINCT x) alone (the two-level rewrite) and the plain SUM alone, same executor, same process -- with a check that
+    the answers agree; gpuq_segment_distinct alone over the id6 column sorted by (keys..., id6) (its launches between two events) with
+    its rate on the algorithmic bytes, 2 x 4 per row: the value read by both passes; and a plain ungrouped SUM over id6, the one-read
+    floor.  10 M Int32 rows are 40 MB, where launches weigh as much as bytes: "at_size" times the same entry point (COUNT and SUM from one
+    scan) over 2^log2big sorted Int64 rows, as one segment and in segments of 1,024 rows, with its share of the 8 TB/s peak on 2 x 8
+    bytes per row."""
+    import ctypes as C
+    import numpy as np
+    import pyarrow as pa
+    import torch
+    from arrow_ballista_amd import binding as B
+    from arrow_ballista_amd.expr import col
+    r = np.random.default_rng(11)
+    cols = {"id4": r.integers(1, k + 1, n).astype(np.int32), "id5": r.integers(1, k + 1, n).astype(np.int32), "id6": r.integers(1, n // k + 1, n).astype(np.int32),
+            "v1": r.integers(1, 6, n).astype(np.int32), "v3": np.round(r.random(n) * 100, 6)}
+    x = pa.table({c: pa.array(v) for c, v in cols.items()})
+    x = x.cast(pa.schema([pa.field(f.name, f.type, nullable=False) for f in x.schema]))
+    src = g.MemoryExec([g.DeviceTable.from_arrow(x, tc.device)])
+    s = src.schema()
+
+    def timed(plan):
+        plan.execute(0); best = None
+        for _ in range(reps):
+            _sync(tc); t0 = time.perf_counter(); res = plan.execute(0); _sync(tc); dt = time.perf_counter() - t0
+            best = dt if best is None or dt < best else best
+        return best * 1e3, res.to_arrow()
+    A = lambda fn, c, name, **kw: dict({"fn": fn, "expr": col(c, s), "name": name}, **kw)
+    out = {"rows": n}
+    L, ctx, stream = B.lib(), tc.ctx.h, tc.stream_ptr()
+    for label, keys in (("by_id4_id5", ["id4", "id5"]), ("ungrouped", [])):
+        ke = [(col(c, s), c) for c in keys]
+        by = [(c, "ascending") for c in keys]
+        e = {}
+        e["step_ms"], one = timed(g.NativePlan(g.AggregateExec("Single", ke, [A("COUNT", "v1", "d1", distinct=True), A("SUM", "v3", "s3"), A("COUNT", "id6", "d6", distinct=True)], src), tc))
+        e["count_distinct_v1_alone_ms"], d1 = timed(g.NativePlan(g.AggregateExec("Single", ke, [A("COUNT", "v1", "d1", distinct=True)], src), tc))
+        e["count_distinct_id6_alone_ms"], d6 = timed(g.NativePlan(g.AggregateExec("Single", ke, [A("COUNT", "id6", "d6", distinct=True)], src), tc))
+        e["sum_v3_alone_ms"], s3 = timed(g.NativePlan(g.AggregateExec("Single", ke, [A("SUM", "v3", "s3")], src), tc))
+        e["three_plans_ms"] = e["count_distinct_v1_alone_ms"] + e["count_distinct_id6_alone_ms"] + e["sum_v3_alone_ms"]
+        e["one_plan_over_three_plans"] = e["step_ms"] / e["three_plans_ms"]
+        one, d1, d6, s3 = ((t.sort_by(by) if keys else t) for t in (one, d1, d6, s3))
+        e["groups"] = one.num_rows
+        e["counts_match"] = bool(one.column("d1").equals(d1.column("d1")) and one.column("d6").equals(d6.column("d6")) and all(one.column(c).equals(d1.column(c)) for c in keys))
+        a, b = one.column("s3").to_numpy(), s3.column("s3").to_numpy()
+        e["sum_worst_relative_difference"] = float(np.max(np.abs(a - b) / np.abs(b)))      # (two orders of a Float64 sum)
+        # the reduction alone: id6 sorted by (keys..., id6) on the host, the segments from gpuq_segment_heads
+        order = np.lexsort([cols["id6"]] + [cols[c] for c in keys[::-1]])
+        st = pa.table({c: pa.array(cols[c][order]) for c in keys + ["id6"]})
+        st = st.cast(pa.schema([pa.field(f.name, f.type, nullable=False) for f in st.schema]))
+        dev = g.DeviceTable.from_arrow(st, tc.device)
+        starts = torch.zeros(n + 2, dtype=torch.int32, device=tc.device); cnt = torch.zeros(2, dtype=torch.int64, device=tc.device)
+        G = 1
+        if keys:
+            kc = (B.gpuq_column * len(keys))(*[dev.column(c).to_c() for c in keys])
+            tc.ctx.check(L.gpuq_segment_heads(ctx, stream, kc, len(keys), n, None, starts.data_ptr(), n, cnt.data_ptr()))
+            _sync(tc); G = int(cnt[0].item())
+        else:
+            starts[1] = n
+        vc = dev.column("id6").to_c()
+        counts = torch.empty(G + 1, dtype=torch.int64, device=tc.device)
+        best = None
+        for _ in range(reps + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            tc.ctx.check(L.gpuq_segment_distinct(ctx, stream, C.byref(vc), starts.data_ptr(), G, n, counts.data_ptr(), None, 8, None, 8, None))
+            e1.record(); _sync(tc)
+            ms = e0.elapsed_time(e1)
+            best = ms if best is None or ms < best else best
+        e["kernel_ms"] = best
+        e["kernel_bytes_per_row"] = 2 * 4
+        e["kernel_GBps"] = n * e["kernel_bytes_per_row"] / best / 1e6
+        e["kernel_counts_match"] = bool(np.array_equal(counts[:G].cpu().numpy(), one.column("d6").to_numpy()))
+        out[label] = e
+        del dev, st, order
+    out["plain_sum_id6_ms"], _ = timed(g.NativePlan(g.AggregateExec("Single", [], [A("SUM", "id6", "s")], src), tc))
+    out["plain_sum_id6_GBps"] = n * 4 / out["plain_sum_id6_ms"] / 1e6
+    for label in ("by_id4_id5", "ungrouped"):
+        out[label]["kernel_over_plain_sum"] = out[label]["kernel_ms"] / out["plain_sum_id6_ms"]
+    # the reduction where bytes dominate: 2^log2big sorted Int64 values (at most 2^24 different ones), COUNT and SUM from one scan -- as one
+    # segment, and in segments of 1,024 rows (the values ascend across them, which the kernel neither knows nor uses)
+    n2 = 1 << log2big
+    big = torch.sort(torch.randint(0, 1 << 24, (n2,), dtype=torch.int64, device=tc.device))[0]
+    uniq = torch.unique_consecutive(big)
+    bc = B.gpuq_column()
+    bc.type, bc.repr, bc.data, bc.length = B.T_INT64, B.REPR_ARROW, big.data_ptr(), n2
+    torch.cuda.synchronize()
+    at = {"rows": n2, "bytes_per_row": 2 * 8}
+    for label, st in (("one_segment", torch.tensor([0, n2], dtype=torch.int32, device=tc.device)), ("segments_of_1024", torch.arange(0, n2 + 1, 1024, dtype=torch.int32, device=tc.device))):
+        G = int(st.numel()) - 1
+        counts, sums = torch.empty(G + 1, dtype=torch.int64, device=tc.device), torch.empty(G + 1, dtype=torch.int64, device=tc.device)
+        torch.cuda.synchronize()
+        best = None
+        for _ in range(reps + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            tc.ctx.check(L.gpuq_segment_distinct(ctx, stream, C.byref(bc), st.data_ptr(), G, n2, counts.data_ptr(), sums.data_ptr(), 8, None, 8, None))
+            e1.record(); _sync(tc)
+            ms = e0.elapsed_time(e1)
+            best = ms if best is None or ms < best else best
+        at[label] = {"segments": G, "kernel_ms": best, "kernel_GBps": n2 * 16 / best / 1e6, "share_of_8TBps": n2 * 16 / best / 1e6 / 8000.0}
+        if G == 1:
+            at[label]["matches_torch_unique"] = bool(int(counts[0].item()) == int(uniq.numel()) and int(sums[0].item()) == int(uniq.sum().item()))
+        else:
+            at[label]["count_total"] = int(counts[:G].sum().item())      # (a value that crosses a boundary counts on both sides: >= the one segment's)
+    out["at_size"] = at
+    return out
+
+
 def window(tc, T, g, log2n=28, log2p=20, reps=3):
     """BoundedWindowAggExec over 2^log2n Int64 rows that are already ordered by an Int32 partition key of about 2^log2p partitions (their
     sizes geometric) and an Int64 order key: one plan computes ROW_NUMBER, a running SUM (ROWS UNBOUNDED PRECEDING .. CURRENT ROW) and
@@ -974,6 +1085,10 @@ if __name__ == "__main__":
         bits = int(sys.argv[sys.argv.index("--log2n") + 1]) if "--log2n" in sys.argv else 28
         rows = int(sys.argv[sys.argv.index("--rows") + 1]) if "--rows" in sys.argv else 10_000_000
         print(json.dumps(approx_distinct(tc, T, g, bits, rows), indent=1))
+        sys.exit(0)
+    if "--distinct" in sys.argv:      # [--rows 10000000]
+        rows = int(sys.argv[sys.argv.index("--rows") + 1]) if "--rows" in sys.argv else 10_000_000
+        print(json.dumps(distinct(tc, T, g, rows)))
         sys.exit(0)
     if "--window" in sys.argv:      # [--log2n 28] [--log2p 20]
         bits = int(sys.argv[sys.argv.index("--log2n") + 1]) if "--log2n" in sys.argv else 28

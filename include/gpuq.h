@@ -582,6 +582,54 @@ int gpuq_segment_median(gpuq_ctx* ctx, void* stream, const gpuq_column* value_co
 int gpuq_segment_approx_distinct(gpuq_ctx* ctx, void* stream, const gpuq_column* value_col, const int32_t* starts, int64_t n_groups, int64_t n_rows, int64_t tile_rows,
                                  uint64_t* out);
 
+/* DISTINCT aggregates beside plain ones and over several arguments (AggregateExprNode.distinct, datafusion.proto; DataFusion 34's
+   DistinctCount / DistinctSum / DistinctBitXor keep a hash set of ScalarValues per group [UPSTREAM-KNOWLEDGE: physical-expr aggregate/
+   count_distinct.rs, sum_distinct.rs, bit_and_or_xor.rs; the crate source is not in the reference tree]).  The "aggregate" descriptor of
+   gpuq_op_create / gpuq_compile_check keeps refusing `distinct`; the native plan executor lowers the node.
+     scope      an AggregateExec of mode Single in which some entry has "distinct": true and which the two-level rewrite does not take
+                (that one: every aggregate DISTINCT over the same argument, no filter, at most three group keys -- it stays as it is).
+                Let D be the set of distinct (expr, filter) pairs among the node's DISTINCT entries: the input is projected to [keys, one
+                column per member of D, what the other aggregates read], sorted once per member by (keys..., argument), the segments come
+                from gpuq_segment_heads over the first sort, and the entry point below reduces every segment's run heads.
+     result     agg(DISTINCT x) [FILTER (WHERE p)] runs over the set of non-NULL values of x in the group; a row where p is not true
+                counts as a NULL x.
+                  COUNT      Int64, never NULL.
+                  SUM        the operator's SUM type and wrapping in mode Single: integers at 64 bits (Int64 / UInt64), Decimal128 at
+                             128 bits with the operator's result precision, floats as Float64 (Float32 widened first); NULL when the set
+                             is empty.
+                  BIT_XOR    the operator's type (the argument's, integers only); NULL when the set is empty.
+                  MIN, MAX, BIT_AND, BIT_OR, BOOL_AND, BOOL_OR: DISTINCT changes nothing; they run as the plain aggregate with its filter.
+                  AVG and the VARIANCE / STDDEV / COVARIANCE / CORRELATION family are refused by name ("AVG(DISTINCT ...)"): DataFusion 34
+                             plans none of them as DISTINCT [UPSTREAM-KNOWLEDGE: create_aggregate_expr; the crate is not in the tree].
+                             AVG(DISTINCT x) alone keeps working through the two-level rewrite.
+     argument   Int8..Int64, UInt8..UInt64: all three; Decimal128: COUNT and SUM (the operator has no BIT_XOR over decimals); Float32 /
+                Float64: COUNT and SUM; Date32 / Date64 / Timestamp and Utf8 while every value fits the packed 15 bytes (refused by name
+                beyond that): COUNT only; Boolean and anything else is refused ("COUNT(DISTINCT) over <type>").
+     equality   two values are the same when their bytes are the same: -0.0 and 0.0 are two values, NaNs differ by payload -- ScalarValue
+                equality on to_bits() in DataFusion [UPSTREAM-KNOWLEDGE], and what adjacency under the sort's totalOrder gives.
+     no rows    ungrouped: one row, COUNT 0, SUM / BIT_XOR NULL; grouped: no rows.
+   Refused (GPUQ_ERR_UNSUPPORTED, GPUQ_REFUSAL_NONE, the message names the function): modes Partial / Final / FinalPartitioned (the
+   state would be a list column, as for MEDIAN); a DISTINCT on a node that also holds a MEDIAN or an APPROX_DISTINCT; Float32 / Float64
+   group keys on a node lowered here; group keys or Utf8 arguments beyond 15 bytes; 2^31 rows or more in a partition.
+
+   gpuq_segment_distinct: over segment [starts[g], starts[g + 1]) of the first n_rows rows of `value_col` (Arrow layout as it lies, width
+   1 / 2 / 4 / 8 / 16 bytes; Utf8 as PACKED15) -- starts: n_groups + 1 ascending device int32, starts[0] = 0, starts[n_groups] = n_rows;
+   gpuq_segment_median's precondition: values ascending inside every segment, NULLs last.  Row i is a run head when it is not NULL and
+   either i = starts[g] or its bytes differ from row i - 1.  Per segment, each pointer optional (NULL: not computed):
+     out_count     int64: the number of run heads.
+     out_sum       the SUM of the run heads' values: integers and decimals in a 128-bit cell (the operator's, wrapping), stored at
+                   sum_width = 8 (the low word) or 16 bytes; floats in Float64 (sum_width 8), Float32 widened first.
+     out_xor       the XOR of the low 64 bits of the run heads' two's-complement patterns, its low xor_width = 1 / 2 / 4 / 8 bytes stored.
+                   (The entry point takes a Decimal128 column here too, by its low word; no plan reaches that: the lowering refuses
+                   BIT_XOR(DISTINCT) over decimals, as above.)
+     out_validity  bit g = count > 0, written as whole 64-bit words (8-byte aligned, padded to a multiple of 8 bytes).
+   An empty segment gives 0 / NULL; n_groups = 0 writes nothing.  One segmented scan of the window functions' shape per accumulator
+   (SUM, BIT_XOR; COUNT comes with either, or runs alone): three launches, work proportional to n_rows whatever the segments are, no
+   atomics -- the order of combination depends on (n_rows, starts) only, so a Float64 SUM is the same bits on every run.  Scratch (one scan
+   element per 2,048 rows) comes from the context's pool and counts against gpuq_memory_limit.  Asynchronous on `stream`. */
+int gpuq_segment_distinct(gpuq_ctx* ctx, void* stream, const gpuq_column* value_col, const int32_t* starts, int64_t n_groups, int64_t n_rows, int64_t* out_count, void* out_sum,
+                          int sum_width, void* out_xor, int xor_width, uint8_t* out_validity);
+
 /* Window functions over an ordered table (WindowAggExecNode with partition_search_mode set, datafusion.proto:1417-1427: DataFusion's
    BoundedWindowAggExec; window expressions :1198-1209, frames :780-799).  The native plan executor's BoundedWindowAggExec node (grammar
    and rules with the plan nodes below) runs on these four entry points over a table that is ordered by (partition_by, order_by):
@@ -657,6 +705,8 @@ int gpuq_copy_bits(gpuq_ctx* ctx, void* stream, uint8_t* dst, int64_t dst_bit_of
                         "strategy"?, "expected_groups"?, "output_capacity"?}}        (:1405-1450)
          fn: the operator's functions, and -- mode Single, this executor only -- MEDIAN ("expr", "filter"?; see gpuq_segment_median)
              and APPROX_DISTINCT ("expr", "filter"?; see gpuq_segment_approx_distinct)
+             "distinct"?: true on COUNT / SUM / BIT_XOR / MIN / MAX / BIT_AND / BIT_OR / BOOL_AND / BOOL_OR ("filter"? allowed), beside plain
+             aggregates and over several arguments -- mode Single; see gpuq_segment_distinct
      {"HashJoinExec": {"left", "right", "on": [{"left": expr, "right": expr}], "join_type", "partition_mode",
                        "null_equals_null", "filter"?}}                               (:1346-1360)
      {"SortExec" | "SortPreservingMergeExec": {"input", "expr": [{"expr","asc","nulls_first"}], "fetch"?}}   (:1465-1478)
