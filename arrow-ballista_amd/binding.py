@@ -91,6 +91,7 @@ def lib():
         "gpuq_segment_median": (i32, [vp, vp, C.POINTER(gpuq_column), vp, i64, vp, vp]),
         "gpuq_segment_approx_distinct": (i32, [vp, vp, C.POINTER(gpuq_column), vp, i64, i64, i64, vp]),
         "gpuq_segment_distinct": (i32, [vp, vp, C.POINTER(gpuq_column), vp, i64, i64, vp, vp, i32, vp, i32, vp]),
+        "gpuq_grouping_expand": (i32, [vp, vp, C.POINTER(gpuq_column), i64, i32, u64, vp, vp]),
         "gpuq_window_scan": (i32, [vp, vp, C.POINTER(gpuq_column), vp, i64, i32, vp, i32, vp, vp, vp]),
         "gpuq_window_rank": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp]),
         "gpuq_window_shift": (i32, [vp, vp, C.POINTER(gpuq_column), vp, vp, i64, i64, C.POINTER(gpuq_column), vp, vp]),

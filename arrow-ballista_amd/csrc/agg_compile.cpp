@@ -1,8 +1,8 @@
 // Aggregate descriptor -> scan program, accumulators, key layout and result projection (agg_compile.h).
 //
 // What the compile knows about an aggregate function is one row of AGG_FNS: the names it answers to, its traits, and four
-// parts -- accumulators from the arguments (Single, Partial), accumulators from the state columns (Final), the state columns
-// a Partial emits, the value a Single / Final emits.  A Partial's state columns (names, order, types) are the ones the Final of
+// parts -- accumulators from the arguments (Single, Partial), accumulators from the state columns (Final, Merge), the state columns
+// a Partial / Merge emits, the value a Single / Final emits.  A Partial's state columns (names, order, types) are the ones the Final of
 // the same function reads by position: both are written next to each other in the function's definition below, and
 // tests/test_cpu_agg_compile.py feeds every Partial's output to its Final.  A new function is a new row.
 //
@@ -247,8 +247,8 @@ struct Moments {
 // ---------------------------------------------------------------- the aggregate functions
 struct AggParts {
   void (*from_args)(Scan&, AggPlan&, NodeP x);      // Single, Partial: accumulators over the argument(s)
-  void (*from_states)(Scan&, AggPlan&, States&);    // Final, FinalPartitioned: accumulators over the Partial's state columns
-  void (*states)(Post&, const AggPlan&);            // Partial: the state columns, in the order from_states takes them
+  void (*from_states)(Scan&, AggPlan&, States&);    // Final, FinalPartitioned, Merge: accumulators over the Partial's state columns
+  void (*states)(Post&, const AggPlan&);            // Partial, Merge: the state columns, in the order from_states takes them
   void (*value)(Post&, const AggPlan&);             // Single, Final: the value
 };
 struct AggFn {
@@ -289,6 +289,7 @@ struct Avg {
   }
   static void from_states(Scan& s, AggPlan& pl, States& st) {
     NodeP c = st.take(), v = st.take();
+    pl.arg_nullable = s.may_be_null(v);      // (read by `states` alone: a Merge hands the sum on NULL where the merged count is 0, as the Partial did)
     pl.cnt = s.state_count(c);
     pl.sum = s.state_sum(v);
     pl.arg_precision = std::max(1, v->type.p - 10);      // the sum state is Decimal(min(38,p+10), s); the argument was Decimal(p, s)
@@ -488,8 +489,10 @@ const AggFn* find_agg_fn(const std::string& upper_name) {
 AggCompiled compile_aggregate(const Schema& in, const Json& d) {
   AggCompiled R;
   R.mode = d.get_str("mode", "Single");
-  const bool is_final = (R.mode == "Final" || R.mode == "FinalPartitioned");
-  const bool emit_state = (R.mode == "Partial");
+  // Merge: states in, states out -- from_states on the scan side, as a Final, `states` on the result side, as a Partial.  DataFusion has no
+  // such mode; the plan executor's lowering of grouping sets re-keys a Partial's output with it (plan_exec.cpp, GroupingExpand).
+  const bool is_final = (R.mode == "Final" || R.mode == "FinalPartitioned" || R.mode == "Merge");
+  const bool emit_state = (R.mode == "Partial" || R.mode == "Merge");
   if (!is_final && !emit_state && R.mode != "Single") throw std::runtime_error("unknown aggregate mode '" + R.mode + "'");
   R.strategy = d.get_str("strategy", "auto");
   R.expected_groups = d.get_i64("expected_groups", 0);

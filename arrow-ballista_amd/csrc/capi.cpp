@@ -1964,6 +1964,28 @@ int gpuq_segment_distinct(gpuq_ctx* ctx, void* stream, const gpuq_column* value_
     HIPCHECK(hipGetLastError());
   });
 }
+// ---------------------------------------------------------------- grouping sets: a column n_sets times over, masked keys as NULLs (AggregateExec grouping sets)
+int gpuq_grouping_expand(gpuq_ctx* ctx, void* stream, const gpuq_column* col, int64_t n, int n_sets, uint64_t null_sets, void* out_data, uint8_t* out_validity) {
+  return guarded(ctx, [&]() {
+    check_ctx(ctx);
+    if (n < 0) throw std::runtime_error("gpuq_grouping_expand: bad arguments");
+    if (n_sets < 1 || n_sets > 64) throw Unsupported("gpuq_grouping_expand (AggregateExec grouping sets): n_sets is " + std::to_string(n_sets) + " (1 to 64 sets: one bit of null_sets each)");
+    if (n >= (1ll << 31) || n * n_sets >= (1ll << 31))
+      throw Unsupported("gpuq_grouping_expand (AggregateExec grouping sets): " + std::to_string(n) + " rows times " + std::to_string(n_sets) + " sets is >= 2^31 output rows in one call");
+    if (!col) throw std::runtime_error("gpuq_grouping_expand: bad arguments");
+    DType dt; dt.id = col->type; dt.p = col->precision; dt.s = col->scale;
+    if (dt.id == T_UTF8 && col->repr != GPUQ_REPR_PACKED15) throw Unsupported("gpuq_grouping_expand (AggregateExec grouping sets): a Utf8 column must be in the fixed-width PACKED15 form");
+    if (n_sets < 64) null_sets &= (1ull << n_sets) - 1;
+    if (!out_validity && (null_sets != 0 || col->validity)) throw std::runtime_error("gpuq_grouping_expand: out_validity may be NULL only when no set is masked and the column has no validity");
+    if (((uintptr_t)out_validity & 7) != 0) throw std::runtime_error("gpuq_grouping_expand: out_validity must be 8-byte aligned");
+    const int width = dt.id == T_BOOL ? 0 : dt.id == T_UTF8 ? 16 : type_width(dt);
+    if (width == 0 && ((uintptr_t)out_data & 7) != 0) throw std::runtime_error("gpuq_grouping_expand: the data bitmap of a Boolean column must be 8-byte aligned");
+    if (n == 0) return;
+    if (!col->data || !out_data || col->length < n) throw std::runtime_error("gpuq_grouping_expand: the column is shorter than n, or a buffer is missing");
+    launch_grouping_expand(use_stream(stream), col->data, col->validity, width, n, n_sets, null_sets, out_data, (u64*)out_validity);
+    HIPCHECK(hipGetLastError());
+  });
+}
 // ---------------------------------------------------------------- window functions over an ordered table (BoundedWindowAggExec)
 // the ABI's numbers are the kernels': gpuq_window_frame hands mode and out_kind over as they come
 static_assert(GPUQ_FRAME_ROWS == WFRAME_ROWS && GPUQ_FRAME_RANGE == WFRAME_RANGE && GPUQ_FRAME_SLIDING == WFRAME_SLIDING, "gpuq.h frame modes differ from WinFrameMode");

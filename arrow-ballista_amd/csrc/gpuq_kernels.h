@@ -579,6 +579,10 @@ void launch_window_frame(hipStream_t s, const WinFrame& F, i64 n);
 // segment without rows is met by no tile: the caller zeroes the outputs.
 void launch_segment_distinct(hipStream_t s, const WinCol& c, const int32_t* starts, i64 n_groups, i64 n, int kind, void* ws, void* out_cells, int cell_width, i64* out_count);
 void launch_segment_distinct_valid(hipStream_t s, const i64* count, i64 n_groups, u64* out_valid);      // bit g = count[g] > 0, whole 64-bit words
+// ----- grouping sets: every row of a column n_sets times over, row-interleaved (kernels_grouping.hip; grouping_expand_op.h has the row rule)
+// out row i * n_sets + s = row i, NULL (and zero) when bit s of null_sets is set or the row is NULL; width 1, 2, 4, 8 or 16 bytes, or 0: a
+// Boolean column, data and out are bitmaps.  out_valid (whole 64-bit words, the last zero-padded) may be nullptr.  n * n_sets < 2^31.
+void launch_grouping_expand(hipStream_t s, const void* data, const uint8_t* valid, int width, i64 n, int n_sets, u64 null_sets, void* out, u64* out_valid);
 // ----- one HyperLogLog estimate per segment of a column (kernels_hll.hip; hll_estimate.h has the hash and the estimator)
 enum HllKind : int32_t { HLL_SINT = 0, HLL_UINT = 1, HLL_F32 = 2, HLL_F64 = 3 };      // how a value of 8 bytes or fewer is widened to 64 bits (width 16: both words as they lie)
 struct HllCol { const void* data; const uint8_t* valid; int32_t width; int32_t kind; };

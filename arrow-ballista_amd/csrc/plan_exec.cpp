@@ -1093,6 +1093,9 @@ PTable project_wide(Exec& x, const PTable& t, const std::vector<Json>& exprs, co
 struct AggregateExec : PNode {
   PNodeP input; std::string mode, strategy = "auto"; Json group_expr, aggr_expr; int64_t expected_groups = 0, output_capacity = 0;
   std::vector<PNode*> children() override { return {input.get()}; }
+  // reads its input's state columns by position, takes nothing from below into its descriptor: the Final modes, and Merge (states in, states
+  // out: the outer node of a Partial with grouping sets, build_node)
+  bool reads_states() const { return mode == "Final" || mode == "FinalPartitioned" || mode == "Merge"; }
   bool has_median() const { for (auto& a : aggr_expr.a) if (is_median(a)) return true; return false; }
   bool has_approx_distinct() const { for (auto& a : aggr_expr.a) if (is_approx_distinct(a)) return true; return false; }
   bool has_segment_agg() const { for (auto& a : aggr_expr.a) if (is_segment_agg(a)) return true; return false; }
@@ -1335,7 +1338,7 @@ struct AggregateExec : PNode {
     return r;
   }
   void require(const Names*) override {
-    if (mode == "Final" || mode == "FinalPartitioned") { input->require(nullptr); return; }      // reads its input's state columns by position
+    if (reads_states()) { input->require(nullptr); return; }      // reads its input's state columns by position
     Names n;
     for (auto& g : group_expr.a) collect_columns(g.at("expr"), n);
     for (auto& a : aggr_expr.a) for_each_agg_arg(a, [&](const char*, const Json& e) { collect_columns(e, n); });
@@ -1357,7 +1360,7 @@ struct AggregateExec : PNode {
     return out;
   }
   PTable execute(int part, Exec& x) override {
-    const bool final_ = mode == "Final" || mode == "FinalPartitioned";
+    const bool final_ = reads_states();
     Fused f; if (final_) f.src = input.get(); else f = fuse(input.get());
     PTable t = f.src->execute(part, x);
     // a join's word about its build rows (BuildRows) is taken from the join itself, directly below (through fused filters / projections)
@@ -1515,6 +1518,57 @@ struct AggregateExec : PNode {
       if (br) return with_group_columns(x, out, *br, over_build);
       return out;       // synchronous call: the input buffers are no longer referenced
     }
+  }
+};
+
+// ---- Grouping sets (AggregateExecNode.groups / null_expr: GROUP BY ROLLUP / CUBE / GROUPING SETS; include/gpuq.h, gpuq_grouping_expand, has
+// the rules).  An AggregateExec that carries sets is lowered in build_node: the input is aggregated ONCE, by all group expressions, in mode
+// Partial, and the sets are made from that much smaller state table --
+//   Single :  Final ( GroupingExpand ( Partial[all group_expr]( input ) ) )        Partial:  Merge ( GroupingExpand ( Partial[...]( input ) ) )
+// This node writes every row of the Partial's output once per set, row-interleaved, the keys a set masks as NULLs and the state columns
+// as they are; the outer node groups the tuples of all sets in one table.  What is pending is settled first: the kernel is launched over
+// the exact row count.  A Utf8 key arrives as 16 packed bytes, or -- from the rung that groups by dictionary codes -- in Arrow layout: that
+// one is packed here while every value fits 15 bytes and refused by name beyond.
+struct GroupingExpand : PNode {
+  PNodeP input; size_t nk = 0; int n_sets = 1; std::vector<uint64_t> null_sets;      // null_sets[k]: bit s = set s masks key k
+  std::vector<PNode*> children() override { return {input.get()}; }
+  void require(const Names*) override { input->require(nullptr); }      // the outer node reads the states by position
+  PSchema schema() override {
+    PSchema s = input->schema();
+    for (size_t k = 0; k < nk && k < s.size(); ++k) s[k].nullable = s[k].nullable || null_sets[k] != 0;
+    return s;
+  }
+  PTable execute(int part, Exec& x) override {
+    PTable t = input->execute(part, x);
+    auto t0 = std::chrono::steady_clock::now();
+    t.by_build = nullptr;
+    settle(x, &t);
+    t = materialize(x, t);
+    const int64_t n = t.n, total = n * n_sets;
+    if (total >= (1ll << 31)) throw Unsupported("grouping sets: " + std::to_string(n) + " groups of the finest grain times " + std::to_string(n_sets) + " sets is >= 2^31 rows in one partition");
+    PTable out; out.n = total;
+    for (size_t i = 0; i < t.cols.size(); ++i) {
+      PCol c = t.cols[i];
+      const uint64_t masks = i < nk ? null_sets[i] : 0;
+      if (c.c.type == T_UTF8 && c.c.repr == GPUQ_REPR_ARROW) {
+        int32_t maxlen = 0;
+        check(x, gpuq_utf8_max_len(x.ctx, x.stream, &c.c, nullptr, n, &maxlen));
+        if (maxlen > 15) throw LongString("grouping sets: group key '" + c.name + "' holds strings longer than 15 bytes (" + std::to_string(maxlen) + ")");
+        PTable one; one.n = n; one.cols.push_back(c); one.sides.push_back(0);
+        const PTable packed = project(x, one, {jcolname(c.name)}, {c.name}, this, 1);
+        c = packed.cols.at(0); c.c.length = n; out.own(packed);
+      }
+      const size_t w = c.c.type == T_UTF8 ? 16 : width_of(c.c);
+      const bool nullable = masks != 0 || c.c.validity != nullptr;
+      BufP data = dev_alloc(c.c.type == T_BOOL ? bitmap_bytes(total) : (size_t)std::max<int64_t>(total, 1) * w + 16), valid = nullable ? dev_alloc(bitmap_bytes(total)) : nullptr;
+      check(x, gpuq_grouping_expand(x.ctx, x.stream, &c.c, n, n_sets, masks, data->p, valid ? (uint8_t*)valid->p : nullptr));
+      c.nullable = c.nullable || masks != 0;
+      c.c.data = data->p; c.c.validity = valid ? (const uint8_t*)valid->p : nullptr; c.c.offsets = nullptr; c.c.length = total;
+      out.cols.push_back(c); out.sides.push_back(0);
+      out.keep.push_back(data); if (valid) out.keep.push_back(valid);
+    }
+    out.own(t);      // (the kernels read the Partial's output asynchronously)
+    return timed(x, t0, out);
   }
 };
 
@@ -3002,6 +3056,43 @@ PNodeP build_node(const Json& j) {
     auto n = std::make_unique<AggregateExec>(); n->input = build_child(v, "input"); n->mode = v.get_str("mode", "Single"); n->strategy = v.get_str("strategy", "auto");
     n->group_expr = v.has("group_expr") ? v.at("group_expr") : jarr(); n->aggr_expr = v.at("aggr_expr");
     n->expected_groups = v.get_i64("expected_groups", 0); n->output_capacity = v.get_i64("output_capacity", 0);
+    // Grouping sets (groups: S sets of one bool per group expression, true = the key is NULL in that set; null_expr: the typed NULLs, checked
+    // for their number only).  One all-false set is the plain GROUP BY DataFusion writes for every node: today's path.  Anything else is
+    // lowered to  Final | Merge ( GroupingExpand ( Partial ) )  -- see GroupingExpand.
+    std::unique_ptr<GroupingExpand> expand;
+    if (v.has("groups")) {
+      const Json& gs = v.at("groups"); const size_t nk = n->group_expr.a.size();
+      if (!gs.is_arr() || gs.a.empty()) throw std::runtime_error("AggregateExec: \"groups\" must be a non-empty list of grouping sets");
+      if (nk == 0) throw std::runtime_error("AggregateExec: \"groups\" (grouping sets) on a node without group expressions");
+      bool plain = gs.a.size() == 1;
+      for (auto& g : gs.a) {
+        if (!g.is_arr() || g.a.size() != nk) throw std::runtime_error("AggregateExec: a grouping set of \"groups\" has " + std::to_string(g.is_arr() ? g.a.size() : 0) + " entries for " + std::to_string(nk) + " group expressions");
+        for (auto& b : g.a) { if (b.kind != Json::BOOL) throw std::runtime_error("AggregateExec: the entries of a grouping set are booleans"); plain = plain && !b.b; }
+      }
+      if (v.has("null_expr") && (!v.at("null_expr").is_arr() || v.at("null_expr").a.size() != nk))
+        throw std::runtime_error("AggregateExec: \"null_expr\" has " + std::to_string(v.at("null_expr").is_arr() ? v.at("null_expr").a.size() : 0) + " entries for " + std::to_string(nk) + " group expressions");
+      if (!plain) {
+        if (n->mode != "Single" && n->mode != "Partial") throw std::runtime_error("AggregateExec: grouping sets (\"groups\") on mode " + n->mode + ": only Partial and Single carry sets, a Final's group-by is plain");
+        if (gs.a.size() > 64) throw Unsupported("AggregateExec: " + std::to_string(gs.a.size()) + " grouping sets are not supported (64 at most)");
+        for (auto& a : n->aggr_expr.a)
+          if (is_median(a) || is_approx_distinct(a) || a.get_bool("distinct", false))
+            throw Unsupported("AggregateExec: grouping sets beside " + (a.get_bool("distinct", false) ? agg_fn_upper(a) + "(DISTINCT ...)" : agg_fn_upper(a)) +
+                              " are not supported (its state is no column a Partial could emit and the sets be made from)");
+        expand = std::make_unique<GroupingExpand>();
+        expand->nk = nk; expand->n_sets = (int)gs.a.size(); expand->null_sets.assign(nk, 0);
+        for (size_t si = 0; si < gs.a.size(); ++si) for (size_t k = 0; k < nk; ++k) if (gs.a[si].a[k].b) expand->null_sets[k] |= 1ull << si;
+      }
+    }
+    if (expand) {
+      auto inner = std::make_unique<AggregateExec>(); inner->kind = kind; inner->input = std::move(n->input); inner->mode = "Partial"; inner->strategy = n->strategy;
+      inner->group_expr = n->group_expr; inner->aggr_expr = n->aggr_expr; inner->expected_groups = n->expected_groups; inner->output_capacity = n->output_capacity;
+      expand->kind = "GroupingExpand"; expand->input = std::move(inner);
+      Json outer_groups = jarr(), outer_aggs = jarr();
+      for (auto& g : n->group_expr.a) outer_groups.a.push_back(jobj({{"expr", jcolname(g.at("name"))}, {"name", g.at("name")}}));
+      for (auto& a : n->aggr_expr.a) outer_aggs.a.push_back(jobj({{"fn", a.at("fn")}, {"name", a.at("name")}}));      // (states by position: no arguments)
+      n->input = std::move(expand); n->mode = n->mode == "Single" ? "Final" : "Merge"; n->strategy = "auto";
+      n->group_expr = outer_groups; n->aggr_expr = outer_aggs; n->expected_groups = 0; n->output_capacity = 0;
+    }
     // agg(DISTINCT x) (AggregateExprNode.distinct; benchmarks/queries/q16.sql:5 count(distinct ps_suppkey)): when every aggregate of the
     // node is DISTINCT over the same argument the node becomes two -- GROUP BY (keys, x) throws the duplicates away, GROUP BY keys
     // aggregates what is left -- which is the rewrite DataFusion's SingleDistinctToGroupBy rule makes [UPSTREAM-KNOWLEDGE]; both levels

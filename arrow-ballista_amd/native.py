@@ -65,6 +65,7 @@ def plan_to_json(node, tc, inputs):
             d["expected_groups"] = int(node.expected_groups)
         if getattr(node, "output_capacity", None):
             d["output_capacity"] = int(node.output_capacity)
+        d.update(node._sets_json())      # "groups" / "null_expr": grouping sets
         return {"AggregateExec": d}
     if isinstance(node, P.HashJoinExec):
         d = {"left": sub(node.left), "right": sub(node.right), "on": [{"left": l, "right": r} for l, r in node.on], "join_type": node.join_type,

@@ -621,12 +621,25 @@ class AggregateExec(ExecutionPlan):
     UInt64 and never NULL); the Python restatement of the executor (GPUQ_PLAN_LAYER=mirror) has neither.
     `"distinct": True` on an entry (mode Single; `"filter"` allowed): COUNT / SUM / BIT_XOR over the set of the group's non-NULL values,
     beside plain aggregates and over several arguments; on MIN / MAX / BIT_AND / BIT_OR / BOOL_AND / BOOL_OR it changes nothing.  The
-    native executor lowers such a node too (include/gpuq.h, gpuq_segment_distinct, has the rules); the mirror layer gets nothing."""
+    native executor lowers such a node too (include/gpuq.h, gpuq_segment_distinct, has the rules); the mirror layer gets nothing.
+    grouping_sets: GROUP BY ROLLUP / CUBE / GROUPING SETS (AggregateExecNode.groups) -- S sets of one bool per group expression, True = the
+    key is NULL in that set (rollup_sets / cube_sets write the two common shapes).  Modes Single and Partial.  Every row counts once per
+    set and all tuples share one table: as in DataFusion 34, which has no grouping id, a really-NULL key lands in the group of the set
+    that masks it, and two equal sets count every row twice (include/gpuq.h, gpuq_grouping_expand, has the rules).  The native executor
+    lowers the node; the mirror layer refuses it."""
 
-    def __init__(self, mode, group_expr, aggr_expr, input, strategy="auto", expected_groups=0):
+    def __init__(self, mode, group_expr, aggr_expr, input, strategy="auto", expected_groups=0, grouping_sets=None):
         super().__init__()
         self.mode, self.group_expr, self.aggr_expr, self.input = mode, list(group_expr), list(aggr_expr), input
         self.strategy, self.expected_groups = strategy, expected_groups
+        self.grouping_sets = None if grouping_sets is None else [[bool(b) for b in g] for g in grouping_sets]
+
+    def _sets_json(self):
+        """The two keys grouping sets add to the node's JSON: the sets, and one typed NULL per group expression (checked for their number
+        only: the executor writes a NULL of the key's type)."""
+        if self.grouping_sets is None:
+            return {}
+        return {"groups": self.grouping_sets, "null_expr": [{"literal": {"type": "Null", "value": None}} for _ in self.group_expr]}
 
     def children(self):
         return [self.input]
@@ -643,7 +656,7 @@ class AggregateExec(ExecutionPlan):
         return d
 
     def schema(self):
-        if any(str(a.get("fn", "")).upper() in ("MEDIAN", "APPROX_DISTINCT") or a.get("distinct") for a in self.aggr_expr):
+        if self.grouping_sets is not None or any(str(a.get("fn", "")).upper() in ("MEDIAN", "APPROX_DISTINCT") or a.get("distinct") for a in self.aggr_expr):
             # MEDIAN, APPROX_DISTINCT and DISTINCT aggregates are no accumulators of the operator (compile_check refuses them): the native
             # executor lowers the node in the plan (csrc/plan_exec.cpp build_node, run_segment_aggs) and types it there, without a device
             # -- ask it, over the input's schema as a leaf
@@ -651,11 +664,13 @@ class AggregateExec(ExecutionPlan):
                                    "partitions": [0]}}
             return B.plan_schema({"AggregateExec": {"input": leaf, "mode": self.mode, "strategy": self.strategy,
                                                     "group_expr": [{"expr": e, "name": n} for e, n in self.group_expr],
-                                                    "aggr_expr": [{k: v for k, v in a.items() if v is not None} for a in self.aggr_expr]}})
+                                                    "aggr_expr": [{k: v for k, v in a.items() if v is not None} for a in self.aggr_expr], **self._sets_json()}})
         d = B.compile_check(self._descriptor(self.input.schema(), None, None))
         return [_field_from_desc(o) for o in d["outputs"]]
 
     def execute(self, partition, context):
+        if self.grouping_sets is not None:
+            raise B.GpuqError(3, "AggregateExec with grouping sets is lowered by the native plan executor only (GPUQ_PLAN_LAYER=mirror has no expansion)")
         final = self.mode in ("Final", "FinalPartitioned")
         fused_for = getattr(self, "_fused_for", None)
         if fused_for is not self.input:
@@ -670,6 +685,16 @@ class AggregateExec(ExecutionPlan):
             op = self._memo[mk] = context.op(self._descriptor(table.schema(), pred, m))
         out = aggregate_table(context, table, op.descriptor, cap=getattr(self, "output_capacity", None), op=op)
         return self._timed(t0, out)
+
+
+def rollup_sets(nk):
+    """ROLLUP(k0 .. k[nk-1]) as grouping sets: (k0..k[nk-1]), (k0..k[nk-2]), ..., (k0), () -- nk + 1 sets, True = the key is NULL."""
+    return [[k >= keep for k in range(nk)] for keep in range(nk, -1, -1)]
+
+
+def cube_sets(nk):
+    """CUBE(k0 .. k[nk-1]): every subset of the keys, 2^nk sets, the full set first and () last; True = the key is NULL."""
+    return [[bool((m >> (nk - 1 - k)) & 1) for k in range(nk)] for m in range(1 << nk)]
 
 
 def aggregate_table(tc, table, descriptor, cap=None, op=None):

@@ -287,9 +287,6 @@ fn walk_node(p: &Arc<dyn ExecutionPlan>, leaves: &mut Vec<(Arc<dyn ExecutionPlan
         return Ok(json!({"ProjectionExec": {"input": walk(n.input(), leaves)?, "expr": e?, "expr_name": names}}));
     }
     if let Some(n) = a.downcast_ref::<AggregateExec>() {
-        if n.group_expr().null_expr().iter().any(|_| true) && n.group_expr().groups().len() > 1 {
-            return unsupported("grouping sets");
-        }
         let mode = match n.mode() {
             AggregateMode::Partial => "Partial", AggregateMode::Final => "Final", AggregateMode::FinalPartitioned => "FinalPartitioned",
             AggregateMode::Single => "Single", AggregateMode::SinglePartitioned => "Single",
@@ -311,7 +308,17 @@ fn walk_node(p: &Arc<dyn ExecutionPlan>, leaves: &mut Vec<(Arc<dyn ExecutionPlan
             ae.push(o);
         }
         if n.filter_expr().iter().any(|f| f.is_some()) { return unsupported("aggregate FILTER clause"); }
-        return Ok(json!({"AggregateExec": {"input": walk(n.input(), leaves)?, "mode": mode, "group_expr": ge?, "aggr_expr": ae}}));
+        let mut node = json!({"input": walk(n.input(), leaves)?, "mode": mode, "group_expr": ge?, "aggr_expr": ae});
+        // Grouping sets (ROLLUP / CUBE / GROUPING SETS): `groups` is one Vec<bool> per set, true = the key is NULL in that set, and null_expr
+        // the typed NULLs.  The one all-false set of a plain GROUP BY is left out; an ungrouped node has no group expressions and no sets.
+        // The executor lowers the node (include/gpuq.h, gpuq_grouping_expand) and refuses what it does not run, loudly.
+        let groups = n.group_expr().groups();
+        if !n.group_expr().expr().is_empty() && !(groups.len() == 1 && groups[0].iter().all(|masked| !*masked)) {
+            let ne: Result<Vec<Value>> = n.group_expr().null_expr().iter().map(|(e, _)| expr(e)).collect();
+            node["groups"] = json!(groups);
+            node["null_expr"] = json!(ne?);
+        }
+        return Ok(json!({"AggregateExec": node}));
     }
     if let Some(n) = a.downcast_ref::<HashJoinExec>() {
         let on: Vec<Value> = n.on().iter().map(|(l, r)| json!({"left": {"column": {"name": l.name(), "index": l.index()}},

@@ -587,6 +587,90 @@ def distinct(tc, T, g, n=10_000_000, k=100, reps=3, log2big=27):
     return out
 
 
+def grouping_sets(tc, T, g, n=10_000_000, k=100, reps=3):
+    """Grouping sets: SUM(v1), COUNT(*), AVG(v3) by ROLLUP(id4, id5) and by CUBE(id1, id4, id5), each as ONE plan over n rows of the
+    db-benchmark shape (id1, id4, id5 in 1..k, v1 in 1..5, v3 Float64), through the native plan executor, inputs resident in HBM, best of
+    `reps` after one warm-up.  Next to the step time: what a user had to run before for the same rows -- the S plain AggregateExec plans,
+    one per set, same executor, same process -- with a check that the answers agree (COUNT and SUM exactly, AVG to a relative
+    difference: two orders of a Float64 sum); and gpuq_grouping_expand alone over the columns of the plan's state table (its launches
+    between two events) with its rate on the algorithmic bytes: n w read, S n w plus the validity bits written, per column."""
+    import ctypes as C
+    import numpy as np
+    import pyarrow as pa
+    import torch
+    from arrow_ballista_amd import binding as B
+    from arrow_ballista_amd.expr import col, lit
+    r = np.random.default_rng(18)
+    cols = {"id1": r.integers(1, k + 1, n).astype(np.int32), "id4": r.integers(1, k + 1, n).astype(np.int32), "id5": r.integers(1, k + 1, n).astype(np.int32),
+            "v1": r.integers(1, 6, n).astype(np.int32), "v3": np.round(r.random(n) * 100, 6)}
+    x = pa.table({c: pa.array(v) for c, v in cols.items()})
+    x = x.cast(pa.schema([pa.field(f.name, f.type, nullable=False) for f in x.schema]))
+    src = g.MemoryExec([g.DeviceTable.from_arrow(x, tc.device)])
+    s = src.schema()
+    aggs = [{"fn": "SUM", "expr": col("v1", s), "name": "s1"}, {"fn": "COUNT", "expr": lit(1), "name": "n"}, {"fn": "AVG", "expr": col("v3", s), "name": "a3"}]
+
+    def timed(plan):
+        plan.execute(0); best = None
+        for _ in range(reps):
+            _sync(tc); t0 = time.perf_counter(); res = plan.execute(0); _sync(tc); dt = time.perf_counter() - t0
+            best = dt if best is None or dt < best else best
+        return best * 1e3, res.to_arrow()
+    L, ctx, stream = B.lib(), tc.ctx.h, tc.stream_ptr()
+    out = {"rows": n}
+    for label, keys, sets in (("rollup_id4_id5", ["id4", "id5"], g.plan.rollup_sets(2)), ("cube_id1_id4_id5", ["id1", "id4", "id5"], g.plan.cube_sets(3))):
+        ke = [(col(c, s), c) for c in keys]
+        e = {"sets": len(sets)}
+        e["one_plan_ms"], one = timed(g.NativePlan(g.AggregateExec("Single", ke, aggs, src, grouping_sets=sets), tc))
+        e["output_rows"] = one.num_rows
+        total, agree, worst, per_set = 0.0, True, 0.0, []
+        nulls = np.stack([np.asarray(one.column(c).is_null()) for c in keys], axis=1)
+        for mask in sets:
+            kept = [c for c, m in zip(keys, mask) if not m]
+            ms, ref = timed(g.NativePlan(g.AggregateExec("Single", [(col(c, s), c) for c in kept], aggs, src), tc))
+            total += ms; per_set.append(ms)
+            mine = one.filter(pa.array(np.all(nulls == np.array(mask), axis=1)))      # (no NULL keys in this table: a set's rows are those NULL exactly where it masks)
+            by = [(c, "ascending") for c in kept]
+            mine, ref = (mine.sort_by(by), ref.sort_by(by)) if kept else (mine, ref)
+            agree = agree and mine.num_rows == ref.num_rows and all(mine.column(c).equals(ref.column(c)) for c in kept + ["s1", "n"])
+            if mine.num_rows == ref.num_rows:
+                a, b = mine.column("a3").to_numpy(), ref.column("a3").to_numpy()
+                worst = max(worst, float(np.max(np.abs(a - b) / np.abs(b))))
+        e["plans_per_set_ms"] = per_set
+        e["s_plans_ms"] = total
+        e["one_plan_over_s_plans"] = e["one_plan_ms"] / total
+        e["answers_agree"] = bool(agree)
+        e["avg_worst_relative_difference"] = worst
+        # the expansion alone, over columns of the state table's widths: the keys, SUM's Int64 state, COUNT's, AVG's count and Float64 sum
+        fine = int(np.sum(~nulls.any(axis=1)))
+        widths = [(B.T_INT32, 4, True)] * len(keys) + [(B.T_INT64, 8, False), (B.T_INT64, 8, False), (B.T_UINT64, 8, False), (B.T_FLOAT64, 8, False)]
+        S = len(sets)
+        bufs = []
+        for ki, (tid, w, is_key) in enumerate(widths):
+            c = B.gpuq_column()
+            data = torch.zeros(fine * w + 16, dtype=torch.uint8, device=tc.device)
+            c.type, c.repr, c.data, c.length = tid, B.REPR_ARROW, data.data_ptr(), fine
+            null_sets = sum(1 << si for si, mask in enumerate(sets) if mask[ki]) if is_key else 0
+            bufs.append((c, data, null_sets, torch.empty(fine * S * w + 16, dtype=torch.uint8, device=tc.device),
+                         torch.empty(((fine * S + 63) // 64 + 1) * 8, dtype=torch.uint8, device=tc.device) if null_sets else None))
+        best = None
+        for _ in range(reps + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for c, _, null_sets, o, v in bufs:
+                tc.ctx.check(L.gpuq_grouping_expand(ctx, stream, C.byref(c), fine, S, null_sets, o.data_ptr(), v.data_ptr() if v is not None else None))
+            e1.record(); _sync(tc)
+            ms = e0.elapsed_time(e1)
+            best = ms if best is None or ms < best else best
+        nbytes = sum(fine * w + S * fine * w + ((S * fine + 7) // 8 if null_sets else 0) for (_, w, _), (_, _, null_sets, _, _) in zip(widths, bufs))
+        e["finest_groups"] = fine
+        e["expand_kernel_ms"] = best
+        e["expand_algorithmic_bytes"] = int(nbytes)
+        e["expand_GBps"] = nbytes / best / 1e6
+        out[label] = e
+        del bufs
+    return out
+
+
 def window(tc, T, g, log2n=28, log2p=20, reps=3):
     """BoundedWindowAggExec over 2^log2n Int64 rows that are already ordered by an Int32 partition key of about 2^log2p partitions (their
     sizes geometric) and an Int64 order key: one plan computes ROW_NUMBER, a running SUM (ROWS UNBOUNDED PRECEDING .. CURRENT ROW) and
@@ -1089,6 +1173,10 @@ if __name__ == "__main__":
     if "--distinct" in sys.argv:      # [--rows 10000000]
         rows = int(sys.argv[sys.argv.index("--rows") + 1]) if "--rows" in sys.argv else 10_000_000
         print(json.dumps(distinct(tc, T, g, rows)))
+        sys.exit(0)
+    if "--grouping-sets" in sys.argv:      # [--rows 10000000]
+        rows = int(sys.argv[sys.argv.index("--rows") + 1]) if "--rows" in sys.argv else 10_000_000
+        print(json.dumps(grouping_sets(tc, T, g, rows)))
         sys.exit(0)
     if "--window" in sys.argv:      # [--log2n 28] [--log2p 20]
         bits = int(sys.argv[sys.argv.index("--log2n") + 1]) if "--log2n" in sys.argv else 28

@@ -287,8 +287,11 @@ const char* gpuq_scan_last_error(void);
    executor).  "op" is one of
      "filter"      FilterExec        {input, predicate}
      "project"     ProjectionExec    {input, exprs:[{expr,name}]}
-     "aggregate"   AggregateExec     {input, mode:Partial|Final|FinalPartitioned|Single, group_expr:[{expr,name}],
+     "aggregate"   AggregateExec     {input, mode:Partial|Final|FinalPartitioned|Single|Merge, group_expr:[{expr,name}],
                                       aggr_expr:[{fn, expr, expr2?, name, filter?}], predicate?, strategy?:auto|tiny|hash|lds|radix|runs, expected_groups?}
+                   mode Merge (no DataFusion mode: it exists for the plan executor's lowering of grouping sets, below) reads state columns
+                   as a Final does, by position, and emits them as a Partial does: its output fields have the names and types of the
+                   Partial over the same functions, one row per key tuple.
                    fn (any letter case; one row of AGG_FNS in csrc/agg_compile.cpp each) and the state columns "<name>[..]" its Partial emits
                    and its Final reads, by position, after the group columns:
                      COUNT (expr optional: COUNT(*))                   [count]
@@ -630,6 +633,39 @@ int gpuq_segment_approx_distinct(gpuq_ctx* ctx, void* stream, const gpuq_column*
 int gpuq_segment_distinct(gpuq_ctx* ctx, void* stream, const gpuq_column* value_col, const int32_t* starts, int64_t n_groups, int64_t n_rows, int64_t* out_count, void* out_sum,
                           int sum_width, void* out_xor, int xor_width, uint8_t* out_validity);
 
+/* Grouping sets: GROUP BY ROLLUP / CUBE / GROUPING SETS (AggregateExecNode.groups and .null_expr, datafusion.proto:1437-1450; the rules
+   are DataFusion 34's [UPSTREAM-KNOWLEDGE: physical-plan aggregates/mod.rs PhysicalGroupBy, evaluate_group_by; the crate is not in the
+   reference tree]).  The "aggregate" descriptor knows no sets; the native plan executor lowers an AggregateExec that carries them.
+     meaning    "groups" is S grouping sets, one bool per group expression: true = the key is NULL in that set (a NULL of the key's type;
+                null_expr is checked for its length and not evaluated).  Every input row that passes the fused predicate is counted once
+                per set, with NULL wherever the set masks a key, and all tuples of all sets go into ONE table.  This version has no
+                grouping id, so -- as in DataFusion 34 --
+                  * a row whose key is really NULL lands in the same group as the set that masks that key, and
+                  * two equal sets count every row twice.
+                An empty set () gives the grand-total row; no input rows give no output rows (the node is grouped).  Output key field k
+                is nullable when its expression is, or when any set masks it.  The GROUPING() function has no physical plan there, or here.
+     lowering   the input is aggregated once, at the finest grain, and the sets are made from the state table:
+                  Single :  Final ( Expand ( Partial[all group_expr]( input ) ) )
+                  Partial:  Merge ( Expand ( Partial[all group_expr]( input ) ) )
+                The inner Partial keeps the node's group_expr, aggr_expr (with filter), strategy, expected_groups, output_capacity and its
+                fusion with the filters / projections below; Expand is the entry point below over every column (state columns unmasked);
+                the outer node groups by the key columns by name and reads states by position.  A Partial with sets therefore emits one row
+                per key tuple of each set, not the finest set's rows S times.  The expansion settles a deferred execution first.
+     accepted   no "groups", or one all-false set: the plain node, untouched.  Modes Partial and Single (a Final's group-by is plain).
+   Refused: GPUQ_ERR_INVALID -- a set of the wrong length, "groups" with no group expressions, an empty "groups" list, null_expr of the
+   wrong length, sets on Final / FinalPartitioned; GPUQ_ERR_UNSUPPORTED -- more than 64 sets, sets beside MEDIAN, APPROX_DISTINCT or any
+   `distinct` aggregate, and (GPUQ_REFUSAL_LONG_STRING) "grouping sets: group key '<name>' holds strings longer than 15 bytes".
+
+   gpuq_grouping_expand: rows [0, n) of `col`, n_sets times over, row-interleaved: output row i * n_sets + s is input row i, and it is
+   NULL when bit s of null_sets is set (or row i is NULL; col->validity == NULL: every row is valid).  No output position depends on n.
+   Types of width 1 / 2 / 4 / 8 / 16 bytes (Utf8 as PACKED15: 16) and Boolean, whose data is a bitmap: out_data holds n * n_sets values,
+   or that many bits in whole 64-bit words.  A NULL row's data is zero.  out_validity: whole 64-bit words (8-byte aligned), the last one
+   zero-padded; it may be NULL only when null_sets == 0 and the input has no validity.  State columns pass null_sets = 0.  One lane per
+   output row, no scratch, no atomics; asynchronous on `stream`.  Refused (GPUQ_ERR_UNSUPPORTED, GPUQ_REFUSAL_NONE, "gpuq_grouping_expand
+   (AggregateExec grouping sets): ..."): n_sets outside 1..64; n * n_sets >= 2^31 (checked before any pointer is looked at); a Utf8
+   column in Arrow layout. */
+int gpuq_grouping_expand(gpuq_ctx* ctx, void* stream, const gpuq_column* col, int64_t n, int n_sets, uint64_t null_sets, void* out_data, uint8_t* out_validity);
+
 /* Window functions over an ordered table (WindowAggExecNode with partition_search_mode set, datafusion.proto:1417-1427: DataFusion's
    BoundedWindowAggExec; window expressions :1198-1209, frames :780-799).  The native plan executor's BoundedWindowAggExec node (grammar
    and rules with the plan nodes below) runs on these four entry points over a table that is ordered by (partition_by, order_by):
@@ -702,7 +738,9 @@ int gpuq_copy_bits(gpuq_ctx* ctx, void* stream, uint8_t* dst, int64_t dst_bit_of
      {"FilterExec": {"input": node, "expr": expr}}                                   (:1291-1294)
      {"ProjectionExec": {"input": node, "expr": [expr], "expr_name": [str]}}         (:1399-1403)
      {"AggregateExec": {"input", "mode", "group_expr": [{"expr","name"}], "aggr_expr": [{"fn","expr","expr2"?,"name"}],
-                        "strategy"?, "expected_groups"?, "output_capacity"?}}        (:1405-1450)
+                        "strategy"?, "expected_groups"?, "output_capacity"?,
+                        "groups"?: [[bool x len(group_expr)] x S], "null_expr"?: [expr]}}    (:1405-1450)
+         groups / null_expr: grouping sets (ROLLUP / CUBE / GROUPING SETS), modes Single and Partial; see gpuq_grouping_expand
          fn: the operator's functions, and -- mode Single, this executor only -- MEDIAN ("expr", "filter"?; see gpuq_segment_median)
              and APPROX_DISTINCT ("expr", "filter"?; see gpuq_segment_approx_distinct)
              "distinct"?: true on COUNT / SUM / BIT_XOR / MIN / MAX / BIT_AND / BIT_OR / BOOL_AND / BOOL_OR ("filter"? allowed), beside plain
