@@ -5,6 +5,7 @@
 #include "expr_compile.h"
 #include "agg_compile.h"
 #include "gpuq_kernels.h"
+#include "sort_key_op.h"
 #include "jit_runtime.h"
 #include "devbuf.h"
 #include "gpuq_internal.h"
@@ -1366,7 +1367,6 @@ int gpuq_join_build_side_rows(gpuq_join_table* t, void* stream, int matched, uin
 }
 
 // ---------------------------------------------------------------- sort
-static int bitlen128(u128 v) { int b = 0; while (v) { ++b; v >>= 1; } return b; }
 
 // Per-key min/max in the ordered view (one pass + read-back) -> the bit layout of the composite key (SortExec and the ordered merge).
 // wstep > 1: the min/max of a strided SAMPLE (every wstep-th 64-row word), widened into a GUESS of the layout that the pack kernel
@@ -1387,60 +1387,8 @@ static SortPack sort_key_plan(gpuq_op* op, hipStream_t s, const DevProgram& P, i
     HIPCHECK(hipMemcpyAsync(&eflags, op->flags_dev.p, 4, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
     raise_unless(op, s, eflags);
-    const i128 I128_MAX = ((i128)0x7FFFFFFFFFFFFFFFll << 64) | (i128)0xFFFFFFFFFFFFFFFFull, I128_MIN = -I128_MAX - 1;
-    i128 mn[MAX_SORT_KEYS], mx[MAX_SORT_KEYS]; u64 fl[MAX_SORT_KEYS] = {0, 0, 0, 0}; int rshift[MAX_SORT_KEYS] = {0, 0, 0, 0};
-    for (int k = 0; k < S.n_keys; ++k) {
-      mn[k] = I128_MAX; mx[k] = I128_MIN;
-      for (int b = 0; b < mb; ++b) {
-        const u64* o = &hmm[((size_t)b * MAX_SORT_KEYS + k) * 5];
-        if (!(o[4] & 1)) { fl[k] |= (o[4] & 0xFF); continue; }
-        const i128 a = (i128)(((u128)o[1] << 64) | o[0]), c = (i128)(((u128)o[3] << 64) | o[2]);
-        if (a < mn[k]) mn[k] = a;
-        if (c > mx[k]) mx[k] = c;
-        fl[k] = ((fl[k] | o[4]) & 0xFF) | std::max<u64>(fl[k] & 0xFF00, o[4] & 0xFF00);
-      }
-      if (S.kind[k] == 2) { const int maxlen = std::min<int>((int)((fl[k] >> 8) & 0xFF), 15); rshift[k] = 8 * (15 - maxlen) + 8; }
-      if (fl[k] & 1) { mn[k] >>= rshift[k]; mx[k] >>= rshift[k]; }
-    }
-    // layout for the ranges [mn - range >> mshift, mx + range >> mshift] (mshift < 0: the ranges as they are)
-    auto layout = [&](int mshift, bool spread, SortPack& K) {
-      int width[MAX_SORT_KEYS] = {0, 0, 0, 0}; int total = 0;
-      K = SortPack{};
-      for (int k = 0; k < S.n_keys; ++k) {
-        int vb = 0; K.rshift[k] = rshift[k];
-        if (fl[k] & 1) {
-          i128 lo = mn[k], hi = mx[k];
-          if (mshift >= 0) {
-            const u128 m = (((u128)(hi - lo)) >> mshift) + 1;
-            lo = (u128)(lo - I128_MIN) > m ? lo - (i128)m : I128_MIN;
-            hi = (u128)(I128_MAX - hi) > m ? hi + (i128)m : I128_MAX;
-          }
-          vb = bitlen128((u128)(hi - lo));
-          if (spread && vb < 127) {      // the field holds 2^vb values whatever the range: centre the range in it
-            const u128 spare = (((u128)1 << vb) - 1) - (u128)(hi - lo), down = spare / 2;
-            lo = (u128)(lo - I128_MIN) > down ? lo - (i128)down : I128_MIN;
-            hi = (u128)(I128_MAX - lo) > (((u128)1 << vb) - 1) ? lo + (i128)(((u128)1 << vb) - 1) : I128_MAX;
-          }
-          const i128 base = S.desc[k] ? hi : lo; K.base_lo[k] = (u64)base; K.base_hi[k] = (u64)((u128)base >> 64);
-        }
-        K.vbits[k] = vb;
-        K.null_bit[k] = (fl[k] & 2) ? vb : -1;
-        width[k] = vb + ((fl[k] & 2) ? 1 : 0);
-        total += width[k];
-      }
-      int sh = 0; for (int k = S.n_keys - 1; k >= 0; --k) { K.shift[k] = sh; sh += width[k]; }
-      return total;
-    };
-    auto cost_class = [](int total) { return ((total + 7) / 8) * 4 + (total <= 32 ? 0 : total <= 64 ? 1 : 2); };
     SortPack K{};
-    int total = layout(-1, false, K);
-    if (wstep > 1) {
-      const int cls = cost_class(total);
-      SortPack G{}; int t = layout(6, true, G);
-      if (cost_class(t) != cls) t = layout(12, true, G);
-      if (cost_class(t) != cls) t = layout(-1, true, G);
-      K = G; total = t; K.check = 1;
-    }
+    const int total = sort_key_layout(S, hmm.data(), mb, wstep > 1, K);      // (sort_key_op.h)
     if (total > 128) throw WideSortKey("composite sort key needs " + std::to_string(total) + " bits (max 128)");
     *total_out = total;
     return K;
@@ -1475,7 +1423,11 @@ int gpuq_sort_run(gpuq_op* op, void* stream, const gpuq_input* in, uint32_t* per
       if (string_key) raise_unless(op, s, read_flags(op, s));      // a value beyond 15 bytes: refuse, do not sort by a prefix
       // a client that defers (gpuq_op_set_deferred was called on this operator) will come back with a BOUND instead of a count, and
       // the bound of a handful of groups is easily beyond what one block sorts: learn the key layout now, while reading back is allowed
-      if (op->defer_client) { int total = 0; const SortPack K = sort_key_plan(op, s, P, n, &total); op->learned.so = {true, K, total}; op->learned.expect_flags = 0; }
+      // (a key whose layout cannot be learned -- WideSortKey -- is sorted all the same: the operator then does not defer)
+      if (op->defer_client) {
+        op->learned.so.valid = false;
+        try { int total = 0; const SortPack K = sort_key_plan(op, s, P, n, &total); op->learned.so = {true, K, total}; op->learned.expect_flags = 0; } catch (const WideSortKey&) {}
+      }
       return;
     }
     int total = 0;

@@ -150,7 +150,7 @@ constexpr uint32_t FLAG_AGG_RUNS = 256u;    // the aggregate's input is not clus
 #define GPUQ_REGS_CPARAM const ::gpuq::u64 (&rlo)[::gpuq::NREG], const ::gpuq::u64 (&rhi)[::gpuq::NREG], const uint32_t& rnulls
 #define GPUQ_REGS rlo, rhi, rnulls
 
-__device__ __forceinline__ i128 mk128(u64 lo, u64 hi) { return (i128)(((u128)hi << 64) | (u128)lo); }
+__host__ __device__ __forceinline__ i128 mk128(u64 lo, u64 hi) { return (i128)(((u128)hi << 64) | (u128)lo); }
 
 __host__ __device__ __forceinline__ i64 f64_total_key(u64 bits) {
   // IEEE-754 totalOrder as a signed integer compare [UPSTREAM-KNOWLEDGE: arrow-ord 49 cmp kernels]

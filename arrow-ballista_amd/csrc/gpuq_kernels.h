@@ -300,6 +300,7 @@ struct SortPack {                   // computed on the host from the per-key min
   int32_t shift[MAX_SORT_KEYS];     // bit position of the key's field in the composite
   int32_t null_bit[MAX_SORT_KEYS];  // bit (inside the field) of the null flag, -1 = none
   int32_t rshift[MAX_SORT_KEYS];    // packed Utf8: drop the length byte and the bytes beyond the longest string
+  int32_t len_bits[MAX_SORT_KEYS];  // packed Utf8: 4 when the length goes below the bytes (a value of the column ends in 0x00: sort_key_op.h), else 0
   int32_t vbits[MAX_SORT_KEYS];     // width of the value field (without the null flag)
   int32_t check;                    // 1: the layout was GUESSED from a sample -- the pack kernel verifies every row against it and raises
                                     // hist[SORT_MAX_PASSES * 256] when a value falls outside its field or a NULL meets a key without a null bit

@@ -12,6 +12,7 @@
 // over the declared Decimal128+Date32 widths.  Hash repartition is one such pass with
 // digit = partition id.  All passes stream HBM with coalesced reads; LDS holds the digit counters.
 #include "gpuq_kernels.h"
+#include "sort_key_op.h"
 #ifndef GPUQ_JIT
 #include <cstdlib>
 #endif
@@ -22,31 +23,12 @@ constexpr int SBLOCK = 256;
 constexpr int SWAVES = SBLOCK / 64;
 constexpr int RADIX = 256;
 
-// ordered 128-bit view of a key register: signed integers as is; f64 through the total-order map;
-// packed strings with the top bit flipped so that signed compare == bytewise compare
-__device__ __forceinline__ i128 sort_view(u64 lo, u64 hi, int kind) {
-  if (kind == 1) { const i64 k = f64_total_key(lo); return (i128)k; }
-  if (kind == 2) hi ^= 0x8000000000000000ull;
-  return mk128(lo, hi);
-}
-
-// ------------------------------------------------------------------ min / max per key
-// out per block: [block][key] {min_lo,min_hi,max_lo,max_hi,flags(bit0 any non-null, bit1 any null)}
-struct MinMax { u64 mn_lo, mn_hi, mx_lo, mx_hi; uint32_t fl; };
-__device__ __forceinline__ void mm_init(MinMax& m) { m.mn_lo = ~0ull; m.mn_hi = 0x7FFFFFFFFFFFFFFFull; m.mx_lo = 0; m.mx_hi = 0x8000000000000000ull; m.fl = 0; }
-__device__ __forceinline__ void mm_update(MinMax& m, i128 v) {
-  if (v < mk128(m.mn_lo, m.mn_hi)) { m.mn_lo = (u64)v; m.mn_hi = (u64)((u128)v >> 64); }
-  if (v > mk128(m.mx_lo, m.mx_hi)) { m.mx_lo = (u64)v; m.mx_hi = (u64)((u128)v >> 64); }
-}
+// ------------------------------------------------------------------ min / max per key (sort_key_op.h has the row rule)
+// out per block: [block][key] {min_lo,min_hi,max_lo,max_hi,flags}
 __device__ __forceinline__ void mm_row(MinMax& m, const SortSpec& S, int k, GPUQ_REGS_CPARAM) {
   if (k < S.n_keys) {
     const int r = __builtin_amdgcn_readfirstlane(S.reg[k]);
-    const bool isn = (rnulls >> r) & 1;
-    if (isn) m.fl |= 2u;
-    else {
-      m.fl |= 1u; mm_update(m, sort_view(rlo[r], rhi[r], S.kind[k]));
-      if (S.kind[k] == 2) { const uint32_t len = (uint32_t)(rlo[r] & 0xFF) << 8; if (len > (m.fl & 0xFF00u)) m.fl = (m.fl & ~0xFF00u) | len; }   // longest string, bits 8..15
-    }
+    mm_value(m, rlo[r], rhi[r], (rnulls >> r) & 1, S.kind[k]);
   }
 }
 __device__ __forceinline__ void mm_reduce_store(MinMax& m, int k, u64 (*red)[MAX_SORT_KEYS][5]) {
@@ -55,7 +37,7 @@ __device__ __forceinline__ void mm_reduce_store(MinMax& m, int k, u64 (*red)[MAX
     const i128 omx = mk128(__shfl_xor(m.mx_lo, off), __shfl_xor(m.mx_hi, off));
     if (omn < mk128(m.mn_lo, m.mn_hi)) { m.mn_lo = (u64)omn; m.mn_hi = (u64)((u128)omn >> 64); }
     if (omx > mk128(m.mx_lo, m.mx_hi)) { m.mx_lo = (u64)omx; m.mx_hi = (u64)((u128)omx >> 64); }
-    { const uint32_t of = __shfl_xor(m.fl, off); const uint32_t ml = (of & 0xFF00u) > (m.fl & 0xFF00u) ? (of & 0xFF00u) : (m.fl & 0xFF00u); m.fl = ((m.fl | of) & 0xFFu) | ml; }
+    m.fl = (uint32_t)mm_flags_merge(m.fl, __shfl_xor(m.fl, off));
   }
   if (lane() == 0) { red[wave()][k][0] = m.mn_lo; red[wave()][k][1] = m.mn_hi; red[wave()][k][2] = m.mx_lo; red[wave()][k][3] = m.mx_hi; red[wave()][k][4] = m.fl; }
 }
@@ -85,7 +67,7 @@ __device__ __forceinline__ void k_sort_minmax_body(const DevProgram P, const i64
       const i128 oa = mk128(red[q][k][0], red[q][k][1]), ob = mk128(red[q][k][2], red[q][k][3]);
       if (oa < a) a = oa;
       if (ob > b) b = ob;
-      { const u64 of = red[q][k][4]; const u64 ml = (of & 0xFF00u) > (f & 0xFF00u) ? (of & 0xFF00u) : (f & 0xFF00u); f = ((f | of) & 0xFFu) | ml; }
+      f = mm_flags_merge(f, red[q][k][4]);
     }
     u64* o = out + ((size_t)blockIdx.x * MAX_SORT_KEYS + k) * 5;
     o[0] = (u64)a; o[1] = (u64)((u128)a >> 64); o[2] = (u64)b; o[3] = (u64)((u128)b >> 64); o[4] = f;
@@ -127,20 +109,7 @@ __device__ __forceinline__ void k_sort_pack_body(const DevProgram P, const i64 n
     for (int k = 0; k < MAX_SORT_KEYS; ++k) {
       if (k < S.n_keys && real) {
         const int r = __builtin_amdgcn_readfirstlane(S.reg[k]);
-        const bool isn = (rnulls >> r) & 1;
-        u128 field = 0;
-        if (!isn) {
-          const i128 v = sort_view(rlo[r], rhi[r], S.kind[k]) >> K.rshift[k];   // arithmetic shift keeps the order
-          const i128 base = mk128(K.base_lo[k], K.base_hi[k]);
-          field = S.desc[k] ? (u128)(base - v) : (u128)(v - base);
-          if (K.check && K.vbits[k] < 128 && (field >> K.vbits[k]) != 0) bad = true;      // below the base wraps to a huge field: caught too
-        } else if (K.check && K.null_bit[k] < 0) bad = true;
-        if (K.null_bit[k] >= 0) {
-          // nulls_first: NULL -> 0, value -> 1 in the bit above the value field
-          const u128 flag = (isn != (bool)S.nulls_first[k]) ? 1 : 0;
-          field |= flag << K.null_bit[k];
-        }
-        comp |= field << K.shift[k];
+        comp |= sort_pack_key(rlo[r], rhi[r], (rnulls >> r) & 1, S, K, k, bad);
       }
     }
     if (hist) {
@@ -199,14 +168,9 @@ __device__ __forceinline__ void k_sort_direct_body(const DevProgram P, const int
       for (int k = 0; k < MAX_SORT_KEYS; ++k) {
         if (k < S.n_keys) {
           const int r = __builtin_amdgcn_readfirstlane(S.reg[k]);
-          const bool isn = (rnulls >> r) & 1;
-          u128 u = 0;
-          if (!isn) {
-            u = (u128)sort_view(rlo[r], rhi[r], S.kind[k]) ^ ((u128)1 << 127);     // signed order -> unsigned order
-            if (S.desc[k]) u = ~u;
-          }
+          u128 u;
+          ranks |= sort_direct_key(rlo[r], rhi[r], (rnulls >> r) & 1, S.kind[k], S.desc[k] != 0, S.nulls_first[k] != 0, u) << (2 * k);
           lo[k] = (u64)u; hi[k] = (u64)(u >> 64);
-          ranks |= (isn ? (S.nulls_first[k] ? 0u : 2u) : 1u) << (2 * k);
         }
       }
     }

@@ -746,7 +746,7 @@ static BufP sort_perm(Exec& x, PTable& t, const Json& sort_exprs, const void* si
 // later keys left them, so ties keep that order.  Nothing is paid on the common path: this runs only after the loud failure.
 struct PermOut { const uint32_t* p = nullptr; std::vector<BufP> keep; };
 static PermOut sort_perm_long(Exec& x, const PTable& t, const Json& sort_exprs, const void* site, int tag, const Rung rung = RUNG_LONG_KEYS) {
-  const size_t max_group = rung == RUNG_WIDE ? 1 : 4;      // RUNG_WIDE: a group of four did not fit 128 bits -- one key a pass
+  const size_t max_group = rung == RUNG_WIDE ? 1 : 4;      // RUNG_WIDE: a group of four did not fit 128 bits -- one key a pass (and two for a key that does not fit alone)
   PTable w = t;
   std::vector<Json> groups; Json cur = jarr();
   auto flush = [&]() { if (!cur.a.empty()) { groups.push_back(cur); cur = jarr(); } };
@@ -767,13 +767,30 @@ static PermOut sort_perm_long(Exec& x, const PTable& t, const Json& sort_exprs, 
   }
   flush();
   PermOut out;
-  for (size_t gi = groups.size(); gi-- > 0;) {
-    if (!out.p) { BufP p = sort_perm(x, w, groups[gi], site, tag, nullptr, rung, (int)gi); out.p = (const uint32_t*)p->p; out.keep.push_back(p); continue; }      // (w is exact: see sort_table)
+  // one stable pass: the rows, in the order the later keys left them, by `keys`
+  auto pass = [&](const Json& keys, int pass_id) {
+    if (!out.p) { BufP p = sort_perm(x, w, keys, site, tag, nullptr, rung, pass_id); out.p = (const uint32_t*)p->p; out.keep.push_back(p); return; }      // (w is exact: see sort_table)
     PTable view = select_view(x, w, out.p, w.n, nullptr);
-    BufP p2 = sort_perm(x, view, groups[gi], site, tag, nullptr, rung, (int)gi);
+    BufP p2 = sort_perm(x, view, keys, site, tag, nullptr, rung, pass_id);
     out.keep.push_back(p2);
     for (auto& b : view.keep) out.keep.push_back(b);
     out.p = take_u32(x, out.p, w.n, (const uint32_t*)p2->p, w.n, out.keep);      // rows in the new order = old order read through the pass's permutation
+  };
+  for (size_t gi = groups.size(); gi-- > 0;) {
+    try { pass(groups[gi], (int)gi); continue; }
+    catch (const WideSortKey&) { if (rung != RUNG_WIDE || groups[gi].a.size() != 1) throw; }
+    // One key ALONE beyond 128 bits: a value range of 128 bits (Decimal128(38) from end to end) and NULLs, whose flag is the 129th.  Two
+    // stable passes: the values as a column without validity (a NULL row sorts by whatever its slot holds), then the 1-bit NULL rank,
+    // which moves the NULL rows to their end and keeps the order of the values.
+    const Json& key = groups[gi].a[0];
+    PTable kv = project(x, w, {key.at("expr")}, {"__widekey"}, site, 1000000 + tag * 64 + (int)gi);
+    const gpuq_column& kc = kv.cols[0].c;
+    const std::string name = "__widekey_" + std::to_string(gi);
+    append_column(w, name, kc.type, kc.data, nullptr, nullptr, w.n, false, kc.precision, kc.scale);
+    for (auto& b : kv.keep) w.keep.push_back(b);
+    pass(jarr({sort_key(key, jcol(name, (int)w.cols.size() - 1))}), 2000 + (int)gi);
+    const bool nulls_first = sort_key(key, key.at("expr")).get_bool("nulls_first", false);
+    pass(jarr({jobj({{"expr", jobj({{"is_null_expr", jobj({{"expr", key.at("expr")}})}})}, {"asc", jbool(!nulls_first)}, {"nulls_first", jbool(false)}})}), 1000 + (int)gi);
   }
   for (auto& b : w.keep) out.keep.push_back(b);
   return out;
