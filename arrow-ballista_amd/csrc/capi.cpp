@@ -203,6 +203,7 @@ uint32_t read_flags(gpuq_op* op, hipStream_t s) { return read_status(op, s, 1).f
 void raise_flags(uint32_t f) {
   if (f & FLAG_STR_TRUNC) throw LongString("a Utf8 value longer than 15 bytes reached a device string comparison/key (PACKED15 limit)");
   if (f & FLAG_DEC_OVERFLOW) throw std::runtime_error("decimal arithmetic overflow: a result or a rescaled operand does not fit Decimal128 (38 digits / 127 bits)");
+  if (f & FLAG_TIME_RANGE) throw std::runtime_error("date / timestamp arithmetic out of range: a Date32 or a Timestamp plus or minus an Interval left its type");
   if (f & FLAG_WIDE_MINMAX) throw Unsupported("MIN/MAX over a value outside the int64 range is not supported on device");
   if (f & FLAG_DUP_BUILD_KEY) throw Unsupported("duplicate build keys without a chain buffer");
   if (f & FLAG_OUT_OVERFLOW) throw Capacity("join output capacity exceeded; see the pair count for the required size");
@@ -217,7 +218,13 @@ void raise_flags(uint32_t f) {
 // raise_flags tests FLAG_GROUP_OVERFLOW (what an aggregate tolerates) behind every other bit an aggregate's kernels raise: only
 // FLAG_SORT_LAYOUT and FLAG_AGG_RUNS follow it.
 uint32_t raise_unless(gpuq_op* op, hipStream_t s, uint32_t f, uint32_t tolerated = 0) {
-  if (f & ~tolerated) { reset_flags(op, s); raise_flags(f & ~tolerated); }
+  if (f & ~tolerated) {
+    reset_flags(op, s);
+    // (an error of the run that names the expression, as arrow-arith's does; every other bit speaks for itself)
+    if ((f & ~tolerated & FLAG_TIME_RANGE) && !(f & FLAG_STR_TRUNC) && !op->prog.range_expr.empty())
+      throw std::runtime_error("date / timestamp arithmetic out of range: the result of " + op->prog.range_expr + " does not fit " + (op->prog.range_expr.rfind("Date32", 0) == 0 ? "the int32 days of a Date32" : "the int64 count of a Timestamp"));
+    raise_flags(f & ~tolerated);
+  }
   return f & tolerated;
 }
 
@@ -1845,7 +1852,7 @@ int gpuq_segment_approx_distinct(gpuq_ctx* ctx, void* stream, const gpuq_column*
     DType dt; dt.id = value_col->type; dt.p = value_col->precision; dt.s = value_col->scale;
     HllCol col{value_col->data, value_col->validity, 0, HLL_SINT};
     switch (dt.id) {
-      case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_DATE32: case T_DATE64: case T_TIMESTAMP: case T_DECIMAL128: col.kind = HLL_SINT; break;
+      case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_DATE32: case T_DATE64: case T_TIMESTAMP: case T_DURATION: case T_DECIMAL128: col.kind = HLL_SINT; break;
       case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: col.kind = HLL_UINT; break;
       case T_FLOAT32: col.kind = HLL_F32; break;
       case T_FLOAT64: col.kind = HLL_F64; break;
@@ -1884,7 +1891,7 @@ int gpuq_segment_distinct(gpuq_ctx* ctx, void* stream, const gpuq_column* value_
       case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: c.kind = SEG_UINT; break;
       case T_FLOAT32: c.kind = SEG_F32; bitwise = false; break;
       case T_FLOAT64: c.kind = SEG_F64; bitwise = false; break;
-      case T_DATE32: case T_DATE64: case T_TIMESTAMP: c.kind = SEG_SINT; summable = bitwise = false; break;
+      case T_DATE32: case T_DATE64: case T_TIMESTAMP: case T_DURATION: c.kind = SEG_SINT; summable = bitwise = false; break;
       case T_UTF8:
         if (value_col->repr != GPUQ_REPR_PACKED15) throw Unsupported("gpuq_segment_distinct (COUNT(DISTINCT)): a Utf8 column must be in the fixed-width PACKED15 form");
         c.kind = SEG_UINT; summable = bitwise = false; break;
@@ -1958,7 +1965,7 @@ int gpuq_window_scan(gpuq_ctx* ctx, void* stream, const gpuq_column* value_col, 
     DType dt; dt.id = value_col->type; dt.p = value_col->precision; dt.s = value_col->scale;
     WinCol c{value_col->data, value_col->validity, 0, SEG_SINT};
     switch (dt.id) {
-      case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_DATE32: case T_DATE64: case T_TIMESTAMP: case T_DECIMAL128: c.kind = SEG_SINT; break;
+      case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_DATE32: case T_DATE64: case T_TIMESTAMP: case T_DURATION: case T_DECIMAL128: c.kind = SEG_SINT; break;
       case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: c.kind = SEG_UINT; break;
       case T_FLOAT32: c.kind = SEG_F32; break;
       case T_FLOAT64: c.kind = SEG_F64; break;

@@ -54,9 +54,18 @@ std::string DType::to_string() const {
     case T_INT8: return "Int8"; case T_INT16: return "Int16"; case T_UINT8: return "UInt8"; case T_UINT16: return "UInt16";
     case T_FLOAT32: return "Float32"; case T_DATE64: return "Date64";
     case T_TIMESTAMP: { static const char* u[4] = {"Second", "Millisecond", "Microsecond", "Nanosecond"}; return std::string("Timestamp(") + u[p & 3] + ")"; }
+    case T_DURATION: { static const char* u[4] = {"Second", "Millisecond", "Microsecond", "Nanosecond"}; return std::string("Duration(") + u[p & 3] + ")"; }
+    case T_INTERVAL: { static const char* u[4] = {"YearMonth", "DayTime", "MonthDayNano", "?"}; return std::string("Interval(") + u[p & 3] + ")"; }
     case T_DECIMAL128: return "Decimal128(" + std::to_string(p) + "," + std::to_string(s) + ")";
   }
   return "?";
+}
+static int time_unit_of(const std::string& u, const char* what) {
+  if (u == "Second" || u == "s") return 0;
+  if (u == "Millisecond" || u == "ms") return 1;
+  if (u == "Microsecond" || u == "us") return 2;
+  if (u == "Nanosecond" || u == "ns") return 3;
+  throw std::runtime_error(std::string("bad ") + what + " unit '" + u + "'");
 }
 DType dtype_from_json(const Json& j) {
   DType t;
@@ -82,9 +91,19 @@ DType dtype_from_json(const Json& j) {
     // values compare: it stays with the schema layer
     const Json& a = j.at("Timestamp");
     std::string u = a.is_arr() ? a.a.at(0).str() : a.str();
-    t.id = T_TIMESTAMP;
-    if (u == "Second" || u == "s") t.p = 0; else if (u == "Millisecond" || u == "ms") t.p = 1; else if (u == "Microsecond" || u == "us") t.p = 2;
-    else if (u == "Nanosecond" || u == "ns") t.p = 3; else throw std::runtime_error("bad Timestamp unit '" + u + "'");
+    t.id = T_TIMESTAMP; t.p = time_unit_of(u, "Timestamp");
+    // ... except for `timestamp +- interval`, whose months and days would be local ones: DType::zoned()
+    if (a.is_arr() && a.a.size() > 1 && a.a[1].is_str()) { const std::string& z = a.a[1].s; t.s = (z.empty() || z == "UTC" || z == "+00:00") ? 0 : 1; }
+    return t;
+  }
+  if (j.is_obj() && j.has("Duration")) {      // {"Duration": unit} (datafusion.proto ArrowType.DURATION = TimeUnit)
+    t.id = T_DURATION; t.p = time_unit_of(j.at("Duration").str(), "Duration");
+    return t;
+  }
+  if (j.is_obj() && j.has("Interval")) {      // {"Interval": IntervalUnit} (datafusion.proto:841): the type of a literal only
+    const std::string& u = j.at("Interval").str();
+    t.id = T_INTERVAL;
+    if (u == "YearMonth") t.p = 0; else if (u == "DayTime") t.p = 1; else if (u == "MonthDayNano") t.p = 2; else throw std::runtime_error("bad Interval unit '" + u + "'");
     return t;
   }
   if (j.is_obj() && j.has("Dictionary")) {
@@ -104,6 +123,7 @@ DType dtype_from_arrow_format(const char* f, bool* large) {
   else if (s == "c") t.id = T_INT8; else if (s == "C") t.id = T_UINT8; else if (s == "s") t.id = T_INT16; else if (s == "S") t.id = T_UINT16;
   else if (s == "f") t.id = T_FLOAT32; else if (s == "tdm") t.id = T_DATE64;
   else if (s == "U") { t.id = T_UTF8; if (large) *large = true; else throw Unsupported("LargeUtf8 where 32-bit offsets are required"); }
+  else if (s == "tDs" || s == "tDm" || s == "tDu" || s == "tDn") { t.id = T_DURATION; t.p = s[2] == 's' ? 0 : s[2] == 'm' ? 1 : s[2] == 'u' ? 2 : 3; }
   else if (s.size() >= 4 && s.compare(0, 2, "ts") == 0 && s[3] == ':') {
     t.id = T_TIMESTAMP;
     switch (s[2]) { case 's': t.p = 0; break; case 'm': t.p = 1; break; case 'u': t.p = 2; break; case 'n': t.p = 3; break; default: throw Unsupported("Arrow format '" + s + "'"); }
@@ -112,7 +132,7 @@ DType dtype_from_arrow_format(const char* f, bool* large) {
     int p = 0, sc = 0, bits = 128;
     if (std::sscanf(s.c_str(), "d:%d,%d,%d", &p, &sc, &bits) < 2 || bits != 128) throw Unsupported("decimal format '" + s + "'");
     t.id = T_DECIMAL128; t.p = p; t.s = sc;
-  } else throw Unsupported("Arrow format '" + s + "' is not supported on device (supported: b c C s S i I l L f g tdD tdm ts{s,m,u,n}: d:p,s u U)");
+  } else throw Unsupported("Arrow format '" + s + "' is not supported on device (supported: b c C s S i I l L f g tdD tdm ts{s,m,u,n}: tD{s,m,u,n} d:p,s u U)");
   return t;
 }
 std::string arrow_format_of(const DType& t) {
@@ -121,6 +141,7 @@ std::string arrow_format_of(const DType& t) {
     case T_BOOL: return "b"; case T_UINT32: return "I"; case T_UINT64: return "L";
     case T_INT8: return "c"; case T_UINT8: return "C"; case T_INT16: return "s"; case T_UINT16: return "S"; case T_FLOAT32: return "f"; case T_DATE64: return "tdm";
     case T_TIMESTAMP: return std::string("ts") + "smun"[t.p & 3] + ":";
+    case T_DURATION: return std::string("tD") + "smun"[t.p & 3];
     case T_DECIMAL128: return "d:" + std::to_string(t.p) + "," + std::to_string(t.s);
   }
   throw Unsupported("type has no Arrow format");
@@ -129,7 +150,7 @@ int col_class_for(const DType& t) {
   switch (t.id) {
     case T_INT32: case T_DATE32: return CC_I32;
     case T_UINT32: return CC_U32;
-    case T_INT64: case T_UINT64: case T_FLOAT64: case T_TIMESTAMP: case T_DATE64: return CC_I64;
+    case T_INT64: case T_UINT64: case T_FLOAT64: case T_TIMESTAMP: case T_DATE64: case T_DURATION: return CC_I64;
     case T_INT8: return CC_I8; case T_INT16: return CC_I16; case T_UINT8: return CC_U8; case T_UINT16: return CC_U16; case T_FLOAT32: return CC_F32;
     case T_DECIMAL128: return CC_I128;
     case T_UTF8: return CC_STR;
@@ -149,6 +170,7 @@ Schema schema_from_json(const Json& j) {
   const Json& fs = j.is_obj() ? j.at("fields") : j;
   for (const Json& f : fs.a) {
     Field fd; fd.name = f.at("name").str(); fd.type = dtype_from_json(f.at("type"));
+    if (fd.type.id == T_INTERVAL) throw Unsupported("field '" + fd.name + "' is an " + fd.type.to_string() + ": Interval columns are not carried (an Interval is a literal operand of + and -)");
     fd.nullable = f.get_bool("nullable", true); fd.side = (int)f.get_i64("side", 0); fd.raw128 = (int)f.get_i64("raw128", 0); fd.dense = (int)f.get_i64("dense", 0);
     s.fields.push_back(fd);
   }
@@ -157,7 +179,7 @@ Schema schema_from_json(const Json& j) {
 
 static int type_bits(const DType& t) {
   switch (t.id) {
-    case T_BOOL: return 2; case T_INT32: case T_DATE32: return 32; case T_UINT32: return 33; case T_INT64: case T_TIMESTAMP: case T_DATE64: return 64;
+    case T_BOOL: return 2; case T_INT32: case T_DATE32: return 32; case T_UINT32: return 33; case T_INT64: case T_TIMESTAMP: case T_DATE64: case T_DURATION: return 64;
     case T_INT8: return 8; case T_UINT8: return 9; case T_INT16: return 16; case T_UINT16: return 17;
     case T_UINT64: return 65; case T_DECIMAL128: return bits_for_precision(t.p); default: return 127;
   }
@@ -304,10 +326,83 @@ NodeP ExprCompiler::rescale_time(NodeP e, i64 from_per_s, i64 to_per_s, DType rt
   return raw(OP_DIV, rt, e->nullable, e->bits, {e, lit_int(mk(T_INT64), from_per_s / to_per_s)});
 }
 
+NodeP ExprCompiler::lit_interval(DType t, i64 months, i64 days, i64 nanos) {
+  auto n = std::make_shared<Node>();
+  n->kind = Node::LIT; n->type = t; n->nullable = false;
+  n->lit_hi = ((u64)(uint32_t)(int32_t)months << 32) | (u64)(uint32_t)(int32_t)days; n->lit_lo = (u64)nanos;
+  n->key = "li:" + t.to_string() + ":" + std::to_string(months) + ":" + std::to_string(days) + ":" + std::to_string(nanos);
+  return intern(n);
+}
+// x + iv / x - iv for a Date32 or Timestamp x and an Interval LITERAL iv.  Values follow arrow-arith 49 as DataFusion 34 calls it
+// [UPSTREAM-KNOWLEDGE: the crate is not in the tree; Date32Type / TimestampXType::add_year_months, add_day_time, add_month_day_nano
+// over chrono's NaiveDate / NaiveDateTime]; subtraction negates the three parts.
+//   Date32:     months first (OP_MONTHSHIFT: the day of the month clamped), then the days, then the sub-day part as WHOLE days
+//               truncated toward zero (chrono adds a Duration to a NaiveDate by its num_days())
+//   Timestamp:  the count split by FLOOR division into (day, time of day) -- an instant before 1970 keeps a non-negative time of day --,
+//               the day shifted by the months, the time of day kept, then days of 86,400 s, then the sub-day part exactly; where that
+//               part is not a whole number of the unit the exact instant is floored to it (chrono's timestamp*() accessors floor), and
+//               since everything else is whole units that is the floor of the part alone
+// The exact result is formed in 128 bits and must fit int32 days / the int64 count: arrow-arith raises where it does not, here the run
+// fails with FLAG_TIME_RANGE.  The test is four checked adds of C = 2^127 - 2^(w-1): x + C leaves 127 bits exactly when x >= 2^(w-1),
+// x - C exactly when x < -2^(w-1), and (x + C) - C - C + C is x again.  Years beyond chrono's +-262,143 are computed, not refused.
+NodeP ExprCompiler::interval_arith(bool minus, NodeP x, NodeP iv) {
+  const DType rt = x->type;
+  const std::string what = rt.to_string() + (minus ? " - " : " + ") + iv->type.to_string();
+  if (rt.id == T_DATE64) throw Unsupported(what + " is not built (a Date32 or a Timestamp takes an Interval: the plan casts a Date64 first)");
+  if (rt.id == T_DURATION) throw Unsupported(what + " is not built (an Interval is added to a Date32 or a Timestamp)");
+  if (rt.id != T_DATE32 && rt.id != T_TIMESTAMP) throw Unsupported("unsupported operands for an Interval: " + what);
+  if (rt.zoned()) throw Unsupported(what + ": the field carries a time zone other than UTC, and month / day arithmetic in local time is not built");
+  if (iv->kind != Node::LIT) throw Unsupported(what + ": an Interval is carried as a literal only");
+  if (iv->lit_null || (x->kind == Node::LIT && x->lit_null)) return lit_null(rt);
+  const i128 sign = minus ? -1 : 1;
+  const i128 months = sign * (i128)(int32_t)(iv->lit_hi >> 32), days = sign * (i128)(int32_t)(uint32_t)iv->lit_hi, nanos = sign * (i128)(i64)iv->lit_lo;
+  const DType i64t = mk(T_INT64), widet = dec_type(38, 0);
+  const bool nb = x->nullable;
+  // the months as whole 400-year eras -- 146,097 days each, the calendar repeats: a constant -- and 0 <= r < 4800 months for OP_MONTHSHIFT
+  i128 eras = months / 4800; if (months % 4800 < 0) --eras;
+  const uint32_t r = (uint32_t)(months - eras * 4800);
+  const i128 era_days = eras * 146097;
+  NodeP z;
+  int w;
+  if (rt.id == T_DATE32) {
+    w = 32;
+    NodeP day = r != 0 ? raw(OP_MONTHSHIFT, i64t, nb, 64, {x}, r) : x;
+    z = raw(OP_ADD, rt, nb, 127, {day, lit_int(widet, era_days + days + nanos / (i128)86400000000000ll)});      // (the quotient truncates toward zero)
+  } else {
+    w = 64;
+    const i64 per_day = units_per_second(rt.p) * 86400, ns_per_unit = 1000000000 / units_per_second(rt.p);
+    i128 sub = nanos / ns_per_unit; if (nanos % ns_per_unit < 0) --sub;      // floor
+    NodeP c = lit_int(widet, (era_days + days) * per_day + sub);
+    if (r == 0) z = raw(OP_ADD, rt, nb, 127, {x, c});
+    else {
+      NodeP pd = lit_int(i64t, per_day);
+      NodeP day = floor_div(x, per_day, i64t);
+      NodeP tod = raw(OP_SUB, i64t, nb, 64, {x, raw(OP_MULW, i64t, nb, 64, {day, pd})});      // [0, per_day)
+      NodeP day2 = raw(OP_MONTHSHIFT, i64t, nb, 64, {day}, r);
+      z = raw(OP_ADD, rt, nb, 127, {raw(OP_ADD, rt, nb, 127, {raw(OP_MULW, rt, nb, 127, {day2, pd}), tod}), c});
+    }
+  }
+  if (range_expr_.empty())
+    range_expr_ = what + " (" + std::to_string((long long)(months * sign)) + " months, " + std::to_string((long long)(days * sign)) + " days, " + std::to_string((long long)(nanos * sign)) + " ns)";
+  NodeP C = lit_int(widet, (i128)(((u128)1 << 127) - ((u128)1 << (w - 1))));
+  z = raw(OP_ADDC, rt, nb, 127, {z, C}, 2u);
+  z = raw(OP_SUBC, rt, nb, 127, {z, C}, 2u);
+  z = raw(OP_SUBC, rt, nb, 127, {z, C}, 2u);
+  return raw(OP_ADDC, rt, nb, w, {z, C}, 2u);
+}
+
 NodeP ExprCompiler::cast(NodeP e, DType to) {
   const DType from = e->type;
   if (from == to) return e;
   if (from.id == T_NULL) return lit_null(to);
+  if (from.id == T_INTERVAL || to.id == T_INTERVAL)
+    throw Unsupported("cast " + from.to_string() + " -> " + to.to_string() + " is not built: Interval columns are not carried (an Interval is a literal operand of + and -)");
+  // a Duration is a span, not a point in time: none of the conversions below applies.  To and from Int64 the count is kept; a change of
+  // unit (arrow-cast multiplies / divides) and every other type are refused by name.
+  if (from.id == T_DURATION || to.id == T_DURATION) {
+    if (from.id == T_INT64 || to.id == T_INT64) return raw(OP_MOV, to, e->nullable, e->bits, {e});
+    throw Unsupported("cast " + from.to_string() + " -> " + to.to_string() + " is not built (a Duration casts to and from Int64, its count kept)");
+  }
   // temporal <-> temporal (arrow-cast 49 cast_with_options [UPSTREAM-KNOWLEDGE]: Date32 = days, Date64 = milliseconds, Timestamp = count of its unit)
   if (from.is_temporal() && to.is_temporal()) {
     const i64 day_ms = 86400000;
@@ -378,6 +473,40 @@ NodeP ExprCompiler::binary(const std::string& op_in, NodeP l, NodeP r) {
   // NULL literal operand adopts the other side's type
   if (l->type.id == T_NULL && r->type.id != T_NULL) l = lit_null(r->type);
   if (r->type.id == T_NULL && l->type.id != T_NULL) r = lit_null(l->type);
+  // ---- Interval and Duration: + and - only (the typing table of include/gpuq.h); everything else with one of them is refused by name
+  {
+    const DType &lt = l->type, &rt = r->type;
+    const std::string what = lt.to_string() + " " + op + " " + rt.to_string();
+    const bool li = lt.id == T_INTERVAL, ri = rt.id == T_INTERVAL, ld = lt.id == T_DURATION, rd = rt.id == T_DURATION;
+    const bool lts = lt.id == T_TIMESTAMP, rts = rt.id == T_TIMESTAMP;
+    if (li || ri) {
+      if (is_cmp) throw Unsupported("a comparison with an Interval operand is not built (" + what + ")");
+      if (op != "+" && op != "-") throw Unsupported("'" + op + "' with an Interval operand is not built (" + what + "): an Interval is added to or subtracted from a Date32 or a Timestamp");
+      if (li && ri) throw Unsupported(what + " is not built: Interval columns are not carried, and the plan folds two literals");
+      if (li && op == "-") throw Unsupported(what + " is not built (an Interval is subtracted FROM a Date32 or a Timestamp)");
+      return interval_arith(op == "-", li ? r : l, li ? l : r);
+    }
+    if (ld || rd) {
+      if (is_bitwise || op == "*" || op == "/" || op == "%") throw Unsupported("'" + op + "' with a Duration operand is not built (" + what + ")");
+      if (is_cmp) {
+        if (!(ld && rd)) throw Unsupported("cannot compare " + lt.to_string() + " with " + rt.to_string() + " (a Duration compares with a Duration)");
+        if (lt != rt) throw Unsupported("cannot compare " + lt.to_string() + " with " + rt.to_string() + ": two units -- the plan carries the casts");
+      } else {
+        const DType other = ld ? rt : lt;
+        if (other.id == T_DATE32 || other.id == T_DATE64) throw Unsupported(what + " is not built (a Duration is added to a Timestamp of its unit: the plan casts the date)");
+        if (!((lts || ld) && (rts || rd))) throw Unsupported("unsupported operands for '" + op + "': " + what);
+        if (ld && rts && op == "-") throw Unsupported(what + " is not built (a Duration is subtracted FROM a Timestamp)");
+      }
+    }
+    // Timestamp - Timestamp -> Duration, Timestamp +- Duration -> Timestamp, Duration +- Duration -> Duration: 64-bit wrapping, at this
+    // node [UPSTREAM-KNOWLEDGE: datafusion 34 calls arrow-arith's sub_wrapping / add_wrapping for these]
+    if (is_arith && ((lts && rts && op == "-") || ld || rd)) {
+      if (lt.p != rt.p) throw Unsupported(what + ": two units -- the plan carries the casts");
+      DType zt = lts ? lt : rts ? rt : lt;
+      if (lts && rts) { zt = mk(T_DURATION); zt.p = lt.p; }
+      return wrap_to(raw(op == "+" ? OP_ADD : OP_SUB, zt, nullable, 65, {l, r}), zt, 65, true);
+    }
+  }
   if (is_bitwise) {
     // two integers of ONE type (the planner has inserted the casts): both 128-bit registers hold the value sign- or zero-extended, and
     // & | ^ of two such patterns is such a pattern again -- no wrap, the result is a value of that type
@@ -489,6 +618,7 @@ NodeP ExprCompiler::not_(NodeP e) {
 }
 NodeP ExprCompiler::is_null(NodeP e, bool negate) { return raw(negate ? OP_ISNOTNULL : OP_ISNULL, mk(T_BOOL), false, 2, {e}); }
 NodeP ExprCompiler::negative(NodeP e) {
+  if (e->type.id == T_INTERVAL) throw Unsupported("the negative of an Interval is not built (an Interval is a literal operand of + and -)");
   if (e->type.is_float()) return raw(OP_FNEG, e->type, e->nullable, 127, {e});
   return wrap_to(raw(OP_NEG, e->type, e->nullable, e->bits + 1, {e}), e->type, e->bits + 1, true);      // -(INT_MIN) wraps to INT_MIN
 }
@@ -509,6 +639,20 @@ NodeP ExprCompiler::select(NodeP c, NodeP t, NodeP f) {
 NodeP ExprCompiler::coalesce0(NodeP e) { return raw(OP_COALESCE0, e->type, false, e->bits, {e}); }
 NodeP ExprCompiler::nullif0(NodeP e, NodeP guard) { return raw(OP_NULLIF0, e->type, true, e->bits, {e, guard}); }
 
+// One integer member of an Interval literal's value, within `bits` bits.  Anything else is a malformed descriptor (status 1) that
+// names the member.
+static Json jobj_one(const char* k, const Json& v) { Json j; j.kind = Json::OBJ; j.o.push_back({k, v}); return j; }
+static i64 interval_member(const Json& v, const char* name, int bits, const DType& t) {
+  const std::string where = t.to_string() + " literal: member '" + name + "'";
+  const Json* m = v.is_obj() ? v.find(name) : nullptr;
+  if (!m || m->is_null()) throw std::runtime_error(where + " is missing");
+  if (!(m->is_num() || m->is_str()) || m->s.empty() || m->s.size() > 24) throw std::runtime_error(where + " is not an integer");
+  for (size_t i = 0; i < m->s.size(); ++i) if (!((m->s[i] >= '0' && m->s[i] <= '9') || (i == 0 && m->s[i] == '-' && m->s.size() > 1))) throw std::runtime_error(where + " is not an integer");
+  const i128 x = parse_i128(m->s), lim = (i128)1 << (bits - 1);
+  if (x < -lim || x >= lim) throw std::runtime_error(where + " is out of its " + std::to_string(bits) + " bits");
+  return (i64)x;
+}
+
 NodeP ExprCompiler::from_json(const Json& e) {
   if (!e.is_obj() || e.o.size() != 1) throw std::runtime_error("expression must be an object with one key: " + e.dump());
   const std::string& kind = e.o[0].first;
@@ -527,6 +671,12 @@ NodeP ExprCompiler::from_json(const Json& e) {
     const DType t = dtype_from_json(v.at("type"));
     const Json* val = v.find("value");
     if (!val || val->is_null()) return lit_null(t);
+    if (t.id == T_INTERVAL) {
+      // the three IntervalUnits as (months, days, nanoseconds): a DayTime's milliseconds are exact in nanoseconds (|ms| < 2^31)
+      if (t.p == 0) { Json m = jobj_one("months", *val); return lit_interval(t, interval_member(m, "months", 32, t), 0, 0); }
+      if (t.p == 1) return lit_interval(t, 0, interval_member(*val, "days", 32, t), interval_member(*val, "milliseconds", 32, t) * 1000000);
+      return lit_interval(t, interval_member(*val, "months", 32, t), interval_member(*val, "days", 32, t), interval_member(*val, "nanoseconds", 64, t));
+    }
     switch (t.id) {
       case T_UTF8: return lit_str(val->str());
       case T_FLOAT64: return lit_f64(val->f64());
@@ -729,7 +879,9 @@ void ExprCompiler::add_predicate(NodeP e) {
   if (e->type.id != T_BOOL) throw std::runtime_error("predicate must be boolean, got " + e->type.to_string());
   pred_ = pred_ ? binary("AND", pred_, e) : e;
 }
-int ExprCompiler::add_output(NodeP e) { outs_.push_back(e); return (int)outs_.size() - 1; }
+int ExprCompiler::add_output(NodeP e) {
+  if (e->type.id == T_INTERVAL) throw Unsupported("an expression of type " + e->type.to_string() + ": Interval columns are not carried (an Interval is a literal operand of + and -)");
+  outs_.push_back(e); return (int)outs_.size() - 1; }
 
 CompiledProgram ExprCompiler::finish() {
   CompiledProgram C;
@@ -773,6 +925,7 @@ CompiledProgram ExprCompiler::finish() {
   }
   if (pred_) topo(pred_.get());
   for (auto& o : outs_) topo(o.get());
+  for (Node* n : order) if (n->type.id == T_INTERVAL) throw Unsupported("an Interval value outside + and - over a Date32 or a Timestamp is not built: Interval columns are not carried");
   for (Node* n : order) if (n->kind == Node::COL) {
     if ((int)C.col_field.size() >= MAX_COLS) throw std::runtime_error("expression references more than " + std::to_string(MAX_COLS) + " columns");
     reg[n] = (int)C.col_field.size();
@@ -850,6 +1003,7 @@ CompiledProgram ExprCompiler::finish() {
     C.out_reg.push_back(reg.at(rep(o.get()))); C.out_type.push_back(o->type); C.out_nullable.push_back(o->nullable); C.out_key.push_back(o->key); C.out_bits.push_back((o->type.is_int() || o->type.is_decimal() || o->type.id == T_DATE32) ? o->bits : 127);
   }
   for (Node* n : order) if (n->kind == Node::OPN && (n->op == OP_ADDC || n->op == OP_SUBC || n->op == OP_MULC)) C.checks_overflow = true;
+  C.range_expr = range_expr_;
   C.jit_src = jit_source(C, order, reg);
   return C;
 }
@@ -889,6 +1043,7 @@ CompiledProgram ExprCompiler::prune(const CompiledProgram& C, int n_outs) {
     R.out_key.push_back(C.out_key[(size_t)k]); R.out_bits.push_back(C.out_bits[(size_t)k]);
   }
   for (Node* n : order) if (n->kind == Node::OPN && (n->op == OP_ADDC || n->op == OP_SUBC || n->op == OP_MULC)) R.checks_overflow = true;
+  R.range_expr = C.range_expr;
   R.jit_src = jit_source(R, order, fin_reg_);
   return R;
 }
@@ -1167,6 +1322,7 @@ std::string ExprCompiler::jit_source(const CompiledProgram& C, const std::vector
       }
       case OP_SHL: e = "(i128)((u128)" + as128(a) + " << " + std::to_string(n->imm) + ")"; ne = N(a); break;
       case OP_DATEPART: e = "date_part_of_days((i64)" + V(a) + ", " + std::to_string(n->imm) + ")"; ne = N(a); break;
+      case OP_MONTHSHIFT: e = "month_shift_fwd<i64>((i64)" + V(a) + ", " + std::to_string(n->imm) + "u)"; ne = N(a); break;
       case OP_SUBSTR: {
         L("bool " + t + "_bad = false; const u128 " + t + "_x = substr_packed(((u128)" + V(a) + "_hi << 64) | (u128)" + V(a) + "_lo, " + std::to_string(n->imm & 0xFFu) + "u, " +
           std::to_string((n->imm >> 8) & 0xFFu) + "u, " + t + "_bad);");
@@ -1183,7 +1339,7 @@ std::string ExprCompiler::jit_source(const CompiledProgram& C, const std::vector
       case OP_WRAP: e = "wrap_int((i128)" + V(a) + ", " + std::to_string(n->imm) + "u)"; ne = N(a); break;
       case OP_ADDC: case OP_SUBC: case OP_MULC: {
         L("bool " + t + "_o; const i128 " + t + "_v = checked_arith(" + std::to_string(n->op) + ", " + as128(a) + ", " + as128(b) + ", " + ((n->imm & 1u) ? "true" : "false") + ", " + t + "_o);");
-        L("if (" + t + "_o && !(" + ne + ") && P.flags) atomicOr(P.flags, FLAG_DEC_OVERFLOW);");
+        L("if (" + t + "_o && !(" + ne + ") && P.flags) atomicOr(P.flags, " + ((n->imm & 2u) ? "FLAG_TIME_RANGE" : "FLAG_DEC_OVERFLOW") + ");");
         e = t + "_v"; break;
       }
       case OP_NULLIF0: {

@@ -38,16 +38,25 @@ enum TypeId : int32_t {
   T_INT8 = 10, T_INT16 = 11, T_UINT8 = 12, T_UINT16 = 13, T_FLOAT32 = 14,
   T_TIMESTAMP = 15,   // p = TimeUnit (0 Second, 1 Millisecond, 2 Microsecond, 3 Nanosecond); 8-byte count since the epoch; tz is schema metadata
   T_DATE64 = 16,      // milliseconds since the epoch
+  T_DURATION = 17,    // p = TimeUnit as for a Timestamp; an 8-byte count, a span and not a point in time: laid out and carried like a Timestamp
+  // An Interval exists as a LITERAL only, the right or left operand of + / - over a Date32 or a Timestamp (ExprCompiler::interval_arith):
+  // p = IntervalUnit (0 YearMonth, 1 DayTime, 2 MonthDayNano).  No column, no register and no C ABI type id has this type.
+  T_INTERVAL = 18,
 };
 
 struct DType {
   int32_t id = T_NULL;
   int32_t p = 0, s = 0;
-  bool operator==(const DType& o) const { return id == o.id && (id != T_DECIMAL128 || (p == o.p && s == o.s)) && (id != T_TIMESTAMP || p == o.p); }
+  bool operator==(const DType& o) const { return id == o.id && (id != T_DECIMAL128 || (p == o.p && s == o.s)) && ((id != T_TIMESTAMP && id != T_DURATION && id != T_INTERVAL) || p == o.p); }
   bool operator!=(const DType& o) const { return !(*this == o); }
   bool is_int() const { return id == T_INT32 || id == T_INT64 || id == T_UINT32 || id == T_UINT64 || id == T_INT8 || id == T_INT16 || id == T_UINT8 || id == T_UINT16; }
   bool is_unsigned() const { return id == T_UINT8 || id == T_UINT16 || id == T_UINT32 || id == T_UINT64; }
-  bool is_temporal() const { return id == T_DATE32 || id == T_DATE64 || id == T_TIMESTAMP; }
+  // stored as a signed integer count, ordered as one, wraps as one: the dates, the Timestamp and the Duration
+  bool is_temporal() const { return id == T_DATE32 || id == T_DATE64 || id == T_TIMESTAMP || id == T_DURATION; }
+  bool is_instant() const { return id == T_DATE32 || id == T_DATE64 || id == T_TIMESTAMP; }      // a point in time (what a temporal cast converts between)
+  // a Timestamp field whose declared zone is other than none / "UTC" / "+00:00" carries s = 1: month and day arithmetic in local time
+  // is not built (interval_arith refuses).  Nothing else reads it, and two Timestamp types compare equal by their unit alone.
+  bool zoned() const { return id == T_TIMESTAMP && s != 0; }
   bool is_decimal() const { return id == T_DECIMAL128; }
   bool is_float() const { return id == T_FLOAT64 || id == T_FLOAT32; }
   std::string to_string() const;
@@ -103,7 +112,8 @@ struct CompiledProgram {
   std::vector<bool> out_nullable;
   std::vector<std::string> out_key;
   std::vector<int> out_bits;    // |value| < 2^bits for every output (from the declared types; 127 = unknown)
-  bool checks_overflow = false; // holds a checked decimal instruction (OP_ADDC / OP_SUBC / OP_MULC): a run may raise FLAG_DEC_OVERFLOW
+  bool checks_overflow = false; // holds a checked instruction (OP_ADDC / OP_SUBC / OP_MULC): a run may raise FLAG_DEC_OVERFLOW or FLAG_TIME_RANGE
+  std::string range_expr;       // the first `date / timestamp +- interval` whose range is checked, as text: what a FLAG_TIME_RANGE error names
   std::vector<std::pair<int, int>> param_imm;   // (run-time parameter, the immediate slot it is read from): ExprCompiler::param_f64
   std::string jit_src;          // C++ source of gpuq_jit_eval() for this program (typed, straight-line)
 };
@@ -124,6 +134,8 @@ class ExprCompiler {
   NodeP floor_div(NodeP e, i64 d, DType rt);
   NodeP rescale_time(NodeP e, i64 from_per_s, i64 to_per_s, DType rt);
   NodeP lit_null(DType t);
+  NodeP lit_interval(DType t, i64 months, i64 days, i64 nanos);      // any IntervalUnit, normalised to (months, days, nanoseconds)
+  NodeP interval_arith(bool minus, NodeP x, NodeP iv);               // Date32 / Timestamp x plus or minus the Interval literal iv
   NodeP lit_str(const std::string& s);
   NodeP binary(const std::string& op, NodeP l, NodeP r);
   NodeP cast(NodeP e, DType to);
@@ -154,6 +166,7 @@ class ExprCompiler {
   NodeP pred_;
   std::vector<NodeP> outs_;
   std::map<std::string, NodeP> interned_;
+  std::string range_expr_;                     // interval_arith: the first range-checked expression (CompiledProgram::range_expr)
   std::map<const Node*, int> param_slot_;      // finish(): parameter node -> immediate slot, for jit_source
   std::vector<Node*> fin_order_;               // finish(): the operation list (representatives, operands first), for prune
   std::map<Node*, int> fin_reg_;

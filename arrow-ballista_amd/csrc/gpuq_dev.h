@@ -21,6 +21,7 @@ typedef unsigned short uint16_t;
 typedef signed int int32_t;
 typedef unsigned int uint32_t;
 #endif
+#include "date_shift_op.h"
 
 namespace gpuq {
 
@@ -86,6 +87,7 @@ enum Op : uint8_t {
   // interpreter runs the whole program before it looks at the predicate and raises for rows the predicate drops as well; the generated
   // code returns at the predicate and does not.  The flag can therefore be raised where arrow would not raise, never the other way round.
   OP_ADDC, OP_SUBC, OP_MULC,
+  // imm bit 1: the instruction checks a Date32 / Timestamp result's range (interval_arith) and raises FLAG_TIME_RANGE instead.
   // OP_BOR's siblings (numbered after the checked ops so that no earlier opcode moves): the scalar & and ^ of two integers of one type.
   // Both halves are combined, so two correctly sign- / zero-extended values give a correctly extended result.  NULL if either side is.
   OP_BAND,    // dst <- a & b
@@ -95,6 +97,11 @@ enum Op : uint8_t {
   // (There is no OP_FROUND: a round() case here cost two interpreter kernels an occupancy step -- DESIGN.md, the interpreter's resource
   // table -- so round-half-away is composed from OP_FTRUNC and the integer opcodes over the float's pattern, expr_compile.cpp.)
   OP_FFLOOR, OP_FCEIL, OP_FTRUNC,
+  // Interval arithmetic's one opcode: dst <- the day number a (days since 1970-01-01, a 64-bit value) imm months later, 0 <= imm < 4800,
+  // the day of the month clamped to the target month's length (date_shift_op.h month_shift_fwd).  NULL iff a is.  The whole 400-year
+  // eras of a shift, the days, the sub-day part and the range check of `date / timestamp +- interval` are composed around it
+  // (expr_compile.cpp, interval_arith).
+  OP_MONTHSHIFT,
 };
 
 struct DevInsn { uint8_t op, dst, a, b; uint32_t imm; };
@@ -141,6 +148,7 @@ constexpr uint32_t FLAG_WIDE_MINMAX = 32u;  // MIN/MAX over a value outside the 
 constexpr uint32_t FLAG_DEC_OVERFLOW = 128u;  // a decimal result (or an operand rescaled by a power of ten) left 127 bits / its 38 digits: arrow-arith raises there
 constexpr uint32_t FLAG_SORT_LAYOUT = 64u;  // a row does not fit the composite sort key layout remembered from the previous run (deferred execution)
 constexpr uint32_t FLAG_AGG_RUNS = 256u;    // the aggregate's input is not clustered on its key in increasing order (the "runs" path does not apply)
+constexpr uint32_t FLAG_TIME_RANGE = 512u;  // a Date32 / Timestamp plus or minus an Interval left int32 days / the int64 count: arrow-arith raises there
 
 // Per-lane register file.  lo/hi MUST be separate plain u64 arrays local to the kernel: hipcc then
 // keeps them in VGPRs and lowers wave-uniform dynamic indexing to s_set_gpr_idx_on.  Wrapped in a
@@ -185,16 +193,9 @@ __device__ __forceinline__ void load_str15(const uint8_t* data, int32_t o0, int3
 // Calendar field of a day number (proleptic Gregorian; the days-from-civil inverse) [UPSTREAM-KNOWLEDGE: arrow-arith 49 temporal
 // kernels behind datafusion's date_part]: which = 0 year, 1 month (1-12), 2 day of month (1-31).
 __device__ __forceinline__ i64 date_part_of_days(i64 days, int which) {
-  const i64 z = days + 719468;
-  const i64 era = (z >= 0 ? z : z - 146096) / 146097;
-  const i64 doe = z - era * 146097;                                           // [0, 146096]
-  const i64 yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365;      // [0, 399]
-  const i64 doy = doe - (365 * yoe + yoe / 4 - yoe / 100);                    // [0, 365]
-  const i64 mp = (5 * doy + 2) / 153;                                         // [0, 11]
-  const i64 d = doy - (153 * mp + 2) / 5 + 1;
-  const i64 m = mp < 10 ? mp + 3 : mp - 9;
-  const i64 y = yoe + era * 400 + (m <= 2 ? 1 : 0);
-  return which == 0 ? y : (which == 1 ? m : d);
+  i64 y; unsigned m, d;
+  civil_of_days<i64>(days, y, m, d);
+  return which == 0 ? y : (i64)(which == 1 ? m : d);
 }
 // substr over the packed form (<= 15 bytes big-endian in bits 127..8, true length in bits 7..0): `skip` leading bytes dropped, at most
 // `len` kept (255 = the rest).  Exact whenever skip + kept <= 15 even for a longer value (its first 15 bytes are all there); `bad`
@@ -487,6 +488,7 @@ __device__ __forceinline__ void run_program(const DevProgram& P, GPUQ_REGS_PARAM
         zn = t ? bn : (bool)((rnulls >> e) & 1); break;
       }
       case OP_SHL: { u128 z = (u128)mk128(alo, ahi) << imm; zlo = (u64)z; zhi = (u64)(z >> 64); zn = an; break; }
+      case OP_MONTHSHIFT: { const i64 z = month_shift_fwd<i64>((i64)alo, imm); zlo = (u64)z; zhi = (u64)(z >> 63); zn = an; break; }
       case OP_DATEPART: { const i64 z = date_part_of_days((i64)alo, (int)imm); zlo = (u64)z; zhi = (u64)(z >> 63); zn = an; break; }
       case OP_SUBSTR: { bool bad = false; const u128 z = substr_packed((u128)mk128(alo, ahi), imm & 0xFFu, (imm >> 8) & 0xFFu, bad); zlo = (u64)z; zhi = (u64)(z >> 64); zn = an;
                         if (bad && !an && P.flags) atomicOr(P.flags, FLAG_STR_TRUNC); break; }
@@ -502,7 +504,7 @@ __device__ __forceinline__ void run_program(const DevProgram& P, GPUQ_REGS_PARAM
       case OP_ADDC: case OP_SUBC: case OP_MULC: {
         bool over; const i128 z = checked_arith(op, mk128(alo, ahi), mk128(blo, bhi), (imm & 1u) != 0, over);
         zlo = (u64)z; zhi = (u64)((u128)z >> 64);
-        if (over && !zn && P.flags) atomicOr(P.flags, FLAG_DEC_OVERFLOW); break;
+        if (over && !zn && P.flags) atomicOr(P.flags, (imm & 2u) ? FLAG_TIME_RANGE : FLAG_DEC_OVERFLOW); break;
       }
       default: zn = false; break;
     }

@@ -59,14 +59,7 @@ __global__ void __launch_bounds__(64) k_csv_line_starts(const uint8_t* __restric
 }
 
 // days since 1970-01-01 of a proleptic Gregorian date [UPSTREAM-KNOWLEDGE: chrono / Howard Hinnant's days_from_civil]
-__device__ __forceinline__ int32_t days_from_civil(int y, int m, int d) {
-  y -= m <= 2;
-  const int era = (y >= 0 ? y : y - 399) / 400;
-  const unsigned yoe = (unsigned)(y - era * 400);
-  const unsigned doy = (153u * (unsigned)(m + (m > 2 ? -3 : 9)) + 2u) / 5u + (unsigned)d - 1u;
-  const unsigned doe = yoe * 365u + yoe / 4u - yoe / 100u + doy;
-  return era * 146097 + (int)doe - 719468;
-}
+__device__ __forceinline__ int32_t days_from_civil(int y, int m, int d) { return (int32_t)civil_to_days<int>(y, (unsigned)m, (unsigned)d); }      // (date_shift_op.h)
 
 // 2. one lane per line: walk the line's bytes once, parse the projected fields in place.  Strings only record (start, length);
 //    their bytes are copied after the lengths have been scanned into offsets.

@@ -77,6 +77,7 @@ Json type_json_of(int tid, int p, int s) {
     case T_FLOAT32: return jstr("Float32"); case T_DATE64: return jstr("Date64");
     case T_DECIMAL128: return jobj({{"Decimal128", jarr({jnum(p), jnum(s)})}});
     case T_TIMESTAMP: { static const char* u[4] = {"Second", "Millisecond", "Microsecond", "Nanosecond"}; return jobj({{"Timestamp", jarr({jstr(u[p & 3]), Json()})}}); }
+    case T_DURATION: { static const char* u[4] = {"Second", "Millisecond", "Microsecond", "Nanosecond"}; return jobj({{"Duration", jstr(u[p & 3])}}); }
   }
   throw std::runtime_error("plan: type id " + std::to_string(tid) + " has no name");
 }
@@ -915,6 +916,7 @@ Json type_json_from_string(const std::string& t) {      // DType::to_string(): "
     return jobj({{"Decimal128", jarr({jnum(p), jnum(sc)})}});
   }
   if (t.rfind("Timestamp(", 0) == 0 && t.back() == ')') return jobj({{"Timestamp", jarr({jstr(t.substr(10, t.size() - 11)), Json()})}});      // "Timestamp(Nanosecond)"
+  if (t.rfind("Duration(", 0) == 0 && t.back() == ')') return jobj({{"Duration", jstr(t.substr(9, t.size() - 10))}});      // "Duration(Second)"
   return jstr(t);
 }
 PSchema compiled_outputs(const Json& desc) {
@@ -1055,7 +1057,7 @@ void distinct_check_arg(const std::string& fn, const DType& t) {
   switch (t.id) {
     case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: ok = true; break;
     case T_DECIMAL128: case T_FLOAT32: case T_FLOAT64: ok = fn != "BIT_XOR"; break;
-    case T_DATE32: case T_DATE64: case T_TIMESTAMP: case T_UTF8: ok = fn == "COUNT"; break;
+    case T_DATE32: case T_DATE64: case T_TIMESTAMP: case T_DURATION: case T_UTF8: ok = fn == "COUNT"; break;
     default: break;
   }
   if (!ok) throw Unsupported(fn + "(DISTINCT) over " + t.to_string() + " is not supported (COUNT: integers, dates, timestamps, Decimal128, Float32, Float64, Utf8 up to 15 bytes; "
@@ -1072,7 +1074,7 @@ PField distinct_result_field(const std::string& fn, const Json& arg_type) {
 }
 void approx_distinct_check_arg(const DType& t) {
   switch (t.id) {
-    case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: case T_DATE32: case T_DATE64: case T_TIMESTAMP:
+    case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: case T_DATE32: case T_DATE64: case T_TIMESTAMP: case T_DURATION:
     case T_FLOAT32: case T_FLOAT64: case T_DECIMAL128: case T_UTF8: return;
     default: throw Unsupported("APPROX_DISTINCT over " + t.to_string() + " is not supported (integers, dates, timestamps, Decimal128, Float32, Float64, Utf8 up to 15 bytes)");
   }
@@ -1422,7 +1424,7 @@ struct AggregateExec : PNode {
           if (bi < 0 || find_column(t, br->build_keys[k]) != bi || br->build.cols[(size_t)bi].type.dump() != t.cols[(size_t)ci].type.dump()) return nullptr;
           // integer-like and date keys only: equal means identical there (a float key's 0.0 would stand in for a probe row's -0.0)
           switch (t.cols[(size_t)ci].c.type) {
-            case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: case T_DATE32: case T_DATE64: case T_TIMESTAMP: break;
+            case T_INT8: case T_INT16: case T_INT32: case T_INT64: case T_UINT8: case T_UINT16: case T_UINT32: case T_UINT64: case T_DATE32: case T_DATE64: case T_TIMESTAMP: case T_DURATION: break;
             default: return nullptr;
           }
           got_probe[k] = true;

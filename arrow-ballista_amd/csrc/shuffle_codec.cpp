@@ -173,6 +173,7 @@ std::vector<uint8_t> build_schema_metadata(const gpuq_field_info* fields, int n_
       case GPUQ_FLOAT64: case GPUQ_FLOAT32: type_type = 3; break;
       case GPUQ_DATE64: type_type = 8; break;
       case GPUQ_TIMESTAMP: type_type = 10; break;
+      case GPUQ_DURATION: type_type = 18; break;
       case GPUQ_UTF8: type_type = 5; break;
       case GPUQ_BOOL: type_type = 6; break;
       case GPUQ_DECIMAL128: type_type = 7; break;
@@ -197,6 +198,7 @@ std::vector<uint8_t> build_schema_metadata(const gpuq_field_info* fields, int n_
       case GPUQ_FLOAT32: tt = w.table(1, {{0, 2, 1 /* SINGLE */}}, ta); break;
       case GPUQ_DATE64: tt = w.table(1, {{0, 2, 1 /* DateUnit MILLISECOND */}}, ta); break;
       case GPUQ_TIMESTAMP: tt = w.table(1, {{0, 2, (uint64_t)(f.precision & 3) /* TimeUnit; no timezone: the schema layer owns it */}}, ta); break;
+      case GPUQ_DURATION: tt = w.table(1, {{0, 2, (uint64_t)(f.precision & 3) /* TimeUnit */}}, ta); break;
       case GPUQ_FLOAT64: tt = w.table(1, {{0, 2, 2 /* DOUBLE */}}, ta); break;
       case GPUQ_UTF8: case GPUQ_BOOL: tt = w.table(0, {}, ta); break;
       case GPUQ_DECIMAL128: tt = w.table(3, {{0, 4, (uint64_t)f.precision}, {1, 4, (uint64_t)f.scale}, {2, 4, 128}}, ta); break;
@@ -228,7 +230,7 @@ std::vector<uint8_t> build_schema_metadata(const gpuq_field_info* fields, int n_
 int type_width_of(int type) {
   switch (type) {
     case GPUQ_INT32: case GPUQ_DATE32: case GPUQ_UINT32: case GPUQ_FLOAT32: return 4;
-    case GPUQ_INT64: case GPUQ_FLOAT64: case GPUQ_UINT64: case GPUQ_TIMESTAMP: case GPUQ_DATE64: return 8;
+    case GPUQ_INT64: case GPUQ_FLOAT64: case GPUQ_UINT64: case GPUQ_TIMESTAMP: case GPUQ_DATE64: case GPUQ_DURATION: return 8;
     case GPUQ_INT8: case GPUQ_UINT8: return 1;
     case GPUQ_INT16: case GPUQ_UINT16: return 2;
     case GPUQ_DECIMAL128: return 16;

@@ -18,6 +18,8 @@ def _type_json(t):
         return {"Decimal128": [int(t[1]), int(t[2])]}
     if isinstance(t, (list, tuple)) and t[0] == "Timestamp":      # ("Timestamp", unit[, tz])
         return {"Timestamp": [t[1], t[2] if len(t) > 2 else None]}
+    if isinstance(t, (list, tuple)) and t[0] == "Duration":       # ("Duration", unit)
+        return {"Duration": t[1]}
     return t
 
 
@@ -54,6 +56,27 @@ def lit(value, type=None):
     if t in ("Utf8", "Boolean", "Float64", "Float32"):
         return {"literal": {"type": t, "value": value}}
     return {"literal": {"type": t, "value": str(int(value))}}
+
+
+def interval_year_month(months):
+    """Interval(YearMonth) literal (datafusion.proto interval_yearmonth_value); None = the NULL interval.  An Interval is a literal only:
+    the operand of + / - over a Date32 or a Timestamp."""
+    return {"literal": {"type": {"Interval": "YearMonth"}, "value": None if months is None else str(int(months))}}
+
+
+def interval_day_time(days, milliseconds):
+    """Interval(DayTime) literal (interval_daytime_value): i32 days and i32 milliseconds."""
+    return {"literal": {"type": {"Interval": "DayTime"}, "value": {"days": int(days), "milliseconds": int(milliseconds)}}}
+
+
+def interval_month_day_nano(months, days, nanoseconds):
+    """Interval(MonthDayNano) literal (interval_month_day_nano): i32 months, i32 days, i64 nanoseconds."""
+    return {"literal": {"type": {"Interval": "MonthDayNano"}, "value": {"months": int(months), "days": int(days), "nanoseconds": str(int(nanoseconds))}}}
+
+
+def duration(count, unit):
+    """Duration(unit) literal (duration_*_value): an Int64 count of Second | Millisecond | Microsecond | Nanosecond; None = NULL."""
+    return lit(count, ("Duration", unit))
 
 
 def binary(l, op, r):

@@ -17,6 +17,9 @@ def type_id(t):
         if "Timestamp" in t:
             u = t["Timestamp"][0] if isinstance(t["Timestamp"], (list, tuple)) else t["Timestamp"]
             return B.T_TIMESTAMP, (_TIME_UNITS.index(u) if u in _TIME_UNITS else _PA_UNITS.index(u)), 0
+        if "Duration" in t:
+            u = t["Duration"]
+            return B.T_DURATION, (_TIME_UNITS.index(u) if u in _TIME_UNITS else _PA_UNITS.index(u)), 0
         if "Dictionary" in t:
             return type_id(t["Dictionary"][1])
         return B.T_DECIMAL128, int(t["Decimal128"][0]), int(t["Decimal128"][1])
@@ -30,13 +33,15 @@ def type_json(tid, p=0, s=0):
         return {"Decimal128": [int(p), int(s)]}
     if tid == B.T_TIMESTAMP:
         return {"Timestamp": [_TIME_UNITS[int(p) & 3], None]}
+    if tid == B.T_DURATION:
+        return {"Duration": _TIME_UNITS[int(p) & 3]}
     return _ID_TYPES[tid]
 
 
 def type_width(t):
     tid = type_id(t)[0]
     return {B.T_INT32: 4, B.T_DATE32: 4, B.T_UINT32: 4, B.T_INT64: 8, B.T_UINT64: 8, B.T_FLOAT64: 8, B.T_DECIMAL128: 16, B.T_UTF8: 16,
-            B.T_INT8: 1, B.T_UINT8: 1, B.T_INT16: 2, B.T_UINT16: 2, B.T_FLOAT32: 4, B.T_TIMESTAMP: 8, B.T_DATE64: 8}.get(tid, 0)
+            B.T_INT8: 1, B.T_UINT8: 1, B.T_INT16: 2, B.T_UINT16: 2, B.T_FLOAT32: 4, B.T_TIMESTAMP: 8, B.T_DATE64: 8, B.T_DURATION: 8}.get(tid, 0)
 
 
 def arrow_type_json(t):
@@ -47,6 +52,8 @@ def arrow_type_json(t):
         return {"Decimal128": [t.precision, t.scale]}
     if pa.types.is_timestamp(t):
         return {"Timestamp": [_TIME_UNITS[_PA_UNITS.index(t.unit)], t.tz]}
+    if pa.types.is_duration(t):
+        return {"Duration": _TIME_UNITS[_PA_UNITS.index(t.unit)]}
     if pa.types.is_dictionary(t):
         return arrow_type_json(t.value_type)
     return {pa.int32(): "Int32", pa.int64(): "Int64", pa.date32(): "Date32", pa.float64(): "Float64", pa.string(): "Utf8",
@@ -64,6 +71,8 @@ def json_arrow_type(t):
     if tid == B.T_TIMESTAMP:
         tz = t["Timestamp"][1] if isinstance(t, dict) and isinstance(t.get("Timestamp"), (list, tuple)) and len(t["Timestamp"]) > 1 else None
         return pa.timestamp(_PA_UNITS[p], tz=tz)
+    if tid == B.T_DURATION:
+        return pa.duration(_PA_UNITS[p])
     return {B.T_INT32: pa.int32(), B.T_INT64: pa.int64(), B.T_DATE32: pa.date32(), B.T_FLOAT64: pa.float64(), B.T_UINT32: pa.uint32(),
             B.T_UINT64: pa.uint64(), B.T_UTF8: pa.string(), B.T_BOOL: pa.bool_(), B.T_INT8: pa.int8(), B.T_INT16: pa.int16(),
             B.T_UINT8: pa.uint8(), B.T_UINT16: pa.uint16(), B.T_FLOAT32: pa.float32(), B.T_DATE64: pa.date64()}[tid]

@@ -84,6 +84,8 @@ pub fn type_json(t: &DataType) -> Result<Value> {
         DataType::Date64 => json!("Date64"),
         // the engine keeps the unit; the zone travels in the descriptor and comes back with this plan's schema (batches are built with it)
         DataType::Timestamp(u, tz) => json!({"Timestamp": [format!("{u:?}"), tz.as_ref().map(|z| z.to_string())]}),
+        // a span of its unit: carried like a Timestamp (an Interval is a literal only: no arm here, a field of that type is refused)
+        DataType::Duration(u) => json!({"Duration": format!("{u:?}")}),
         // converted where the batches enter (gpuq_table_import_arrow / gpuq_ingest_push): inside, 32-bit offsets / the value type
         DataType::LargeUtf8 => json!("LargeUtf8"),
         DataType::Dictionary(k, v) => json!({"Dictionary": [type_json(k)?, type_json(v)?]}),
@@ -118,6 +120,21 @@ fn literal(v: &ScalarValue) -> Result<Value> {
         ScalarValue::TimestampMillisecond(x, tz) => json!({"type": {"Timestamp": ["Millisecond", tz.as_ref().map(|z| z.to_string())]}, "value": x.map(|v| v.to_string())}),
         ScalarValue::TimestampMicrosecond(x, tz) => json!({"type": {"Timestamp": ["Microsecond", tz.as_ref().map(|z| z.to_string())]}, "value": x.map(|v| v.to_string())}),
         ScalarValue::TimestampNanosecond(x, tz) => json!({"type": {"Timestamp": ["Nanosecond", tz.as_ref().map(|z| z.to_string())]}, "value": x.map(|v| v.to_string())}),
+        // the three IntervalUnits in their parts (arrow packs DayTime as days << 32 | milliseconds and MonthDayNano as
+        // months << 96 | days << 64 | nanoseconds: to_parts undoes that), the four Durations as their count
+        ScalarValue::IntervalYearMonth(x) => json!({"type": {"Interval": "YearMonth"}, "value": x.map(|v| v.to_string())}),
+        ScalarValue::IntervalDayTime(x) => json!({"type": {"Interval": "DayTime"}, "value": x.map(|v| {
+            let (days, milliseconds) = arrow::datatypes::IntervalDayTimeType::to_parts(v);
+            json!({"days": days, "milliseconds": milliseconds})
+        })}),
+        ScalarValue::IntervalMonthDayNano(x) => json!({"type": {"Interval": "MonthDayNano"}, "value": x.map(|v| {
+            let (months, days, nanoseconds) = arrow::datatypes::IntervalMonthDayNanoType::to_parts(v);
+            json!({"months": months, "days": days, "nanoseconds": nanoseconds.to_string()})
+        })}),
+        ScalarValue::DurationSecond(x) => json!({"type": {"Duration": "Second"}, "value": x.map(|v| v.to_string())}),
+        ScalarValue::DurationMillisecond(x) => json!({"type": {"Duration": "Millisecond"}, "value": x.map(|v| v.to_string())}),
+        ScalarValue::DurationMicrosecond(x) => json!({"type": {"Duration": "Microsecond"}, "value": x.map(|v| v.to_string())}),
+        ScalarValue::DurationNanosecond(x) => json!({"type": {"Duration": "Nanosecond"}, "value": x.map(|v| v.to_string())}),
         ScalarValue::Decimal128(x, p, s) => json!({"type": {"Decimal128": [p, s]}, "value": x.map(|v| v.to_string())}),
         other => return unsupported(format!("literal {other:?}")),
     })

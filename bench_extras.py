@@ -734,6 +734,48 @@ def window(tc, T, g, log2n=28, log2p=20, reps=3):
     return out
 
 
+def temporal(tc, T, g, log2n=27, reps=5):
+    """Interval and Duration arithmetic: a projection of `ts + interval '1' month` and one of `ts - other_ts` over 2^log2n
+    Timestamp(Microsecond) rows (instants of 1950 .. 2050, required columns resident in HBM), through the native plan executor, best of
+    `reps` after one warm-up.  Next to them, in the same process, `cast(cast(ts as Int64) + 1 as Timestamp)`: one column read, one
+    written, one add -- the floor of a one-column projection.  ts - ts reads two columns, so its floor is 1.5 times that."""
+    import numpy as np
+    import pyarrow as pa
+    from arrow_ballista_amd import expr as E
+    from arrow_ballista_amd.expr import Operator as Op
+    from arrow_ballista_amd.expr import binary, cast, col, lit
+    n = 1 << log2n
+    r = np.random.default_rng(11)
+    lo, hi = -631152000 * 10 ** 6, 2524608000 * 10 ** 6      # 1950-01-01 .. 2050-01-01
+    ts = pa.timestamp("us")
+    t = pa.Table.from_arrays([pa.array(r.integers(lo, hi, n)).cast(ts), pa.array(r.integers(lo, hi, n)).cast(ts)],
+                             schema=pa.schema([pa.field("a", ts, nullable=False), pa.field("b", ts, nullable=False)]))
+    head = t.slice(0, 4)
+    src = g.MemoryExec([g.DeviceTable.from_arrow(t, tc.device)])
+    del t
+    s = src.schema()
+
+    def timed(e):
+        plan = g.NativePlan(g.ProjectionExec([(e, "x")], src), tc)
+        res = plan.execute(0); first = res.to_arrow().slice(0, 4)["x"].to_pylist(); del res
+        best = None
+        for _ in range(reps):
+            _sync(tc); t0 = time.perf_counter(); res = plan.execute(0); _sync(tc); dt = time.perf_counter() - t0
+            del res
+            best = dt if best is None or dt < best else best
+        return best * 1e3, [str(x) for x in first]
+    out = {"rows": n, "first_rows": {"a": [str(x) for x in head["a"].to_pylist()], "b": [str(x) for x in head["b"].to_pylist()]}}
+    out["floor_ms"], out["first_rows"]["a+1"] = timed(cast(binary(cast(col("a", s), "Int64"), Op.Plus, lit(1)), ("Timestamp", "Microsecond")))
+    out["month_ms"], out["first_rows"]["a+1month"] = timed(binary(col("a", s), Op.Plus, E.interval_year_month(1)))
+    out["diff_ms"], out["first_rows"]["a-b"] = timed(binary(col("a", s), Op.Minus, col("b", s)))
+    out["month_over_floor"] = out["month_ms"] / out["floor_ms"]
+    out["diff_over_floor"] = out["diff_ms"] / out["floor_ms"]
+    out["floor_GBps"] = n * 16 / out["floor_ms"] / 1e6
+    out["month_GBps"] = n * 16 / out["month_ms"] / 1e6
+    out["diff_GBps"] = n * 24 / out["diff_ms"] / 1e6
+    return out
+
+
 def like_micro(tc, T, g, n=1 << 23, reps=5):
     """LikeExpr throughput (q13's `o_comment NOT LIKE '%special%requests%'` shape): n comment-like strings of 19-78 bytes built
     from a word list, Arrow layout in HBM; one gpuq_like_utf8 launch per pattern.  Bytes = offsets + string bytes read."""
@@ -1161,6 +1203,10 @@ if __name__ == "__main__":
     if "--scan" in sys.argv:
         sf = 10 if "--sf10" in sys.argv else 1
         print(json.dumps(scan_decode(tc, T, g, sf), indent=1))
+        sys.exit(0)
+    if "--temporal" in sys.argv:      # [--log2n 27]
+        bits = int(sys.argv[sys.argv.index("--log2n") + 1]) if "--log2n" in sys.argv else 27
+        print(json.dumps(temporal(tc, T, g, bits)))
         sys.exit(0)
     if "--like" in sys.argv:
         print(json.dumps(like_micro(tc, T, g), indent=1))

@@ -66,7 +66,10 @@ typedef enum gpuq_type {
   /* second wave: Arrow physical layout as well (1 / 2 / 4 / 8 bytes per value); kernels widen on load and narrow on store */
   GPUQ_INT8 = 10, GPUQ_INT16 = 11, GPUQ_UINT8 = 12, GPUQ_UINT16 = 13, GPUQ_FLOAT32 = 14,
   GPUQ_TIMESTAMP = 15, /* int64 count of `precision` = TimeUnit (0 s, 1 ms, 2 us, 3 ns) since the epoch; the time zone is schema metadata */
-  GPUQ_DATE64 = 16     /* int64 milliseconds since the epoch */
+  GPUQ_DATE64 = 16,    /* int64 milliseconds since the epoch */
+  GPUQ_DURATION = 17   /* int64 count of `precision` = TimeUnit, a span and not a point in time; laid out and carried like GPUQ_TIMESTAMP.
+                          JSON {"Duration": "Second" | "Millisecond" | "Microsecond" | "Nanosecond"}, Arrow C data formats tDs tDm tDu tDn.
+                          An Interval has no id: it exists as a literal only (the expression grammar below) */
   /* LargeUtf8 and Dictionary(_, T) columns are converted where they enter: gpuq_table_import_arrow and gpuq_ingest_* narrow the offsets / decode the dictionary while staging; inside, Utf8 has 32-bit offsets */
 } gpuq_type;
 
@@ -280,8 +283,8 @@ const char* gpuq_scan_last_error(void);
 
 /* ---- compiled operators ------------------------------------------------------------------ */
 /* Descriptor JSON (see INTEGRATION.md for the grammar).  Expression nodes mirror PhysicalExprNode
-   (datafusion.proto:1142-1180): column, literal, binary_expr (+ - * / %, the comparisons, AND / OR, and & | ^ over two integers
-   of one type), scalar_function (date_part, substr, coalesce, nullif, nanvl, isnan, iszero, abs, signum, ceil, floor, trunc, round, sqrt:
+   (datafusion.proto:1142-1180): column, literal, binary_expr (+ - * / %, the comparisons, AND / OR, & | ^ over two integers
+   of one type, and + - over dates, timestamps, Intervals and Durations: below), scalar_function (date_part, substr, coalesce, nullif, nanvl, isnan, iszero, abs, signum, ceil, floor, trunc, round, sqrt:
    INTEGRATION.md has the argument types), cast, try_cast, not_expr, is_null_expr,
    is_not_null_expr, negative, in_list, case_ (like_expr is evaluated by gpuq_like_utf8 and lowered to a Boolean column by the plan
    executor).  "op" is one of
@@ -312,7 +315,40 @@ const char* gpuq_scan_last_error(void);
      "sort"        SortExec          {input, expr:[{expr, asc, nulls_first}], fetch?}
      "partition"   BatchPartitioner  {input, hash_expr:[expr], partition_count}
    "input" = {"fields":[{"name","type","nullable","side"}]}; side k>0 means the column is addressed
-   through index vector k of the call (late materialisation after a filter or join). */
+   through index vector k of the call (late materialisation after a filter or join).
+
+   Interval and Duration arithmetic (values as arrow-arith 49 computes them under DataFusion 34).  u is a TimeUnit.
+     Date32       + -  Interval      -> Date32            Interval    +  Date32 / Timestamp(u)  -> the same, commuted
+     Timestamp(u) + -  Interval      -> Timestamp(u)      Timestamp(u) -  Timestamp(u)          -> Duration(u)
+     Timestamp(u) + -  Duration(u)   -> Timestamp(u)      Duration(u)  +  Timestamp(u)          -> Timestamp(u)
+     Duration(u)  + -  Duration(u)   -> Duration(u)       negative Duration(u)                  -> Duration(u)
+   The result is nullable iff an operand is; a NULL Interval literal makes it NULL.  Date32 + - integer -> Date32 and
+   Date32 - Date32 -> Int32 are as before.
+   An Interval is a LITERAL: {"literal": {"type": {"Interval": kind}, "value": v}} with
+     kind "YearMonth"     v = the months (i32) as a string, like the other integer literals
+     kind "DayTime"       v = {"days": i32, "milliseconds": i32}
+     kind "MonthDayNano"  v = {"months": i32, "days": i32, "nanoseconds": i64}
+   A missing member, a non-integer or a value out of its width is GPUQ_ERR_INVALID and names the member.  An Interval as a field's
+   type, a cast's target or an expression's result is refused ("Interval columns are not carried").
+   A Duration is a column type (GPUQ_DURATION) and a literal ({"type": {"Duration": unit}, "value": count}).  It passes as an opaque
+   64-bit integer wherever a Timestamp does: import / export, ingest, projection, filter, comparison with a Duration of its unit,
+   sort / group / join key, COUNT / MIN / MAX.  cast Duration(u) <-> Int64 keeps the count.
+   Values:
+     months     (y, m, d) -> month index y * 12 + (m - 1) + - k -> (y', m'), d' = min(d, days in month (y', m')); proleptic Gregorian
+     Date32     months first, then + - days, then + - the sub-day part as whole days truncated toward zero (a DayTime of
+                -86,399,999 ms leaves a date unchanged)
+     Timestamp  the count is split by floor division into (day, time of day), the day is shifted by the months and the time of day
+                kept, then days of 86,400 s, then the sub-day part exactly; a part that is not a whole number of u floors the
+                exact instant to u (Timestamp(Second) + 1,500 ms adds one second, - 1,500 ms takes two)
+     Timestamp - Timestamp, Timestamp + - Duration, Duration + - Duration: 64-bit wrapping, at the node
+   A Date32 result outside int32 days or a Timestamp result outside int64 is an error of the run (GPUQ_ERR_INVALID, the message names
+   the expression), as a decimal overflow is: never a silent value.  Years beyond chrono's +-262,143, where arrow-arith raises, are
+   computed, not refused.
+   Refused by name (GPUQ_ERR_UNSUPPORTED, GPUQ_REFUSAL_NONE): Date64 + - Interval; Date32 + - Duration; Timestamp + - Interval over a
+   field whose type carries a time zone other than none / "UTC" / "+00:00" (month arithmetic in local time is not built; Duration
+   arithmetic is zone-free and allowed); two Timestamp or Duration operands of different units (the plan carries the casts);
+   Interval op Interval; * / % with an Interval or a Duration; a comparison with an Interval operand; Interval - Date32 / Timestamp;
+   a cast between two Duration units or between a Duration and anything but Int64; SUM / AVG and the moment family over a Duration. */
 int gpuq_op_create(gpuq_ctx* ctx, const char* json, gpuq_op** out);
 /* Host-only: compiles the descriptor without a device and writes a JSON description (program
    listing, output schema; an aggregate also "posts": every program of its result projection, in order, "post" being the first
